@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- decompress throughput of the Sprintz hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, lets the clocks settle (--ramp-ms), warms up, times the K steps and prints the line; --dump-outputs DIR
+also writes what the last step decoded (see dump_outputs).  Everything else below -- the decode checked against the input,
+compress timings, `per_config`, data_sweep, the extras, the CPU baseline, bench_full.json -- runs with --full only.
 
 Headline workload (BASELINE.json configs[1], SURVEY.md 8d "cfg2"): uint16 row-major, 8
 variables, FIRE predictor + bit-pack + RLE (sprintz_*_xff_16b), 10 KB chunks
@@ -74,7 +78,19 @@ def parse():
     p.add_argument("--rccl", action="store_true",
                    help="with --dry-launch: also run the library's own layout gather (comm.cpp, ncclAllGather behind the C-ABI) over the N "
                         "ranks and check what every rank received -- seconds on a multi-GPU box, needs one GPU per rank")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the decode checked against the input, compress timings, the streaming "
+                        "probe, the Huffman / query / latency extras, the CPU baseline, data_sweep, every per_config entry and "
+                        "bench_full.json.  Without it a run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step decoded (rank 0) to DIR as float32 / float64 .npy files: "
+                        "a fixed, seeded sample of whole chunks and the sum of every chunk")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if not args.full and (args.only or args.configs not in ("all", "none")):
+        p.error("--only and --configs name per_config entries, which run only with --full")
+    return args
 
 
 DATA_KINDS = {"walk8": ("walk", 8), "walk300": ("walk", 300), "uniform": ("uniform", 0), "walkflat": ("walkflat", 8)}
@@ -886,9 +902,12 @@ def main():
     def compress_two_launches():             # round 2's path: encode into slots, then size scan + copy
         codec.compress_to_slots(src_padded, x.numel(), ws)
         codec.compact(ws, nchunks, dense, offsets)
-    compress_2l_ms = timer(compress_two_launches, 5)
-    compress_ms = timer(compress_step, 5)
-    compress_ms = max_over_ranks(compress_ms, device)
+    if args.full:
+        compress_2l_ms = timer(compress_two_launches, 5)
+        compress_ms = timer(compress_step, 5)
+        compress_ms = max_over_ranks(compress_ms, device)
+    else:                                    # one write: the input of the timed decode
+        compress_step()
     total_comp = int(offsets[-1].item())
     stream_bytes = int(ws["sizes"].to(torch.int64).sum().item())
     comp = dense[: total_comp + _lib.READ_SLACK].clone()
@@ -897,14 +916,16 @@ def main():
     assert gather.ranks_seen == world and len(layout.rank_bytes) == world and all(b > 0 for b in layout.rank_bytes), \
         f"rank {rank}: the layout exchange saw {gather.ranks_seen} of {world} ranks: {layout.rank_bytes}"
     out = torch.empty(nchunks * chunk_len, dtype=torch.int16, device=device)
-    rets = torch.empty(nchunks, dtype=torch.int64, device=device)
 
     # correctness of what is about to be timed
-    codec.decompress_into(comp, offsets, nchunks, out, rets)
-    torch.cuda.synchronize()
-    if not args.no_verify:
-        assert torch.equal(out, x), "GPU decode != input"
-        assert bool((rets == chunk_len).all().item())
+    if args.full:
+        rets = torch.empty(nchunks, dtype=torch.int64, device=device)
+        codec.decompress_into(comp, offsets, nchunks, out, rets)
+        torch.cuda.synchronize()
+        if not args.no_verify:
+            assert torch.equal(out, x), "GPU decode != input"
+            assert bool((rets == chunk_len).all().item())
+        del rets
 
     # ---------------- untimed: let DVFS settle on this workload (steady-state serving is what is measured)
     t_ramp = time.perf_counter()
@@ -942,6 +963,8 @@ def main():
         wall_ranks = [float(g.item()) for g in got]
     wall = max_over_ranks(wall, device)
     kernel_ms = ev0.elapsed_time(ev1) / args.steps                       # HIP-event average launch duration
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, out, nchunks, rows, ndims, args.dump_outputs)
 
     total_raw = sum_over_ranks(nchunks * chunk_bytes, device)
     total_stream = sum_over_ranks(stream_bytes, device)
@@ -961,13 +984,13 @@ def main():
                    "chunks_per_gpu": nchunks, "chunk_bytes": chunk_bytes, "raw_bytes_per_gpu": nchunks * chunk_bytes,
                    "sharding": f"chunks x{world}, no data-path collective"},
         "ratio": round(total_raw / total_stream, 4),
-        "compress_MBps": round(total_raw / (compress_ms * 1e-3) / 1e6, 1),
-        "compress": {"ms_per_step_max_rank": round(compress_ms, 4),
-                     "what": "sprintz_mi355x_compress_batch_dense: ONE launch, the encoder's workgroups find their place in the container by a chained "
-                             "scan and copy their own chunks into it (csrc/compact_tail.h)" + (" + all-gather of per-rank byte counts" if world > 1 else ""),
-                     "two_launch_ms_this_rank": round(compress_2l_ms, 4), "layout_gather": gather.backend,
-                     "roofline_frac": round((nchunks * chunk_bytes + total_comp + 12 * nchunks) / (compress_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                     "roofline_algorithmic": "raw samples in + dense container out + sizes/offsets, this rank"},
+        **({"compress_MBps": round(total_raw / (compress_ms * 1e-3) / 1e6, 1),
+            "compress": {"ms_per_step_max_rank": round(compress_ms, 4),
+                         "what": "sprintz_mi355x_compress_batch_dense: ONE launch, the encoder's workgroups find their place in the container by a chained "
+                                 "scan and copy their own chunks into it (csrc/compact_tail.h)" + (" + all-gather of per-rank byte counts" if world > 1 else ""),
+                         "two_launch_ms_this_rank": round(compress_2l_ms, 4), "layout_gather": gather.backend,
+                         "roofline_frac": round((nchunks * chunk_bytes + total_comp + 12 * nchunks) / (compress_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                         "roofline_algorithmic": "raw samples in + dense container out + sizes/offsets, this rank"}} if args.full else {}),
         "ms_per_step_ranks": [round(w / args.steps * 1e3, 4) for w in wall_ranks],
         "kernel_ms": round(kernel_ms, 4),
         # `achieved` / `frac`: this rank's algorithmic bytes per launch over the line's own ms_per_step (the wall clock the driver can
@@ -986,44 +1009,45 @@ def main():
         "host": {**host_description(), **numa},
     }
 
-    if rank == 0 and not args.no_extras:
-        sp = streaming_probe()
-        if sp:
-            moved = (traffic or algo_bytes) / (kernel_ms * 1e-3) / 1e9
-            sp["decoder_GBps_of_traffic"] = round(moved, 1)
-            sp["decoder_vs_best_streaming"] = round(moved / sp["GBps_best"], 3)
-            result["roofline"]["streaming_probe"] = sp
-    if not args.no_extras:
-        result.update(headline_extras(cx, codec, x, comp, offsets, ws, out, nchunks, total_comp, chunk_len, ndims, esz, wall / args.steps * 1e3))
+    if args.full:
+        if rank == 0 and not args.no_extras:
+            sp = streaming_probe()
+            if sp:
+                moved = (traffic or algo_bytes) / (kernel_ms * 1e-3) / 1e9
+                sp["decoder_GBps_of_traffic"] = round(moved, 1)
+                sp["decoder_vs_best_streaming"] = round(moved / sp["GBps_best"], 3)
+                result["roofline"]["streaming_probe"] = sp
+        if not args.no_extras:
+            result.update(headline_extras(cx, codec, x, comp, offsets, ws, out, nchunks, total_comp, chunk_len, ndims, esz, wall / args.steps * 1e3))
 
-    if rank == 0 and not args.no_cpu_baseline:
-        ns = min(nchunks, max(64, CPU_SAMPLE_BYTES // chunk_bytes))
-        offs_np = offsets[: ns + 1].cpu().numpy().astype("uint64")
-        comp_np = comp[: int(offs_np[ns]) + 64].cpu().numpy()
-        cx.cpu_jobs.append((result, lambda: cpu_baseline(comp_np, offs_np, ns, 1, esz, chunk_len, args.cpu_seconds, "sprintz_decompress_xff_16b")))
-    del x, comp, out, src_padded
-    codec._ws = {}
-    torch.cuda.empty_cache()
+        if rank == 0 and not args.no_cpu_baseline:
+            ns = min(nchunks, max(64, CPU_SAMPLE_BYTES // chunk_bytes))
+            offs_np = offsets[: ns + 1].cpu().numpy().astype("uint64")
+            comp_np = comp[: int(offs_np[ns]) + 64].cpu().numpy()
+            cx.cpu_jobs.append((result, lambda: cpu_baseline(comp_np, offs_np, ns, 1, esz, chunk_len, args.cpu_seconds, "sprintz_decompress_xff_16b")))
+        del x, comp, out, src_padded
+        codec._ws = {}
+        torch.cuda.empty_cache()
 
-    # ---------------- the headline shape on SURVEY 8d's other generators (G0 uniform, G1 +-300, G2 walk + flat spans)
-    if not args.no_sweep:
-        result["data_sweep"] = data_sweep(cx, codec, nchunks, rows, ndims, chunk_len, esz)
+        # ---------------- the headline shape on SURVEY 8d's other generators (G0 uniform, G1 +-300, G2 walk + flat spans)
+        if not args.no_sweep:
+            result["data_sweep"] = data_sweep(cx, codec, nchunks, rows, ndims, chunk_len, esz)
 
-    # ---------------- every other BASELINE configuration, same process, same clock
-    names = [] if args.configs == "none" else (ALL_CONFIGS if args.configs == "all" else [c for c in args.configs.split(",") if c])
-    per = [{"name": "cfg2", "workload": result["config"]["workload"], "scaling": "weak", "see": "top-level fields of this line"}]
-    for nm in names:
-        try:
-            per.append(merge_over_ranks(cx, run_config(cx, nm)))
-        except Exception as e:      # a failing leg must not cost the headline line
-            if world > 1:
-                raise
-            per.append({"name": nm, "error": f"{type(e).__name__}: {e}"})
-    result["per_config"] = per
-    # ---------------- what ONE GPU takes for one rank's share of the strong-scaled configurations at 2 / 4 / 8 ranks: the prediction a
-    # measured N-GPU run is to be read against (cfg4 at BASELINE's 10 000 chunks is three serial latencies: 8 GPUs cannot buy 8x)
-    if world == 1 and names and not args.no_extras:
-        result["strong_scaling_prediction"] = strong_scaling_prediction(cx, per)
+        # ---------------- every other BASELINE configuration, same process, same clock
+        names = [] if args.configs == "none" else (ALL_CONFIGS if args.configs == "all" else [c for c in args.configs.split(",") if c])
+        per = [{"name": "cfg2", "workload": result["config"]["workload"], "scaling": "weak", "see": "top-level fields of this line"}]
+        for nm in names:
+            try:
+                per.append(merge_over_ranks(cx, run_config(cx, nm)))
+            except Exception as e:      # a failing leg must not cost the headline line
+                if world > 1:
+                    raise
+                per.append({"name": nm, "error": f"{type(e).__name__}: {e}"})
+        result["per_config"] = per
+        # ---------------- what ONE GPU takes for one rank's share of the strong-scaled configurations at 2 / 4 / 8 ranks: the prediction a
+        # measured N-GPU run is to be read against (cfg4 at BASELINE's 10 000 chunks is three serial latencies: 8 GPUs cannot buy 8x)
+        if world == 1 and names and not args.no_extras:
+            result["strong_scaling_prediction"] = strong_scaling_prediction(cx, per)
 
     # ---------------- the last collective is behind us: the ranks part, and ONLY THEN does rank 0 spend its minute of CPU legs
     # (no rank waits inside RCCL while another one times the host)
@@ -1063,7 +1087,13 @@ def compact(obj, depth=0):
 
 def finish_and_emit(result, emit):
     """per_config_summary (LAST key: a reader who keeps only the tail of the line sees every configuration), the full record to
-    bench_full.json + stderr, the compact line to stdout"""
+    bench_full.json + stderr, the compact line to stdout.  A run without --full has no per_config: its line alone, no record file."""
+    result["config"]["multi_gpu_evidence"] = result.get("configs_8gpu_sharding")
+    if result.get("layout_gather_fallback"):
+        result["config"]["layout_gather_fallback"] = result["layout_gather_fallback"]
+    if "per_config" not in result:
+        emit(compact(result))
+        return
     per = result["per_config"]
     summ = {"cfg2": [result["ms_per_step"], result["roofline"]["frac"], result["compress"]["ms_per_step_max_rank"], result["compress"]["roofline_frac"],
                      result.get("cpu_baseline", {}).get("value"), result.get("cpu_baseline", {}).get("value_1thread")]}
@@ -1080,9 +1110,6 @@ def finish_and_emit(result, emit):
     # fractions ride inside `roofline` so that a reader of BENCH_rNN.json's `parsed` alone sees them
     result["roofline"]["per_config_fracs"] = {"fields": "dec_ms, dec_frac, enc_ms, enc_frac (algorithmic bytes / time / 8 TB/s; cfg4: the whole chain)",
                                         **{k: (v[:4] if isinstance(v, list) else v) for k, v in summ.items()}}
-    result["config"]["multi_gpu_evidence"] = result.get("configs_8gpu_sharding")
-    if result.get("layout_gather_fallback"):
-        result["config"]["layout_gather_fallback"] = result["layout_gather_fallback"]
     full_path = os.path.join(ROOT, "bench_full.json")
     result["full_record"] = "bench_full.json next to bench.py (per_config entries, the prose of every field); also on stderr"
     result["per_config_summary"] = result.pop("per_config_summary")          # stays the last key
@@ -1103,6 +1130,35 @@ def finish_and_emit(result, emit):
             line.pop(k)
             line.setdefault("dropped_from_line", []).append(k)
     emit(line)
+
+
+DUMP_SAMPLE_BYTES = 32 << 20      # --dump-outputs: the float32 sample of whole chunks stays below this ...
+DUMP_MAX_SUMS = 1 << 21            # ... and the float64 chunk sums below 16 MB (beyond that many chunks: sums of runs of chunks)
+
+
+def dump_outputs(torch, out, nchunks, rows, ndims, path):
+    """--dump-outputs: what the last timed step decoded (the int16 tensor the caller receives, read as the uint16 samples it holds), as
+    float arrays that two builds can compare file for file:
+      decoded_sample.npy      float32 [chunks, rows, columns]: whole chunks, numbers drawn once by numpy's default_rng(2024) without
+                              replacement and sorted -- the same chunks for the same --nchunks
+      decoded_chunk_sums.npy  float64: the sum of every chunk's samples, in chunk order (more than DUMP_MAX_SUMS chunks: of every run of
+                              ceil(nchunks / DUMP_MAX_SUMS) consecutive chunks)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    per_chunk = rows * ndims
+    u = out.view(nchunks, per_chunk)
+    k = min(nchunks, max(1, DUMP_SAMPLE_BYTES // (per_chunk * 4)))
+    pick = np.sort(np.random.default_rng(2024).choice(nchunks, k, replace=False))
+    sample = u.index_select(0, torch.from_numpy(pick).to(out.device)).to(torch.int32) & 0xFFFF
+    np.save(os.path.join(path, "decoded_sample.npy"), sample.to(torch.float32).view(k, rows, ndims).cpu().numpy())
+    sums = torch.empty(nchunks, dtype=torch.float64, device=out.device)
+    for lo in range(0, nchunks, 8192):
+        sums[lo:lo + 8192] = (u[lo:lo + 8192].to(torch.int32) & 0xFFFF).sum(1, dtype=torch.float64)
+    if nchunks > DUMP_MAX_SUMS:
+        g = -(-nchunks // DUMP_MAX_SUMS)
+        m = -(-nchunks // g)
+        sums = torch.nn.functional.pad(sums, (0, m * g - nchunks)).view(m, g).sum(1)
+    np.save(os.path.join(path, "decoded_chunk_sums.npy"), sums.cpu().numpy())
 
 
 def native_threads_leg(counts=(1, 8, 64)):

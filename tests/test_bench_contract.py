@@ -1,4 +1,4 @@
-"""The record `bench.py` produces, checked on what a default run of the committed build produced on an MI355X
+"""The record `bench.py --full` produces, checked on what such a run of the committed build produced on an MI355X
 (profiles/r<round>_bench_full_*.json = bench_full.json of that run): the driver's contract fields, BASELINE.json's metric, the
 two objects the hot-path tier asks for (`roofline`, `cpu_baseline`), a `per_config` entry for every other BASELINE
 configuration -- and the ONE LINE of it that goes to stdout (bench.compact): short enough for the driver's parser

@@ -90,3 +90,10 @@ def test_host_topology_counts_physical_cores():
     avail, firsts = bench.host_topology()
     assert 1 <= len(firsts) <= len(avail)
     assert set(firsts) <= set(avail) and len(set(firsts)) == len(firsts)
+
+
+def test_per_config_entries_ask_for_full():
+    """per_config runs only with --full: a plain run that names entries is refused before it touches a device"""
+    for argv in (["--only", "cfg1"], ["--configs", "cfg1,cfg5"]):
+        p = run_bench(argv)
+        assert p.returncode == 2 and "--full" in p.stderr, (argv, p.stderr[-2000:])

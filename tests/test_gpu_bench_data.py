@@ -238,7 +238,7 @@ def test_the_line_of_an_8_rank_run_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"BENCH_ONE_DEVICE": "1", "BENCH_BACKEND": "gloo"})
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--nchunks", "8192", "--steps", "5", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--nchunks", "8192", "--steps", "5", "--warmup", "2",
                         "--configs", "cfg4_10000,cfg5", "--no-sweep", "--no-extras", "--cpu-seconds", "0.5", "--config-reps", "5", "--ramp-ms", "20"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -253,3 +253,33 @@ def test_the_line_of_an_8_rank_run_on_one_device():
     summ = d["per_config_summary"]
     assert set(summ) >= {"fields", "cfg2", "cfg4_10000", "cfg5"} and summ["cfg4_10000"] != "error" and summ["cfg5"] != "error"
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+
+
+def test_a_plain_run_times_its_steps_and_dumps_what_it_decoded(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: ONE line with the contract fields and none of
+    the --full legs, `value` following from `ms_per_step`, and the dumped sample and chunk sums equal to the samples the bench
+    generated (the decode is lossless)"""
+    import json
+    import subprocess
+    import torch
+    from synth import synth_torch
+    nchunks = 4096
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nchunks", str(nchunks), "--steps", "7", "--warmup", "2",
+                        "--ramp-ms", "20", "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "MB/s" and d["higher_is_better"] is True and d["dtype"] == "u16" and d["steps"] == 7 and d["warmup"] == 2
+    assert abs(d["value"] - nchunks * 5120 * 2 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
+    for k in ("per_config_summary", "cpu_baseline", "data_sweep", "compress", "huffman"):
+        assert k not in d, k
+    sample = np.load(tmp_path / "decoded_sample.npy")
+    sums = np.load(tmp_path / "decoded_chunk_sums.npy")
+    assert sample.dtype == np.float32 and sums.dtype == np.float64 and sums.shape == (nchunks,)
+    x = synth_torch("walk", 2, nchunks, 640, 8, "cuda:0", seed=123, step=8, chunk0=0).view(torch.int16).to(torch.int32) & 0xFFFF
+    x = x.view(nchunks, 640, 8).cpu().numpy()
+    pick = np.sort(np.random.default_rng(2024).choice(nchunks, sample.shape[0], replace=False))
+    assert sample.shape[1:] == (640, 8) and np.array_equal(sample, x[pick].astype(np.float32))
+    assert np.array_equal(sums, x.reshape(nchunks, -1).sum(1).astype(np.float64))

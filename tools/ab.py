@@ -35,9 +35,9 @@ def main():
                 k, val = kv.split("=", 1)
                 env[k] = val
             if a.cfg == "headline":
-                cmd = [sys.executable, "bench.py", "--configs", "none", "--no-extras", "--no-cpu-baseline", "--steps", str(a.reps)]
+                cmd = [sys.executable, "bench.py", "--full", "--configs", "none", "--no-extras", "--no-cpu-baseline", "--steps", str(a.reps)]
             else:
-                cmd = [sys.executable, "bench.py", "--only", a.cfg, "--no-cpu-baseline", "--config-reps", str(a.reps)]
+                cmd = [sys.executable, "bench.py", "--full", "--only", a.cfg, "--no-cpu-baseline", "--config-reps", str(a.reps)]
             if a.no_verify:
                 cmd.append("--no-verify")
             p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)

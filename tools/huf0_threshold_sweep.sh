@@ -9,7 +9,7 @@ import sys, json, subprocess, os
 n, form = sys.argv[1], sys.argv[2]
 code = f"""
 import sys
-sys.argv = ['bench.py', '--only', 'cfg4_{n}', '--no-cpu-baseline', '--config-reps', '20']
+sys.argv = ['bench.py', '--full', '--only', 'cfg4_{n}', '--no-cpu-baseline', '--config-reps', '20']
 from sprintz_amd import _lib
 _lib.set_option(_lib.OPT_HUF0_BIG_BATCH, {0 if form == 'big' else 10**9})
 import runpy

@@ -1,6 +1,6 @@
 #!/bin/bash
 # durations of, and gaps between, consecutive kernels of a chain:   tools/kgaps.sh <outdir-name> <name-substring,name-substring,...> <command...>
-#   e.g. tools/kgaps.sh kg huf0_tree_wave,huf0_stream_small,decode_fast python /root/repo/bench.py --only cfg4_10000 --no-cpu-baseline --config-reps 20
+#   e.g. tools/kgaps.sh kg huf0_tree_wave,huf0_stream_small,decode_fast python bench.py --full --only cfg4_10000 --no-cpu-baseline --config-reps 20
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/$1; KEYS=$2; shift 2

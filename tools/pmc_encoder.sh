@@ -10,7 +10,7 @@ i=0
 while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
-  (cd /tmp && timeout 200 rocprofv3 --pmc $group --kernel-trace --output-format csv -d $OUT/p$i -o p -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --configs none --no-extras --no-sweep --no-verify > $OUT/p$i.json 2> $OUT/p$i.err < /dev/null)
+  (cd /tmp && timeout 200 rocprofv3 --pmc $group --kernel-trace --output-format csv -d $OUT/p$i -o p -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --configs none --no-extras --no-sweep --no-verify > $OUT/p$i.json 2> $OUT/p$i.err < /dev/null)
 done <<'GROUPS'
 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS
 SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU

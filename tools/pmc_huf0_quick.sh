@@ -5,7 +5,7 @@ ROOT=$PWD
 export TMPDIR=/tmp
 for L in "$@"; do
   OUT=$ROOT/gpurun_out/pmcq_$(basename $L .so); rm -rf $OUT; mkdir -p $OUT
-  (cd /tmp && SPRINTZ_MI355X_LIB=$ROOT/sprintz_amd/$L timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $OUT/p -o p -- python $ROOT/bench.py --only cfg4_${CHUNKS:-800000} --no-cpu-baseline --config-reps 3 --no-verify > $OUT/p.json 2> $OUT/p.err < /dev/null)
+  (cd /tmp && SPRINTZ_MI355X_LIB=$ROOT/sprintz_amd/$L timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $OUT/p -o p -- python $ROOT/bench.py --full --only cfg4_${CHUNKS:-800000} --no-cpu-baseline --config-reps 3 --no-verify > $OUT/p.json 2> $OUT/p.err < /dev/null)
   echo "== $L"; python tools/pmc_report.py $OUT "huf0_stream_kernel<true" | awk '{print $(NF-2), $(NF-1), $NF}'
   python - "$OUT" <<'PY'
 import csv, glob, sys

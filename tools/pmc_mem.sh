@@ -1,6 +1,7 @@
 #!/bin/bash
 # memory-side counters of one bench configuration: tools/pmc_mem.sh <outdir-name> <cfg> <kernel-substr> [lib.so]
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
+ROOT=$PWD
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/$1; CFG=$2; PAT=$3; LIB=$4
 mkdir -p $OUT
@@ -9,7 +10,7 @@ i=0
 while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
-  (cd /tmp && timeout 200 rocprofv3 --pmc $group --kernel-trace --output-format csv -d $OUT/mem_${CFG}_$i -o p -- python $GRAFT_REPO_ROOT/bench.py --only $CFG --no-cpu-baseline --config-reps 3 > /dev/null 2> $OUT/mem_${CFG}_$i.err)
+  (cd /tmp && timeout 200 rocprofv3 --pmc $group --kernel-trace --output-format csv -d $OUT/mem_${CFG}_$i -o p -- python $ROOT/bench.py --full --only $CFG --no-cpu-baseline --config-reps 3 > /dev/null 2> $OUT/mem_${CFG}_$i.err)
 done <<'GROUPS'
 TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TA_FLAT_READ_WAVEFRONTS_sum TA_FLAT_WRITE_WAVEFRONTS_sum TA_BUSY_max
 TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum

@@ -12,8 +12,8 @@ OUT=$ROOT/gpurun_out/$1; shift
 WL=${@:-headline cfg1 cfg3_1k cfg3_10k cfg4_10000 cfg4_80000 cfg4_800000 cfg5}
 mkdir -p $OUT
 for w in $WL; do
-  if [ $w = headline ]; then ARGS="--configs none --no-extras --no-cpu-baseline --steps 20 --warmup 3"; PARGS="--configs none --no-extras --no-cpu-baseline --steps 3 --warmup 1 --ramp-ms 0"
-  else ARGS="--only $w --no-cpu-baseline --config-reps 20"; PARGS="--only $w --no-cpu-baseline --config-reps 3"; fi
+  if [ $w = headline ]; then ARGS="--full --configs none --no-extras --no-cpu-baseline --steps 20 --warmup 3"; PARGS="--full --configs none --no-extras --no-cpu-baseline --steps 3 --warmup 1 --ramp-ms 0"
+  else ARGS="--full --only $w --no-cpu-baseline --config-reps 20"; PARGS="--full --only $w --no-cpu-baseline --config-reps 3"; fi
   mkdir -p $OUT/$w
   (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/$w/trace -o r -- python $ROOT/bench.py $ARGS > $OUT/$w/bench_under_trace.json 2> $OUT/$w/trace.err)
   (cd /tmp && timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/$w/pmc_fetch -o r -- python $ROOT/bench.py $PARGS > /dev/null 2> $OUT/$w/pmc_fetch.err)
