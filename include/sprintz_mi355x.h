@@ -433,6 +433,16 @@ size_t sprintz_mi355x_huf0_tmp_bytes(uint64_t nchunks);
 size_t sprintz_mi355x_huf0_bound(uint64_t total_stream_bytes, uint64_t nchunks);
 int sprintz_mi355x_huf0_compress_batch(const void* d_dense, const uint64_t* d_offsets, const uint32_t* d_sizes, uint64_t nchunks,
                                        void* d_blocks, uint64_t* d_block_offsets, void* d_tmp, void* hip_stream);
+/* The same direction, with one code table per chunk: each block is byte for byte what libzstd 1.4.8's
+ * HUF_compress2(dst, HUF_compressBound(size), chunk, size, 255, table_log) returns -- the bytes the paper's
+ * CPU pipeline writes (a chunk HUF_compress declines is stored verbatim, a chunk of one repeated byte is that
+ * byte, an empty chunk an empty block).  table_log: 0 (= 11, plain HUF_compress) or 5 .. 12.  Specification:
+ * tests/huf0_exact_model.py; kernels in sprintz_amd/csrc/huf0_exact.h.  d_blocks: sprintz_mi355x_huf0_bound(sum
+ * of sizes, nchunks) bytes (a block is never larger than its chunk); d_tmp: sprintz_mi355x_huf0_exact_tmp_bytes(nchunks). */
+size_t sprintz_mi355x_huf0_exact_tmp_bytes(uint64_t nchunks);
+int sprintz_mi355x_huf0_compress_batch_exact(const void* d_dense, const uint64_t* d_offsets, const uint32_t* d_sizes, uint64_t nchunks,
+                                             unsigned table_log /* 0 = 11; 5..12 */, void* d_blocks, uint64_t* d_block_offsets,
+                                             void* d_tmp, void* hip_stream);
 
 /* ------------------------------------------------------------------------
  * Stand-alone transforms.  Replace

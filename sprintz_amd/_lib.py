@@ -95,6 +95,8 @@ huf_compress_batch = _sig("sprintz_mi355x_huf_compress_batch", _i, _vp, _vp, _vp
 huf0_tmp_bytes = _sig("sprintz_mi355x_huf0_tmp_bytes", _sz, _u64)
 huf0_bound = _sig("sprintz_mi355x_huf0_bound", _sz, _u64, _u64)
 huf0_compress_batch = _sig("sprintz_mi355x_huf0_compress_batch", _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
+huf0_exact_tmp_bytes = _sig("sprintz_mi355x_huf0_exact_tmp_bytes", _sz, _u64)
+huf0_compress_batch_exact = _sig("sprintz_mi355x_huf0_compress_batch_exact", _i, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
 huf0_decompress_batch = _sig("sprintz_mi355x_huf0_decompress_batch", _i, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
 huf0_decode_tmp_bytes = _sig("sprintz_mi355x_huf0_decode_tmp_bytes", _sz, _u64)
 huf0_decompress_batch_ws = _sig("sprintz_mi355x_huf0_decompress_batch_ws", _i, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
@@ -172,6 +174,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_huf_compress_batch", "sprintz_mi355x_huf_decompress_batch", "sprintz_mi355x_huf0_decompress_batch",
     "sprintz_mi355x_huf0_decode_tmp_bytes", "sprintz_mi355x_huf0_decompress_batch_ws", "sprintz_mi355x_huf0_decompress_batch_hint",
     "sprintz_mi355x_huf0_tmp_bytes", "sprintz_mi355x_huf0_bound", "sprintz_mi355x_huf0_compress_batch",
+    "sprintz_mi355x_huf0_exact_tmp_bytes", "sprintz_mi355x_huf0_compress_batch_exact",
     "sprintz_mi355x_query_batch", "sprintz_mi355x_query_reduce",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",

@@ -548,6 +548,24 @@ def huf0_compress(batch):
     return blocks, boffs
 
 
+def huf0_compress_exact(batch, table_log=11):
+    """CompressedBatch -> (blocks uint8 tensor, block_offsets int64 [nchunks+1]) like huf0_compress, but every chunk
+    has its own code table and its block is byte for byte libzstd 1.4.8's HUF_compress2(..., 255, table_log) of it
+    (table_log 11 = HUF_compress; 5 .. 12).  Specification: tests/huf0_exact_model.py."""
+    import torch
+    dev = batch.data.device
+    n = batch.nchunks
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    total = int(batch.sizes.sum().item())
+    blocks = torch.zeros(int(_lib.huf0_bound(total, n)), dtype=torch.uint8, device=dev)
+    boffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    tmp = torch.empty(int(_lib.huf0_exact_tmp_bytes(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.huf0_compress_batch_exact(batch.data.data_ptr(), batch.offsets.data_ptr(), batch.sizes.data_ptr(), n,
+                                                  int(table_log), blocks.data_ptr(), boffs.data_ptr(), tmp.data_ptr(), stream))
+    return blocks, boffs
+
+
 def huf0_decompress(blocks, block_offsets, out_offsets, rets=None, out=None, max_block_bytes=0):
     """Genuine Huff0 blocks (HUF_compress's output, one per chunk; torch uint8 tensor + int64 offsets
     [nchunks+1]) -> the bytes they encode, chunk c at out_offsets[c] (int64 [nchunks+1], device).

@@ -857,6 +857,7 @@ __global__ void __launch_bounds__(256) huf_decode_kernel(const uint8_t* huf, con
 thread_local std::string g_huf_error;
 
 #include "huf0_write.h"
+#include "huf0_exact.h"
 
 }  // namespace
 
@@ -934,6 +935,35 @@ int sprintz_mi355x_huf0_compress_batch(const void* d_dense, const uint64_t* d_of
     if (launch_size_scan(bsizes, nchunks, 1, d_block_offsets, scan_tmp, st) != hipSuccess) return sprintz::set_error(SPRINTZ_E_HIP, "Huffman stage: a HIP call or kernel launch failed");
     hipLaunchKernelGGL(huf0_encode_kernel, dim3((unsigned)nseg), dim3(256), 0, st, (const uint8_t*)d_dense, d_offsets, d_sizes, nchunks,
                        (const uint8_t*)recs, (const uint64_t*)meta, (uint8_t*)d_blocks, (const uint64_t*)d_block_offsets);
+    return hipGetLastError() == hipSuccess ? 0 : sprintz::set_error(SPRINTZ_E_HIP, "Huffman stage: a HIP call or kernel launch failed");
+}
+
+// ---- exact Huff0 writer (huf0_exact.h).  tmp: chunk records | block sizes | meta | scan scratch
+size_t sprintz_mi355x_huf0_exact_tmp_bytes(uint64_t nchunks)
+{
+    return (size_t)(nchunks * kXRecBytes + ((nchunks * 4 + 15) & ~(uint64_t)15) + nchunks * 8 + sprintz_mi355x_compact_tmp_bytes(nchunks) + 64);
+}
+
+int sprintz_mi355x_huf0_compress_batch_exact(const void* d_dense, const uint64_t* d_offsets, const uint32_t* d_sizes, uint64_t nchunks,
+                                             unsigned table_log, void* d_blocks, uint64_t* d_block_offsets, void* d_tmp, void* hip_stream)
+{
+    if (!d_dense || !d_offsets || !d_sizes || !d_blocks || !d_block_offsets || !d_tmp) return sprintz::set_error(SPRINTZ_E_INVALID, "Huffman stage: invalid argument (null pointer, alignment or size)");
+    if (table_log == 0) table_log = 11;
+    if (table_log < 5 || table_log > 12) return sprintz::set_error(SPRINTZ_E_INVALID, "Huffman stage: table_log must be 0 (= 11) or 5 .. 12");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sprintz::set_error(SPRINTZ_E_NO_DEVICE, "Huffman stage: no usable HIP device (there is no CPU fallback)");
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (nchunks == 0) return hipMemsetAsync(d_block_offsets, 0, 8, st) == hipSuccess ? 0 : sprintz::set_error(SPRINTZ_E_HIP, "Huffman stage: a HIP call or kernel launch failed");
+    if (nchunks > 0xffffffffull) return sprintz::set_error(SPRINTZ_E_INVALID, "Huffman stage: invalid argument (null pointer, alignment or size)");
+    uint8_t* recs = (uint8_t*)d_tmp;
+    uint32_t* bsizes = (uint32_t*)(recs + nchunks * kXRecBytes);
+    uint64_t* meta = (uint64_t*)((uint8_t*)bsizes + ((nchunks * 4 + 15) & ~(uint64_t)15));
+    void* scan_tmp = (uint8_t*)meta + nchunks * 8;
+    hipLaunchKernelGGL(huf0x_table_kernel, dim3((unsigned)nchunks), dim3(64), 0, st, (const uint8_t*)d_dense, d_offsets, d_sizes, (uint32_t)table_log,
+                       recs, bsizes, meta);
+    if (launch_size_scan(bsizes, nchunks, 1, d_block_offsets, scan_tmp, st) != hipSuccess) return sprintz::set_error(SPRINTZ_E_HIP, "Huffman stage: a HIP call or kernel launch failed");
+    hipLaunchKernelGGL(huf0x_encode_kernel, dim3((unsigned)((nchunks + kXChunksPerWave - 1) / kXChunksPerWave)), dim3(64), 0, st, (const uint8_t*)d_dense,
+                       d_offsets, d_sizes, nchunks, (const uint8_t*)recs, (const uint64_t*)meta, (uint8_t*)d_blocks, (const uint64_t*)d_block_offsets);
     return hipGetLastError() == hipSuccess ? 0 : sprintz::set_error(SPRINTZ_E_HIP, "Huffman stage: a HIP call or kernel launch failed");
 }
 
