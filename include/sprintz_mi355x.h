@@ -48,7 +48,8 @@ extern "C" {
  *   4  round 3: compress_batch_colmajor_dense, SPRINTZ_OPT_SPLIT_LANES, SPRINTZ_OPT_ENC_PAIR
  *   5  round 4: SPRINTZ_OPT_HOST_WAIT, SPRINTZ_OPT_LAT_CHUNKS, SPRINTZ_OPT_HOST_STREAMS, SPRINTZ_OPT_REF_DECODER_QUIRK (the single-call entry points work on a mapped staging buffer: one wait per call)
  *   6  round 5: huf0_decompress_batch_hint, SPRINTZ_OPT_HUF0_SYNC_CHUNKS, SPRINTZ_MI355X_MAX_NDIMS 65535
- *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len */
+ *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
+ *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -372,6 +373,35 @@ int sprintz_mi355x_query_batch(int codec, int elem_bytes, const void* d_comp, co
                                uint64_t* d_partials, int64_t* d_rets, void* hip_stream);
 int sprintz_mi355x_query_reduce(int op, const uint64_t* d_partials, uint64_t nchunks, uint16_t ndims, uint64_t* d_result,
                                 void* hip_stream);
+
+/* Windowed query: per-window min / max / sum of every column, fused into the decode, nothing else leaving the chip.
+ * The paper stores series in small segments so that queries over arbitrary time intervals are cheap
+ * (communicate/intro.tex:55) and plans "sliding mean on 8b data" and "max on 16b data" (communicate/results.tex:265-272);
+ * the ops are those of QueryParams (cpp/Compress/query.hpp:23-29) plus the minimum, per window instead of per chunk.
+ *
+ * The batch is given exactly as to sprintz_mi355x_query_batch (codec, elem_bytes, container, offsets, nchunks, chunk_len,
+ * ndims, flags: SPRINTZ_QUERY_GENERAL_LAYOUT).  With D = ndims, R = ceil(chunk_len / D) rows a chunk slot,
+ * W = window_rows (a multiple of 8, at least 8) and nwin = ceil(R / W): element e of chunk c (0 <= e < the element count its
+ * stream header gives) is in column e % D and window (e / D) / W -- windows are relative to the chunk.  For chunk c,
+ * window w and column d the call writes, at index (c*nwin + w)*D + d,
+ *   d_min: the unsigned minimum, element type (uint8 / uint16)      (ops & SPRINTZ_QUERY_WIN_MIN)
+ *   d_max: the unsigned maximum, element type                      (ops & SPRINTZ_QUERY_WIN_MAX)
+ *   d_sum: the sum, uint64                                         (ops & SPRINTZ_QUERY_WIN_SUM)
+ * over the samples sprintz_mi355x_decompress_batch would write under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK
+ * included; the verbatim tail and a partial last row count).  A window without elements -- in a short last chunk, or in
+ * any chunk whose stream holds fewer rows than its slot -- holds the identities: min 0xFF / 0xFFFF, max 0, sum 0.  Every
+ * one of the nchunks*nwin*D entries of each selected output is written; an output not selected may be NULL.
+ * d_rets (optional) as in decompress_batch: elements decoded, or < 0 for a damaged chunk, whose entries are then
+ * unspecified -- nothing is written outside them, and every other chunk's are exact.
+ * Returns SPRINTZ_E_INVALID for a window_rows that is not a multiple of 8 >= 8, ops outside 1..7, a selected output that
+ * is NULL, a selected d_min / d_max not aligned to the element size or d_sum not to 8 bytes, an unknown flag; SPRINTZ_E_UNSUPPORTED
+ * for more than 512 columns -- all before the device is touched. */
+#define SPRINTZ_QUERY_WIN_MIN 1u
+#define SPRINTZ_QUERY_WIN_MAX 2u
+#define SPRINTZ_QUERY_WIN_SUM 4u
+int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                 uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
+                                 void* d_min, void* d_max, uint64_t* d_sum, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -302,6 +302,99 @@ class ChunkedCodec:
                 _lib.check(_lib.query_reduce(opid, partials.data_ptr(), n, self.ndims, res.data_ptr(), self._stream()))
         return res, (out[: batch.total_len] if materialize else None)
 
+    def query_windows(self, batch, window_rows, ops=("min", "max", "sum"), general_layout=False, per_chunk=False, check=True):
+        """Per-window min / max / sum of every column, fused into the decode (nothing but the results leaves the chip).
+
+        per_chunk=True: the kernel's chunk-relative windows as they are, {op: [nchunks, nwin, ndims]} with
+        nwin = ceil(ceil(chunk_len / ndims) / window_rows); window_rows a multiple of 8.
+        Default: windows over the batch's rows -- window w covers rows [w*W, min((w+1)*W, rows)), rows =
+        ceil(total_len / ndims) -- as {op: [nwindows, ndims]}.  That needs chunk_len % ndims == 0 and R = chunk_len / ndims
+        either a multiple of W or a divisor of it (then the kernel takes one window a chunk and W / R chunks fold here).
+        ops: any of "min", "max" (codec dtype), "sum" (int64) and, global windows only, "count" (int64) and "mean" (float64).
+        Empty windows hold the identities (min all ones, max 0, sum 0).  check=True raises SprintzError naming the first
+        damaged chunk."""
+        torch = self.torch
+        ops = (ops,) if isinstance(ops, str) else tuple(ops)
+        unknown = set(ops) - {"min", "max", "sum", "count", "mean"}
+        if unknown or not ops:
+            raise ValueError(f"ops must be a non-empty subset of min / max / sum / count / mean, not {ops}")
+        if per_chunk and set(ops) & {"count", "mean"}:
+            raise ValueError("count and mean exist for global windows only (per_chunk=False)")
+        W, D, n = int(window_rows), self.ndims, batch.nchunks
+        R = -(-self.chunk_len // D)
+        if per_chunk:
+            kw = W
+        else:
+            if W < 1:
+                raise ValueError("window_rows must be positive")
+            if self.chunk_len % D:
+                raise ValueError(f"global windows need chunk_len % ndims == 0 ({self.chunk_len} % {D}): use per_chunk=True")
+            if R % W == 0:
+                kw = W
+            elif W % R == 0:
+                kw = -(-R // 8) * 8                         # one window a chunk (any multiple of 8 >= R), folded below
+            else:
+                raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: "
+                                 "use per_chunk=True")
+        nwin = -(-R // kw) if kw > 0 else 0
+        bits = (_lib.QUERY_WIN_MIN if "min" in ops else 0) | (_lib.QUERY_WIN_MAX if "max" in ops else 0) | \
+               (_lib.QUERY_WIN_SUM if set(ops) & {"sum", "mean"} else 0)
+        if bits == 0:                                       # count alone: no decode needed
+            bits = _lib.QUERY_WIN_SUM
+        shape = (n, nwin, D)
+        res = {}
+        if bits & _lib.QUERY_WIN_MIN:
+            res["min"] = torch.empty(shape, dtype=self.dtype, device=self.device)
+        if bits & _lib.QUERY_WIN_MAX:
+            res["max"] = torch.empty(shape, dtype=self.dtype, device=self.device)
+        if bits & _lib.QUERY_WIN_SUM:
+            res["sum"] = torch.empty(shape, dtype=torch.int64, device=self.device)
+        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        with self._on():
+            _lib.check(_lib.query_windows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                          self.chunk_len, D, kw, bits,
+                                          _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                          res["min"].data_ptr() if "min" in res else None,
+                                          res["max"].data_ptr() if "max" in res else None,
+                                          res["sum"].data_ptr() if "sum" in res else None,
+                                          rets.data_ptr() if rets is not None else None, self._stream()))
+        if check and n:
+            bad = (rets < 0).nonzero()
+            if bad.numel():
+                c = int(bad[0, 0].item())
+                raise _lib.SprintzError(int(rets[c].item()), f"query_windows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if per_chunk:
+            return {k: v for k, v in res.items() if k in ops}
+        rows = -(-batch.total_len // D)
+        nw = -(-rows // W)
+        if R % W == 0:                                      # chunk windows are global windows: chunk c holds rows [c R, (c+1) R)
+            out = {k: v.reshape(n * nwin, D)[:nw] for k, v in res.items()}
+        else:                                               # f = W / R consecutive chunks a window (int32: torch's uint16 lacks most reductions)
+            f = W // R
+            pad = nw * f - n
+            out = {}
+            for k, v in res.items():
+                v = v.reshape(n, D)
+                if k == "sum":
+                    out[k] = torch.cat([v, v.new_zeros((pad, D))]).reshape(nw, f, D).sum(dim=1)
+                else:
+                    ident = (1 << (8 * self.esz)) - 1 if k == "min" else 0
+                    v32 = torch.cat([v.to(torch.int32), torch.full((pad, D), ident, dtype=torch.int32, device=self.device)])
+                    v32 = v32.reshape(nw, f, D)
+                    out[k] = (v32.amin(dim=1) if k == "min" else v32.amax(dim=1)).to(self.dtype)
+        if set(ops) & {"count", "mean"}:
+            # column d of window w: the full rows of the window, plus the partial last row where it reaches column d
+            full, part = divmod(batch.total_len, D)
+            w0 = torch.arange(nw, dtype=torch.int64, device=self.device) * W
+            cnt = (torch.clamp(torch.clamp(w0 + W, max=full) - w0, min=0))[:, None].expand(nw, D).clone()
+            if part:
+                wl = full // W
+                cnt[wl, :part] += 1
+            out["count"] = cnt
+            if "mean" in ops:
+                out["mean"] = out["sum"].to(torch.float64) / cnt.to(torch.float64)
+        return {k: v for k, v in out.items() if k in ops}
+
 
 # ---- query on compressed data, single call (the reference's names) -----------------------
 

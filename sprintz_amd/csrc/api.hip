@@ -388,9 +388,14 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff / kQueryMaterialize / kQueryReduceOnly
+    int q = kQueryOff;          // kQueryOff / kQueryMaterialize / kQueryReduceOnly / kQueryWindow
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
+    // kQueryWindow: window_rows, windows per chunk slot, SPRINTZ_QUERY_WIN_* ops, [nchunks][win_count][ndims] outputs
+    uint32_t window_rows = 0, win_count = 0, win_ops = 0;
+    void* win_min = nullptr;
+    void* win_max = nullptr;
+    uint64_t* win_sum = nullptr;
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -458,6 +463,12 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
     a.chunks_per_group = 1;
     a.qop = qs.qop;
     a.qres = qs.qres;
+    a.window_rows = qs.window_rows;
+    a.win_count = qs.win_count;
+    a.win_ops = qs.win_ops;
+    a.win_min = qs.win_min;
+    a.win_max = qs.win_max;
+    a.win_sum = qs.win_sum;
     a.norle = norle ? (codec == SPRINTZ_CODEC_XFF_NORLE ? 2 : 1) : 0;
     a.raw = codec == SPRINTZ_CODEC_BITPACK_NORLE ? 1 : 0;
     a.col_stride = qs.col_stride;
@@ -504,7 +515,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
     const size_t groups_per_block = kThreads / DP;
     size_t shmem = 0;
     a.vec_store = 0;
-    if (!cs && blk_bytes % 16 == 0 && (qs.q == kQueryReduceOnly || ((uintptr_t)d_out % 16) == 0) && ((uint64_t)chunk_len * esz) % 16 == 0 &&
+    if (!cs && blk_bytes % 16 == 0 && (query_reduce_only(qs.q) || ((uintptr_t)d_out % 16) == 0) && ((uint64_t)chunk_len * esz) % 16 == 0 &&
         stride * groups_per_block <= 64 * 1024) {
         a.vec_store = 1;
         a.lds_group_stride = (uint32_t)stride;
@@ -1824,6 +1835,38 @@ int sprintz_mi355x_query_batch(int codec, int elem_bytes, const void* d_comp, co
     qs.qres = op ? d_partials : nullptr;
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
     return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
+                         0, 0, 0, qs);
+}
+
+int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                 uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
+                                 void* d_min, void* d_max, uint64_t* d_sum, int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if (window_rows < 8 || window_rows % 8) return fail(SPRINTZ_E_INVALID, "window_rows must be a multiple of 8, at least 8");
+    if (ops < 1 || ops > 7) return fail(SPRINTZ_E_INVALID, "ops must be a non-empty OR of SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM");
+    if (((ops & SPRINTZ_QUERY_WIN_MIN) && !d_min) || ((ops & SPRINTZ_QUERY_WIN_MAX) && !d_max) || ((ops & SPRINTZ_QUERY_WIN_SUM) && !d_sum))
+        return fail(SPRINTZ_E_INVALID, "a selected op without its output buffer");
+    if (((ops & SPRINTZ_QUERY_WIN_MIN) && (uintptr_t)d_min % (uintptr_t)elem_bytes) || ((ops & SPRINTZ_QUERY_WIN_MAX) && (uintptr_t)d_max % (uintptr_t)elem_bytes) ||
+        ((ops & SPRINTZ_QUERY_WIN_SUM) && (uintptr_t)d_sum % 8))
+        return fail(SPRINTZ_E_INVALID, "min / max must be aligned to the element size, sum to 8 bytes");
+    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
+    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no query");
+    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if (!d_comp || !d_offsets) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if ((rc = ensure_device())) return rc;
+    const uint32_t rows = (chunk_len + ndims - 1) / ndims;
+    QuerySpec qs;
+    qs.q = kQueryWindow;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.window_rows = window_rows;
+    qs.win_count = (rows + window_rows - 1) / window_rows;
+    qs.win_ops = ops;
+    qs.win_min = (ops & SPRINTZ_QUERY_WIN_MIN) ? d_min : nullptr;
+    qs.win_max = (ops & SPRINTZ_QUERY_WIN_MAX) ? d_max : nullptr;
+    qs.win_sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
+    return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                          0, 0, 0, qs);
 }
 

@@ -288,16 +288,28 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t qbs[CPL];
 #pragma unroll
     for (int k = 0; k < CPL; k++) { qmax[k] = 0; qsum[k] = 0; qbs[k] = 0; }
+    // windowed query (Q == kQueryWindow): the minimum too, and the chunk's window being accumulated with the rows it
+    // still takes; a window's entries leave with the block that completes it (blocks never straddle a window edge)
+    constexpr uint32_t MASK = Elem<W>::MASK;
+    uint32_t qmin[CPL];                                    // (set at each chunk start, in that mode alone)
+    uint32_t wi = 0, wleft = 0;
+    uint64_t wbase = 0;
     auto q_row = [&](int k) {                              // pv[k] carries garbage above bit W: SDWA selects the element
         if constexpr (Q != 0) {
             if constexpr (W == 16) {
                 asm("v_max_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
                     : "=v"(qmax[k]) : "v"(qmax[k]), "v"(pv[k]));
+                if constexpr (Q == kQueryWindow)
+                    asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
+                        : "=v"(qmin[k]) : "v"(qmin[k]), "v"(pv[k]));
                 asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
                     : "=v"(qbs[k]) : "v"(qbs[k]), "v"(pv[k]));
             } else {
                 asm("v_max_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
                     : "=v"(qmax[k]) : "v"(qmax[k]), "v"(pv[k]));
+                if constexpr (Q == kQueryWindow)
+                    asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
+                        : "=v"(qmin[k]) : "v"(qmin[k]), "v"(pv[k]));
                 asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
                     : "=v"(qbs[k]) : "v"(qbs[k]), "v"(pv[k]));
             }
@@ -305,6 +317,19 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     };
     auto q_block = [&](int k) {
         if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
+    };
+    auto win_flush_all = [&]() {                           // window wi of this chunk leaves, every genuine column of the lane
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (col_ok[k]) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
+        wi++;
+        wleft = a.window_rows;
+    };
+    auto q_window = [&]() {                                // after every block of 8 rows
+        if constexpr (Q == kQueryWindow) {
+            wleft -= 8;
+            if (wleft == 0) win_flush_all();
+        }
     };
     uint32_t ovo = 0;                                      // output cursor (byte offset from this wave's out_base)
 
@@ -395,7 +420,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
     };
     auto stage_out = [&](int slot) {
-        if constexpr (Q == kQueryReduceOnly) return;
+        if constexpr (query_reduce_only(Q)) return;
         if constexpr (CMB) {                               // ovo counts ROW bytes here
             if (slot >= 0) {
                 const uint32_t blk = (stepno & 1u) * 2u + (uint32_t)slot;
@@ -452,6 +477,27 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         ovo += blk_bytes;
     };
     auto run_blocks = [&](uint32_t len) {                  // RUN slot: `len` blocks of zero error (:828-958)
+        if constexpr (Q == kQueryWindow && !FIRE) {
+            // a delta run repeats the previous row 8 len times (method.tex:150): per window it touches, min / max take the row
+            // once and the sum takes it times the run's rows in that window -- O(windows), not O(rows)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            uint32_t rows = len * 8u;
+            while (rows > 0) {
+                const uint32_t n = rows < wleft ? rows : wleft;
+#pragma unroll
+                for (int k = 0; k < CPL; k++) {
+                    const uint32_t x = pv[k] & MASK;
+                    qmin[k] = x < qmin[k] ? x : qmin[k];
+                    qmax[k] = x > qmax[k] ? x : qmax[k];
+                    qsum[k] += (uint64_t)x * n;
+                }
+                rows -= n;
+                wleft -= n;
+                if (wleft == 0) win_flush_all();
+            }
+            return;
+        }
         for (; len > 0; len--) {
             if (out_left < blk_elems) { corrupt = true; break; }
             out_left -= blk_elems;
@@ -476,7 +522,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     q_row(k);
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                    if constexpr (Q != kQueryReduceOnly && !CM)
+                    if constexpr (!query_reduce_only(Q) && !CM)
                         *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
 #endif
                 }
@@ -499,6 +545,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
                 for (int k = 0; k < CPL; k++) run_col(k);
             }
+            q_window();
             stage_out(-1);
         }
     };
@@ -594,7 +641,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 q_row(k);
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                if constexpr (Q != kQueryReduceOnly && !CM)
+                if constexpr (!query_reduce_only(Q) && !CM)
                     *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
 #else
                 asm volatile("" :: "v"(pv[k]));
@@ -625,6 +672,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
             for (int k = 0; k < CPL; k++) one_col(k);
         }
+        q_window();
         stage_out(slot);
     };
     auto run_length = [&](uint32_t at, uint32_t& nbytes) -> uint32_t {   // varint in blocks (:829-833)
@@ -671,6 +719,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         ahead -= hbytes;
 #pragma unroll
         for (int k = 0; k < CPL; k++) { pv[k] = 0; pd[k] = 0; ctr[k] = 0; qmax[k] = 0; qsum[k] = 0; }
+        if constexpr (Q == kQueryWindow) {                 // windows are relative to the chunk
+#pragma unroll
+            for (int k = 0; k < CPL; k++) qmin[k] = MASK;
+            wi = 0;
+            wleft = a.window_rows;
+            wbase = chunk * (uint64_t)a.win_count;
+        }
         out_left = a.chunk_len;
         ovo = CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
                  : (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * ESZ);
@@ -774,15 +829,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // counter for loads and stores, so parking the loads must not wait for the stores
         // just issued: with every VMEM op of the common path unconditional, hipcc emits
         // s_waitcnt vmcnt(<number of stores>) here instead of vmcnt(0).
-        if constexpr (Q != kQueryReduceOnly && CMB) {
+        if constexpr (!query_reduce_only(Q) && CMB) {
             cm_flush((stepno & 1u) != 0);
             stepno++;
-        } else if constexpr (Q != kQueryReduceOnly && CM) {
+        } else if constexpr (!query_reduce_only(Q) && CM) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
                 for (int k = 0; k < CPL; k++) store_col(cheld[s2][k], cheld_vo[s2][k]);
-        } else if constexpr (Q != kQueryReduceOnly) {
+        } else if constexpr (!query_reduce_only(Q)) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -802,7 +857,31 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // ---- verbatim tail (:1171), straight from HBM
     const uint32_t out_elems = a.chunk_len - out_left;
     if (!corrupt && remaining > out_left) corrupt = true;
-    if constexpr (Q != 0) {
+    if constexpr (Q == kQueryWindow) {
+        // tail element e is in column e % D, one row past the column's previous one: a window edge can fall inside the
+        // tail (W = 8).  Then the partial window leaves, and the identities of the slot's windows past the data.
+        if (!corrupt) {
+            const uint8_t* t = a.comp + gabs + rp;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                if (!col_ok[k]) continue;
+                uint32_t w = wi, left = wleft;
+                for (uint32_t e = (uint32_t)genk[k]; e < remaining; e += (uint32_t)D) {
+                    if (left == 0) {
+                        win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
+                        w++;
+                        left = a.window_rows;
+                    }
+                    left--;
+                    const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16_unaligned*)(t + 2 * e);
+                    qmin[k] = x < qmin[k] ? x : qmin[k];
+                    qmax[k] = x > qmax[k] ? x : qmax[k];
+                    qsum[k] += x;
+                }
+                for (; w < a.win_count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
+            }
+        }
+    } else if constexpr (Q != 0) {
         // the verbatim tail continues the row-major order: element e sits in column e % D
         if (!corrupt) {
             const uint8_t* t = a.comp + gabs + rp;
@@ -818,14 +897,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
     }
-    if (!corrupt && remaining > 0 && Q != kQueryReduceOnly && CM) {
+    if (!corrupt && remaining > 0 && !query_reduce_only(Q) && CM) {
         const uint8_t* t = a.comp + gabs + rp;
         U* const c0 = (U*)((uint8_t*)a.out + out_base + ovo);          // column 0 at the tail's first row
         for (uint32_t e = (uint32_t)lane_d; e < remaining; e += DP) {
             const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16_unaligned*)(t + 2 * e);
             c0[(uint64_t)(e % (uint32_t)D) * a.col_stride + e / (uint32_t)D] = (U)x;
         }
-    } else if (!corrupt && remaining > 0 && Q != kQueryReduceOnly) {
+    } else if (!corrupt && remaining > 0 && !query_reduce_only(Q)) {
         const uint8_t* t = a.comp + gabs + rp;
         uint8_t* d = (uint8_t*)a.out + out_base + ovo;
         copy_verbatim(t, d, remaining * ESZ, (uint32_t)lane_d, (uint32_t)DP);

@@ -48,11 +48,35 @@ struct DecodeArgs {
     uint64_t one_off0, one_off1;
     uint64_t* host_flag;
     uint64_t host_ticket;
+    // windowed query (Q == kQueryWindow; sprintz_mi355x_query_windows): chunk c, window w (rows [w*W, (w+1)*W) of the chunk
+    // slot) and column d land at entry (c*win_count + w)*D + d of each selected output; appended so that no field above moves
+    uint32_t window_rows;       // W, a multiple of 8: a block of 8 rows never straddles a window edge
+    uint32_t win_count;         // windows per chunk slot: ceil(ceil(chunk_len / D) / W)
+    uint32_t win_ops;           // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4
+    void* win_min;              // element type
+    void* win_max;              // element type
+    uint64_t* win_sum;
 };
 
 // Q (template): 0 = plain decode; 1 = decode + reduce; 2 = reduce only (nothing is written
-// to `out` -- QueryParams::materialize == false)
-constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2;
+// to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only
+constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3;
+// the modes that never store a decoded sample
+constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow; }
+
+// windowed query: one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the
+// accumulators start over from the identities (min = all ones, max = 0, sum = 0)
+template <int W>
+__device__ __forceinline__ void win_flush(const DecodeArgs& a, uint64_t idx, uint32_t& qmin, uint32_t& qmax, uint64_t& qsum)
+{
+    using U = typename Elem<W>::U;
+    if (a.win_ops & 1u) ((U*)a.win_min)[idx] = (U)qmin;
+    if (a.win_ops & 2u) ((U*)a.win_max)[idx] = (U)qmax;
+    if (a.win_ops & 4u) a.win_sum[idx] = qsum;
+    qmin = Elem<W>::MASK;
+    qmax = 0;
+    qsum = 0;
+}
 
 constexpr int64_t kErrCorrupt = -5;
 
@@ -134,6 +158,17 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     uint64_t qsum[CPL];
 #pragma unroll
     for (int k = 0; k < CPL; k++) { qmax[k] = 0; qsum[k] = 0; }
+    // windowed query: the window being accumulated and the rows it still takes
+    // (set up in that mode alone: the other instantiations stay exactly as they were)
+    uint32_t qmin[CPL];
+    uint32_t wi = 0, wleft = 0;
+    uint64_t wbase = 0;
+    if constexpr (Q == kQueryWindow) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) qmin[k] = MASK;
+        wleft = a.window_rows;
+        wbase = chunk * (uint64_t)a.win_count;
+    }
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -259,15 +294,28 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     qmax[k] = v[i][k] > qmax[k] ? v[i][k] : qmax[k];
+                    if constexpr (Q == kQueryWindow) qmin[k] = v[i][k] < qmin[k] ? v[i][k] : qmin[k];
                     bs += v[i][k];
                 }
                 qsum[k] += bs;
             }
         }
+        if constexpr (Q == kQueryWindow) {       // the block's 8 rows lie in one window: flush it when they complete it
+            wleft -= 8;
+            if (wleft == 0) {
+#pragma unroll
+                for (int k = 0; k < CPL; k++) {
+                    const int col = lane_d * CPL + k;
+                    if (col < D) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
+                }
+                wi++;
+                wleft = a.window_rows;
+            }
+        }
 
         // ---- store the 8 x D block (contiguous 8*D*ESZ bytes of the output)
         U* const ob = o + out_elems;
-        if constexpr (Q == kQueryReduceOnly) {
+        if constexpr (query_reduce_only(Q)) {
             (void)ob;
         } else if (cs) {
             const uint32_t r0 = out_elems / (uint32_t)D;
@@ -331,7 +379,32 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
     // ---- verbatim tail (:1171)
     if (!corrupt && (out_elems + remaining > a.chunk_len || (uint64_t)remaining * ESZ > (uint64_t)(stream_len - pos))) corrupt = true;
-    if constexpr (Q != 0) {
+    if constexpr (Q == kQueryWindow) {
+        // tail element e is in column e % D, one row further on than the column's previous one; a window
+        // edge can fall inside the tail.  Then the partial window and the identities of the slot's last ones.
+        if (!corrupt) {
+            const uint8_t* t = s + pos;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                const int col = lane_d * CPL + k;
+                if (col >= D) continue;
+                uint32_t w = wi, left = wleft;
+                for (uint32_t e = (uint32_t)col; e < remaining; e += (uint32_t)D) {
+                    if (left == 0) {
+                        win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
+                        w++;
+                        left = a.window_rows;
+                    }
+                    left--;
+                    const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
+                    qmin[k] = x < qmin[k] ? x : qmin[k];
+                    qmax[k] = x > qmax[k] ? x : qmax[k];
+                    qsum[k] += x;
+                }
+                for (; w < a.win_count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
+            }
+        }
+    } else if constexpr (Q != 0) {
         // the verbatim tail continues the row-major order: element e sits in column e % D
         // (out_elems is a multiple of 8*D)
         if (!corrupt) {
@@ -349,14 +422,14 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             }
         }
     }
-    if (!corrupt && Q != kQueryReduceOnly && cs) {
+    if (!corrupt && !query_reduce_only(Q) && cs) {
         const uint8_t* t = s + pos;
         const uint32_t r0 = out_elems / (uint32_t)D;
         for (uint32_t e = (uint32_t)lane_d; e < remaining; e += (uint32_t)DP) {
             const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
             cm0[(uint64_t)(e % (uint32_t)D) * cs + r0 + e / (uint32_t)D] = (U)x;
         }
-    } else if (!corrupt && Q != kQueryReduceOnly) {
+    } else if (!corrupt && !query_reduce_only(Q)) {
         const uint8_t* t = s + pos;
         uint8_t* d = (uint8_t*)(o + out_elems);
         copy_verbatim(t, d, remaining * ESZ, (uint32_t)lane_d, (uint32_t)DP);

@@ -151,6 +151,23 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
     uint64_t qsum[ND];
 #pragma unroll
     for (int k = 0; k < ND; k++) { qmax[k] = 0; qsum[k] = 0; }
+    // windowed query (Q == kQueryWindow): the minimum too, and this chunk's window being accumulated with the rows it still takes
+    // (set up in that mode alone: the other instantiations stay exactly as they were)
+    uint32_t qmin[ND];
+    uint32_t wi = 0, wleft = 0;
+    uint64_t wbase = 0;
+    if constexpr (Q == kQueryWindow) {
+#pragma unroll
+        for (int k = 0; k < ND; k++) qmin[k] = MASK;
+        wleft = a.window_rows;
+        wbase = chunk * (uint64_t)a.win_count;
+    }
+    auto win_flush_all = [&]() {
+#pragma unroll
+        for (int k = 0; k < ND; k++) win_flush<W>(a, (wbase + wi) * (uint64_t)ND + (uint64_t)k, qmin[k], qmax[k], qsum[k]);
+        wi++;
+        wleft = a.window_rows;
+    };
     int slot = 2;
     uint8_t* const obase = (uint8_t*)a.out + chunk * (uint64_t)a.chunk_len * ESZ;
     const bool odd1 = (t & 1) != 0, odd2 = (t & 2) != 0;
@@ -347,6 +364,7 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                         pd[k] = delta;
                         x[k][i] = pv[k];
                         if constexpr (Q != 0) { qmax[k] = pv[k] > qmax[k] ? pv[k] : qmax[k]; qsum[k] += pv[k]; }
+                        if constexpr (Q == kQueryWindow) qmin[k] = pv[k] < qmin[k] ? pv[k] : qmin[k];
                     }
                     if (FIRE && nbsum != 0) ctr[k] = wrap_counter<W>(ctr[k] + (sext<W>(grad) >> 2));   // counters only move on real blocks
                     cf += nbk;
@@ -363,13 +381,17 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                 }
                 valid |= 1u << b;
                 out_elems += 8 * ND;
+                if constexpr (Q == kQueryWindow) {         // a block's 8 rows lie in one window: it leaves with the block that completes it
+                    wleft -= 8;
+                    if (wleft == 0) win_flush_all();
+                }
             }
         }
         // ---- the window leaves.  Full windows: the quad transposes its 16-byte pieces (two DPP
         // butterfly stages: (member m, piece k) -> (lane k, slot m)) and stores one member's 64
         // bytes per instruction.  A partly filled window (the chunk's end) is stored block by block.
         const bool full = valid == (1u << BW) - 1u;
-        if constexpr (Q != kQueryReduceOnly) {
+        if constexpr (!query_reduce_only(Q)) {
 #pragma unroll
         for (int wn = 0; wn < WINS; wn++) {
         uint32_t v[4][4];
@@ -439,11 +461,25 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
         if (!corrupt && (uint64_t)(c - c_begin) + (uint64_t)remaining * ESZ > stream_len + 2) corrupt = true;
         if (!corrupt) {
             const uint8_t* src = a.comp + off + (c - c_begin);
-            if constexpr (Q != kQueryReduceOnly) {
+            if constexpr (!query_reduce_only(Q)) {
                 uint8_t* d = obase + (uint64_t)out_elems * ESZ;
                 for (uint32_t j = 0; j < remaining * ESZ; j++) d[j] = src[j];
             }
-            if constexpr (Q != 0) {                      // the verbatim tail continues the row-major order: element e is column e % ND
+            if constexpr (Q == kQueryWindow) {           // element e of the tail is column e % ND; a row starts with column 0, a window edge can fall inside
+                uint32_t col = 0;
+                for (uint32_t e = 0; e < remaining; e++) {
+                    if (col == 0) {
+                        if (wleft == 0) win_flush_all();
+                        wleft--;
+                    }
+                    const uint32_t x = ESZ == 1 ? (uint32_t)src[e] : ((uint32_t)src[2 * e] | ((uint32_t)src[2 * e + 1] << 8));
+#pragma unroll
+                    for (int k = 0; k < ND; k++)
+                        if (col == (uint32_t)k) { qmin[k] = x < qmin[k] ? x : qmin[k]; qmax[k] = x > qmax[k] ? x : qmax[k]; qsum[k] += x; }
+                    col = col + 1 == (uint32_t)ND ? 0u : col + 1;
+                }
+                while (wi < a.win_count) win_flush_all();  // the partial window, then the identities of the slot's last ones
+            } else if constexpr (Q != 0) {               // the verbatim tail continues the row-major order: element e is column e % ND
                 for (uint32_t e = 0; e < remaining; e++) {
                     const uint32_t x = ESZ == 1 ? (uint32_t)src[e] : ((uint32_t)src[2 * e] | ((uint32_t)src[2 * e + 1] << 8));
 #pragma unroll

@@ -28,9 +28,11 @@ hipError_t launch_decode_uni_w16(bool fire, int nd, int q, unsigned grid, hipStr
     SPRINTZ_UNI_CASE(1, kQueryOff)
     SPRINTZ_UNI_CASE(1, kQueryMaterialize)
     SPRINTZ_UNI_CASE(1, kQueryReduceOnly)
+    SPRINTZ_UNI_CASE(1, kQueryWindow)
     SPRINTZ_UNI_CASE(2, kQueryOff)
     SPRINTZ_UNI_CASE(2, kQueryMaterialize)
     SPRINTZ_UNI_CASE(2, kQueryReduceOnly)
+    SPRINTZ_UNI_CASE(2, kQueryWindow)
     return hipErrorInvalidValue;
 }
 #undef SPRINTZ_UNI_CASE

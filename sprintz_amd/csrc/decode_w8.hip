@@ -28,15 +28,19 @@ hipError_t launch_decode_uni_w8(bool fire, int nd, int q, unsigned grid, hipStre
     SPRINTZ_UNI_CASE(1, kQueryOff)
     SPRINTZ_UNI_CASE(1, kQueryMaterialize)
     SPRINTZ_UNI_CASE(1, kQueryReduceOnly)
+    SPRINTZ_UNI_CASE(1, kQueryWindow)
     SPRINTZ_UNI_CASE(2, kQueryOff)
     SPRINTZ_UNI_CASE(2, kQueryMaterialize)
     SPRINTZ_UNI_CASE(2, kQueryReduceOnly)
+    SPRINTZ_UNI_CASE(2, kQueryWindow)
     SPRINTZ_UNI_CASE(3, kQueryOff)
     SPRINTZ_UNI_CASE(3, kQueryMaterialize)
     SPRINTZ_UNI_CASE(3, kQueryReduceOnly)
+    SPRINTZ_UNI_CASE(3, kQueryWindow)
     SPRINTZ_UNI_CASE(4, kQueryOff)
     SPRINTZ_UNI_CASE(4, kQueryMaterialize)
     SPRINTZ_UNI_CASE(4, kQueryReduceOnly)
+    SPRINTZ_UNI_CASE(4, kQueryWindow)
     return hipErrorInvalidValue;
 }
 #undef SPRINTZ_UNI_CASE

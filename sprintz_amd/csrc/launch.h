@@ -128,11 +128,13 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
         default: return hipErrorInvalidValue;                                                         \
     }
 
-// q: kQueryOff / kQueryMaterialize / kQueryReduceOnly (decode_kernel.h)
+// q: kQueryOff / kQueryMaterialize / kQueryReduceOnly / kQueryWindow (decode_kernel.h)
 #define SPRINTZ_DISPATCH(KERNEL, W)                                                                   \
     if (q == kQueryOff) { SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryOff) }                                  \
     if (q == kQueryMaterialize) { SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryMaterialize) }                  \
-    SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryReduceOnly)
+    if (q == kQueryReduceOnly) { SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryReduceOnly) }                    \
+    if (q == kQueryWindow) { SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryWindow) }                            \
+    return hipErrorInvalidValue;
 
 #define SPRINTZ_FAST_CASE(KERNEL, W, DPV, CPLV, Q, CMV)                                              \
     if (dp == DPV && cpl == CPLV) {                                                                   \
@@ -161,7 +163,9 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
     if (a.col_stride && q == kQueryMaterialize) return hipErrorInvalidValue;                          \
     if (q == kQueryOff) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryOff, false) }               \
     if (q == kQueryMaterialize) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryMaterialize, false) } \
-    SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryReduceOnly, false)
+    if (q == kQueryReduceOnly) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryReduceOnly, false) } \
+    if (q == kQueryWindow) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryWindow, false) }         \
+    return hipErrorInvalidValue;
 
 #define SPRINTZ_ENC_FAST_CASE(KERNEL, W, DPV, CMV)                                                   \
     case DPV:                                                                                         \
