@@ -402,6 +402,32 @@ int sprintz_mi355x_query_reduce(int op, const uint64_t* d_partials, uint64_t nch
 int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                  uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
                                  void* d_min, void* d_max, uint64_t* d_sum, int64_t* d_rets, void* hip_stream);
+/* Gather rows: N row ranges of a compressed batch, decoded in one launch into a dense [N][rows][ndims] array -- the read
+ * the chunked format exists for ("so that queries over arbitrary time intervals are cheap", communicate/intro.tex:55).
+ *
+ * The batch is given exactly as to sprintz_mi355x_decompress_batch (the payload layout is the one it infers from ndims).
+ * With D = ndims and R = chunk_len / D rows a chunk slot, batch row g is row g % R of chunk g / R.  Range i is batch rows
+ * [d_starts[i], d_starts[i] + rows); element (row r, column d) of range i lands at d_out[(i*rows + r)*D + d], element type
+ * uint8 / uint16, with the value decompress_batch writes for that row under the same options
+ * (SPRINTZ_OPT_REF_DECODER_QUIRK included).  Ranges may overlap, repeat, come in any order and span any number of chunks.
+ * d_starts lives on the device: the call does not read it on the host, does not synchronise, does not allocate and needs
+ * no scratch.  A range costs the decode of every chunk it touches from that chunk's row 0 up to the last row it needs --
+ * parsing stops there -- and a chunk shared by several ranges is decoded once per range (sort and merge dense ranges on
+ * the caller's side).
+ * d_rets (optional, nranges entries): `rows` for a range delivered in full; SPRINTZ_E_INVALID if the range needs a row that
+ * does not exist (a chunk >= nchunks, or a row past the rows its chunk's stream holds: the short last chunk);
+ * SPRINTZ_E_CORRUPT if a chunk it touches is found damaged before the last row the range needs from it (the smaller code
+ * if both).  The rows*D output elements of such a range are unspecified; nothing outside them is written and every
+ * other range is exact.  Damage that lies AFTER the last needed row of a chunk may go unnoticed: this call is no integrity
+ * check of the container.  When d_rets is given, a small fill kernel runs in front of the decode launch.
+ * The container must be laid out as this library writes it (offsets[c+1] - offsets[c] <= compress_bound + alignment).
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0 (rows must not straddle chunks),
+ * rows == 0, chunk_len outside 1..2^30, a NULL d_comp / d_offsets / d_out, a NULL d_starts with nranges > 0, d_out not
+ * aligned to the element size, d_starts / d_rets not aligned to 8 bytes; SPRINTZ_E_UNSUPPORTED for more than 512 columns and
+ * for the non-RLE codecs.  nranges == 0 returns 0 and launches nothing. */
+int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, const uint64_t* d_starts, uint64_t nranges, uint32_t rows,
+                               void* d_out, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

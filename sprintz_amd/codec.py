@@ -395,6 +395,52 @@ class ChunkedCodec:
                 out["mean"] = out["sum"].to(torch.float64) / cnt.to(torch.float64)
         return {k: v for k, v in out.items() if k in ops}
 
+    def gather_rows(self, batch, starts, rows, out=None, rets=None, check=True):
+        """N row ranges of the compressed batch, decoded in one launch -> tensor [N, rows, ndims] of the codec's dtype.
+
+        Batch row g is row g % R of chunk g / R, R = chunk_len / ndims (chunk_len must be a multiple of ndims); range i is
+        batch rows [starts[i], starts[i] + rows).  starts: an int64 / uint64 device tensor, or anything torch.as_tensor
+        takes.  Ranges may overlap, repeat and span chunks; a chunk several ranges touch is decoded once per range.
+        check=True allocates `rets` if none was given and raises SprintzError naming the first range that needs a row the
+        batch does not hold or touches a damaged chunk (damage behind the last row a range needs from a chunk may go
+        unnoticed); check=False does not synchronise -- pass `rets` [N] int64 to look at the outcome later."""
+        torch = self.torch
+        if not torch.is_tensor(starts) or starts.dtype not in (torch.int64, torch.uint64) or starts.device != self.device:
+            starts = torch.as_tensor(starts, dtype=torch.int64).to(self.device)
+        starts = starts.reshape(-1).contiguous()
+        n, rows, D = int(starts.numel()), int(rows), self.ndims
+        if rows < 1:
+            raise ValueError("rows must be positive")
+        if out is None:
+            out = torch.empty((n, rows, D), dtype=self.dtype, device=self.device)
+        elif out.dtype != self.dtype or out.device != self.device or out.numel() != n * rows * D or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {self.dtype} tensor of {n} x {rows} x {D} elements on {self.device}")
+        if rets is None and check:
+            rets = torch.empty(n, dtype=torch.int64, device=self.device)
+        if rets is not None and (rets.dtype != torch.int64 or rets.device != self.device or rets.numel() < n or not rets.is_contiguous()):
+            raise ValueError(f"rets must be a contiguous int64 tensor of at least {n} entries on {self.device}")
+        if n == 0:
+            return out.view(0, rows, D)
+        with self._on():
+            _lib.check(_lib.gather_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), batch.nchunks,
+                                        self.chunk_len, D, starts.data_ptr(), n, rows, out.data_ptr(),
+                                        rets.data_ptr() if rets is not None else None, self._stream()))
+        if check:
+            bad = (rets[:n] < 0).nonzero()
+            if bad.numel():
+                i = int(bad[0, 0].item())
+                code = int(rets[i].item())
+                what = "needs a row the batch does not hold" if code == _lib.E_INVALID else "touches a damaged chunk"
+                raise _lib.SprintzError(code, f"gather_rows: range {i} (start {int(starts[i].item())}) {what} (decoder returned {code})")
+        return out.view(n, rows, D)
+
+    def read_rows(self, batch, lo, hi):
+        """batch rows [lo, hi) -> [hi - lo, ndims]: one range of gather_rows, its chunks decoded side by side in the same launch"""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi:
+            raise ValueError("read_rows needs 0 <= lo < hi")
+        return self.gather_rows(batch, [lo], hi - lo)[0]
+
 
 # ---- query on compressed data, single call (the reference's names) -----------------------
 

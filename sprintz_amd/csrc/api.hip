@@ -338,6 +338,13 @@ namespace {
 
 // ---------------------------------------------------------------- launch helpers
 
+// gather_rows: every range's entry starts at `rows`; a failing piece lowers it to its code (decode_kernel.h: gather_fail)
+__global__ void gather_rets_fill(int64_t* rets, uint64_t n, int64_t v)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) rets[i] = v;
+}
+
 int check_common(int codec, int esz, uint16_t ndims)
 {
     if (codec < SPRINTZ_CODEC_DELTA || codec > SPRINTZ_CODEC_XFF_NORLE)
@@ -1868,6 +1875,86 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
     qs.win_sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
     return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                          0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- gather rows
+int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, const uint64_t* d_starts, uint64_t nranges, uint32_t rows,
+                               void* d_out, int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if (codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, "gather_rows: the RLE codecs (delta, xff) only");
+    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no gather");
+    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "gather_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if (rows == 0) return fail(SPRINTZ_E_INVALID, "gather_rows: rows == 0");
+    if (!d_comp || !d_offsets || !d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if (nranges > 0 && !d_starts) return fail(SPRINTZ_E_INVALID, "gather_rows: ranges without their starts");
+    if ((uintptr_t)d_out % (uintptr_t)elem_bytes) return fail(SPRINTZ_E_INVALID, "gather_rows: d_out must be aligned to the element size");
+    if ((uintptr_t)d_starts % 8 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "gather_rows: d_starts and d_rets must be aligned to 8 bytes");
+    const int D = ndims, esz = elem_bytes;
+    const uint32_t R = chunk_len / ndims;
+    const uint64_t P = ((uint64_t)rows + R - 2) / R + 1;                 // the most chunks a range of `rows` rows can touch
+    if (nranges > (1ull << 40) || nranges * P > (1ull << 40)) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
+    if ((rc = ensure_device())) return rc;
+    if (nranges == 0) return 0;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    const bool lowdim = is_lowdim(esz, D);
+    const Mapping m = choose_mapping(D, lowdim);
+    DecodeArgs a{};
+    a.comp = (const uint8_t*)d_comp;
+    a.offsets = d_offsets;
+    a.nchunks = nchunks;
+    a.chunk_len = chunk_len;
+    a.D = D;
+    a.log2DP = m.log2DP;
+    a.out = d_out;
+    a.rets = d_rets;
+    a.chunks_per_group = 1;
+    a.quirk = decode_ref_quirk(codec, esz, lowdim) ? 1 : 0;
+    a.g_starts = d_starts;
+    a.g_nranges = nranges;
+    a.g_rows = rows;
+    a.g_rpc = R;
+    a.g_pieces = (uint32_t)P;
+    if (d_rets) {
+        hipLaunchKernelGGL(gather_rets_fill, dim3((unsigned)((nranges + 255) / 256)), dim3(256), 0, st, d_rets, nranges, (int64_t)rows);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint64_t slots = nranges * P;
+    const bool fire = codec == SPRINTZ_CODEC_XFF;
+
+    // decode_fast.h: the shapes the decode takes there, with rows of whole 16-byte store pieces, and both the container and the output
+    // within reach of one descriptor's 32-bit offsets.  The container's size is on the device; every container this library writes
+    // stays below nchunks * (compress_bound + alignment).  Everything else goes to the generic kernel: plain 64-bit addresses.
+    int fdp = 4, fcpl = 1;
+    while (fdp < D && fdp < 64) fdp <<= 1;
+    while (fdp * fcpl < D) fcpl <<= 1;
+    const size_t fstride = decode_fast_lds_bytes(8 * esz, fdp, fcpl, D, false, 0);
+    const uint64_t out_bytes = nranges * (uint64_t)rows * (uint64_t)D * esz;          // (nranges * P <= 2^40 and rows <= P * R: no wrap)
+    const uint64_t comp_bound = nchunks * (uint64_t)(sprintz_mi355x_compress_bound(esz, chunk_len, ndims) + 64);
+    const bool fast = !lowdim && D <= 256 && 2 * D > fdp * fcpl && (uint64_t)chunk_len * esz * 2 >= fstride && ((uint64_t)D * esz) % 16 == 0 &&
+                      ((uintptr_t)d_out % 16) == 0 && out_bytes < 0xf0000000ull && nchunks < (1ull << 32) && comp_bound < 0xf0000000ull &&
+                      !process().no_fast.load(std::memory_order_relaxed);
+    hipError_t e;
+    if (fast) {
+        a.log2DP = 0;
+        while ((1 << a.log2DP) < fdp) a.log2DP++;
+        const size_t fgroups = kThreads / fdp;
+        a.lds_group_stride = (uint32_t)fstride;
+        const uint64_t fgrid = (slots * (uint64_t)fdp + kThreads - 1) / kThreads;
+        if (fgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
+        e = launch_decode_fast_gather(8 * esz, fire, fdp, fcpl, D == fdp * fcpl, (unsigned)fgrid, fstride * fgroups, st, a);
+        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_fast gather kernel launch", e);
+        return 0;
+    }
+    const uint64_t grid = ((slots << m.log2DP) + kThreads - 1) / kThreads;
+    if (grid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
+    e = launch_decode_gather(8 * esz, fire, lowdim, m.cpl, (unsigned)grid, st, a);
+    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode gather kernel launch", e);
+    return 0;
 }
 
 int sprintz_mi355x_query_reduce(int op, const uint64_t* d_partials, uint64_t nchunks, uint16_t ndims, uint64_t* d_result,

@@ -118,6 +118,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     constexpr uint32_t UNIT = ROW16 * CPL;                 // bytes one refill unit brings in (CPL pieces per lane)
     constexpr bool SPLIT = CPL == 3;
     static_assert(!SPLIT || (W == 8 && DP == 32 && !EXACT && !CM && Q == 0), "the split mapping is built for 8-bit row-major decodes");
+    // GATHER (sprintz_mi355x_gather_rows): a lane group decodes ONE piece -- rows [lo, hi) of one chunk, for one range -- from the chunk's
+    // row 0, stores those rows alone and stops after row hi - 1.  The groups of a wave then work on unrelated chunks and unrelated output
+    // rows: both descriptors are based at the container / at `out` (the launch checks that both spans fit 32-bit offsets), and the
+    // launch takes only rows of whole 16-byte pieces, so that a store piece lies in ONE row and the row test decides it as a whole.
+    constexpr bool GATHER = Q == kQueryGather;
+    static_assert(!GATHER || (!CM && !SPLIT && DS == 0), "gather: row-major destination, plain mappings");
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -141,9 +147,18 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // A group decodes `chunks_per_group` CONSECUTIVE chunks.  Their streams are
     // (nearly) contiguous in the container, so the ring's read-ahead runs straight
     // across chunk boundaries: one cold start per group instead of one per chunk.
-    const uint64_t c_first = (gtid >> LOG2DP) * (uint64_t)a.chunks_per_group;
+    GatherPiece gp{};
+    uint64_t c_sel = (gtid >> LOG2DP) * (uint64_t)a.chunks_per_group;
+    if constexpr (GATHER) {                                // consecutive piece slots on consecutive groups: a range's chunks share a wave
+        if (!gather_piece(a, gtid >> LOG2DP, gp)) return;
+        // (a stream that 32-bit offsets cannot reach: the launch's size bound holds for every container the library writes)
+        if (gp.exists && a.offsets[gp.chunk + 1] > 0xfffffff0ull - 4096u) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); return; }
+        if (!gp.exists) { if (lane_d == 0) gather_fail(a, gp.range, kErrNoRow); return; }
+        c_sel = gp.chunk;
+    }
+    const uint64_t c_first = c_sel;
     if (c_first >= a.nchunks) return;
-    const uint64_t c_end = (c_first + a.chunks_per_group < a.nchunks) ? c_first + a.chunks_per_group : a.nchunks;
+    const uint64_t c_end = GATHER ? c_first + 1 : (c_first + a.chunks_per_group < a.nchunks) ? c_first + a.chunks_per_group : a.nchunks;
 
     // LDS carve per group: [ring RB | apron APRON | block staging]
     uint8_t* const ringp = smem + (size_t)(threadIdx.x >> LOG2DP) * a.lds_group_stride;
@@ -154,9 +169,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // descriptor that spans the container from this wavefront's first stream to its
     // end: offsets are 32-bit, and a load that runs past the container returns 0
     // instead of faulting -- the read-ahead needs no bounds test.
-    const uint64_t wave_first = (((uint64_t)blockIdx.x * kThreads + (threadIdx.x & ~63u)) >> LOG2DP) * (uint64_t)a.chunks_per_group;
-    uint64_t wave_base = a.offsets[wave_first < a.nchunks ? wave_first : 0] & ~(uint64_t)15;
-    wave_base = wave_uniform64(wave_base);
+    const uint64_t wave_first = GATHER ? 0 : (((uint64_t)blockIdx.x * kThreads + (threadIdx.x & ~63u)) >> LOG2DP) * (uint64_t)a.chunks_per_group;
+    uint64_t wave_base = 0;
+    if constexpr (!GATHER) {
+        wave_base = a.offsets[wave_first < a.nchunks ? wave_first : 0] & ~(uint64_t)15;
+        wave_base = wave_uniform64(wave_base);
+    }
     // rounded up to whole 16-byte pieces (gfx950 zeroes a dwordx4 whose END is out of range);
     // the <= 15 extra bytes are inside the SPRINTZ_MI355X_READ_SLACK the API asks for
     const uint64_t wave_span = ((a.offsets[a.nchunks] - wave_base) + 15) & ~(uint64_t)15;
@@ -171,6 +189,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     const uint64_t out_base = CM ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)rows_per_chunk * ESZ
                                  : (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * ESZ;
     const uint64_t out_span = CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
+                            : GATHER ? a.g_nranges * (uint64_t)a.g_rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
                                  : a.nchunks * (uint64_t)a.chunk_len * ESZ - out_base;
     // (both are wave-uniform by construction; saying so keeps hipcc from wrapping every store in a
     //  readfirstlane waterfall loop -- 8 VALU per store it cannot prove away)
@@ -332,6 +351,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
     };
     uint32_t ovo = 0;                                      // output cursor (byte offset from this wave's out_base)
+    // gather: the chunk-relative row of the next block, and the row of the block each of this lane's 16-byte store pieces lies in
+    // (a row is a whole number of pieces and a block starts a row, so that is the same for every block)
+    uint32_t grow = 0;
+    uint32_t prow[PIECES];
+#pragma unroll
+    for (int q = 0; q < PIECES; q++) prow[q] = GATHER ? (lane16 + (uint32_t)q * ROW16) / row_stride : 0u;
+    const uint32_t gspan = gp.hi - gp.lo;
 
     // ---- per-block workers ------------------------------------------------------
     // The staged 8 x D block is contiguous in the output.  Packed blocks are read
@@ -451,7 +477,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
         for (int q = 0; q < PIECES; q++) {
             const uint32_t u = lane16 + q * ROW16;
-            const bool in = u < blk_bytes;
+            bool in = u < blk_bytes;
+            if constexpr (GATHER) in = in && grow + prow[q] - gp.lo < gspan;   // the piece's row is one the range wants
             const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
             if (slot >= 0) {
                 held[slot][q] = t;
@@ -498,7 +525,18 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             return;
         }
+        if constexpr (GATHER && !FIRE) {
+            // a delta run repeats the previous row: the blocks in front of row lo change no state and store nothing
+            uint32_t skip = grow + 8u <= gp.lo ? (gp.lo - grow) >> 3 : 0u;
+            skip = skip < len ? skip : len;
+            if ((uint64_t)skip * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= skip * blk_elems;
+            ovo += skip * blk_bytes;
+            grow += skip * 8u;
+            len -= skip;
+        }
         for (; len > 0; len--) {
+            if constexpr (GATHER) { if (grow >= gp.hi) break; }   // row hi - 1 has left: the rest of the run is not replayed
             if (out_left < blk_elems) { corrupt = true; break; }
             out_left -= blk_elems;
             auto run_step = [&](int k, int coef) {
@@ -546,7 +584,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 for (int k = 0; k < CPL; k++) run_col(k);
             }
             q_window();
-            stage_out(-1);
+            if constexpr (GATHER) {                        // (a FIRE run in front of row lo is replayed for its state, not staged out)
+                if (grow + 8u > gp.lo) stage_out(-1); else ovo += blk_bytes;
+                grow += 8u;
+            } else {
+                stage_out(-1);
+            }
         }
     };
     // Field fetch fused with zigzag^-1.  With z = bits [sh, sh+nb) of the loaded dword,
@@ -674,6 +717,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
         q_window();
         stage_out(slot);
+        if constexpr (GATHER) grow += 8u;
     };
     auto run_length = [&](uint32_t at, uint32_t& nbytes) -> uint32_t {   // varint in blocks (:829-833)
         const uint32_t b0 = lds_rd8(at);
@@ -728,6 +772,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
         out_left = a.chunk_len;
         ovo = CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
+          : GATHER ? (uint32_t)(uint64_t)(gp.obase * ESZ)  // where the chunk's row 0 would land: only rows [lo, hi) are stored, and those lie in `out`
                  : (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * ESZ);
         corrupt = (int)nd_hdr != D;
         // a damaged header must not make the loop spin: every group takes at least its
@@ -738,6 +783,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     }
 
     while (groups_left > 0 && !corrupt) {
+        if constexpr (GATHER) { if (grow >= gp.hi) break; }   // the piece is complete: nothing behind row hi - 1 is parsed
         groups_left--;
         // ---- request the units that fit now; they are parked at the bottom of this step
         {
@@ -817,7 +863,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (tot1 != 0) fetch_rows(z1, at1, off1, nb1, rb1);
 
         if (tot0 == 0) run_blocks(len0); else packed_block(z0, 0);
-        if (!corrupt) { if (tot1 == 0) run_blocks(len1); else packed_block(z1, 1); }
+        if (!corrupt && !(GATHER && grow >= gp.hi)) { if (tot1 == 0) run_blocks(len1); else packed_block(z1, 1); }
 
         rp += used;
         rofs += used;
@@ -856,6 +902,23 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     }
     // ---- verbatim tail (:1171), straight from HBM
     const uint32_t out_elems = a.chunk_len - out_left;
+    if constexpr (GATHER) {
+        // rows of the tail the piece still needs -- or rows the stream does not hold (the short last chunk)
+        if (corrupt) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); return; }
+        if (grow >= gp.hi) return;                         // delivered in full: the range's entry keeps g_rows
+        if (remaining > out_left || (uint64_t)gp.hi * (uint32_t)D > (uint64_t)out_elems + remaining) {
+            if (lane_d == 0) gather_fail(a, gp.range, remaining > out_left ? kErrCorrupt : kErrNoRow);
+            return;
+        }
+        if (gabs + rp + (uint64_t)remaining * ESZ > a.offsets[chunk + 1]) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); return; }
+        const uint8_t* t = a.comp + gabs + rp;
+        const uint32_t e_lo = gp.lo * (uint32_t)D > out_elems ? gp.lo * (uint32_t)D - out_elems : 0u;
+        const uint32_t e_hi = gp.hi * (uint32_t)D - out_elems;
+        U* const d = (U*)a.out + (gp.obase + (int64_t)out_elems);
+        for (uint32_t e = e_lo + (uint32_t)lane_d; e < e_hi; e += DP)
+            d[e] = ESZ == 1 ? (U)t[e] : (U)*(const u16_unaligned*)(t + 2 * e);
+        return;
+    }
     if (!corrupt && remaining > out_left) corrupt = true;
     if constexpr (Q == kQueryWindow) {
         // tail element e is in column e % D, one row past the column's previous one: a window edge can fall inside the

@@ -56,11 +56,19 @@ struct DecodeArgs {
     void* win_min;              // element type
     void* win_max;              // element type
     uint64_t* win_sum;
+    // gather rows (Q == kQueryGather; sprintz_mi355x_gather_rows): range i is batch rows [g_starts[i], g_starts[i] + g_rows), batch row g
+    // being row g % g_rpc of chunk g / g_rpc; piece slot s = i * g_pieces + k decodes chunk g_starts[i] / g_rpc + k (gather_piece below)
+    const uint64_t* g_starts;   // [g_nranges], on the device
+    uint64_t g_nranges;
+    uint32_t g_rows;            // rows of every range
+    uint32_t g_rpc;             // R: rows of a chunk slot, chunk_len / D
+    uint32_t g_pieces;          // P: the most chunks a range can touch, (g_rows + R - 2) / R + 1
 };
 
 // Q (template): 0 = plain decode; 1 = decode + reduce; 2 = reduce only (nothing is written
-// to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only
-constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3;
+// to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only;
+// 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1
+constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow; }
 
@@ -79,6 +87,40 @@ __device__ __forceinline__ void win_flush(const DecodeArgs& a, uint64_t idx, uin
 }
 
 constexpr int64_t kErrCorrupt = -5;
+constexpr int64_t kErrNoRow = -1;             // gather: the range needs a row that does not exist (SPRINTZ_E_INVALID)
+
+// gather: what piece slot `slot` has to do.  All of it follows from g_starts[range] on the device; a slot past the range's last
+// chunk has nothing to do (false).  `obase` is where row 0 of the piece's CHUNK would land in `out`, in elements: negative or past
+// the range's own rows for most pieces -- the row test [lo, hi) alone decides which stores happen.
+struct GatherPiece {
+    uint64_t range, chunk;
+    uint32_t lo, hi;            // chunk-relative rows the range needs from this chunk, lo < hi <= g_rpc
+    int64_t obase;
+    bool exists;                // chunk < nchunks; if not, the range fails without a decode
+};
+__device__ __forceinline__ bool gather_piece(const DecodeArgs& a, uint64_t slot, GatherPiece& p)
+{
+    p.range = slot / a.g_pieces;
+    if (p.range >= a.g_nranges) return false;
+    const uint64_t k = slot - p.range * a.g_pieces, R = a.g_rpc;
+    const uint64_t g0 = a.g_starts[p.range], c0 = g0 / R;
+    p.exists = c0 < a.nchunks;                      // (checked first: c0 + k cannot wrap below)
+    p.chunk = 0; p.lo = 0; p.hi = 1; p.obase = 0;
+    if (!p.exists) return k == 0;                   // one slot reports the missing rows
+    const uint64_t first = g0 - c0 * R, end = first + a.g_rows;   // the range, in rows from row 0 of chunk c0
+    if (k * R >= end) return false;
+    p.chunk = c0 + k;
+    p.exists = p.chunk < a.nchunks;
+    p.lo = (uint32_t)((first > k * R ? first : k * R) - k * R);
+    p.hi = (uint32_t)((end < (k + 1) * R ? end : (k + 1) * R) - k * R);
+    p.obase = ((int64_t)(p.range * a.g_rows) + (int64_t)(k * R) - (int64_t)first) * (int64_t)a.D;
+    return true;
+}
+// a failing piece leaves its code in the range's entry (the entries start at g_rows: gather_rets_fill; the smallest code wins)
+__device__ __forceinline__ void gather_fail(const DecodeArgs& a, uint64_t range, int64_t code)
+{
+    if (a.rets) atomicMin((long long*)&a.rets[range], (long long)code);
+}
 
 template <int W, bool FIRE, bool LOWDIM, int CPL, int Q = 0>
 __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
@@ -92,8 +134,18 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     const int DP = 1 << a.log2DP;
     const int D = a.D;
     const uint64_t gtid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const uint64_t chunk = gtid >> a.log2DP;
     const int lane_d = (int)(threadIdx.x & (uint32_t)(DP - 1));
+    GatherPiece gp{};
+    uint64_t chunk_sel = gtid >> a.log2DP;
+    if constexpr (Q == kQueryGather) {              // the group's piece instead of the group's chunk
+        if (!gather_piece(a, chunk_sel, gp)) return;
+        if (!gp.exists) {
+            if (lane_d == 0) gather_fail(a, gp.range, kErrNoRow);
+            return;
+        }
+        chunk_sel = gp.chunk;
+    }
+    const uint64_t chunk = chunk_sel;
     if (chunk >= a.nchunks) return;                 // whole groups leave together
 
     const uint64_t off_c = a.offsets[chunk];
@@ -115,7 +167,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         const uint32_t ndo = a.norle == 2 ? 6u : 4u;
         const uint32_t nd = load_u8(s + ndo) | (load_u8(s + ndo + 1) << 8);
         if ((int)nd != D || len > a.chunk_len) {
-            if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
+            if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
+            else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             return;
         }
         groups_left = len < 128u ? 0u : len / (16u * (uint32_t)D);
@@ -127,7 +180,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         remaining = w1 & 0xffffu;
         pos = 8;
         if ((int)(w1 >> 16) != D) {
-            if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
+            if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
+            else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             return;
         }
     } else {
@@ -317,6 +371,21 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         U* const ob = o + out_elems;
         if constexpr (query_reduce_only(Q)) {
             (void)ob;
+        } else if constexpr (Q == kQueryGather) {
+            // rows [lo, hi) of the chunk alone, each at its place in the range; the parse stops after row hi - 1
+            (void)ob;
+            const uint32_t r0 = out_elems / (uint32_t)D;
+            const int64_t eb = gp.obase + (int64_t)out_elems;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                const int col = lane_d * CPL + k;
+                if (col < D) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        if (r0 + (uint32_t)i >= gp.lo && r0 + (uint32_t)i < gp.hi) ((U*)a.out)[eb + (int64_t)(i * D + col)] = (U)v[i][k];
+                }
+            }
+            if (r0 + 8u >= gp.hi) return;            // delivered in full: the range's entry keeps g_rows
         } else if (cs) {
             const uint32_t r0 = out_elems / (uint32_t)D;
 #pragma unroll
@@ -421,6 +490,25 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 if (a.qres) a.qres[chunk * (uint64_t)D + (uint64_t)col] = a.qop == 1 ? (uint64_t)qmax[k] : qsum[k];
             }
         }
+    }
+    if constexpr (Q == kQueryGather) {
+        // the piece still needs rows of the verbatim tail -- or rows the stream does not hold (the short last chunk)
+        if (!corrupt && (uint64_t)gp.hi * (uint32_t)D > (uint64_t)out_elems + remaining) {
+            if (lane_d == 0) gather_fail(a, gp.range, kErrNoRow);
+            return;
+        }
+        if (corrupt) {
+            if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt);
+            return;
+        }
+        const uint8_t* t = s + pos;
+        const uint32_t e_lo = gp.lo * (uint32_t)D > out_elems ? gp.lo * (uint32_t)D - out_elems : 0u;
+        const uint32_t e_hi = gp.hi * (uint32_t)D - out_elems;                  // <= remaining, checked above
+        for (uint32_t e = e_lo + (uint32_t)lane_d; e < e_hi; e += (uint32_t)DP) {
+            const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
+            ((U*)a.out)[gp.obase + (int64_t)out_elems + (int64_t)e] = (U)x;
+        }
+        return;
     }
     if (!corrupt && !query_reduce_only(Q) && cs) {
         const uint8_t* t = s + pos;

@@ -23,6 +23,9 @@ constexpr int kCplSet[] = {1, 2, 3, 4, 5, 6, 8};
 
 hipError_t launch_decode_w8(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t launch_decode_w16(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+// gather rows (Q = kQueryGather, decode_gather.hip): the generic kernel, both layouts; decode_fast for rows of whole 16-byte pieces
+hipError_t launch_decode_gather(int w, bool fire, bool lowdim, int cpl, unsigned grid, hipStream_t st, const DecodeArgs& a);
+hipError_t launch_decode_fast_gather(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h)
 // (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
 hipError_t launch_decode_fast_w8(bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
@@ -165,6 +168,16 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
     if (q == kQueryMaterialize) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryMaterialize, false) } \
     if (q == kQueryReduceOnly) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryReduceOnly, false) } \
     if (q == kQueryWindow) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryWindow, false) }         \
+    return hipErrorInvalidValue;
+
+// gather (kQueryGather): row-major destination, rows of whole 16-byte pieces -- 16 columns and more (8 columns of 16 bits: decode_gather.hip)
+#define SPRINTZ_DISPATCH_DECODE_FAST_GATHER(KERNEL, W)                                                \
+    if (a.col_stride) return hipErrorInvalidValue;                                                    \
+    SPRINTZ_FAST_CASE(KERNEL, W, 16, 1, kQueryGather, false)                                          \
+    SPRINTZ_FAST_CASE(KERNEL, W, 32, 1, kQueryGather, false)                                          \
+    SPRINTZ_FAST_CASE(KERNEL, W, 64, 1, kQueryGather, false)                                          \
+    SPRINTZ_FAST_CASE(KERNEL, W, 64, 2, kQueryGather, false)                                          \
+    SPRINTZ_FAST_CASE(KERNEL, W, 64, 4, kQueryGather, false)                                          \
     return hipErrorInvalidValue;
 
 #define SPRINTZ_ENC_FAST_CASE(KERNEL, W, DPV, CMV)                                                   \
