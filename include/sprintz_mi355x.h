@@ -49,7 +49,8 @@ extern "C" {
  *   5  round 4: SPRINTZ_OPT_HOST_WAIT, SPRINTZ_OPT_LAT_CHUNKS, SPRINTZ_OPT_HOST_STREAMS, SPRINTZ_OPT_REF_DECODER_QUIRK (the single-call entry points work on a mapped staging buffer: one wait per call)
  *   6  round 5: huf0_decompress_batch_hint, SPRINTZ_OPT_HUF0_SYNC_CHUNKS, SPRINTZ_MI355X_MAX_NDIMS 65535
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
- *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM */
+ *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
+ *      dispatch_counts / dispatch_name, SPRINTZ_KF_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -146,6 +147,68 @@ const char* sprintz_mi355x_last_error(void);     /* thread-local, never NULL; de
 #define SPRINTZ_OPT_BLK_CHUNKS 11
 #define SPRINTZ_OPT_BLK_KERNELS 12
 int sprintz_mi355x_set_option(int option, int value);
+
+/* Which kernel family served a call (per process, atomic).  Every family writes the same bytes as every other, so the output of a call
+ * cannot tell which one ran; these counters can.  A family is one of the alternatives a launch site chooses between: by shape,
+ * alignment, batch size and the knobs above.  A family's counter goes up by one behind each launch of it that the runtime accepted;
+ * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
+ * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
+ * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, the column-major form):
+ *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
+ *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
+ *     DEC_GENERIC (decode_kernel.h)
+ *   gather_rows: GATHER_FAST (decode_fast.h)  GATHER_GENERIC (decode_kernel.h)
+ *   compress_batch, compress_batch_dense and every call that encodes through them:
+ *     ENC_BIG  ENC_ANY  ENC_LAT (encode_lat.h)  ENC_BLK / ENC_BLK_UNI (encode_blk.h: general layout / univariate)
+ *     ENC_PAIR / ENC_WIDE / ENC_SPLIT (encode_wide.h: 5 .. 64 columns, two a lane / 65 .. 128 columns / 8 bits, 65 .. 80 columns)
+ *     ENC_FAST (encode_fast.h)  ENC_UNI (encode_uni.h)  ENC_GENERIC (encode_kernel.h)
+ *   how a dense container was built: DENSE_FUSED (inside the encode launch, csrc/compact_tail.h; counted with the encoder's family)
+ *     DENSE_VERBATIM (chunks shorter than a group: one copy kernel, no encoder)  DENSE_COMPACT (sprintz_mi355x_compact's scan + copy
+ *     passes, whether compress_batch_dense or the caller started them)
+ *   transform_decode*: TR_CHAIN (one pass, chained scan)  TR_WAVE (wave scans: two passes over the stream, one where it is a single
+ *     run)  TR_LEVELS (the generic levels alone)
+ *   online_unpack* of the dynamic-delta kinds: ON_CHAIN (one pass)  ON_THREE (tile, scan, decode: three launches)
+ *   the Huff0 reader's stream stage: HUF0_BIG (SPRINTZ_OPT_HUF0_BIG_BATCH)  HUF0_SYNC (SPRINTZ_OPT_HUF0_SYNC_CHUNKS)  HUF0_DEFAULT
+ * sprintz_mi355x_dispatch_counts writes the first min(capacity, SPRINTZ_KF_COUNT) counters to counts[] (which may be NULL where capacity
+ * <= 0) and returns SPRINTZ_KF_COUNT; sprintz_mi355x_dispatch_name returns a family's short lower-case name ("dec_row"), NULL out of range.
+ * New families are appended: the numbers below do not change. */
+#define SPRINTZ_KF_DEC_BIG 0
+#define SPRINTZ_KF_DEC_ANY 1
+#define SPRINTZ_KF_DEC_VERBATIM 2
+#define SPRINTZ_KF_DEC_LAT 3
+#define SPRINTZ_KF_DEC_ROW 4
+#define SPRINTZ_KF_DEC_BLK 5
+#define SPRINTZ_KF_DEC_FAST 6
+#define SPRINTZ_KF_DEC_UNI 7
+#define SPRINTZ_KF_DEC_GENERIC 8
+#define SPRINTZ_KF_GATHER_FAST 9
+#define SPRINTZ_KF_GATHER_GENERIC 10
+#define SPRINTZ_KF_ENC_BIG 11
+#define SPRINTZ_KF_ENC_ANY 12
+#define SPRINTZ_KF_ENC_LAT 13
+#define SPRINTZ_KF_ENC_BLK 14
+#define SPRINTZ_KF_ENC_BLK_UNI 15
+#define SPRINTZ_KF_ENC_PAIR 16
+#define SPRINTZ_KF_ENC_FAST 17
+#define SPRINTZ_KF_ENC_WIDE 18
+#define SPRINTZ_KF_ENC_SPLIT 19
+#define SPRINTZ_KF_ENC_UNI 20
+#define SPRINTZ_KF_ENC_GENERIC 21
+#define SPRINTZ_KF_DENSE_FUSED 22
+#define SPRINTZ_KF_DENSE_VERBATIM 23
+#define SPRINTZ_KF_DENSE_COMPACT 24
+#define SPRINTZ_KF_TR_CHAIN 25
+#define SPRINTZ_KF_TR_WAVE 26
+#define SPRINTZ_KF_TR_LEVELS 27
+#define SPRINTZ_KF_ON_CHAIN 28
+#define SPRINTZ_KF_ON_THREE 29
+#define SPRINTZ_KF_HUF0_BIG 30
+#define SPRINTZ_KF_HUF0_SYNC 31
+#define SPRINTZ_KF_HUF0_DEFAULT 32
+#define SPRINTZ_KF_COUNT 33
+int         sprintz_mi355x_dispatch_counts(uint64_t* counts, int capacity);
+const char* sprintz_mi355x_dispatch_name(int family);
 
 /* ------------------------------------------------------------------------
  * (1) Drop-in single-call API (host pointers).  Replaces, one to one:
@@ -421,6 +484,10 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
  * other range is exact.  Damage that lies AFTER the last needed row of a chunk may go unnoticed: this call is no integrity
  * check of the container.  When d_rets is given, a small fill kernel runs in front of the decode launch.
  * The container must be laid out as this library writes it (offsets[c+1] - offsets[c] <= compress_bound + alignment).
+ * Limit of the fast path (csrc/decode_fast.h; rows of whole 16-byte pieces, a 16-byte aligned d_out): it addresses the container
+ * with 32-bit offsets from d_comp.  A stream that ends at d_offsets[c + 1] > 0xfffffff0 - 4096 -- a sub-range of a container larger
+ * than 4 GiB addressed from that container's base -- makes every range that touches it SPRINTZ_E_CORRUPT there.  Pass d_comp + base
+ * and offsets relative to it instead.  (decompress_batch has no such limit.)
  * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0 (rows must not straddle chunks),
  * rows == 0, chunk_len outside 1..2^30, a NULL d_comp / d_offsets / d_out, a NULL d_starts with nranges > 0, d_out not
  * aligned to the element size, d_starts / d_rets not aligned to 8 bytes; SPRINTZ_E_UNSUPPORTED for more than 512 columns and

@@ -59,6 +59,20 @@ _last_error = _sig("sprintz_mi355x_last_error", C.c_char_p)
 OPT_NO_FAST, OPT_CHUNKS_PER_GROUP, OPT_DENSE_MODE, OPT_HUF0_BIG_BATCH, OPT_SPLIT_LANES, OPT_ENC_PAIR, OPT_HOST_WAIT, OPT_LAT_CHUNKS, OPT_HOST_STREAMS, OPT_REF_DECODER_QUIRK, OPT_HUF0_SYNC_CHUNKS, OPT_BLK_CHUNKS, OPT_BLK_KERNELS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 set_option = _sig("sprintz_mi355x_set_option", _i, _i, _i)
 
+# which kernel family served a call: per-process counters behind every launch site (include/sprintz_mi355x.h, SPRINTZ_KF_*)
+_dispatch_counts = _sig("sprintz_mi355x_dispatch_counts", _i, C.POINTER(C.c_uint64), _i)
+_dispatch_name = _sig("sprintz_mi355x_dispatch_name", C.c_char_p, _i)
+KF_COUNT = _dispatch_counts(None, 0)
+KF_NAMES = [_dispatch_name(k).decode("ascii") for k in range(KF_COUNT)]
+
+
+def dispatch_counts():
+    """-> {family name: launches of that kernel family by this process so far}; never reset: compare two readings"""
+    buf = (C.c_uint64 * KF_COUNT)()
+    _dispatch_counts(buf, KF_COUNT)
+    return dict(zip(KF_NAMES, (int(v) for v in buf)))
+
+
 # (1) drop-in single-call API, host pointers
 compress = {
     ("delta", 1): _sig("sprintz_mi355x_compress_delta_8b", _i64, _vp, _u32, _vp, _u16, _i),
@@ -161,6 +175,7 @@ decompress_chunked_host = _sig("sprintz_mi355x_decompress_chunked_host", _i64, _
 
 EXPORTED_SYMBOLS = [
     "sprintz_mi355x_abi_version", "sprintz_mi355x_last_error", "sprintz_mi355x_set_option",
+    "sprintz_mi355x_dispatch_counts", "sprintz_mi355x_dispatch_name",
     "sprintz_mi355x_compress_delta_8b", "sprintz_mi355x_compress_xff_8b",
     "sprintz_mi355x_compress_delta_16b", "sprintz_mi355x_compress_xff_16b",
     "sprintz_mi355x_decompress_delta_8b", "sprintz_mi355x_decompress_xff_8b",

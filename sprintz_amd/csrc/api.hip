@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "launch.h"
+#include "dispatch.h"
 #include "encode_blk.h"
 #include "decode_blk.h"
 #include "decode_row.h"
@@ -316,6 +317,7 @@ __global__ void __launch_bounds__(kThreads) verbatim_decode_kernel(const uint8_t
 }  // namespace
 
 namespace sprintz {
+std::atomic<uint64_t> g_dispatch_counts[SPRINTZ_KF_COUNT];      // dispatch.h: which kernel family served a call
 int set_error(int code, const char* what) { return fail(code, what); }
 // exclusive scan of (aligned) u32 sizes into u64 offsets[n+1]; tmp = sprintz_mi355x_compact_tmp_bytes(n)
 hipError_t launch_size_scan(const uint32_t* d_sizes, uint64_t n, uint32_t align, uint64_t* d_offsets, void* d_tmp, hipStream_t st)
@@ -414,6 +416,9 @@ struct QuerySpec {
 bool lat_chunk_fits(bool encode, int esz, uint64_t nchunks, uint32_t chunk_len, int D)
 {
     const uint64_t bytes = (uint64_t)chunk_len * esz;
+    // (the 48 KB term never decides: both kernels keep 4 bytes an element of working set next to the stream -- 96 KB for 48 KB of uint16, 192 KB
+    //  for uint8 -- so the 150 KB carve below refuses a chunk long before it: uint16 x 8 from 45 696 bytes on to decode, from 33 104 to encode
+    //  (tests/test_gpu_dispatch.py pins both sides).  It stays as the bound that keeps the 32-bit arithmetic of the carves far from a wrap)
     if (bytes > (48u << 10) || (bytes > kLatMaxChunkBytes && nchunks > 64)) return false;
     // the carve and the 16-bit position limit are checked for EVERY size: a shape whose working set does not fit goes to the
     // lane-per-column kernels instead of failing its launch
@@ -496,10 +501,12 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
             const hipError_t eb = launch_decode_big(8 * esz, fire, (unsigned)nchunks, st, a, counters);
             if (counters) (void)hipFreeAsync(counters, st);
             if (eb != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_big kernel launch", eb);
+            dispatched(SPRINTZ_KF_DEC_BIG);
             return 0;
         }
         const hipError_t ea = launch_decode_any(8 * esz, codec == SPRINTZ_CODEC_XFF, (unsigned)nchunks, st, a);
         if (ea != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_any kernel launch", ea);
+        dispatched(SPRINTZ_KF_DEC_ANY);
         return 0;
     }
 
@@ -513,6 +520,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
         hipLaunchKernelGGL(verbatim_decode_kernel, dim3((unsigned)vgrid), dim3(kThreads), 0, st, (const uint8_t*)d_comp, d_offsets, nchunks, chunk_len,
                            (uint32_t)esz, (uint32_t)D, (uint8_t*)d_out, d_rets);
         HIP_TRY(hipGetLastError());
+        dispatched(SPRINTZ_KF_DEC_VERBATIM);
         return 0;
     }
 
@@ -561,6 +569,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
         if (esz == 1 && ldp < 8 && !lowdim) ldp = 8;
         e = launch_decode_lat(8 * esz, codec == SPRINTZ_CODEC_XFF, ldp, lowdim, (unsigned)nchunks, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims), st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_lat kernel launch", e);
+        dispatched(SPRINTZ_KF_DEC_LAT);
         return 0;
     }
     // large batches of the DELTA codec, general layout, rows of whole dwords: a lane per dword-wide column group, blocks in order (decode_row.h)
@@ -574,13 +583,15 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
             // (4 lanes a chunk) 0.233 against 0.182, and 16-bit elements -- two fields a dword carry the same per-row work as four -- 8 / 16 / 24 / 128 columns 0.129 /
             // 0.103 / 0.171 / 0.186 against 0.114 / 0.096 / 0.136 / 0.132 (32 and 64 columns level).  Mask bit 4 takes every shape the kernel fits (tests).
             const bool wins = (esz == 1 && g.U >= 8u) || (process().blk_kernels.load(std::memory_order_relaxed) & 16);
-            // (32-bit offsets inside the kernel: the output and -- whatever the streams' lengths -- the container below 4 GB)
-            const bool below_4g = (uint64_t)nchunks * chunk_len * esz < 0xf0000000ull && (uint64_t)nchunks * sprintz_mi355x_compress_bound(esz, chunk_len, ndims) < 0xf0000000ull;
+            // (32-bit offsets into the OUTPUT inside the kernel: a batch that decodes to 4 GB or more goes to the kernels below.  The container may lie
+            //  anywhere -- d_offsets are the caller's, and a stream's base is a 64-bit address there)
+            const bool below_4g = (uint64_t)nchunks * chunk_len * esz < 0xf0000000ull;
             if (g.ok && below_4g && wins) {
                 const uint64_t rgrid = (nchunks + 4ull * g.G - 1) / (4ull * g.G);
                 if (rgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
                 e = launch_decode_row(8 * esz, (unsigned)rgrid, st, a, g);
                 if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_row kernel launch", e);
+                dispatched(SPRINTZ_KF_DEC_ROW);
                 return 0;
             }
         }
@@ -596,6 +607,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
                 if (bgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
                 e = launch_decode_blk(8 * esz, (unsigned)bgrid, st, a, g);
                 if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_blk kernel launch", e);
+                dispatched(SPRINTZ_KF_DEC_BLK);
                 return 0;
             }
         }
@@ -618,6 +630,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
         e = esz == 1 ? launch_decode_fast_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, fcpl, D == fdp * fcpl, qs.q, fds, (unsigned)fgrid, fstride * fgroups, st, a)
                      : launch_decode_fast_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, fcpl, D == fdp * fcpl, qs.q, fds, (unsigned)fgrid, fstride * fgroups, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_fast kernel launch", e);
+        dispatched(SPRINTZ_KF_DEC_FAST);
         return 0;
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
@@ -628,6 +641,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
         e = esz == 1 ? launch_decode_uni_w8(codec == SPRINTZ_CODEC_XFF, D, qs.q, (unsigned)ugrid, st, a)
                      : launch_decode_uni_w16(codec == SPRINTZ_CODEC_XFF, D, qs.q, (unsigned)ugrid, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_uni kernel launch", e);
+        dispatched(SPRINTZ_KF_DEC_UNI);
         return 0;
     }
     const uint64_t threads = nchunks * (uint64_t)DP;
@@ -636,6 +650,7 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
     e = esz == 1 ? launch_decode_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, qs.q, (unsigned)grid, shmem, st, a)
                  : launch_decode_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, qs.q, (unsigned)grid, shmem, st, a);
     if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode kernel launch", e);
+    dispatched(SPRINTZ_KF_DEC_GENERIC);
     return 0;
 }
 
@@ -702,11 +717,13 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
             const hipError_t eb = launch_encode_big(8 * esz, fire, (unsigned)nchunks, st, a, counters);
             if (counters) (void)hipFreeAsync(counters, st);
             if (eb != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_big kernel launch", eb);
+            dispatched(SPRINTZ_KF_ENC_BIG);
             return 0;
         }
         a.cap = ((uint32_t)group_bytes_max(esz, D) + 64u + 15u) & ~15u;
         const hipError_t ea = launch_encode_any(8 * esz, codec == SPRINTZ_CODEC_XFF, (unsigned)nchunks, a.cap, st, a);
         if (ea != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_any kernel launch", ea);
+        dispatched(SPRINTZ_KF_ENC_ANY);
         return 0;
     }
     // the generic kernel's window is a power-of-two RING flushed in 16-byte pieces; the kernels that flush whole 128-byte lines
@@ -734,6 +751,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
         if (esz == 1 && ldp < 8 && !lowdim) ldp = 8;
         e = launch_encode_lat(8 * esz, codec == SPRINTZ_CODEC_XFF, ldp, lowdim, (unsigned)nchunks, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims), st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_lat kernel launch", e);
+        dispatched(SPRINTZ_KF_ENC_LAT);
         return 0;
     }
     // large batches of the DELTA codec, general layout, rows of whole 16-byte pieces: the block-parallel encoder (encode_blk.h) -- a thread
@@ -761,6 +779,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
                 if (bgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
                 e = launch_encode_blk(8 * esz, (unsigned)bgrid, st, a, g);
                 if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_blk kernel launch", e);
+                dispatched(SPRINTZ_KF_ENC_BLK);
                 return 0;
             }
         }
@@ -773,6 +792,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
                 if (bgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
                 e = launch_encode_blk_uni(8 * esz, (unsigned)bgrid, st, a, g);
                 if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_blk_uni kernel launch", e);
+                dispatched(SPRINTZ_KF_ENC_BLK_UNI);
                 return 0;
             }
         }
@@ -820,6 +840,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
         e = esz == 1 ? launch_encode_pair_w8(pfire, pdp, D == 2 * pdp, (unsigned)pgrid, (size_t)a.lds_group_stride * pgroups + lds_pad, st, a)
                      : launch_encode_pair_w16(pfire, pdp, D == 2 * pdp, (unsigned)pgrid, (size_t)a.lds_group_stride * pgroups + lds_pad, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_wide (pair) kernel launch", e);
+        dispatched(SPRINTZ_KF_ENC_PAIR);
         return 0;
     }
     if (fast) {
@@ -836,6 +857,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
         e = esz == 1 ? launch_encode_fast_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, D == fdp, (unsigned)fgrid, fshmem, st, a)
                      : launch_encode_fast_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, D == fdp, (unsigned)fgrid, fshmem, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_fast kernel launch", e);
+        dispatched(SPRINTZ_KF_ENC_FAST);
         return 0;
     }
     // streams of 65 .. 128 columns (BASELINE config 3): two columns per lane (encode_wide.h)
@@ -854,6 +876,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
           : esz == 1 ? launch_encode_wide_w8(wfire, D == 128, (unsigned)wgrid, (size_t)a.lds_group_stride * wgroups, st, a)
                      : launch_encode_wide_w16(wfire, D == 128, (unsigned)wgrid, (size_t)a.lds_group_stride * wgroups, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_wide kernel launch", e);
+        dispatched(wsplit ? SPRINTZ_KF_ENC_SPLIT : SPRINTZ_KF_ENC_WIDE);
         return 0;
     }
     // univariate streams: one lane per chunk, quad-loaded 64-byte input windows, 64-byte output units (encode_uni.h)
@@ -867,6 +890,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
         e = esz == 1 ? launch_encode_uni_w8(codec == SPRINTZ_CODEC_XFF, D, (unsigned)ugrid, st, a)
                      : launch_encode_uni_w16(codec == SPRINTZ_CODEC_XFF, D, (unsigned)ugrid, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_uni kernel launch", e);
+        dispatched(SPRINTZ_KF_ENC_UNI);
         return 0;
     }
     const uint64_t threads = nchunks * (uint64_t)DP;
@@ -875,6 +899,7 @@ int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uin
     e = esz == 1 ? launch_encode_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, (unsigned)grid, shmem, st, a)
                  : launch_encode_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, (unsigned)grid, shmem, st, a);
     if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode kernel launch", e);
+    dispatched(SPRINTZ_KF_ENC_GENERIC);
     return 0;
 }
 
@@ -1594,6 +1619,22 @@ int sprintz_mi355x_set_option(int option, int value)
 }
 const char* sprintz_mi355x_last_error(void) { return g_last_error.c_str(); }
 
+int sprintz_mi355x_dispatch_counts(uint64_t* counts, int capacity)
+{
+    for (int k = 0; counts && k < capacity && k < SPRINTZ_KF_COUNT; k++) counts[k] = sprintz::g_dispatch_counts[k].load(std::memory_order_relaxed);
+    return SPRINTZ_KF_COUNT;
+}
+const char* sprintz_mi355x_dispatch_name(int family)
+{
+    static const char* const names[] = {"dec_big", "dec_any", "dec_verbatim", "dec_lat", "dec_row", "dec_blk", "dec_fast", "dec_uni", "dec_generic",
+                                        "gather_fast", "gather_generic",
+                                        "enc_big", "enc_any", "enc_lat", "enc_blk", "enc_blk_uni", "enc_pair", "enc_fast", "enc_wide", "enc_split", "enc_uni", "enc_generic",
+                                        "dense_fused", "dense_verbatim", "dense_compact",
+                                        "tr_chain", "tr_wave", "tr_levels", "on_chain", "on_three", "huf0_big", "huf0_sync", "huf0_default"};
+    static_assert(sizeof(names) / sizeof(names[0]) == SPRINTZ_KF_COUNT, "a name per SPRINTZ_KF_* family");
+    return family >= 0 && family < SPRINTZ_KF_COUNT ? names[family] : nullptr;
+}
+
 size_t sprintz_mi355x_compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)
 {
     const size_t esz = (size_t)elem_bytes, D = ndims ? ndims : 1;
@@ -1667,6 +1708,7 @@ int sprintz_mi355x_compress_batch_dense(int codec, int elem_bytes, const void* d
         hipLaunchKernelGGL(verbatim_dense_kernel, dim3((unsigned)grid), dim3(kThreads), 0, st, (const uint8_t*)d_src, total_len, chunk_len,
                            (uint32_t)elem_bytes, (uint32_t)ndims, nchunks, (uint8_t*)d_dense, d_offsets, d_sizes, d_rets);
         HIP_TRY(hipGetLastError());
+        dispatched(SPRINTZ_KF_DENSE_VERBATIM);
         return 0;
     }
     DenseRequest dr;
@@ -1674,6 +1716,7 @@ int sprintz_mi355x_compress_batch_dense(int codec, int elem_bytes, const void* d
     dr.d_offsets = d_offsets;
     dr.d_tmp = d_tmp;
     rc = encode_launch(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, 1, 0, 0, mode ? &dr : nullptr);
+    if (!rc && dr.fused) dispatched(SPRINTZ_KF_DENSE_FUSED);
     if (rc || dr.fused) return rc;
     // shapes whose encoder has no dense tail (low-dim, more than 64 columns, misaligned blocks): the two-launch path
     return sprintz_mi355x_compact(d_slots, slot_stride, d_sizes, nchunks, 16, d_dense, d_offsets, d_tmp, hip_stream);
@@ -1710,6 +1753,7 @@ int sprintz_mi355x_compact(const void* d_slots, size_t slot_stride, const uint32
                            (uint64_t)slot_stride, d_sizes, d_offsets, nchunks, align, (uint8_t*)d_dense);
     }
     HIP_TRY(hipGetLastError());
+    dispatched(SPRINTZ_KF_DENSE_COMPACT);
     return 0;
 }
 
@@ -1948,12 +1992,14 @@ int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, co
         if (fgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
         e = launch_decode_fast_gather(8 * esz, fire, fdp, fcpl, D == fdp * fcpl, (unsigned)fgrid, fstride * fgroups, st, a);
         if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_fast gather kernel launch", e);
+        dispatched(SPRINTZ_KF_GATHER_FAST);
         return 0;
     }
     const uint64_t grid = ((slots << m.log2DP) + kThreads - 1) / kThreads;
     if (grid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
     e = launch_decode_gather(8 * esz, fire, lowdim, m.cpl, (unsigned)grid, st, a);
     if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode gather kernel launch", e);
+    dispatched(SPRINTZ_KF_GATHER_GENERIC);
     return 0;
 }
 
@@ -2041,6 +2087,7 @@ int sprintz_mi355x_compress_batch_colmajor_dense(int codec, int elem_bytes, cons
     dr.d_tmp = d_tmp;
     rc = encode_launch(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, 1, col_stride, 0,
                        process().dense_mode.load(std::memory_order_relaxed) ? &dr : nullptr);
+    if (!rc && dr.fused) dispatched(SPRINTZ_KF_DENSE_FUSED);
     if (rc || dr.fused) return rc;
     return sprintz_mi355x_compact(d_slots, slot_stride, d_sizes, nchunks, 16, d_dense, d_offsets, d_tmp, hip_stream);
 }

@@ -14,7 +14,8 @@
 //     L1: a chunk's lanes read one contiguous stream front to back), all eight rows of a block in flight together.
 // 64 / U chunks a wavefront (cfg3: 20 lanes a chunk, 3 chunks a wave); ~60 registers: the waves that hide the loads' latency fit.
 // (A first form with 16 columns a lane -- 5 lanes a chunk -- had a quarter of the waves and 142 registers: 0.337 ms on cfg3, latency-bound.)
-// Shapes (api.hip): delta codec, general layout, rows of whole dwords, U <= 64, 4-byte aligned container and output, any chunk length.
+// Shapes (api.hip): delta codec, general layout, rows of whole dwords, U <= 64, 4-byte aligned container and output, any chunk length that holds
+// a group, an output below 4 GB.  The container may be of any size and the streams anywhere in it: a chunk's stream base is a 64-bit address.
 #pragma once
 
 #include "decode_fast.h"
@@ -42,10 +43,10 @@ inline RowDecGeom row_dec_geom(uint32_t esz, uint32_t chunk_len, uint32_t D)
     return g;
 }
 
-// An 8-byte window at bit address `bit` of the byte stream that starts `off` bytes into the 4-byte aligned container `comp` (global memory):
-// one aligned 8-byte load; v_alignbit by sh gives the 32 bits at `bit`.  Offsets are 32-bit (the launch checks that the container and the
-// output are below 4 GB): the address is the kernel's uniform pointer + a 32-bit lane offset -- the loads stay GLOBAL loads of the
-// scalar-base form, and a row's address is two vector instructions.
+// An 8-byte window at bit address `bit` of the byte stream that starts `off` bytes behind the 4-byte aligned address `comp` (global memory):
+// one aligned 8-byte load; v_alignbit by sh gives the 32 bits at `bit`.  `comp` is the CHUNK's base -- the container's address + the stream's
+// 64-bit offset rounded down to a dword, so `off` is 0 .. 3 -- and everything inside a stream is a 32-bit offset from it (a stream is clamped
+// to 256 MB below): d_offsets are the caller's and may point anywhere, e.g. past 4 GiB of a large container addressed from its base.
 struct Win2 { uint32_t lo, hi; };
 __device__ __forceinline__ Win2 gwin_load(const uint8_t* comp, uint32_t off, uint32_t bit)
 {
@@ -63,8 +64,10 @@ __device__ __forceinline__ uint32_t gbits32(const uint8_t* comp, uint32_t off, u
     return __builtin_amdgcn_alignbit(w.hi, w.lo, gwin_shift(off, bit));
 }
 
+// (four waves a SIMD are what hides the loads' latency: the 64-bit stream bases cost the allocator 130 registers where 121 did before, one wave
+//  less -- asked to fit four waves it takes 124, nothing spilled)
 template <int W>
-__global__ void __launch_bounds__(256) decode_row_kernel(DecodeArgs a, RowDecGeom g)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) decode_row_kernel(DecodeArgs a, RowDecGeom g)
 {
     constexpr int HB = Elem<W>::HB;
     constexpr int ESZ = W / 8;
@@ -83,17 +86,17 @@ __global__ void __launch_bounds__(256) decode_row_kernel(DecodeArgs a, RowDecGeo
     const uint64_t off64 = exists ? a.offsets[chunk] : 0ull;
     const uint64_t slen64 = exists ? a.offsets[chunk + 1] - off64 : 0ull;
     const uint32_t slen = slen64 < 0x0fffffffull ? (uint32_t)slen64 : 0x0fffffffu;
-    const uint32_t off = (uint32_t)off64;        // (the launch checked: the whole container is below 4 GB)
-    const uint8_t* const s = a.comp + off;
+    const uint8_t* const cbase = a.comp + (off64 & ~3ull);       // my chunk's base: a 64-bit address, 4-byte aligned like the container
+    const uint32_t off = (uint32_t)off64 & 3u;
+    const uint8_t* const s = cbase + off;
     uint8_t* const out8 = (uint8_t*)a.out;
     const uint32_t o = (uint32_t)chunk * a.chunk_len * ESZ + u * 4u;      // byte offset of my dword of the chunk's first row (the output is below 4 GB too)
 
     // ---- 8-byte stream header (format.h:48-62)
-    // (offsets are the caller's data: a stream that does not lie inside the first 4 GB of the container is never touched)
-    bool corrupt = !exists || slen < 8u || off64 + slen64 >= 0xfffffff0ull;
+    bool corrupt = !exists || slen < 8u;
     uint32_t groups_left = 0, remaining = 0;
     if (!corrupt) {
-        const uint32_t w0 = gbits32(a.comp, off, 0), w1 = gbits32(a.comp, off, 32);
+        const uint32_t w0 = gbits32(cbase, off, 0), w1 = gbits32(cbase, off, 32);
         groups_left = w0;
         remaining = w1 & 0xffffu;
         // a damaged header must not make the loop spin: every group of a valid stream holds at least one non-empty slot, except the last
@@ -118,7 +121,7 @@ __global__ void __launch_bounds__(256) decode_row_kernel(DecodeArgs a, RowDecGeo
         const uint32_t cap4 = (R + 3u) & ~3u, mine4 = 4u * u < cap4 ? 4u * u : cap4;
 #pragma unroll
         for (int r = 0; r < 8; r++) {
-            const uint32_t* q = (const uint32_t*)(a.comp + ((A & ~3u) + mine4));
+            const uint32_t* q = (const uint32_t*)(cbase + ((A & ~3u) + mine4));
             raw[r].lo = q[0];
             raw[r].hi = q[1];
             phases |= (A & 3u) << (2 * r);                               // the rows' byte phases, two bits each
@@ -203,8 +206,8 @@ __global__ void __launch_bounds__(256) decode_row_kernel(DecodeArgs a, RowDecGeo
         const uint32_t hb0 = hpos * 8u + u * (uint32_t)(FPD * HB), hb1 = hb0 + D * HB;
         Win2 h0 = pre0, h1 = pre1;
         if (act && !bad && pre_pos != hpos) {
-            h0 = gwin_load(a.comp, off, hb0);
-            h1 = gwin_load(a.comp, off, hb1);
+            h0 = gwin_load(cbase, off, hb0);
+            h1 = gwin_load(cbase, off, hb1);
         }
         uint32_t hf[2] = {0u, 0u};
         if (act && !bad) {
@@ -245,8 +248,8 @@ __global__ void __launch_bounds__(256) decode_row_kernel(DecodeArgs a, RowDecGeo
                 load_rows(wa, pa, c0, pay0 >> 3);
                 load_rows(wb, pb, c1, pay1 >> 3);
                 if (groups_left > 1u && hdr_bytes <= slen - npos) {
-                    pre0 = gwin_load(a.comp, off, npos * 8u + u * (uint32_t)(FPD * HB));
-                    pre1 = gwin_load(a.comp, off, npos * 8u + u * (uint32_t)(FPD * HB) + D * HB);
+                    pre0 = gwin_load(cbase, off, npos * 8u + u * (uint32_t)(FPD * HB));
+                    pre1 = gwin_load(cbase, off, npos * 8u + u * (uint32_t)(FPD * HB) + D * HB);
                     pre_pos = npos;
                 }
                 const uint32_t ob = o + out_blocks * blk * ESZ;
@@ -310,7 +313,7 @@ __global__ void __launch_bounds__(256) decode_row_kernel(DecodeArgs a, RowDecGeo
         if (!corrupt) {
             const uint32_t tb = remaining * ESZ;
             uint8_t* const d = out8 + ((uint32_t)chunk * a.chunk_len + out_blocks * blk) * ESZ;
-            for (uint32_t i = u; i < tb >> 2; i += g.U) *(uint32_t*)(d + 4u * i) = gbits32(a.comp, off + pos, 32u * i);
+            for (uint32_t i = u; i < tb >> 2; i += g.U) *(uint32_t*)(d + 4u * i) = gbits32(cbase, off + pos, 32u * i);
             if (u == 0) for (uint32_t i = tb & ~3u; i < tb; i++) d[i] = s[pos + i];
         }
         if (u == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_blocks * blk + remaining;

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lds_attr.h"
+#include "dispatch.h"
 
 #include <cstdlib>
 #include <string>
@@ -1883,7 +1884,9 @@ int sprintz_mi355x_huf0_decompress_batch_hint(const void* d_blocks, const uint64
     }
     // the one-table kernel: bandwidth-sized batches as workgroups of HUF0_BIG_WG waves with 2^HUF0_BIG_PLOG-byte stream pieces (built: 2 waves, 64 bytes),
     // then the per-chunk-table kernel for the segments that are not its; small batches: both wave by wave in one launch
+    int family = SPRINTZ_KF_HUF0_DEFAULT;
     if (nchunks >= (uint64_t)sprintz::huf0_big_batch().load(std::memory_order_relaxed)) {
+        family = SPRINTZ_KF_HUF0_BIG;
         hipLaunchKernelGGL((huf0_stream_kernel<true, HUF0_BIG_WG, HUF0_BIG_PLOG, HUF0_CADENCED != 0, HUF0_BIG_NS, HUF0_BIG_UA != 0, HUF0_BIG_QW != 0>), dim3((unsigned)((nchunks + 16 * HUF0_BIG_WG - 1) / (16 * HUF0_BIG_WG))),
                            dim3(64 * HUF0_BIG_WG), 0, st, blk, d_block_offsets, nchunks,
                            (uint8_t*)d_out, d_out_offsets, d_rets, (const uint8_t*)desc, (const uint8_t*)share);
@@ -1894,6 +1897,7 @@ int sprintz_mi355x_huf0_decompress_batch_hint(const void* d_blocks, const uint64
         // The block image a wave keeps in LDS is sized by the caller's hint (the largest block of the batch; a block above the image is read
         // from global memory by the same code)
         constexpr int kWpb = 4;
+        family = SPRINTZ_KF_HUF0_SYNC;
         const uint32_t want = max_block_bytes ? max_block_bytes : 4096u;
         const uint32_t img = ((want < 16384u ? want : 16384u) + 16u + 63u) & ~63u;
         const size_t lds = sync_lds_bytes(kWpb, img);
@@ -1908,7 +1912,9 @@ int sprintz_mi355x_huf0_decompress_batch_hint(const void* d_blocks, const uint64
         hipLaunchKernelGGL(huf0_stream_small_kernel, dim3((unsigned)grid2), dim3(64), 0, st, blk, d_block_offsets, nchunks,
                            (uint8_t*)d_out, d_out_offsets, d_rets, (const uint8_t*)desc, (const uint8_t*)share, 0);
     }
-    return hipGetLastError() == hipSuccess ? 0 : sprintz::set_error(SPRINTZ_E_HIP, "Huff0 stage: a HIP call or kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return sprintz::set_error(SPRINTZ_E_HIP, "Huff0 stage: a HIP call or kernel launch failed");
+    sprintz::dispatched(family);
+    return 0;
 }
 
 #ifdef HUF0_TREE_TIMING

@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "launch.h"
+#include "dispatch.h"
 
 using namespace sprintz;
 
@@ -933,11 +934,15 @@ int sprintz_mi355x_online_unpack_device(int kind, const void* d_src, uint32_t le
             const uint32_t wgs = ctiles < (uint32_t)dc_resident_wgs() ? ctiles : (uint32_t)dc_resident_wgs();
             hipLaunchKernelGGL(dyndelta_chain_kernel, dim3(wgs), dim3(kDcT), 0, st, body, choices, len, nblocks, ctiles, (uint32_t*)d_tmp,
                                (uint64_t*)((uint8_t*)d_tmp + 256), d_dest, d_ret);
-            return hipGetLastError() == hipSuccess ? 0 : fail(SPRINTZ_E_HIP, "online: unpack launch");
+            if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "online: unpack launch");
+            sprintz::dispatched(SPRINTZ_KF_ON_CHAIN);
+            return 0;
         }
         hipLaunchKernelGGL(dyndelta_tile_kernel, dim3(ntiles), dim3(kT), 0, st, body, choices, nblocks, tiles);
         hipLaunchKernelGGL(dyndelta_tilescan_kernel, dim3(1), dim3(kDdScanT), 0, st, tiles, ntiles);
         hipLaunchKernelGGL(dyndelta_decode_kernel, dim3(ntiles), dim3(kT), 0, st, body, choices, len, nblocks, (const uint64_t*)tiles, d_dest, d_ret);
+        if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "online: unpack launch");
+        sprintz::dispatched(SPRINTZ_KF_ON_THREE);
     } else {
         const int zig = kind == SPRINTZ_ONLINE_PACK_ZIGZAG;
         const uint32_t nblocks = len / 8, hb = hdr_bytes_of(len), helems = (hb + 1) / 2;

@@ -23,6 +23,7 @@
 // ("replicas only") and is here so that the whole transform surface of the
 // reference exists behind one boundary.  Many independent series belong in the batched codec.
 #include "../../include/sprintz_mi355x.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -968,13 +969,17 @@ int decode_wave(const U* y, uint64_t len, uint32_t D_real, U* dest, uint8_t* tmp
             if (hipMemsetAsync(tmp, 0, need, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode: hipMemsetAsync of the tiles' words");
             const uint64_t wgs = ntiles < (uint64_t)chain_resident_wgs() ? ntiles : (uint64_t)chain_resident_wgs();
             hipLaunchKernelGGL((chain_scan_kernel<E, KIND>), dim3((unsigned)wgs), dim3(kChainT), 0, st, (const T*)y, len_e, dv, ws, (T*)dest, (uint32_t)ntiles);
-            return hipGetLastError() == hipSuccess ? 0 : fail(SPRINTZ_E_HIP, "transform decode launch");
+            if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode launch");
+            sprintz::dispatched(SPRINTZ_KF_TR_CHAIN);
+            return 0;
         }
     }
     if (nruns == 1) {
         hipLaunchKernelGGL((wave_scan_kernel<E, KIND, true>), dim3(grid), dim3(kTB), 0, st, (const T*)y, len_e, dv, nruns,
                            (const T*)nullptr, (const T*)nullptr, (T*)nullptr, (T*)nullptr, (T*)dest, run_loads);
-        return hipGetLastError() == hipSuccess ? 0 : fail(SPRINTZ_E_HIP, "transform decode launch");
+        if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode launch");
+        sprintz::dispatched(SPRINTZ_KF_TR_WAVE);
+        return 0;
     }
     // level 1 = one summary per run, laid out like rows of the stream
     uint8_t* t = tmp;
@@ -996,7 +1001,9 @@ int decode_wave(const U* y, uint64_t len, uint32_t D_real, U* dest, uint8_t* tmp
     }
     hipLaunchKernelGGL((wave_scan_kernel<E, KIND, true>), dim3(grid), dim3(kTB), 0, st, (const T*)y, len_e, dv, nruns, (const T*)xi,
                        (const T*)di, (T*)nullptr, (T*)nullptr, (T*)dest, run_loads);
-    return hipGetLastError() == hipSuccess ? 0 : fail(SPRINTZ_E_HIP, "transform decode launch");
+    if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode launch");
+    sprintz::dispatched(SPRINTZ_KF_TR_WAVE);
+    return 0;
 }
 
 template <typename U, int KIND>
@@ -1020,7 +1027,9 @@ int decode_device(const U* y, uint64_t len, uint32_t D, U* dest, uint8_t* tmp, h
         default: break;
     }
     const uint64_t rows0 = (len + D - 1) / D;
-    return scan_levels<U, KIND>(Level<U>{y, y, nullptr, nullptr, rows0, 1}, len, D, rows0, dest, tmp, st);
+    const int rc = scan_levels<U, KIND>(Level<U>{y, y, nullptr, nullptr, rows0, 1}, len, D, rows0, dest, tmp, st);
+    if (!rc) sprintz::dispatched(SPRINTZ_KF_TR_LEVELS);
+    return rc;
 }
 
 template <typename U, int KIND>

@@ -1,10 +1,16 @@
-"""GPU tests (-m gpu) of the BLOCK-PARALLEL delta kernels (csrc/encode_blk.h, decode_blk.h; SPRINTZ_OPT_BLK_CHUNKS): every
-shape family they take, batched through the C-ABI, against the oracle -- stream bytes, sizes, return values, samples.  The
-general parity modules run on these kernels too (tests/conftest.py: decode_path "blk"); here the shapes are chosen to sit
-ON the new kernels (the module asserts that the option is honoured by comparing with the lane-per-column kernels' bytes)."""
+"""GPU tests (-m gpu) of the round-6 delta kernels (csrc/encode_blk.h, decode_blk.h, decode_row.h; SPRINTZ_OPT_BLK_CHUNKS, SPRINTZ_OPT_BLK_KERNELS):
+every shape family they take, batched through the C-ABI, against the oracle -- stream bytes, sizes, return values, samples.  The general
+parity modules run with these kernels switched on too (tests/conftest.py: decode_path "blk").
+
+Equal bytes do not show which kernel wrote them -- every family writes the same, and a launch site that refuses a shape falls through to an
+older kernel without a word.  So every call here also asserts the kernel family it was served by, from the library's dispatch counters
+(tests/dispatch.py): SHAPES states, per shape and per `path`, the encoder and the decoder the shape must land on, derived from the "Shapes"
+paragraphs of the kernels' headers and the option's text in sprintz_mi355x.h -- or, where a kernel does not take the shape, `falls through:`
+and why, and then that NO round-6 family ran.  path "old" must show none of them anywhere."""
 import numpy as np
 import pytest
 
+from dispatch import OLD_DECODERS, OLD_ENCODERS, ROUND6, ran
 from harness import DTYPES, gen_walk
 
 pytestmark = pytest.mark.gpu
@@ -53,57 +59,83 @@ def make_data(kind, rng, n, ndims, esz):
     raise ValueError(kind)
 
 
+# why a shape is not on a round-6 kernel under a path that asks for it
+COLS8 = "falls through: decode_blk.h walks a group header on 16 lanes of 10 fields: 8-bit rows of at most 80 columns"
+COLS16 = "falls through: decode_blk.h walks a group header on 16 lanes of 8 fields: 16-bit rows of at most 64 columns"
+COLS8_SHORT = COLS8 + "; and chunks of at least 32 rows"
+PIECES = "falls through: encode_blk.h and decode_blk.h take rows of whole 16-byte pieces"
+LOWDIM = "falls through: the low-dim layout has no round-6 decoder (decode_uni.h)"
+MASK25 = "falls through: mask 25 leaves bit 2 (encode_blk_uni) off"
+
 SHAPES = [
-    # esz, ndims, chunk_len (elements), nchunks, ragged last chunk (elements short of a full one)
-    (1, 80, 10240, 37, 0),            # BASELINE config 3 at 10 KB
-    (1, 80, 10240, 5, 3000),
-    (1, 16, 2048, 64, 0),
-    (1, 16, 16 * 16 * 3 + 32, 19, 48),  # chunk not a whole number of blocks
-    (1, 32, 4096, 33, 0),
-    (1, 48, 48 * 40, 21, 0),
-    (1, 64, 8192, 17, 64 * 5),
-    (1, 96, 96 * 24, 13, 0),
-    (1, 128, 128 * 16, 11, 0),        # exactly one group a chunk
-    (1, 256, 256 * 16 * 2, 6, 0),
-    (2, 8, 5120, 70, 0),              # the headline shape on the delta codec
-    (2, 8, 5120, 9, 1000),
-    (2, 8, 8 * 16 * 2 + 8, 40, 0),
-    (2, 16, 4096, 21, 0),
-    (2, 24, 24 * 56, 15, 24 * 3),
-    (2, 40, 40 * 128, 9, 0),
-    (2, 64, 64 * 32, 9, 0),
-    (2, 80, 80 * 64, 7, 0),
-    (2, 128, 128 * 16, 5, 0),
+    # esz, ndims, chunk_len (elements), nchunks, ragged last chunk (elements short of a full one);
+    # then the kernel family: path "blk" (mask 7) encode, decode; path "row" (mask 25) encode, decode
+    (1, 80, 10240, 37, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),            # BASELINE config 3 at 10 KB
+    (1, 80, 10240, 5, 3000, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (1, 16, 2048, 64, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (1, 16, 16 * 16 * 3 + 32, 19, 48, "enc_blk", "dec_blk", "enc_blk", "dec_row"),  # chunk not a whole number of blocks
+    (1, 32, 4096, 33, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (1, 48, 48 * 40, 21, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (1, 64, 8192, 17, 64 * 5, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (1, 96, 96 * 24, 13, 0, "enc_blk", COLS8_SHORT, "enc_blk", "dec_row"),
+    (1, 128, 128 * 16, 11, 0, "enc_blk", COLS8_SHORT, "enc_blk", "dec_row"),        # exactly one group a chunk
+    (1, 256, 256 * 16 * 2, 6, 0, "enc_blk", COLS8, "enc_blk", "dec_row"),
+    (2, 8, 5120, 70, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),              # the headline shape on the delta codec
+    (2, 8, 5120, 9, 1000, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (2, 8, 8 * 16 * 2 + 8, 40, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (2, 16, 4096, 21, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (2, 24, 24 * 56, 15, 24 * 3, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (2, 40, 40 * 128, 9, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (2, 64, 64 * 32, 9, 0, "enc_blk", "dec_blk", "enc_blk", "dec_row"),
+    (2, 80, 80 * 64, 7, 0, "enc_blk", COLS16, "enc_blk", "dec_row"),
+    (2, 128, 128 * 16, 5, 0, "enc_blk", COLS16 + "; and chunks of at least 32 rows", "enc_blk", "dec_row"),
     # rows of whole dwords that are not whole 16-byte pieces: the column-group-sequential decoder alone (decode_row.h)
-    (1, 12, 12 * 40, 50, 0),
-    (1, 20, 20 * 64, 31, 20 * 7),
-    (1, 8, 1024, 90, 0),
-    (2, 6, 6 * 80, 41, 0),
-    (2, 10, 10 * 48, 33, 0),
-    (2, 4, 2048, 60, 0),
+    (1, 12, 12 * 40, 50, 0, PIECES, PIECES, PIECES, "dec_row"),
+    (1, 20, 20 * 64, 31, 20 * 7, PIECES, PIECES, PIECES, "dec_row"),
+    (1, 8, 1024, 90, 0, PIECES, PIECES, PIECES, "dec_row"),
+    (2, 6, 6 * 80, 41, 0, PIECES, PIECES, PIECES, "dec_row"),
+    (2, 10, 10 * 48, 33, 0, PIECES, PIECES, PIECES, "dec_row"),
+    (2, 4, 2048, 60, 0, PIECES, PIECES, PIECES, "dec_row"),
     # univariate streams of the low-dim layout (encode_blk_uni_kernel)
-    (1, 1, 1024, 300, 0),             # BASELINE config 1
-    (1, 1, 1024, 67, 500),
-    (1, 1, 4096, 40, 16),
-    (1, 1, 272, 90, 0),
-    (1, 1, 128, 90, 0),               # the shortest coded chunk
-    (1, 1, 112, 33, 0),               # below 128 elements: verbatim
-    (2, 1, 512, 150, 0),
-    (2, 1, 2048, 40, 200),
-    (2, 1, 200, 77, 0),
+    (1, 1, 1024, 300, 0, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),             # BASELINE config 1
+    (1, 1, 1024, 67, 500, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),
+    (1, 1, 4096, 40, 16, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),
+    (1, 1, 272, 90, 0, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),
+    (1, 1, 128, 90, 0, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),               # the shortest chunk that holds a group
+    (1, 1, 112, 33, 0, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),               # below 128 elements: no group, all of it the tail -- still seven 16-byte tasks of the kernel
+    (2, 1, 512, 150, 0, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),
+    (2, 1, 2048, 40, 200, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),
+    (2, 1, 200, 77, 0, "enc_blk_uni", LOWDIM, MASK25, LOWDIM),
 ]
+FAMILY = {s[:5]: {"blk": s[5:7], "row": s[7:9]} for s in SHAPES}
+assert len(FAMILY) == len(SHAPES)
+
+
+def encodes_on(path, fam):
+    """the dispatch assertion around a compress() call whose container is 16-byte aligned: the encoder, then how the container was built"""
+    if path == "old" or fam.startswith("falls through:"):
+        return ran(never=ROUND6, one_of=OLD_ENCODERS, only=OLD_ENCODERS + ("dense_fused", "dense_compact"), what=f"path {path}: {fam}")
+    return ran(only=[fam, "dense_compact"], what=f"path {path}", **{fam: 1, "dense_compact": 1})
+
+
+def decodes_on(path, fam):
+    if path == "old" or fam.startswith("falls through:"):
+        return ran(never=ROUND6, one_of=OLD_DECODERS, only=OLD_DECODERS, what=f"path {path}: {fam}")
+    return ran(only=[fam], what=f"path {path}", **{fam: 1})
 
 
 @pytest.mark.parametrize("kind", ["walk", "walk_flat", "zeros", "const_cols", "noise", "mixed"])
-@pytest.mark.parametrize("esz,ndims,chunk_len,nchunks,short", SHAPES)
+@pytest.mark.parametrize("esz,ndims,chunk_len,nchunks,short", [s[:5] for s in SHAPES])
 def test_delta_batches_match_the_oracle(sz, oracle, path, kind, esz, ndims, chunk_len, nchunks, short):
     import torch
+    enc_fam, dec_fam = FAMILY[(esz, ndims, chunk_len, nchunks, short)].get(path, ("old", "old"))
     rng = np.random.default_rng(1000 * ndims + chunk_len + esz)
     n = nchunks * chunk_len - short
     data = make_data(kind, rng, n, ndims, esz)
     cd = sz.ChunkedCodec("delta", esz, ndims, chunk_len, device="cuda:0")
     t = torch.from_numpy(data.view(np.int8 if esz == 1 else np.int16)).cuda().view(cd.dtype)
-    batch = cd.compress(t)
+    with encodes_on(path, enc_fam):
+        batch = cd.compress(t)
     sizes, offs, comp = batch.sizes.cpu().numpy(), batch.offsets.cpu().numpy(), batch.data.cpu().numpy()
     for c in range(nchunks):
         want, wret = oracle.compress("delta", data[c * chunk_len:(c + 1) * chunk_len], ndims)
@@ -114,7 +146,9 @@ def test_delta_batches_match_the_oracle(sz, oracle, path, kind, esz, ndims, chun
             raise AssertionError((path, kind, "chunk", c, "first differing stream bytes", bad[:6].tolist(), "of", want.size,
                                   got[bad[:6]].tolist(), want[bad[:6]].tolist()))
     rets = torch.empty(nchunks, dtype=torch.int64, device="cuda:0")
-    out = cd.decompress(batch, rets=rets).cpu().numpy().view(DTYPES[esz])
+    with decodes_on(path, dec_fam):
+        out = cd.decompress(batch, rets=rets)
+    out = out.cpu().numpy().view(DTYPES[esz])
     assert np.array_equal(out[:n], data), (path, kind)
     r = rets.cpu().numpy()
     assert (r[:-1] == chunk_len).all() and r[-1] == chunk_len - short, (path, kind, r[-3:])
@@ -122,20 +156,32 @@ def test_delta_batches_match_the_oracle(sz, oracle, path, kind, esz, ndims, chun
 
 @pytest.mark.parametrize("esz,ndims,chunk_len", [(1, 80, 10240), (2, 8, 5120), (1, 16, 1024), (1, 1, 1024), (2, 1, 1024)])
 def test_a_large_batch_takes_the_new_kernels_by_default(sz, oracle, esz, ndims, chunk_len):
-    """default options, more chunks than SPRINTZ_OPT_BLK_CHUNKS' default: bytes against the oracle on every chunk"""
+    """default options, more chunks than SPRINTZ_OPT_BLK_CHUNKS' default: bytes against the oracle on every chunk -- and the kernels of the
+    default mask 9 (encode_blk; decode_row where it measured faster: 8-bit rows of at least 8 dwords) where the test's name says so"""
     import torch
+    enc_fam, dec_fam = {
+        (1, 80, 10240): ("enc_blk", "dec_row"),
+        (2, 8, 5120): ("enc_blk", "dec_fast"),        # 16-bit elements: decode_row.h did not win, decode_blk.h (bit 1) is off -- the lane-per-column kernel
+        (1, 16, 1024): ("enc_blk", "dec_fast"),       # 4 dwords a row < 8: likewise
+        # bit 2 (encode_blk_uni) is off by default: the lane-per-chunk kernels of the low-dim layout (encode_uni.h, decode_uni.h)
+        (1, 1, 1024): ("enc_uni", "dec_uni"),
+        (2, 1, 1024): ("enc_uni", "dec_uni"),
+    }[(esz, ndims, chunk_len)]
     nchunks = 5000
     rng = np.random.default_rng(7)
     data = gen_walk(rng, nchunks * chunk_len, ndims, esz, 4, flat_every=5)
     cd = sz.ChunkedCodec("delta", esz, ndims, chunk_len, device="cuda:0")
     t = torch.from_numpy(data.view(np.int8 if esz == 1 else np.int16)).cuda().view(cd.dtype)
-    batch = cd.compress(t)
+    with ran(only=[enc_fam, "dense_compact"], **{enc_fam: 1, "dense_compact": 1}):
+        batch = cd.compress(t)
     sizes, offs, comp = batch.sizes.cpu().numpy(), batch.offsets.cpu().numpy(), batch.data.cpu().numpy()
     want, stride, wsizes = oracle.compress_chunks_mt("delta", data, chunk_len, ndims)
     assert np.array_equal(sizes, wsizes)
     for c in range(nchunks):
         assert np.array_equal(comp[offs[c]:offs[c] + sizes[c]], want[c * stride:c * stride + sizes[c]]), c
-    assert np.array_equal(cd.decompress(batch).cpu().numpy().view(DTYPES[esz]), data)
+    with ran(only=[dec_fam], **{dec_fam: 1}):
+        out = cd.decompress(batch)
+    assert np.array_equal(out.cpu().numpy().view(DTYPES[esz]), data)
 
 
 @pytest.mark.parametrize("esz,ndims,chunk_len,nchunks", [(1, 80, 10240, 23), (2, 8, 5120, 41), (1, 16, 2048, 50), (2, 40, 40 * 64, 17)])
@@ -147,14 +193,18 @@ def test_byte_dense_containers(sz, oracle, path, esz, ndims, chunk_len, nchunks)
     data = gen_walk(rng, nchunks * chunk_len, ndims, esz, 6, flat_every=3)
     cd = sz.ChunkedCodec("delta", esz, ndims, chunk_len, device="cuda:0", align=1)
     t = torch.from_numpy(data.view(np.int8 if esz == 1 else np.int16)).cuda().view(cd.dtype)
-    batch = cd.compress(t)
+    # (all four shapes have rows of whole 16-byte pieces, at least 32 rows a chunk and at most 80 / 64 columns: every round-6 kernel takes them)
+    with ran(never=ROUND6, one_of=OLD_ENCODERS) if path == "old" else ran(enc_blk=1, dense_compact=1, only=["enc_blk", "dense_compact"]):
+        batch = cd.compress(t)
     offs, sizes, comp = batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy(), batch.data.cpu().numpy()
     assert (np.diff(offs) == sizes).all() and (offs % 16 != 0).any()
     for c in range(nchunks):
         want, _ = oracle.compress("delta", data[c * chunk_len:(c + 1) * chunk_len], ndims)
         assert np.array_equal(comp[offs[c]:offs[c + 1]], want), (path, c)
     rets = torch.empty(nchunks, dtype=torch.int64, device="cuda:0")
-    out = cd.decompress(batch, rets=rets).cpu().numpy().view(DTYPES[esz])
+    with decodes_on(path, {"blk": "dec_blk", "row": "dec_row", "old": "old"}[path]):
+        out = cd.decompress(batch, rets=rets)
+    out = out.cpu().numpy().view(DTYPES[esz])
     assert np.array_equal(out, data), path
     assert (rets.cpu().numpy() == chunk_len).all()
 
@@ -188,7 +238,8 @@ def test_damaged_streams_stay_inside_their_chunk(sz, path, esz, ndims, chunk_len
         guard = 4096
         out = torch.full((nchunks * chunk_len + guard,), 0x5A, dtype=torch.int16 if esz == 2 else torch.int8, device="cuda:0")
         rets = torch.zeros(nchunks, dtype=torch.int64, device="cuda:0")
-        cd.decompress_into(torch.from_numpy(comp).cuda(), batch.offsets, nchunks, out, rets)
+        with decodes_on(path, {"blk": "dec_blk", "row": "dec_row", "old": "old"}[path]):          # (the shapes of the byte-dense test: every round-6 decoder takes them)
+            cd.decompress_into(torch.from_numpy(comp).cuda(), batch.offsets, nchunks, out, rets)
         torch.cuda.synchronize()
         r = rets.cpu().numpy()
         assert ((r == sz._lib.E_CORRUPT) | ((r >= 0) & (r <= chunk_len))).all(), (path, trial, r[:8])

@@ -1,6 +1,7 @@
 """GPU tests (-m gpu) of gather rows (sprintz_mi355x_gather_rows, ChunkedCodec.gather_rows / read_rows): N row ranges of a
 compressed batch decoded in one launch by the gather mode of decode_fast.h and of decode_kernel.h.  The expected samples
-are always rows of the ORIGINAL input -- decode is lossless and pinned elsewhere."""
+are always rows of the ORIGINAL input -- decode is lossless and pinned elsewhere.  Both families deliver the same rows, so wherever a
+case names its family -- `fam` (SPRINTZ_OPT_NO_FAST), a shape marked decode_fast -- the call also asserts it from the dispatch counters."""
 import ctypes as C
 import os
 import sys
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import gather_model as gm
+from dispatch import ran
 from harness import DTYPES, gen_sparse
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +42,38 @@ def no_fast():
         _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
     yield setter
     _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
+
+
+def gathers_on(fam, fast_shape=None):
+    """the dispatch assertion around ONE gather_rows call: fam 1 (SPRINTZ_OPT_NO_FAST) -> the generic kernel whatever the shape; fam 0 ->
+    decode_fast.h's gather mode where the shape is its (general layout, at most 256 columns, rows of whole 16-byte pieces, chunks of at
+    least half its ring, a 16-byte aligned output), the generic kernel where it is not; fast_shape None: the case does not say"""
+    if fam == 0 and fast_shape is None:
+        return ran(one_of=["gather_fast", "gather_generic"], only=["gather_fast", "gather_generic"])
+    k = "gather_fast" if fam == 0 and fast_shape else "gather_generic"
+    return ran(only=[k], **{k: 1})
+
+
+def fast_ring_bytes(esz, D):
+    """LDS one lane group of decode_fast.h's gather mode holds (decode_fast_lds_bytes): the read-ahead ring -- whole units of 16 bytes a lane
+    and column, at least twice the largest stream group (header + two packed blocks) and one unit more -- its apron and one block of staging.
+    The lanes: the next power of two up to 64, then 2 / 4 columns a lane."""
+    dp, cpl = 4, 1
+    while dp < D and dp < 64:
+        dp *= 2
+    while dp * cpl < D:
+        cpl *= 2
+    unit, dcap = dp * 16 * cpl, dp * cpl
+    cg = (2 * dcap * (3 if esz == 1 else 4) + 7) // 8 + 2 * 8 * dcap * esz + 4
+    ring = ((2 * (cg + 24) + 3 + unit - 1) // unit + 1) * unit
+    return ring + ((cg + 24 + 8 + 15) & ~15) + ((8 * D * esz + 15) & ~15) + 16
+
+
+def fast_shape_of(esz, D, chunk_len):
+    """the shapes sprintz_mi355x_gather_rows serves from decode_fast.h (given a 16-byte aligned output and a container below 4 GB): the general
+    layout, at most 256 columns, rows of whole 16-byte pieces, chunks of at least half the ring"""
+    lowdim = D <= 4 if esz == 1 else D <= 2
+    return not lowdim and D <= 256 and (D * esz) % 16 == 0 and 2 * chunk_len * esz >= fast_ring_bytes(esz, D)
 
 
 def rows_per_chunk(shape, D):
@@ -122,7 +156,8 @@ def test_gather_rows_parity(sz, no_fast, codec, esz, D, shape, data):
             starts = start_vector(rng, rows, R, total)
             assert starts.size >= 8
             rets = torch.full((starts.size,), -77, dtype=torch.int64, device="cuda")
-            got = cd.gather_rows(batch, starts, rows, rets=rets)
+            with gathers_on(fam, fast_shape_of(esz, D, R * D)):
+                got = cd.gather_rows(batch, starts, rows, rets=rets)
             want, ok = gm.expected(x, starts, rows)
             assert ok.all()
             assert got.shape == (starts.size, rows, D) and got.dtype == cd.dtype
@@ -151,7 +186,8 @@ def test_gather_rows_fast_mappings(sz, no_fast, codec, esz, D):
         no_fast(fam)
         for rows in (1, 40, R + 9):
             starts = start_vector(rng, rows, R, total)
-            got = cd.gather_rows(batch, starts, rows)
+            with gathers_on(fam, True):                    # every mapping listed is decode_fast.h's
+                got = cd.gather_rows(batch, starts, rows)
             want, ok = gm.expected(x, starts, rows)
             assert ok.all()
             bad = np.nonzero((got.cpu().numpy() != want).reshape(starts.size, -1).any(axis=1))[0]
@@ -166,6 +202,7 @@ GUARD_SHAPES = [
     ("delta", 2, 300, 9600),      # generic kernel
     ("xff", 2, 12, 1200),         # general layout, rows of 24 bytes: generic kernel
 ]
+GUARD_FAST = {("xff", 2, 8, 5120), ("delta", 1, 80, 10240)}         # ... while d_out is 16-byte aligned
 
 
 @pytest.mark.parametrize("codec,esz,D,chunk_len", GUARD_SHAPES)
@@ -193,9 +230,10 @@ def test_gather_rows_output_guards(sz, no_fast, codec, esz, D, chunk_len, fam):
             buf = torch.full((pad + shift + m + pad,), 0x5A, dtype=torch.uint8, device="cuda")
             assert buf.data_ptr() % 16 == 0
             rets = torch.full((starts.size + 1,), -77, dtype=torch.int64, device="cuda")
-            _lib.check(_lib.gather_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(),
-                                        batch.offsets.data_ptr(), nchunks, chunk_len, D, d_starts.data_ptr(), starts.size, rows,
-                                        buf.data_ptr() + pad + shift, rets.data_ptr(), st))
+            with gathers_on(fam, (codec, esz, D, chunk_len) in GUARD_FAST and shift % 16 == 0):
+                _lib.check(_lib.gather_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(),
+                                            batch.offsets.data_ptr(), nchunks, chunk_len, D, d_starts.data_ptr(), starts.size, rows,
+                                            buf.data_ptr() + pad + shift, rets.data_ptr(), st))
             torch.cuda.synchronize()
             h = buf.cpu().numpy()
             assert np.all(h[:pad + shift] == 0x5A), (codec, D, rows, shift, "in front")
@@ -209,7 +247,7 @@ def test_gather_rows_output_guards(sz, no_fast, codec, esz, D, chunk_len, fam):
     ("xff", 2, 8, 5120, 0),
     ("xff", 2, 8, 5120, 1),       # the reference decoder's run replay: what decompress writes with the option on
     ("xff", 2, 16, 2048, 1),
-    ("xff", 2, 24, 2400, 1),      # generic kernel
+    ("xff", 2, 24, 2400, 1),      # decompress: the generic kernel
     ("delta", 1, 80, 10240, 0),
     ("delta", 1, 2, 1000, 0),
 ])
@@ -241,7 +279,9 @@ def test_gather_rows_identity_with_decompress(sz, no_fast, codec, esz, D, chunk_
     _lib.check(_lib.set_option(_lib.OPT_REF_DECODER_QUIRK, quirk))
     try:
         dec = cd.decompress(batch)
-        got = cd.gather_rows(batch, torch.arange(nchunks, dtype=torch.int64, device="cuda") * R, R)
+        # (rows of 16 / 32 / 48 / 80 bytes are decode_fast.h's, whatever the quirk; the low-dim layout is not)
+        with gathers_on(fam, D != 2):
+            got = cd.gather_rows(batch, torch.arange(nchunks, dtype=torch.int64, device="cuda") * R, R)
         # and unaligned windows of it: rows the quirk has changed sit where decompress puts them
         starts = torch.tensor([5, R - 3, 7 * R + 11, 39 * R - 40], dtype=torch.int64, device="cuda")
         win = cd.gather_rows(batch, starts, 40)
@@ -282,7 +322,8 @@ def test_gather_rows_missing_rows(sz, no_fast, codec, esz, D, chunk_len, fam):
     sent = 0x5A if esz == 1 else 0x5A5A
     out = torch.full((starts.size, rows, D), sent, dtype=torch.int32, device="cuda").to(cd.dtype)
     rets = torch.full((starts.size,), -77, dtype=torch.int64, device="cuda")
-    cd.gather_rows(batch, starts, rows, out=out, rets=rets, check=False)
+    with gathers_on(fam, (codec, D) in (("xff", 8), ("delta", 80))):
+        cd.gather_rows(batch, starts, rows, out=out, rets=rets, check=False)
     r = rets.cpu().numpy()
     assert np.array_equal(r, want_rets), (r, want_rets)
     g = out.cpu().numpy()
@@ -318,7 +359,8 @@ def test_gather_rows_damaged_chunks(sz, no_fast, codec, esz, D, chunk_len, fam):
     hdr = batch.data[off + 6].clone()
     batch.data[off + 6] = hdr ^ 0x5                        # the header's ndims field
     rets = torch.full((starts.size,), -77, dtype=torch.int64, device="cuda")
-    got = cd.gather_rows(batch, starts, rows, rets=rets, check=False)
+    with gathers_on(fam, (codec, D) in (("xff", 8), ("delta", 80))):
+        got = cd.gather_rows(batch, starts, rows, rets=rets, check=False)
     r = rets.cpu().numpy()
     assert np.all(r[touches] < 0) and np.all(r[~touches] == rows), r
     assert np.array_equal(got.cpu().numpy()[~touches], want[~touches])
@@ -351,7 +393,8 @@ def test_read_rows_over_3000_chunks(sz, no_fast, fam):
     total = nchunks * R - 77
     x = gen_rows("walk", rng, total, 2, D)
     cd, batch = compress(sz, "xff", 2, D, R * D, x)
-    got = cd.read_rows(batch, 1, total - 1)
+    with gathers_on(fam, True):                               # uint16 x 8: rows of 16 bytes
+        got = cd.read_rows(batch, 1, total - 1)
     assert got.shape == (total - 2, D)
     assert np.array_equal(got.cpu().numpy(), x[1:total - 1])
     assert np.array_equal(cd.read_rows(batch, 5 * R - 1, 5 * R + 1).cpu().numpy(), x[5 * R - 1:5 * R + 1])

@@ -4,6 +4,7 @@ oracle, then on into the Sprintz decoder.  Nothing here needs libzstd or /root/r
 import numpy as np
 import pytest
 
+from dispatch import ran
 from harness import DTYPES
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,8 @@ pytestmark = pytest.mark.gpu
 def sz(request):
     """every test on every stream kernel: the one-wave-per-chunk form with self-synchronising decoders (huf0_sync.h: what batches up to
     8 192 chunks get; without a size hint its blocks above 4 KB are read from global memory, with one they sit in LDS), the single-wave form
-    it replaced there (a wave per 16 chunks), and the bandwidth-sized form forced (2-wave workgroups around one table, 64-byte pieces)"""
+    it replaced there (a wave per 16 chunks), and the bandwidth-sized form forced (2-wave workgroups around one table, 64-byte pieces).  All three
+    write the same bytes, so every huf0_decompress of this module also asserts, from the dispatch counters, that the form its options ask for ran"""
     import functools
     import types
     import torch
@@ -22,10 +24,21 @@ def sz(request):
     from sprintz_amd import _lib
     assert _lib.set_option(_lib.OPT_HUF0_BIG_BATCH, 0 if request.param == "big-batch form" else 16385) == 0
     assert _lib.set_option(_lib.OPT_HUF0_SYNC_CHUNKS, (1 << 30) if request.param.startswith("sync") else 0) == 0
-    mod = sprintz_amd
+    mod = types.SimpleNamespace(**{k: getattr(sprintz_amd, k) for k in dir(sprintz_amd) if not k.startswith("__")})
+    decompress = sprintz_amd.huf0_decompress
     if request.param == "sync form, hinted":                  # the same module with the hint filled in
-        mod = types.SimpleNamespace(**{k: getattr(sprintz_amd, k) for k in dir(sprintz_amd) if not k.startswith("__")})
-        mod.huf0_decompress = functools.partial(sprintz_amd.huf0_decompress, max_block_bytes=16384)
+        decompress = functools.partial(sprintz_amd.huf0_decompress, max_block_bytes=16384)
+    family = {"sync form": "huf0_sync", "sync form, hinted": "huf0_sync", "single-wave form": "huf0_default", "big-batch form": "huf0_big"}[request.param]
+    stream_stage = ["huf0_big", "huf0_sync", "huf0_default"]
+
+    def checked(blocks, block_offsets, *args, **kwargs):
+        nchunks = block_offsets.numel() - 1
+        launches = 1 if nchunks > 0 else 0                    # (a batch of no chunks launches nothing)
+        # SPRINTZ_OPT_HUF0_BIG_BATCH is asked first: from 16 385 chunks on (the value set above) a batch is the big-batch form's under every label
+        took = "huf0_big" if nchunks >= 16385 else family
+        with ran(only=stream_stage, **{k: launches if k == took else 0 for k in stream_stage}):
+            return decompress(blocks, block_offsets, *args, **kwargs)
+    mod.huf0_decompress = checked
     yield mod
     # back to what the process was configured with (the environment's value, else the library's default), not to a constant
     import os

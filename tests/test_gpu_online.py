@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from dispatch import ran
 from harness import gen_fuzz, gen_walk
 from test_online_cpu import oracle_pack, oracle_unpack, orc, golden_online  # noqa: F401  (fixtures)
 
@@ -73,7 +74,16 @@ def test_device_forms_on_long_streams(lib, orc, kind, chain, monkeypatch):
             assert r == wret, (kind, n)
             assert np.array_equal(dest[: 2 * r].cpu().numpy(), want), (kind, n)
             out = torch.zeros(n + 16, dtype=torch.int16, device="cuda")
-            lib.check(lib.online_unpack_device(kind, dest.data_ptr(), n, out.data_ptr(), ret.data_ptr(), tmp.data_ptr(), st))
+            # the dynamic-delta decoder's two forms write the same samples: the counters say which ran.  A tile is 8 192 blocks of 8 samples;
+            # "1": every stream of at least one block; default: from 128 tiles on -- none of these streams (at most 16 tiles); "0": never
+            if kind > 1:
+                expect = ran(on_chain=0, on_three=0)
+            elif chain == "1" and (n - 1) // 8 >= 1:
+                expect = ran(on_chain=1, on_three=0)
+            else:
+                expect = ran(on_chain=0, on_three=1)
+            with expect:
+                lib.check(lib.online_unpack_device(kind, dest.data_ptr(), n, out.data_ptr(), ret.data_ptr(), tmp.data_ptr(), st))
             assert int(ret.item()) == n
             assert np.array_equal(out[:n].cpu().numpy().view(np.uint16), x), (kind, n)
             # a wrong length is reported, not decoded past the buffers

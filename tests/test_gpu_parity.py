@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from dispatch import ran
 from harness import DTYPES, REF_TEST_SIZES, gen_fuzz, gen_patterns, gen_sparse, gen_walk
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("decode_path")]
@@ -576,10 +577,13 @@ def test_host_chunked_convenience(sz, oracle):
 
 # ------------------------------------------------ BASELINE.json full sizes (properties)
 
-def test_full_size_cfg2_roundtrip_and_size_checksum(sz, oracle):
+def test_full_size_cfg2_roundtrip_and_size_checksum(sz, oracle, decode_path):
     """131072 chunks x 10 KB (1.34 GB): encode->decode round trip on the
-    GPU, plus the sizes and the stream bytes of EVERY chunk against the oracle (run over the host's cores)."""
+    GPU, plus the sizes and the stream bytes of EVERY chunk against the oracle (run over the host's cores).  The kernels: under "lat" the
+    workgroup-per-chunk pair (the container by scan + copy); otherwise -- FIRE is not the block-parallel kernels' -- the two-column encoder
+    on 4 lanes a chunk, 64 chunks a workgroup, which builds the container itself, and the lane-per-column decoder"""
     import torch
+    enc, dec = {"lat": (dict(enc_lat=1, dense_compact=1), "dec_lat")}.get(decode_path, (dict(enc_pair=1, dense_fused=1), "dec_fast"))
     codec, esz, ndims, chunk_len, nchunks = "xff", 2, 8, 5120, 131072
     g = torch.Generator(device="cuda:0").manual_seed(123)
     steps = torch.randint(-8, 9, (nchunks, chunk_len // ndims, ndims), device="cuda:0", generator=g, dtype=torch.int32)
@@ -587,8 +591,10 @@ def test_full_size_cfg2_roundtrip_and_size_checksum(sz, oracle):
     x = (torch.cumsum(steps, dim=1) + 20000).to(torch.int16).view(torch.uint16).reshape(-1)
     del steps
     cd = sz.ChunkedCodec(codec, esz, ndims, chunk_len, device="cuda:0")
-    batch = cd.compress(x)
-    out = cd.decompress(batch)
+    with ran(only=list(enc), **enc):
+        batch = cd.compress(x)
+    with ran(only=[dec], **{dec: 1}):
+        out = cd.decompress(batch)
     assert torch.equal(out.view(torch.int16), x.view(torch.int16))
     sizes = batch.sizes.cpu().numpy()
     offs = batch.offsets.cpu().numpy()
@@ -609,10 +615,20 @@ def test_full_size_cfg2_roundtrip_and_size_checksum(sz, oracle):
     ("cfg3_1k", "delta", 1, 80, 1024, 524288, 2),        # 80 columns, 1 KB chunks: shorter than one group, stored verbatim
     ("cfg3_10k", "delta", 1, 80, 10240, 52429, 2),       # 80 columns, 10 KB chunks
 ])
-def test_full_size_8bit_configs_roundtrip_and_parity_on_every_chunk(sz, oracle, name, codec, esz, ndims, chunk_len, nchunks, step):
+def test_full_size_8bit_configs_roundtrip_and_parity_on_every_chunk(sz, oracle, decode_path, name, codec, esz, ndims, chunk_len, nchunks, step):
     """BASELINE configs 1 and 3 at the sizes bench.py runs them: encode -> decode round trip on the GPU, and the sizes and
-    compressed bytes of EVERY chunk against the oracle (run over the host's cores; round 5 compared a 150-chunk sample)."""
+    compressed bytes of EVERY chunk against the oracle (run over the host's cores; round 5 compared a 150-chunk sample).
+    The kernel families, from the dispatch counters: config 1 is the low-dim layout (the workgroup-per-chunk pair under "lat", else the
+    lane-per-chunk pair, with the block-parallel univariate encoder under "blk"); config 3 at 1 KB holds no group (one copy kernel each
+    way, whatever the options); config 3 at 10 KB has 80 columns -- more than the workgroup-per-chunk kernels take: the split-lane
+    encoder and the lane-per-column decoder, under "blk" encode_blk.h and decode_row.h.  None of these encoders builds the container."""
     import torch
+    enc, dec = {
+        "cfg1": {"lat": ("enc_lat", "dec_lat"), "wide": ("enc_uni", "dec_uni"), "blk": ("enc_blk_uni", "dec_uni")},
+        "cfg3_1k": {"lat": (None, "dec_verbatim"), "wide": (None, "dec_verbatim"), "blk": (None, "dec_verbatim")},
+        "cfg3_10k": {"lat": ("enc_split", "dec_fast"), "wide": ("enc_split", "dec_fast"), "blk": ("enc_blk", "dec_row")},
+    }[name][decode_path]
+    enc = {enc: 1, "dense_compact": 1} if enc else {"dense_verbatim": 1}
     g = torch.Generator(device="cuda:0").manual_seed(321)
     rows = chunk_len // ndims
     tail = chunk_len - rows * ndims
@@ -626,9 +642,11 @@ def test_full_size_8bit_configs_roundtrip_and_parity_on_every_chunk(sz, oracle, 
     x = body.reshape(-1).contiguous()
     del body
     cd = sz.ChunkedCodec(codec, esz, ndims, chunk_len, device="cuda:0")
-    batch = cd.compress(x)
+    with ran(only=list(enc), **enc):
+        batch = cd.compress(x)
     rets = torch.empty(nchunks, dtype=torch.int64, device="cuda:0")
-    out = cd.decompress(batch, rets=rets)
+    with ran(only=[dec], **{dec: 1}):
+        out = cd.decompress(batch, rets=rets)
     assert torch.equal(out, x), name
     assert bool((rets == chunk_len).all().item())
     sizes, offs = batch.sizes.cpu().numpy(), batch.offsets.cpu().numpy()
@@ -900,8 +918,11 @@ def test_huffman_decoder_survives_damaged_containers(sz):
 
 
 @pytest.mark.parametrize("name,codec,esz,ndims,chunk_len", [c for c in CONFIGS if c[0] in ("cfg2", "cfg3_1k", "cfg3_10k", "cfg5", "xff8", "cfg1", "uni16_xff", "uni16_delta_ragged", "low8_d2", "low8_d4", "lowdim16", "low16_d2_delta_ragged", "lowdim8", "low8_d3_delta", "wide8_d128_xff", "wide8_d100_delta", "wide8_d66_xff", "wide16_d80_xff", "wide16_d128_delta", "wide16_d72_xff")])
-def test_generic_kernels_agree_with_the_fast_ones(sz, request, name, codec, esz, ndims, chunk_len):
-    """SPRINTZ_OPT_NO_FAST routes the same calls to decode_kernel.h / encode_kernel.h: same bytes, same samples"""
+def test_generic_kernels_agree_with_the_fast_ones(sz, request, decode_path, name, codec, esz, ndims, chunk_len):
+    """SPRINTZ_OPT_NO_FAST routes the same calls to decode_kernel.h / encode_kernel.h: same bytes, same samples -- and the dispatch counters
+    say that it did (the one exception: a batch whose chunks hold no group is copied into its container by one kernel, whatever the
+    option).  Likewise SPRINTZ_OPT_ENC_PAIR: the FIRE shapes of 8 and 32 columns go to the two-column encoder with it and to the
+    one-column encoder without, wherever the workgroup-per-chunk encoder ("lat") does not take them first."""
     import torch
     from sprintz_amd import _lib
     request.addfinalizer(lambda: _lib.set_option(_lib.OPT_NO_FAST, 0))
@@ -909,19 +930,26 @@ def test_generic_kernels_agree_with_the_fast_ones(sz, request, name, codec, esz,
     data = np.concatenate([gen_walk(rng, 40 * chunk_len, ndims, esz, 5, flat_every=3), gen_fuzz(rng, 9 * chunk_len + 17 * ndims, esz, 2)])
     cd = sz.ChunkedCodec(codec, esz, ndims, chunk_len, device="cuda:0")
     x = torch.from_numpy(data).cuda()
-    fast = cd.compress(x)
+    pair_shape = name in ("cfg2", "cfg5", "xff8") and decode_path != "lat"
+    with ran(enc_pair=1, enc_fast=0) if pair_shape else ran():
+        fast = cd.compress(x)
     _lib.check(_lib.set_option(_lib.OPT_ENC_PAIR, 0))          # one column per lane (encode_fast.h) where two are the default
     request.addfinalizer(lambda: _lib.set_option(_lib.OPT_ENC_PAIR, 1))
-    fast1 = cd.compress(x)
+    with ran(enc_pair=0, enc_fast=1) if pair_shape else ran(enc_pair=0):
+        fast1 = cd.compress(x)
     _lib.check(_lib.set_option(_lib.OPT_ENC_PAIR, 1))
     assert torch.equal(fast.sizes, fast1.sizes) and torch.equal(fast.data[: fast.total_bytes()], fast1.data[: fast1.total_bytes()])
     _lib.check(_lib.set_option(_lib.OPT_NO_FAST, 1))
-    slow = cd.compress(x)
+    slow_enc = dict(dense_verbatim=1) if name == "cfg3_1k" else dict(enc_generic=1, dense_compact=1)
+    with ran(only=list(slow_enc), **slow_enc):
+        slow = cd.compress(x)
     assert torch.equal(fast.sizes, slow.sizes) and torch.equal(fast.offsets, slow.offsets)
     assert torch.equal(fast.data[: fast.total_bytes()], slow.data[: slow.total_bytes()])
-    out_slow = cd.decompress(fast)
+    with ran(dec_generic=1, only=["dec_generic"]):
+        out_slow = cd.decompress(fast)
     _lib.check(_lib.set_option(_lib.OPT_NO_FAST, 0))
-    out_fast = cd.decompress(slow)
+    with ran(dec_generic=1 if name == "wide16_d72_xff" else 0):      # (that one's chunks are shorter than half of decode_fast.h's ring)
+        out_fast = cd.decompress(slow)
     assert torch.equal(out_slow, out_fast) and np.array_equal(out_fast.cpu().numpy(), data)
 
 
@@ -1012,7 +1040,7 @@ def test_random_shapes(sz, oracle, seed):
     ("xff", 2, 4, 4000, 500), ("delta", 2, 3, 3000, 257),              # 3 and 4 uint16 columns: encode_fast.h on 4 lanes a chunk, the one shape of it that arms the tail
 ])
 @pytest.mark.parametrize("enc_pair", [1, 0])
-def test_container_built_inside_the_encode_launch(sz, oracle, request, codec, esz, ndims, chunk_len, nchunks, enc_pair):
+def test_container_built_inside_the_encode_launch(sz, oracle, request, decode_path, codec, esz, ndims, chunk_len, nchunks, enc_pair):
     """sprintz_mi355x_compress_batch_dense (one launch: chained scan over workgroups + in-kernel copy, compact_tail.h) writes
     the container, offsets and sizes that compress_batch + compact(align 16) write -- and that the oracle specifies; with two
     columns per lane (encode_wide.h, the default for 5 .. 128 columns) and with one (encode_fast.h, SPRINTZ_OPT_ENC_PAIR 0)"""
@@ -1020,6 +1048,41 @@ def test_container_built_inside_the_encode_launch(sz, oracle, request, codec, es
     from sprintz_amd import _lib
     _lib.check(_lib.set_option(_lib.OPT_ENC_PAIR, enc_pair))
     request.addfinalizer(lambda: _lib.set_option(_lib.OPT_ENC_PAIR, 1))
+    # Whether the container WAS built inside the launch, from the dispatch counters.  Only an encoder with 64 chunks a workgroup carries the
+    # tail (api.hip, arm_dense): the two-column encoder on 4 lanes a chunk -- 5 .. 8 columns in blocks of whole 16-byte pieces -- and the
+    # one-column encoder on 4 lanes, 3 and 4 uint16 columns.  The workgroup-per-chunk encoder ("lat": it takes every such shape here)
+    # and the block-parallel one ("blk": none of these, their rows are shorter than 16 bytes) leave the container to scan + copy; chunks that
+    # hold no group are copied into it by one kernel without any encoder.  Mode 0 is scan + copy by definition.
+    shape = (codec, esz, ndims, chunk_len)
+    if shape in (("delta", 1, 80, 1024), ("xff", 2, 8, 100), ("xff", 2, 128, 2000), ("delta", 1, 5, 77)):
+        how = "dense_verbatim"
+    elif decode_path != "lat" and ((enc_pair and shape in (("xff", 2, 8, 5120), ("xff", 2, 8, 1280), ("xff", 2, 7, 7 * 160), ("delta", 1, 8, 128)))
+                                   or shape in (("xff", 2, 4, 4000), ("delta", 2, 3, 3000))):
+        how = "dense_fused"
+    else:
+        how = "dense_compact"
+    dense_ways = ["dense_fused", "dense_verbatim", "dense_compact"]
+    # ... and the encoder, per decode_path ("lat", "wide", "blk"); PAIR: the two-column encoder with SPRINTZ_OPT_ENC_PAIR, the one-column one without
+    PAIR = ("enc_pair", "enc_fast")
+    encoder = {
+        ("xff", 2, 8, 5120): ("enc_lat", PAIR, PAIR), ("xff", 2, 8, 1280): ("enc_lat", PAIR, PAIR),
+        ("delta", 1, 16, 4096): ("enc_lat", PAIR, "enc_blk"), ("xff", 2, 32, 5120): ("enc_lat", PAIR, PAIR), ("delta", 2, 64, 4096): ("enc_lat", PAIR, "enc_blk"),
+        ("xff", 1, 5, 4000): ("enc_lat", "enc_generic", "enc_generic"),                    # blocks of 40 bytes: not the lane-per-column fast encoders'
+        ("delta", 1, 80, 10240): ("enc_split", "enc_split", "enc_blk"), ("xff", 1, 72, 72 * 64): ("enc_split", "enc_split", "enc_split"),
+        ("xff", 2, 80, 10240): ("enc_wide", "enc_wide", "enc_wide"), ("delta", 1, 128, 16384): ("enc_wide", "enc_wide", "enc_blk"),
+        ("xff", 2, 7, 7 * 160): ("enc_lat", PAIR, PAIR),
+        ("delta", 1, 1, 1024): ("enc_lat", "enc_uni", "enc_blk_uni"), ("xff", 1, 3, 3 * 400): ("enc_lat", "enc_uni", "enc_uni"),
+        ("xff", 2, 2, 2048): ("enc_lat", "enc_uni", "enc_uni"), ("delta", 2, 1, 1000): ("enc_lat", "enc_uni", "enc_blk_uni"),
+        # chunks that hold no group: no encoder at all where the container is written directly (mode 1); under mode 0 the generic encoder (their
+        # chunks are no whole 16-byte pieces, or shorter than two blocks) -- but the single 77-byte chunk is the workgroup-per-chunk encoder's
+        ("delta", 1, 80, 1024): ("enc_generic",) * 3, ("xff", 2, 8, 100): ("enc_generic",) * 3, ("xff", 2, 128, 2000): ("enc_generic",) * 3,
+        ("delta", 1, 5, 77): ("enc_lat", "enc_generic", "enc_generic"),
+        ("delta", 1, 8, 128): ("enc_lat", PAIR, PAIR),                                       # rows of 8 bytes: not encode_blk.h's
+        ("xff", 2, 4, 4000): ("enc_lat", "enc_fast", "enc_fast"), ("delta", 2, 3, 3000): ("enc_lat", "enc_fast", "enc_fast"),
+    }[shape][("lat", "wide", "blk").index(decode_path)]
+    if encoder is PAIR:
+        encoder = PAIR[0] if enc_pair else PAIR[1]
+    from dispatch import ENCODERS
     rng = np.random.default_rng(nchunks * 7 + ndims)
     total = nchunks * chunk_len - (chunk_len // 3 if nchunks > 1 else 0)          # a short last chunk
     data = gen_walk(rng, total, ndims, esz, 8, flat_every=4)
@@ -1033,7 +1096,10 @@ def test_container_built_inside_the_encode_launch(sz, oracle, request, codec, es
             cd._ws = {}
             dense = torch.full((nchunks * cd.slot_stride + 16,), 0xEE, dtype=torch.uint8, device="cuda")
             offs = torch.full((nchunks + 1,), -1, dtype=torch.int64, device="cuda")
-            ws, dense, offs = cd.compress_dense(src, total, dense=dense, offsets=offs)
+            took = {k: int(k == (how if mode else "dense_compact")) for k in dense_ways}
+            took.update({k: int(k == encoder and not took["dense_verbatim"]) for k in ENCODERS})
+            with ran(**took):
+                ws, dense, offs = cd.compress_dense(src, total, dense=dense, offsets=offs)
             torch.cuda.synchronize()
             res[mode] = (dense.cpu().numpy(), offs.cpu().numpy(), ws["sizes"].cpu().numpy().copy(), ws["rets"].cpu().numpy().copy())
         finally:

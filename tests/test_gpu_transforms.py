@@ -4,6 +4,7 @@ multi-level scan has several levels.  Nothing here reads /root/reference."""
 import numpy as np
 import pytest
 
+from dispatch import ran
 from harness import DTYPES
 
 pytestmark = pytest.mark.gpu
@@ -17,6 +18,23 @@ def sz():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     import sprintz_amd
     return sprintz_amd
+
+
+def chain_takes(esz, ndims, n):
+    """the one-pass decode (chain_scan_kernel) exists for 16-bit streams cut into 16-byte pieces -- rows of whole pieces, or rows of 2 / 4 / 8
+    bytes, several to a piece, in a stream of whole pieces -- with at most 8 pieces a row (csrc/transforms.hip, decode_wave)"""
+    row, total = ndims * esz, n * esz
+    return esz == 2 and total % 16 == 0 and ((row % 16 == 0 and row // 16 <= 8) or row in (2, 4, 8))
+
+
+def wave_takes(esz, ndims, n):
+    """the wave-scan decode (csrc/transforms.hip, decode_device / wave_piece_bytes) cuts a stream into pieces of 16, 4 or one element's bytes: the
+    largest size that divides both the row and the stream and leaves at most 64 pieces a row -- 1 or 2, or at least 3 -- or, for rows of 1 / 2 /
+    4 / 8 bytes in a stream of whole 16-byte pieces, several rows a piece.  A stream no piece size fits is the generic levels' alone."""
+    row, total = ndims * esz, n * esz
+    if row < 16 and 16 % row == 0 and total % 16 == 0:
+        return True
+    return any(pb >= esz and row % pb == 0 and total % pb == 0 and row // pb <= 64 for pb in (16, 4, esz))
 
 
 def test_reference_containers_single_call(sz, golden_transforms):
@@ -72,7 +90,21 @@ def test_long_streams_on_device(sz, oracle, kind, esz, ndims, n, chain, monkeypa
         want = xi - 2 * p1 + p2
     mask = (1 << (8 * esz)) - 1
     assert torch.equal(y.view(torch.int8 if esz == 1 else torch.int16).to(torch.int32) & mask, want & mask)
-    back = sz.transform_device(kind, y, ndims, inverse=True)
+    # the two forms write the same samples: which one decoded is the dispatch counters' to say.  Every 16-bit stream the chained scan takes, on it
+    # from the first tile on (the default, and "1"); everything else -- 8-bit streams, rows of more than 8 pieces, rows and streams that are not
+    # whole 16-byte pieces -- and everything under "0" on the two-pass form: the wave scans, or the generic levels alone where a row has more
+    # than 64 pieces of the size its length allows
+    # (of this parametrisation only uint16 x 300 -- rows of 600 bytes: 150 pieces of 4 -- and uint8 x 80 with 13 odd elements -- 80 pieces of 1 --
+    #  have no piece size with at most 64 pieces a row)
+    assert wave_takes(esz, ndims, n) == ((esz, ndims, n) not in ((2, 300, 300 * 40_000), (1, 80, 80 * 70_001 + 13)))
+    if chain != "0" and chain_takes(esz, ndims, n):
+        expect = ran(tr_chain=1, only=["tr_chain"])
+    elif wave_takes(esz, ndims, n):
+        expect = ran(tr_wave=1, only=["tr_wave"])
+    else:
+        expect = ran(tr_levels=1, only=["tr_levels"])
+    with expect:
+        back = sz.transform_device(kind, y, ndims, inverse=True)
     assert torch.equal(back, x)
 
 
