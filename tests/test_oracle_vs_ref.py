@@ -68,3 +68,37 @@ def test_big_stream(oracle, reference):
     n = 1024 * 1024 + 7
     for esz, codec, nd in [(1, "xff", 8), (2, "xff", 8), (2, "delta", 32), (1, "delta", 1)]:
         _check(oracle, reference, codec, gen_walk(rng, n, nd, esz, 8, flat_every=5), nd)
+
+
+@pytest.mark.parametrize("w,ndims", [(8, 1), (8, 3), (8, 8), (8, 80), (16, 1), (16, 2)])
+@pytest.mark.parametrize("runs", [True, False])
+def test_fire_counters_through_their_wrap(oracle, reference, w, ndims, runs):
+    """tests/fire_drive.py: the 8-bit counter through its int16 wrap in both directions, the 16-bit low-dim coefficient past 2^23, with and
+    without run spans at the frozen extreme coefficients -- compress bytes and return value, and the reference DECODER's samples (_check).
+    (16-bit general FIRE is left out: its reference decoder does not invert runs -- OPT_REF_DECODER_QUIRK, pinned above -- and its truncated
+    coefficient has 16 values, all covered by the families)"""
+    import fire_drive as fd
+    for seed, pattern in ((0, 2), (1, 3)):
+        x, ctr = fd.chunk(w, ndims, seed, pattern, runs=None if runs else ())
+        if w == 8:
+            assert fd.wraps(ctr).any(axis=0).all()
+        else:
+            assert np.abs(fd.coefficient(ctr, 16, True)).max() > (1 << 23)
+        data = np.ascontiguousarray(x).ravel()
+        _check(oracle, reference, "xff", data, ndims)
+        dr, drr = reference.decompress("xff", oracle.compress("xff", data, ndims)[0], w // 8, data.size, ndims)
+        assert drr == data.size and np.array_equal(dr, data)          # (no divergence is legal here: low-dim or 8 bits)
+
+
+@pytest.mark.parametrize("ndims", [1, 8, 33])
+def test_fire_transform_counters_through_their_wrap(oracle, reference, ndims):
+    """the stand-alone transform's forecaster (predict.cpp:140-202) on inputs steered against ITS forecast: containers, return values, and back"""
+    import fire_drive as fd
+    if not reference.has_transforms():
+        pytest.skip("oracle/_ref built without the transforms")
+    x = fd.transform_input(ndims)
+    co, ro = oracle.transform_encode(2, x, ndims)
+    cr, rr = reference.transform_encode(2, x, ndims)
+    assert ro == rr and np.array_equal(co, cr)
+    back, bret = reference.transform_decode(2, co, 1)
+    assert bret == x.size and np.array_equal(back, x)
