@@ -1,5 +1,6 @@
 // api.hip -- C-ABI of libsprintz_mi355x.so (include/sprintz_mi355x.h): argument
-// checking, lane-mapping selection, kernel launches, the size-scan/compaction
+// checking, the launchers of what plan.h decided (which kernel, which geometry: no
+// eligibility predicate lives here), the size-scan/compaction
 // kernels and the host-pointer drop-in wrappers.  No codec arithmetic on the
 // host; the only host-side stream logic is the framing walk that sizes the
 // H2D copy of the length-less reference decompress() signature.
@@ -23,11 +24,10 @@
 
 #include "launch.h"
 #include "dispatch.h"
-#include "encode_blk.h"
-#include "decode_blk.h"
-#include "decode_row.h"
-#include "decode_lat.h"
-#include "encode_lat.h"
+#include "plan.h"
+#include "encode_blk.h"      // launch_encode_blk, launch_encode_blk_uni
+#include "decode_blk.h"      // launch_decode_blk
+#include "decode_row.h"      // launch_decode_row
 
 using namespace sprintz;
 
@@ -102,56 +102,8 @@ int ensure_device()
     return 0;
 }
 
-bool is_lowdim(int esz, int D) { return esz == 1 ? D <= 4 : D <= 2; }   // sprintz.cpp:34-50
-
-struct Mapping { int log2DP; int cpl; };
-
-// Choose lanes-per-chunk (DP = 2^k) and columns-per-lane so that DP*CPL >= D
-// with little padding; among mappings within 75% of the best lane utilisation
-// prefer the widest group (better coalescing of the D*esz-byte rows).
-Mapping choose_mapping(int D, bool lowdim)
-{
-    if (lowdim) {
-        int l = 0;
-        while ((1 << l) < D) l++;
-        return {l, 1};
-    }
-    double best = 0;
-    for (int l = 0; l <= 6; l++)
-        for (int c : kCplSet)
-            if ((1 << l) * c >= D) best = std::max(best, (double)D / ((1 << l) * c));
-    Mapping m{6, 8};
-    bool found = false;
-    for (int l = 6; l >= 0 && !found; l--) {
-        for (int c : kCplSet) {
-            if ((1 << l) * c < D) continue;
-            if ((double)D / ((1 << l) * c) >= 0.75 * best) { m = {l, c}; found = true; break; }
-        }
-    }
-    return m;
-}
-
-uint32_t next_pow2(uint32_t x)
-{
-    uint32_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-size_t group_bytes_max(int esz, int D)
-{
-    const size_t hb = esz == 1 ? 3 : 4;
-    return (2 * (size_t)D * hb + 7) / 8 + 16 * (size_t)D * esz;
-}
-
 // ---------------------------------------------------------------- compaction kernels
 
-#ifndef SPRINTZ_BOUND_ALIGN
-#define SPRINTZ_BOUND_ALIGN 128           // sprintz_mi355x_compress_bound is a multiple of this: slots start on 128-byte lines
-#endif
-#ifndef SPRINTZ_ENC_DRAIN_ALIGN
-#define SPRINTZ_ENC_DRAIN_ALIGN 128       // encode_fast.h / encode_wide.h: granularity of the window's flushes to the slot
-#endif
 constexpr int kScanBlock = 1024;
 
 __global__ void __launch_bounds__(kScanBlock) scan_local_kernel(const uint32_t* sizes, uint64_t n, uint32_t align,
@@ -410,69 +362,59 @@ struct QuerySpec {
     const HostCall* hc = nullptr;
 };
 
-// One chunk's working set of the workgroup-per-chunk kernels (decode_lat.h / encode_lat.h) must fit a workgroup's LDS: up to 16 KB of
-// samples several workgroups share a CU (what the batch limits of SPRINTZ_OPT_LAT_CHUNKS were measured with); larger chunks -- up to
-// ~40 KB of uint16, ~24 KB of uint8: 150 KB of LDS, a workgroup a CU -- only for batches that leave most CUs empty anyway (single calls)
-bool lat_chunk_fits(bool encode, int esz, uint64_t nchunks, uint32_t chunk_len, int D)
+// The dispatch options as ONE exported call sees them: every atomic is loaded once, here, and everything the call decides --
+// the host paths' choice between the ticket and the staged form, the planner, the launcher -- uses this copy (plan.h)
+Knobs snapshot()
 {
-    const uint64_t bytes = (uint64_t)chunk_len * esz;
-    // (the 48 KB term never decides: both kernels keep 4 bytes an element of working set next to the stream -- 96 KB for 48 KB of uint16, 192 KB
-    //  for uint8 -- so the 150 KB carve below refuses a chunk long before it: uint16 x 8 from 45 696 bytes on to decode, from 33 104 to encode
-    //  (tests/test_gpu_dispatch.py pins both sides).  It stays as the bound that keeps the 32-bit arithmetic of the carves far from a wrap)
-    if (bytes > (48u << 10) || (bytes > kLatMaxChunkBytes && nchunks > 64)) return false;
-    // the carve and the 16-bit position limit are checked for EVERY size: a shape whose working set does not fit goes to the
-    // lane-per-column kernels instead of failing its launch
-    const uint32_t bound = (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, (uint16_t)D);
-    if (bound > 60000u) return false;                            // (stream positions travel in 16 bits between the kernels' phases)
-    const uint32_t total = encode ? enc_lat_carve(bound, chunk_len, (uint32_t)D, (uint32_t)esz).total : lat_carve(bound, chunk_len, (uint32_t)D).total;
-    return total <= 150u * 1024u;
+    const Process& p = process();
+    auto ld = [](const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); };
+    return Knobs{ld(p.no_fast), ld(p.lat_chunks), ld(p.blk_chunks), ld(p.blk_kernels), ld(p.enc_pair), ld(p.split_lanes), ld(p.chunks_per_group), ld(p.dense_mode), ld(p.ref_quirk)};
 }
 
-bool decode_ref_quirk(int codec, int esz, bool lowdim)
+unsigned low4(const void* p) { return (unsigned)((uintptr_t)p & 15u); }
+
+// more than 2 047 columns, FIRE: the counters of the column-tiled kernels live in stream-ordered scratch around the launch (any_ndims.hip, "big")
+int alloc_counters(const Plan& p, uint64_t nchunks, int D, hipStream_t st, int32_t** counters)
 {
-    // (only 16-bit general-layout FIRE streams have the divergence: sprintz_xff_rle.cpp:893-901)
-    return esz == 2 && codec == SPRINTZ_CODEC_XFF && !lowdim && process().ref_quirk.load(std::memory_order_relaxed);
+    *counters = nullptr;
+    if (p.counters && hipMallocAsync((void**)counters, (size_t)nchunks * (size_t)D * 4, st) != hipSuccess)
+        return fail(SPRINTZ_E_HIP, "hipMallocAsync of the counters' scratch (not available during stream capture)");
+    return 0;
 }
 
-// small batches: one WORKGROUP per chunk (decode_lat.h) -- a chunk's 40 dependent group steps on one lane group take 50 us
-// however few chunks there are; split into a header walk, parallel bit extraction, the bare recurrence and a prefix sum it is ~13
-bool decode_lat_fits(int codec, int esz, uint64_t nchunks, uint32_t chunk_len, int D, int noheader, const QuerySpec& qs, const void* d_out)
+Shape decode_shape(int codec, int esz, const void* d_comp, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, const void* d_out, int noheader,
+                   const QuerySpec& qs)
 {
-    const bool norle = codec >= SPRINTZ_CODEC_DELTA_NORLE;
-    const bool lowdim = (qs.general || norle) ? false : is_lowdim(esz, D);
-    return !norle && !noheader && !qs.col_stride && !decode_ref_quirk(codec, esz, lowdim) && qs.q == kQueryOff && D <= 64 &&
-           lat_chunk_fits(false, esz, nchunks, chunk_len, D) && chunk_len >= 16u * (uint32_t)D && ((uintptr_t)d_out % 16) == 0 &&
-           (nchunks == 1 || ((uint64_t)chunk_len * esz) % 16 == 0) &&      // (a chunk's output starts 16-byte aligned; its end may lie anywhere)
-           // (about one round of workgroups on the chip is where it wins: 5 a CU at 8 columns -- measured 33 vs 47 us at 1 250 chunks, 41 vs 47
-           //  at 2 048, 59 vs 47 at 3 072; with more columns a chunk has fewer groups to walk and the lane-per-column kernel catches up
-           //  sooner: 32 columns 11.6 vs 14.7 at 640 chunks, 19.7 vs 14.8 at 1 250 -- a third of the limit from 17 columns on)
-           nchunks <= (uint64_t)process().lat_chunks.load(std::memory_order_relaxed) / (D > 16 ? 3u : 1u) && !process().no_fast.load(std::memory_order_relaxed);
+    Shape s;
+    s.codec = codec; s.esz = esz; s.D = ndims; s.nchunks = nchunks; s.chunk_len = chunk_len;
+    s.noheader = noheader; s.q = qs.q; s.general = qs.general; s.col_stride = qs.col_stride; s.host_call = qs.hc != nullptr;
+    s.comp_lo = low4(d_comp); s.out_lo = low4(d_out);
+    return s;
 }
 
-int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
-                  uint32_t chunk_len, uint16_t ndims, void* d_out, int64_t* d_rets, hipStream_t st,
-                  int noheader, uint32_t nh_ngroups, uint32_t nh_remaining, const QuerySpec& qs = QuerySpec{})
+// launches what plan_decode (plan.h) decided for this call: the arguments from the plan, one switch on the family, the counter
+int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims,
+                  void* d_out, int64_t* d_rets, hipStream_t st, int noheader, uint32_t nh_ngroups, uint32_t nh_remaining, const QuerySpec& qs)
 {
-    if (nchunks == 0) return 0;
-    const int D = ndims;
-    const bool norle = codec >= SPRINTZ_CODEC_DELTA_NORLE;      // general layout for every ndims, generic kernels
-    const bool lowdim = (qs.general || norle) ? false : is_lowdim(esz, D);
-    const Mapping m = choose_mapping(D, lowdim);
-    const int DP = 1 << m.log2DP;
+    // (the host paths hand over the plan they chose the ticket form by: not reached from there)
+    if (qs.hc && p.family != SPRINTZ_KF_DEC_LAT) return fail(SPRINTZ_E_HIP, "internal: host call on a kernel that cannot end it");
+    // more than 2 047 columns: the column-tiled kernels build the stream with device-scope atomics on the slot and read their own output back
+    if (p.plain_memory && !is_plain_device_memory(d_out)) return fail(SPRINTZ_E_INVALID, "more than 2047 columns: the output must be device memory (hipMalloc), not mapped host or managed memory");
+    if (p.err) return fail(p.err, p.what);
 
     DecodeArgs a{};
     a.comp = (const uint8_t*)d_comp;
     a.offsets = d_offsets;
     a.nchunks = nchunks;
     a.chunk_len = chunk_len;
-    a.D = D;
-    a.log2DP = m.log2DP;
+    a.D = ndims;
+    a.log2DP = p.log2DP;
     a.out = d_out;
     a.rets = d_rets;
     a.noheader = noheader;
     a.nh_ngroups = nh_ngroups;
     a.nh_remaining = nh_remaining;
-    a.chunks_per_group = 1;
+    a.chunks_per_group = p.chunks_per_group;
     a.qop = qs.qop;
     a.qres = qs.qres;
     a.window_rows = qs.window_rows;
@@ -481,426 +423,172 @@ int decode_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offs
     a.win_min = qs.win_min;
     a.win_max = qs.win_max;
     a.win_sum = qs.win_sum;
-    a.norle = norle ? (codec == SPRINTZ_CODEC_XFF_NORLE ? 2 : 1) : 0;
-    a.raw = codec == SPRINTZ_CODEC_BITPACK_NORLE ? 1 : 0;
+    a.norle = p.norle;
+    a.raw = p.raw;
     a.col_stride = qs.col_stride;
-    const uint64_t cs = qs.col_stride;
-    a.quirk = decode_ref_quirk(codec, esz, lowdim) ? 1 : 0;
-    if (qs.hc && !decode_lat_fits(codec, esz, nchunks, chunk_len, D, noheader, qs, d_out)) return fail(SPRINTZ_E_HIP, "internal: host call on a kernel that cannot end it");
+    a.quirk = p.quirk;
+    a.vec_store = p.vec_store;
+    a.lds_group_stride = p.lds_group_stride;
 
-    // 513 .. 2047 columns: one workgroup per chunk (any_ndims.hip) -- the RLE codecs, row-major, plain decode
-    if (D > 512) {
-        if (norle || cs || qs.q != kQueryOff) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: the RLE codecs, row-major, without query only");
-        if (nchunks > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        if (D > 2047) {                                        // column tiles; the FIRE counters in stream-ordered scratch (any_ndims.hip, "big")
-            if (!is_plain_device_memory(d_out)) return fail(SPRINTZ_E_INVALID, "more than 2047 columns: the output must be device memory (hipMalloc), not mapped host or managed memory");
-            int32_t* counters = nullptr;
-            const bool fire = codec == SPRINTZ_CODEC_XFF;
-            if (fire && (uint64_t)nchunks * (uint64_t)D * 4 > (1ull << 30)) return fail(SPRINTZ_E_UNSUPPORTED, "more than 2047 columns, FIRE: the counters' scratch (nchunks x ndims x 4 bytes) is limited to 1 GiB a launch: split the batch");
-            if (fire && hipMallocAsync((void**)&counters, (size_t)nchunks * (size_t)D * 4, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "hipMallocAsync of the counters' scratch (not available during stream capture)");
-            const hipError_t eb = launch_decode_big(8 * esz, fire, (unsigned)nchunks, st, a, counters);
-            if (counters) (void)hipFreeAsync(counters, st);
-            if (eb != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_big kernel launch", eb);
-            dispatched(SPRINTZ_KF_DEC_BIG);
-            return 0;
-        }
-        const hipError_t ea = launch_decode_any(8 * esz, codec == SPRINTZ_CODEC_XFF, (unsigned)nchunks, st, a);
-        if (ea != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_any kernel launch", ea);
-        dispatched(SPRINTZ_KF_DEC_ANY);
-        return 0;
+    const int w = 8 * esz;
+    const unsigned grid = (unsigned)p.grid;
+    hipError_t e = hipSuccess;
+    const char* what = "";
+    switch (p.family) {
+    case SPRINTZ_KF_DEC_BIG: {
+        int32_t* counters;
+        if (int rc = alloc_counters(p, nchunks, ndims, st, &counters)) return rc;
+        e = launch_decode_big(w, p.counters, grid, st, a, counters);
+        if (counters) (void)hipFreeAsync(counters, st);
+        what = "decode_big kernel launch";
+        break;
     }
-
-    // batches whose chunks are too short for a stream group: header check + copy (verbatim_decode_kernel)
-    // (only where a chunk cannot hold a group at all, chunk_len < 16 D: a stream of 16 D <= chunk_len < 128 elements that announces
-    //  groups is one the reference ENCODER never writes but its decoder reads -- that one goes to the decoders below)
-    if (!norle && !lowdim && !noheader && !cs && qs.q == kQueryOff && chunk_len < 16u * (uint32_t)D &&
-        !process().no_fast.load(std::memory_order_relaxed)) {
-        const uint64_t vgrid = (nchunks * 64 + kThreads - 1) / kThreads;
-        if (vgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        hipLaunchKernelGGL(verbatim_decode_kernel, dim3((unsigned)vgrid), dim3(kThreads), 0, st, (const uint8_t*)d_comp, d_offsets, nchunks, chunk_len,
-                           (uint32_t)esz, (uint32_t)D, (uint8_t*)d_out, d_rets);
-        HIP_TRY(hipGetLastError());
-        dispatched(SPRINTZ_KF_DEC_VERBATIM);
-        return 0;
-    }
-
-    // LDS-transposed 16-byte stores need every 8 x D block of the output 16-byte aligned
-    const size_t blk_bytes = (size_t)8 * D * esz;
-    const size_t stride = ((blk_bytes + 15) & ~(size_t)15) + 16;     // +16: spread groups over LDS banks
-    const size_t groups_per_block = kThreads / DP;
-    size_t shmem = 0;
-    a.vec_store = 0;
-    if (!cs && blk_bytes % 16 == 0 && (query_reduce_only(qs.q) || ((uintptr_t)d_out % 16) == 0) && ((uint64_t)chunk_len * esz) % 16 == 0 &&
-        stride * groups_per_block <= 64 * 1024) {
-        a.vec_store = 1;
-        a.lds_group_stride = (uint32_t)stride;
-        shmem = stride * groups_per_block;
-    }
-
-    // Fast path (decode_fast.h): general layout, one column per lane, headered stream,
-    // vector stores legal, and the power-of-two group at least half full.
-    int fdp = 4, fcpl = 1;
-    while (fdp < D && fdp < 64) fdp <<= 1;
-    while (fdp * fcpl < D) fcpl <<= 1;                         // 2 / 4 columns per lane for D in 65..256
-    // (for 65..96 columns <DP 32, CPL 3> keeps 84 % of the lanes busy instead of 62 % but holds 9 waves per CU
-    //  instead of 12: measured slower, u8 D=80 1.29 -> 1.26 TB/s, u16 D=80 1.63 -> 1.34)
-    // (two columns per lane at D = 8, i.e. <DP 4, CPL 2>, halves the lanes per chunk but not the LDS per chunk:
-    //  8 waves per CU instead of 16, measured 0.494 vs 0.400 ms -- the doubled ILP does not replace the lost waves)
-    // (32-bit offsets inside one wavefront's span of the output)
-    // and chunks not much shorter than the read-ahead ring (it is filled before the first header is parsed)
-    // 8 bits, 65 .. 80 columns, plain row-major decode: 32 lanes x (a pair + a single column), two chunks a wavefront, the LDS
-    // carve sized for 80 columns so that 12 wavefronts a CU stay resident (decode_fast.h, SPLIT)
-    int fds = 0;
-    if (esz == 1 && D > 64 && D <= 80 && !cs && qs.q == kQueryOff && process().split_lanes.load(std::memory_order_relaxed)) { fdp = 32; fcpl = 3; fds = 80; }
-    // 16 bits, the same widths: 64 x 2 stays, with the carve of 80 columns (12.2 KB a chunk instead of 17.8: 12 waves a CU instead of 8)
-    if (esz == 2 && D > 64 && D <= 80 && !cs && qs.q == kQueryOff && process().split_lanes.load(std::memory_order_relaxed)) fds = 80;
-    const size_t fring = decode_fast_lds_bytes(8 * esz, fdp, fcpl, D, cs != 0 && fcpl == 1, fds);
-    const bool fast_common = !lowdim && !a.raw && !noheader && D <= 256 && 2 * D > fdp * fcpl && (uint64_t)chunk_len * esz * 2 >= fring &&
-                             !process().no_fast.load(std::memory_order_relaxed);
-    // column-major: a lane's 8 samples per block are one aligned 16-byte (8-byte) piece of its column
-    const bool fast = cs ? fast_common && qs.q == kQueryOff && cs % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0 &&
-                               ((uintptr_t)d_out % 16) == 0 && (uint64_t)D * cs * esz < 0xf0000000ull
-                         : fast_common && a.vec_store && (uint64_t)chunk_len * esz * 64 * 64 < 0xf0000000ull;
-    hipError_t e;
-    if (decode_lat_fits(codec, esz, nchunks, chunk_len, D, noheader, qs, d_out)) {     // (a.raw is a run-less codec)
+    case SPRINTZ_KF_DEC_ANY: what = "decode_any kernel launch"; e = launch_decode_any(w, p.fire, grid, st, a); break;
+    case SPRINTZ_KF_DEC_VERBATIM:
+        what = "hipGetLastError()";
+        hipLaunchKernelGGL(verbatim_decode_kernel, dim3(grid), dim3(kThreads), 0, st, (const uint8_t*)d_comp, d_offsets, nchunks, chunk_len,
+                           (uint32_t)esz, (uint32_t)ndims, (uint8_t*)d_out, d_rets);
+        e = hipGetLastError();
+        break;
+    case SPRINTZ_KF_DEC_LAT:
+        what = "decode_lat kernel launch";
         if (qs.hc) { a.offsets = nullptr; a.one_off0 = qs.hc->off0; a.one_off1 = qs.hc->off1; a.host_flag = qs.hc->flag; a.host_ticket = qs.hc->ticket; }
-        int ldp = 4;
-        while (ldp < D) ldp <<= 1;
-        if (esz == 1 && ldp < 8 && !lowdim) ldp = 8;
-        e = launch_decode_lat(8 * esz, codec == SPRINTZ_CODEC_XFF, ldp, lowdim, (unsigned)nchunks, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims), st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_lat kernel launch", e);
-        dispatched(SPRINTZ_KF_DEC_LAT);
-        return 0;
+        e = launch_decode_lat(w, p.fire, p.dp, p.lowdim, grid, p.lat_bound, st, a);
+        break;
+    case SPRINTZ_KF_DEC_ROW: what = "decode_row kernel launch"; e = launch_decode_row(w, grid, st, a, p.row); break;
+    case SPRINTZ_KF_DEC_BLK: what = "decode_blk kernel launch"; e = launch_decode_blk(w, grid, st, a, p.blkd); break;
+    case SPRINTZ_KF_DEC_FAST:
+        what = "decode_fast kernel launch";
+        e = esz == 1 ? launch_decode_fast_w8(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a)
+                     : launch_decode_fast_w16(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a);
+        break;
+    case SPRINTZ_KF_DEC_UNI: what = "decode_uni kernel launch"; e = esz == 1 ? launch_decode_uni_w8(p.fire, ndims, qs.q, grid, st, a) : launch_decode_uni_w16(p.fire, ndims, qs.q, grid, st, a); break;
+    default:
+        what = "decode kernel launch";
+        e = esz == 1 ? launch_decode_w8(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a)
+                     : launch_decode_w16(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a);
+        break;
     }
-    // large batches of the DELTA codec, general layout, rows of whole dwords: a lane per dword-wide column group, blocks in order (decode_row.h)
-    {
-        const int blk_from = process().blk_chunks.load(std::memory_order_relaxed);
-        if (blk_from > 0 && (process().blk_kernels.load(std::memory_order_relaxed) & 8) && nchunks >= (uint64_t)blk_from && codec == SPRINTZ_CODEC_DELTA && !lowdim && !noheader && !cs &&
-            qs.q == kQueryOff && !qs.hc && ((uintptr_t)d_out % 4) == 0 && ((uintptr_t)d_comp % 4) == 0 && !process().no_fast.load(std::memory_order_relaxed)) {
-            const RowDecGeom g = row_dec_geom((uint32_t)esz, chunk_len, (uint32_t)D);
-            // where it wins (tools/blk_shapes.py, profiles/r6_blk_shapes.txt; 10 KB chunks, ms against the lane-per-column kernels): 8-bit rows of 32 / 48 / 64 / 80 /
-            // 128 / 256 columns 0.153 / 0.202 / 0.121 / 0.132 / 0.136 / 0.187 against 0.172 / 0.237 / 0.184 / 0.172 / 0.155 / 0.539; where it does not: 16 8-bit columns
-            // (4 lanes a chunk) 0.233 against 0.182, and 16-bit elements -- two fields a dword carry the same per-row work as four -- 8 / 16 / 24 / 128 columns 0.129 /
-            // 0.103 / 0.171 / 0.186 against 0.114 / 0.096 / 0.136 / 0.132 (32 and 64 columns level).  Mask bit 4 takes every shape the kernel fits (tests).
-            const bool wins = (esz == 1 && g.U >= 8u) || (process().blk_kernels.load(std::memory_order_relaxed) & 16);
-            // (32-bit offsets into the OUTPUT inside the kernel: a batch that decodes to 4 GB or more goes to the kernels below.  The container may lie
-            //  anywhere -- d_offsets are the caller's, and a stream's base is a 64-bit address there)
-            const bool below_4g = (uint64_t)nchunks * chunk_len * esz < 0xf0000000ull;
-            if (g.ok && below_4g && wins) {
-                const uint64_t rgrid = (nchunks + 4ull * g.G - 1) / (4ull * g.G);
-                if (rgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-                e = launch_decode_row(8 * esz, (unsigned)rgrid, st, a, g);
-                if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_row kernel launch", e);
-                dispatched(SPRINTZ_KF_DEC_ROW);
-                return 0;
-            }
-        }
-    }
-    // ... or the block-parallel decoder (decode_blk.h)
-    {
-        const int blk_from = process().blk_chunks.load(std::memory_order_relaxed);
-        if (blk_from > 0 && (process().blk_kernels.load(std::memory_order_relaxed) & 2) && nchunks >= (uint64_t)blk_from && codec == SPRINTZ_CODEC_DELTA && !lowdim && !noheader && !cs && qs.q == kQueryOff && !qs.hc &&
-            ((uintptr_t)d_out % 16) == 0 && !process().no_fast.load(std::memory_order_relaxed)) {
-            const BlkDecGeom g = blk_dec_geom((uint32_t)esz, chunk_len, (uint32_t)D, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims));
-            if (g.ok) {
-                const uint64_t bgrid = (nchunks + g.CPW - 1) / g.CPW;
-                if (bgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-                e = launch_decode_blk(8 * esz, (unsigned)bgrid, st, a, g);
-                if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_blk kernel launch", e);
-                dispatched(SPRINTZ_KF_DEC_BLK);
-                return 0;
-            }
-        }
-    }
-    if (fast) {
-        a.log2DP = 0;
-        while ((1 << a.log2DP) < fdp) a.log2DP++;
-        const size_t fgroups = kThreads / fdp;
-        // (padding the stride by 16 / 32 / 48 bytes to move the groups' staging rows onto other banks: no change, 0.4225 ms each)
-        const size_t fstride = decode_fast_lds_bytes(8 * esz, fdp, fcpl, D, cs != 0 && fcpl == 1, fds);
-        a.lds_group_stride = (uint32_t)fstride;
-        // consecutive chunks per lane group.  Measured on MI355X (cfg2, 131072 chunks): k = 1 / 2 / 4 /
-        // 8 -> 0.498 / 0.496 / 0.510 / 0.560 ms: one generation of lock-stepped groups is no faster
-        // than four staggered ones, so the default stays at one chunk per group (env knob for tuning).
-        a.chunks_per_group = (uint32_t)process().chunks_per_group.load(std::memory_order_relaxed);
-        const uint64_t ngroups_launch = (nchunks + a.chunks_per_group - 1) / a.chunks_per_group;
-        const uint64_t fthreads = ngroups_launch * (uint64_t)fdp;
-        const uint64_t fgrid = (fthreads + kThreads - 1) / kThreads;
-        if (fgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        e = esz == 1 ? launch_decode_fast_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, fcpl, D == fdp * fcpl, qs.q, fds, (unsigned)fgrid, fstride * fgroups, st, a)
-                     : launch_decode_fast_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, fcpl, D == fdp * fcpl, qs.q, fds, (unsigned)fgrid, fstride * fgroups, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_fast kernel launch", e);
-        dispatched(SPRINTZ_KF_DEC_FAST);
-        return 0;
-    }
-    // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
-    // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    if (lowdim && (D <= 2 || esz == 1) && !noheader && !cs && !process().no_fast.load(std::memory_order_relaxed)) {
-        const uint64_t ugrid = (nchunks + 255) / 256;
-        if (ugrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        e = esz == 1 ? launch_decode_uni_w8(codec == SPRINTZ_CODEC_XFF, D, qs.q, (unsigned)ugrid, st, a)
-                     : launch_decode_uni_w16(codec == SPRINTZ_CODEC_XFF, D, qs.q, (unsigned)ugrid, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_uni kernel launch", e);
-        dispatched(SPRINTZ_KF_DEC_UNI);
-        return 0;
-    }
-    const uint64_t threads = nchunks * (uint64_t)DP;
-    const uint64_t grid = (threads + kThreads - 1) / kThreads;
-    if (grid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-    e = esz == 1 ? launch_decode_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, qs.q, (unsigned)grid, shmem, st, a)
-                 : launch_decode_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, qs.q, (unsigned)grid, shmem, st, a);
-    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode kernel launch", e);
-    dispatched(SPRINTZ_KF_DEC_GENERIC);
+    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, what, e);
+    dispatched(p.family);
     return 0;
 }
 
-// what the encode launch needs to build the dense container itself (compact_tail.h); `fused` reports whether it did
+// plan (with this call's options) and launch
+int decode_batch(const Knobs& k, int codec, int esz, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims,
+                 void* d_out, int64_t* d_rets, hipStream_t st, int noheader, uint32_t nh_ngroups, uint32_t nh_remaining, const QuerySpec& qs = QuerySpec{})
+{
+    if (nchunks == 0) return 0;
+    return decode_launch(plan_decode(decode_shape(codec, esz, d_comp, nchunks, chunk_len, ndims, d_out, noheader, qs), k), esz, d_comp, d_offsets, nchunks,
+                         chunk_len, ndims, d_out, d_rets, st, noheader, nh_ngroups, nh_remaining, qs);
+}
+
+// where the encode launch builds the dense container itself (compact_tail.h; Plan::fused)
 struct DenseRequest {
     void* d_dense = nullptr;
     uint64_t* d_offsets = nullptr;
     void* d_tmp = nullptr;
-    bool fused = false;
 };
 
-// small batches: one WORKGROUP per chunk (encode_lat.h), the counterpart of decode_lat.h -- 90 us for ONE 10 KB chunk on a lane
-// group, ~20 with the coefficient chain and the RLE state machine as the only serial parts (the container, if one was asked
-// for, is then built by the scan + copy passes: dense->fused stays false)
-bool encode_lat_fits(int codec, int esz, uint64_t nchunks, uint32_t chunk_len, int D, uint64_t col_stride, const void* d_src, const void* d_slots, size_t slot_stride)
+Shape encode_shape(int codec, int esz, const void* d_src, uint64_t total_len, uint32_t chunk_len, uint16_t ndims, const void* d_slots, size_t slot_stride,
+                   int write_size, uint64_t col_stride, int general, bool dense, bool host_call)
 {
-    const bool norle = codec >= SPRINTZ_CODEC_DELTA_NORLE;
-    return !norle && !col_stride && D <= 64 && lat_chunk_fits(true, esz, nchunks, chunk_len, D) &&
-           ((uintptr_t)d_src % 16) == 0 && (nchunks == 1 || ((uint64_t)chunk_len * esz) % 16 == 0) && slot_stride % 16 == 0 && ((uintptr_t)d_slots % 16) == 0 &&
-           // (a chunk is read in 16-byte pieces from a 16-byte aligned start: the last piece may reach past its end, never past the piece that holds its last byte)
-           // (the encoder's crossover sits higher than the decoder's -- the lane-per-column encoders take ~100 us (uint16 x 8) / ~175 us (uint8 x 8)
-           //  for ANY batch up to ~16 000 chunks: 75 vs 100 us at 3 072 chunks, 105 vs 101 at 4 096; 32 columns: 24 vs 26 at 1 024 -- tools/lat_sweep_enc.py)
-           nchunks <= (uint64_t)process().lat_chunks.load(std::memory_order_relaxed) * (D > 16 ? 1u : 3u) / (D > 16 ? 3u : 2u) && !process().no_fast.load(std::memory_order_relaxed);
+    Shape s;
+    s.codec = codec; s.esz = esz; s.D = ndims; s.total_len = total_len; s.nchunks = sprintz_mi355x_num_chunks(total_len, chunk_len); s.chunk_len = chunk_len;
+    s.general = general; s.col_stride = col_stride; s.write_size = write_size; s.dense = dense; s.host_call = host_call;
+    s.src_lo = low4(d_src); s.slots_lo = low4(d_slots); s.slot_stride = slot_stride;
+    return s;
 }
 
-int encode_launch(int codec, int esz, const void* d_src, uint64_t total_len, uint32_t chunk_len, uint16_t ndims,
-                  void* d_slots, size_t slot_stride, uint32_t* d_sizes, int64_t* d_rets, hipStream_t st, int write_size,
-                  uint64_t col_stride = 0, int general = 0, DenseRequest* dense = nullptr, const HostCall* hc = nullptr)
+// launches what plan_encode (plan.h) decided for this call; `dense` is read only where the plan says the encoder builds the container
+int encode_launch(const Plan& p, int esz, const void* d_src, uint64_t total_len, uint32_t chunk_len, uint16_t ndims, void* d_slots, size_t slot_stride,
+                  uint32_t* d_sizes, int64_t* d_rets, hipStream_t st, int write_size, uint64_t col_stride = 0, const DenseRequest* dense = nullptr,
+                  const HostCall* hc = nullptr)
 {
+    // (the host paths hand over the plan they chose the ticket form by: not reached from there)
+    if (hc && p.family != SPRINTZ_KF_ENC_LAT) return fail(SPRINTZ_E_HIP, "internal: host call on a kernel that cannot end it");
+    if (p.plain_memory && !is_plain_device_memory(d_slots)) return fail(SPRINTZ_E_INVALID, "more than 2047 columns: the slots must be device memory (hipMalloc), not mapped host or managed memory");
+    if (p.err) return fail(p.err, p.what);
     const uint64_t nchunks = sprintz_mi355x_num_chunks(total_len, chunk_len);
-    if (nchunks == 0) return 0;
-    const int D = ndims;
-    const bool norle = codec >= SPRINTZ_CODEC_DELTA_NORLE;
-    const bool lowdim = (norle || general) ? false : is_lowdim(esz, D);
-    const Mapping m = choose_mapping(D, lowdim);
-    const int DP = 1 << m.log2DP;
 
     EncodeArgs a{};
     a.src = d_src;
     a.total_len = total_len;
     a.chunk_len = chunk_len;
     a.nchunks = nchunks;
-    a.D = D;
-    a.log2DP = m.log2DP;
+    a.D = ndims;
+    a.log2DP = p.log2DP;
     a.slots = (uint8_t*)d_slots;
     a.slot_stride = slot_stride;
     a.sizes = d_sizes;
     a.rets = d_rets;
     a.write_size = write_size;
     a.col_stride = col_stride;
-    a.norle = norle ? (codec == SPRINTZ_CODEC_XFF_NORLE ? 2 : 1) : 0;
-    a.raw = codec == SPRINTZ_CODEC_BITPACK_NORLE ? 1 : 0;
-    // 513 .. 2047 columns: one workgroup per chunk, the window holds one stream group (any_ndims.hip)
-    if (D > 512) {
-        if (norle || col_stride) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: the RLE codecs, row-major only");
-        if (nchunks > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        if (D > 2047) {                                        // column tiles, fields OR-ed straight into the zeroed slot (any_ndims.hip, "big")
-            if (slot_stride % 16 || ((uintptr_t)d_slots & 15)) return fail(SPRINTZ_E_INVALID, "more than 2047 columns: slots must be 16-byte aligned and a multiple of 16 bytes");
-            if (!is_plain_device_memory(d_slots)) return fail(SPRINTZ_E_INVALID, "more than 2047 columns: the slots must be device memory (hipMalloc), not mapped host or managed memory");
-            int32_t* counters = nullptr;
-            const bool fire = codec == SPRINTZ_CODEC_XFF;
-            if (fire && (uint64_t)nchunks * (uint64_t)D * 4 > (1ull << 30)) return fail(SPRINTZ_E_UNSUPPORTED, "more than 2047 columns, FIRE: the counters' scratch (nchunks x ndims x 4 bytes) is limited to 1 GiB a launch: split the batch");
-            if (fire && hipMallocAsync((void**)&counters, (size_t)nchunks * (size_t)D * 4, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "hipMallocAsync of the counters' scratch (not available during stream capture)");
-            const hipError_t eb = launch_encode_big(8 * esz, fire, (unsigned)nchunks, st, a, counters);
-            if (counters) (void)hipFreeAsync(counters, st);
-            if (eb != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_big kernel launch", eb);
-            dispatched(SPRINTZ_KF_ENC_BIG);
-            return 0;
-        }
-        a.cap = ((uint32_t)group_bytes_max(esz, D) + 64u + 15u) & ~15u;
-        const hipError_t ea = launch_encode_any(8 * esz, codec == SPRINTZ_CODEC_XFF, (unsigned)nchunks, a.cap, st, a);
-        if (ea != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_any kernel launch", ea);
-        dispatched(SPRINTZ_KF_ENC_ANY);
-        return 0;
-    }
-    // the generic kernel's window is a power-of-two RING flushed in 16-byte pieces; the kernels that flush whole 128-byte lines
-    // (encode_fast.h, encode_wide.h) need that much more room in front of the write position: cap_drain (theirs alone -- added
-    // to every encoder it doubled the generic ring wherever the group sat just under a power of two)
-    a.cap = next_pow2((uint32_t)group_bytes_max(esz, D) + 48u);
-    const uint32_t cap_drain = next_pow2((uint32_t)group_bytes_max(esz, D) + 48u + (uint32_t)(SPRINTZ_ENC_DRAIN_ALIGN - 16));
-    const size_t shmem = ((size_t)a.cap + 16) * (kThreads / DP);
-    if (shmem > 160 * 1024) return fail(SPRINTZ_E_UNSUPPORTED, "ndims too large for the LDS output ring");
-
-    // Fast path (encode_fast.h): general layout, one column per lane, every 8 x D input
-    // block 16-byte aligned, the power-of-two group at least half full.
-    int fdp = 4;
-    while (fdp < D) fdp <<= 1;
-    const size_t blk_bytes = (size_t)8 * D * esz;
-    const bool fast_common = !lowdim && !a.raw && D <= 64 && 2 * D > fdp && ((uintptr_t)d_src % 16) == 0 && !process().no_fast.load(std::memory_order_relaxed);
-    const bool fast = col_stride ? fast_common && col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0
-                                 : fast_common && blk_bytes % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0;
-    hipError_t e;
-    if (hc && !encode_lat_fits(codec, esz, nchunks, chunk_len, D, col_stride, d_src, d_slots, slot_stride)) return fail(SPRINTZ_E_HIP, "internal: host call on a kernel that cannot end it");
-    if (encode_lat_fits(codec, esz, nchunks, chunk_len, D, col_stride, d_src, d_slots, slot_stride)) {
-        if (hc) { a.host_flag = hc->flag; a.host_ticket = hc->ticket; }
-        int ldp = 4;
-        while (ldp < D) ldp <<= 1;
-        if (esz == 1 && ldp < 8 && !lowdim) ldp = 8;
-        e = launch_encode_lat(8 * esz, codec == SPRINTZ_CODEC_XFF, ldp, lowdim, (unsigned)nchunks, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims), st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_lat kernel launch", e);
-        dispatched(SPRINTZ_KF_ENC_LAT);
-        return 0;
-    }
-    // large batches of the DELTA codec, general layout, rows of whole 16-byte pieces: the block-parallel encoder (encode_blk.h) -- a thread
-    // per (block, 16-byte row piece), the RLE state machine as scans; the container, if one was asked for, by the scan + copy passes.
-    // (The container inside this launch -- images flushed straight to their place, found by compact_tail.h's chained scan -- was built and
-    //  measured on BASELINE config 3 at 10 KB, 17 476 workgroups of three chunks: 0.296 ms against 0.267 for the launches in a row.  Taken
-    //  apart: no scan, no tickets 0.177; tickets alone +0.070 (17 476 atomics on one word); the look-back alone +0.089 with 256 predecessors
-    //  a hop, +0.114 with 1 024 -- a workgroup that lives 10 us waits for the slowest of a thousand resident predecessors with 33 KB of LDS
-    //  held.  The tail pays from 64 chunks a workgroup on, as on the lane-per-column kernels.
-    //  Second form: a workgroup takes 16 / 32 / 64 chunks in passes of three and ends with compact_tail.h's dense_tail (slot -> container copy, one
-    //  chained-scan step per workgroup): 0.352 / 0.369 / 0.432 ms against 0.280 on the same box -- the looped kernel needs 149 registers (3 waves a
-    //  SIMD instead of 4) and 820 - 3 277 workgroups are one to three cohorts: the tails do not hide behind anybody's encoding.
-    //  Third form, priced before it was built: encoders that never wait -- they flush to their slots with write-through (sc0 sc1) stores, wait for
-    //  them and add their size to their block's word; the block's last finisher finds the block's place (a look-back over a few hundred blocks) and
-    //  copies it.  The encoder's side alone (the stores, the s_waitcnt, one atomic a chunk; no placement at all) measured 0.302 against 0.270 ms for
-    //  the whole compress call: a third of the 0.098 ms the scan + copy launches cost is gone before the placers' copies and the last block's tail.)
-    {
-        const int blk_from = process().blk_chunks.load(std::memory_order_relaxed);
-        const int blk_which = process().blk_kernels.load(std::memory_order_relaxed);
-        if (blk_from > 0 && (blk_which & 1) && nchunks >= (uint64_t)blk_from && codec == SPRINTZ_CODEC_DELTA && !lowdim && !col_stride && !hc && write_size &&
-            ((uintptr_t)d_src % 16) == 0 && slot_stride % 16 == 0 && ((uintptr_t)d_slots % 16) == 0 && !process().no_fast.load(std::memory_order_relaxed)) {
-            const BlkEncGeom g = blk_enc_geom((uint32_t)esz, chunk_len, (uint32_t)D, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims));
-            if (g.ok) {
-                const uint64_t bgrid = (nchunks + g.CPW - 1) / g.CPW;
-                if (bgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-                e = launch_encode_blk(8 * esz, (unsigned)bgrid, st, a, g);
-                if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_blk kernel launch", e);
-                dispatched(SPRINTZ_KF_ENC_BLK);
-                return 0;
-            }
-        }
-        // the same for univariate streams of the low-dim layout (BASELINE config 1): a thread per 16 bytes of the series
-        if (blk_from > 0 && (blk_which & 4) && nchunks >= (uint64_t)blk_from && codec == SPRINTZ_CODEC_DELTA && lowdim && D == 1 && !col_stride && !hc && write_size &&
-            ((uintptr_t)d_src % 16) == 0 && slot_stride % 16 == 0 && ((uintptr_t)d_slots % 16) == 0 && !process().no_fast.load(std::memory_order_relaxed)) {
-            const BlkEncGeom g = blk_enc_uni_geom((uint32_t)esz, chunk_len, (uint32_t)sprintz_mi355x_compress_bound(esz, chunk_len, ndims));
-            if (g.ok) {
-                const uint64_t bgrid = (nchunks + g.CPW - 1) / g.CPW;
-                if (bgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-                e = launch_encode_blk_uni(8 * esz, (unsigned)bgrid, st, a, g);
-                if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_blk_uni kernel launch", e);
-                dispatched(SPRINTZ_KF_ENC_BLK_UNI);
-                return 0;
-            }
-        }
-    }
-    // the container built inside the launch (compact_tail.h): every kernel of encode_fast.h / encode_wide.h carries the tail
-    auto arm_dense = [&](uint64_t grid, size_t groups) -> int {
-        // (column-major sources keep the two-launch path: with the tail in encode_fast<CM> BASELINE config 5 took 0.089 instead of 0.076 ms, its
-        //  8 M-row form 0.407 instead of 0.359 -- eight chunks a workgroup make the chained scan eight times as long per byte as sixty-four do)
-        //  Measured likewise on the row-major kernels: 8 uint16 columns (64 chunks a workgroup) 0.661 with the tail, 0.670 without; 16 columns (32 chunks)
-        //  0.148 / 0.142; 64 columns (8) 0.158 / 0.144; BASELINE config 3 at 10 KB (8) 0.431 / 0.408 -- the tail pays from 64 chunks a workgroup on.
-        if (!(dense && dense->d_dense && groups == 64) || col_stride) return 0;
+    a.norle = p.norle;
+    a.raw = p.raw;
+    a.cap = p.cap;
+    a.lds_group_stride = p.lds_group_stride;
+    if (p.fused) {
         a.dn.dense = (uint8_t*)dense->d_dense;
         a.dn.offsets = dense->d_offsets;
         a.dn.wg_state = (uint64_t*)dense->d_tmp;
-        a.dn.grid = (uint32_t)grid;
-        HIP_TRY(hipMemsetAsync(dense->d_tmp, 0, ((size_t)grid + 1) * sizeof(uint64_t), st));   // look-back words + the ticket counter
-        dense->fused = true;
-        return 0;
-    };
-    // two columns per lane for narrow row-major streams too (encode_wide.h with 4 .. 32 lanes a chunk): fewer instructions per sample
-    // than encode_fast.h's one column per lane on every shape measured (tools/enc_pair_sweep.sh: -6 % .. -35 %)
-    // (not for a handful of chunks: there a chunk's latency is what counts, and half the lanes per chunk make it longer -- a single 10 KB
-    //  sprintz_compress_xff_16b call 127 us against 111 with one column per lane; from a thousand chunks on the two are level or better)
-    const int pair_from = process().enc_pair.load(std::memory_order_relaxed);
-    // (column-major sources too: encode_fast.h's bursts, two columns' blocks per lane)
-    const bool pair_layout = col_stride ? col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0
-                                        : blk_bytes % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0;
-    if (pair_from > 0 && nchunks >= (uint64_t)pair_from && fast_common && D >= 5 && pair_layout && (uint64_t)chunk_len * esz >= 2 * blk_bytes) {
-        int pdp = 4;
-        while (2 * pdp < D) pdp <<= 1;
-        const size_t pgroups = kThreads / pdp;
-        // the window as long as it must be (the linear window needs no power of two): 592 instead of 672 bytes a chunk at 8 uint16 columns,
-        // four workgroups a CU instead of three
-        a.cap = ((uint32_t)group_bytes_max(esz, D) + 48u + (uint32_t)(SPRINTZ_ENC_DRAIN_ALIGN - 16) + 15u) & ~15u;
-        // input staging: one 8 x D block (row-major: LDS transpose) or a burst of 4 blocks x (2 * pdp) columns (column-major)
-        const size_t pstage = col_stride ? (size_t)4 * (2 * pdp) * (esz == 2 ? 16 : 8) : ((blk_bytes + 15) & ~(size_t)15);
-        a.lds_group_stride = (uint32_t)(a.cap + pstage + 16);
-        if ((a.lds_group_stride / 16) % 2 == 0) a.lds_group_stride += 16;    // an odd number of 16-byte units: the chunks of a wavefront start on different banks
-        const uint64_t pgrid = (nchunks * (uint64_t)pdp + kThreads - 1) / kThreads;
-        if (pgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        if (int rc = arm_dense(pgrid, pgroups)) return rc;
-        const bool pfire = codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE;
+        a.dn.grid = (uint32_t)p.grid;
+        HIP_TRY(hipMemsetAsync(dense->d_tmp, 0, ((size_t)p.grid + 1) * sizeof(uint64_t), st));   // look-back words + the ticket counter
+    }
+
+    const int w = 8 * esz;
+    const unsigned grid = (unsigned)p.grid;
+    hipError_t e = hipSuccess;
+    const char* what = "";
+    switch (p.family) {
+    case SPRINTZ_KF_ENC_BIG: {
+        int32_t* counters;
+        if (int rc = alloc_counters(p, nchunks, ndims, st, &counters)) return rc;
+        e = launch_encode_big(w, p.counters, grid, st, a, counters);
+        if (counters) (void)hipFreeAsync(counters, st);
+        what = "encode_big kernel launch";
+        break;
+    }
+    case SPRINTZ_KF_ENC_ANY: what = "encode_any kernel launch"; e = launch_encode_any(w, p.fire, grid, (size_t)p.lds, st, a); break;
+    case SPRINTZ_KF_ENC_LAT:
+        what = "encode_lat kernel launch";
+        if (hc) { a.host_flag = hc->flag; a.host_ticket = hc->ticket; }
+        e = launch_encode_lat(w, p.fire, p.dp, p.lowdim, grid, p.lat_bound, st, a);
+        break;
+    case SPRINTZ_KF_ENC_BLK: what = "encode_blk kernel launch"; e = launch_encode_blk(w, grid, st, a, p.blke); break;
+    case SPRINTZ_KF_ENC_BLK_UNI: what = "encode_blk_uni kernel launch"; e = launch_encode_blk_uni(w, grid, st, a, p.blke); break;
+    case SPRINTZ_KF_ENC_PAIR: {
         // (experiment knob: extra, unused LDS a workgroup claims -- fewer resident waves; what occupancy is worth to this loop: DESIGN 4.4)
         static const size_t lds_pad = getenv("SPRINTZ_MI355X_ENC_LDS_PAD") ? (size_t)atol(getenv("SPRINTZ_MI355X_ENC_LDS_PAD")) : 0;
-        e = esz == 1 ? launch_encode_pair_w8(pfire, pdp, D == 2 * pdp, (unsigned)pgrid, (size_t)a.lds_group_stride * pgroups + lds_pad, st, a)
-                     : launch_encode_pair_w16(pfire, pdp, D == 2 * pdp, (unsigned)pgrid, (size_t)a.lds_group_stride * pgroups + lds_pad, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_wide (pair) kernel launch", e);
-        dispatched(SPRINTZ_KF_ENC_PAIR);
-        return 0;
+        e = esz == 1 ? launch_encode_pair_w8(p.fire, p.dp, p.exact, grid, (size_t)p.lds + lds_pad, st, a)
+                     : launch_encode_pair_w16(p.fire, p.dp, p.exact, grid, (size_t)p.lds + lds_pad, st, a);
+        what = "encode_wide (pair) kernel launch";
+        break;
     }
-    if (fast) {
-        const size_t fgroups = kThreads / fdp;
-        a.cap = cap_drain;
-        // input staging: one 8 x D block (row-major: LDS transpose) or two bursts of 4 blocks x fdp columns (column-major)
-        const size_t in_stage = col_stride ? (size_t)4 * fdp * (esz == 2 ? 16 : 8) : ((blk_bytes + 15) & ~(size_t)15);
-        a.lds_group_stride = (uint32_t)(a.cap + in_stage + 16);
-        const size_t fshmem = (size_t)a.lds_group_stride * fgroups;
-        const uint64_t fthreads = nchunks * (uint64_t)fdp;
-        const uint64_t fgrid = (fthreads + kThreads - 1) / kThreads;
-        if (fgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        if (int rc = arm_dense(fgrid, fgroups)) return rc;
-        e = esz == 1 ? launch_encode_fast_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, D == fdp, (unsigned)fgrid, fshmem, st, a)
-                     : launch_encode_fast_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), fdp, D == fdp, (unsigned)fgrid, fshmem, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_fast kernel launch", e);
-        dispatched(SPRINTZ_KF_ENC_FAST);
-        return 0;
+    case SPRINTZ_KF_ENC_FAST:
+        what = "encode_fast kernel launch";
+        e = esz == 1 ? launch_encode_fast_w8(p.fire, p.dp, p.exact, grid, (size_t)p.lds, st, a) : launch_encode_fast_w16(p.fire, p.dp, p.exact, grid, (size_t)p.lds, st, a);
+        break;
+    case SPRINTZ_KF_ENC_SPLIT: what = "encode_wide kernel launch"; e = launch_encode_split_w8(p.fire, grid, (size_t)p.lds, st, a); break;
+    case SPRINTZ_KF_ENC_WIDE:
+        what = "encode_wide kernel launch";
+        e = esz == 1 ? launch_encode_wide_w8(p.fire, p.exact, grid, (size_t)p.lds, st, a) : launch_encode_wide_w16(p.fire, p.exact, grid, (size_t)p.lds, st, a);
+        break;
+    case SPRINTZ_KF_ENC_UNI: what = "encode_uni kernel launch"; e = esz == 1 ? launch_encode_uni_w8(p.fire, ndims, grid, st, a) : launch_encode_uni_w16(p.fire, ndims, grid, st, a); break;
+    default: what = "encode kernel launch"; e = esz == 1 ? launch_encode_w8(p.fire, p.lowdim, p.cpl, grid, (size_t)p.lds, st, a) : launch_encode_w16(p.fire, p.lowdim, p.cpl, grid, (size_t)p.lds, st, a); break;
     }
-    // streams of 65 .. 128 columns (BASELINE config 3): two columns per lane (encode_wide.h)
-    if (!lowdim && !a.raw && !col_stride && D > 64 && D <= 128 && blk_bytes % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0 &&
-        (uint64_t)chunk_len * esz >= 2 * blk_bytes && ((uintptr_t)d_src % 16) == 0 && !process().no_fast.load(std::memory_order_relaxed)) {
-        // (8 bits, 65 .. 80 columns: 32 lanes a chunk -- a pair + a single column per lane -- two chunks a wavefront)
-        const bool wsplit = esz == 1 && D <= 80 && process().split_lanes.load(std::memory_order_relaxed) != 0;
-        const size_t wlanes = wsplit ? 32 : 64, wgroups = kThreads / wlanes;
-        a.cap = cap_drain;
-        a.lds_group_stride = (uint32_t)(a.cap + ((blk_bytes + 15) & ~(size_t)15) + 16);
-        const uint64_t wgrid = (nchunks * (uint64_t)wlanes + kThreads - 1) / kThreads;
-        if (wgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        if (int rc = arm_dense(wgrid, wgroups)) return rc;
-        const bool wfire = codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE;
-        e = wsplit   ? launch_encode_split_w8(wfire, (unsigned)wgrid, (size_t)a.lds_group_stride * wgroups, st, a)
-          : esz == 1 ? launch_encode_wide_w8(wfire, D == 128, (unsigned)wgrid, (size_t)a.lds_group_stride * wgroups, st, a)
-                     : launch_encode_wide_w16(wfire, D == 128, (unsigned)wgrid, (size_t)a.lds_group_stride * wgroups, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_wide kernel launch", e);
-        dispatched(wsplit ? SPRINTZ_KF_ENC_SPLIT : SPRINTZ_KF_ENC_WIDE);
-        return 0;
-    }
-    // univariate streams: one lane per chunk, quad-loaded 64-byte input windows, 64-byte output units (encode_uni.h)
-    // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    if (lowdim && (D <= 2 || esz == 1) && !col_stride && !process().no_fast.load(std::memory_order_relaxed)) {
-        const uint64_t ugrid = (nchunks + 255) / 256;
-        if (ugrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        // (round 6: the container inside THIS launch was built too -- 256 chunks a workgroup, 2 048 workgroups on BASELINE config 1, a short chain --
-        //  and measured: 0.405 ms with a lane-parallel copy (a piece's chunk found by bisection), 0.49 - 0.51 chunk by chunk, against 0.3945 for
-        //  encode + scan + copy in a row: streams of ~440 bytes re-read from their slots cost the workgroup what the copy pass costs.  Not kept.)
-        e = esz == 1 ? launch_encode_uni_w8(codec == SPRINTZ_CODEC_XFF, D, (unsigned)ugrid, st, a)
-                     : launch_encode_uni_w16(codec == SPRINTZ_CODEC_XFF, D, (unsigned)ugrid, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode_uni kernel launch", e);
-        dispatched(SPRINTZ_KF_ENC_UNI);
-        return 0;
-    }
-    const uint64_t threads = nchunks * (uint64_t)DP;
-    const uint64_t grid = (threads + kThreads - 1) / kThreads;
-    if (grid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-    e = esz == 1 ? launch_encode_w8((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, (unsigned)grid, shmem, st, a)
-                 : launch_encode_w16((codec == SPRINTZ_CODEC_XFF || codec == SPRINTZ_CODEC_XFF_NORLE), lowdim, m.cpl, (unsigned)grid, shmem, st, a);
-    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode kernel launch", e);
-    dispatched(SPRINTZ_KF_ENC_GENERIC);
+    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, what, e);
+    dispatched(p.family);
     return 0;
+}
+
+// plan (with this call's options) and launch; slots only: no container
+int encode_batch(const Knobs& k, int codec, int esz, const void* d_src, uint64_t total_len, uint32_t chunk_len, uint16_t ndims, void* d_slots,
+                 size_t slot_stride, uint32_t* d_sizes, int64_t* d_rets, hipStream_t st, int write_size, uint64_t col_stride = 0, int general = 0)
+{
+    if (sprintz_mi355x_num_chunks(total_len, chunk_len) == 0) return 0;
+    return encode_launch(plan_encode(encode_shape(codec, esz, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, write_size, col_stride, general, false, false), k),
+                         esz, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, write_size, col_stride);
 }
 
 // RAII device buffer for the host-pointer wrappers
@@ -1237,6 +925,8 @@ int64_t compress_host(int codec, int esz, const void* src, uint32_t len, void* d
     const size_t bound = sprintz_mi355x_compress_bound(esz, len, ndims);
     const size_t src_bytes = (size_t)len * esz;
     CallGuard inside;
+    const Knobs knobs = snapshot();
+    const int general = layout == SPRINTZ_LAYOUT_GENERAL;
     // ---- the zero-copy call (everything that fits the staging buffer; the RLE codecs, whose encoders only WRITE their slot):
     // memcpy into the mapped staging buffer -> stage_in + encoder on the thread's stream, the encoder's slot, size and return
     // value landing straight in the staging buffer -> ONE wait -> memcpy out.  No copy engine, no memset, no second round trip.
@@ -1251,19 +941,21 @@ int64_t compress_host(int codec, int esz, const void* src, uint32_t len, void* d
         memcpy(sc->pin + p_meta, &size, 4);
         memcpy(sc->pin + p_meta + 8, &ret, 8);
         // one chunk the workgroup-per-chunk encoder takes: it reads the staging buffer itself (one wide read, as stage_in's) and
-        // ends the call by writing the ticket -- ONE launch, no runtime wait
-        if (encode_lat_fits(codec, esz, 1, len, ndims, 0, sc->pin_dev, sc->pin_dev + p_slot, bound)) {
+        // ends the call by writing the ticket -- ONE launch, no runtime wait.  Planned ONCE, for the staging addresses: the plan that
+        // chooses the ticket form is the plan the launcher runs
+        const Plan zc = plan_encode(encode_shape(codec, esz, sc->pin_dev, len, len, ndims, sc->pin_dev + p_slot, bound, write_size, 0, general, false, true), knobs);
+        if (zc.family == SPRINTZ_KF_ENC_LAT) {
             HostCall hc;
             hc.flag = sc->flag_dev;
             hc.ticket = ++sc->ticket;
-            rc = encode_launch(codec, esz, sc->pin_dev, len, len, ndims, sc->pin_dev + p_slot, bound, (uint32_t*)(sc->pin_dev + p_meta),
-                               (int64_t*)(sc->pin_dev + p_meta + 8), sc->stream, write_size, 0, layout == SPRINTZ_LAYOUT_GENERAL, nullptr, &hc);
+            rc = encode_launch(zc, esz, sc->pin_dev, len, len, ndims, sc->pin_dev + p_slot, bound, (uint32_t*)(sc->pin_dev + p_meta),
+                               (int64_t*)(sc->pin_dev + p_meta + 8), sc->stream, write_size, 0, nullptr, &hc);
             if (rc) return rc;
             if ((rc = wait_flag(sc, hc.ticket, spin_wait(inside.n)))) { (void)hipStreamSynchronize(sc->stream); *sc->flag = 0; return rc; }   // nothing of this call may still target sc->pin / sc->flag when the scratch is reused
         } else {
             if ((rc = stage_in(sc, 0, 0, src_bytes))) return rc;
-            rc = encode_launch(codec, esz, sc->dev, len, len, ndims, sc->pin_dev + p_slot, bound, (uint32_t*)(sc->pin_dev + p_meta),
-                               (int64_t*)(sc->pin_dev + p_meta + 8), sc->stream, write_size, 0, layout == SPRINTZ_LAYOUT_GENERAL);
+            rc = encode_batch(knobs, codec, esz, sc->dev, len, len, ndims, sc->pin_dev + p_slot, bound, (uint32_t*)(sc->pin_dev + p_meta),
+                              (int64_t*)(sc->pin_dev + p_meta + 8), sc->stream, write_size, 0, general);
             if (rc) { (void)hipStreamSynchronize(sc->stream); return rc; }   // stage_in may still be reading sc->pin
             if ((rc = wait_call(sc, inside.n))) return rc;
         }
@@ -1288,8 +980,7 @@ int64_t compress_host(int codec, int esz, const void* src, uint32_t len, void* d
     int64_t* d_ret = (int64_t*)(sc->dev + o_meta + 8);
     // the scratch is reused: a kernel that never reports must read as an error (size 0xffffffff > bound), not as the last call's answer
     HIP_TRY(hipMemsetAsync(d_size, 0xff, 16, sc->stream));
-    rc = encode_launch(codec, esz, sc->dev, len, len, ndims, sc->dev + o_slot, bound, d_size, d_ret, sc->stream, write_size, 0,
-                       layout == SPRINTZ_LAYOUT_GENERAL);
+    rc = encode_batch(knobs, codec, esz, sc->dev, len, len, ndims, sc->dev + o_slot, bound, d_size, d_ret, sc->stream, write_size, 0, general);
     if (rc) { (void)hipStreamSynchronize(sc->stream); return rc; }   // the H2D copy out of sc->pin may still be in flight
     uint32_t size = 0;
     int64_t ret = 0;
@@ -1334,6 +1025,7 @@ int64_t decode_host_common(int codec, int esz, const uint8_t* s, uint64_t nbytes
     const size_t out_bytes = (size_t)nelems * esz;
     const bool want_out = !qspec || qspec->q != kQueryReduceOnly;
     CallGuard inside;
+    const Knobs knobs = snapshot();
     // ---- the zero-copy call (plain decodes that fit the staging buffer): memcpy the stream into the mapped staging buffer ->
     // stage_in + decoder on the thread's stream, the decoder writing samples and its return value straight into the staging
     // buffer -> ONE wait -> memcpy out.   staging: [offsets[2] | stream | ret (16 B) | out]      device: [offsets[2] | stream + slack]
@@ -1347,21 +1039,22 @@ int64_t decode_host_common(int codec, int esz, const uint8_t* s, uint64_t nbytes
         memcpy(sc->pin, meta, 16);
         memcpy(sc->pin + 16, s, nbytes);
         memcpy(sc->pin + p_ret, &ret, 8);
-        if (decode_lat_fits(codec, esz, 1, (uint32_t)nelems, ndims, noheader, QuerySpec{}, sc->pin_dev + p_out)) {   // (see compress_host)
-            HostCall hc;
-            hc.off0 = 16; hc.off1 = 16 + nbytes;
-            hc.flag = sc->flag_dev;
+        HostCall hc;
+        hc.off0 = 16; hc.off1 = 16 + nbytes;
+        hc.flag = sc->flag_dev;
+        QuerySpec qs;
+        qs.hc = &hc;
+        const Plan zc = plan_decode(decode_shape(codec, esz, sc->pin_dev, 1, (uint32_t)nelems, ndims, sc->pin_dev + p_out, noheader, qs), knobs);   // (see compress_host)
+        if (zc.family == SPRINTZ_KF_DEC_LAT) {
             hc.ticket = ++sc->ticket;
-            QuerySpec qs;
-            qs.hc = &hc;
-            rc = decode_launch(codec, esz, sc->pin_dev, nullptr, 1, (uint32_t)nelems, ndims, sc->pin_dev + p_out,
+            rc = decode_launch(zc, esz, sc->pin_dev, nullptr, 1, (uint32_t)nelems, ndims, sc->pin_dev + p_out,
                                (int64_t*)(sc->pin_dev + p_ret), sc->stream, noheader, ngroups, remaining, qs);
             if (rc) return rc;
             if ((rc = wait_flag(sc, hc.ticket, spin_wait(inside.n)))) { (void)hipStreamSynchronize(sc->stream); *sc->flag = 0; return rc; }   // nothing of this call may still target sc->pin / sc->flag when the scratch is reused
         } else {
             if ((rc = stage_in(sc, 0, 0, 16 + nbytes))) return rc;
-            rc = decode_launch(codec, esz, sc->dev, (const uint64_t*)sc->dev, 1, (uint32_t)nelems, ndims, sc->pin_dev + p_out,
-                               (int64_t*)(sc->pin_dev + p_ret), sc->stream, noheader, ngroups, remaining, QuerySpec{});
+            rc = decode_batch(knobs, codec, esz, sc->dev, (const uint64_t*)sc->dev, 1, (uint32_t)nelems, ndims, sc->pin_dev + p_out,
+                              (int64_t*)(sc->pin_dev + p_ret), sc->stream, noheader, ngroups, remaining);
             if (rc) { (void)hipStreamSynchronize(sc->stream); return rc; }
             if ((rc = wait_call(sc, inside.n))) return rc;
         }
@@ -1394,8 +1087,8 @@ int64_t decode_host_common(int codec, int esz, const uint8_t* s, uint64_t nbytes
         qs.qres = (uint64_t*)(sc->dev + o_res);
         HIP_TRY(hipMemsetAsync(qs.qres, 0, res_bytes, sc->stream));
     }
-    rc = decode_launch(codec, esz, sc->dev, (const uint64_t*)sc->dev, 1, (uint32_t)nelems, ndims, want_out ? sc->dev + o_out : nullptr,
-                       d_ret, sc->stream, noheader, ngroups, remaining, qs);
+    rc = decode_batch(knobs, codec, esz, sc->dev, (const uint64_t*)sc->dev, 1, (uint32_t)nelems, ndims, want_out ? sc->dev + o_out : nullptr,
+                      d_ret, sc->stream, noheader, ngroups, remaining, qs);
     if (rc) { (void)hipStreamSynchronize(sc->stream); return rc; }   // the H2D copy out of sc->pin may still be in flight
     int64_t ret = 0;
     if (want_out && pin_out) {                                // ret and the samples in one copy
@@ -1626,25 +1319,10 @@ int sprintz_mi355x_dispatch_counts(uint64_t* counts, int capacity)
 }
 const char* sprintz_mi355x_dispatch_name(int family)
 {
-    static const char* const names[] = {"dec_big", "dec_any", "dec_verbatim", "dec_lat", "dec_row", "dec_blk", "dec_fast", "dec_uni", "dec_generic",
-                                        "gather_fast", "gather_generic",
-                                        "enc_big", "enc_any", "enc_lat", "enc_blk", "enc_blk_uni", "enc_pair", "enc_fast", "enc_wide", "enc_split", "enc_uni", "enc_generic",
-                                        "dense_fused", "dense_verbatim", "dense_compact",
-                                        "tr_chain", "tr_wave", "tr_levels", "on_chain", "on_three", "huf0_big", "huf0_sync", "huf0_default"};
-    static_assert(sizeof(names) / sizeof(names[0]) == SPRINTZ_KF_COUNT, "a name per SPRINTZ_KF_* family");
-    return family >= 0 && family < SPRINTZ_KF_COUNT ? names[family] : nullptr;
+    return family >= 0 && family < SPRINTZ_KF_COUNT ? kFamilyNames[family] : nullptr;
 }
 
-size_t sprintz_mi355x_compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)
-{
-    const size_t esz = (size_t)elem_bytes, D = ndims ? ndims : 1;
-    const size_t hb = elem_bytes == 1 ? 3 : 4;
-    const size_t hdr_bytes = (2 * D * hb + 7) / 8;
-    const size_t max_groups = chunk_len / (16 * D) + 1;
-    // header + per group (header + 2 run bytes worst case beyond raw) + raw payload + flush padding
-    const size_t b = 8 + max_groups * (hdr_bytes + 3) + (size_t)chunk_len * esz + 32;
-    return (b + (SPRINTZ_BOUND_ALIGN - 1)) & ~(size_t)(SPRINTZ_BOUND_ALIGN - 1);
-}
+size_t sprintz_mi355x_compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims) { return compress_bound(elem_bytes, chunk_len, ndims); }
 
 uint64_t sprintz_mi355x_num_chunks(uint64_t total_len, uint32_t chunk_len)
 {
@@ -1665,8 +1343,8 @@ int sprintz_mi355x_compress_batch(int codec, int elem_bytes, const void* d_src, 
         return fail(SPRINTZ_E_INVALID, "slot_stride below sprintz_mi355x_compress_bound");
     if ((rc = check_batch_tail(total_len, chunk_len, ndims))) return rc;
     if ((rc = ensure_device())) return rc;
-    return encode_launch(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets,
-                         (hipStream_t)hip_stream, 1);
+    return encode_batch(snapshot(), codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets,
+                        (hipStream_t)hip_stream, 1);
 }
 
 size_t sprintz_mi355x_compress_dense_tmp_bytes(uint64_t nchunks)
@@ -1697,15 +1375,11 @@ int sprintz_mi355x_compress_batch_dense(int codec, int elem_bytes, const void* d
         HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, st));
         return 0;
     }
-    // (Tried and dropped, measured on the headline batch: the batch in 4 parts, a part's scan + copy on a second stream while
-    //  the next part encodes -- 0.87 ms against 0.79 for the launches in a row; the kernels do not fill each other's gaps.)
-    const int mode = process().dense_mode.load(std::memory_order_relaxed);
-    // chunks too short for a group: all of them verbatim, all sizes known -- written straight into the container (see the kernel)
-    if (mode && (codec == SPRINTZ_CODEC_DELTA || codec == SPRINTZ_CODEC_XFF) && !is_lowdim(elem_bytes, ndims) &&
-        (chunk_len < 128u || chunk_len < 16u * (uint32_t)ndims) && chunk_len <= 0xffffu) {
-        const uint64_t grid = (nchunks * 64 + kThreads - 1) / kThreads;
-        if (grid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "too many chunks for one launch");
-        hipLaunchKernelGGL(verbatim_dense_kernel, dim3((unsigned)grid), dim3(kThreads), 0, st, (const uint8_t*)d_src, total_len, chunk_len,
+    Plan enc;                                               // (stays empty where the verbatim kernel takes the batch)
+    const Plan dp = plan_dense(encode_shape(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, 1, 0, 0, false, false), snapshot(), &enc);
+    if (dp.err && !enc.err) return fail(dp.err, dp.what);   // (the encoder's own refusal is encode_launch's to report, behind the checks it makes first)
+    if (dp.family == SPRINTZ_KF_DENSE_VERBATIM) {
+        hipLaunchKernelGGL(verbatim_dense_kernel, dim3((unsigned)dp.grid), dim3(kThreads), 0, st, (const uint8_t*)d_src, total_len, chunk_len,
                            (uint32_t)elem_bytes, (uint32_t)ndims, nchunks, (uint8_t*)d_dense, d_offsets, d_sizes, d_rets);
         HIP_TRY(hipGetLastError());
         dispatched(SPRINTZ_KF_DENSE_VERBATIM);
@@ -1715,9 +1389,9 @@ int sprintz_mi355x_compress_batch_dense(int codec, int elem_bytes, const void* d
     dr.d_dense = d_dense;
     dr.d_offsets = d_offsets;
     dr.d_tmp = d_tmp;
-    rc = encode_launch(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, 1, 0, 0, mode ? &dr : nullptr);
-    if (!rc && dr.fused) dispatched(SPRINTZ_KF_DENSE_FUSED);
-    if (rc || dr.fused) return rc;
+    rc = encode_launch(enc, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, 1, 0, &dr);
+    if (!rc && enc.fused) dispatched(SPRINTZ_KF_DENSE_FUSED);
+    if (rc || enc.fused) return rc;
     // shapes whose encoder has no dense tail (low-dim, more than 64 columns, misaligned blocks): the two-launch path
     return sprintz_mi355x_compact(d_slots, slot_stride, d_sizes, nchunks, 16, d_dense, d_offsets, d_tmp, hip_stream);
 }
@@ -1765,8 +1439,8 @@ int sprintz_mi355x_decompress_batch(int codec, int elem_bytes, const void* d_com
     if (chunk_len == 0) return fail(SPRINTZ_E_INVALID, "chunk_len == 0");
     if (!d_comp || !d_offsets || !d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
     if ((rc = ensure_device())) return rc;
-    return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets,
-                         (hipStream_t)hip_stream, 0, 0, 0);
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets,
+                        (hipStream_t)hip_stream, 0, 0, 0);
 }
 
 // ---- drop-in single-call API (host pointers)
@@ -1817,8 +1491,8 @@ int64_t sprintz_mi355x_compress_chunked_host(int codec, int elem_bytes, const vo
     HIP_TRY(d_tmp.alloc(sprintz_mi355x_compact_tmp_bytes(nchunks)));
     HIP_TRY(d_dense.alloc(stride * nchunks + SPRINTZ_MI355X_READ_SLACK));
     HIP_TRY(hipMemcpy(d_src.p, src, total_len * elem_bytes, hipMemcpyHostToDevice));
-    rc = encode_launch(codec, elem_bytes, d_src.p, total_len, chunk_len, ndims, d_slots.p, stride, (uint32_t*)d_sizes.p,
-                       nullptr, nullptr, 1);
+    rc = encode_batch(snapshot(), codec, elem_bytes, d_src.p, total_len, chunk_len, ndims, d_slots.p, stride, (uint32_t*)d_sizes.p,
+                      nullptr, nullptr, 1);
     if (rc) return rc;
     rc = sprintz_mi355x_compact(d_slots.p, stride, (const uint32_t*)d_sizes.p, nchunks, 1, d_dense.p, (uint64_t*)d_offs.p,
                                 d_tmp.p, nullptr);
@@ -1847,8 +1521,8 @@ int64_t sprintz_mi355x_decompress_chunked_host(int codec, int elem_bytes, const 
     HIP_TRY(d_rets.alloc(nchunks * 8));
     HIP_TRY(hipMemcpy(d_comp.p, comp, total, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_offs.p, offsets, (nchunks + 1) * 8, hipMemcpyHostToDevice));
-    rc = decode_launch(codec, elem_bytes, d_comp.p, (const uint64_t*)d_offs.p, nchunks, chunk_len, ndims, d_out.p,
-                       (int64_t*)d_rets.p, nullptr, 0, 0, 0);
+    rc = decode_batch(snapshot(), codec, elem_bytes, d_comp.p, (const uint64_t*)d_offs.p, nchunks, chunk_len, ndims, d_out.p,
+                      (int64_t*)d_rets.p, nullptr, 0, 0, 0);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     std::vector<int64_t> rets(nchunks);
@@ -1885,8 +1559,8 @@ int sprintz_mi355x_query_batch(int codec, int elem_bytes, const void* d_comp, co
     qs.qop = op;
     qs.qres = op ? d_partials : nullptr;
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
-                         0, 0, 0, qs);
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
 }
 
 int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
@@ -1917,8 +1591,8 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
     qs.win_min = (ops & SPRINTZ_QUERY_WIN_MIN) ? d_min : nullptr;
     qs.win_max = (ops & SPRINTZ_QUERY_WIN_MAX) ? d_max : nullptr;
     qs.win_sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
-    return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
-                         0, 0, 0, qs);
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
 }
 
 // ---------------------------------------------------------------- gather rows
@@ -1939,25 +1613,27 @@ int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, co
     if ((uintptr_t)d_starts % 8 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "gather_rows: d_starts and d_rets must be aligned to 8 bytes");
     const int D = ndims, esz = elem_bytes;
     const uint32_t R = chunk_len / ndims;
-    const uint64_t P = ((uint64_t)rows + R - 2) / R + 1;                 // the most chunks a range of `rows` rows can touch
+    const uint64_t P = gather_pieces(rows, R);
     if (nranges > (1ull << 40) || nranges * P > (1ull << 40)) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
     if ((rc = ensure_device())) return rc;
     if (nranges == 0) return 0;
     hipStream_t st = (hipStream_t)hip_stream;
 
-    const bool lowdim = is_lowdim(esz, D);
-    const Mapping m = choose_mapping(D, lowdim);
+    Shape s;
+    s.codec = codec; s.esz = esz; s.D = D; s.nchunks = nchunks; s.chunk_len = chunk_len; s.nranges = nranges; s.rows = rows; s.out_lo = low4(d_out);
+    const Plan p = plan_gather(s, snapshot());
     DecodeArgs a{};
     a.comp = (const uint8_t*)d_comp;
     a.offsets = d_offsets;
     a.nchunks = nchunks;
     a.chunk_len = chunk_len;
     a.D = D;
-    a.log2DP = m.log2DP;
+    a.log2DP = p.log2DP;
     a.out = d_out;
     a.rets = d_rets;
     a.chunks_per_group = 1;
-    a.quirk = decode_ref_quirk(codec, esz, lowdim) ? 1 : 0;
+    a.quirk = p.quirk;
+    a.lds_group_stride = p.lds_group_stride;
     a.g_starts = d_starts;
     a.g_nranges = nranges;
     a.g_rows = rows;
@@ -1967,39 +1643,18 @@ int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, co
         hipLaunchKernelGGL(gather_rets_fill, dim3((unsigned)((nranges + 255) / 256)), dim3(256), 0, st, d_rets, nranges, (int64_t)rows);
         HIP_TRY(hipGetLastError());
     }
-    const uint64_t slots = nranges * P;
-    const bool fire = codec == SPRINTZ_CODEC_XFF;
-
-    // decode_fast.h: the shapes the decode takes there, with rows of whole 16-byte store pieces, and both the container and the output
-    // within reach of one descriptor's 32-bit offsets.  The container's size is on the device; every container this library writes
-    // stays below nchunks * (compress_bound + alignment).  Everything else goes to the generic kernel: plain 64-bit addresses.
-    int fdp = 4, fcpl = 1;
-    while (fdp < D && fdp < 64) fdp <<= 1;
-    while (fdp * fcpl < D) fcpl <<= 1;
-    const size_t fstride = decode_fast_lds_bytes(8 * esz, fdp, fcpl, D, false, 0);
-    const uint64_t out_bytes = nranges * (uint64_t)rows * (uint64_t)D * esz;          // (nranges * P <= 2^40 and rows <= P * R: no wrap)
-    const uint64_t comp_bound = nchunks * (uint64_t)(sprintz_mi355x_compress_bound(esz, chunk_len, ndims) + 64);
-    const bool fast = !lowdim && D <= 256 && 2 * D > fdp * fcpl && (uint64_t)chunk_len * esz * 2 >= fstride && ((uint64_t)D * esz) % 16 == 0 &&
-                      ((uintptr_t)d_out % 16) == 0 && out_bytes < 0xf0000000ull && nchunks < (1ull << 32) && comp_bound < 0xf0000000ull &&
-                      !process().no_fast.load(std::memory_order_relaxed);
+    if (p.err) return fail(p.err, p.what);
     hipError_t e;
-    if (fast) {
-        a.log2DP = 0;
-        while ((1 << a.log2DP) < fdp) a.log2DP++;
-        const size_t fgroups = kThreads / fdp;
-        a.lds_group_stride = (uint32_t)fstride;
-        const uint64_t fgrid = (slots * (uint64_t)fdp + kThreads - 1) / kThreads;
-        if (fgrid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
-        e = launch_decode_fast_gather(8 * esz, fire, fdp, fcpl, D == fdp * fcpl, (unsigned)fgrid, fstride * fgroups, st, a);
-        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode_fast gather kernel launch", e);
-        dispatched(SPRINTZ_KF_GATHER_FAST);
-        return 0;
+    const char* what;
+    if (p.family == SPRINTZ_KF_GATHER_FAST) {
+        e = launch_decode_fast_gather(8 * esz, p.fire, p.dp, p.cpl, p.exact, (unsigned)p.grid, (size_t)p.lds, st, a);
+        what = "decode_fast gather kernel launch";
+    } else {
+        e = launch_decode_gather(8 * esz, p.fire, p.lowdim, p.cpl, (unsigned)p.grid, st, a);
+        what = "decode gather kernel launch";
     }
-    const uint64_t grid = ((slots << m.log2DP) + kThreads - 1) / kThreads;
-    if (grid > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "gather_rows: too many pieces for one launch");
-    e = launch_decode_gather(8 * esz, fire, lowdim, m.cpl, (unsigned)grid, st, a);
-    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "decode gather kernel launch", e);
-    dispatched(SPRINTZ_KF_GATHER_GENERIC);
+    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, what, e);
+    dispatched(p.family);
     return 0;
 }
 
@@ -2054,8 +1709,8 @@ int sprintz_mi355x_compress_batch_colmajor(int codec, int elem_bytes, const void
     if (slot_stride < sprintz_mi355x_compress_bound(elem_bytes, chunk_len, ndims))
         return fail(SPRINTZ_E_INVALID, "slot_stride below sprintz_mi355x_compress_bound");
     if ((rc = ensure_device())) return rc;
-    return encode_launch(codec, elem_bytes, d_src, nrows * (uint64_t)ndims, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets,
-                         (hipStream_t)hip_stream, 1, col_stride);
+    return encode_batch(snapshot(), codec, elem_bytes, d_src, nrows * (uint64_t)ndims, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets,
+                        (hipStream_t)hip_stream, 1, col_stride);
 }
 
 int sprintz_mi355x_compress_batch_colmajor_dense(int codec, int elem_bytes, const void* d_src, uint64_t nrows, uint64_t col_stride,
@@ -2085,10 +1740,12 @@ int sprintz_mi355x_compress_batch_colmajor_dense(int codec, int elem_bytes, cons
     dr.d_dense = d_dense;
     dr.d_offsets = d_offsets;
     dr.d_tmp = d_tmp;
-    rc = encode_launch(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, 1, col_stride, 0,
-                       process().dense_mode.load(std::memory_order_relaxed) ? &dr : nullptr);
-    if (!rc && dr.fused) dispatched(SPRINTZ_KF_DENSE_FUSED);
-    if (rc || dr.fused) return rc;
+    // (a column-major source never carries the container's tail -- plan.h, plan_encode -- so this is the two-launch path today)
+    const Knobs knobs = snapshot();
+    const Plan enc = plan_encode(encode_shape(codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, 1, col_stride, 0, knobs.dense_mode != 0, false), knobs);
+    rc = encode_launch(enc, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets, st, 1, col_stride, &dr);
+    if (!rc && enc.fused) dispatched(SPRINTZ_KF_DENSE_FUSED);
+    if (rc || enc.fused) return rc;
     return sprintz_mi355x_compact(d_slots, slot_stride, d_sizes, nchunks, 16, d_dense, d_offsets, d_tmp, hip_stream);
 }
 
@@ -2105,8 +1762,8 @@ int sprintz_mi355x_decompress_batch_colmajor(int codec, int elem_bytes, const vo
     if ((rc = ensure_device())) return rc;
     QuerySpec qs;
     qs.col_stride = col_stride;
-    return decode_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, rows_per_chunk * (uint32_t)ndims, ndims, d_out, d_rets,
-                         (hipStream_t)hip_stream, 0, 0, 0, qs);
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, rows_per_chunk * (uint32_t)ndims, ndims, d_out, d_rets,
+                        (hipStream_t)hip_stream, 0, 0, 0, qs);
 }
 
 // ---------------------------------------------------------------- non-RLE codecs, single call (host pointers)

@@ -23,43 +23,6 @@
 
 namespace sprintz {
 
-struct BlkDecGeom {
-    uint32_t P, NBC, T, CPW;
-    uint32_t img_cap;                                    // bytes of one chunk's stream image (multiple of 16)
-    uint32_t o_desc, o_psum, o_csum, o_info, total;      // LDS carve (bytes)
-    uint32_t invT, invP;                                 // ceil(2^16 / T), ceil(2^16 / P): n / d == (n * inv) >> 16 for n < 256, d <= 256
-    uint32_t ok;
-};
-
-inline BlkDecGeom blk_dec_geom(uint32_t esz, uint32_t chunk_len, uint32_t D, uint32_t bound_bytes)
-{
-    BlkDecGeom g{};
-    const uint32_t rowbytes = D * esz, hb = esz == 1 ? 3u : 4u;
-    if (rowbytes % 16u || ((uint64_t)chunk_len * esz) % 16u || chunk_len < 32u * D) return g;      // (>= 4 blocks: the scan's lanes are tasks)
-    if (2u * D > 16u * (hb == 3u ? 10u : 8u)) return g;  // a group header's 2 D fields over the walk's 16 lanes: 10 x 3 / 8 x 4 bits each (80 / 64 columns)
-    g.P = rowbytes / 16u;
-    g.NBC = chunk_len / (8u * D);
-    g.T = g.NBC * g.P;
-    if (g.T > 256u || g.NBC >= 32767u) return g;
-    g.img_cap = (bound_bytes + 64u + 15u) & ~15u;        // + the start's phase in its 16-byte piece, + windows that look past the last byte
-    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
-    uint32_t cpw = 256u / g.T;
-    if (cpw > 16u) cpw = 16u;                            // (four wavefronts walk four chunks each)
-    for (; cpw >= 1; cpw--) {
-        g.CPW = cpw;
-        g.o_desc = cpw * g.img_cap;
-        g.o_psum = g.o_desc + al(cpw * g.NBC * 8u);
-        g.o_csum = g.o_psum + al(cpw * g.T * 2u);
-        g.o_info = g.o_csum + cpw * g.T * 16u;
-        g.total = g.o_info + cpw * 16u;
-        if (g.total <= 64u * 1024u) break;
-    }
-    g.invT = (65536u + g.T - 1u) / g.T;
-    g.invP = (65536u + g.P - 1u) / g.P;
-    g.ok = cpw >= 1 ? 1u : 0u;
-    return g;
-}
-
 // bytewise / halfword-wise a + b
 template <int W> __device__ __forceinline__ uint32_t lanes_add(uint32_t a, uint32_t b)
 {

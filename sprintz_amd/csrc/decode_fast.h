@@ -977,19 +977,4 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     }   // chunk loop
 }
 
-// bytes of LDS one group needs in decode_fast_kernel
-constexpr uint32_t decode_fast_lds_bytes(int W, int DP, int CPL, int D, bool colmajor_burst = false, int DS = 0)
-{
-    const uint32_t unit = DP * 16 * CPL;
-    const uint32_t hb = W == 8 ? 3 : 4;
-    const uint32_t dcap = DS ? DS : DP * CPL;
-    const uint32_t hdrmax = (2 * dcap * hb + 7) / 8, blkmax = 8 * dcap * (W / 8);
-    const uint32_t cg = hdrmax + 2 * blkmax + 4;
-    const uint32_t rb = ((2 * (cg + 24) + 3 + unit - 1) / unit + 1) * unit;
-    const uint32_t apron = (cg + 24 + 8 + 15) & ~15u;
-    // column-major burst staging: 4 blocks of every column the group can hold + 4 row offsets
-    const uint32_t stage = colmajor_burst ? 4u * blkmax + 16 : ((8u * D * (W / 8) + 15) & ~15u) + 16;   // +16: spread groups over banks
-    return rb + apron + stage;
-}
-
 }  // namespace sprintz

@@ -65,13 +65,6 @@ struct DecodeArgs {
     uint32_t g_pieces;          // P: the most chunks a range can touch, (g_rows + R - 2) / R + 1
 };
 
-// Q (template): 0 = plain decode; 1 = decode + reduce; 2 = reduce only (nothing is written
-// to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only;
-// 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1
-constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4;
-// the modes that never store a decoded sample
-constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow; }
-
 // windowed query: one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the
 // accumulators start over from the identities (min = all ones, max = 0, sum = 0)
 template <int W>

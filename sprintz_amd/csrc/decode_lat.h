@@ -3,7 +3,7 @@
 // 10 000-chunk batches on eight).  Same streams, same samples, same return values as decode_fast.h / decode_kernel.h
 // (sprintz_xff_rle.cpp:569-1179, sprintz_delta_rle.cpp:418-772; the low-dim layouts of sprintz_{delta,xff}_lowdim.cpp as template
 // parameter LOW), headered RLE streams, ndims <= 64, chunks of at most 16 KB in batches (several workgroups a CU) and up to what a
-// workgroup's 150 KB of LDS holds (~40 KB of uint16, ~24 KB of uint8) for single calls and batches of at most 64 chunks (api.hip: lat_chunk_fits).
+// workgroup's 150 KB of LDS holds (~40 KB of uint16, ~24 KB of uint8) for single calls and batches of at most 64 chunks (plan.h: lat_chunk_fits; the carve is geom.h's lat_carve).
 //
 // decode_fast.h walks a chunk's 40 groups in 40 dependent steps of ~600 wave-instructions each: 50 us a chunk however few
 // chunks there are (a lone wave issues an instruction every 4 .. 8 cycles).  Only two things in the format are serial:
@@ -37,24 +37,6 @@
 #include "decode_fast.h"
 
 namespace sprintz {
-
-constexpr uint32_t kLatMaxChunkBytes = 16u << 10;     // the stream, the error image and the tables of ONE chunk must fit LDS
-constexpr uint32_t lat_align16(uint32_t x) { return (x + 15u) & ~15u; }
-// LDS carve: [stream: strm_cap + 32 | grp: NB + 3 pairs of words | err: one int per block element | sum: one word per (column, block)]
-struct LatCarve {
-    uint32_t strm_cap, o_grp, o_err, o_sum, total;
-};
-inline LatCarve lat_carve(uint32_t bound_bytes, uint32_t chunk_len, uint32_t D)
-{
-    LatCarve c;
-    const uint32_t nb = chunk_len / (8u * D);
-    c.strm_cap = lat_align16(bound_bytes + 32u);
-    c.o_grp = c.strm_cap + 32u;
-    c.o_err = c.o_grp + lat_align16((nb + 3u) * 8u + 16u);
-    c.o_sum = c.o_err + (nb + 1u) * 8u * D * 4u + 16u;      // (+1 block: phase C reads one block ahead)
-    c.total = c.o_sum + lat_align16(D * (nb | 1u) * 4u + 16u);
-    return c;
-}
 
 // LOW: the low-dim layout (D <= 4 at 8 bits, <= 2 at 16: sprintz_{delta,xff}_lowdim.cpp) -- column-major payload (a column's 8 values in
 // nbits bytes), no row padding, untruncated FIRE coefficient (counter >> 1; 32-bit multiply at 16 bits).  Its errors travel

@@ -14,7 +14,7 @@
 //     L1: a chunk's lanes read one contiguous stream front to back), all eight rows of a block in flight together.
 // 64 / U chunks a wavefront (cfg3: 20 lanes a chunk, 3 chunks a wave); ~60 registers: the waves that hide the loads' latency fit.
 // (A first form with 16 columns a lane -- 5 lanes a chunk -- had a quarter of the waves and 142 registers: 0.337 ms on cfg3, latency-bound.)
-// Shapes (api.hip): delta codec, general layout, rows of whole dwords, U <= 64, 4-byte aligned container and output, any chunk length that holds
+// Shapes (plan.h: plan_decode; RowDecGeom is geom.h's): delta codec, general layout, rows of whole dwords, U <= 64, 4-byte aligned container and output, any chunk length that holds
 // a group, an output below 4 GB.  The container may be of any size and the streams anywhere in it: a chunk's stream base is a 64-bit address.
 #pragma once
 
@@ -22,26 +22,6 @@
 #include "decode_blk.h"
 
 namespace sprintz {
-
-struct RowDecGeom {
-    uint32_t U;          // dwords per row = lanes per chunk
-    uint32_t G;          // chunks per wavefront = 64 / U
-    uint32_t invU;       // ceil(2^16 / U): lane / U == (lane * invU) >> 16 for lane < 64
-    uint32_t ok;
-};
-
-inline RowDecGeom row_dec_geom(uint32_t esz, uint32_t chunk_len, uint32_t D)
-{
-    RowDecGeom g{};
-    const uint32_t rowbytes = D * esz;
-    if (rowbytes % 4u || ((uint64_t)chunk_len * esz) % 4u || chunk_len < 16u * D) return g;
-    g.U = rowbytes / 4u;
-    if (g.U > 64u) return g;
-    g.G = 64u / g.U;
-    g.invU = (65536u + g.U - 1u) / g.U;
-    g.ok = 1u;
-    return g;
-}
 
 // An 8-byte window at bit address `bit` of the byte stream that starts `off` bytes behind the 4-byte aligned address `comp` (global memory):
 // one aligned 8-byte load; v_alignbit by sh gives the 32 bits at `bit`.  `comp` is the CHUNK's base -- the container's address + the stream's

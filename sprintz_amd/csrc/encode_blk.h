@@ -18,7 +18,7 @@
 // A workgroup of 256 threads takes as many whole chunks as it has threads for (tasks per chunk <= 256: chunks of at most ~25 KB
 // at 80 columns), so a block's samples stay in its thread's registers from the load to the last OR.
 //
-// Shapes it takes (api.hip: encode_blk_fits): delta codec, general layout, row bytes a multiple of 16, chunk bytes a multiple of
+// Shapes it takes (plan.h: plan_encode; BlkEncGeom is geom.h's): delta codec, general layout, row bytes a multiple of 16, chunk bytes a multiple of
 // 16, 16-byte aligned source, <= 256 tasks a chunk, the chunk images of a workgroup within 64 KB of LDS.
 #pragma once
 
@@ -27,44 +27,6 @@
 #include "group_ops.h"
 
 namespace sprintz {
-
-struct BlkEncGeom {
-    uint32_t P;          // 16-byte pieces per row
-    uint32_t NBC;        // whole blocks of a full chunk
-    uint32_t T;          // tasks per chunk = NBC * P (<= 256)
-    uint32_t CPW;        // chunks per workgroup
-    uint32_t GW;         // lanes per chunk in the walk: 16 / 32 / 64
-    uint32_t img_cap;    // bytes of one chunk's stream image (multiple of 16; >= compress_bound + 16)
-    uint32_t o_psum, o_rbits, o_wofs, o_info, total;     // LDS carve (bytes)
-    uint32_t ok;
-};
-
-inline BlkEncGeom blk_enc_geom(uint32_t esz, uint32_t chunk_len, uint32_t D, uint32_t bound_bytes)
-{
-    BlkEncGeom g{};
-    const uint32_t rowbytes = D * esz;
-    if (rowbytes % 16u || ((uint64_t)chunk_len * esz) % 16u || chunk_len < 16u * D) return g;
-    g.P = rowbytes / 16u;
-    g.NBC = chunk_len / (8u * D);
-    g.T = g.NBC * g.P;
-    if (g.T == 0 || g.T > 256u || g.NBC >= 32767u) return g;
-    g.GW = g.NBC > 32u ? 64u : g.NBC > 16u ? 32u : 16u;
-    const uint32_t by_tasks = 256u / g.T, by_walk = 4u * (64u / g.GW);
-    g.img_cap = (bound_bytes + 16u + 15u) & ~15u;
-    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
-    uint32_t cpw = by_tasks < by_walk ? by_tasks : by_walk;
-    for (; cpw >= 1; cpw--) {
-        g.CPW = cpw;
-        g.o_psum = cpw * g.img_cap;
-        g.o_rbits = g.o_psum + al(cpw * g.T * 2u);
-        g.o_wofs = g.o_rbits + al(cpw * g.NBC * 4u);
-        g.o_info = g.o_wofs + al(cpw * g.NBC * 8u);
-        g.total = g.o_info + cpw * 16u;
-        if (g.total <= 64u * 1024u) break;
-    }
-    g.ok = cpw >= 1 ? 1u : 0u;
-    return g;
-}
 
 // ---- sample arithmetic, four 8-bit / two 16-bit samples to a dword
 // zigzag(x - y) per element (sprintz_delta_rle.cpp:197-205, bitpack.h:302-303)
@@ -425,34 +387,7 @@ __global__ void __launch_bounds__(256) encode_blk_kernel(EncodeArgs a, BlkEncGeo
 // ---- the same scheme for UNIVARIATE streams of the low-dim layout (compress_rowmajor_delta_rle_lowdim, ndims == 1:
 // sprintz_delta_lowdim.cpp:39-384; BASELINE config 1): a task is 16 bytes of the series = two blocks of uint8 / one of uint16; a
 // block's payload is its 8 fields back to back = nbits BYTES, its header field the 3 / 4 bits of its slot; widths are
-// rounded W - 1 -> W only (:207-208).  g: P = 1, T = tasks a chunk, NBC = blocks a chunk (blk_enc_uni_geom).
-inline BlkEncGeom blk_enc_uni_geom(uint32_t esz, uint32_t chunk_len, uint32_t bound_bytes)
-{
-    BlkEncGeom g{};
-    if (((uint64_t)chunk_len * esz) % 16u || chunk_len < 16u) return g;
-    g.P = 1;
-    g.NBC = chunk_len / 8u;
-    g.T = chunk_len * esz / 16u;
-    if (g.T == 0 || g.T > 256u) return g;
-    // (BASELINE config 1, 128 blocks a chunk: 0.565 ms with 64 lanes a chunk in the walk, 0.661 with 16 -- four chunks a walking wavefront, eight
-    //  blocks a lane: the walk's price is its passes over a lane's blocks, not its wave-wide scans; the lane-per-chunk kernel takes 0.399)
-    g.GW = g.NBC > 32u ? 64u : g.NBC > 16u ? 32u : 16u;
-    const uint32_t by_tasks = 256u / g.T, by_walk = 4u * (64u / g.GW);
-    g.img_cap = (bound_bytes + 16u + 15u) & ~15u;
-    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
-    uint32_t cpw = by_tasks < by_walk ? by_tasks : by_walk;
-    for (; cpw >= 1; cpw--) {
-        g.CPW = cpw;
-        g.o_psum = cpw * g.img_cap;                      // (unused: one column)
-        g.o_rbits = g.o_psum;
-        g.o_wofs = g.o_rbits + al(cpw * g.NBC * 4u);
-        g.o_info = g.o_wofs + al(cpw * g.NBC * 8u);
-        g.total = g.o_info + cpw * 16u;
-        if (g.total <= 64u * 1024u) break;
-    }
-    g.ok = cpw >= 1 ? 1u : 0u;
-    return g;
-}
+// rounded W - 1 -> W only (:207-208).  g: P = 1, T = tasks a chunk, NBC = blocks a chunk (geom.h: blk_enc_uni_geom).
 
 template <int W>
 __global__ void __launch_bounds__(256) encode_blk_uni_kernel(EncodeArgs a, BlkEncGeom g)

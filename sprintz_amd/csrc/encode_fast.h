@@ -22,9 +22,6 @@ namespace sprintz {
 #ifndef SPRINTZ_ENC_PAIR_MERGE
 #define SPRINTZ_ENC_PAIR_MERGE 1
 #endif
-#ifndef SPRINTZ_ENC_DRAIN_ALIGN
-#define SPRINTZ_ENC_DRAIN_ALIGN 128
-#endif
 
 // CM: column-major source (EncodeArgs::col_stride): a lane's 8 samples of a block are
 // contiguous in ITS column -- one 16-byte (8-byte at W == 8) load per lane, no LDS transpose.

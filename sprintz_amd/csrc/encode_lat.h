@@ -24,26 +24,6 @@
 namespace sprintz {
 
 constexpr uint32_t kEncLatMaxChunkBytes = 16u << 10;
-struct EncLatCarve {
-    uint32_t o_dl, o_zz, o_coef, o_nbx, o_rb, o_wo, o_img, img_cap, total;
-};
-inline EncLatCarve enc_lat_carve(uint32_t bound_bytes, uint32_t chunk_len, uint32_t D, uint32_t esz)
-{
-    EncLatCarve c;
-    const uint32_t nb = chunk_len / (8u * D), body = nb * 8u * D * esz;
-    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
-    c.o_dl = al(chunk_len * esz + 16u);
-    c.o_zz = c.o_dl + al(body + 16u);
-    c.o_coef = c.o_zz + al(body + 16u);
-    c.o_nbx = c.o_coef + al(nb * D * 4u + 16u);
-    c.o_rb = c.o_nbx + al(nb * D * 4u + 16u);
-    c.o_wo = c.o_rb + al(nb * 4u + 16u);
-    c.o_img = c.o_wo + al(nb * 8u + 16u);
-    c.img_cap = al(bound_bytes + 48u);
-    c.total = c.o_img + c.img_cap;
-    return c;
-}
-
 // LOW: the low-dim layout (D <= 4 at 8 bits, <= 2 at 16; sprintz_{delta,xff}_lowdim.cpp:39-400): column-major payload, widths rounded
 // only W-1 -> W, untruncated coefficient (32-bit multiply at 16 bits), "<" in the tail test of both codecs.
 template <int W, bool FIRE, int DP, bool LOW = false>

@@ -1,0 +1,271 @@
+// geom.h -- the shape arithmetic host and kernels share: workgroup size, alignment units, lane mappings, the LDS carves and task
+// geometries the kernels take as arguments, the stream bound.  Plain C++17, no HIP: the kernel headers include it for the structs
+// their kernels read, plan.h for the decisions it takes from them, and a host compiler builds both (tests/plan_probe.cpp).
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#ifndef SPRINTZ_THREADS
+#define SPRINTZ_THREADS 256
+#endif
+#ifndef SPRINTZ_BOUND_ALIGN
+#define SPRINTZ_BOUND_ALIGN 128           // sprintz_mi355x_compress_bound is a multiple of this: slots start on 128-byte lines
+#endif
+#ifndef SPRINTZ_ENC_DRAIN_ALIGN
+#define SPRINTZ_ENC_DRAIN_ALIGN 128       // encode_fast.h / encode_wide.h: granularity of the window's flushes to the slot
+#endif
+
+namespace sprintz {
+
+constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 64
+
+// Q (template parameter of the decoders): 0 = plain decode; 1 = decode + reduce; 2 = reduce only (nothing is written
+// to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only;
+// 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1
+constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4;
+// the modes that never store a decoded sample
+constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow; }
+
+// sprintz_mi355x_compress_bound: the longest stream a chunk of chunk_len elements can have, a multiple of SPRINTZ_BOUND_ALIGN
+inline size_t compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)
+{
+    const size_t esz = (size_t)elem_bytes, D = ndims ? ndims : 1;
+    const size_t hb = elem_bytes == 1 ? 3 : 4;
+    const size_t hdr_bytes = (2 * D * hb + 7) / 8;
+    const size_t max_groups = chunk_len / (16 * D) + 1;
+    // header + per group (header + 2 run bytes worst case beyond raw) + raw payload + flush padding
+    const size_t b = 8 + max_groups * (hdr_bytes + 3) + (size_t)chunk_len * esz + 32;
+    return (b + (SPRINTZ_BOUND_ALIGN - 1)) & ~(size_t)(SPRINTZ_BOUND_ALIGN - 1);
+}
+
+inline bool is_lowdim(int esz, int D) { return esz == 1 ? D <= 4 : D <= 2; }   // sprintz.cpp:34-50
+
+// columns-per-lane values that are instantiated (general layout); low-dim uses CPL = 1
+constexpr int kCplSet[] = {1, 2, 3, 4, 5, 6, 8};
+
+struct Mapping { int log2DP; int cpl; };
+
+// Choose lanes-per-chunk (DP = 2^k) and columns-per-lane so that DP*CPL >= D
+// with little padding; among mappings within 75% of the best lane utilisation
+// prefer the widest group (better coalescing of the D*esz-byte rows).
+inline Mapping choose_mapping(int D, bool lowdim)
+{
+    if (lowdim) {
+        int l = 0;
+        while ((1 << l) < D) l++;
+        return {l, 1};
+    }
+    double best = 0;
+    for (int l = 0; l <= 6; l++)
+        for (int c : kCplSet)
+            if ((1 << l) * c >= D) best = std::max(best, (double)D / ((1 << l) * c));
+    Mapping m{6, 8};
+    bool found = false;
+    for (int l = 6; l >= 0 && !found; l--) {
+        for (int c : kCplSet) {
+            if ((1 << l) * c < D) continue;
+            if ((double)D / ((1 << l) * c) >= 0.75 * best) { m = {l, c}; found = true; break; }
+        }
+    }
+    return m;
+}
+
+inline uint32_t next_pow2(uint32_t x)
+{
+    uint32_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+inline size_t group_bytes_max(int esz, int D)
+{
+    const size_t hb = esz == 1 ? 3 : 4;
+    return (2 * (size_t)D * hb + 7) / 8 + 16 * (size_t)D * esz;
+}
+
+// ---- decode_fast.h: bytes of LDS one group needs in decode_fast_kernel
+constexpr uint32_t decode_fast_lds_bytes(int W, int DP, int CPL, int D, bool colmajor_burst = false, int DS = 0)
+{
+    const uint32_t unit = DP * 16 * CPL;
+    const uint32_t hb = W == 8 ? 3 : 4;
+    const uint32_t dcap = DS ? DS : DP * CPL;
+    const uint32_t hdrmax = (2 * dcap * hb + 7) / 8, blkmax = 8 * dcap * (W / 8);
+    const uint32_t cg = hdrmax + 2 * blkmax + 4;
+    const uint32_t rb = ((2 * (cg + 24) + 3 + unit - 1) / unit + 1) * unit;
+    const uint32_t apron = (cg + 24 + 8 + 15) & ~15u;
+    // column-major burst staging: 4 blocks of every column the group can hold + 4 row offsets
+    const uint32_t stage = colmajor_burst ? 4u * blkmax + 16 : ((8u * D * (W / 8) + 15) & ~15u) + 16;   // +16: spread groups over banks
+    return rb + apron + stage;
+}
+
+// ---- decode_lat.h
+constexpr uint32_t kLatMaxChunkBytes = 16u << 10;     // the stream, the error image and the tables of ONE chunk must fit LDS
+constexpr uint32_t lat_align16(uint32_t x) { return (x + 15u) & ~15u; }
+// LDS carve: [stream: strm_cap + 32 | grp: NB + 3 pairs of words | err: one int per block element | sum: one word per (column, block)]
+struct LatCarve {
+    uint32_t strm_cap, o_grp, o_err, o_sum, total;
+};
+inline LatCarve lat_carve(uint32_t bound_bytes, uint32_t chunk_len, uint32_t D)
+{
+    LatCarve c;
+    const uint32_t nb = chunk_len / (8u * D);
+    c.strm_cap = lat_align16(bound_bytes + 32u);
+    c.o_grp = c.strm_cap + 32u;
+    c.o_err = c.o_grp + lat_align16((nb + 3u) * 8u + 16u);
+    c.o_sum = c.o_err + (nb + 1u) * 8u * D * 4u + 16u;      // (+1 block: phase C reads one block ahead)
+    c.total = c.o_sum + lat_align16(D * (nb | 1u) * 4u + 16u);
+    return c;
+}
+
+// ---- encode_lat.h
+struct EncLatCarve {
+    uint32_t o_dl, o_zz, o_coef, o_nbx, o_rb, o_wo, o_img, img_cap, total;
+};
+inline EncLatCarve enc_lat_carve(uint32_t bound_bytes, uint32_t chunk_len, uint32_t D, uint32_t esz)
+{
+    EncLatCarve c;
+    const uint32_t nb = chunk_len / (8u * D), body = nb * 8u * D * esz;
+    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
+    c.o_dl = al(chunk_len * esz + 16u);
+    c.o_zz = c.o_dl + al(body + 16u);
+    c.o_coef = c.o_zz + al(body + 16u);
+    c.o_nbx = c.o_coef + al(nb * D * 4u + 16u);
+    c.o_rb = c.o_nbx + al(nb * D * 4u + 16u);
+    c.o_wo = c.o_rb + al(nb * 4u + 16u);
+    c.o_img = c.o_wo + al(nb * 8u + 16u);
+    c.img_cap = al(bound_bytes + 48u);
+    c.total = c.o_img + c.img_cap;
+    return c;
+}
+
+// ---- decode_row.h
+struct RowDecGeom {
+    uint32_t U;          // dwords per row = lanes per chunk
+    uint32_t G;          // chunks per wavefront = 64 / U
+    uint32_t invU;       // ceil(2^16 / U): lane / U == (lane * invU) >> 16 for lane < 64
+    uint32_t ok;
+};
+
+inline RowDecGeom row_dec_geom(uint32_t esz, uint32_t chunk_len, uint32_t D)
+{
+    RowDecGeom g{};
+    const uint32_t rowbytes = D * esz;
+    if (rowbytes % 4u || ((uint64_t)chunk_len * esz) % 4u || chunk_len < 16u * D) return g;
+    g.U = rowbytes / 4u;
+    if (g.U > 64u) return g;
+    g.G = 64u / g.U;
+    g.invU = (65536u + g.U - 1u) / g.U;
+    g.ok = 1u;
+    return g;
+}
+
+// ---- decode_blk.h
+struct BlkDecGeom {
+    uint32_t P, NBC, T, CPW;
+    uint32_t img_cap;                                    // bytes of one chunk's stream image (multiple of 16)
+    uint32_t o_desc, o_psum, o_csum, o_info, total;      // LDS carve (bytes)
+    uint32_t invT, invP;                                 // ceil(2^16 / T), ceil(2^16 / P): n / d == (n * inv) >> 16 for n < 256, d <= 256
+    uint32_t ok;
+};
+
+inline BlkDecGeom blk_dec_geom(uint32_t esz, uint32_t chunk_len, uint32_t D, uint32_t bound_bytes)
+{
+    BlkDecGeom g{};
+    const uint32_t rowbytes = D * esz, hb = esz == 1 ? 3u : 4u;
+    if (rowbytes % 16u || ((uint64_t)chunk_len * esz) % 16u || chunk_len < 32u * D) return g;      // (>= 4 blocks: the scan's lanes are tasks)
+    if (2u * D > 16u * (hb == 3u ? 10u : 8u)) return g;  // a group header's 2 D fields over the walk's 16 lanes: 10 x 3 / 8 x 4 bits each (80 / 64 columns)
+    g.P = rowbytes / 16u;
+    g.NBC = chunk_len / (8u * D);
+    g.T = g.NBC * g.P;
+    if (g.T > 256u || g.NBC >= 32767u) return g;
+    g.img_cap = (bound_bytes + 64u + 15u) & ~15u;        // + the start's phase in its 16-byte piece, + windows that look past the last byte
+    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
+    uint32_t cpw = 256u / g.T;
+    if (cpw > 16u) cpw = 16u;                            // (four wavefronts walk four chunks each)
+    for (; cpw >= 1; cpw--) {
+        g.CPW = cpw;
+        g.o_desc = cpw * g.img_cap;
+        g.o_psum = g.o_desc + al(cpw * g.NBC * 8u);
+        g.o_csum = g.o_psum + al(cpw * g.T * 2u);
+        g.o_info = g.o_csum + cpw * g.T * 16u;
+        g.total = g.o_info + cpw * 16u;
+        if (g.total <= 64u * 1024u) break;
+    }
+    g.invT = (65536u + g.T - 1u) / g.T;
+    g.invP = (65536u + g.P - 1u) / g.P;
+    g.ok = cpw >= 1 ? 1u : 0u;
+    return g;
+}
+
+// ---- encode_blk.h
+struct BlkEncGeom {
+    uint32_t P;          // 16-byte pieces per row
+    uint32_t NBC;        // whole blocks of a full chunk
+    uint32_t T;          // tasks per chunk = NBC * P (<= 256)
+    uint32_t CPW;        // chunks per workgroup
+    uint32_t GW;         // lanes per chunk in the walk: 16 / 32 / 64
+    uint32_t img_cap;    // bytes of one chunk's stream image (multiple of 16; >= compress_bound + 16)
+    uint32_t o_psum, o_rbits, o_wofs, o_info, total;     // LDS carve (bytes)
+    uint32_t ok;
+};
+
+inline BlkEncGeom blk_enc_geom(uint32_t esz, uint32_t chunk_len, uint32_t D, uint32_t bound_bytes)
+{
+    BlkEncGeom g{};
+    const uint32_t rowbytes = D * esz;
+    if (rowbytes % 16u || ((uint64_t)chunk_len * esz) % 16u || chunk_len < 16u * D) return g;
+    g.P = rowbytes / 16u;
+    g.NBC = chunk_len / (8u * D);
+    g.T = g.NBC * g.P;
+    if (g.T == 0 || g.T > 256u || g.NBC >= 32767u) return g;
+    g.GW = g.NBC > 32u ? 64u : g.NBC > 16u ? 32u : 16u;
+    const uint32_t by_tasks = 256u / g.T, by_walk = 4u * (64u / g.GW);
+    g.img_cap = (bound_bytes + 16u + 15u) & ~15u;
+    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
+    uint32_t cpw = by_tasks < by_walk ? by_tasks : by_walk;
+    for (; cpw >= 1; cpw--) {
+        g.CPW = cpw;
+        g.o_psum = cpw * g.img_cap;
+        g.o_rbits = g.o_psum + al(cpw * g.T * 2u);
+        g.o_wofs = g.o_rbits + al(cpw * g.NBC * 4u);
+        g.o_info = g.o_wofs + al(cpw * g.NBC * 8u);
+        g.total = g.o_info + cpw * 16u;
+        if (g.total <= 64u * 1024u) break;
+    }
+    g.ok = cpw >= 1 ? 1u : 0u;
+    return g;
+}
+
+// the same scheme for univariate streams of the low-dim layout (encode_blk.h, encode_blk_uni_kernel): P = 1, T = tasks a chunk
+// (16 bytes of the series each), NBC = blocks a chunk
+inline BlkEncGeom blk_enc_uni_geom(uint32_t esz, uint32_t chunk_len, uint32_t bound_bytes)
+{
+    BlkEncGeom g{};
+    if (((uint64_t)chunk_len * esz) % 16u || chunk_len < 16u) return g;
+    g.P = 1;
+    g.NBC = chunk_len / 8u;
+    g.T = chunk_len * esz / 16u;
+    if (g.T == 0 || g.T > 256u) return g;
+    // (BASELINE config 1, 128 blocks a chunk: 0.565 ms with 64 lanes a chunk in the walk, 0.661 with 16 -- four chunks a walking wavefront, eight
+    //  blocks a lane: the walk's price is its passes over a lane's blocks, not its wave-wide scans; the lane-per-chunk kernel takes 0.399)
+    g.GW = g.NBC > 32u ? 64u : g.NBC > 16u ? 32u : 16u;
+    const uint32_t by_tasks = 256u / g.T, by_walk = 4u * (64u / g.GW);
+    g.img_cap = (bound_bytes + 16u + 15u) & ~15u;
+    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
+    uint32_t cpw = by_tasks < by_walk ? by_tasks : by_walk;
+    for (; cpw >= 1; cpw--) {
+        g.CPW = cpw;
+        g.o_psum = cpw * g.img_cap;                      // (unused: one column)
+        g.o_rbits = g.o_psum;
+        g.o_wofs = g.o_rbits + al(cpw * g.NBC * 4u);
+        g.o_info = g.o_wofs + al(cpw * g.NBC * 8u);
+        g.total = g.o_info + cpw * 16u;
+        if (g.total <= 64u * 1024u) break;
+    }
+    g.ok = cpw >= 1 ? 1u : 0u;
+    return g;
+}
+
+}  // namespace sprintz

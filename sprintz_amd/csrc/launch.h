@@ -18,9 +18,6 @@
 
 namespace sprintz {
 
-// columns-per-lane values that are instantiated (general layout); low-dim uses CPL = 1
-constexpr int kCplSet[] = {1, 2, 3, 4, 5, 6, 8};
-
 hipError_t launch_decode_w8(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t launch_decode_w16(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 // gather rows (Q = kQueryGather, decode_gather.hip): the generic kernel, both layouts; decode_fast for rows of whole 16-byte pieces

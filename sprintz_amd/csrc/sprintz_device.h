@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "geom.h"      // kThreads and the shape arithmetic the host shares
+
 namespace sprintz {
 
 template <int W> struct Elem;
@@ -141,11 +143,6 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-#ifndef SPRINTZ_THREADS
-#define SPRINTZ_THREADS 256
-#endif
-constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 64
 
 // The verbatim tail of a stream (:1171) -- for chunks shorter than one group, the whole chunk (BASELINE config 3 at
 // 1 KB): `nlanes` lanes copy nbytes from t to d.  16 bytes per lane per trip, FOUR trips' loads issued before the first

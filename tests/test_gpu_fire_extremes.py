@@ -7,7 +7,7 @@ fits the 24-bit multiply fire_predict uses everywhere else.  The inputs are test
 with run spans at frozen extreme coefficients before and behind the wrap (tests/test_fire_extremes_cpu.py asserts that they do).
 
 Every case: compress -> the oracle's bytes for every chunk -> decompress -> the input and every return value, and the kernel family on
-both sides from the dispatch counters (tests/dispatch.py); the families are read off csrc/api.hip's decode_launch / encode_launch.  A
+both sides from the dispatch counters (tests/dispatch.py); the families are read off csrc/plan.h's plan_decode / plan_encode.  A
 batch holds 5 to 7 chunks with seeds and direction patterns of their own, so that the lanes of a wave sit at different counter states;
 its first chunk is the golden fixture's case (tests/golden/golden_firewrap_v1, minted from the compiled reference by
 oracle/gen_golden_firewrap.py) where there is one, and is compared with the reference's bytes too.  Nothing here needs the reference or anything built from its sources."""

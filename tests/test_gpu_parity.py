@@ -108,7 +108,7 @@ def test_golden_vectors_of_2048_to_65535_columns(sz, golden_wide2):
                                                ("delta", 1, 8, 24000), ("xff", 1, 16, 22005), ("xff", 1, 1, 20000), ("xff", 1, 3, 23999), ("xff", 2, 33, 19999)])
 def test_single_calls_of_17_to_40_KB(sz, oracle, codec, esz, ndims, n):
     """single chunks above 16 KB still take the workgroup-per-chunk kernels while one chunk's working set fits a workgroup's LDS
-    (api.hip: lat_chunk_fits): the oracle's bytes, the oracle's samples; flat spans put runs across the larger block counts"""
+    (plan.h: lat_chunk_fits): the oracle's bytes, the oracle's samples; flat spans put runs across the larger block counts"""
     rng = np.random.default_rng(n)
     for flat in (0, 3):
         data = gen_walk(rng, n, ndims, esz, 8, flat_every=flat)
@@ -1049,7 +1049,7 @@ def test_container_built_inside_the_encode_launch(sz, oracle, request, decode_pa
     _lib.check(_lib.set_option(_lib.OPT_ENC_PAIR, enc_pair))
     request.addfinalizer(lambda: _lib.set_option(_lib.OPT_ENC_PAIR, 1))
     # Whether the container WAS built inside the launch, from the dispatch counters.  Only an encoder with 64 chunks a workgroup carries the
-    # tail (api.hip, arm_dense): the two-column encoder on 4 lanes a chunk -- 5 .. 8 columns in blocks of whole 16-byte pieces -- and the
+    # tail (plan.h, plan_encode: fused): the two-column encoder on 4 lanes a chunk -- 5 .. 8 columns in blocks of whole 16-byte pieces -- and the
     # one-column encoder on 4 lanes, 3 and 4 uint16 columns.  The workgroup-per-chunk encoder ("lat": it takes every such shape here)
     # and the block-parallel one ("blk": none of these, their rows are shorter than 16 bytes) leave the container to scan + copy; chunks that
     # hold no group are copied into it by one kernel without any encoder.  Mode 0 is scan + copy by definition.
