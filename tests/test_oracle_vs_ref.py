@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from harness import (REF_TEST_SIZES, gen_fuzz, gen_patterns, gen_sparse, gen_walk)
+from test_online_cpu import oracle_pack, orc  # noqa: F401  (fixtures)
 
 
 def _check(oracle, reference, codec, data, ndims):
@@ -102,3 +103,19 @@ def test_fire_transform_counters_through_their_wrap(oracle, reference, ndims):
     assert ro == rr and np.array_equal(co, cr)
     back, bret = reference.transform_decode(2, co, 1)
     assert bret == x.size and np.array_equal(back, x)
+
+
+@pytest.mark.parametrize("kind", [0, 1, 3, 4])
+def test_steered_online_inputs(orc, reference, kind):
+    """tests/online_drive.py past the 64th chain-tile edge (66 tiles of 8 192 blocks) and two periods of the sprintzpack widths: the compiled
+    reference's *_pack_u16 writes the oracle's bytes and its decoder restores the input (the smaller plans: tests/test_online_drive_cpu.py)"""
+    import online_drive as od
+    if kind <= 1:
+        x = od.dyndelta_input(od.PLAN_MANY(66), 11, 3)
+    else:
+        x = od.pack_input(2, 2 * od.PACK_PERIOD + 77, zig=kind == 4, tail=7)
+    got, ret, _ = oracle_pack(orc, kind, x)
+    if kind <= 1:
+        bits = od.choice_bits(got, x.size)
+        assert od.longest_dd_run(bits) >= 8192 and bits[64 * 8192 - 1] == 1 and bits[64 * 8192] == 1
+    od.reference_agrees(reference.lib, kind, x, got, ret)
