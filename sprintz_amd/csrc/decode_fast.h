@@ -14,7 +14,9 @@
 //     ring of 6 units (+ an apron that mirrors the ring head, so that a group's
 //     reads never wrap).  Headers, run lengths and bit fields are then LDS reads
 //     (aligned ds_read2_b32 + v_alignbyte_b32) -- no global load sits on the
-//     parse critical path.
+//     parse critical path.  Units are whole cache lines: the read-ahead starts
+//     on the 128-byte line the stream starts in, so that a unit is ONE line per
+//     group and load instruction and no line is asked for by two of them.
 //   * FIELDS. rows are byte aligned, so the in-byte shift of a column is the
 //     same for all 8 rows: field = v_bfe_u32(dword at row base, shift, nbits).
 //   * FIRE.   with E = err << W:  delta = sbfe((prev_delta*coef + E), W, W)
@@ -139,6 +141,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     constexpr uint32_t APRON = (CG + CSTART + 8 + 15) & ~15u;   // a step never reads past its start + APRON
     static_assert(RB - UNIT >= 2 * (CG + CSTART) + 3, "ring too small for one step of read-ahead");
     static_assert(NPEND <= 3, "pending registers");
+    // A read-ahead (re)starts on a cache line: the ABSOLUTE address of a group's first unit is rounded down to LINE, so that
+    // a unit -- 128 contiguous bytes per group and load instruction where it is that long -- lies in one line instead of two.
+    // The parse cursor then starts up to LINE - 1 bytes into the ring, which the prime has to leave room for.
+    constexpr uint32_t LINE = UNIT >= 128u ? 128u : UNIT;
+    static_assert((LINE & (LINE - 1)) == 0 && LINE >= 16, "line phase is a mask");
+    static_assert(RB - (LINE - 1) >= CG + CSTART, "ring too small for the first step after a line-aligned prime");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int D = EXACT ? DCAP : a.D;
@@ -170,14 +178,20 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // end: offsets are 32-bit, and a load that runs past the container returns 0
     // instead of faulting -- the read-ahead needs no bounds test.
     const uint64_t wave_first = GATHER ? 0 : (((uint64_t)blockIdx.x * kThreads + (threadIdx.x & ~63u)) >> LOG2DP) * (uint64_t)a.chunks_per_group;
+    // The descriptor starts on the cache line of the wave's first stream -- unless that line starts in front of the
+    // container (a first stream less than LINE bytes into a container that is not line-aligned): no address below a.comp
+    // is ever formed, and such a wave keeps the 16-byte rule.  Every load address is base + offset with offset >= 0.
+    const uint32_t comp_lo = (uint32_t)(uintptr_t)a.comp;
     uint64_t wave_base = 0;
     if constexpr (!GATHER) {
-        wave_base = a.offsets[wave_first < a.nchunks ? wave_first : 0] & ~(uint64_t)15;
+        const uint64_t off0 = a.offsets[wave_first < a.nchunks ? wave_first : 0];
+        const uint32_t ph0 = (comp_lo + (uint32_t)off0) & (LINE - 1);
+        wave_base = ph0 <= off0 ? off0 - ph0 : off0 & ~(uint64_t)15;
         wave_base = wave_uniform64(wave_base);
     }
-    // rounded up to whole 16-byte pieces (gfx950 zeroes a dwordx4 whose END is out of range);
-    // the <= 15 extra bytes are inside the SPRINTZ_MI355X_READ_SLACK the API asks for
-    const uint64_t wave_span = ((a.offsets[a.nchunks] - wave_base) + 15) & ~(uint64_t)15;
+    // 15 bytes past the last stream, so that the 16-byte piece holding its last byte ends in range whatever the piece's
+    // phase (gfx950 zeroes a dwordx4 whose END is out of range); they are inside the SPRINTZ_MI355X_READ_SLACK the API asks for
+    const uint64_t wave_span = (a.offsets[a.nchunks] - wave_base) + 15;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.comp + wave_base), 0, (uint32_t)(wave_span < 0xffffffffull ? wave_span : 0xffffffffull), 0x00020000);
     // output: one descriptor per wave as well, based at its first chunk's slot; a store
@@ -243,11 +257,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         cofs += UNIT;
         if (cofs >= RB) cofs -= RB;
     };
-    // (re)start the read-ahead at container offset `off`: fill the whole ring
+    // (re)start the read-ahead at container offset `off`: fill the whole ring, from the cache line `off` lies in.
+    // (Where that line starts in front of the descriptor -- only a wave under the 16-byte rule above, or a gather piece in
+    //  the container's first line -- from the 16-byte piece instead: off & ~15 >= wave_base, which is a multiple of 16 there.)
     auto prime = [&](uint64_t off) {
-        gabs = off & ~(uint64_t)15;
+        const uint32_t ph = (comp_lo + (uint32_t)off) & (LINE - 1);
+        gabs = ph <= off - wave_base ? off - ph : off & ~(uint64_t)15;
         gvo = (uint32_t)(gabs - wave_base) + lane16;
-        rp = (uint32_t)(off & 15);
+        rp = (uint32_t)(off - gabs);
         rofs = rp;
         cofs = lane16;
         npend = 0;
@@ -745,6 +762,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         need_prime = false;
     }
     uint32_t groups_left, remaining;
+    uint64_t stream_len;
     {
         const uint32_t w0 = lds_rd32(ring + rofs), w1 = lds_rd32(ring + rofs + 4);
         uint32_t hbytes = 8, nd_hdr = w1 >> 16;
@@ -777,7 +795,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         corrupt = (int)nd_hdr != D;
         // a damaged header must not make the loop spin: every group takes at least its
         // header and two slot bytes (none in the run-less codecs) out of the stream
-        const uint64_t stream_len = a.offsets[chunk + 1] - off_c;
+        stream_len = a.offsets[chunk + 1] - off_c;
         if ((uint64_t)groups_left * (hdr_bytes + (a.norle ? 0u : 2u)) > stream_len || groups_left > a.chunk_len / blk_elems + 2u) corrupt = true;
         if (corrupt) groups_left = 0;
     }
@@ -788,7 +806,6 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // ---- request the units that fit now; they are parked at the bottom of this step
         {
             const uint32_t room = RB - ahead;              // ring bytes the parser no longer needs
-            {
             npend = 0;
 #pragma unroll
             for (uint32_t k = 0; k < NPEND; k++) {
@@ -797,7 +814,6 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 npend += wanted ? 1u : 0u;
             }
             ahead += npend * UNIT;
-            }
         }
 
         // ---- group header: 2*D fields of HB bits (sprintz_xff_rle.cpp:713-735); both slots'
@@ -920,6 +936,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         return;
     }
     if (!corrupt && remaining > out_left) corrupt = true;
+    // the groups and the tail the header announces must end inside the stream: a truncated stream is damaged, whatever the
+    // bytes behind it (the next stream's, or padding) decoded to
+    if (!corrupt && gabs + rp + (uint64_t)remaining * ESZ > off_c + stream_len) corrupt = true;
     if constexpr (Q == kQueryWindow) {
         // tail element e is in column e % D, one row past the column's previous one: a window edge can fall inside the
         // tail (W = 8).  Then the partial window leaves, and the identities of the slot's windows past the data.

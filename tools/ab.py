@@ -2,7 +2,7 @@
 """Interleaved A/B of library builds (and/or env knobs) on ONE box -- box-to-box spread of the same
 binary is +-4 %, so variants are only ever compared inside one gpurun call.
 
-    python tools/ab.py --cfg headline|cfg1|cfg3_10k|... [--rounds 3] NAME=path/to/lib.so[,ENV=VAL...] ...
+    python tools/ab.py --cfg headline|cfg1|cfg3_10k|... [--rounds 3] [--data uniform] NAME=path/to/lib.so[,ENV=VAL...] ...
 
 Prints decompress / compress ms of every variant per round and the medians."""
 import argparse
@@ -21,6 +21,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--no-verify", action="store_true", help="ablated builds that decode garbage on purpose")
+    ap.add_argument("--data", default="", help="headline only: bench.py's --data (walk8 | walk300 | uniform | walkflat)")
     ap.add_argument("variants", nargs="+")
     a = ap.parse_args()
     res = {}
@@ -40,6 +41,8 @@ def main():
                 cmd = [sys.executable, "bench.py", "--full", "--only", a.cfg, "--no-cpu-baseline", "--config-reps", str(a.reps)]
             if a.no_verify:
                 cmd.append("--no-verify")
+            if a.data and a.cfg == "headline":
+                cmd += ["--data", a.data]
             p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
             try:
                 d = json.loads(p.stdout.strip().splitlines()[-1])
