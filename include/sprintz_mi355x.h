@@ -50,7 +50,7 @@ extern "C" {
  *   6  round 5: huf0_decompress_batch_hint, SPRINTZ_OPT_HUF0_SYNC_CHUNKS, SPRINTZ_MI355X_MAX_NDIMS 65535
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
- *      dispatch_counts / dispatch_name, SPRINTZ_KF_* */
+ *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -154,7 +154,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -465,6 +465,45 @@ int sprintz_mi355x_query_reduce(int op, const uint64_t* d_partials, uint64_t nch
 int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                  uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
                                  void* d_min, void* d_max, uint64_t* d_sum, int64_t* d_rets, void* hip_stream);
+/* Filter rows: which rows satisfy a condition on their columns?  One bit per row and one count per chunk, fused into the decode:
+ * nothing but the mask and the counts leaves the chip.  With sprintz_mi355x_filter_row_ids and sprintz_mi355x_gather_rows it is
+ * "find the rows, then fetch them" without ever materialising the batch.
+ *
+ * The batch is given exactly as to sprintz_mi355x_query_batch (codec, elem_bytes, container, offsets, nchunks, chunk_len,
+ * ndims, flags: SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else).  With D = ndims, R = ceil(chunk_len / D) rows a chunk slot and
+ * MB = ceil(R / 8) mask bytes a chunk slot: element e of chunk c is in row e / D and column e % D, and row r of chunk c EXISTS if
+ * all D of its elements lie inside the element count the chunk's stream header gives -- a partial last row is not a row.
+ * d_lo, d_hi: device arrays of ndims elements of the element type.  Comparison is unsigned and inclusive; lo[d] > hi[d] means
+ * "column d never matches" (the neutral element of ANY), 0 .. 0xFF / 0 .. 0xFFFF "always matches" (the neutral element of ALL).
+ * A row matches, under SPRINTZ_FILTER_ALL, if every column d has lo[d] <= x <= hi[d]; under SPRINTZ_FILTER_ANY, if some column has.
+ *   d_mask  : bit r & 7 of d_mask[c*MB + (r >> 3)] is 1 iff row r of chunk c exists and matches, judged on the values
+ *             sprintz_mi355x_decompress_batch would write under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK included; the
+ *             verbatim tail counts, and so does a chunk without groups).  Every one of the nchunks*MB bytes is written; bits of rows
+ *             that do not exist are 0 -- a row that does not exist never matches, whatever the bounds.  When chunk_len % D == 0 and
+ *             R % 8 == 0 the mask is the batch's rows in order, little-endian bit order.
+ *   d_counts: d_counts[c] = the number of set bits of chunk c.
+ * d_mask or d_counts may be NULL, not both.  d_rets (optional) as in decompress_batch: elements decoded, or < 0 for a damaged
+ * chunk, whose mask bytes and count are then unspecified -- nothing is written outside them, and every other chunk is exact.
+ * The call does not read the bounds on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST,
+ * DEC_UNI or DEC_GENERIC, as query_windows' does.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for an unknown mode or flag, a NULL d_lo / d_hi / d_comp / d_offsets,
+ * both outputs NULL, d_lo / d_hi not aligned to the element size, d_counts not aligned to 4 bytes, d_rets not aligned to 8 bytes,
+ * chunk_len outside 1..2^30; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0 returns 0
+ * and launches nothing. */
+#define SPRINTZ_FILTER_ALL 0u   /* a row matches if EVERY column d has lo[d] <= x <= hi[d] */
+#define SPRINTZ_FILTER_ANY 1u   /* ... if SOME column has */
+int sprintz_mi355x_filter_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, const void* d_lo, const void* d_hi, uint32_t mode,
+                               uint32_t flags, uint8_t* d_mask, uint32_t* d_counts, int64_t* d_rets, void* hip_stream);
+/* A mask of filter_rows as batch row numbers.  Needs chunk_len % ndims == 0, as gather_rows does: with R = chunk_len / D, batch row g
+ * is row g % R of chunk g / R, and d_mask holds MB = ceil(R / 8) bytes a chunk.  d_bases[c] is the exclusive prefix sum of the
+ * chunks' counts, computed by the caller (torch.cumsum, hipcub, ...).  The i-th set bit of chunk c, in ascending row order, writes
+ * c*R + r to d_ids[d_bases[c] + i]; a position >= capacity is dropped.  Each entry has exactly one writer: no atomics, and the
+ * output is deterministic -- ascending where the bases are the prefix sums.  Bits of rows >= R in a chunk's last byte are ignored.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0 (or ndims == 0, chunk_len outside 1..2^30),
+ * NULL pointers with nchunks > 0, d_bases / d_ids not aligned to 8 bytes.  nchunks == 0 returns 0 and launches nothing. */
+int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases, uint64_t nchunks, uint32_t chunk_len,
+                                  uint16_t ndims, uint64_t* d_ids, uint64_t capacity, void* hip_stream);
 /* Gather rows: N row ranges of a compressed batch, decoded in one launch into a dense [N][rows][ndims] array -- the read
  * the chunked format exists for ("so that queries over arbitrary time intervals are cheap", communicate/intro.tex:55).
  *

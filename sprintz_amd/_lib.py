@@ -127,6 +127,10 @@ QUERY_WIN_MIN, QUERY_WIN_MAX, QUERY_WIN_SUM = 1, 2, 4
 query_windows = _sig("sprintz_mi355x_query_windows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp)
 # N row ranges of a batch into a dense [N, rows, ndims] array, one launch (include/sprintz_mi355x.h)
 gather_rows = _sig("sprintz_mi355x_gather_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _u64, _u32, _vp, _vp, _vp)
+# which rows satisfy per-column bounds: one bit per row, one count per chunk; and the mask as row numbers (include/sprintz_mi355x.h)
+FILTER_ALL, FILTER_ANY = 0, 1
+filter_rows = _sig("sprintz_mi355x_filter_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp)
+filter_row_ids = _sig("sprintz_mi355x_filter_row_ids", _i, _vp, _vp, _u64, _u32, _u16, _vp, _u64, _vp)
 query = {
     ("delta", 1): _sig("sprintz_mi355x_query_delta_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
     ("xff", 1): _sig("sprintz_mi355x_query_xff_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
@@ -196,7 +200,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_huf0_tmp_bytes", "sprintz_mi355x_huf0_bound", "sprintz_mi355x_huf0_compress_batch",
     "sprintz_mi355x_huf0_exact_tmp_bytes", "sprintz_mi355x_huf0_compress_batch_exact",
     "sprintz_mi355x_query_batch", "sprintz_mi355x_query_reduce", "sprintz_mi355x_query_windows",
-    "sprintz_mi355x_gather_rows",
+    "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",
     "sprintz_mi355x_compress_batch_colmajor", "sprintz_mi355x_compress_batch_colmajor_dense", "sprintz_mi355x_decompress_batch_colmajor",

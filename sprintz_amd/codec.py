@@ -434,6 +434,86 @@ class ChunkedCodec:
                 raise _lib.SprintzError(code, f"gather_rows: range {i} (start {int(starts[i].item())}) {what} (decoder returned {code})")
         return out.view(n, rows, D)
 
+    def _filter_bounds(self, lo, hi, mode):
+        """lo / hi: a scalar, a sequence of ndims entries (None = open end) or a device tensor -> two contiguous device tensors [ndims]"""
+        torch = self.torch
+        D, top = self.ndims, (1 << (8 * self.esz)) - 1
+
+        def entries(v, name):
+            if torch.is_tensor(v):
+                if v.dtype != self.dtype or v.numel() != D:
+                    raise ValueError(f"{name} must hold {D} entries of {self.dtype}")
+                return None
+            vals = [v] * D if v is None or np.isscalar(v) else list(v)
+            if len(vals) != D:
+                raise ValueError(f"{name} must be a scalar or have {D} entries, not {len(vals)}")
+            if any(e is not None and not 0 <= int(e) <= top for e in vals):
+                raise ValueError(f"{name} entries must be in 0..{top}")
+            return vals
+
+        lo_l, hi_l = entries(lo, "lo"), entries(hi, "hi")
+        if lo_l is not None and hi_l is not None and mode == "any":      # a column without any bound never matches: an empty interval
+            for d in range(D):
+                if lo_l[d] is None and hi_l[d] is None:
+                    lo_l[d], hi_l[d] = top, 0
+
+        def tensor(v, vals, open_end):
+            if vals is None:
+                return v.to(self.device).reshape(-1).contiguous()
+            a = np.array([open_end if e is None else int(e) for e in vals], np.uint8 if self.esz == 1 else np.uint16)
+            return torch.from_numpy(a.view(np.int8 if self.esz == 1 else np.int16)).to(self.device).view(self.dtype)
+
+        return tensor(lo, lo_l, 0), tensor(hi, hi_l, top)
+
+    def filter_rows(self, batch, lo, hi, mode="all", general_layout=False, ids=False, check=True):
+        """Which rows satisfy a condition on their columns, straight from the compressed batch (one launch, no sample leaves the chip).
+
+        A row matches under mode="all" if every column d has lo[d] <= x <= hi[d] (unsigned, inclusive), under mode="any" if some
+        column has.  lo / hi: a scalar, a sequence of ndims entries, or a device tensor of the codec's dtype; a None entry is an
+        open end (0 / the type's maximum), and a column with neither bound is unconstrained: it always matches under "all" and
+        never -- an empty interval -- under "any".
+        -> {"mask": uint8 [nchunks, MB], "counts": int32 [nchunks]}: bit r & 7 of mask[c, r >> 3] is row r of chunk c, MB =
+        ceil(ceil(chunk_len / ndims) / 8); rows that do not exist (a short last chunk, a partial last row) are 0.
+        ids=True adds "ids": int64 [total], the matching batch rows in ascending order (row g is row g % R of chunk g // R, R =
+        chunk_len / ndims: chunk_len must be a multiple of ndims) -- what gather_rows takes as starts.
+        check=True raises SprintzError naming the first damaged chunk.  ids=True checks too, whatever check says: a damaged chunk's
+        count is unspecified, and it would size the ids and place every later chunk's."""
+        torch = self.torch
+        check = check or ids
+        if mode not in ("all", "any"):
+            raise ValueError("mode must be 'all' or 'any'")
+        D, n = self.ndims, batch.nchunks
+        if ids and self.chunk_len % D:
+            raise ValueError(f"ids need chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        lo_t, hi_t = self._filter_bounds(lo, hi, mode)
+        R = -(-self.chunk_len // D)
+        MB = -(-R // 8)
+        mask = torch.empty((n, MB), dtype=torch.uint8, device=self.device)
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        with self._on():
+            _lib.check(_lib.filter_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                        self.chunk_len, D, lo_t.data_ptr(), hi_t.data_ptr(),
+                                        _lib.FILTER_ALL if mode == "all" else _lib.FILTER_ANY,
+                                        _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                        mask.data_ptr(), counts.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
+        if check and n:
+            bad = (rets < 0).nonzero()
+            if bad.numel():
+                c = int(bad[0, 0].item())
+                raise _lib.SprintzError(int(rets[c].item()), f"filter_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        res = {"mask": mask, "counts": counts}
+        if ids:
+            incl = torch.cumsum(counts.to(torch.int64), 0)
+            total = int(incl[-1].item()) if n else 0
+            out = torch.empty(total, dtype=torch.int64, device=self.device)
+            if total:
+                bases = (incl - counts).contiguous()
+                with self._on():
+                    _lib.check(_lib.filter_row_ids(mask.data_ptr(), bases.data_ptr(), n, self.chunk_len, D, out.data_ptr(), total, self._stream()))
+            res["ids"] = out
+        return res
+
     def read_rows(self, batch, lo, hi):
         """batch rows [lo, hi) -> [hi - lo, ndims]: one range of gather_rows, its chunks decoded side by side in the same launch"""
         lo, hi = int(lo), int(hi)

@@ -357,6 +357,12 @@ struct QuerySpec {
     void* win_min = nullptr;
     void* win_max = nullptr;
     uint64_t* win_sum = nullptr;
+    // kQueryFilter: per-column bounds on the device, SPRINTZ_FILTER_ALL / _ANY, the mask ([nchunks][mask_stride] bytes) and the counts
+    const void* f_lo = nullptr;
+    const void* f_hi = nullptr;
+    uint32_t f_mode = 0, f_mask_stride = 0;
+    uint8_t* f_mask = nullptr;
+    uint32_t* f_counts = nullptr;
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -423,6 +429,12 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.win_min = qs.win_min;
     a.win_max = qs.win_max;
     a.win_sum = qs.win_sum;
+    a.f_lo = qs.f_lo;
+    a.f_hi = qs.f_hi;
+    a.f_mode = qs.f_mode;
+    a.f_mask = qs.f_mask;
+    a.f_counts = qs.f_counts;
+    a.f_mask_stride = qs.f_mask_stride;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -459,12 +471,17 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     case SPRINTZ_KF_DEC_BLK: what = "decode_blk kernel launch"; e = launch_decode_blk(w, grid, st, a, p.blkd); break;
     case SPRINTZ_KF_DEC_FAST:
         what = "decode_fast kernel launch";
+        if (qs.q == kQueryFilter) { e = launch_decode_fast_filter(w, p.fire, p.dp, p.cpl, p.exact, grid, (size_t)p.lds, st, a); break; }
         e = esz == 1 ? launch_decode_fast_w8(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a)
                      : launch_decode_fast_w16(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a);
         break;
-    case SPRINTZ_KF_DEC_UNI: what = "decode_uni kernel launch"; e = esz == 1 ? launch_decode_uni_w8(p.fire, ndims, qs.q, grid, st, a) : launch_decode_uni_w16(p.fire, ndims, qs.q, grid, st, a); break;
+    case SPRINTZ_KF_DEC_UNI:
+        what = "decode_uni kernel launch";
+        if (qs.q == kQueryFilter) { e = launch_decode_uni_filter(w, p.fire, ndims, st, a); break; }
+        e = esz == 1 ? launch_decode_uni_w8(p.fire, ndims, qs.q, grid, st, a) : launch_decode_uni_w16(p.fire, ndims, qs.q, grid, st, a); break;
     default:
         what = "decode kernel launch";
+        if (qs.q == kQueryFilter) { e = launch_decode_filter(w, p.fire, p.lowdim, p.cpl, grid, (size_t)p.lds, st, a); break; }
         e = esz == 1 ? launch_decode_w8(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a)
                      : launch_decode_w16(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a);
         break;
@@ -1593,6 +1610,54 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
     qs.win_sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- filter rows
+int sprintz_mi355x_filter_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, const void* d_lo, const void* d_hi, uint32_t mode,
+                               uint32_t flags, uint8_t* d_mask, uint32_t* d_counts, int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if (mode != SPRINTZ_FILTER_ALL && mode != SPRINTZ_FILTER_ANY) return fail(SPRINTZ_E_INVALID, "filter_rows: mode must be SPRINTZ_FILTER_ALL or SPRINTZ_FILTER_ANY");
+    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
+    if (!d_lo || !d_hi || !d_comp || !d_offsets) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if (!d_mask && !d_counts) return fail(SPRINTZ_E_INVALID, "filter_rows: neither a mask nor counts asked for");
+    if ((uintptr_t)d_lo % (uintptr_t)elem_bytes || (uintptr_t)d_hi % (uintptr_t)elem_bytes)
+        return fail(SPRINTZ_E_INVALID, "filter_rows: d_lo / d_hi must be aligned to the element size");
+    if ((uintptr_t)d_counts % 4 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "filter_rows: d_counts must be aligned to 4 bytes, d_rets to 8");
+    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no filter");
+    if (codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, "filter_rows: the RLE codecs (delta, xff) only");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    const uint32_t rows = (chunk_len + ndims - 1) / ndims;
+    QuerySpec qs;
+    qs.q = kQueryFilter;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.f_lo = d_lo;
+    qs.f_hi = d_hi;
+    qs.f_mode = mode;
+    qs.f_mask = d_mask;
+    qs.f_counts = d_counts;
+    qs.f_mask_stride = (rows + 7) / 8;
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
+}
+
+int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases, uint64_t nchunks, uint32_t chunk_len,
+                                  uint16_t ndims, uint64_t* d_ids, uint64_t capacity, void* hip_stream)
+{
+    if (ndims == 0 || chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "filter_row_ids: ndims == 0 or chunk_len outside 1..2^30");
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "filter_row_ids: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if (nchunks > 0 && (!d_mask || !d_bases || !d_ids)) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if ((uintptr_t)d_bases % 8 || (uintptr_t)d_ids % 8) return fail(SPRINTZ_E_INVALID, "filter_row_ids: d_bases and d_ids must be aligned to 8 bytes");
+    if (nchunks == 0) return 0;
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (launch_filter_row_ids(d_mask, d_bases, nchunks, chunk_len / ndims, d_ids, capacity, (hipStream_t)hip_stream) != hipSuccess)
+        return fail(SPRINTZ_E_HIP, "filter_row_ids kernel launch");
+    return 0;
 }
 
 // ---------------------------------------------------------------- gather rows

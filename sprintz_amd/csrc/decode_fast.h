@@ -330,8 +330,20 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t qmin[CPL];                                    // (set at each chunk start, in that mode alone)
     uint32_t wi = 0, wleft = 0;
     uint64_t wbase = 0;
-    auto q_row = [&](int k) {                              // pv[k] carries garbage above bit W: SDWA selects the element
-        if constexpr (Q != 0) {
+    // filter rows (Q == kQueryFilter): this lane's columns' bounds, loaded once; fcm collects the 8 rows of the column being decoded,
+    // fl the lane's columns (inverted domain: decode_kernel.h, FilterCol); the group ORs its lanes once per block (f_block)
+    FilterCol fc[CPL];
+    uint32_t finv = 0, fcm = 0, fl = 0, fb = 0, fcnt = 0;  // fb: blocks of this chunk done = the mask byte the next block writes
+    uint8_t* fmb = nullptr;
+    if constexpr (Q == kQueryFilter) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) fc[k] = filter_col<W>(a, genk[k], col_ok[k]);
+        finv = filter_inv(a);
+    }
+    auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
+        if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
+            fcm |= filter_hit<W>(fc[k], pv[k]) << i;
+        } else if constexpr (Q != 0) {
             if constexpr (W == 16) {
                 asm("v_max_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
                     : "=v"(qmax[k]) : "v"(qmax[k]), "v"(pv[k]));
@@ -352,7 +364,21 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
     };
     auto q_block = [&](int k) {
-        if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
+        if constexpr (Q == kQueryFilter) {                 // a lane column past the last one contributes the identity
+            fl |= col_ok[k] ? (fcm ^ finv) & 0xffu : 0u;
+            fcm = 0;
+        } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
+    };
+    // after every block of 8 rows: the group's lanes combine, one lane stores the block's byte (fb < chunk_len / blk_elems <=
+    // f_mask_stride: the capacity guard has passed), every lane keeps the count
+    auto f_block = [&]() {
+        if constexpr (Q == kQueryFilter) {
+            const uint32_t m = (group_or<DP>(fl) ^ finv) & 0xffu;
+            fl = 0;
+            if (fmb && lane_d == 0) fmb[fb] = (uint8_t)m;
+            fcnt += (uint32_t)__popc(m);
+            fb++;
+        }
     };
     auto win_flush_all = [&]() {                           // window wi of this chunk leaves, every genuine column of the lane
 #pragma unroll
@@ -521,6 +547,23 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         ovo += blk_bytes;
     };
     auto run_blocks = [&](uint32_t len) {                  // RUN slot: `len` blocks of zero error (:828-958)
+        if constexpr (Q == kQueryFilter && !FIRE) {
+            // a delta run repeats the previous row 8 len times: one test of that row, then len bytes of 0x00 or 0xFF -- up to
+            // 32 767 of them -- spread over the group's lanes
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) v |= col_ok[k] ? (filter_hit<W>(fc[k], pv[k]) ^ finv) & 1u : 0u;
+            const uint32_t hit = (group_or<DP>(v) ^ finv) & 1u;
+            if (fmb) {
+                const uint8_t byte = hit ? 0xffu : 0u;
+                for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) fmb[fb + j] = byte;
+            }
+            fcnt += hit ? 8u * len : 0u;
+            fb += len;
+            return;
+        }
         if constexpr (Q == kQueryWindow && !FIRE) {
             // a delta run repeats the previous row 8 len times (method.tex:150): per window it touches, min / max take the row
             // once and the sum takes it times the run's rows in that window -- O(windows), not O(rows)
@@ -574,7 +617,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     run_step(k, coef);
-                    q_row(k);
+                    q_row(k, i);
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
                     if constexpr (!query_reduce_only(Q) && !CM)
@@ -601,6 +644,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 for (int k = 0; k < CPL; k++) run_col(k);
             }
             q_window();
+            f_block();
             if constexpr (GATHER) {                        // (a FIRE run in front of row lo is replayed for its state, not staged out)
                 if (grow + 8u > gp.lo) stage_out(-1); else ovo += blk_bytes;
                 grow += 8u;
@@ -698,7 +742,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 col_step(k, i, coef, grad);
-                q_row(k);
+                q_row(k, i);
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
                 if constexpr (!query_reduce_only(Q) && !CM)
@@ -733,6 +777,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             for (int k = 0; k < CPL; k++) one_col(k);
         }
         q_window();
+        f_block();
         stage_out(slot);
         if constexpr (GATHER) grow += 8u;
     };
@@ -787,6 +832,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             wi = 0;
             wleft = a.window_rows;
             wbase = chunk * (uint64_t)a.win_count;
+        }
+        if constexpr (Q == kQueryFilter) {
+            fb = 0; fcnt = 0; fl = 0; fcm = 0;
+            fmb = a.f_mask ? a.f_mask + chunk * (uint64_t)a.f_mask_stride : nullptr;
         }
         out_left = a.chunk_len;
         ovo = CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
@@ -939,7 +988,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // the groups and the tail the header announces must end inside the stream: a truncated stream is damaged, whatever the
     // bytes behind it (the next stream's, or padding) decoded to
     if (!corrupt && gabs + rp + (uint64_t)remaining * ESZ > off_c + stream_len) corrupt = true;
-    if constexpr (Q == kQueryWindow) {
+    if constexpr (Q == kQueryFilter) {
+        // the tail is read by column, 32 rows a trip; the mask bytes of the slot's rows past the data are zeroed (decode_kernel.h)
+        if (!corrupt) filter_tail<W, CPL>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, fb, lane_d, DP, fc, genk, col_ok, fcnt);
+        if (lane_d == 0 && a.f_counts) a.f_counts[chunk] = fcnt;
+    } else if constexpr (Q == kQueryWindow) {
         // tail element e is in column e % D, one row past the column's previous one: a window edge can fall inside the
         // tail (W = 8).  Then the partial window leaves, and the identities of the slot's windows past the data.
         if (!corrupt) {

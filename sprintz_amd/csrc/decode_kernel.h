@@ -63,6 +63,14 @@ struct DecodeArgs {
     uint32_t g_rows;            // rows of every range
     uint32_t g_rpc;             // R: rows of a chunk slot, chunk_len / D
     uint32_t g_pieces;          // P: the most chunks a range can touch, (g_rows + R - 2) / R + 1
+    // filter rows (Q == kQueryFilter; sprintz_mi355x_filter_rows): row r of chunk c matches if every (f_mode 0) / some (f_mode 1) column d
+    // has f_lo[d] <= x <= f_hi[d], unsigned; bit r & 7 of f_mask[c * f_mask_stride + (r >> 3)], the chunk's matches in f_counts[c]
+    const void* f_lo;           // [D], element type, on the device
+    const void* f_hi;
+    uint32_t f_mode;            // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter
+    uint8_t* f_mask;            // optional
+    uint32_t* f_counts;         // optional
+    uint32_t f_mask_stride;     // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
 };
 
 // windowed query: one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the
@@ -77,6 +85,69 @@ __device__ __forceinline__ void win_flush(const DecodeArgs& a, uint64_t idx, uin
     qmin = Elem<W>::MASK;
     qmax = 0;
     qsum = 0;
+}
+
+// ---- filter rows.  A column's test is one subtract and one compare: ((x - lo) & MASK) < span with span = hi - lo + 1, or 0 where
+// lo > hi ("never").  The kernels combine in the INVERTED domain of ALL -- a column contributes hit ^ inv, inv = all ones for ALL and
+// 0 for ANY -- so that both modes are one OR across columns and lanes with the identity 0 (what a lane column past the last one
+// contributes), and the result is un-inverted once per block.
+struct FilterCol { uint32_t lo, span; };
+template <int W>
+__device__ __forceinline__ FilterCol filter_col(const DecodeArgs& a, int col, bool genuine)
+{
+    using U = typename Elem<W>::U;
+    FilterCol f{0u, 0u};
+    if (genuine) {
+        const uint32_t lo = ((const U*)a.f_lo)[col], hi = ((const U*)a.f_hi)[col];
+        f.lo = lo;
+        f.span = lo <= hi ? hi - lo + 1u : 0u;
+    }
+    return f;
+}
+// (x may carry garbage above bit W: only its low W bits reach the masked difference)
+template <int W> __device__ __forceinline__ uint32_t filter_hit(const FilterCol& f, uint32_t x) { return ((x - f.lo) & Elem<W>::MASK) < f.span ? 1u : 0u; }
+__device__ __forceinline__ uint32_t filter_inv(const DecodeArgs& a) { return a.f_mode == 0u ? 0xffffffffu : 0u; }
+__device__ __forceinline__ uint32_t group_or_any(uint32_t v, int DP)
+{
+    for (int off = DP >> 1; off > 0; off >>= 1) v |= (uint32_t)__shfl_xor((int)v, off, DP);
+    return v;
+}
+// The verbatim tail, for the lane-per-column kernels: `remaining` elements at t, row-major from the row behind the chunk's
+// `blocks_done` blocks.  A partial last row is not a row.  32 rows a trip: a lane folds its columns into one word, the group ORs
+// the words, lanes 0 .. 3 store the trip's bytes; then the mask bytes of the slot's rows past the data are zeroed, spread over the
+// lanes.  Every byte has one writer, and all of them lie in the chunk's f_mask_stride bytes: blocks_done * 8 + remaining / D rows
+// are at most chunk_len / D (the callers check the tail against the slot before they come here).
+template <int W, int CPL>
+__device__ __forceinline__ void filter_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t blocks_done,
+                                            int lane_d, int DP, const FilterCol (&fc)[CPL], const int (&col)[CPL], const bool (&genuine)[CPL], uint32_t& count)
+{
+    constexpr int ESZ = W / 8;
+    typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;   // the tail starts at any byte: one 2-byte load an element
+    const uint32_t nfull = remaining / D, tbytes = (nfull + 7u) >> 3;
+    const uint32_t inv = filter_inv(a);
+    uint8_t* const mb = a.f_mask ? a.f_mask + chunk * (uint64_t)a.f_mask_stride : nullptr;
+    for (uint32_t r0 = 0; r0 < nfull; r0 += 32u) {
+        const uint32_t n = nfull - r0 < 32u ? nfull - r0 : 32u;
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!genuine[k]) continue;
+            for (uint32_t j = 0; j < n; j++) {
+                const uint32_t e = (r0 + j) * D + (uint32_t)col[k];
+                const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16u*)(t + 2 * e);
+                v |= (filter_hit<W>(fc[k], x) ^ (inv & 1u)) << j;
+            }
+        }
+        v = (group_or_any(v, DP) ^ inv) & (n == 32u ? 0xffffffffu : (1u << n) - 1u);
+        count += (uint32_t)__popc(v);
+        if (mb) {
+            for (uint32_t b = (uint32_t)lane_d; b < 4u; b += (uint32_t)DP)
+                if ((r0 >> 3) + b < tbytes) mb[blocks_done + (r0 >> 3) + b] = (uint8_t)(v >> (8u * b));
+        }
+    }
+    if (mb) {
+        for (uint32_t j = blocks_done + tbytes + (uint32_t)lane_d; j < a.f_mask_stride; j += (uint32_t)DP) mb[j] = 0;
+    }
 }
 
 constexpr int64_t kErrCorrupt = -5;
@@ -216,6 +287,23 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         wleft = a.window_rows;
         wbase = chunk * (uint64_t)a.win_count;
     }
+    // filter rows: each lane's columns' bounds, loaded once; the group ORs its lanes' block masks with wave shuffles (groups of up to
+    // 64 lanes, both layouts), lane 0 stores the block's byte -- runs are replayed block by block here, as the decode does
+    FilterCol fc[CPL];
+    int fcol[CPL];
+    bool fgen[CPL];
+    uint32_t finv = 0, fcnt = 0;
+    uint8_t* fmb = nullptr;
+    if constexpr (Q == kQueryFilter) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            fcol[k] = lane_d * CPL + k;
+            fgen[k] = fcol[k] < D;
+            fc[k] = filter_col<W>(a, fcol[k], fgen[k]);
+        }
+        finv = filter_inv(a);
+        if (a.f_mask) fmb = a.f_mask + chunk * (uint64_t)a.f_mask_stride;
+    }
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -314,6 +402,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         // ---- zigzag^-1 + forecast recurrence, lane-local down each column (:993-1150)
         uint32_t v[8][CPL];
+        uint32_t fl = 0;                         // filter: this lane's columns' rows, inverted domain
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -336,7 +425,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             pv[k] = pvk;
             pd[k] = pdk;
             if (FIRE) ctr[k] = wrap_counter<W>(ctr[k] + (sext<W>(grad) >> 2));   // :1120-1128
-            if constexpr (Q != 0) {              // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
+            if constexpr (Q == kQueryFilter) {
+                uint32_t cm = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) cm |= filter_hit<W>(fc[k], v[i][k]) << i;
+                fl |= fgen[k] ? (cm ^ finv) & 0xffu : 0u;
+            } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
@@ -358,6 +452,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 wi++;
                 wleft = a.window_rows;
             }
+        }
+
+        if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= f_mask_stride (checked above)
+            const uint32_t m = (group_or_any(fl, DP) ^ finv) & 0xffu;
+            if (fmb && lane_d == 0) fmb[out_elems / blk_elems] = (uint8_t)m;
+            fcnt += (uint32_t)__popc(m);
         }
 
         // ---- store the 8 x D block (contiguous 8*D*ESZ bytes of the output)
@@ -441,7 +541,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
     // ---- verbatim tail (:1171)
     if (!corrupt && (out_elems + remaining > a.chunk_len || (uint64_t)remaining * ESZ > (uint64_t)(stream_len - pos))) corrupt = true;
-    if constexpr (Q == kQueryWindow) {
+    if constexpr (Q == kQueryFilter) {
+        if (!corrupt) filter_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, fc, fcol, fgen, fcnt);
+        if (lane_d == 0 && a.f_counts) a.f_counts[chunk] = fcnt;
+    } else if constexpr (Q == kQueryWindow) {
         // tail element e is in column e % D, one row further on than the column's previous one; a window
         // edge can fall inside the tail.  Then the partial window and the identities of the slot's last ones.
         if (!corrupt) {

@@ -168,6 +168,18 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
         wi++;
         wleft = a.window_rows;
     };
+    // filter rows (Q == kQueryFilter): all ND columns sit in this lane, so a row's verdict needs no other lane; a block's byte is one
+    // 1-byte store at the lane's own address (chunk * f_mask_stride has any alignment and the lanes of a wave are at different
+    // blocks after the first run: the bytes are not gathered into dwords)
+    FilterCol fc[ND];
+    uint32_t finv = 0, fcnt = 0;
+    uint8_t* fmb = nullptr;
+    if constexpr (Q == kQueryFilter) {
+#pragma unroll
+        for (int k = 0; k < ND; k++) fc[k] = filter_col<W>(a, k, true);
+        finv = filter_inv(a);
+        if (a.f_mask && exists) fmb = a.f_mask + chunk * (uint64_t)a.f_mask_stride;
+    }
     int slot = 2;
     uint8_t* const obase = (uint8_t*)a.out + chunk * (uint64_t)a.chunk_len * ESZ;
     const bool odd1 = (t & 1) != 0, odd2 = (t & 2) != 0;
@@ -363,7 +375,7 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                         }
                         pd[k] = delta;
                         x[k][i] = pv[k];
-                        if constexpr (Q != 0) { qmax[k] = pv[k] > qmax[k] ? pv[k] : qmax[k]; qsum[k] += pv[k]; }
+                        if constexpr (Q != 0 && Q != kQueryFilter) { qmax[k] = pv[k] > qmax[k] ? pv[k] : qmax[k]; qsum[k] += pv[k]; }
                         if constexpr (Q == kQueryWindow) qmin[k] = pv[k] < qmin[k] ? pv[k] : qmin[k];
                     }
                     if (FIRE && nbsum != 0) ctr[k] = wrap_counter<W>(ctr[k] + (sext<W>(grad) >> 2));   // counters only move on real blocks
@@ -378,6 +390,19 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                 } else {
 #pragma unroll
                 for (int e = 0; e < 8 * ND; e++) win[b][(e * ESZ) / 4] |= x[e % ND][e / ND] << (((e * ESZ) % 4) * 8);
+                }
+                if constexpr (Q == kQueryFilter) {         // block out_elems / (8 ND) < chunk_len / (8 ND) <= f_mask_stride (the step's guard)
+                    uint32_t m = 0;
+#pragma unroll
+                    for (int k = 0; k < ND; k++) {
+                        uint32_t cm = 0;
+#pragma unroll
+                        for (int i = 0; i < 8; i++) cm |= filter_hit<W>(fc[k], x[k][i]) << i;
+                        m |= cm ^ finv;
+                    }
+                    m = (m ^ finv) & 0xffu;
+                    if (fmb) fmb[out_elems / (8u * ND)] = (uint8_t)m;
+                    fcnt += (uint32_t)__popc(m);
                 }
                 valid |= 1u << b;
                 out_elems += 8 * ND;
@@ -465,7 +490,26 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                 uint8_t* d = obase + (uint64_t)out_elems * ESZ;
                 for (uint32_t j = 0; j < remaining * ESZ; j++) d[j] = src[j];
             }
-            if constexpr (Q == kQueryWindow) {           // element e of the tail is column e % ND; a row starts with column 0, a window edge can fall inside
+            if constexpr (Q == kQueryFilter) {           // the tail's whole rows (a partial last row is not a row), then zeros up to the slot's end
+                const uint32_t nfull = remaining / ND, done = out_elems / (8u * ND);
+                uint32_t byte = 0;
+                for (uint32_t r = 0; r < nfull; r++) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int k = 0; k < ND; k++) {
+                        const uint32_t e = r * ND + k;
+                        const uint32_t x = ESZ == 1 ? (uint32_t)src[e] : ((uint32_t)src[2 * e] | ((uint32_t)src[2 * e + 1] << 8));
+                        v |= filter_hit<W>(fc[k], x) ^ (finv & 1u);
+                    }
+                    byte |= ((v ^ finv) & 1u) << (r & 7u);
+                    if ((r & 7u) == 7u || r + 1 == nfull) {
+                        if (fmb) fmb[done + (r >> 3)] = (uint8_t)byte;
+                        fcnt += (uint32_t)__popc(byte);
+                        byte = 0;
+                    }
+                }
+                if (fmb) for (uint32_t j = done + ((nfull + 7u) >> 3); j < a.f_mask_stride; j++) fmb[j] = 0;
+            } else if constexpr (Q == kQueryWindow) {    // element e of the tail is column e % ND; a row starts with column 0, a window edge can fall inside
                 uint32_t col = 0;
                 for (uint32_t e = 0; e < remaining; e++) {
                     if (col == 0) {
@@ -491,6 +535,7 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                     if (a.qres) a.qres[chunk * (uint64_t)ND + (uint64_t)k] = a.qop == 1 ? (uint64_t)qmax[k] : qsum[k];
             }
         }
+        if constexpr (Q == kQueryFilter) { if (a.f_counts) a.f_counts[chunk] = fcnt; }
         if (a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
     }
 }

@@ -23,10 +23,11 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 
 // Q (template parameter of the decoders): 0 = plain decode; 1 = decode + reduce; 2 = reduce only (nothing is written
 // to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only;
-// 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1
-constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4;
+// 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1;
+// 5 = filter: one bit per row -- does the row satisfy the per-column bounds? -- and the chunk's count of them, reduce only
+constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5;
 // the modes that never store a decoded sample
-constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow; }
+constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter; }
 
 // sprintz_mi355x_compress_bound: the longest stream a chunk of chunk_len elements can have, a multiple of SPRINTZ_BOUND_ALIGN
 inline size_t compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)

@@ -78,4 +78,19 @@ __device__ __forceinline__ uint32_t group_scan(uint32_t x, int lane_d, uint32_t&
     return incl - x;
 }
 
+// Bitwise OR over a group of DP adjacent lanes, the result in every lane of the group: the butterflies group_scan forms its total
+// with (quad permutes, half mirror, row mirror: no LDS for DP <= 16), wave shuffles across the 16-lane rows above that.  Every lane
+// of the group must be active; lanes of other groups may be anywhere.
+template <int DP>
+__device__ __forceinline__ uint32_t group_or(uint32_t x)
+{
+    uint32_t t = x | dpp<DPP_QUAD_PERM(1, 0, 3, 2)>(0, x);
+    t |= dpp<DPP_QUAD_PERM(2, 3, 0, 1)>(0, t);
+    if constexpr (DP >= 8) t |= dpp<DPP_ROW_HALF_MIRROR>(0, t);
+    if constexpr (DP >= 16) t |= dpp<DPP_ROW_MIRROR>(0, t);
+    if constexpr (DP >= 32) t |= (uint32_t)__shfl_xor((int)t, 16, DP);
+    if constexpr (DP >= 64) t |= (uint32_t)__shfl_xor((int)t, 32, DP);
+    return t;
+}
+
 }  // namespace sprintz
