@@ -50,7 +50,7 @@ extern "C" {
  *   6  round 5: huf0_decompress_batch_hint, SPRINTZ_OPT_HUF0_SYNC_CHUNKS, SPRINTZ_MI355X_MAX_NDIMS 65535
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
- *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY */
+ *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -154,7 +154,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -515,7 +515,7 @@ int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases
  * d_starts lives on the device: the call does not read it on the host, does not synchronise, does not allocate and needs
  * no scratch.  A range costs the decode of every chunk it touches from that chunk's row 0 up to the last row it needs --
  * parsing stops there -- and a chunk shared by several ranges is decoded once per range (sort and merge dense ranges on
- * the caller's side).
+ * the caller's side; for single rows named by a mask, sprintz_mi355x_select_rows decodes every chunk once).
  * d_rets (optional, nranges entries): `rows` for a range delivered in full; SPRINTZ_E_INVALID if the range needs a row that
  * does not exist (a chunk >= nchunks, or a row past the rows its chunk's stream holds: the short last chunk);
  * SPRINTZ_E_CORRUPT if a chunk it touches is found damaged before the last row the range needs from it (the smaller code
@@ -534,6 +534,36 @@ int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases
 int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                uint32_t chunk_len, uint16_t ndims, const uint64_t* d_starts, uint64_t nranges, uint32_t rows,
                                void* d_out, int64_t* d_rets, void* hip_stream);
+/* Select rows: the rows a mask names, decoded and packed densely -- stream compaction fused into the decode.  Every chunk is decoded
+ * ONCE, whatever the number of rows it gives (gather_rows decodes a chunk once per range); with filter_rows in front it is
+ * "SELECT * WHERE lo <= x <= hi": two decode-speed launches and a prefix sum of the counts between them.
+ *
+ * The batch is given as to sprintz_mi355x_filter_rows (flags: SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else); chunk_len % ndims == 0
+ * is required, as for gather_rows and filter_row_ids.  With D = ndims, R = chunk_len / D and MB = ceil(R / 8):
+ *   d_mask : [nchunks][MB] bytes in exactly the layout filter_rows writes -- from filter_rows, from several of its masks combined by
+ *            the caller, or from anywhere else: no predicate is evaluated here.  A bit is ignored if its row does not exist: rows
+ *            >= R in the last byte, and rows past what the chunk's stream holds (the short last chunk).
+ *   d_bases: d_bases[c] is the output row at which chunk c's selected rows start -- normally the exclusive prefix sum of the counts,
+ *            computed by the caller.  The bases need not be monotonic: chunks may be placed in any order, with gaps.
+ * The i-th set bit of chunk c, in ascending row order over the rows that exist, is row r: its D elements are written to
+ * d_out[(d_bases[c] + i)*D ...] -- the values decompress_batch writes for that row under the same options
+ * (SPRINTZ_OPT_REF_DECODER_QUIRK included) -- and, if d_ids is not NULL, c*R + r to d_ids[d_bases[c] + i].  A position >= capacity
+ * is dropped (compared in 64 bits, before any narrowing); nothing else is written.  Each output row has one writer: no atomics,
+ * and the output is deterministic.
+ * d_rets (optional) as in decompress_batch: elements decoded, or < 0 for a damaged chunk, of which only the output rows
+ * [d_bases[c], d_bases[c] + the set bits of its mask over rows 0 .. R-1) are then unspecified -- nothing is written outside them,
+ * and every other chunk is exact.
+ * The call does not read the mask or the bases on the host, does not synchronise and does not allocate.  Its launch counts under
+ * DEC_FAST (csrc/decode_fast.h: the shapes a filter takes there whose rows are whole 16-byte pieces, (D * elem_bytes) % 16 == 0,
+ * with d_out 16-byte aligned and capacity * D * elem_bytes < 0xf0000000) or DEC_GENERIC (csrc/decode_kernel.h, plain 64-bit
+ * addresses: everything else, the low-dimension layouts included -- csrc/decode_uni.h is not taught to select).
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown flag,
+ * a NULL d_comp / d_offsets / d_mask / d_bases / d_out, d_out not aligned to the element size, d_bases / d_ids / d_rets not aligned
+ * to 8 bytes; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0 returns 0 and launches
+ * nothing. */
+int sprintz_mi355x_select_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, const uint64_t* d_bases,
+                               uint64_t capacity, uint32_t flags, void* d_out, uint64_t* d_ids, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -131,6 +131,8 @@ gather_rows = _sig("sprintz_mi355x_gather_rows", _i, _i, _i, _vp, _vp, _u64, _u3
 FILTER_ALL, FILTER_ANY = 0, 1
 filter_rows = _sig("sprintz_mi355x_filter_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp)
 filter_row_ids = _sig("sprintz_mi355x_filter_row_ids", _i, _vp, _vp, _u64, _u32, _u16, _vp, _u64, _vp)
+# the rows a mask names, each chunk decoded once, packed densely behind the chunk's base (include/sprintz_mi355x.h)
+select_rows = _sig("sprintz_mi355x_select_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
 query = {
     ("delta", 1): _sig("sprintz_mi355x_query_delta_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
     ("xff", 1): _sig("sprintz_mi355x_query_xff_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
@@ -200,7 +202,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_huf0_tmp_bytes", "sprintz_mi355x_huf0_bound", "sprintz_mi355x_huf0_compress_batch",
     "sprintz_mi355x_huf0_exact_tmp_bytes", "sprintz_mi355x_huf0_compress_batch_exact",
     "sprintz_mi355x_query_batch", "sprintz_mi355x_query_reduce", "sprintz_mi355x_query_windows",
-    "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids",
+    "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids", "sprintz_mi355x_select_rows",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",
     "sprintz_mi355x_compress_batch_colmajor", "sprintz_mi355x_compress_batch_colmajor_dense", "sprintz_mi355x_decompress_batch_colmajor",

@@ -514,6 +514,69 @@ class ChunkedCodec:
             res["ids"] = out
         return res
 
+    def select_rows(self, batch, mask, counts=None, out=None, ids=False, general_layout=False, check=True):
+        """The rows a mask names, packed densely: every chunk decoded once, only the selected rows stored (one launch).
+
+        mask: uint8 [nchunks, MB] in filter_rows' layout (bit r & 7 of mask[c, r >> 3] is row r of chunk c, MB = ceil(R / 8),
+        R = chunk_len / ndims: chunk_len must be a multiple of ndims) -- from filter_rows, several of its masks combined, or anywhere
+        else; bits of rows that do not exist are ignored.  counts: the set bits of every chunk over the rows that exist (int32 / int64
+        [nchunks], as filter_rows returns them); without them a device popcount of the mask over rows 0 .. R-1 stands in, which is
+        right for masks that are 0 where no row exists (filter_rows' are).
+        -> {"rows": [total, ndims] of the codec's dtype}, plus "ids": int64 [total] -- the rows' batch row numbers -- with ids=True;
+        ascending batch row order.  out: a contiguous tensor of at least total * ndims elements to write into.
+        check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        D, n = self.ndims, batch.nchunks
+        if self.chunk_len % D:
+            raise ValueError(f"select_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        R = self.chunk_len // D
+        MB = -(-R // 8)
+        if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
+            raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
+        mask = mask.contiguous()
+        if counts is None:
+            m = mask.view(n, MB).to(torch.int32)
+            if R % 8:
+                m[:, -1] &= (1 << (R % 8)) - 1
+            counts = sum(((m >> b) & 1).sum(dim=1) for b in range(8)) if n else m.new_zeros(0)
+        elif not torch.is_tensor(counts) or counts.device != self.device or counts.numel() != n:
+            raise ValueError(f"counts must be a tensor of {n} entries on {self.device}")
+        counts = counts.reshape(-1).to(torch.int64)
+        incl = torch.cumsum(counts, 0)
+        total = int(incl[-1].item()) if n else 0
+        if out is None:
+            out = torch.empty(total * D, dtype=self.dtype, device=self.device)
+        elif out.dtype != self.dtype or out.device != self.device or out.numel() < total * D or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {self.dtype} tensor of at least {total} x {D} elements on {self.device}")
+        res = {"rows": out.view(-1)[: total * D].view(total, D)}
+        if ids:
+            res["ids"] = torch.empty(total, dtype=torch.int64, device=self.device)
+        if n == 0:
+            return res
+        bases = (incl - counts).contiguous()
+        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        dest = out if out.numel() else torch.empty(D, dtype=self.dtype, device=self.device)   # (no row selected: the chunks are still checked)
+        with self._on():
+            _lib.check(_lib.select_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                        self.chunk_len, D, mask.data_ptr(), bases.data_ptr(), total,
+                                        _lib.QUERY_GENERAL_LAYOUT if general_layout else 0, dest.data_ptr(),
+                                        res["ids"].data_ptr() if ids else None, rets.data_ptr() if rets is not None else None, self._stream()))
+        if check:
+            bad = (rets < 0).nonzero()
+            if bad.numel():
+                c = int(bad[0, 0].item())
+                raise _lib.SprintzError(int(rets[c].item()), f"select_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        return res
+
+    def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False):
+        """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
+        filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.
+        -> {"rows": [total, ndims], and with ids=True "ids": int64 [total]}, in ascending batch row order."""
+        if self.chunk_len % self.ndims:
+            raise ValueError(f"where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=general_layout, check=True)
+        return self.select_rows(batch, f["mask"], counts=f["counts"], ids=ids, general_layout=general_layout)
+
     def read_rows(self, batch, lo, hi):
         """batch rows [lo, hi) -> [hi - lo, ndims]: one range of gather_rows, its chunks decoded side by side in the same launch"""
         lo, hi = int(lo), int(hi)

@@ -363,6 +363,13 @@ struct QuerySpec {
     uint32_t f_mode = 0, f_mask_stride = 0;
     uint8_t* f_mask = nullptr;
     uint32_t* f_counts = nullptr;
+    // kQuerySelect: the mask (f_mask_stride bytes a chunk, filter_rows' layout), every chunk's first output row, the rows of the output,
+    // the optional row numbers; rows of a chunk slot
+    const uint8_t* s_mask = nullptr;
+    const uint64_t* s_bases = nullptr;
+    uint64_t s_capacity = 0;
+    uint64_t* s_ids = nullptr;
+    uint32_t s_rpc = 0;
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -395,6 +402,7 @@ Shape decode_shape(int codec, int esz, const void* d_comp, uint64_t nchunks, uin
     s.codec = codec; s.esz = esz; s.D = ndims; s.nchunks = nchunks; s.chunk_len = chunk_len;
     s.noheader = noheader; s.q = qs.q; s.general = qs.general; s.col_stride = qs.col_stride; s.host_call = qs.hc != nullptr;
     s.comp_lo = low4(d_comp); s.out_lo = low4(d_out);
+    s.capacity = qs.s_capacity;
     return s;
 }
 
@@ -435,6 +443,11 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.f_mask = qs.f_mask;
     a.f_counts = qs.f_counts;
     a.f_mask_stride = qs.f_mask_stride;
+    a.s_mask = qs.s_mask;
+    a.s_bases = qs.s_bases;
+    a.s_capacity = qs.s_capacity;
+    a.s_ids = qs.s_ids;
+    if (qs.q == kQuerySelect) a.g_rpc = qs.s_rpc;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -472,6 +485,7 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     case SPRINTZ_KF_DEC_FAST:
         what = "decode_fast kernel launch";
         if (qs.q == kQueryFilter) { e = launch_decode_fast_filter(w, p.fire, p.dp, p.cpl, p.exact, grid, (size_t)p.lds, st, a); break; }
+        if (qs.q == kQuerySelect) { e = launch_decode_fast_select(w, p.fire, p.dp, p.cpl, p.exact, grid, (size_t)p.lds, st, a); break; }
         e = esz == 1 ? launch_decode_fast_w8(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a)
                      : launch_decode_fast_w16(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a);
         break;
@@ -482,6 +496,7 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     default:
         what = "decode kernel launch";
         if (qs.q == kQueryFilter) { e = launch_decode_filter(w, p.fire, p.lowdim, p.cpl, grid, (size_t)p.lds, st, a); break; }
+        if (qs.q == kQuerySelect) { e = launch_decode_select(w, p.fire, p.lowdim, p.cpl, grid, st, a); break; }
         e = esz == 1 ? launch_decode_w8(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a)
                      : launch_decode_w16(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a);
         break;
@@ -1658,6 +1673,38 @@ int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases
     if (launch_filter_row_ids(d_mask, d_bases, nchunks, chunk_len / ndims, d_ids, capacity, (hipStream_t)hip_stream) != hipSuccess)
         return fail(SPRINTZ_E_HIP, "filter_row_ids kernel launch");
     return 0;
+}
+
+// ---------------------------------------------------------------- select rows
+int sprintz_mi355x_select_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, const uint64_t* d_bases,
+                               uint64_t capacity, uint32_t flags, void* d_out, uint64_t* d_ids, int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
+    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "select_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if (!d_comp || !d_offsets || !d_mask || !d_bases || !d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if ((uintptr_t)d_out % (uintptr_t)elem_bytes) return fail(SPRINTZ_E_INVALID, "select_rows: d_out must be aligned to the element size");
+    if ((uintptr_t)d_bases % 8 || (uintptr_t)d_ids % 8 || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "select_rows: d_bases, d_ids and d_rets must be aligned to 8 bytes");
+    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no select");
+    if (codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, "select_rows: the RLE codecs (delta, xff) only");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    const uint32_t rows = chunk_len / ndims;
+    QuerySpec qs;
+    qs.q = kQuerySelect;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.f_mask_stride = (rows + 7) / 8;
+    qs.s_mask = d_mask;
+    qs.s_bases = d_bases;
+    qs.s_capacity = capacity;
+    qs.s_ids = d_ids;
+    qs.s_rpc = rows;
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
 }
 
 // ---------------------------------------------------------------- gather rows

@@ -126,6 +126,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // launch takes only rows of whole 16-byte pieces, so that a store piece lies in ONE row and the row test decides it as a whole.
     constexpr bool GATHER = Q == kQueryGather;
     static_assert(!GATHER || (!CM && !SPLIT && DS == 0), "gather: row-major destination, plain mappings");
+    // SELECT (sprintz_mi355x_select_rows): a plain decode of the group's chunks whose store pieces go, row by row, where the caller's mask
+    // and the chunk's base send them -- or nowhere.  The chunks of a wave land in unrelated output rows: the store descriptor is based
+    // at `out` and spans its s_capacity rows (the launch checks that they fit 32-bit offsets), and, as for the gather, the launch takes
+    // only rows of whole 16-byte pieces.
+    constexpr bool SELECT = Q == kQuerySelect;
+    static_assert(!SELECT || (!CM && !SPLIT && DS == 0), "select: row-major destination, plain mappings");
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -201,9 +207,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     //  end of the last column; offsets are column*col_stride + row, in bytes)
     const uint32_t rows_per_chunk = CM ? a.chunk_len / (uint32_t)(EXACT ? DCAP : a.D) : 0u;
     const uint64_t out_base = CM ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)rows_per_chunk * ESZ
+                            : SELECT ? 0
                                  : (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * ESZ;
     const uint64_t out_span = CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
                             : GATHER ? a.g_nranges * (uint64_t)a.g_rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
+                            : SELECT ? a.s_capacity * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
                                  : a.nchunks * (uint64_t)a.chunk_len * ESZ - out_base;
     // (both are wave-uniform by construction; saying so keeps hipcc from wrapping every store in a
     //  readfirstlane waterfall loop -- 8 VALU per store it cannot prove away)
@@ -399,8 +407,46 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t grow = 0;
     uint32_t prow[PIECES];
 #pragma unroll
-    for (int q = 0; q < PIECES; q++) prow[q] = GATHER ? (lane16 + (uint32_t)q * ROW16) / row_stride : 0u;
+    for (int q = 0; q < PIECES; q++) prow[q] = (GATHER || SELECT) ? (lane16 + (uint32_t)q * ROW16) / row_stride : 0u;
     const uint32_t gspan = gp.hi - gp.lo;
+    // select: where in its row each of this lane's store pieces starts; the chunk's mask bytes, its first output row, its first batch row,
+    // the set bits of its blocks done so far (fb counts those blocks, as for the filter) and the mask byte of the block being decoded
+    uint32_t pcol[PIECES];
+#pragma unroll
+    for (int q = 0; q < PIECES; q++) pcol[q] = SELECT ? lane16 + (uint32_t)q * ROW16 - prow[q] * row_stride : 0u;
+    const uint8_t* smb = nullptr;
+    uint64_t sbase = 0, srow0 = 0;
+    uint32_t srank = 0, sm = 0;
+    // The mask bytes are read ahead of the blocks, 4 DP of them at a time: lane l of the group keeps dword l of the window that starts at
+    // byte mwin0 (a multiple of 4) of the chunk's mask, and a block's byte comes out of its lane's dword with one cross-lane read -- no
+    // load from memory sits between a block's header and its stores.  (A chunk's mask starts at any address, and its last dword may be
+    // short: those bytes are read one by one.)
+    uint32_t mwin = 0, mwin0 = 0x80000000u;
+    auto sel_byte = [&](uint32_t b) -> uint32_t {
+        if (b - mwin0 >= 4u * DP) {
+            mwin0 = b & ~3u;
+            const uint32_t o = mwin0 + 4u * (uint32_t)lane_d;
+            mwin = 0;
+            if (o + 4u <= a.f_mask_stride) {
+                mwin = *(const u32_unaligned*)(smb + o);
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; j++)
+                    if (o + j < a.f_mask_stride) mwin |= (uint32_t)smb[o + j] << (8u * j);
+            }
+        }
+        const uint32_t i = b - mwin0;
+        const uint32_t w = (uint32_t)__shfl((int)mwin, (int)(i >> 2), DP);
+        return (w >> (8u * (i & 3u))) & 0xffu;
+    };
+    // after every block of 8 rows: the selected rows' numbers leave, the chunk's rank moves on
+    auto s_block = [&]() {
+        if constexpr (SELECT) {
+            if (sm) select_ids(a, sbase + srank, sm, srow0 + 8u * fb, lane_d, DP);
+            srank += (uint32_t)__popc(sm);
+            fb++;
+        }
+    };
 
     // ---- per-block workers ------------------------------------------------------
     // The staged 8 x D block is contiguous in the output.  Packed blocks are read
@@ -522,6 +568,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             const uint32_t u = lane16 + q * ROW16;
             bool in = u < blk_bytes;
             if constexpr (GATHER) in = in && grow + prow[q] - gp.lo < gspan;   // the piece's row is one the range wants
+            uint32_t vo = ovo + u;
+            if constexpr (SELECT) {                        // the piece's row is one the mask wants, and its place is inside `out` (compared in 64 bits)
+                const uint64_t p = select_place(sbase + srank, sm, prow[q]);
+                in = in && ((sm >> prow[q]) & 1u) && p < a.s_capacity;
+                vo = (uint32_t)p * row_stride + pcol[q];   // (s_capacity rows fit 32-bit offsets: the launch checks)
+            }
             const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
             if (slot >= 0) {
                 held[slot][q] = t;
@@ -537,10 +589,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #elif defined(SPRINTZ_ABL_STORE_HALF_LANES)
                 held_vo[slot][q] = (in && (lane_d & 1) == 0) ? ovo + u : kDropStore;   // ablation: every second lane's 16 bytes are dropped
 #else
-                held_vo[slot][q] = in ? ovo + u : kDropStore;
+                held_vo[slot][q] = in ? vo : kDropStore;
 #endif
             } else {
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), orsrc, in ? ovo + u : kDropStore, 0, kStoreAux);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), orsrc, in ? vo : kDropStore, 0, kStoreAux);
             }
         }
         wave_lds_sync();
@@ -585,6 +637,18 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             return;
         }
+        if constexpr (SELECT && !FIRE) {
+            // a delta run repeats the previous row and changes no state: a run none of whose rows the mask wants is stepped over
+            // (its mask bytes lie inside the chunk's: the run fits the chunk slot)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            uint32_t any = 0;
+            for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) any |= smb[fb + j];
+            if (group_or<DP>(any) == 0) {
+                out_left -= len * blk_elems;
+                fb += len;
+                return;
+            }
+        }
         if constexpr (GATHER && !FIRE) {
             // a delta run repeats the previous row: the blocks in front of row lo change no state and store nothing
             uint32_t skip = grow + 8u <= gp.lo ? (gp.lo - grow) >> 3 : 0u;
@@ -599,6 +663,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             if constexpr (GATHER) { if (grow >= gp.hi) break; }   // row hi - 1 has left: the rest of the run is not replayed
             if (out_left < blk_elems) { corrupt = true; break; }
             out_left -= blk_elems;
+            if constexpr (SELECT) {
+                sm = sel_byte(fb);
+                if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
+            }
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -621,7 +689,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
                     if constexpr (!query_reduce_only(Q) && !CM)
-                        *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
+                        if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
 #endif
                 }
                 q_block(k);
@@ -648,6 +716,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             if constexpr (GATHER) {                        // (a FIRE run in front of row lo is replayed for its state, not staged out)
                 if (grow + 8u > gp.lo) stage_out(-1); else ovo += blk_bytes;
                 grow += 8u;
+            } else if constexpr (SELECT) {
+                if (sm != 0) stage_out(-1);
+                s_block();
             } else {
                 stage_out(-1);
             }
@@ -716,6 +787,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto packed_block = [&](const int (&e)[CPL][8], int slot) {   // forecast recurrence (:993-1150)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
+        if constexpr (SELECT) sm = sel_byte(fb);           // (block fb < chunk_len / blk_elems <= f_mask_stride: the guard has passed)
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -746,7 +818,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
                 if constexpr (!query_reduce_only(Q) && !CM)
-                    *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
+                    if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
 #else
                 asm volatile("" :: "v"(pv[k]));
 #endif
@@ -779,6 +851,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         q_window();
         f_block();
         stage_out(slot);
+        s_block();
         if constexpr (GATHER) grow += 8u;
     };
     auto run_length = [&](uint32_t at, uint32_t& nbytes) -> uint32_t {   // varint in blocks (:829-833)
@@ -836,6 +909,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (Q == kQueryFilter) {
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
             fmb = a.f_mask ? a.f_mask + chunk * (uint64_t)a.f_mask_stride : nullptr;
+        }
+        if constexpr (SELECT) {
+            fb = 0; srank = 0; sm = 0;
+            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
+            smb = a.s_mask + chunk * (uint64_t)a.f_mask_stride;
+            sbase = a.s_bases[chunk];
+            srow0 = chunk * (uint64_t)a.g_rpc;
         }
         out_left = a.chunk_len;
         ovo = CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
@@ -1032,7 +1112,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
     }
-    if (!corrupt && remaining > 0 && !query_reduce_only(Q) && CM) {
+    if constexpr (SELECT) {
+        // the tail's whole rows by the same rule, straight from HBM (fb blocks = 8 fb rows lie in front of it)
+        if (!corrupt && remaining > 0)
+            select_tail<W>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, sbase, srank, lane_d, DP, [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if (!corrupt && remaining > 0 && !query_reduce_only(Q) && CM) {
         const uint8_t* t = a.comp + gabs + rp;
         U* const c0 = (U*)((uint8_t*)a.out + out_base + ovo);          // column 0 at the tail's first row
         for (uint32_t e = (uint32_t)lane_d; e < remaining; e += DP) {

@@ -71,7 +71,54 @@ struct DecodeArgs {
     uint8_t* f_mask;            // optional
     uint32_t* f_counts;         // optional
     uint32_t f_mask_stride;     // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
+    // select rows (Q == kQuerySelect; sprintz_mi355x_select_rows): the i-th set bit of chunk c's mask bytes s_mask[c * f_mask_stride ...]
+    // (filter_rows' layout), row r, lands at row s_bases[c] + i of `out` and c * g_rpc + r at the same place of s_ids; a place
+    // >= s_capacity is dropped
+    const uint8_t* s_mask;      // [nchunks][f_mask_stride]
+    const uint64_t* s_bases;    // [nchunks]
+    uint64_t s_capacity;        // rows of `out` (and entries of s_ids)
+    uint64_t* s_ids;            // optional
 };
+
+// select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the
+// chunk's base plus the set bits in front of the block
+__device__ __forceinline__ uint64_t select_place(uint64_t first, uint32_t m, uint32_t row) { return first + (uint32_t)__popc(m & ((1u << row) - 1u)); }
+// the row numbers of those rows: lanes 0 .. 7 of the group take a row each (groups of fewer lanes take turns); one writer an entry
+__device__ __forceinline__ void select_ids(const DecodeArgs& a, uint64_t first, uint32_t m, uint64_t row0, int lane_d, int DP)
+{
+    if (!a.s_ids) return;
+    for (uint32_t j = (uint32_t)lane_d; j < 8u; j += (uint32_t)DP) {
+        const uint64_t p = select_place(first, m, j);
+        if (((m >> j) & 1u) && p < a.s_capacity) a.s_ids[p] = row0 + j;
+    }
+}
+// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
+// A partial last row is not a row.  Every selected row is copied by the group's lanes, an element each; `rank` is the number of
+// the chunk's set bits in front of row0.  mask_at(b) is the chunk's mask byte b, read only where 8 b is below row0 + the tail's whole rows.
+template <int W, typename F>
+__device__ __forceinline__ void select_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0,
+                                            uint64_t base, uint32_t rank, int lane_d, int DP, F mask_at)
+{
+    using U = typename Elem<W>::U;
+    constexpr int ESZ = W / 8;
+    typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
+    const uint32_t nfull = remaining / D;
+    for (uint32_t r0 = 0; r0 < nfull; r0 += 8u) {
+        const uint32_t n = nfull - r0 < 8u ? nfull - r0 : 8u;
+        const uint32_t m = mask_at((row0 + r0) >> 3) & ((1u << n) - 1u);
+        const uint64_t first = base + rank;
+        for (uint32_t j = 0; j < n; j++) {
+            if (!((m >> j) & 1u)) continue;
+            const uint64_t p = select_place(first, m, j);
+            if (p >= a.s_capacity) continue;
+            U* const d = (U*)a.out + p * (uint64_t)D;
+            const uint8_t* const s = t + (size_t)(r0 + j) * D * ESZ;
+            for (uint32_t e = (uint32_t)lane_d; e < D; e += (uint32_t)DP) d[e] = ESZ == 1 ? (U)s[e] : (U)*(const u16u*)(s + 2 * e);
+        }
+        select_ids(a, first, m, chunk * (uint64_t)a.g_rpc + row0 + r0, lane_d, DP);
+        rank += (uint32_t)__popc(m);
+    }
+}
 
 // windowed query: one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the
 // accumulators start over from the identities (min = all ones, max = 0, sum = 0)
@@ -305,6 +352,15 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if (a.f_mask) fmb = a.f_mask + chunk * (uint64_t)a.f_mask_stride;
     }
 
+    // select rows: the chunk's mask bytes, its first output row and the set bits of the blocks done so far
+    const uint8_t* smb = nullptr;
+    uint64_t sbase = 0;
+    uint32_t srank = 0;
+    if constexpr (Q == kQuerySelect) {
+        smb = a.s_mask + chunk * (uint64_t)a.f_mask_stride;
+        sbase = a.s_bases[chunk];
+    }
+
     for (;;) {
         uint32_t z[8][CPL];
 #pragma unroll
@@ -479,6 +535,28 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 }
             }
             if (r0 + 8u >= gp.hi) return;            // delivered in full: the range's entry keeps g_rows
+        } else if constexpr (Q == kQuerySelect) {
+            // the block's rows whose bits are set, each at its place behind the chunk's base (block out_elems / blk_elems <
+            // chunk_len / blk_elems <= f_mask_stride: checked above); 64-bit addresses, a place >= s_capacity is dropped
+            (void)ob;
+            const uint32_t r0 = out_elems / (uint32_t)D;
+            const uint32_t m = smb[r0 >> 3];
+            const uint64_t first = sbase + srank;
+            if (m) {
+#pragma unroll
+                for (int k = 0; k < CPL; k++) {
+                    const int col = lane_d * CPL + k;
+                    if (col < D) {
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const uint64_t p = select_place(first, m, (uint32_t)i);
+                            if (((m >> i) & 1u) && p < a.s_capacity) ((U*)a.out)[p * (uint64_t)D + (uint64_t)col] = (U)v[i][k];
+                        }
+                    }
+                }
+                select_ids(a, first, m, chunk * (uint64_t)a.g_rpc + r0, lane_d, DP);
+            }
+            srank += (uint32_t)__popc(m);
         } else if (cs) {
             const uint32_t r0 = out_elems / (uint32_t)D;
 #pragma unroll
@@ -604,6 +682,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
             ((U*)a.out)[gp.obase + (int64_t)out_elems + (int64_t)e] = (U)x;
         }
+        return;
+    }
+    if constexpr (Q == kQuerySelect) {
+        if (!corrupt) select_tail<W>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, sbase, srank, lane_d, DP,
+                                     [&](uint32_t b) { return (uint32_t)smb[b]; });
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }
     if (!corrupt && !query_reduce_only(Q) && cs) {

@@ -24,8 +24,9 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // Q (template parameter of the decoders): 0 = plain decode; 1 = decode + reduce; 2 = reduce only (nothing is written
 // to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only;
 // 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1;
-// 5 = filter: one bit per row -- does the row satisfy the per-column bounds? -- and the chunk's count of them, reduce only
-constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5;
+// 5 = filter: one bit per row -- does the row satisfy the per-column bounds? -- and the chunk's count of them, reduce only;
+// 6 = select: a chunk is decoded once and only the rows whose bit is set in the caller's mask are stored, packed densely behind the chunk's base
+constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter; }
 

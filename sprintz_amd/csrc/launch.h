@@ -29,6 +29,9 @@ hipError_t launch_decode_fast_filter(int w, bool fire, int dp, int cpl, bool exa
 hipError_t launch_decode_uni_filter(int w, bool fire, int nd, hipStream_t st, const DecodeArgs& a);
 // filter_row_ids: a mask of filter_rows into ascending batch row numbers, a lane group per chunk (decode_filter.hip)
 hipError_t launch_filter_row_ids(const uint8_t* mask, const uint64_t* bases, uint64_t nchunks, uint32_t rows, uint64_t* ids, uint64_t capacity, hipStream_t st);
+// select rows (Q = kQuerySelect, decode_select.hip): the generic kernel, both layouts; decode_fast for rows of whole 16-byte pieces
+hipError_t launch_decode_select(int w, bool fire, bool lowdim, int cpl, unsigned grid, hipStream_t st, const DecodeArgs& a);
+hipError_t launch_decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h)
 // (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
 hipError_t launch_decode_fast_w8(bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);

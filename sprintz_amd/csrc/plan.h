@@ -42,6 +42,7 @@ struct Shape {
     uint64_t slot_stride = 0;
     uint64_t nranges = 0;                  // gather
     uint32_t rows = 0;
+    uint64_t capacity = 0;                 // select: rows of the output
 };
 
 struct Plan {
@@ -190,7 +191,12 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     // column-major: a lane's 8 samples per block are one aligned 16-byte (8-byte) piece of its column
     const bool fast = cs ? fast_common && s.q == kQueryOff && cs % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0 &&
                                (s.out_lo % 16) == 0 && (uint64_t)D * cs * esz < 0xf0000000ull
-                         : fast_common && p.vec_store && (uint64_t)chunk_len * esz * 64 * 64 < 0xf0000000ull;
+                         : fast_common && p.vec_store && (uint64_t)chunk_len * esz * 64 * 64 < 0xf0000000ull &&
+                               // select rows: the shapes a filter takes here, with rows of whole 16-byte store pieces (a piece lies in ONE row, as
+                               // for the gather) and an output -- `capacity` rows from a 16-byte aligned start -- within reach of the store
+                               // descriptor's 32-bit offsets (the quotient: capacity is any 64-bit number)
+                               (s.q != kQuerySelect || (((uint64_t)D * esz) % 16 == 0 && (s.out_lo % 16) == 0 &&
+                                                        s.capacity <= (0xf0000000ull - 1) / ((uint64_t)D * esz)));
     // small batches: one WORKGROUP per chunk (decode_lat.h) -- a chunk's 40 dependent group steps on one lane group take 50 us
     // however few chunks there are; split into a header walk, parallel bit extraction, the bare recurrence and a prefix sum it is ~13
     if (!norle && !s.noheader && !cs && !p.quirk && s.q == kQueryOff && D <= 64 &&
@@ -244,7 +250,8 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
+    // (decode_uni.h is not taught to select rows: those shapes go to the generic kernel)
+    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
     return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, shmem);
 }
 
