@@ -286,13 +286,33 @@ hipError_t launch_size_scan(const uint32_t* d_sizes, uint64_t n, uint32_t align,
     hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nblocks), dim3(kScanBlock), 0, st, d_offsets, n, tmp);
     return hipGetLastError();
 }
+
+// The lane-per-column decoders' launchers (launch.h): each forwards to the translation unit that holds the instantiation -- the row
+// operation's own unit, else the width's
+hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+{
+    const auto unit = q == kQueryGather ? decode_generic_gather : q == kQueryFilter ? decode_generic_filter : q == kQuerySelect ? decode_generic_select
+                    : w == 8 ? decode_generic_w8 : decode_generic_w16;
+    return unit(w, fire, lowdim, cpl, q, grid, shmem, st, a);
+}
+hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+{
+    const auto unit = q == kQueryGather ? decode_fast_gather : q == kQueryFilter ? decode_fast_filter : q == kQuerySelect ? decode_fast_select
+                    : w == 8 ? decode_fast_w8 : decode_fast_w16;
+    return unit(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
+}
+hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
+{
+    const auto unit = q == kQueryFilter ? decode_uni_filter : w == 8 ? decode_uni_w8 : decode_uni_w16;
+    return unit(w, fire, nd, q, grid, st, a);
+}
 }  // namespace sprintz
 
 namespace {
 
 // ---------------------------------------------------------------- launch helpers
 
-// gather_rows: every range's entry starts at `rows`; a failing piece lowers it to its code (decode_kernel.h: gather_fail)
+// gather_rows: every range's entry starts at `rows`; a failing piece lowers it to its code (decode_ops.h: gather_fail)
 __global__ void gather_rets_fill(int64_t* rets, uint64_t n, int64_t v)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -307,6 +327,19 @@ int check_common(int codec, int esz, uint16_t ndims)
     if (esz != 1 && esz != 2) return fail(SPRINTZ_E_INVALID, "elem_bytes must be 1 or 2");
     if (ndims == 0) return fail(SPRINTZ_E_INVALID, "ndims == 0 (reference: sprintz.cpp:36 returns -1)");
     if (ndims > SPRINTZ_MI355X_MAX_NDIMS) return fail(SPRINTZ_E_UNSUPPORTED, "ndims above SPRINTZ_MI355X_MAX_NDIMS");
+    return 0;
+}
+
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows) check alike, behind check_common; the refusals that
+// name the operation come in its own words (rle_only == null: every codec is taken)
+int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
+                 const char* rle_only)
+{
+    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
+    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if (!d_comp || !d_offsets) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, many_columns);
+    if (rle_only && codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, rle_only);
     return 0;
 }
 
@@ -338,7 +371,7 @@ bool is_plain_device_memory(const void* p)
     return at.type == hipMemoryTypeDevice;
 }
 
-// query-on-compressed options of one decode launch (decode_kernel.h: Q template parameter)
+// query-on-compressed options of one decode launch (the decoders' Q template parameter; decode_ops.h)
 // a single call served straight from the caller thread's mapped host buffer by ONE launch of a workgroup-per-chunk kernel
 // (decode_lat.h / encode_lat.h): no staging kernel in front, no runtime wait behind -- the kernel's last store is the
 // call's ticket into a mapped host word
@@ -349,27 +382,14 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff / kQueryMaterialize / kQueryReduceOnly / kQueryWindow
+    int q = kQueryOff;          // kQueryOff .. kQuerySelect (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
-    // kQueryWindow: window_rows, windows per chunk slot, SPRINTZ_QUERY_WIN_* ops, [nchunks][win_count][ndims] outputs
-    uint32_t window_rows = 0, win_count = 0, win_ops = 0;
-    void* win_min = nullptr;
-    void* win_max = nullptr;
-    uint64_t* win_sum = nullptr;
-    // kQueryFilter: per-column bounds on the device, SPRINTZ_FILTER_ALL / _ANY, the mask ([nchunks][mask_stride] bytes) and the counts
-    const void* f_lo = nullptr;
-    const void* f_hi = nullptr;
-    uint32_t f_mode = 0, f_mask_stride = 0;
-    uint8_t* f_mask = nullptr;
-    uint32_t* f_counts = nullptr;
-    // kQuerySelect: the mask (f_mask_stride bytes a chunk, filter_rows' layout), every chunk's first output row, the rows of the output,
-    // the optional row numbers; rows of a chunk slot
-    const uint8_t* s_mask = nullptr;
-    const uint64_t* s_bases = nullptr;
-    uint64_t s_capacity = 0;
-    uint64_t* s_ids = nullptr;
-    uint32_t s_rpc = 0;
+    // the mode's own arguments, as the kernels take them (decode_ops.h)
+    WindowArgs win{};           // kQueryWindow
+    GatherArgs gather{};        // kQueryGather
+    FilterArgs filter{};        // kQueryFilter
+    SelectArgs select{};        // kQuerySelect
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -402,7 +422,7 @@ Shape decode_shape(int codec, int esz, const void* d_comp, uint64_t nchunks, uin
     s.codec = codec; s.esz = esz; s.D = ndims; s.nchunks = nchunks; s.chunk_len = chunk_len;
     s.noheader = noheader; s.q = qs.q; s.general = qs.general; s.col_stride = qs.col_stride; s.host_call = qs.hc != nullptr;
     s.comp_lo = low4(d_comp); s.out_lo = low4(d_out);
-    s.capacity = qs.s_capacity;
+    s.capacity = qs.select.capacity;
     return s;
 }
 
@@ -431,23 +451,10 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.chunks_per_group = p.chunks_per_group;
     a.qop = qs.qop;
     a.qres = qs.qres;
-    a.window_rows = qs.window_rows;
-    a.win_count = qs.win_count;
-    a.win_ops = qs.win_ops;
-    a.win_min = qs.win_min;
-    a.win_max = qs.win_max;
-    a.win_sum = qs.win_sum;
-    a.f_lo = qs.f_lo;
-    a.f_hi = qs.f_hi;
-    a.f_mode = qs.f_mode;
-    a.f_mask = qs.f_mask;
-    a.f_counts = qs.f_counts;
-    a.f_mask_stride = qs.f_mask_stride;
-    a.s_mask = qs.s_mask;
-    a.s_bases = qs.s_bases;
-    a.s_capacity = qs.s_capacity;
-    a.s_ids = qs.s_ids;
-    if (qs.q == kQuerySelect) a.g_rpc = qs.s_rpc;
+    a.win = qs.win;
+    a.gather = qs.gather;
+    a.filter = qs.filter;
+    a.select = qs.select;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -484,21 +491,20 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     case SPRINTZ_KF_DEC_BLK: what = "decode_blk kernel launch"; e = launch_decode_blk(w, grid, st, a, p.blkd); break;
     case SPRINTZ_KF_DEC_FAST:
         what = "decode_fast kernel launch";
-        if (qs.q == kQueryFilter) { e = launch_decode_fast_filter(w, p.fire, p.dp, p.cpl, p.exact, grid, (size_t)p.lds, st, a); break; }
-        if (qs.q == kQuerySelect) { e = launch_decode_fast_select(w, p.fire, p.dp, p.cpl, p.exact, grid, (size_t)p.lds, st, a); break; }
-        e = esz == 1 ? launch_decode_fast_w8(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a)
-                     : launch_decode_fast_w16(p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a);
+        e = launch_decode_fast(w, p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a);
         break;
-    case SPRINTZ_KF_DEC_UNI:
-        what = "decode_uni kernel launch";
-        if (qs.q == kQueryFilter) { e = launch_decode_uni_filter(w, p.fire, ndims, st, a); break; }
-        e = esz == 1 ? launch_decode_uni_w8(p.fire, ndims, qs.q, grid, st, a) : launch_decode_uni_w16(p.fire, ndims, qs.q, grid, st, a); break;
+    case SPRINTZ_KF_GATHER_FAST:
+        what = "decode_fast gather kernel launch";
+        e = launch_decode_fast(w, p.fire, p.dp, p.cpl, p.exact, qs.q, p.ds, grid, (size_t)p.lds, st, a);
+        break;
+    case SPRINTZ_KF_DEC_UNI: what = "decode_uni kernel launch"; e = launch_decode_uni(w, p.fire, ndims, qs.q, grid, st, a); break;
+    case SPRINTZ_KF_GATHER_GENERIC:
+        what = "decode gather kernel launch";
+        e = launch_decode_generic(w, p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a);
+        break;
     default:
         what = "decode kernel launch";
-        if (qs.q == kQueryFilter) { e = launch_decode_filter(w, p.fire, p.lowdim, p.cpl, grid, (size_t)p.lds, st, a); break; }
-        if (qs.q == kQuerySelect) { e = launch_decode_select(w, p.fire, p.lowdim, p.cpl, grid, st, a); break; }
-        e = esz == 1 ? launch_decode_w8(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a)
-                     : launch_decode_w16(p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a);
+        e = launch_decode_generic(w, p.fire, p.lowdim, p.cpl, qs.q, grid, (size_t)p.lds, st, a);
         break;
     }
     if (e != hipSuccess) return fail(SPRINTZ_E_HIP, what, e);
@@ -1608,21 +1614,18 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
     if (((ops & SPRINTZ_QUERY_WIN_MIN) && (uintptr_t)d_min % (uintptr_t)elem_bytes) || ((ops & SPRINTZ_QUERY_WIN_MAX) && (uintptr_t)d_max % (uintptr_t)elem_bytes) ||
         ((ops & SPRINTZ_QUERY_WIN_SUM) && (uintptr_t)d_sum % 8))
         return fail(SPRINTZ_E_INVALID, "min / max must be aligned to the element size, sum to 8 bytes");
-    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
-    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no query");
-    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
-    if (!d_comp || !d_offsets) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "more than 512 columns: no query", nullptr))) return rc;
     if ((rc = ensure_device())) return rc;
     const uint32_t rows = (chunk_len + ndims - 1) / ndims;
     QuerySpec qs;
     qs.q = kQueryWindow;
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.window_rows = window_rows;
-    qs.win_count = (rows + window_rows - 1) / window_rows;
-    qs.win_ops = ops;
-    qs.win_min = (ops & SPRINTZ_QUERY_WIN_MIN) ? d_min : nullptr;
-    qs.win_max = (ops & SPRINTZ_QUERY_WIN_MAX) ? d_max : nullptr;
-    qs.win_sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
+    qs.win.rows = window_rows;
+    qs.win.count = (rows + window_rows - 1) / window_rows;
+    qs.win.ops = ops;
+    qs.win.min = (ops & SPRINTZ_QUERY_WIN_MIN) ? d_min : nullptr;
+    qs.win.max = (ops & SPRINTZ_QUERY_WIN_MAX) ? d_max : nullptr;
+    qs.win.sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }
@@ -1635,27 +1638,19 @@ int sprintz_mi355x_filter_rows(int codec, int elem_bytes, const void* d_comp, co
     int rc = check_common(codec, elem_bytes, ndims);
     if (rc) return rc;
     if (mode != SPRINTZ_FILTER_ALL && mode != SPRINTZ_FILTER_ANY) return fail(SPRINTZ_E_INVALID, "filter_rows: mode must be SPRINTZ_FILTER_ALL or SPRINTZ_FILTER_ANY");
-    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
-    if (!d_lo || !d_hi || !d_comp || !d_offsets) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "more than 512 columns: no filter", "filter_rows: the RLE codecs (delta, xff) only"))) return rc;
+    if (!d_lo || !d_hi) return fail(SPRINTZ_E_INVALID, "null device pointer");
     if (!d_mask && !d_counts) return fail(SPRINTZ_E_INVALID, "filter_rows: neither a mask nor counts asked for");
     if ((uintptr_t)d_lo % (uintptr_t)elem_bytes || (uintptr_t)d_hi % (uintptr_t)elem_bytes)
         return fail(SPRINTZ_E_INVALID, "filter_rows: d_lo / d_hi must be aligned to the element size");
     if ((uintptr_t)d_counts % 4 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "filter_rows: d_counts must be aligned to 4 bytes, d_rets to 8");
-    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
-    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no filter");
-    if (codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, "filter_rows: the RLE codecs (delta, xff) only");
     if (nchunks == 0) return 0;
     if ((rc = ensure_device())) return rc;
     const uint32_t rows = (chunk_len + ndims - 1) / ndims;
     QuerySpec qs;
     qs.q = kQueryFilter;
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.f_lo = d_lo;
-    qs.f_hi = d_hi;
-    qs.f_mode = mode;
-    qs.f_mask = d_mask;
-    qs.f_counts = d_counts;
-    qs.f_mask_stride = (rows + 7) / 8;
+    qs.filter = FilterArgs{d_lo, d_hi, mode, d_mask, d_counts, (rows + 7) / 8};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }
@@ -1682,27 +1677,19 @@ int sprintz_mi355x_select_rows(int codec, int elem_bytes, const void* d_comp, co
 {
     int rc = check_common(codec, elem_bytes, ndims);
     if (rc) return rc;
-    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
-    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "more than 512 columns: no select", "select_rows: the RLE codecs (delta, xff) only"))) return rc;
     if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "select_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
-    if (!d_comp || !d_offsets || !d_mask || !d_bases || !d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if (!d_mask || !d_bases || !d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
     if ((uintptr_t)d_out % (uintptr_t)elem_bytes) return fail(SPRINTZ_E_INVALID, "select_rows: d_out must be aligned to the element size");
     if ((uintptr_t)d_bases % 8 || (uintptr_t)d_ids % 8 || (uintptr_t)d_rets % 8)
         return fail(SPRINTZ_E_INVALID, "select_rows: d_bases, d_ids and d_rets must be aligned to 8 bytes");
-    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no select");
-    if (codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, "select_rows: the RLE codecs (delta, xff) only");
     if (nchunks == 0) return 0;
     if ((rc = ensure_device())) return rc;
     const uint32_t rows = chunk_len / ndims;
     QuerySpec qs;
     qs.q = kQuerySelect;
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.f_mask_stride = (rows + 7) / 8;
-    qs.s_mask = d_mask;
-    qs.s_bases = d_bases;
-    qs.s_capacity = capacity;
-    qs.s_ids = d_ids;
-    qs.s_rpc = rows;
+    qs.select = SelectArgs{d_mask, d_bases, capacity, d_ids, rows, (rows + 7) / 8};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }
@@ -1714,12 +1701,10 @@ int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, co
 {
     int rc = check_common(codec, elem_bytes, ndims);
     if (rc) return rc;
-    if (codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, "gather_rows: the RLE codecs (delta, xff) only");
-    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no gather");
-    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
+    if ((rc = check_row_op(codec, chunk_len, ndims, 0, d_comp, d_offsets, "more than 512 columns: no gather", "gather_rows: the RLE codecs (delta, xff) only"))) return rc;
     if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "gather_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
     if (rows == 0) return fail(SPRINTZ_E_INVALID, "gather_rows: rows == 0");
-    if (!d_comp || !d_offsets || !d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if (!d_out) return fail(SPRINTZ_E_INVALID, "null device pointer");
     if (nranges > 0 && !d_starts) return fail(SPRINTZ_E_INVALID, "gather_rows: ranges without their starts");
     if ((uintptr_t)d_out % (uintptr_t)elem_bytes) return fail(SPRINTZ_E_INVALID, "gather_rows: d_out must be aligned to the element size");
     if ((uintptr_t)d_starts % 8 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "gather_rows: d_starts and d_rets must be aligned to 8 bytes");
@@ -1734,40 +1719,14 @@ int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, co
     Shape s;
     s.codec = codec; s.esz = esz; s.D = D; s.nchunks = nchunks; s.chunk_len = chunk_len; s.nranges = nranges; s.rows = rows; s.out_lo = low4(d_out);
     const Plan p = plan_gather(s, snapshot());
-    DecodeArgs a{};
-    a.comp = (const uint8_t*)d_comp;
-    a.offsets = d_offsets;
-    a.nchunks = nchunks;
-    a.chunk_len = chunk_len;
-    a.D = D;
-    a.log2DP = p.log2DP;
-    a.out = d_out;
-    a.rets = d_rets;
-    a.chunks_per_group = 1;
-    a.quirk = p.quirk;
-    a.lds_group_stride = p.lds_group_stride;
-    a.g_starts = d_starts;
-    a.g_nranges = nranges;
-    a.g_rows = rows;
-    a.g_rpc = R;
-    a.g_pieces = (uint32_t)P;
-    if (d_rets) {
+    QuerySpec qs;
+    qs.q = kQueryGather;
+    qs.gather = GatherArgs{d_starts, nranges, rows, R, (uint32_t)P};
+    if (d_rets) {                                          // (in front of the plan's verdict: a refused call leaves its entries filled, too)
         hipLaunchKernelGGL(gather_rets_fill, dim3((unsigned)((nranges + 255) / 256)), dim3(256), 0, st, d_rets, nranges, (int64_t)rows);
         HIP_TRY(hipGetLastError());
     }
-    if (p.err) return fail(p.err, p.what);
-    hipError_t e;
-    const char* what;
-    if (p.family == SPRINTZ_KF_GATHER_FAST) {
-        e = launch_decode_fast_gather(8 * esz, p.fire, p.dp, p.cpl, p.exact, (unsigned)p.grid, (size_t)p.lds, st, a);
-        what = "decode_fast gather kernel launch";
-    } else {
-        e = launch_decode_gather(8 * esz, p.fire, p.lowdim, p.cpl, (unsigned)p.grid, st, a);
-        what = "decode gather kernel launch";
-    }
-    if (e != hipSuccess) return fail(SPRINTZ_E_HIP, what, e);
-    dispatched(p.family);
-    return 0;
+    return decode_launch(p, esz, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, st, 0, 0, 0, qs);
 }
 
 int sprintz_mi355x_query_reduce(int op, const uint64_t* d_partials, uint64_t nchunks, uint16_t ndims, uint64_t* d_result,

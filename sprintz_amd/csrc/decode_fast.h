@@ -33,7 +33,6 @@
 namespace sprintz {
 
 typedef uint32_t __attribute__((aligned(1), may_alias)) u32_unaligned;
-typedef uint16_t __attribute__((aligned(1), may_alias)) u16_unaligned;
 struct __attribute__((aligned(1), packed)) u128_unaligned { uint32_t x, y, z, w; };
 
 typedef __attribute__((address_space(3))) const uint32_t lds_u32;
@@ -128,7 +127,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     static_assert(!GATHER || (!CM && !SPLIT && DS == 0), "gather: row-major destination, plain mappings");
     // SELECT (sprintz_mi355x_select_rows): a plain decode of the group's chunks whose store pieces go, row by row, where the caller's mask
     // and the chunk's base send them -- or nowhere.  The chunks of a wave land in unrelated output rows: the store descriptor is based
-    // at `out` and spans its s_capacity rows (the launch checks that they fit 32-bit offsets), and, as for the gather, the launch takes
+    // at `out` and spans its select.capacity rows (the launch checks that they fit 32-bit offsets), and, as for the gather, the launch takes
     // only rows of whole 16-byte pieces.
     constexpr bool SELECT = Q == kQuerySelect;
     static_assert(!SELECT || (!CM && !SPLIT && DS == 0), "select: row-major destination, plain mappings");
@@ -210,8 +209,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                             : SELECT ? 0
                                  : (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * ESZ;
     const uint64_t out_span = CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
-                            : GATHER ? a.g_nranges * (uint64_t)a.g_rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
-                            : SELECT ? a.s_capacity * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
+                            : GATHER ? a.gather.nranges * (uint64_t)a.gather.rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
+                            : SELECT ? a.select.capacity * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
                                  : a.nchunks * (uint64_t)a.chunk_len * ESZ - out_base;
     // (both are wave-uniform by construction; saying so keeps hipcc from wrapping every store in a
     //  readfirstlane waterfall loop -- 8 VALU per store it cannot prove away)
@@ -339,7 +338,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t wi = 0, wleft = 0;
     uint64_t wbase = 0;
     // filter rows (Q == kQueryFilter): this lane's columns' bounds, loaded once; fcm collects the 8 rows of the column being decoded,
-    // fl the lane's columns (inverted domain: decode_kernel.h, FilterCol); the group ORs its lanes once per block (f_block)
+    // fl the lane's columns (inverted domain: decode_ops.h, FilterCol); the group ORs its lanes once per block (f_block)
     FilterCol fc[CPL];
     uint32_t finv = 0, fcm = 0, fl = 0, fb = 0, fcnt = 0;  // fb: blocks of this chunk done = the mask byte the next block writes
     uint8_t* fmb = nullptr;
@@ -378,7 +377,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
     // after every block of 8 rows: the group's lanes combine, one lane stores the block's byte (fb < chunk_len / blk_elems <=
-    // f_mask_stride: the capacity guard has passed), every lane keeps the count
+    // mask_stride: the capacity guard has passed), every lane keeps the count
     auto f_block = [&]() {
         if constexpr (Q == kQueryFilter) {
             const uint32_t m = (group_or<DP>(fl) ^ finv) & 0xffu;
@@ -393,7 +392,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         for (int k = 0; k < CPL; k++)
             if (col_ok[k]) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
         wi++;
-        wleft = a.window_rows;
+        wleft = a.win.rows;
     };
     auto q_window = [&]() {                                // after every block of 8 rows
         if constexpr (Q == kQueryWindow) {
@@ -427,12 +426,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             mwin0 = b & ~3u;
             const uint32_t o = mwin0 + 4u * (uint32_t)lane_d;
             mwin = 0;
-            if (o + 4u <= a.f_mask_stride) {
+            if (o + 4u <= a.select.mask_stride) {
                 mwin = *(const u32_unaligned*)(smb + o);
             } else {
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; j++)
-                    if (o + j < a.f_mask_stride) mwin |= (uint32_t)smb[o + j] << (8u * j);
+                    if (o + j < a.select.mask_stride) mwin |= (uint32_t)smb[o + j] << (8u * j);
             }
         }
         const uint32_t i = b - mwin0;
@@ -571,8 +570,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             uint32_t vo = ovo + u;
             if constexpr (SELECT) {                        // the piece's row is one the mask wants, and its place is inside `out` (compared in 64 bits)
                 const uint64_t p = select_place(sbase + srank, sm, prow[q]);
-                in = in && ((sm >> prow[q]) & 1u) && p < a.s_capacity;
-                vo = (uint32_t)p * row_stride + pcol[q];   // (s_capacity rows fit 32-bit offsets: the launch checks)
+                in = in && ((sm >> prow[q]) & 1u) && p < a.select.capacity;
+                vo = (uint32_t)p * row_stride + pcol[q];   // (select.capacity rows fit 32-bit offsets: the launch checks)
             }
             const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
             if (slot >= 0) {
@@ -787,7 +786,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto packed_block = [&](const int (&e)[CPL][8], int slot) {   // forecast recurrence (:993-1150)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
-        if constexpr (SELECT) sm = sel_byte(fb);           // (block fb < chunk_len / blk_elems <= f_mask_stride: the guard has passed)
+        if constexpr (SELECT) sm = sel_byte(fb);           // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -903,19 +902,19 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
             for (int k = 0; k < CPL; k++) qmin[k] = MASK;
             wi = 0;
-            wleft = a.window_rows;
-            wbase = chunk * (uint64_t)a.win_count;
+            wleft = a.win.rows;
+            wbase = chunk * (uint64_t)a.win.count;
         }
         if constexpr (Q == kQueryFilter) {
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
-            fmb = a.f_mask ? a.f_mask + chunk * (uint64_t)a.f_mask_stride : nullptr;
+            fmb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
         }
         if constexpr (SELECT) {
             fb = 0; srank = 0; sm = 0;
             mwin0 = 0x80000000u;                           // no window yet: the first block loads one
-            smb = a.s_mask + chunk * (uint64_t)a.f_mask_stride;
-            sbase = a.s_bases[chunk];
-            srow0 = chunk * (uint64_t)a.g_rpc;
+            smb = a.select.mask + chunk * (uint64_t)a.select.mask_stride;
+            sbase = a.select.bases[chunk];
+            srow0 = chunk * (uint64_t)a.select.rpc;
         }
         out_left = a.chunk_len;
         ovo = CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
@@ -1048,20 +1047,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // ---- verbatim tail (:1171), straight from HBM
     const uint32_t out_elems = a.chunk_len - out_left;
     if constexpr (GATHER) {
-        // rows of the tail the piece still needs -- or rows the stream does not hold (the short last chunk)
-        if (corrupt) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); return; }
-        if (grow >= gp.hi) return;                         // delivered in full: the range's entry keeps g_rows
-        if (remaining > out_left || (uint64_t)gp.hi * (uint32_t)D > (uint64_t)out_elems + remaining) {
-            if (lane_d == 0) gather_fail(a, gp.range, remaining > out_left ? kErrCorrupt : kErrNoRow);
-            return;
-        }
-        if (gabs + rp + (uint64_t)remaining * ESZ > a.offsets[chunk + 1]) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); return; }
-        const uint8_t* t = a.comp + gabs + rp;
-        const uint32_t e_lo = gp.lo * (uint32_t)D > out_elems ? gp.lo * (uint32_t)D - out_elems : 0u;
-        const uint32_t e_hi = gp.hi * (uint32_t)D - out_elems;
-        U* const d = (U*)a.out + (gp.obase + (int64_t)out_elems);
-        for (uint32_t e = e_lo + (uint32_t)lane_d; e < e_hi; e += DP)
-            d[e] = ESZ == 1 ? (U)t[e] : (U)*(const u16_unaligned*)(t + 2 * e);
+        // (Two ways out of the kernel here, where there were five: with the earlier returns hipcc no longer proved the stream loads'
+        //  descriptor wave-uniform and wrapped each ring load in a v_readfirstlane loop -- 40 - 53 v_readfirstlane a kernel against
+        //  4 - 5 now, the gather 6 - 10 % slower.  Nothing in the source states that uniformity: count them after an edit here.)
+        if (grow >= gp.hi && !corrupt) return;             // delivered in full: the range's entry keeps gather.rows
+        gather_tail<W>(a, gp, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP, corrupt || remaining > out_left,
+                       gabs + rp + (uint64_t)remaining * ESZ > a.offsets[chunk + 1]);
         return;
     }
     if (!corrupt && remaining > out_left) corrupt = true;
@@ -1069,12 +1060,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // bytes behind it (the next stream's, or padding) decoded to
     if (!corrupt && gabs + rp + (uint64_t)remaining * ESZ > off_c + stream_len) corrupt = true;
     if constexpr (Q == kQueryFilter) {
-        // the tail is read by column, 32 rows a trip; the mask bytes of the slot's rows past the data are zeroed (decode_kernel.h)
         if (!corrupt) filter_tail<W, CPL>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, fb, lane_d, DP, fc, genk, col_ok, fcnt);
-        if (lane_d == 0 && a.f_counts) a.f_counts[chunk] = fcnt;
+        if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
     } else if constexpr (Q == kQueryWindow) {
-        // tail element e is in column e % D, one row past the column's previous one: a window edge can fall inside the
-        // tail (W = 8).  Then the partial window leaves, and the identities of the slot's windows past the data.
+        // window_tail and reduce_tail (decode_ops.h), kept local: through the shared helpers these kernels were scheduled differently
+        // and measured 0.6 - 1.2 % slower on the headline and 80-column batches (profiles/decode_ops_ab.txt); this is their code
         if (!corrupt) {
             const uint8_t* t = a.comp + gabs + rp;
 #pragma unroll
@@ -1085,26 +1075,25 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     if (left == 0) {
                         win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
                         w++;
-                        left = a.window_rows;
+                        left = a.win.rows;
                     }
                     left--;
-                    const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16_unaligned*)(t + 2 * e);
+                    const uint32_t x = tail_elem<W>(t, e);
                     qmin[k] = x < qmin[k] ? x : qmin[k];
                     qmax[k] = x > qmax[k] ? x : qmax[k];
                     qsum[k] += x;
                 }
-                for (; w < a.win_count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
+                for (; w < a.win.count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
             }
         }
-    } else if constexpr (Q != 0) {
-        // the verbatim tail continues the row-major order: element e sits in column e % D
+    } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) {
             const uint8_t* t = a.comp + gabs + rp;
 #pragma unroll
             for (int k = 0; k < CPL; k++) {
                 if (!col_ok[k]) continue;
                 for (uint32_t e = (uint32_t)genk[k]; e < remaining; e += (uint32_t)D) {
-                    const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16_unaligned*)(t + 2 * e);
+                    const uint32_t x = tail_elem<W>(t, e);
                     qmax[k] = x > qmax[k] ? x : qmax[k];
                     qsum[k] += x;
                 }
@@ -1113,13 +1102,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
     }
     if constexpr (SELECT) {
-        // the tail's whole rows by the same rule, straight from HBM (fb blocks = 8 fb rows lie in front of it)
+        // fb blocks = 8 fb rows lie in front of the tail
         if (!corrupt && remaining > 0)
             select_tail<W>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, sbase, srank, lane_d, DP, [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if (!corrupt && remaining > 0 && !query_reduce_only(Q) && CM) {
         const uint8_t* t = a.comp + gabs + rp;
         U* const c0 = (U*)((uint8_t*)a.out + out_base + ovo);          // column 0 at the tail's first row
         for (uint32_t e = (uint32_t)lane_d; e < remaining; e += DP) {
+            // tail_elem, spelled out: called here, the 16-bit column-major kernels of the plain decode come out with two address
+            // additions in the other order (tools/kernel_diff.py), and the plain decode keeps its code
             const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16_unaligned*)(t + 2 * e);
             c0[(uint64_t)(e % (uint32_t)D) * a.col_stride + e / (uint32_t)D] = (U)x;
         }

@@ -3,15 +3,16 @@
 // decode_w16.hip keep the code and the flags they had.
 #include "launch.h"
 namespace sprintz {
-hipError_t launch_decode_filter(int w, bool fire, bool lowdim, int cpl, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_generic_filter(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
+    if (q != kQueryFilter) return hipErrorInvalidValue;
     if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, kQueryFilter) }
     if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, kQueryFilter) }
     return hipErrorInvalidValue;
 }
-hipError_t launch_decode_fast_filter(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_fast_filter(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (a.col_stride) return hipErrorInvalidValue;
+    if (q != kQueryFilter || ds != 0 || a.col_stride) return hipErrorInvalidValue;
     if (w == 8) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 8, kQueryFilter, false) }
     if (w == 16) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 16, kQueryFilter, false) }
     return hipErrorInvalidValue;
@@ -24,8 +25,9 @@ hipError_t launch_decode_fast_filter(int w, bool fire, int dp, int cpl, bool exa
         else hipLaunchKernelGGL((decode_uni_kernel<WV, false, NDV, kQueryFilter>), dim3(g), dim3(tpb), 0, st, a);      \
         return hipGetLastError();                                                                                     \
     }
-hipError_t launch_decode_uni_filter(int w, bool fire, int nd, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_uni_filter(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
 {
+    if (q != kQueryFilter) return hipErrorInvalidValue;
     SPRINTZ_UNI_FILTER_CASE(8, 1)
     SPRINTZ_UNI_FILTER_CASE(8, 2)
     SPRINTZ_UNI_FILTER_CASE(8, 3)

@@ -11,227 +11,9 @@
 // see DESIGN.md "Reference decoder quirk".
 #pragma once
 
-#include "sprintz_device.h"
+#include "decode_ops.h"
 
 namespace sprintz {
-
-struct DecodeArgs {
-    const uint8_t* comp;        // compressed bytes
-    const uint64_t* offsets;    // [nchunks] byte offset of each chunk stream
-    uint64_t nchunks;
-    uint32_t chunk_len;         // elements per decoded chunk slot (output stride)
-    int D;                      // ndims
-    int log2DP;                 // lanes per chunk = 1 << log2DP
-    void* out;                  // decoded elements, chunk c at out + c*chunk_len
-    int64_t* rets;              // optional per-chunk element counts
-    int vec_store;              // 1: LDS-transposed 16-byte stores are legal (alignment checked on host)
-    uint32_t lds_group_stride;  // bytes of LDS per group when vec_store
-    // headerless form (sprintz_xff.h:56-58)
-    int noheader;
-    uint32_t nh_ngroups;
-    uint32_t nh_remaining;
-    uint32_t chunks_per_group;  // decode_fast: consecutive chunks decoded by one lane group
-    // query-on-compressed (sprintz_delta.h:95-98, sprintz_xff.h:90-93, query.hpp:23-29): kernels
-    // instantiated with Q != 0 reduce every column of every chunk while decoding
-    // column-major destination (BASELINE config 5): element (row r, column d) at out[d*col_stride + r];
-    // chunk c holds rows [c*chunk_len/D, ...).  0 = row-major.
-    uint64_t col_stride;
-    // non-RLE codecs (sprintz_delta.cpp:64-1391; generic kernel only): 6-byte header {u32 len; u16 ndims},
-    // len/(16 D) groups, an all-zero block has no payload and no run length; raw: bit-packing only
-    int norle;
-    int raw;
-    int quirk;                  // 1: replay the runs of 16-bit general-layout FIRE streams as the REFERENCE DECODER does (fire_coef_ref_run16)
-    int qop;                    // 1: max, 2: sum (what lands in qres)
-    uint64_t* qres;             // [nchunks][D] per-chunk, per-column partial results
-    // a single call on the caller thread's mapped host buffer (decode_lat.h alone): offsets == null -> the one chunk's stream is
-    // comp[one_off0, one_off1); host_flag != null -> the kernel ends by writing host_ticket there, after every lane's stores
-    uint64_t one_off0, one_off1;
-    uint64_t* host_flag;
-    uint64_t host_ticket;
-    // windowed query (Q == kQueryWindow; sprintz_mi355x_query_windows): chunk c, window w (rows [w*W, (w+1)*W) of the chunk
-    // slot) and column d land at entry (c*win_count + w)*D + d of each selected output; appended so that no field above moves
-    uint32_t window_rows;       // W, a multiple of 8: a block of 8 rows never straddles a window edge
-    uint32_t win_count;         // windows per chunk slot: ceil(ceil(chunk_len / D) / W)
-    uint32_t win_ops;           // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4
-    void* win_min;              // element type
-    void* win_max;              // element type
-    uint64_t* win_sum;
-    // gather rows (Q == kQueryGather; sprintz_mi355x_gather_rows): range i is batch rows [g_starts[i], g_starts[i] + g_rows), batch row g
-    // being row g % g_rpc of chunk g / g_rpc; piece slot s = i * g_pieces + k decodes chunk g_starts[i] / g_rpc + k (gather_piece below)
-    const uint64_t* g_starts;   // [g_nranges], on the device
-    uint64_t g_nranges;
-    uint32_t g_rows;            // rows of every range
-    uint32_t g_rpc;             // R: rows of a chunk slot, chunk_len / D
-    uint32_t g_pieces;          // P: the most chunks a range can touch, (g_rows + R - 2) / R + 1
-    // filter rows (Q == kQueryFilter; sprintz_mi355x_filter_rows): row r of chunk c matches if every (f_mode 0) / some (f_mode 1) column d
-    // has f_lo[d] <= x <= f_hi[d], unsigned; bit r & 7 of f_mask[c * f_mask_stride + (r >> 3)], the chunk's matches in f_counts[c]
-    const void* f_lo;           // [D], element type, on the device
-    const void* f_hi;
-    uint32_t f_mode;            // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter
-    uint8_t* f_mask;            // optional
-    uint32_t* f_counts;         // optional
-    uint32_t f_mask_stride;     // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
-    // select rows (Q == kQuerySelect; sprintz_mi355x_select_rows): the i-th set bit of chunk c's mask bytes s_mask[c * f_mask_stride ...]
-    // (filter_rows' layout), row r, lands at row s_bases[c] + i of `out` and c * g_rpc + r at the same place of s_ids; a place
-    // >= s_capacity is dropped
-    const uint8_t* s_mask;      // [nchunks][f_mask_stride]
-    const uint64_t* s_bases;    // [nchunks]
-    uint64_t s_capacity;        // rows of `out` (and entries of s_ids)
-    uint64_t* s_ids;            // optional
-};
-
-// select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the
-// chunk's base plus the set bits in front of the block
-__device__ __forceinline__ uint64_t select_place(uint64_t first, uint32_t m, uint32_t row) { return first + (uint32_t)__popc(m & ((1u << row) - 1u)); }
-// the row numbers of those rows: lanes 0 .. 7 of the group take a row each (groups of fewer lanes take turns); one writer an entry
-__device__ __forceinline__ void select_ids(const DecodeArgs& a, uint64_t first, uint32_t m, uint64_t row0, int lane_d, int DP)
-{
-    if (!a.s_ids) return;
-    for (uint32_t j = (uint32_t)lane_d; j < 8u; j += (uint32_t)DP) {
-        const uint64_t p = select_place(first, m, j);
-        if (((m >> j) & 1u) && p < a.s_capacity) a.s_ids[p] = row0 + j;
-    }
-}
-// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
-// A partial last row is not a row.  Every selected row is copied by the group's lanes, an element each; `rank` is the number of
-// the chunk's set bits in front of row0.  mask_at(b) is the chunk's mask byte b, read only where 8 b is below row0 + the tail's whole rows.
-template <int W, typename F>
-__device__ __forceinline__ void select_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0,
-                                            uint64_t base, uint32_t rank, int lane_d, int DP, F mask_at)
-{
-    using U = typename Elem<W>::U;
-    constexpr int ESZ = W / 8;
-    typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
-    const uint32_t nfull = remaining / D;
-    for (uint32_t r0 = 0; r0 < nfull; r0 += 8u) {
-        const uint32_t n = nfull - r0 < 8u ? nfull - r0 : 8u;
-        const uint32_t m = mask_at((row0 + r0) >> 3) & ((1u << n) - 1u);
-        const uint64_t first = base + rank;
-        for (uint32_t j = 0; j < n; j++) {
-            if (!((m >> j) & 1u)) continue;
-            const uint64_t p = select_place(first, m, j);
-            if (p >= a.s_capacity) continue;
-            U* const d = (U*)a.out + p * (uint64_t)D;
-            const uint8_t* const s = t + (size_t)(r0 + j) * D * ESZ;
-            for (uint32_t e = (uint32_t)lane_d; e < D; e += (uint32_t)DP) d[e] = ESZ == 1 ? (U)s[e] : (U)*(const u16u*)(s + 2 * e);
-        }
-        select_ids(a, first, m, chunk * (uint64_t)a.g_rpc + row0 + r0, lane_d, DP);
-        rank += (uint32_t)__popc(m);
-    }
-}
-
-// windowed query: one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the
-// accumulators start over from the identities (min = all ones, max = 0, sum = 0)
-template <int W>
-__device__ __forceinline__ void win_flush(const DecodeArgs& a, uint64_t idx, uint32_t& qmin, uint32_t& qmax, uint64_t& qsum)
-{
-    using U = typename Elem<W>::U;
-    if (a.win_ops & 1u) ((U*)a.win_min)[idx] = (U)qmin;
-    if (a.win_ops & 2u) ((U*)a.win_max)[idx] = (U)qmax;
-    if (a.win_ops & 4u) a.win_sum[idx] = qsum;
-    qmin = Elem<W>::MASK;
-    qmax = 0;
-    qsum = 0;
-}
-
-// ---- filter rows.  A column's test is one subtract and one compare: ((x - lo) & MASK) < span with span = hi - lo + 1, or 0 where
-// lo > hi ("never").  The kernels combine in the INVERTED domain of ALL -- a column contributes hit ^ inv, inv = all ones for ALL and
-// 0 for ANY -- so that both modes are one OR across columns and lanes with the identity 0 (what a lane column past the last one
-// contributes), and the result is un-inverted once per block.
-struct FilterCol { uint32_t lo, span; };
-template <int W>
-__device__ __forceinline__ FilterCol filter_col(const DecodeArgs& a, int col, bool genuine)
-{
-    using U = typename Elem<W>::U;
-    FilterCol f{0u, 0u};
-    if (genuine) {
-        const uint32_t lo = ((const U*)a.f_lo)[col], hi = ((const U*)a.f_hi)[col];
-        f.lo = lo;
-        f.span = lo <= hi ? hi - lo + 1u : 0u;
-    }
-    return f;
-}
-// (x may carry garbage above bit W: only its low W bits reach the masked difference)
-template <int W> __device__ __forceinline__ uint32_t filter_hit(const FilterCol& f, uint32_t x) { return ((x - f.lo) & Elem<W>::MASK) < f.span ? 1u : 0u; }
-__device__ __forceinline__ uint32_t filter_inv(const DecodeArgs& a) { return a.f_mode == 0u ? 0xffffffffu : 0u; }
-__device__ __forceinline__ uint32_t group_or_any(uint32_t v, int DP)
-{
-    for (int off = DP >> 1; off > 0; off >>= 1) v |= (uint32_t)__shfl_xor((int)v, off, DP);
-    return v;
-}
-// The verbatim tail, for the lane-per-column kernels: `remaining` elements at t, row-major from the row behind the chunk's
-// `blocks_done` blocks.  A partial last row is not a row.  32 rows a trip: a lane folds its columns into one word, the group ORs
-// the words, lanes 0 .. 3 store the trip's bytes; then the mask bytes of the slot's rows past the data are zeroed, spread over the
-// lanes.  Every byte has one writer, and all of them lie in the chunk's f_mask_stride bytes: blocks_done * 8 + remaining / D rows
-// are at most chunk_len / D (the callers check the tail against the slot before they come here).
-template <int W, int CPL>
-__device__ __forceinline__ void filter_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t blocks_done,
-                                            int lane_d, int DP, const FilterCol (&fc)[CPL], const int (&col)[CPL], const bool (&genuine)[CPL], uint32_t& count)
-{
-    constexpr int ESZ = W / 8;
-    typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;   // the tail starts at any byte: one 2-byte load an element
-    const uint32_t nfull = remaining / D, tbytes = (nfull + 7u) >> 3;
-    const uint32_t inv = filter_inv(a);
-    uint8_t* const mb = a.f_mask ? a.f_mask + chunk * (uint64_t)a.f_mask_stride : nullptr;
-    for (uint32_t r0 = 0; r0 < nfull; r0 += 32u) {
-        const uint32_t n = nfull - r0 < 32u ? nfull - r0 : 32u;
-        uint32_t v = 0;
-#pragma unroll
-        for (int k = 0; k < CPL; k++) {
-            if (!genuine[k]) continue;
-            for (uint32_t j = 0; j < n; j++) {
-                const uint32_t e = (r0 + j) * D + (uint32_t)col[k];
-                const uint32_t x = ESZ == 1 ? (uint32_t)t[e] : (uint32_t)*(const u16u*)(t + 2 * e);
-                v |= (filter_hit<W>(fc[k], x) ^ (inv & 1u)) << j;
-            }
-        }
-        v = (group_or_any(v, DP) ^ inv) & (n == 32u ? 0xffffffffu : (1u << n) - 1u);
-        count += (uint32_t)__popc(v);
-        if (mb) {
-            for (uint32_t b = (uint32_t)lane_d; b < 4u; b += (uint32_t)DP)
-                if ((r0 >> 3) + b < tbytes) mb[blocks_done + (r0 >> 3) + b] = (uint8_t)(v >> (8u * b));
-        }
-    }
-    if (mb) {
-        for (uint32_t j = blocks_done + tbytes + (uint32_t)lane_d; j < a.f_mask_stride; j += (uint32_t)DP) mb[j] = 0;
-    }
-}
-
-constexpr int64_t kErrCorrupt = -5;
-constexpr int64_t kErrNoRow = -1;             // gather: the range needs a row that does not exist (SPRINTZ_E_INVALID)
-
-// gather: what piece slot `slot` has to do.  All of it follows from g_starts[range] on the device; a slot past the range's last
-// chunk has nothing to do (false).  `obase` is where row 0 of the piece's CHUNK would land in `out`, in elements: negative or past
-// the range's own rows for most pieces -- the row test [lo, hi) alone decides which stores happen.
-struct GatherPiece {
-    uint64_t range, chunk;
-    uint32_t lo, hi;            // chunk-relative rows the range needs from this chunk, lo < hi <= g_rpc
-    int64_t obase;
-    bool exists;                // chunk < nchunks; if not, the range fails without a decode
-};
-__device__ __forceinline__ bool gather_piece(const DecodeArgs& a, uint64_t slot, GatherPiece& p)
-{
-    p.range = slot / a.g_pieces;
-    if (p.range >= a.g_nranges) return false;
-    const uint64_t k = slot - p.range * a.g_pieces, R = a.g_rpc;
-    const uint64_t g0 = a.g_starts[p.range], c0 = g0 / R;
-    p.exists = c0 < a.nchunks;                      // (checked first: c0 + k cannot wrap below)
-    p.chunk = 0; p.lo = 0; p.hi = 1; p.obase = 0;
-    if (!p.exists) return k == 0;                   // one slot reports the missing rows
-    const uint64_t first = g0 - c0 * R, end = first + a.g_rows;   // the range, in rows from row 0 of chunk c0
-    if (k * R >= end) return false;
-    p.chunk = c0 + k;
-    p.exists = p.chunk < a.nchunks;
-    p.lo = (uint32_t)((first > k * R ? first : k * R) - k * R);
-    p.hi = (uint32_t)((end < (k + 1) * R ? end : (k + 1) * R) - k * R);
-    p.obase = ((int64_t)(p.range * a.g_rows) + (int64_t)(k * R) - (int64_t)first) * (int64_t)a.D;
-    return true;
-}
-// a failing piece leaves its code in the range's entry (the entries start at g_rows: gather_rets_fill; the smallest code wins)
-__device__ __forceinline__ void gather_fail(const DecodeArgs& a, uint64_t range, int64_t code)
-{
-    if (a.rets) atomicMin((long long*)&a.rets[range], (long long)code);
-}
 
 template <int W, bool FIRE, bool LOWDIM, int CPL, int Q = 0>
 __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
@@ -319,10 +101,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     uint32_t out_elems = 0;
     int slot = 2;
     uint32_t run_left = 0;
+    // the row operations (decode_ops.h) take the lane's columns as a list: which they are, and which of them exist
+    int colk[CPL];
+    bool genk[CPL];
     uint32_t qmax[CPL];
     uint64_t qsum[CPL];
 #pragma unroll
-    for (int k = 0; k < CPL; k++) { qmax[k] = 0; qsum[k] = 0; }
+    for (int k = 0; k < CPL; k++) { colk[k] = lane_d * CPL + k; genk[k] = colk[k] < D; qmax[k] = 0; qsum[k] = 0; }
     // windowed query: the window being accumulated and the rows it still takes
     // (set up in that mode alone: the other instantiations stay exactly as they were)
     uint32_t qmin[CPL];
@@ -331,25 +116,19 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (Q == kQueryWindow) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) qmin[k] = MASK;
-        wleft = a.window_rows;
-        wbase = chunk * (uint64_t)a.win_count;
+        wleft = a.win.rows;
+        wbase = chunk * (uint64_t)a.win.count;
     }
     // filter rows: each lane's columns' bounds, loaded once; the group ORs its lanes' block masks with wave shuffles (groups of up to
     // 64 lanes, both layouts), lane 0 stores the block's byte -- runs are replayed block by block here, as the decode does
     FilterCol fc[CPL];
-    int fcol[CPL];
-    bool fgen[CPL];
     uint32_t finv = 0, fcnt = 0;
     uint8_t* fmb = nullptr;
     if constexpr (Q == kQueryFilter) {
 #pragma unroll
-        for (int k = 0; k < CPL; k++) {
-            fcol[k] = lane_d * CPL + k;
-            fgen[k] = fcol[k] < D;
-            fc[k] = filter_col<W>(a, fcol[k], fgen[k]);
-        }
+        for (int k = 0; k < CPL; k++) fc[k] = filter_col<W>(a, colk[k], genk[k]);
         finv = filter_inv(a);
-        if (a.f_mask) fmb = a.f_mask + chunk * (uint64_t)a.f_mask_stride;
+        if (a.filter.mask) fmb = a.filter.mask + chunk * (uint64_t)a.filter.mask_stride;
     }
 
     // select rows: the chunk's mask bytes, its first output row and the set bits of the blocks done so far
@@ -357,8 +136,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     uint64_t sbase = 0;
     uint32_t srank = 0;
     if constexpr (Q == kQuerySelect) {
-        smb = a.s_mask + chunk * (uint64_t)a.f_mask_stride;
-        sbase = a.s_bases[chunk];
+        smb = a.select.mask + chunk * (uint64_t)a.select.mask_stride;
+        sbase = a.select.bases[chunk];
     }
 
     for (;;) {
@@ -485,7 +264,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 uint32_t cm = 0;
 #pragma unroll
                 for (int i = 0; i < 8; i++) cm |= filter_hit<W>(fc[k], v[i][k]) << i;
-                fl |= fgen[k] ? (cm ^ finv) & 0xffu : 0u;
+                fl |= genk[k] ? (cm ^ finv) & 0xffu : 0u;
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
 #pragma unroll
@@ -506,11 +285,11 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     if (col < D) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
                 }
                 wi++;
-                wleft = a.window_rows;
+                wleft = a.win.rows;
             }
         }
 
-        if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= f_mask_stride (checked above)
+        if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride (checked above)
             const uint32_t m = (group_or_any(fl, DP) ^ finv) & 0xffu;
             if (fmb && lane_d == 0) fmb[out_elems / blk_elems] = (uint8_t)m;
             fcnt += (uint32_t)__popc(m);
@@ -534,10 +313,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                         if (r0 + (uint32_t)i >= gp.lo && r0 + (uint32_t)i < gp.hi) ((U*)a.out)[eb + (int64_t)(i * D + col)] = (U)v[i][k];
                 }
             }
-            if (r0 + 8u >= gp.hi) return;            // delivered in full: the range's entry keeps g_rows
+            if (r0 + 8u >= gp.hi) return;            // delivered in full: the range's entry keeps gather.rows
         } else if constexpr (Q == kQuerySelect) {
             // the block's rows whose bits are set, each at its place behind the chunk's base (block out_elems / blk_elems <
-            // chunk_len / blk_elems <= f_mask_stride: checked above); 64-bit addresses, a place >= s_capacity is dropped
+            // chunk_len / blk_elems <= mask_stride: checked above); 64-bit addresses, a place >= capacity is dropped
             (void)ob;
             const uint32_t r0 = out_elems / (uint32_t)D;
             const uint32_t m = smb[r0 >> 3];
@@ -550,11 +329,11 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 #pragma unroll
                         for (int i = 0; i < 8; i++) {
                             const uint64_t p = select_place(first, m, (uint32_t)i);
-                            if (((m >> i) & 1u) && p < a.s_capacity) ((U*)a.out)[p * (uint64_t)D + (uint64_t)col] = (U)v[i][k];
+                            if (((m >> i) & 1u) && p < a.select.capacity) ((U*)a.out)[p * (uint64_t)D + (uint64_t)col] = (U)v[i][k];
                         }
                     }
                 }
-                select_ids(a, first, m, chunk * (uint64_t)a.g_rpc + r0, lane_d, DP);
+                select_ids(a, first, m, chunk * (uint64_t)a.select.rpc + r0, lane_d, DP);
             }
             srank += (uint32_t)__popc(m);
         } else if (cs) {
@@ -620,68 +399,15 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // ---- verbatim tail (:1171)
     if (!corrupt && (out_elems + remaining > a.chunk_len || (uint64_t)remaining * ESZ > (uint64_t)(stream_len - pos))) corrupt = true;
     if constexpr (Q == kQueryFilter) {
-        if (!corrupt) filter_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, fc, fcol, fgen, fcnt);
-        if (lane_d == 0 && a.f_counts) a.f_counts[chunk] = fcnt;
+        if (!corrupt) filter_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, fc, colk, genk, fcnt);
+        if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
     } else if constexpr (Q == kQueryWindow) {
-        // tail element e is in column e % D, one row further on than the column's previous one; a window
-        // edge can fall inside the tail.  Then the partial window and the identities of the slot's last ones.
-        if (!corrupt) {
-            const uint8_t* t = s + pos;
-#pragma unroll
-            for (int k = 0; k < CPL; k++) {
-                const int col = lane_d * CPL + k;
-                if (col >= D) continue;
-                uint32_t w = wi, left = wleft;
-                for (uint32_t e = (uint32_t)col; e < remaining; e += (uint32_t)D) {
-                    if (left == 0) {
-                        win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
-                        w++;
-                        left = a.window_rows;
-                    }
-                    left--;
-                    const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
-                    qmin[k] = x < qmin[k] ? x : qmin[k];
-                    qmax[k] = x > qmax[k] ? x : qmax[k];
-                    qsum[k] += x;
-                }
-                for (; w < a.win_count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
-            }
-        }
-    } else if constexpr (Q != 0) {
-        // the verbatim tail continues the row-major order: element e sits in column e % D
-        // (out_elems is a multiple of 8*D)
-        if (!corrupt) {
-            const uint8_t* t = s + pos;
-#pragma unroll
-            for (int k = 0; k < CPL; k++) {
-                const int col = lane_d * CPL + k;
-                if (col >= D) continue;
-                for (uint32_t e = (uint32_t)col; e < remaining; e += (uint32_t)D) {
-                    const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
-                    qmax[k] = x > qmax[k] ? x : qmax[k];
-                    qsum[k] += x;
-                }
-                if (a.qres) a.qres[chunk * (uint64_t)D + (uint64_t)col] = a.qop == 1 ? (uint64_t)qmax[k] : qsum[k];
-            }
-        }
+        if (!corrupt) window_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum);
+    } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
+        if (!corrupt) reduce_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, colk, genk, qmax, qsum);      // (out_elems is a multiple of 8*D)
     }
     if constexpr (Q == kQueryGather) {
-        // the piece still needs rows of the verbatim tail -- or rows the stream does not hold (the short last chunk)
-        if (!corrupt && (uint64_t)gp.hi * (uint32_t)D > (uint64_t)out_elems + remaining) {
-            if (lane_d == 0) gather_fail(a, gp.range, kErrNoRow);
-            return;
-        }
-        if (corrupt) {
-            if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt);
-            return;
-        }
-        const uint8_t* t = s + pos;
-        const uint32_t e_lo = gp.lo * (uint32_t)D > out_elems ? gp.lo * (uint32_t)D - out_elems : 0u;
-        const uint32_t e_hi = gp.hi * (uint32_t)D - out_elems;                  // <= remaining, checked above
-        for (uint32_t e = e_lo + (uint32_t)lane_d; e < e_hi; e += (uint32_t)DP) {
-            const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
-            ((U*)a.out)[gp.obase + (int64_t)out_elems + (int64_t)e] = (U)x;
-        }
+        gather_tail<W>(a, gp, s + pos, out_elems, remaining, (uint32_t)D, lane_d, DP, corrupt, false);
         return;
     }
     if constexpr (Q == kQuerySelect) {
@@ -694,7 +420,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         const uint8_t* t = s + pos;
         const uint32_t r0 = out_elems / (uint32_t)D;
         for (uint32_t e = (uint32_t)lane_d; e < remaining; e += (uint32_t)DP) {
-            const uint32_t x = ESZ == 1 ? load_u8(t + e) : (load_u8(t + 2 * e) | (load_u8(t + 2 * e + 1) << 8));
+            const uint32_t x = tail_elem<W>(t, e);
             cm0[(uint64_t)(e % (uint32_t)D) * cs + r0 + e / (uint32_t)D] = (U)x;
         }
     } else if (!corrupt && !query_reduce_only(Q)) {

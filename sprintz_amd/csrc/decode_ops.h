@@ -1,0 +1,310 @@
+// decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter and select
+// rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
+// its lane's columns (`col`, with `genuine` false for a lane column past the last one), its place in the group (`lane_d` of `DP`
+// lanes) and the mode's running state; decode_uni.h is the lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane
+// mapping -- how a block's rows reach the accumulators, the staging and the stores -- stays in that kernel.
+#pragma once
+
+#include "sprintz_device.h"
+
+namespace sprintz {
+
+// windowed query (Q == kQueryWindow; sprintz_mi355x_query_windows): chunk c, window w (rows [w*W, (w+1)*W) of the chunk
+// slot) and column d land at entry (c*count + w)*D + d of each selected output
+struct WindowArgs {
+    uint32_t rows;              // W, a multiple of 8: a block of 8 rows never straddles a window edge
+    uint32_t count;             // windows per chunk slot: ceil(ceil(chunk_len / D) / W)
+    uint32_t ops;               // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4
+    void* min;                  // element type
+    void* max;                  // element type
+    uint64_t* sum;
+};
+// gather rows (Q == kQueryGather; sprintz_mi355x_gather_rows): range i is batch rows [starts[i], starts[i] + rows), batch row g
+// being row g % rpc of chunk g / rpc; piece slot s = i * pieces + k decodes chunk starts[i] / rpc + k (gather_piece below)
+struct GatherArgs {
+    const uint64_t* starts;     // [nranges], on the device
+    uint64_t nranges;
+    uint32_t rows;              // rows of every range
+    uint32_t rpc;               // R: rows of a chunk slot, chunk_len / D
+    uint32_t pieces;            // P: the most chunks a range can touch, (rows + R - 2) / R + 1
+};
+// filter rows (Q == kQueryFilter; sprintz_mi355x_filter_rows): row r of chunk c matches if every (mode 0) / some (mode 1) column d
+// has lo[d] <= x <= hi[d], unsigned; bit r & 7 of mask[c * mask_stride + (r >> 3)], the chunk's matches in counts[c]
+struct FilterArgs {
+    const void* lo;             // [D], element type, on the device
+    const void* hi;
+    uint32_t mode;              // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter
+    uint8_t* mask;              // optional
+    uint32_t* counts;           // optional
+    uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
+};
+// select rows (Q == kQuerySelect; sprintz_mi355x_select_rows): the i-th set bit of chunk c's mask bytes mask[c * mask_stride ...]
+// (filter_rows' layout), row r, lands at row bases[c] + i of `out` and c * rpc + r at the same place of ids; a place
+// >= capacity is dropped
+struct SelectArgs {
+    const uint8_t* mask;        // [nchunks][mask_stride]
+    const uint64_t* bases;      // [nchunks]
+    uint64_t capacity;          // rows of `out` (and entries of ids)
+    uint64_t* ids;              // optional
+    uint32_t rpc;               // rows of a chunk slot, chunk_len / D
+    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rpc / 8)
+};
+
+struct DecodeArgs {
+    const uint8_t* comp;        // compressed bytes
+    const uint64_t* offsets;    // [nchunks] byte offset of each chunk stream
+    uint64_t nchunks;
+    uint32_t chunk_len;         // elements per decoded chunk slot (output stride)
+    int D;                      // ndims
+    int log2DP;                 // lanes per chunk = 1 << log2DP
+    void* out;                  // decoded elements, chunk c at out + c*chunk_len
+    int64_t* rets;              // optional per-chunk element counts
+    int vec_store;              // 1: LDS-transposed 16-byte stores are legal (alignment checked on host)
+    uint32_t lds_group_stride;  // bytes of LDS per group when vec_store
+    // headerless form (sprintz_xff.h:56-58)
+    int noheader;
+    uint32_t nh_ngroups;
+    uint32_t nh_remaining;
+    uint32_t chunks_per_group;  // decode_fast: consecutive chunks decoded by one lane group
+    // column-major destination (BASELINE config 5): element (row r, column d) at out[d*col_stride + r];
+    // chunk c holds rows [c*chunk_len/D, ...).  0 = row-major.
+    uint64_t col_stride;
+    // non-RLE codecs (sprintz_delta.cpp:64-1391; generic kernel only): 6-byte header {u32 len; u16 ndims},
+    // len/(16 D) groups, an all-zero block has no payload and no run length; raw: bit-packing only
+    int norle;
+    int raw;
+    int quirk;                  // 1: replay the runs of 16-bit general-layout FIRE streams as the REFERENCE DECODER does (fire_coef_ref_run16)
+    // query-on-compressed (sprintz_delta.h:95-98, sprintz_xff.h:90-93, query.hpp:23-29): kernels
+    // instantiated with Q == kQueryMaterialize / kQueryReduceOnly reduce every column of every chunk while decoding
+    int qop;                    // 1: max, 2: sum (what lands in qres)
+    uint64_t* qres;             // [nchunks][D] per-chunk, per-column partial results
+    // a single call on the caller thread's mapped host buffer (decode_lat.h alone): offsets == null -> the one chunk's stream is
+    // comp[one_off0, one_off1); host_flag != null -> the kernel ends by writing host_ticket there, after every lane's stores
+    uint64_t one_off0, one_off1;
+    uint64_t* host_flag;
+    uint64_t host_ticket;
+    // the row operations: appended, a mode behind the other, so that no field above moves
+    WindowArgs win;
+    GatherArgs gather;
+    FilterArgs filter;
+    SelectArgs select;
+};
+
+// the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
+typedef uint16_t __attribute__((aligned(1), may_alias)) u16_unaligned;
+template <int W> __device__ __forceinline__ uint32_t tail_elem(const uint8_t* t, uint32_t e)
+{
+    return W == 8 ? (uint32_t)t[e] : (uint32_t)*(const u16_unaligned*)(t + 2 * e);
+}
+
+// ---- reduce (Q == kQueryMaterialize / kQueryReduceOnly).  The verbatim tail continues the row-major order: element e sits in
+// column e % D.  Each genuine column's maximum and sum take the tail's elements in, then the chunk's result leaves.
+template <int W, int CPL>
+__device__ __forceinline__ void reduce_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, const int (&col)[CPL],
+                                            const bool (&genuine)[CPL], uint32_t (&qmax)[CPL], uint64_t (&qsum)[CPL])
+{
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        for (uint32_t e = (uint32_t)col[k]; e < remaining; e += D) {
+            const uint32_t x = tail_elem<W>(t, e);
+            qmax[k] = x > qmax[k] ? x : qmax[k];
+            qsum[k] += x;
+        }
+        if (a.qres) a.qres[chunk * (uint64_t)D + (uint64_t)col[k]] = a.qop == 1 ? (uint64_t)qmax[k] : qsum[k];
+    }
+}
+
+// ---- windowed query: one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the
+// accumulators start over from the identities (min = all ones, max = 0, sum = 0)
+template <int W>
+__device__ __forceinline__ void win_flush(const DecodeArgs& a, uint64_t idx, uint32_t& qmin, uint32_t& qmax, uint64_t& qsum)
+{
+    using U = typename Elem<W>::U;
+    if (a.win.ops & 1u) ((U*)a.win.min)[idx] = (U)qmin;
+    if (a.win.ops & 2u) ((U*)a.win.max)[idx] = (U)qmax;
+    if (a.win.ops & 4u) a.win.sum[idx] = qsum;
+    qmin = Elem<W>::MASK;
+    qmax = 0;
+    qsum = 0;
+}
+// The verbatim tail: element e is in column e % D, one row further on than the column's previous one, so a window edge can fall
+// inside the tail.  Window `wi` of the chunk (the first of them at entry `wbase`) still takes `wleft` rows.  Then the partial window
+// leaves, and the identities of the slot's windows past the data.
+template <int W, int CPL>
+__device__ __forceinline__ void window_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, const int (&col)[CPL], const bool (&genuine)[CPL],
+                                            uint64_t wbase, uint32_t wi, uint32_t wleft, uint32_t (&qmin)[CPL], uint32_t (&qmax)[CPL], uint64_t (&qsum)[CPL])
+{
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        uint32_t w = wi, left = wleft;
+        for (uint32_t e = (uint32_t)col[k]; e < remaining; e += D) {
+            if (left == 0) {
+                win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
+                w++;
+                left = a.win.rows;
+            }
+            left--;
+            const uint32_t x = tail_elem<W>(t, e);
+            qmin[k] = x < qmin[k] ? x : qmin[k];
+            qmax[k] = x > qmax[k] ? x : qmax[k];
+            qsum[k] += x;
+        }
+        for (; w < a.win.count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
+    }
+}
+
+// ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the
+// chunk's base plus the set bits in front of the block
+__device__ __forceinline__ uint64_t select_place(uint64_t first, uint32_t m, uint32_t row) { return first + (uint32_t)__popc(m & ((1u << row) - 1u)); }
+// the row numbers of those rows: lanes 0 .. 7 of the group take a row each (groups of fewer lanes take turns); one writer an entry
+__device__ __forceinline__ void select_ids(const DecodeArgs& a, uint64_t first, uint32_t m, uint64_t row0, int lane_d, int DP)
+{
+    if (!a.select.ids) return;
+    for (uint32_t j = (uint32_t)lane_d; j < 8u; j += (uint32_t)DP) {
+        const uint64_t p = select_place(first, m, j);
+        if (((m >> j) & 1u) && p < a.select.capacity) a.select.ids[p] = row0 + j;
+    }
+}
+// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
+// A partial last row is not a row.  Every selected row is copied by the group's lanes, an element each; `rank` is the number of
+// the chunk's set bits in front of row0.  mask_at(b) is the chunk's mask byte b, read only where 8 b is below row0 + the tail's whole rows.
+template <int W, typename F>
+__device__ __forceinline__ void select_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0,
+                                            uint64_t base, uint32_t rank, int lane_d, int DP, F mask_at)
+{
+    using U = typename Elem<W>::U;
+    const uint32_t nfull = remaining / D;
+    for (uint32_t r0 = 0; r0 < nfull; r0 += 8u) {
+        const uint32_t n = nfull - r0 < 8u ? nfull - r0 : 8u;
+        const uint32_t m = mask_at((row0 + r0) >> 3) & ((1u << n) - 1u);
+        const uint64_t first = base + rank;
+        for (uint32_t j = 0; j < n; j++) {
+            if (!((m >> j) & 1u)) continue;
+            const uint64_t p = select_place(first, m, j);
+            if (p >= a.select.capacity) continue;
+            U* const d = (U*)a.out + p * (uint64_t)D;
+            for (uint32_t e = (uint32_t)lane_d; e < D; e += (uint32_t)DP) d[e] = (U)tail_elem<W>(t, (r0 + j) * D + e);
+        }
+        select_ids(a, first, m, chunk * (uint64_t)a.select.rpc + row0 + r0, lane_d, DP);
+        rank += (uint32_t)__popc(m);
+    }
+}
+
+// ---- filter rows.  A column's test is one subtract and one compare: ((x - lo) & MASK) < span with span = hi - lo + 1, or 0 where
+// lo > hi ("never").  The kernels combine in the INVERTED domain of ALL -- a column contributes hit ^ inv, inv = all ones for ALL and
+// 0 for ANY -- so that both modes are one OR across columns and lanes with the identity 0 (what a lane column past the last one
+// contributes), and the result is un-inverted once per block.
+struct FilterCol { uint32_t lo, span; };
+template <int W>
+__device__ __forceinline__ FilterCol filter_col(const DecodeArgs& a, int col, bool genuine)
+{
+    using U = typename Elem<W>::U;
+    FilterCol f{0u, 0u};
+    if (genuine) {
+        const uint32_t lo = ((const U*)a.filter.lo)[col], hi = ((const U*)a.filter.hi)[col];
+        f.lo = lo;
+        f.span = lo <= hi ? hi - lo + 1u : 0u;
+    }
+    return f;
+}
+// (x may carry garbage above bit W: only its low W bits reach the masked difference)
+template <int W> __device__ __forceinline__ uint32_t filter_hit(const FilterCol& f, uint32_t x) { return ((x - f.lo) & Elem<W>::MASK) < f.span ? 1u : 0u; }
+__device__ __forceinline__ uint32_t filter_inv(const DecodeArgs& a) { return a.filter.mode == 0u ? 0xffffffffu : 0u; }
+__device__ __forceinline__ uint32_t group_or_any(uint32_t v, int DP)
+{
+    for (int off = DP >> 1; off > 0; off >>= 1) v |= (uint32_t)__shfl_xor((int)v, off, DP);
+    return v;
+}
+// The verbatim tail: `remaining` elements at t, row-major from the row behind the chunk's `blocks_done` blocks.  A partial last row
+// is not a row.  32 rows a trip: a lane folds its columns into one word, the group ORs the words, lanes 0 .. 3 store the trip's
+// bytes; then the mask bytes of the slot's rows past the data are zeroed, spread over the lanes.  Every byte has one writer, and all
+// of them lie in the chunk's mask_stride bytes: blocks_done * 8 + remaining / D rows are at most chunk_len / D (the callers check the
+// tail against the slot before they come here).
+template <int W, int CPL>
+__device__ __forceinline__ void filter_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t blocks_done,
+                                            int lane_d, int DP, const FilterCol (&fc)[CPL], const int (&col)[CPL], const bool (&genuine)[CPL], uint32_t& count)
+{
+    const uint32_t nfull = remaining / D, tbytes = (nfull + 7u) >> 3;
+    const uint32_t inv = filter_inv(a);
+    uint8_t* const mb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
+    for (uint32_t r0 = 0; r0 < nfull; r0 += 32u) {
+        const uint32_t n = nfull - r0 < 32u ? nfull - r0 : 32u;
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!genuine[k]) continue;
+            for (uint32_t j = 0; j < n; j++) v |= (filter_hit<W>(fc[k], tail_elem<W>(t, (r0 + j) * D + (uint32_t)col[k])) ^ (inv & 1u)) << j;
+        }
+        v = (group_or_any(v, DP) ^ inv) & (n == 32u ? 0xffffffffu : (1u << n) - 1u);
+        count += (uint32_t)__popc(v);
+        if (mb) {
+            for (uint32_t b = (uint32_t)lane_d; b < 4u; b += (uint32_t)DP)
+                if ((r0 >> 3) + b < tbytes) mb[blocks_done + (r0 >> 3) + b] = (uint8_t)(v >> (8u * b));
+        }
+    }
+    if (mb) {
+        for (uint32_t j = blocks_done + tbytes + (uint32_t)lane_d; j < a.filter.mask_stride; j += (uint32_t)DP) mb[j] = 0;
+    }
+}
+
+// ---- gather rows
+constexpr int64_t kErrCorrupt = -5;
+constexpr int64_t kErrNoRow = -1;             // gather: the range needs a row that does not exist (SPRINTZ_E_INVALID)
+
+// what piece slot `slot` has to do.  All of it follows from starts[range] on the device; a slot past the range's last
+// chunk has nothing to do (false).  `obase` is where row 0 of the piece's CHUNK would land in `out`, in elements: negative or past
+// the range's own rows for most pieces -- the row test [lo, hi) alone decides which stores happen.
+struct GatherPiece {
+    uint64_t range, chunk;
+    uint32_t lo, hi;            // chunk-relative rows the range needs from this chunk, lo < hi <= rpc
+    int64_t obase;
+    bool exists;                // chunk < nchunks; if not, the range fails without a decode
+};
+__device__ __forceinline__ bool gather_piece(const DecodeArgs& a, uint64_t slot, GatherPiece& p)
+{
+    p.range = slot / a.gather.pieces;
+    if (p.range >= a.gather.nranges) return false;
+    const uint64_t k = slot - p.range * a.gather.pieces, R = a.gather.rpc;
+    const uint64_t g0 = a.gather.starts[p.range], c0 = g0 / R;
+    p.exists = c0 < a.nchunks;                      // (checked first: c0 + k cannot wrap below)
+    p.chunk = 0; p.lo = 0; p.hi = 1; p.obase = 0;
+    if (!p.exists) return k == 0;                   // one slot reports the missing rows
+    const uint64_t first = g0 - c0 * R, end = first + a.gather.rows;   // the range, in rows from row 0 of chunk c0
+    if (k * R >= end) return false;
+    p.chunk = c0 + k;
+    p.exists = p.chunk < a.nchunks;
+    p.lo = (uint32_t)((first > k * R ? first : k * R) - k * R);
+    p.hi = (uint32_t)((end < (k + 1) * R ? end : (k + 1) * R) - k * R);
+    p.obase = ((int64_t)(p.range * a.gather.rows) + (int64_t)(k * R) - (int64_t)first) * (int64_t)a.D;
+    return true;
+}
+// a failing piece leaves its code in the range's entry (the entries start at gather.rows: gather_rets_fill; the smallest code wins)
+__device__ __forceinline__ void gather_fail(const DecodeArgs& a, uint64_t range, int64_t code)
+{
+    if (a.rets) atomicMin((long long*)&a.rets[range], (long long)code);
+}
+// The verbatim tail, `remaining` elements at t behind the `out_elems` the blocks held: the piece still needs rows of it -- or rows
+// the stream does not hold (the short last chunk), which outranks a tail that overruns its stream but not a stream found `corrupt`
+// before.  Elements [e_lo, e_hi) of the tail are the piece's, spread over the group's lanes.
+template <int W>
+__device__ __forceinline__ void gather_tail(const DecodeArgs& a, const GatherPiece& gp, const uint8_t* t, uint32_t out_elems, uint32_t remaining, uint32_t D,
+                                            int lane_d, int DP, bool corrupt, bool overrun)
+{
+    using U = typename Elem<W>::U;
+    if (!corrupt && (uint64_t)gp.hi * D > (uint64_t)out_elems + remaining) {
+        if (lane_d == 0) gather_fail(a, gp.range, kErrNoRow);
+        return;
+    }
+    if (corrupt || overrun) {
+        if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt);
+        return;
+    }
+    const uint32_t e_lo = gp.lo * D > out_elems ? gp.lo * D - out_elems : 0u;
+    const uint32_t e_hi = gp.hi * D - out_elems;                              // <= remaining, checked above
+    U* const d = (U*)a.out + (gp.obase + (int64_t)out_elems);
+    for (uint32_t e = e_lo + (uint32_t)lane_d; e < e_hi; e += (uint32_t)DP) d[e] = (U)tail_elem<W>(t, e);
+}
+
+}  // namespace sprintz

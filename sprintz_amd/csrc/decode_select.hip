@@ -3,17 +3,18 @@
 // decode_w16.hip keep the code and the flags they had.  decode_uni.h is not taught the mode: its shapes go to the generic kernel.
 #include "launch.h"
 namespace sprintz {
-hipError_t launch_decode_select(int w, bool fire, bool lowdim, int cpl, unsigned grid, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_generic_select(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    const size_t shmem = 0;                                // scalar stores: no LDS transpose
+    if (q != kQuerySelect) return hipErrorInvalidValue;
+    shmem = 0;                                             // whatever the plan carved: scalar stores, no LDS transpose
     if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, kQuerySelect) }
     if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, kQuerySelect) }
     return hipErrorInvalidValue;
 }
 // row-major destination, rows of whole 16-byte store pieces: 16 columns and more, or 8 columns of 16 bits (the gather's set)
-hipError_t launch_decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (a.col_stride) return hipErrorInvalidValue;
+    if (q != kQuerySelect || ds != 0 || a.col_stride) return hipErrorInvalidValue;
     if (w == 16) {
         SPRINTZ_FAST_CASE(decode_fast_kernel, 16, 8, 1, kQuerySelect, false)
         SPRINTZ_FAST_CASE(decode_fast_kernel, 16, 16, 1, kQuerySelect, false)

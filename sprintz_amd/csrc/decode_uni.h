@@ -42,7 +42,7 @@ constexpr int decode_uni_ring_pieces(int W, int ND)
 }
 constexpr int decode_uni_threads(int W, int ND) { return (decode_uni_ring_pieces(W, ND) == 4 && decode_uni_refill_every(W, ND) > 1) ? 128 : 256; }
 
-// Q: query-on-compressed (decode_kernel.h): per-column max and sum ride along; reduce-only never stores samples
+// Q: query-on-compressed (decode_ops.h): per-column max and sum ride along; reduce-only never stores samples
 template <int W, bool FIRE, int ND = 1, int Q = 0>
 __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(DecodeArgs a)
 {
@@ -159,17 +159,17 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
     if constexpr (Q == kQueryWindow) {
 #pragma unroll
         for (int k = 0; k < ND; k++) qmin[k] = MASK;
-        wleft = a.window_rows;
-        wbase = chunk * (uint64_t)a.win_count;
+        wleft = a.win.rows;
+        wbase = chunk * (uint64_t)a.win.count;
     }
     auto win_flush_all = [&]() {
 #pragma unroll
         for (int k = 0; k < ND; k++) win_flush<W>(a, (wbase + wi) * (uint64_t)ND + (uint64_t)k, qmin[k], qmax[k], qsum[k]);
         wi++;
-        wleft = a.window_rows;
+        wleft = a.win.rows;
     };
     // filter rows (Q == kQueryFilter): all ND columns sit in this lane, so a row's verdict needs no other lane; a block's byte is one
-    // 1-byte store at the lane's own address (chunk * f_mask_stride has any alignment and the lanes of a wave are at different
+    // 1-byte store at the lane's own address (chunk * mask_stride has any alignment and the lanes of a wave are at different
     // blocks after the first run: the bytes are not gathered into dwords)
     FilterCol fc[ND];
     uint32_t finv = 0, fcnt = 0;
@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
 #pragma unroll
         for (int k = 0; k < ND; k++) fc[k] = filter_col<W>(a, k, true);
         finv = filter_inv(a);
-        if (a.f_mask && exists) fmb = a.f_mask + chunk * (uint64_t)a.f_mask_stride;
+        if (a.filter.mask && exists) fmb = a.filter.mask + chunk * (uint64_t)a.filter.mask_stride;
     }
     int slot = 2;
     uint8_t* const obase = (uint8_t*)a.out + chunk * (uint64_t)a.chunk_len * ESZ;
@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
 #pragma unroll
                 for (int e = 0; e < 8 * ND; e++) win[b][(e * ESZ) / 4] |= x[e % ND][e / ND] << (((e * ESZ) % 4) * 8);
                 }
-                if constexpr (Q == kQueryFilter) {         // block out_elems / (8 ND) < chunk_len / (8 ND) <= f_mask_stride (the step's guard)
+                if constexpr (Q == kQueryFilter) {         // block out_elems / (8 ND) < chunk_len / (8 ND) <= mask_stride (the step's guard)
                     uint32_t m = 0;
 #pragma unroll
                     for (int k = 0; k < ND; k++) {
@@ -490,52 +490,34 @@ __global__ void __launch_bounds__(decode_uni_threads(W, ND)) decode_uni_kernel(D
                 uint8_t* d = obase + (uint64_t)out_elems * ESZ;
                 for (uint32_t j = 0; j < remaining * ESZ; j++) d[j] = src[j];
             }
-            if constexpr (Q == kQueryFilter) {           // the tail's whole rows (a partial last row is not a row), then zeros up to the slot's end
-                const uint32_t nfull = remaining / ND, done = out_elems / (8u * ND);
-                uint32_t byte = 0;
-                for (uint32_t r = 0; r < nfull; r++) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int k = 0; k < ND; k++) {
-                        const uint32_t e = r * ND + k;
-                        const uint32_t x = ESZ == 1 ? (uint32_t)src[e] : ((uint32_t)src[2 * e] | ((uint32_t)src[2 * e + 1] << 8));
-                        v |= filter_hit<W>(fc[k], x) ^ (finv & 1u);
-                    }
-                    byte |= ((v ^ finv) & 1u) << (r & 7u);
-                    if ((r & 7u) == 7u || r + 1 == nfull) {
-                        if (fmb) fmb[done + (r >> 3)] = (uint8_t)byte;
-                        fcnt += (uint32_t)__popc(byte);
-                        byte = 0;
-                    }
-                }
-                if (fmb) for (uint32_t j = done + ((nfull + 7u) >> 3); j < a.f_mask_stride; j++) fmb[j] = 0;
-            } else if constexpr (Q == kQueryWindow) {    // element e of the tail is column e % ND; a row starts with column 0, a window edge can fall inside
+            if constexpr (Q == kQueryWindow) {
+                // window_tail (decode_ops.h), kept local: with the shared tail the 8-bit univariate batch at 8-row windows measured above
+                // the slowest round of the code before (profiles/decode_ops_ab.txt).  Element e of the tail is column e % ND; a row starts
+                // with column 0, a window edge can fall inside
                 uint32_t col = 0;
                 for (uint32_t e = 0; e < remaining; e++) {
                     if (col == 0) {
                         if (wleft == 0) win_flush_all();
                         wleft--;
                     }
-                    const uint32_t x = ESZ == 1 ? (uint32_t)src[e] : ((uint32_t)src[2 * e] | ((uint32_t)src[2 * e + 1] << 8));
+                    const uint32_t x = tail_elem<W>(src, e);
 #pragma unroll
                     for (int k = 0; k < ND; k++)
                         if (col == (uint32_t)k) { qmin[k] = x < qmin[k] ? x : qmin[k]; qmax[k] = x > qmax[k] ? x : qmax[k]; qsum[k] += x; }
                     col = col + 1 == (uint32_t)ND ? 0u : col + 1;
                 }
-                while (wi < a.win_count) win_flush_all();  // the partial window, then the identities of the slot's last ones
-            } else if constexpr (Q != 0) {               // the verbatim tail continues the row-major order: element e is column e % ND
-                for (uint32_t e = 0; e < remaining; e++) {
-                    const uint32_t x = ESZ == 1 ? (uint32_t)src[e] : ((uint32_t)src[2 * e] | ((uint32_t)src[2 * e + 1] << 8));
+                while (wi < a.win.count) win_flush_all();  // the partial window, then the identities of the slot's last ones
+            } else if constexpr (Q != 0) {
+                // the other row operations' tails (decode_ops.h): this lane is the whole group and holds every column
+                int colk[ND];
+                bool genk[ND];
 #pragma unroll
-                    for (int k = 0; k < ND; k++)
-                        if (e % ND == (uint32_t)k) { qmax[k] = x > qmax[k] ? x : qmax[k]; qsum[k] += x; }
-                }
-#pragma unroll
-                for (int k = 0; k < ND; k++)
-                    if (a.qres) a.qres[chunk * (uint64_t)ND + (uint64_t)k] = a.qop == 1 ? (uint64_t)qmax[k] : qsum[k];
+                for (int k = 0; k < ND; k++) { colk[k] = k; genk[k] = true; }
+                if constexpr (Q == kQueryFilter) filter_tail<W, ND>(a, chunk, src, remaining, (uint32_t)ND, out_elems / (8u * ND), 0, 1, fc, colk, genk, fcnt);
+                else reduce_tail<W, ND>(a, chunk, src, remaining, (uint32_t)ND, colk, genk, qmax, qsum);
             }
         }
-        if constexpr (Q == kQueryFilter) { if (a.f_counts) a.f_counts[chunk] = fcnt; }
+        if constexpr (Q == kQueryFilter) { if (a.filter.counts) a.filter.counts[chunk] = fcnt; }
         if (a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
     }
 }

@@ -1,12 +1,15 @@
-// decode_w16.hip -- instantiations of the batched decoder for 16-bit elements.
+// decode_w16.hip -- instantiations of the batched decoder for 16-bit elements: the plain decode and the reduce / window queries
+// (launch.h: the launchers of api.hip forward here by width).
 #include "launch.h"
 namespace sprintz {
-hipError_t launch_decode_w16(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_generic_w16(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
+    if (w != 16) return hipErrorInvalidValue;
     SPRINTZ_DISPATCH(decode_kernel, 16)
 }
-hipError_t launch_decode_fast_w16(bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_fast_w16(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
+    if (w != 16) return hipErrorInvalidValue;
     if (ds == 80) {                                        // 65 .. 80 columns on 64 x 2 with the LDS carve of 80 columns: 12 waves a CU instead of 8
         if (dp != 64 || cpl != 2 || q != kQueryOff || a.col_stride || exact || a.D <= 64 || a.D > 80) return hipErrorInvalidValue;
         return fire ? launch_one(decode_fast_kernel<16, true, 64, 2, false, kQueryOff, false, 80>, grid, shmem, st, a)
@@ -23,8 +26,9 @@ hipError_t launch_decode_fast_w16(bool fire, int dp, int cpl, bool exact, int q,
         else hipLaunchKernelGGL((decode_uni_kernel<16, false, NDV, QV>), dim3(g), dim3(tpb), 0, st, a);       \
         return hipGetLastError();                                                                           \
     }
-hipError_t launch_decode_uni_w16(bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
 {
+    if (w != 16) return hipErrorInvalidValue;
     SPRINTZ_UNI_CASE(1, kQueryOff)
     SPRINTZ_UNI_CASE(1, kQueryMaterialize)
     SPRINTZ_UNI_CASE(1, kQueryReduceOnly)

@@ -1,12 +1,15 @@
-// decode_w8.hip -- instantiations of the batched decoder for 8-bit elements.
+// decode_w8.hip -- instantiations of the batched decoder for 8-bit elements: the plain decode and the reduce / window queries
+// (launch.h: the launchers of api.hip forward here by width).
 #include "launch.h"
 namespace sprintz {
-hipError_t launch_decode_w8(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_generic_w8(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
+    if (w != 8) return hipErrorInvalidValue;
     SPRINTZ_DISPATCH(decode_kernel, 8)
 }
-hipError_t launch_decode_fast_w8(bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_fast_w8(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
+    if (w != 8) return hipErrorInvalidValue;
     if (dp == 32 && cpl == 3) {                            // the split mapping: 8 bits, 65 .. 80 columns, plain row-major decode only
         if (ds != 80 || q != kQueryOff || a.col_stride || exact || a.D <= 64 || a.D > 80) return hipErrorInvalidValue;
         return fire ? launch_one(decode_fast_kernel<8, true, 32, 3, false, kQueryOff, false, 80>, grid, shmem, st, a)
@@ -23,8 +26,9 @@ hipError_t launch_decode_fast_w8(bool fire, int dp, int cpl, bool exact, int q, 
         else hipLaunchKernelGGL((decode_uni_kernel<8, false, NDV, QV>), dim3(g), dim3(tpb), 0, st, a);       \
         return hipGetLastError();                                                                           \
     }
-hipError_t launch_decode_uni_w8(bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
+hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
 {
+    if (w != 8) return hipErrorInvalidValue;
     SPRINTZ_UNI_CASE(1, kQueryOff)
     SPRINTZ_UNI_CASE(1, kQueryMaterialize)
     SPRINTZ_UNI_CASE(1, kQueryReduceOnly)

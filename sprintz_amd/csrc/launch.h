@@ -18,24 +18,33 @@
 
 namespace sprintz {
 
-hipError_t launch_decode_w8(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_w16(bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// gather rows (Q = kQueryGather, decode_gather.hip): the generic kernel, both layouts; decode_fast for rows of whole 16-byte pieces
-hipError_t launch_decode_gather(int w, bool fire, bool lowdim, int cpl, unsigned grid, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_fast_gather(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// filter rows (Q = kQueryFilter, decode_filter.hip): all three decoder families, both widths
-hipError_t launch_decode_filter(int w, bool fire, bool lowdim, int cpl, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_fast_filter(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_uni_filter(int w, bool fire, int nd, hipStream_t st, const DecodeArgs& a);
+// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQuerySelect).  Each forwards to the
+// translation unit that holds the instantiation -- decode_w8.hip / decode_w16.hip for the plain decode and the reduce / window
+// queries, decode_gather.hip, decode_filter.hip, decode_select.hip for those modes -- so that every unit keeps its compile flags.
+// generic lane mapping, both layouts, up to 512 columns (decode_kernel.h)
+hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+// fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h); gather and select for rows of whole 16-byte pieces
+// (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
+hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather and select
+hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
+// internal -- the units' own entry points, reached through the three launchers above alone (api.hip).  A unit refuses a width or
+// a mode it does not hold; the decode_uni units size their grid themselves (decode_uni_threads) and ignore `grid`
+hipError_t decode_generic_w8(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_generic_w16(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_generic_gather(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_generic_filter(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_generic_select(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_fast_w8(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_fast_w16(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_fast_gather(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_fast_filter(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_uni_filter(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // filter_row_ids: a mask of filter_rows into ascending batch row numbers, a lane group per chunk (decode_filter.hip)
 hipError_t launch_filter_row_ids(const uint8_t* mask, const uint64_t* bases, uint64_t nchunks, uint32_t rows, uint64_t* ids, uint64_t capacity, hipStream_t st);
-// select rows (Q = kQuerySelect, decode_select.hip): the generic kernel, both layouts; decode_fast for rows of whole 16-byte pieces
-hipError_t launch_decode_select(int w, bool fire, bool lowdim, int cpl, unsigned grid, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h)
-// (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
-hipError_t launch_decode_fast_w8(bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_fast_w16(bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 // small batches: one workgroup per chunk, both layouts, 1 .. 64 columns (decode_lat.h); bound_bytes = the longest stream a chunk can have
 hipError_t launch_decode_lat(int w, bool fire, int dp, bool lowdim, unsigned grid, uint32_t bound_bytes, hipStream_t st, const DecodeArgs& a);
 hipError_t launch_encode_lat(int w, bool fire, int dp, bool lowdim, unsigned grid, uint32_t bound_bytes, hipStream_t st, const EncodeArgs& a);   // encode_lat.h
@@ -45,9 +54,6 @@ hipError_t launch_encode_any(int w, bool fire, unsigned grid, size_t shmem, hipS
 // streams of 2 048 .. 65 535 columns: the same scheme in column tiles, per-column state behind the rows / in `counters` (nchunks x ndims int32; FIRE only)
 hipError_t launch_decode_big(int w, bool fire, unsigned grid, hipStream_t st, const DecodeArgs& a, int32_t* counters);
 hipError_t launch_encode_big(int w, bool fire, unsigned grid, hipStream_t st, const EncodeArgs& a, int32_t* counters);
-// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h)
-hipError_t launch_decode_uni_w8(bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
-hipError_t launch_decode_uni_w16(bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // streams of 65 .. 128 columns, two columns per lane (encode_wide.h)
 hipError_t launch_encode_wide_w8(bool fire, bool exact, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
 hipError_t launch_encode_wide_w16(bool fire, bool exact, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
@@ -137,7 +143,7 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
         default: return hipErrorInvalidValue;                                                         \
     }
 
-// q: kQueryOff / kQueryMaterialize / kQueryReduceOnly / kQueryWindow (decode_kernel.h)
+// q: kQueryOff / kQueryMaterialize / kQueryReduceOnly / kQueryWindow (geom.h)
 #define SPRINTZ_DISPATCH(KERNEL, W)                                                                   \
     if (q == kQueryOff) { SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryOff) }                                  \
     if (q == kQueryMaterialize) { SPRINTZ_DISPATCH_Q(KERNEL, W, kQueryMaterialize) }                  \
