@@ -50,7 +50,7 @@ extern "C" {
  *   6  round 5: huf0_decompress_batch_hint, SPRINTZ_OPT_HUF0_SYNC_CHUNKS, SPRINTZ_MI355X_MAX_NDIMS 65535
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
- *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows */
+ *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -154,7 +154,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -564,6 +564,41 @@ int sprintz_mi355x_gather_rows(int codec, int elem_bytes, const void* d_comp, co
 int sprintz_mi355x_select_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, const uint64_t* d_bases,
                                uint64_t capacity, uint32_t flags, void* d_out, uint64_t* d_ids, int64_t* d_rets, void* hip_stream);
+/* Aggregate rows: per-window min / max / sum / count of the rows a mask names -- "SELECT count(*), min(x), max(x), sum(x) WHERE ...
+ * [GROUP BY time window]" with filter_rows in front, fused into the decode: only the results leave the chip.
+ *
+ * The batch is given as to sprintz_mi355x_select_rows (flags: SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else; chunk_len % ndims == 0
+ * is required).  With D = ndims, R = chunk_len / D, MB = ceil(R / 8), W = window_rows (a multiple of 8, at least 8) and
+ * nwin = ceil(R / W): windows are relative to the chunk, exactly as in sprintz_mi355x_query_windows; W >= R gives one aggregate a chunk.
+ *   d_mask : [nchunks][MB] bytes in the layout filter_rows writes -- from filter_rows on this batch, from several masks combined, or
+ *            from ANOTHER batch on the same time base; no predicate is evaluated here.  A bit is ignored if its row does not exist:
+ *            rows >= R in the last byte, rows past what the chunk's stream holds, and a partial last row is not a row.
+ * For chunk c, window w and column d the call writes, at index (c*nwin + w)*D + d, over the selected existing rows of that window,
+ *   d_min  : the unsigned minimum, element type (uint8 / uint16)    (ops & SPRINTZ_AGG_MIN)
+ *   d_max  : the unsigned maximum, element type                     (ops & SPRINTZ_AGG_MAX)
+ *   d_sum  : the sum, uint64                                        (ops & SPRINTZ_AGG_SUM)
+ * and at index c*nwin + w
+ *   d_count: the number of those rows, uint32                       (ops & SPRINTZ_AGG_COUNT)
+ * on the values decompress_batch writes under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK included).  A window with no selected
+ * row holds the identities: min 0xFF / 0xFFFF, max 0, sum 0, count 0.  Every entry of every selected output is written; an output not
+ * selected may be NULL.  One writer an entry, no atomics: the output is deterministic.
+ * d_rets (optional) as in query_windows: elements decoded, or < 0 for a damaged chunk, whose own entries are then unspecified --
+ * nothing is written outside them, and every other chunk is exact.
+ * The call does not read the mask on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST
+ * (csrc/decode_fast.h: the shapes the windowed query takes there) or DEC_GENERIC (csrc/decode_kernel.h: everything else, the
+ * low-dimension layouts included -- csrc/decode_uni.h is not taught the mode).
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, a window_rows that
+ * is not a multiple of 8 >= 8, ops outside 1..15, a selected output that is NULL, a NULL d_comp / d_offsets / d_mask, d_min / d_max
+ * not aligned to the element size, d_count not aligned to 4 bytes, d_sum / d_rets not aligned to 8 bytes, an unknown flag;
+ * SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0 returns 0 and launches nothing. */
+#define SPRINTZ_AGG_MIN 1u
+#define SPRINTZ_AGG_MAX 2u
+#define SPRINTZ_AGG_SUM 4u
+#define SPRINTZ_AGG_COUNT 8u
+int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                  uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t window_rows, uint32_t ops,
+                                  uint32_t flags, void* d_min, void* d_max, uint64_t* d_sum, uint32_t* d_count, int64_t* d_rets,
+                                  void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

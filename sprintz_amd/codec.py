@@ -577,6 +577,106 @@ class ChunkedCodec:
         f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=general_layout, check=True)
         return self.select_rows(batch, f["mask"], counts=f["counts"], ids=ids, general_layout=general_layout)
 
+    def aggregate_rows(self, batch, mask, window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False, per_chunk=False,
+                       check=True):
+        """Per-window min / max / sum / count of the rows a mask names, fused into the decode (one launch; only the results leave the chip).
+
+        mask: uint8 [nchunks, MB] in filter_rows' layout (MB = ceil(R / 8), R = chunk_len / ndims: chunk_len must be a multiple of
+        ndims) -- from filter_rows on this batch, several masks combined, or another batch on the same time base; bits of rows that do
+        not exist are ignored.  window_rows=None: one window a chunk.
+        per_chunk=True: the kernel's chunk-relative windows, {op: [nchunks, nwin, ndims]} and "count": [nchunks, nwin], nwin =
+        ceil(R / window_rows), window_rows a multiple of 8.  Default: windows over the batch's rows, as query_windows folds them --
+        {op: [nwindows, ndims]}, "count": [nwindows] -- which needs R to be a multiple or a divisor of window_rows.
+        ops: any of "min", "max" (codec dtype), "sum", "count" (int64) and "mean" (float64: sum / count, NaN where count is 0).  A window
+        with no selected row holds the identities (min all ones, max 0, sum 0, count 0).  check=True raises SprintzError naming the
+        first damaged chunk."""
+        torch = self.torch
+        ops = (ops,) if isinstance(ops, str) else tuple(ops)
+        unknown = set(ops) - {"min", "max", "sum", "count", "mean"}
+        if unknown or not ops:
+            raise ValueError(f"ops must be a non-empty subset of min / max / sum / count / mean, not {ops}")
+        D, n = self.ndims, batch.nchunks
+        if self.chunk_len % D:
+            raise ValueError(f"aggregate_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        R = self.chunk_len // D
+        MB = -(-R // 8)
+        r8 = MB * 8
+        if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
+            raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
+        mask = mask.contiguous()
+        W = R if window_rows is None else int(window_rows)
+        if W < 1:
+            raise ValueError("window_rows must be positive")
+        fold = 1
+        if per_chunk:
+            kw = r8 if window_rows is None else W
+        elif W % R == 0:
+            kw, fold = r8, W // R                           # one window a chunk (any multiple of 8 >= R), folded below
+        elif R % W == 0:
+            kw = W
+        else:
+            raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: use per_chunk=True")
+        nwin = -(-R // kw) if kw > 0 else 0
+        want = set(ops) | ({"sum", "count"} if "mean" in ops else set())
+        bits = (_lib.AGG_MIN if "min" in want else 0) | (_lib.AGG_MAX if "max" in want else 0) | (_lib.AGG_SUM if "sum" in want else 0) | \
+               (_lib.AGG_COUNT if "count" in want else 0)
+        res = {}
+        if bits & _lib.AGG_MIN:
+            res["min"] = torch.empty((n, nwin, D), dtype=self.dtype, device=self.device)
+        if bits & _lib.AGG_MAX:
+            res["max"] = torch.empty((n, nwin, D), dtype=self.dtype, device=self.device)
+        if bits & _lib.AGG_SUM:
+            res["sum"] = torch.empty((n, nwin, D), dtype=torch.int64, device=self.device)
+        cnt32 = torch.empty((n, nwin), dtype=torch.int32, device=self.device) if bits & _lib.AGG_COUNT else None
+        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        with self._on():
+            _lib.check(_lib.aggregate_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                           self.chunk_len, D, mask.data_ptr(), kw, bits,
+                                           _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                           res["min"].data_ptr() if "min" in res else None,
+                                           res["max"].data_ptr() if "max" in res else None,
+                                           res["sum"].data_ptr() if "sum" in res else None,
+                                           cnt32.data_ptr() if cnt32 is not None else None,
+                                           rets.data_ptr() if rets is not None else None, self._stream()))
+        if check and n:
+            bad = (rets < 0).nonzero()
+            if bad.numel():
+                c = int(bad[0, 0].item())
+                raise _lib.SprintzError(int(rets[c].item()), f"aggregate_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if cnt32 is not None:
+            res["count"] = cnt32.to(torch.int64)
+        if per_chunk:
+            out = res
+        else:
+            rows = -(-batch.total_len // D)
+            nw = -(-rows // W)
+            if fold == 1:                                   # chunk windows are global windows: chunk c holds rows [c R, (c+1) R)
+                out = {k: (v.reshape(n * nwin) if k == "count" else v.reshape(n * nwin, D))[:nw] for k, v in res.items()}
+            else:                                           # `fold` consecutive chunks a window (int32: torch's uint16 lacks most reductions)
+                pad = nw * fold - n
+                out = {}
+                for k, v in res.items():
+                    if k == "count":
+                        out[k] = torch.cat([v.reshape(n), v.new_zeros(pad)]).reshape(nw, fold).sum(dim=1)
+                    elif k == "sum":
+                        out[k] = torch.cat([v.reshape(n, D), v.new_zeros((pad, D))]).reshape(nw, fold, D).sum(dim=1)
+                    else:
+                        ident = (1 << (8 * self.esz)) - 1 if k == "min" else 0
+                        v32 = torch.cat([v.reshape(n, D).to(torch.int32), torch.full((pad, D), ident, dtype=torch.int32, device=self.device)])
+                        v32 = v32.reshape(nw, fold, D)
+                        out[k] = (v32.amin(dim=1) if k == "min" else v32.amax(dim=1)).to(self.dtype)
+        if "mean" in ops:                                   # 0 / 0 is NaN: a window with no selected row has no mean
+            out["mean"] = out["sum"].to(torch.float64) / out["count"].to(torch.float64).unsqueeze(-1)
+        return {k: v for k, v in out.items() if k in ops}
+
+    def aggregate_where(self, batch, lo, hi, mode="all", window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False):
+        """SELECT count(*), min(x), max(x), sum(x) WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and aggregate_rows
+        on its mask -- two decode-speed launches; the batch is never materialised.  -> aggregate_rows' global windows."""
+        if self.chunk_len % self.ndims:
+            raise ValueError(f"aggregate_where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=general_layout, check=True)
+        return self.aggregate_rows(batch, f["mask"], window_rows=window_rows, ops=ops, general_layout=general_layout)
+
     def read_rows(self, batch, lo, hi):
         """batch rows [lo, hi) -> [hi - lo, ndims]: one range of gather_rows, its chunks decoded side by side in the same launch"""
         lo, hi = int(lo), int(hi)

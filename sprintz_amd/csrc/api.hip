@@ -292,12 +292,14 @@ hipError_t launch_size_scan(const uint32_t* d_sizes, uint64_t n, uint32_t align,
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
     const auto unit = q == kQueryGather ? decode_generic_gather : q == kQueryFilter ? decode_generic_filter : q == kQuerySelect ? decode_generic_select
+                    : q == kQueryAggregate ? decode_generic_aggregate
                     : w == 8 ? decode_generic_w8 : decode_generic_w16;
     return unit(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
     const auto unit = q == kQueryGather ? decode_fast_gather : q == kQueryFilter ? decode_fast_filter : q == kQuerySelect ? decode_fast_select
+                    : q == kQueryAggregate ? decode_fast_aggregate
                     : w == 8 ? decode_fast_w8 : decode_fast_w16;
     return unit(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
@@ -330,14 +332,20 @@ int check_common(int codec, int esz, uint16_t ndims)
     return 0;
 }
 
-// what the row operations (query_windows, gather_rows, filter_rows, select_rows) check alike, behind check_common; the refusals that
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
-                 const char* rle_only)
+                 const char* rle_only, const char* op = nullptr)
 {
-    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return fail(SPRINTZ_E_INVALID, "unknown flag");
-    if (chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "chunk_len must be in 1..2^30");
-    if (!d_comp || !d_offsets) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    // (op != null: the operation's name in front of the shared messages)
+    auto shared = [&](const char* what) {
+        if (!op) return fail(SPRINTZ_E_INVALID, what);
+        const std::string named = std::string(op) + ": " + what;
+        return fail(SPRINTZ_E_INVALID, named.c_str());
+    };
+    if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return shared("unknown flag");
+    if (chunk_len == 0 || chunk_len > (1u << 30)) return shared("chunk_len must be in 1..2^30");
+    if (!d_comp || !d_offsets) return shared("null device pointer");
     if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, many_columns);
     if (rle_only && codec != SPRINTZ_CODEC_DELTA && codec != SPRINTZ_CODEC_XFF) return fail(SPRINTZ_E_UNSUPPORTED, rle_only);
     return 0;
@@ -382,7 +390,7 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQuerySelect (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryAggregate (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -390,6 +398,7 @@ struct QuerySpec {
     GatherArgs gather{};        // kQueryGather
     FilterArgs filter{};        // kQueryFilter
     SelectArgs select{};        // kQuerySelect
+    AggregateArgs agg{};        // kQueryAggregate (with win)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -455,6 +464,7 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.gather = qs.gather;
     a.filter = qs.filter;
     a.select = qs.select;
+    a.agg = qs.agg;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -1691,6 +1701,42 @@ int sprintz_mi355x_select_rows(int codec, int elem_bytes, const void* d_comp, co
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
     qs.select = SelectArgs{d_mask, d_bases, capacity, d_ids, rows, (rows + 7) / 8};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- aggregate rows
+int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                  uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t window_rows, uint32_t ops,
+                                  uint32_t flags, void* d_min, void* d_max, uint64_t* d_sum, uint32_t* d_count, int64_t* d_rets,
+                                  void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "aggregate_rows: more than 512 columns", "aggregate_rows: the RLE codecs (delta, xff) only",
+                           "aggregate_rows"))) return rc;
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "aggregate_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if (window_rows < 8 || window_rows % 8) return fail(SPRINTZ_E_INVALID, "aggregate_rows: window_rows must be a multiple of 8, at least 8");
+    if (ops < 1 || ops > 15) return fail(SPRINTZ_E_INVALID, "aggregate_rows: ops must be a non-empty OR of SPRINTZ_AGG_MIN / _MAX / _SUM / _COUNT");
+    if (!d_mask) return fail(SPRINTZ_E_INVALID, "aggregate_rows: null device pointer");
+    if (((ops & SPRINTZ_AGG_MIN) && !d_min) || ((ops & SPRINTZ_AGG_MAX) && !d_max) || ((ops & SPRINTZ_AGG_SUM) && !d_sum) || ((ops & SPRINTZ_AGG_COUNT) && !d_count))
+        return fail(SPRINTZ_E_INVALID, "aggregate_rows: a selected op without its output buffer");
+    if (((ops & SPRINTZ_AGG_MIN) && (uintptr_t)d_min % (uintptr_t)elem_bytes) || ((ops & SPRINTZ_AGG_MAX) && (uintptr_t)d_max % (uintptr_t)elem_bytes) ||
+        ((ops & SPRINTZ_AGG_SUM) && (uintptr_t)d_sum % 8) || ((ops & SPRINTZ_AGG_COUNT) && (uintptr_t)d_count % 4) || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "aggregate_rows: min / max must be aligned to the element size, count to 4 bytes, sum and d_rets to 8");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    const uint32_t rows = chunk_len / ndims;
+    QuerySpec qs;
+    qs.q = kQueryAggregate;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.win.rows = window_rows;
+    qs.win.count = (rows + window_rows - 1) / window_rows;
+    qs.win.ops = ops & 7u;
+    qs.win.min = (ops & SPRINTZ_AGG_MIN) ? d_min : nullptr;
+    qs.win.max = (ops & SPRINTZ_AGG_MAX) ? d_max : nullptr;
+    qs.win.sum = (ops & SPRINTZ_AGG_SUM) ? d_sum : nullptr;
+    qs.agg = AggregateArgs{d_mask, (ops & SPRINTZ_AGG_COUNT) ? d_count : nullptr, (rows + 7) / 8};
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }
 

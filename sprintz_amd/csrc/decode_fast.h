@@ -131,6 +131,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // only rows of whole 16-byte pieces.
     constexpr bool SELECT = Q == kQuerySelect;
     static_assert(!SELECT || (!CM && !SPLIT && DS == 0), "select: row-major destination, plain mappings");
+    // AGGREGATE (sprintz_mi355x_aggregate_rows): the windowed query over the rows the caller's mask names.  Nothing is stored but the
+    // windows' entries, so any shape the windowed query takes is taken; the mask bytes come through select's read-ahead window.
+    constexpr bool AGG = Q == kQueryAggregate;
+    static_assert(!AGG || (!CM && !SPLIT && DS == 0), "aggregate: plain mappings");
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -341,6 +345,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // fl the lane's columns (inverted domain: decode_ops.h, FilterCol); the group ORs its lanes once per block (f_block)
     FilterCol fc[CPL];
     uint32_t finv = 0, fcm = 0, fl = 0, fb = 0, fcnt = 0;  // fb: blocks of this chunk done = the mask byte the next block writes
+    // select / aggregate rows: the mask byte of the block being decoded (fb counts the chunk's blocks, as for the filter); aggregate: the
+    // rows of the column being decoded and the selected rows of the window so far
+    uint32_t sm = 0;
+    uint32_t arow[8];
+    uint32_t acnt = 0;
     uint8_t* fmb = nullptr;
     if constexpr (Q == kQueryFilter) {
 #pragma unroll
@@ -350,6 +359,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
+        } else if constexpr (AGG) {                        // the column's 8 rows wait for q_block: one test of the mask byte a column
+            arow[i] = pv[k];
         } else if constexpr (Q != 0) {
             if constexpr (W == 16) {
                 asm("v_max_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
@@ -374,6 +385,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (Q == kQueryFilter) {                 // a lane column past the last one contributes the identity
             fl |= col_ok[k] ? (fcm ^ finv) & 0xffu : 0u;
             fcm = 0;
+        } else if constexpr (AGG) {                        // a block whose mask byte is 0 only moves the predictor on
+            if (sm != 0) {
+                uint32_t bs = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) aggregate_row<W>(arow[i], aggregate_sel<W>(sm, i), qmin[k], qmax[k], bs);
+                qsum[k] += bs;
+            }
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
     // after every block of 8 rows: the group's lanes combine, one lane stores the block's byte (fb < chunk_len / blk_elems <=
@@ -391,11 +409,18 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
         for (int k = 0; k < CPL; k++)
             if (col_ok[k]) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
+        if constexpr (AGG) aggregate_count_flush(a, wbase + wi, acnt, lane_d);
         wi++;
         wleft = a.win.rows;
     };
     auto q_window = [&]() {                                // after every block of 8 rows
         if constexpr (Q == kQueryWindow) {
+            wleft -= 8;
+            if (wleft == 0) win_flush_all();
+        }
+        if constexpr (AGG) {                               // the block's selected rows are counted, then as above
+            acnt += (uint32_t)__popc(sm);
+            fb++;
             wleft -= 8;
             if (wleft == 0) win_flush_all();
         }
@@ -415,23 +440,24 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     for (int q = 0; q < PIECES; q++) pcol[q] = SELECT ? lane16 + (uint32_t)q * ROW16 - prow[q] * row_stride : 0u;
     const uint8_t* smb = nullptr;
     uint64_t sbase = 0, srow0 = 0;
-    uint32_t srank = 0, sm = 0;
+    uint32_t srank = 0;
     // The mask bytes are read ahead of the blocks, 4 DP of them at a time: lane l of the group keeps dword l of the window that starts at
     // byte mwin0 (a multiple of 4) of the chunk's mask, and a block's byte comes out of its lane's dword with one cross-lane read -- no
     // load from memory sits between a block's header and its stores.  (A chunk's mask starts at any address, and its last dword may be
     // short: those bytes are read one by one.)
     uint32_t mwin = 0, mwin0 = 0x80000000u;
+    auto sel_stride = [&]() -> uint32_t { if constexpr (AGG) return a.agg.mask_stride; else return a.select.mask_stride; };
     auto sel_byte = [&](uint32_t b) -> uint32_t {
         if (b - mwin0 >= 4u * DP) {
             mwin0 = b & ~3u;
             const uint32_t o = mwin0 + 4u * (uint32_t)lane_d;
             mwin = 0;
-            if (o + 4u <= a.select.mask_stride) {
+            if (o + 4u <= sel_stride()) {
                 mwin = *(const u32_unaligned*)(smb + o);
             } else {
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; j++)
-                    if (o + j < a.select.mask_stride) mwin |= (uint32_t)smb[o + j] << (8u * j);
+                    if (o + j < sel_stride()) mwin |= (uint32_t)smb[o + j] << (8u * j);
             }
         }
         const uint32_t i = b - mwin0;
@@ -636,6 +662,35 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             return;
         }
+        if constexpr (AGG && !FIRE) {
+            // a delta run repeats the previous row 8 len times: per window it touches, the selected rows among them are counted -- the set
+            // bits of the run's mask bytes in that window, spread over the group's lanes -- min / max take the row once if there is one,
+            // and the sum takes it times their number.  (The bytes lie inside the chunk's: the run fits the chunk slot.)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            uint32_t blocks = len;
+            while (blocks > 0) {
+                const uint32_t nb = blocks < (wleft >> 3) ? blocks : (wleft >> 3);
+                uint32_t c = 0;
+                for (uint32_t j = (uint32_t)lane_d; j < nb; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
+                c = group_sum(c, DP);
+                if (c != 0) {
+#pragma unroll
+                    for (int k = 0; k < CPL; k++) {
+                        const uint32_t x = pv[k] & MASK;
+                        qmin[k] = x < qmin[k] ? x : qmin[k];
+                        qmax[k] = x > qmax[k] ? x : qmax[k];
+                        qsum[k] += (uint64_t)x * c;
+                    }
+                    acnt += c;
+                }
+                blocks -= nb;
+                fb += nb;
+                wleft -= 8u * nb;
+                if (wleft == 0) win_flush_all();
+            }
+            return;
+        }
         if constexpr (SELECT && !FIRE) {
             // a delta run repeats the previous row and changes no state: a run none of whose rows the mask wants is stepped over
             // (its mask bytes lie inside the chunk's: the run fits the chunk slot)
@@ -666,6 +721,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 sm = sel_byte(fb);
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
             }
+            if constexpr (AGG) sm = sel_byte(fb);          // (a FIRE run is replayed for its state, block by block, as the window mode does)
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -786,7 +842,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto packed_block = [&](const int (&e)[CPL][8], int slot) {   // forecast recurrence (:993-1150)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
-        if constexpr (SELECT) sm = sel_byte(fb);           // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
+        if constexpr (SELECT || AGG) sm = sel_byte(fb);    // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -898,7 +954,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         ahead -= hbytes;
 #pragma unroll
         for (int k = 0; k < CPL; k++) { pv[k] = 0; pd[k] = 0; ctr[k] = 0; qmax[k] = 0; qsum[k] = 0; }
-        if constexpr (Q == kQueryWindow) {                 // windows are relative to the chunk
+        if constexpr (Q == kQueryWindow || AGG) {          // windows are relative to the chunk
 #pragma unroll
             for (int k = 0; k < CPL; k++) qmin[k] = MASK;
             wi = 0;
@@ -908,6 +964,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (Q == kQueryFilter) {
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
             fmb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
+        }
+        if constexpr (AGG) {
+            fb = 0; sm = 0; acnt = 0;
+            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
+            smb = a.agg.mask + chunk * (uint64_t)a.agg.mask_stride;
         }
         if constexpr (SELECT) {
             fb = 0; srank = 0; sm = 0;
@@ -1086,6 +1147,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 for (; w < a.win.count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
             }
         }
+    } else if constexpr (AGG) {
+        // fb blocks = 8 fb rows lie in front of the tail
+        if (!corrupt)
+            aggregate_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
+                                   [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) {
             const uint8_t* t = a.comp + gabs + rp;

@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     uint32_t qmin[CPL];
     uint32_t wi = 0, wleft = 0;
     uint64_t wbase = 0;
-    if constexpr (Q == kQueryWindow) {
+    if constexpr (Q == kQueryWindow || Q == kQueryAggregate) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) qmin[k] = MASK;
         wleft = a.win.rows;
@@ -139,6 +139,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         smb = a.select.mask + chunk * (uint64_t)a.select.mask_stride;
         sbase = a.select.bases[chunk];
     }
+    // aggregate rows: the chunk's mask bytes, the mask byte of the block being decoded and the selected rows of the window so far
+    const uint8_t* amb = nullptr;
+    uint32_t am = 0, acnt = 0;
+    if constexpr (Q == kQueryAggregate) amb = a.agg.mask + chunk * (uint64_t)a.agg.mask_stride;
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -238,6 +242,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         // ---- zigzag^-1 + forecast recurrence, lane-local down each column (:993-1150)
         uint32_t v[8][CPL];
         uint32_t fl = 0;                         // filter: this lane's columns' rows, inverted domain
+        // (block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride: checked above; all 8 rows of a block exist)
+        if constexpr (Q == kQueryAggregate) am = amb[out_elems / blk_elems];
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -265,6 +271,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 #pragma unroll
                 for (int i = 0; i < 8; i++) cm |= filter_hit<W>(fc[k], v[i][k]) << i;
                 fl |= genk[k] ? (cm ^ finv) & 0xffu : 0u;
+            } else if constexpr (Q == kQueryAggregate) {
+                if (am) {                        // (a block none of whose rows the mask names only moves the predictor on)
+                    uint32_t bs = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) aggregate_row<W>(v[i][k], aggregate_sel<W>(am, i), qmin[k], qmax[k], bs);
+                    qsum[k] += bs;
+                }
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
 #pragma unroll
@@ -276,7 +289,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 qsum[k] += bs;
             }
         }
-        if constexpr (Q == kQueryWindow) {       // the block's 8 rows lie in one window: flush it when they complete it
+        if constexpr (Q == kQueryWindow || Q == kQueryAggregate) {       // the block's 8 rows lie in one window: flush it when they complete it
+            if constexpr (Q == kQueryAggregate) acnt += (uint32_t)__popc(am);
             wleft -= 8;
             if (wleft == 0) {
 #pragma unroll
@@ -284,6 +298,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     const int col = lane_d * CPL + k;
                     if (col < D) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
                 }
+                if constexpr (Q == kQueryAggregate) aggregate_count_flush(a, wbase + wi, acnt, lane_d);
                 wi++;
                 wleft = a.win.rows;
             }
@@ -403,6 +418,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
     } else if constexpr (Q == kQueryWindow) {
         if (!corrupt) window_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum);
+    } else if constexpr (Q == kQueryAggregate) {
+        if (!corrupt) aggregate_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
+                                             [&](uint32_t b) { return (uint32_t)amb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) reduce_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, colk, genk, qmax, qsum);      // (out_elems is a multiple of 8*D)
     }

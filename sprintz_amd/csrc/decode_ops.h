@@ -1,5 +1,5 @@
-// decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter and select
-// rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
+// decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select and
+// aggregate rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
 // its lane's columns (`col`, with `genuine` false for a lane column past the last one), its place in the group (`lane_d` of `DP`
 // lanes) and the mode's running state; decode_uni.h is the lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane
 // mapping -- how a block's rows reach the accumulators, the staging and the stores -- stays in that kernel.
@@ -49,6 +49,14 @@ struct SelectArgs {
     uint32_t rpc;               // rows of a chunk slot, chunk_len / D
     uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rpc / 8)
 };
+// aggregate rows (Q == kQueryAggregate; sprintz_mi355x_aggregate_rows): the windowed query over the rows whose bits are set in chunk c's
+// mask bytes mask[c * mask_stride ...] (filter_rows' layout) alone.  The windows, the selected ops and the min / max / sum outputs are
+// WindowArgs' (`win`); the number of selected rows of chunk c's window w lands in count[c * win.count + w]
+struct AggregateArgs {
+    const uint8_t* mask;        // [nchunks][mask_stride]
+    uint32_t* count;            // optional (SPRINTZ_AGG_COUNT)
+    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
+};
 
 struct DecodeArgs {
     const uint8_t* comp;        // compressed bytes
@@ -88,6 +96,7 @@ struct DecodeArgs {
     GatherArgs gather;
     FilterArgs filter;
     SelectArgs select;
+    AggregateArgs agg;
 };
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
@@ -153,6 +162,72 @@ __device__ __forceinline__ void window_tail(const DecodeArgs& a, const uint8_t* 
         }
         for (; w < a.win.count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
     }
+}
+
+// ---- aggregate rows: the windowed query's accumulators take a row only where its mask bit is set.  For a selected row `am` is all
+// ones and `om` is 0, for any other row the other way round: x & am is 0 in front of max and sum, x | om is all ones in front of
+// min -- the identities.  x may carry garbage above bit W: max and sum take the element through the AND with Elem<W>::MASK folded into
+// am, the minimum selects it with SDWA as the windowed query does.
+struct AggregateSel { uint32_t am, om; };
+template <int W> __device__ __forceinline__ AggregateSel aggregate_sel(uint32_t m, int row)
+{
+    const bool on = (m >> row) & 1u;
+    return AggregateSel{on ? Elem<W>::MASK : 0u, on ? 0u : 0xffffffffu};
+}
+template <int W>
+__device__ __forceinline__ void aggregate_row(uint32_t x, const AggregateSel& s, uint32_t& qmin, uint32_t& qmax, uint32_t& qbs)
+{
+    const uint32_t t = x & s.am;
+    const uint32_t u = x | s.om;
+    qmax = t > qmax ? t : qmax;
+    qbs += t;
+    if constexpr (W == 16)
+        asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(qmin) : "v"(qmin), "v"(u));
+    else
+        asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(qmin) : "v"(qmin), "v"(u));
+}
+// one window's count leaves with the window's other entries (one lane of the group: one writer an entry), and starts over
+__device__ __forceinline__ void aggregate_count_flush(const DecodeArgs& a, uint64_t widx, uint32_t& acnt, int lane_d)
+{
+    if (a.agg.count && lane_d == 0) a.agg.count[widx] = acnt;
+    acnt = 0;
+}
+// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
+// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  Window `wi` of the chunk (the first of
+// them at entry `wbase`) still takes `wleft` rows; a window edge can fall inside the tail.  Then the partial window leaves, and the
+// identities of the slot's windows past the data.  mask_at(b) is the chunk's mask byte b.
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void aggregate_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0, const int (&col)[CPL],
+                                               const bool (&genuine)[CPL], uint64_t wbase, uint32_t wi, uint32_t wleft, uint32_t (&qmin)[CPL],
+                                               uint32_t (&qmax)[CPL], uint64_t (&qsum)[CPL], uint32_t acnt, int lane_d, F mask_at)
+{
+    const uint32_t nfull = remaining / D;
+    uint32_t w = wi, left = wleft;
+    auto flush = [&]() {
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
+        aggregate_count_flush(a, wbase + w, acnt, lane_d);
+        w++;
+        left = a.win.rows;
+    };
+    uint32_t m = 0;
+    for (uint32_t r = 0; r < nfull; r++) {
+        if (left == 0) flush();
+        left--;
+        if ((r & 7u) == 0) m = mask_at((row0 + r) >> 3);
+        if (!((m >> (r & 7u)) & 1u)) continue;
+        acnt++;
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!genuine[k]) continue;
+            const uint32_t x = tail_elem<W>(t, r * D + (uint32_t)col[k]);
+            qmin[k] = x < qmin[k] ? x : qmin[k];
+            qmax[k] = x > qmax[k] ? x : qmax[k];
+            qsum[k] += x;
+        }
+    }
+    while (w < a.win.count) flush();
 }
 
 // ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the

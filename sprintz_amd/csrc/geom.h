@@ -25,10 +25,12 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // to `out` -- QueryParams::materialize == false); 3 = per-window min / max / sum, reduce only;
 // 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1;
 // 5 = filter: one bit per row -- does the row satisfy the per-column bounds? -- and the chunk's count of them, reduce only;
-// 6 = select: a chunk is decoded once and only the rows whose bit is set in the caller's mask are stored, packed densely behind the chunk's base
-constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6;
+// 6 = select: a chunk is decoded once and only the rows whose bit is set in the caller's mask are stored, packed densely behind the chunk's base;
+// 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only
+constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
+              kQueryAggregate = 7;
 // the modes that never store a decoded sample
-constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter; }
+constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate; }
 
 // sprintz_mi355x_compress_bound: the longest stream a chunk of chunk_len elements can have, a multiple of SPRINTZ_BOUND_ALIGN
 inline size_t compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)
