@@ -55,9 +55,12 @@ def _drive(w, lowdim, dirs, seed, nblocks, runs, transform):
     cbits = 16 if w == 8 else 32
     push = np.where(dirs > 0, B, -(B + 1))
     odd_col = (np.arange(nd) & 1) == 1
-    in_run = np.zeros(nblocks, bool)
-    for a, b in runs:
-        in_run[a:b] = True
+    if isinstance(runs, np.ndarray):                 # per column: [nblocks, ncols] bool (tests/rle_drive.py lays chunks out side by side)
+        in_run = runs.reshape(nblocks, -1)
+    else:
+        in_run = np.zeros((nblocks, 1), bool)
+        for a, b in runs:
+            in_run[a:b] = True
     e_all = rng.integers(1, 4, size=(nblocks, 4, nd))
     prev_val = np.zeros(nd, np.int64)
     prev_delta = np.zeros(nd, np.int64)
@@ -71,12 +74,10 @@ def _drive(w, lowdim, dirs, seed, nblocks, runs, transform):
         grad = np.zeros(nd, np.int64)
         for i in range(8):
             pred = _predict(prev_delta, coef, w, transform, odd_col)
-            if in_run[b]:
-                delta = pred
-            elif i & 1:
-                delta = _wrap(pred + e_all[b, i >> 1], w)
+            if i & 1:
+                delta = np.where(in_run[b], pred, _wrap(pred + e_all[b, i >> 1], w))
             else:
-                delta = push
+                delta = np.where(in_run[b], pred, push)
             err = _wrap(delta - pred, w)
             if i & 1:
                 grad = _wrap(grad + _wrap(np.sign(err) * prev_delta, w), w)
@@ -99,7 +100,9 @@ def _cached(w, lowdim, dirs, seed, nblocks, runs, transform):
 
 def drive(w, lowdim, dirs, seed, nblocks, runs=(), transform=False):
     """dirs: per column +1 (up) / -1 (down) -> (samples [8 * nblocks, ncols], counters [nblocks, ncols], the model's errors like the samples);
-    read-only arrays, cached per process"""
+    read-only arrays, cached per process.  runs may also be a bool array [nblocks, ncols] -- a schedule of each column's own (not cached)"""
+    if isinstance(runs, np.ndarray):
+        return _drive(int(w), bool(lowdim), dirs, int(seed), int(nblocks), np.asarray(runs, bool), bool(transform))
     return _cached(int(w), bool(lowdim), tuple(int(d) for d in dirs), int(seed), int(nblocks), tuple((int(a), int(b)) for a, b in runs), bool(transform))
 
 

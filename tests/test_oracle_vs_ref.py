@@ -119,3 +119,20 @@ def test_steered_online_inputs(orc, reference, kind):
         bits = od.choice_bits(got, x.size)
         assert od.longest_dd_run(bits) >= 8192 and bits[64 * 8192 - 1] == 1 and bits[64 * 8192] == 1
     od.reference_agrees(reference.lib, kind, x, got, ret)
+
+
+@pytest.mark.parametrize("w,ndims", [(8, 1), (8, 5), (8, 8), (16, 2), (16, 8)])
+@pytest.mark.parametrize("codec", ["delta", "xff"])
+def test_run_drive(oracle, reference, codec, w, ndims):
+    """tests/rle_drive.py: every chunk of the five batches that steer the RLE / group state machine (run lengths 1 .. 16 and 126 .. 129
+    closing in both slots, roll-overs, runs at the stream's start and end, the padding slot), at chunk lengths of whole blocks and
+    1 and 8 D - 1 elements more, and the cap -- the compiled reference writes the oracle's bytes (_check: and decodes them)"""
+    import rle_drive as rd
+    for kind in rd.KINDS:
+        for r in (0, 1, 8 * ndims - 1):
+            x, chunk_len, _ = rd.batch(codec, w, ndims, kind, 16, 256, r)
+            for c in range(16):
+                _check(oracle, reference, codec, x[c * chunk_len:(c + 1) * chunk_len], ndims)
+    if (w, ndims) in ((8, 1), (8, 5)):
+        x, chunk_len, _ = rd.cap_chunks(codec, w, ndims, nchunks=1)
+        _check(oracle, reference, codec, x, ndims)
