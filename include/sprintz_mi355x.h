@@ -50,7 +50,8 @@ extern "C" {
  *   6  round 5: huf0_decompress_batch_hint, SPRINTZ_OPT_HUF0_SYNC_CHUNKS, SPRINTZ_MI355X_MAX_NDIMS 65535
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
- *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_* */
+ *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
+ *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -154,7 +155,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -599,6 +600,40 @@ int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp,
                                   uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t window_rows, uint32_t ops,
                                   uint32_t flags, void* d_min, void* d_max, uint64_t* d_sum, uint32_t* d_count, int64_t* d_rets,
                                   void* hip_stream);
+/* Histogram rows: per-column value counts of the rows a mask names -- the distribution behind "median / p95 / p99 of a channel",
+ * "value counts" and "rows per bucket", fused into the decode: only the counts leave the chip.
+ *
+ * The batch is given as to sprintz_mi355x_aggregate_rows (flags: SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else; chunk_len % ndims == 0
+ * is required).  With D = ndims, R = chunk_len / D, MB = ceil(R / 8), W = 8 * elem_bytes:
+ *   d_mask : [nchunks][MB] bytes in the layout filter_rows writes, or NULL: every existing row.  A bit is ignored if its row does not
+ *            exist: rows >= R in the last byte, rows past what the chunk's stream holds, and a partial last row is not a row.
+ *   d_lo   : [D] of element type (uint8 / uint16), or NULL: all zero.
+ *   shift, nbins : value x of column d, in a selected row, has t = (x - d_lo[d]) mod 2^W and is counted in bin t >> shift of its column if
+ *            that is below nbins; otherwise it is not counted.  0 <= shift < W, 1 <= nbins <= 2^(W - shift).
+ *   hist_chunks : H.  Chunks [g*H, (g+1)*H) share histogram g, ngroups = ceil(nchunks / H); 0: the whole batch is one histogram.
+ *   d_hist : [ngroups][D][nbins] uint64: entry (g*D + d)*nbins + b is the number of counted samples of column d in bin b among the
+ *            chunks of group g, on the values decompress_batch writes under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK included).
+ *            The call zeroes it on the stream, then adds: every entry is written and nothing else is.  Integer adds: the result is
+ *            exact and the same on every run although atomics are used.
+ * One call holds at most SPRINTZ_HIST_MAX_COUNTERS = 16384 counters, D * nbins (a workgroup's table in LDS).  A wider request is split
+ * by the caller with d_lo: bins [k*nbins, (k+1)*nbins) of the same shift are one call with d_lo[d] + ((k*nbins) << shift) in place of
+ * d_lo[d] -- values outside a call's bins are dropped, so the calls' results lie side by side.  uint8 x 80 columns at full resolution
+ * is two calls of 128 bins, d_lo = 0 and d_lo = 128.
+ * d_rets (optional) as in aggregate_rows: elements decoded, or < 0 for a damaged chunk, whose own histogram (group) is then
+ * unspecified -- nothing is written outside d_hist, and every other group is exact.
+ * The call does not read the mask on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST
+ * (csrc/decode_fast.h: the shapes the windowed query takes there whose table fits the launch's LDS next to the groups' carves) or
+ * DEC_GENERIC (csrc/decode_kernel.h: everything else, the low-dimension layouts included -- csrc/decode_uni.h is not taught the mode).
+ * A workgroup whose chunks lie in more than one histogram (small H) adds every sample to d_hist directly: correct, and much slower.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, shift >= W, nbins
+ * outside 1..2^(W - shift), a NULL d_comp / d_offsets / d_hist, d_hist / d_rets not aligned to 8 bytes, d_lo not aligned to the element
+ * size, an unknown flag, more than 2^40 entries of d_hist (ngroups * D * nbins); SPRINTZ_E_UNSUPPORTED for more than 512 columns, for the non-RLE codecs and for D * nbins above
+ * SPRINTZ_HIST_MAX_COUNTERS.  nchunks == 0 returns 0 and launches nothing. */
+#define SPRINTZ_HIST_MAX_COUNTERS 16384u
+int sprintz_mi355x_histogram_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                  uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */,
+                                  const void* d_lo /* may be NULL */, uint32_t shift, uint32_t nbins, uint64_t hist_chunks,
+                                  uint32_t flags, uint64_t* d_hist, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -677,6 +677,142 @@ class ChunkedCodec:
         f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=general_layout, check=True)
         return self.aggregate_rows(batch, f["mask"], window_rows=window_rows, ops=ops, general_layout=general_layout)
 
+    def _elem_tensor(self, v, name):
+        """a scalar, a sequence of ndims entries, or a tensor of ndims integers -> a contiguous device tensor [ndims] of the codec's
+        dtype (tensors are taken modulo 2^W)"""
+        torch = self.torch
+        D, W = self.ndims, 8 * self.esz
+        if torch.is_tensor(v):
+            if v.numel() != D:
+                raise ValueError(f"{name} must hold {D} entries")
+            if v.dtype == self.dtype:
+                return v.to(self.device).reshape(-1).contiguous()
+            half = 1 << (W - 1)                             # through the signed type of the same width: torch's uint16 lacks arithmetic
+            s = ((v.to(self.device).reshape(-1).to(torch.int64) + half) % (1 << W)) - half
+            return s.to(torch.int8 if self.esz == 1 else torch.int16).view(self.dtype).contiguous()
+        vals = [v] * D if np.isscalar(v) else list(v)
+        if len(vals) != D:
+            raise ValueError(f"{name} must be a scalar or have {D} entries, not {len(vals)}")
+        if any(not 0 <= int(e) < (1 << W) for e in vals):
+            raise ValueError(f"{name} entries must be in 0..{(1 << W) - 1}")
+        a = np.array([int(e) for e in vals], np.uint8 if self.esz == 1 else np.uint16)
+        return torch.from_numpy(a.view(np.int8 if self.esz == 1 else np.int16)).to(self.device).view(self.dtype)
+
+    def histogram_rows(self, batch, mask=None, nbins=256, lo=None, shift=None, chunks_per_hist=0, general_layout=False, check=True):
+        """Per-column value counts of the rows a mask names, fused into the decode (one launch; only the counts leave the chip).
+
+        mask: uint8 [nchunks, MB] in filter_rows' layout (MB = ceil(R / 8), R = chunk_len / ndims: chunk_len must be a multiple of
+        ndims), or None: every row; bits of rows that do not exist are ignored.
+        A value x of column d is counted in bin ((x - lo[d]) mod 2^W) >> shift if that is below nbins, and dropped otherwise.  lo: a
+        scalar, ndims entries or a tensor; None: 0.  shift=None: the one that makes nbins bins cover the element range,
+        W - ceil(log2(nbins)) (W - 1 for one bin).  ndims * nbins is at most 16384 a call: split wider requests with lo.
+        chunks_per_hist = H: chunks [g H, (g + 1) H) share histogram g; 0: one histogram for the batch.
+        -> int64 [ngroups, ndims, nbins].  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        D, n, W = self.ndims, batch.nchunks, 8 * self.esz
+        if self.chunk_len % D:
+            raise ValueError(f"histogram_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        nbins, H = int(nbins), int(chunks_per_hist)
+        if nbins < 1 or H < 0:
+            raise ValueError("nbins must be positive and chunks_per_hist must not be negative")
+        if shift is None:
+            shift = min(max(W - max(nbins - 1, 0).bit_length(), 0), W - 1)
+        shift = int(shift)
+        R = self.chunk_len // D
+        MB = -(-R // 8)
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
+                raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
+            mask = mask.contiguous()
+        lo_t = None if lo is None else self._elem_tensor(lo, "lo")
+        ngroups = -(-n // H) if H else 1
+        hist = torch.empty((ngroups if n else 0, D, nbins), dtype=torch.int64, device=self.device)
+        if n == 0:
+            return hist
+        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        with self._on():
+            _lib.check(_lib.histogram_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                           self.chunk_len, D, mask.data_ptr() if mask is not None else None,
+                                           lo_t.data_ptr() if lo_t is not None else None, shift, nbins, H,
+                                           _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                           hist.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
+        if check and n:
+            bad = (rets < 0).nonzero()
+            if bad.numel():
+                c = int(bad[0, 0].item())
+                raise _lib.SprintzError(int(rets[c].item()), f"histogram_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        return hist
+
+    def histogram_where(self, batch, lo, hi, mode="all", **kw):
+        """The distribution of the rows that satisfy a condition: filter_rows (its lo / hi / mode) and histogram_rows on its mask -- two
+        decode-speed launches; the batch is never materialised.  kw: histogram_rows' other arguments (nbins, its own lo as hist_lo,
+        shift, chunks_per_hist, general_layout)."""
+        if "hist_lo" in kw:
+            kw["lo"] = kw.pop("hist_lo")
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
+        return self.histogram_rows(batch, mask=f["mask"], **kw)
+
+    def _hist_span(self, batch, mask, shift, total_bins, lo64=None):
+        """one histogram of the batch, total_bins bins of 2^shift values from lo64 [ndims] (int64 device tensor; None: 0) on, as int64
+        [ndims, total_bins]: as many calls as the cap on ndims * nbins asks for, side by side"""
+        torch = self.torch
+        D, W = self.ndims, 8 * self.esz
+        nb = total_bins
+        while D * nb > _lib.HIST_MAX_COUNTERS:
+            nb //= 2
+        parts = []
+        for k in range(total_bins // nb):
+            if lo64 is None and k == 0:
+                lo_k = None
+            else:
+                base = lo64 if lo64 is not None else torch.zeros(D, dtype=torch.int64, device=self.device)
+                lo_k = (base + ((k * nb) << shift)) % (1 << W)
+            parts.append(self.histogram_rows(batch, mask=mask, nbins=nb, lo=lo_k, shift=shift)[0])
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+    def quantiles(self, batch, q, mask=None):
+        """EXACT per-column quantiles of the whole batch (of the rows a mask names), straight from the compressed data: histogram
+        passes and cumulative sums on the device, no sample leaves the chip.
+
+        q: quantiles in [0, 1].  -> [len(q), ndims] of the codec's dtype: for a column with n selected values, the value at index
+        max(ceil(q n), 1) - 1 of them sorted.  Raises ValueError where n == 0.
+        8-bit data: one full-resolution pass.  16-bit data: a coarse pass (256 bins of 256 values), then one refinement pass (256
+        bins of one value, lo at the start of the wanted coarse bin, column by column) for each group of quantiles that fall in the
+        same coarse bin of their column.  Passes are split with lo where ndims * 256 exceeds a call's counters."""
+        torch = self.torch
+        D, W = self.ndims, 8 * self.esz
+        qs = [float(x) for x in (q if np.ndim(q) else [q])]
+        if not qs or any(not 0.0 <= x <= 1.0 for x in qs):
+            raise ValueError("q must be one or more numbers in [0, 1]")
+        if batch.nchunks == 0:
+            raise ValueError("quantiles of an empty batch")
+        Q = len(qs)
+        coarse = self._hist_span(batch, mask, W - 8, 256)                        # [D, 256]
+        cum = torch.cumsum(coarse, dim=1)
+        n = cum[:, -1]
+        if bool((n == 0).any().item()):
+            raise ValueError("quantiles: no row is selected")
+        qt = torch.tensor(qs, dtype=torch.float64, device=self.device)
+        k = (torch.ceil(qt[None, :] * n[:, None].to(torch.float64)).to(torch.int64).clamp(min=1) - 1).contiguous()   # [D, Q]
+        cb = torch.searchsorted(cum, k, right=True)                              # the first bin whose cumulative count exceeds the index
+        if W == 8:
+            return cb.t().contiguous().to(torch.uint8)
+        k2 = k - (torch.gather(cum, 1, cb) - torch.gather(coarse, 1, cb))        # the index inside the coarse bin
+        # the quantiles of a column that share a coarse bin share a pass: rank of each quantile's bin among its column's distinct bins
+        scb, order = torch.sort(cb, dim=1)
+        step = torch.zeros_like(scb)
+        step[:, 1:] = (scb[:, 1:] != scb[:, :-1]).to(torch.int64)
+        rank = torch.empty_like(cb).scatter_(1, order, torch.cumsum(step, dim=1))
+        out = torch.zeros_like(cb)
+        for j in range(int(rank.max().item()) + 1):
+            here = rank == j
+            bin_j = torch.where(here, cb, torch.zeros_like(cb)).amax(dim=1)      # [D]: the column's j-th distinct bin (0 where it has fewer)
+            fine = self._hist_span(batch, mask, 0, 256, lo64=bin_j << 8)
+            fb = torch.searchsorted(torch.cumsum(fine, dim=1), k2, right=True)
+            out = torch.where(here, (cb << 8) + fb, out)
+        half = 1 << 15
+        return (((out.t().contiguous() + half) % (1 << 16)) - half).to(torch.int16).view(torch.uint16)
+
     def read_rows(self, batch, lo, hi):
         """batch rows [lo, hi) -> [hi - lo, ndims]: one range of gather_rows, its chunks decoded side by side in the same launch"""
         lo, hi = int(lo), int(hi)

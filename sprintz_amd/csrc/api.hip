@@ -292,14 +292,14 @@ hipError_t launch_size_scan(const uint32_t* d_sizes, uint64_t n, uint32_t align,
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
     const auto unit = q == kQueryGather ? decode_generic_gather : q == kQueryFilter ? decode_generic_filter : q == kQuerySelect ? decode_generic_select
-                    : q == kQueryAggregate ? decode_generic_aggregate
+                    : q == kQueryAggregate ? decode_generic_aggregate : q == kQueryHistogram ? decode_generic_histogram
                     : w == 8 ? decode_generic_w8 : decode_generic_w16;
     return unit(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
     const auto unit = q == kQueryGather ? decode_fast_gather : q == kQueryFilter ? decode_fast_filter : q == kQuerySelect ? decode_fast_select
-                    : q == kQueryAggregate ? decode_fast_aggregate
+                    : q == kQueryAggregate ? decode_fast_aggregate : q == kQueryHistogram ? decode_fast_histogram
                     : w == 8 ? decode_fast_w8 : decode_fast_w16;
     return unit(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
@@ -332,7 +332,7 @@ int check_common(int codec, int esz, uint16_t ndims)
     return 0;
 }
 
-// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows) check alike, behind check_common; the refusals that
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
                  const char* rle_only, const char* op = nullptr)
@@ -390,7 +390,7 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryAggregate (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryHistogram (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -399,6 +399,7 @@ struct QuerySpec {
     FilterArgs filter{};        // kQueryFilter
     SelectArgs select{};        // kQuerySelect
     AggregateArgs agg{};        // kQueryAggregate (with win)
+    HistogramArgs hist{};       // kQueryHistogram (table_off and wg_chunks come from the plan)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -432,6 +433,7 @@ Shape decode_shape(int codec, int esz, const void* d_comp, uint64_t nchunks, uin
     s.noheader = noheader; s.q = qs.q; s.general = qs.general; s.col_stride = qs.col_stride; s.host_call = qs.hc != nullptr;
     s.comp_lo = low4(d_comp); s.out_lo = low4(d_out);
     s.capacity = qs.select.capacity;
+    s.hist_bins = qs.hist.nbins;
     return s;
 }
 
@@ -465,6 +467,9 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.filter = qs.filter;
     a.select = qs.select;
     a.agg = qs.agg;
+    a.hist = qs.hist;
+    a.hist.table_off = p.hist_table_off;
+    a.hist.wg_chunks = p.hist_wg_chunks;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -1738,6 +1743,41 @@ int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp,
     qs.agg = AggregateArgs{d_mask, (ops & SPRINTZ_AGG_COUNT) ? d_count : nullptr, (rows + 7) / 8};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- histogram rows
+int sprintz_mi355x_histogram_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                  uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, const void* d_lo, uint32_t shift, uint32_t nbins,
+                                  uint64_t hist_chunks, uint32_t flags, uint64_t* d_hist, int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "histogram_rows: more than 512 columns", "histogram_rows: the RLE codecs (delta, xff) only",
+                           "histogram_rows"))) return rc;
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "histogram_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    const uint32_t W = 8u * (uint32_t)elem_bytes;
+    if (shift >= W) return fail(SPRINTZ_E_INVALID, "histogram_rows: shift must be below the element width");
+    if (nbins < 1 || nbins > (1u << (W - shift))) return fail(SPRINTZ_E_INVALID, "histogram_rows: nbins must be in 1..2^(W - shift)");
+    if (!d_hist) return fail(SPRINTZ_E_INVALID, "histogram_rows: null device pointer");
+    if ((uintptr_t)d_hist % 8 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "histogram_rows: d_hist and d_rets must be aligned to 8 bytes");
+    if (d_lo && (uintptr_t)d_lo % (uintptr_t)elem_bytes) return fail(SPRINTZ_E_INVALID, "histogram_rows: d_lo must be aligned to the element size");
+    if ((uint64_t)ndims * nbins > SPRINTZ_HIST_MAX_COUNTERS)
+        return fail(SPRINTZ_E_UNSUPPORTED, "histogram_rows: ndims x nbins above SPRINTZ_HIST_MAX_COUNTERS: split the bins with d_lo");
+    const uint64_t ngroups = hist_chunks ? (nchunks + hist_chunks - 1) / hist_chunks : 1;
+    if (ngroups > (1ull << 40) / ((uint64_t)ndims * nbins))
+        return fail(SPRINTZ_E_INVALID, "histogram_rows: too many histograms for one call (ngroups x ndims x nbins above 2^40 entries)");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    QuerySpec qs;
+    qs.q = kQueryHistogram;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.hist = HistogramArgs{d_mask, d_lo, d_hist, hist_chunks, shift, nbins, (chunk_len / ndims + 7) / 8, 0, 0};
+    // planned first: a call the planner refuses leaves d_hist as it was
+    const Plan p = plan_decode(decode_shape(codec, elem_bytes, d_comp, nchunks, chunk_len, ndims, nullptr, 0, qs), snapshot());
+    if (p.err) return fail(p.err, p.what);
+    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)(ngroups * ndims * nbins * 8), st));
+    return decode_launch(p, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, st, 0, 0, 0, qs);
 }
 
 // ---------------------------------------------------------------- gather rows

@@ -135,6 +135,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // windows' entries, so any shape the windowed query takes is taken; the mask bytes come through select's read-ahead window.
     constexpr bool AGG = Q == kQueryAggregate;
     static_assert(!AGG || (!CM && !SPLIT && DS == 0), "aggregate: plain mappings");
+    // HIST (sprintz_mi355x_histogram_rows): per-column value counts of the rows the caller's mask names (or of every row).  Nothing is
+    // stored: the samples are counted in the workgroup's LDS table behind the groups' carves (decode_ops.h: hist_begin .. hist_end); the
+    // mask bytes come through select's read-ahead window.  The workgroup's lanes meet at two barriers, so no lane leaves early.
+    constexpr bool HIST = Q == kQueryHistogram;
+    static_assert(!HIST || (!CM && !SPLIT && DS == 0), "histogram: plain mappings");
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -174,7 +179,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         c_sel = gp.chunk;
     }
     const uint64_t c_first = c_sel;
-    if (c_first >= a.nchunks) return;
+    if constexpr (!HIST) {
+        if (c_first >= a.nchunks) return;
+    }                                                      // (histogram: c_end <= c_first below, and the chunk loop does not run)
     const uint64_t c_end = GATHER ? c_first + 1 : (c_first + a.chunks_per_group < a.nchunks) ? c_first + a.chunks_per_group : a.nchunks;
 
     // LDS carve per group: [ring RB | apron APRON | block staging]
@@ -351,6 +358,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t arow[8];
     uint32_t acnt = 0;
     uint8_t* fmb = nullptr;
+    // histogram rows: the lane's columns and where the samples are counted
+    HistCol hcol[CPL];
+    HistCtx hctx{};
+    if constexpr (HIST) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) hcol[k] = hist_col<W>(a, genk[k], col_ok[k]);
+        hctx = hist_begin(a, smem);
+    }
     if constexpr (Q == kQueryFilter) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) fc[k] = filter_col<W>(a, genk[k], col_ok[k]);
@@ -359,7 +374,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG) {                        // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST) {                // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (Q != 0) {
             if constexpr (W == 16) {
@@ -392,6 +407,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 for (int i = 0; i < 8; i++) aggregate_row<W>(arow[i], aggregate_sel<W>(sm, i), qmin[k], qmax[k], bs);
                 qsum[k] += bs;
             }
+        } else if constexpr (HIST) {                       // (a lane column past the last one counts nothing)
+            if (sm != 0 && col_ok[k]) hist_rows8<W>(hctx, hcol[k], arow, sm);
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
     // after every block of 8 rows: the group's lanes combine, one lane stores the block's byte (fb < chunk_len / blk_elems <=
@@ -424,6 +441,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             wleft -= 8;
             if (wleft == 0) win_flush_all();
         }
+        if constexpr (HIST) fb++;
     };
     uint32_t ovo = 0;                                      // output cursor (byte offset from this wave's out_base)
     // gather: the chunk-relative row of the next block, and the row of the block each of this lane's 16-byte store pieces lies in
@@ -446,7 +464,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // load from memory sits between a block's header and its stores.  (A chunk's mask starts at any address, and its last dword may be
     // short: those bytes are read one by one.)
     uint32_t mwin = 0, mwin0 = 0x80000000u;
-    auto sel_stride = [&]() -> uint32_t { if constexpr (AGG) return a.agg.mask_stride; else return a.select.mask_stride; };
+    auto sel_stride = [&]() -> uint32_t {
+        if constexpr (AGG) return a.agg.mask_stride;
+        else if constexpr (HIST) return a.hist.mask_stride;
+        else return a.select.mask_stride;
+    };
     auto sel_byte = [&](uint32_t b) -> uint32_t {
         if (b - mwin0 >= 4u * DP) {
             mwin0 = b & ~3u;
@@ -691,6 +713,24 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             return;
         }
+        if constexpr (HIST && !FIRE) {
+            // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows -- the set
+            // bits of its mask bytes, spread over the group's lanes; 8 len without a mask.  (The bytes lie inside the chunk's: the run
+            // fits the chunk slot.)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            uint32_t c = 8u * len;
+            if (smb) {
+                c = 0;
+                for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
+                c = group_sum(c, DP);
+            }
+#pragma unroll
+            for (int k = 0; k < CPL; k++)
+                if (col_ok[k]) hist_value<W>(hctx, hcol[k], pv[k], c);
+            fb += len;
+            return;
+        }
         if constexpr (SELECT && !FIRE) {
             // a delta run repeats the previous row and changes no state: a run none of whose rows the mask wants is stepped over
             // (its mask bytes lie inside the chunk's: the run fits the chunk slot)
@@ -722,6 +762,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
             }
             if constexpr (AGG) sm = sel_byte(fb);          // (a FIRE run is replayed for its state, block by block, as the window mode does)
+            if constexpr (HIST) sm = smb ? sel_byte(fb) : 0xffu;
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -843,6 +884,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
         if constexpr (SELECT || AGG) sm = sel_byte(fb);    // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
+        if constexpr (HIST) sm = smb ? sel_byte(fb) : 0xffu;
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -969,6 +1011,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fb = 0; sm = 0; acnt = 0;
             mwin0 = 0x80000000u;                           // no window yet: the first block loads one
             smb = a.agg.mask + chunk * (uint64_t)a.agg.mask_stride;
+        }
+        if constexpr (HIST) {
+            fb = 0; sm = 0;
+            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
+            smb = a.hist.mask ? a.hist.mask + chunk * (uint64_t)a.hist.mask_stride : nullptr;
+            hctx.g = hist_of_chunk(a, chunk);
         }
         if constexpr (SELECT) {
             fb = 0; srank = 0; sm = 0;
@@ -1152,6 +1200,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (!corrupt)
             aggregate_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
                                    [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (HIST) {
+        // fb blocks = 8 fb rows lie in front of the tail
+        if (!corrupt)
+            hist_tail<W, CPL>(a, hctx, hcol, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) {
             const uint8_t* t = a.comp + gabs + rp;
@@ -1188,6 +1240,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     if (corrupt || remaining > 0) need_prime = true;       // cursor no longer at the next stream
     if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
     }   // chunk loop
+    if constexpr (HIST) hist_end(a, hctx);
 }
 
 }  // namespace sprintz

@@ -22,6 +22,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     constexpr int HB = Elem<W>::HB;
     constexpr uint32_t MASK = Elem<W>::MASK;
     constexpr int ESZ = W / 8;
+    // HIST (sprintz_mi355x_histogram_rows): the workgroup's lanes meet at two barriers -- behind the zeroing of its table and in front of
+    // the table's merge (decode_ops.h: hist_begin, hist_end) -- so in this mode no lane leaves early: a group past the last chunk
+    // (hlive false) and a chunk whose header is refused (hbad) walk on as empty streams.
+    constexpr bool HIST = Q == kQueryHistogram;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int DP = 1 << a.log2DP;
@@ -38,8 +42,17 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         }
         chunk_sel = gp.chunk;
     }
+    bool hlive = true, hbad = false;
+    HistCtx hctx{};
+    if constexpr (HIST) {
+        hctx = hist_begin(a, smem);
+        hlive = chunk_sel < a.nchunks;
+        if (!hlive) chunk_sel = a.nchunks - 1;      // (any stream will do: none of it is read)
+    }
     const uint64_t chunk = chunk_sel;
-    if (chunk >= a.nchunks) return;                 // whole groups leave together
+    if constexpr (!HIST) {
+        if (chunk >= a.nchunks) return;             // whole groups leave together
+    }
 
     const uint64_t off_c = a.offsets[chunk];
     const uint8_t* s = a.comp + off_c;
@@ -54,7 +67,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
     // ---- 8-byte stream header (format.h:48-62)
     uint32_t groups_left, remaining, pos;
-    if (a.norle) {                                   // format.h:65-86; sprintz_delta.cpp:803-807, :832
+    if (HIST && !hlive) {
+        groups_left = 0; remaining = 0; pos = 0;
+    } else if (a.norle) {                                   // format.h:65-86; sprintz_delta.cpp:803-807, :832
         // norle == 2: compress8b_rowmajor_xff's 8-byte header, a u64 len whose bytes 6..7 hold ndims (sprintz_xff.cpp:58-63)
         const uint32_t len = load_u32_any(s);
         const uint32_t ndo = a.norle == 2 ? 6u : 4u;
@@ -62,7 +77,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)nd != D || len > a.chunk_len) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
-            return;
+            if constexpr (HIST) hbad = true; else return;
         }
         groups_left = len < 128u ? 0u : len / (16u * (uint32_t)D);
         remaining = len - groups_left * 16u * (uint32_t)D;
@@ -75,7 +90,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)(w1 >> 16) != D) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
-            return;
+            if constexpr (HIST) hbad = true; else return;
         }
     } else {
         groups_left = a.nh_ngroups;
@@ -88,6 +103,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // a damaged header must not make the loop spin: every group of a valid stream holds at
     // least one non-empty slot, except the one that closes the stream
     bool corrupt = groups_left > a.chunk_len / blk_elems + 2u || pos > stream_len;
+    if (HIST && hbad) corrupt = true;
     if (corrupt) groups_left = 0;
 
     // per-column predictor state (all start at 0: sprintz_xff_rle.cpp:149-152)
@@ -143,6 +159,16 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     const uint8_t* amb = nullptr;
     uint32_t am = 0, acnt = 0;
     if constexpr (Q == kQueryAggregate) amb = a.agg.mask + chunk * (uint64_t)a.agg.mask_stride;
+    // histogram rows: the lane's columns, the chunk's histogram and mask bytes (null: every row), the mask byte of the block being decoded
+    HistCol hcol[CPL];
+    const uint8_t* hmb = nullptr;
+    uint32_t hm = 0xffu;
+    if constexpr (HIST) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) hcol[k] = hist_col<W>(a, colk[k], genk[k]);
+        hctx.g = hist_of_chunk(a, chunk);
+        if (a.hist.mask) hmb = a.hist.mask + chunk * (uint64_t)a.hist.mask_stride;
+    }
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -199,6 +225,25 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     if (b0 & 0x80u) { len |= load_u8(s + pos + 1) << 7; pos += 2; }
                     else pos += 1;
                     slot++;
+                    if constexpr (HIST && !FIRE) {
+                        // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows --
+                        // the set bits of its mask bytes, spread over the group's lanes (they lie inside the chunk's: the run fits the slot)
+                        if (len > 0) {
+                            if ((uint64_t)out_elems + (uint64_t)len * blk_elems > a.chunk_len) { corrupt = true; break; }
+                            const uint32_t b0r = out_elems / blk_elems;
+                            uint32_t c = 8u * len;
+                            if (hmb) {
+                                c = 0;
+                                for (uint32_t j = (uint32_t)lane_d; j < len; j += (uint32_t)DP) c += (uint32_t)__popc((uint32_t)hmb[b0r + j]);
+                                c = group_sum(c, DP);
+                            }
+#pragma unroll
+                            for (int k = 0; k < CPL; k++)
+                                if (genk[k]) hist_value<W>(hctx, hcol[k], pv[k], c);
+                            out_elems += len * blk_elems;
+                        }
+                        continue;
+                    }
                     if (len > 0) { run_left = len - 1; have = true; run_block = true; break; }
                     // len == 0: padding slot, look at the next one
                 } else {                         // packed block
@@ -244,6 +289,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         uint32_t fl = 0;                         // filter: this lane's columns' rows, inverted domain
         // (block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride: checked above; all 8 rows of a block exist)
         if constexpr (Q == kQueryAggregate) am = amb[out_elems / blk_elems];
+        if constexpr (HIST) hm = hmb ? (uint32_t)hmb[out_elems / blk_elems] : 0xffu;
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -277,6 +323,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 #pragma unroll
                     for (int i = 0; i < 8; i++) aggregate_row<W>(v[i][k], aggregate_sel<W>(am, i), qmin[k], qmax[k], bs);
                     qsum[k] += bs;
+                }
+            } else if constexpr (HIST) {
+                if (hm != 0 && genk[k]) {
+                    uint32_t xs[8];
+#pragma unroll
+                    for (int i = 0; i < 8; i++) xs[i] = v[i][k];
+                    hist_rows8<W>(hctx, hcol[k], xs, hm);
                 }
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
@@ -423,6 +476,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                                              [&](uint32_t b) { return (uint32_t)amb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) reduce_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, colk, genk, qmax, qsum);      // (out_elems is a multiple of 8*D)
+    }
+    if constexpr (HIST) {
+        if (!corrupt) hist_tail<W, CPL>(a, hctx, hcol, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk,
+                                        [&](uint32_t b) { return (uint32_t)hmb[b]; });
+        if (hlive && lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        hist_end(a, hctx);
+        return;
     }
     if constexpr (Q == kQueryGather) {
         gather_tail<W>(a, gp, s + pos, out_elems, remaining, (uint32_t)D, lane_d, DP, corrupt, false);

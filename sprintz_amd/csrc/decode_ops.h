@@ -1,5 +1,5 @@
-// decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select and
-// aggregate rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
+// decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
+// aggregate and histogram rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
 // its lane's columns (`col`, with `genuine` false for a lane column past the last one), its place in the group (`lane_d` of `DP`
 // lanes) and the mode's running state; decode_uni.h is the lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane
 // mapping -- how a block's rows reach the accumulators, the staging and the stores -- stays in that kernel.
@@ -57,6 +57,21 @@ struct AggregateArgs {
     uint32_t* count;            // optional (SPRINTZ_AGG_COUNT)
     uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
 };
+// histogram rows (Q == kQueryHistogram; sprintz_mi355x_histogram_rows): value x of column d, in a row whose bit is set in chunk c's mask
+// bytes (filter_rows' layout; no mask: every existing row), counts in bin b = ((x - lo[d]) mod 2^W) >> shift of histogram c / group_chunks
+// if b < nbins, and nowhere otherwise: hist[(g * D + d) * nbins + b].  A workgroup decodes the wg_chunks consecutive chunks from
+// blockIdx.x * wg_chunks on and counts them in its own table of D * nbins uint32 at byte table_off of its dynamic LDS -- if they all lie
+// in one histogram; if not (or wg_chunks == 0: the planner found that a counter could wrap) every sample goes to `hist` directly
+struct HistogramArgs {
+    const uint8_t* mask;        // [nchunks][mask_stride], or null: a run-time, wave-uniform switch, as filter.mode is
+    const void* lo;             // [D], element type, on the device, or null: all zero
+    uint64_t* hist;             // [ngroups][D][nbins], zeroed on the stream in front of the launch
+    uint64_t group_chunks;      // H; 0: the whole batch is one histogram
+    uint32_t shift, nbins;
+    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
+    uint32_t table_off;
+    uint32_t wg_chunks;
+};
 
 struct DecodeArgs {
     const uint8_t* comp;        // compressed bytes
@@ -97,6 +112,7 @@ struct DecodeArgs {
     FilterArgs filter;
     SelectArgs select;
     AggregateArgs agg;
+    HistogramArgs hist;
 };
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
@@ -228,6 +244,127 @@ __device__ __forceinline__ void aggregate_tail(const DecodeArgs& a, const uint8_
         }
     }
     while (w < a.win.count) flush();
+}
+
+// ---- histogram rows.  A sample's test is filter_hit's shape: one masked subtract, one shift, one compare.  The counters are a table in
+// the workgroup's LDS (non-returning ds_add_u32; HistCtx::tab) or, for a workgroup whose chunks lie in more than one histogram, the
+// caller's 64-bit entries themselves (HistCtx::g: the histogram of the chunk being decoded).
+#ifndef SPRINTZ_HIST_MERGE
+// what a column's 8 rows of one block cost in atomics, all three forms measured in profiles/histogram_rows.txt -- 2 (kept): one add of 8
+// where all 8 rows are selected and share a bin, an add a sample otherwise; 1: every run of equal consecutive bins is one add of its
+// length; 0: an add a sample
+#define SPRINTZ_HIST_MERGE 2
+#endif
+typedef __attribute__((address_space(3))) uint32_t hist_lds_u32;
+struct HistCtx {
+    hist_lds_u32* tab;          // the workgroup's table, or null: every add goes to g
+    uint64_t* g;
+    uint32_t shift, nbins;
+};
+struct HistCol { uint32_t lo, base; };    // the column's lo and the index of its bin 0 inside a histogram, column * nbins
+template <int W>
+__device__ __forceinline__ HistCol hist_col(const DecodeArgs& a, int col, bool genuine)
+{
+    using U = typename Elem<W>::U;
+    return HistCol{genuine && a.hist.lo ? (uint32_t)((const U*)a.hist.lo)[col] : 0u, (uint32_t)col * a.hist.nbins};
+}
+__device__ __forceinline__ uint64_t* hist_of_chunk(const DecodeArgs& a, uint64_t chunk)
+{
+    const uint64_t g = a.hist.group_chunks ? chunk / a.hist.group_chunks : 0;
+    return a.hist.hist + g * ((uint64_t)a.D * a.hist.nbins);
+}
+__device__ __forceinline__ void hist_add(const HistCtx& c, uint32_t idx, uint32_t n)
+{
+    if (c.tab) (void)__hip_atomic_fetch_add(c.tab + idx, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else (void)__hip_atomic_fetch_add(c.g + idx, (uint64_t)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// (x may carry garbage above bit W: only its low W bits reach the masked difference)
+template <int W> __device__ __forceinline__ uint32_t hist_bin(const HistCtx& c, const HistCol& h, uint32_t x) { return ((x - h.lo) & Elem<W>::MASK) >> c.shift; }
+// one value that `n` selected rows hold (a delta run's constant row, a row of the tail)
+template <int W> __device__ __forceinline__ void hist_value(const HistCtx& c, const HistCol& h, uint32_t x, uint32_t n)
+{
+    const uint32_t b = hist_bin<W>(c, h, x);
+    if (b < c.nbins && n != 0) hist_add(c, h.base + b, n);
+}
+// a column's 8 rows of one block; bit i of m: row i is selected
+template <int W>
+__device__ __forceinline__ void hist_rows8(const HistCtx& c, const HistCol& h, const uint32_t (&x)[8], uint32_t m)
+{
+#if SPRINTZ_HIST_MERGE == 1
+    uint32_t pb = 0, pc = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t b = hist_bin<W>(c, h, x[i]);
+        const bool on = b < c.nbins && ((m >> i) & 1u);
+        if (on && pc != 0 && b == pb) {
+            pc++;
+        } else {
+            if (pc != 0) hist_add(c, h.base + pb, pc);
+            pb = b;
+            pc = on ? 1u : 0u;
+        }
+    }
+    if (pc != 0) hist_add(c, h.base + pb, pc);
+#else
+    uint32_t b[8], diff = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        b[i] = hist_bin<W>(c, h, x[i]);
+        diff |= b[i] ^ b[0];
+    }
+    if (SPRINTZ_HIST_MERGE == 2 && diff == 0 && m == 0xffu) {     // 2: only a block whose 8 rows are selected and share a bin is one add
+        if (b[0] < c.nbins) hist_add(c, h.base + b[0], 8u);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        if (b[i] < c.nbins && ((m >> i) & 1u)) hist_add(c, h.base + b[i], 1u);
+#endif
+}
+// At the kernel's start, every lane of the workgroup: does the workgroup count in its table?  (Workgroup-uniform: its chunks
+// [blockIdx.x * wg_chunks, + wg_chunks) -- those that exist -- lie in one histogram.)  The table is zeroed, behind a barrier.
+__device__ __forceinline__ HistCtx hist_begin(const DecodeArgs& a, uint8_t* smem)
+{
+    HistCtx c{nullptr, a.hist.hist, a.hist.shift, a.hist.nbins};
+    const uint64_t first = (uint64_t)blockIdx.x * a.hist.wg_chunks;
+    if (a.hist.wg_chunks == 0 || first >= a.nchunks) return c;
+    const uint64_t last = (first + a.hist.wg_chunks < a.nchunks ? first + a.hist.wg_chunks : a.nchunks) - 1;
+    if (a.hist.group_chunks && first / a.hist.group_chunks != last / a.hist.group_chunks) return c;
+    c.tab = (hist_lds_u32*)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + a.hist.table_off);
+    const uint32_t n = (uint32_t)a.D * a.hist.nbins;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) c.tab[i] = 0;
+    __syncthreads();
+    return c;
+}
+// At the kernel's end, every lane of the workgroup (none has left): behind a barrier the table's nonzero counters are added to the
+// workgroup's histogram, spread over all lanes -- device-scope 64-bit adds: integer sums, exact in any order.
+__device__ __forceinline__ void hist_end(const DecodeArgs& a, const HistCtx& c)
+{
+    if (!c.tab) return;
+    __syncthreads();
+    uint64_t* const g = hist_of_chunk(a, (uint64_t)blockIdx.x * a.hist.wg_chunks);
+    const uint32_t n = (uint32_t)a.D * a.hist.nbins;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+        const uint32_t v = c.tab[i];
+        if (v != 0) (void)__hip_atomic_fetch_add(g + i, (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
+// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  mask_at(b) is the chunk's mask byte b
+// (asked only where there is a mask).
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void hist_tail(const DecodeArgs& a, const HistCtx& c, const HistCol (&h)[CPL], const uint8_t* t, uint32_t remaining, uint32_t D,
+                                          uint32_t row0, const int (&col)[CPL], const bool (&genuine)[CPL], F mask_at)
+{
+    const uint32_t nfull = remaining / D;
+    uint32_t m = 0xffu;
+    for (uint32_t r = 0; r < nfull; r++) {
+        if ((r & 7u) == 0 && a.hist.mask) m = mask_at((row0 + r) >> 3);
+        if (!((m >> (r & 7u)) & 1u)) continue;
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) hist_value<W>(c, h[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), 1u);
+    }
 }
 
 // ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the

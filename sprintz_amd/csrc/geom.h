@@ -26,11 +26,19 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 4 = gather: a lane group decodes one PIECE (a range's rows [lo, hi) of one chunk), stores those rows alone and stops after row hi - 1;
 // 5 = filter: one bit per row -- does the row satisfy the per-column bounds? -- and the chunk's count of them, reduce only;
 // 6 = select: a chunk is decoded once and only the rows whose bit is set in the caller's mask are stored, packed densely behind the chunk's base;
-// 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only
+// 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only;
+// 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7;
+              kQueryAggregate = 7, kQueryHistogram = 8;
 // the modes that never store a decoded sample
-constexpr bool query_reduce_only(int q) { return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate; }
+constexpr bool query_reduce_only(int q)
+{
+    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram;
+}
+// histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
+// dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB
+constexpr uint32_t kHistMaxCounters = 16384;
+constexpr uint32_t kHistFastLdsBudget = 80u * 1024u;
 
 // sprintz_mi355x_compress_bound: the longest stream a chunk of chunk_len elements can have, a multiple of SPRINTZ_BOUND_ALIGN
 inline size_t compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)

@@ -43,6 +43,7 @@ struct Shape {
     uint64_t nranges = 0;                  // gather
     uint32_t rows = 0;
     uint64_t capacity = 0;                 // select: rows of the output
+    uint32_t hist_bins = 0;                // histogram: nbins (D x nbins counters, at most kHistMaxCounters)
 };
 
 struct Plan {
@@ -58,6 +59,9 @@ struct Plan {
     bool fused = false;                    // the encoder builds the container itself: grid + 1 zeroed words of d_tmp in front of it
     bool plain_memory = false;             // the output / the slots must be ordinary device memory (checked BEFORE err is reported, as the launch sites did)
     bool counters = false;                 // FIRE counters in stream-ordered scratch, nchunks x D x 4 bytes
+    // histogram: where a workgroup's table of D x nbins uint32 counters starts in its dynamic LDS (behind the groups' carves), and the
+    // consecutive chunks a workgroup decodes -- 0 where their rows could wrap a 32-bit counter: such a launch counts in global memory
+    uint32_t hist_table_off = 0, hist_wg_chunks = 0;
     RowDecGeom row{};
     BlkDecGeom blkd{};
     BlkEncGeom blke{};
@@ -132,6 +136,14 @@ inline bool big_counters(Plan& p, const Shape& s)
         return false;
     }
     return true;
+}
+
+static_assert(kHistMaxCounters == SPRINTZ_HIST_MAX_COUNTERS, "the table's size is the header's cap");
+// histogram rows: a table counter takes at most one add a row of the workgroup's chunks -- wg_chunks x (chunk_len / D) of them, which must
+// fit 32 bits; the table is merged once, at the kernel's end
+inline uint32_t hist_wg_chunks(uint64_t wg_chunks, uint32_t chunk_len, int D)
+{
+    return wg_chunks * (uint64_t)(chunk_len / (uint32_t)D) <= 0xffffffffull ? (uint32_t)wg_chunks : 0u;
 }
 
 inline Plan plan_decode(const Shape& s, const Knobs& k)
@@ -236,7 +248,9 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
             return plan_take(p, SPRINTZ_KF_DEC_BLK, (nchunks + g.CPW - 1) / g.CPW, g.total);
         }
     }
-    if (fast) {
+    // histogram rows: the workgroup's table sits behind the groups' carves, and both must fit the launch's LDS budget
+    const uint64_t hist_bytes = s.q == kQueryHistogram ? 4ull * (uint64_t)D * s.hist_bins : 0;
+    if (fast && (s.q != kQueryHistogram || (uint64_t)f.ring * (kThreads / f.dp) + hist_bytes <= kHistFastLdsBudget)) {
         p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
         p.exact = D == f.dp * f.cpl;
         p.log2DP = f.log2dp;
@@ -246,12 +260,20 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
         // than four staggered ones, so the default stays at one chunk per group (env knob for tuning).
         p.chunks_per_group = (uint32_t)k.chunks_per_group;
         const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
-        return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * (kThreads / f.dp));
+        if (s.q == kQueryHistogram) {
+            p.hist_table_off = f.ring * (uint32_t)(kThreads / f.dp);
+            p.hist_wg_chunks = hist_wg_chunks((uint64_t)(kThreads / f.dp) * p.chunks_per_group, chunk_len, D);
+        }
+        return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * (kThreads / f.dp) + hist_bytes);
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    // (decode_uni.h is not taught to select or to aggregate rows: those shapes go to the generic kernel)
-    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
+    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram: those shapes go to the generic kernel)
+    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
+    if (s.q == kQueryHistogram) {                              // nothing is staged: the table is the launch's LDS
+        p.hist_wg_chunks = hist_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D);
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, hist_bytes);
+    }
     return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, shmem);
 }
 
