@@ -51,7 +51,7 @@ extern "C" {
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
- *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS */
+ *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -155,7 +155,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -634,6 +634,40 @@ int sprintz_mi355x_histogram_rows(int codec, int elem_bytes, const void* d_comp,
                                   uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */,
                                   const void* d_lo /* may be NULL */, uint32_t shift, uint32_t nbins, uint64_t hist_chunks,
                                   uint32_t flags, uint64_t* d_hist, int64_t* d_rets, void* hip_stream);
+/* Moments rows: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names -- what
+ * variance, standard deviation, covariance and correlation follow from exactly -- fused into the decode: only the results leave the chip.
+ *
+ * The batch, the flags, the windows and the mask are sprintz_mi355x_aggregate_rows' (chunk_len % ndims == 0 is required; D = ndims,
+ * R = chunk_len / D, MB = ceil(R / 8), W = window_rows, a multiple of 8, at least 8, nwin = ceil(R / W): windows are relative to the
+ * chunk), except that d_mask may be NULL: every existing row, as in sprintz_mi355x_histogram_rows.  A mask bit is ignored if its row
+ * does not exist, and a partial last row is not a row.
+ * For chunk c and window w, over the selected existing rows of that window, the call writes
+ *   d_count[c*nwin + w]          : the number of those rows, uint32    (ops & SPRINTZ_MOM_COUNT)
+ *   d_sum  [(c*nwin + w)*D + d]  : the sum of x_d, uint64              (ops & SPRINTZ_MOM_SUM)
+ *   d_sumsq[(c*nwin + w)*D + d]  : the sum of x_d^2, uint64            (ops & SPRINTZ_MOM_SUMSQ)
+ *   d_cross[(c*nwin + w)*D + d]  : the sum of x_d * x_ref, uint64      (ops & SPRINTZ_MOM_CROSS; ref = ref_col; for d = ref the sumsq entry)
+ * on the unsigned values decompress_batch writes under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK included).  All of them are
+ * exact: x * y <= (2^16 - 1)^2 < 2^32, a chunk slot has fewer than 2^30 rows (chunk_len <= 2^30), so every sum of a chunk is below
+ * 2^62 and no 64-bit entry wraps.  A window with no selected row holds zeros.  Every entry of every selected output is written, one
+ * writer an entry, no atomics: the output is deterministic.  An output not selected may be NULL and is not touched.
+ * d_rets (optional) as in aggregate_rows: elements decoded, or < 0 for a damaged chunk, whose own entries are then unspecified --
+ * nothing is written outside them, and every other chunk is exact.
+ * The call does not read the mask on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST
+ * (csrc/decode_fast.h: the shapes the windowed query takes there) or DEC_GENERIC (csrc/decode_kernel.h: everything else, the
+ * low-dimension layouts included -- csrc/decode_uni.h is not taught the mode).
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, a window_rows that
+ * is not a multiple of 8 >= 8, ops outside 1..15, a selected output that is NULL, a NULL d_comp / d_offsets, d_count not aligned to
+ * 4 bytes, d_sum / d_sumsq / d_cross / d_rets not aligned to 8 bytes, ref_col >= ndims where SPRINTZ_MOM_CROSS is selected (ref_col is
+ * ignored otherwise), an unknown flag; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0
+ * returns 0 and launches nothing. */
+#define SPRINTZ_MOM_COUNT 1u
+#define SPRINTZ_MOM_SUM 2u
+#define SPRINTZ_MOM_SUMSQ 4u
+#define SPRINTZ_MOM_CROSS 8u
+int sprintz_mi355x_moments_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */, uint32_t window_rows,
+                                uint32_t ops, uint32_t ref_col, uint32_t flags, uint32_t* d_count, uint64_t* d_sum,
+                                uint64_t* d_sumsq, uint64_t* d_cross, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

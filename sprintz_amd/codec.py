@@ -813,6 +813,176 @@ class ChunkedCodec:
         half = 1 << 15
         return (((out.t().contiguous() + half) % (1 << 16)) - half).to(torch.int16).view(torch.uint16)
 
+    _MOM_INT = ("count", "sum", "sumsq", "cross")
+    _MOM_DERIVED = ("mean", "var", "std", "cov", "corr")
+
+    def moments_rows(self, batch, mask=None, window_rows=None, ref=None, ops=("count", "sum", "sumsq"), general_layout=False, per_chunk=False,
+                     check=True, ddof=0):
+        """Per-window count, sum, sum of squares and sum of products with the column `ref` of the rows a mask names -- and the mean,
+        variance, standard deviation, covariance and correlation that follow from them -- fused into the decode (one launch; only the
+        results leave the chip).
+
+        mask, window_rows, general_layout, per_chunk, check: as in aggregate_rows, except that mask=None means every existing row.
+        per_chunk=True: the kernel's chunk-relative windows, {op: [nchunks, nwin, ndims]} and "count": [nchunks, nwin]; default: windows
+        over the batch's rows, {op: [nwindows, ndims]}, "count": [nwindows], which needs the chunk's rows to be a multiple or a divisor
+        of window_rows.
+        ops: any of the exact integer sums "count" (n), "sum" (S = sum x), "sumsq" (Q = sum x^2), "cross" (P = sum x * x_ref) -- int64 --
+        and of the derived "mean", "var", "std", "cov" (with x_ref), "corr" (with x_ref) -- float64.  "cross", "cov" and "corr" need
+        ref.  ddof (0 or 1) divides var / std / cov by n - ddof.  A window with no selected row holds zeros; derived values are NaN
+        where n == 0 or n <= ddof, and corr also where either variance is 0.
+
+        Derived values are NOT formed as n Q - S^2 in float64: that difference reaches 2^94 and cancels.  With the integer pivot
+        m = S // n and r = S - n m (0 <= r < n),
+            C = Q - 2 m S + n m^2 = sum (x - m)^2
+        in wrapping int64 arithmetic on the device: intermediates may wrap, but two's-complement arithmetic is exact modulo 2^64 and
+        0 <= C <= Q < 2^63, so C is exact.  Then n var = C - r^2 / n, i.e.
+            var = C / (n - ddof) - (r / n) (r / (n - ddof))
+        in float64: the second term is at most 1 and the first is never smaller than the result, so nothing cancels badly.  Likewise
+        with two pivots, Cxy = P - m_x S_y - m_y S_x + n m_x m_y = sum (x - m_x)(y - m_y) (|Cxy| < 2^62: exact as a signed int64) and
+            cov = Cxy / (n - ddof) - (r_x / n) (r_y / (n - ddof)),     corr = cov_0 / sqrt(var_0(x) var_0(y))   (ddof = 0 throughout).
+        A variance is 0 exactly where C == 0.  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        ops = (ops,) if isinstance(ops, str) else tuple(ops)
+        unknown = set(ops) - set(self._MOM_INT) - set(self._MOM_DERIVED)
+        if unknown or not ops:
+            raise ValueError(f"ops must be a non-empty subset of count / sum / sumsq / cross / mean / var / std / cov / corr, not {ops}")
+        if ddof not in (0, 1):
+            raise ValueError("ddof must be 0 or 1")
+        D, n = self.ndims, batch.nchunks
+        if set(ops) & {"cross", "cov", "corr"}:
+            if ref is None:
+                raise ValueError('"cross", "cov" and "corr" need ref, the reference column')
+            if not 0 <= int(ref) < D:
+                raise ValueError(f"ref must be a column of the batch, 0 .. {D - 1}")
+        if self.chunk_len % D:
+            raise ValueError(f"moments_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        R = self.chunk_len // D
+        MB = -(-R // 8)
+        r8 = MB * 8
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
+                raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
+            mask = mask.contiguous()
+        W = R if window_rows is None else int(window_rows)
+        if W < 1:
+            raise ValueError("window_rows must be positive")
+        fold = 1
+        if per_chunk:
+            kw = r8 if window_rows is None else W
+        elif W % R == 0:
+            kw, fold = r8, W // R                           # one window a chunk (any multiple of 8 >= R), folded below
+        elif R % W == 0:
+            kw = W
+        else:
+            raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: use per_chunk=True")
+        nwin = -(-R // kw) if kw > 0 else 0
+        want = set(ops) & set(self._MOM_INT)
+        if "mean" in ops:
+            want |= {"count", "sum"}
+        if set(ops) & {"var", "std"}:
+            want |= {"count", "sum", "sumsq"}
+        if "cov" in ops:
+            want |= {"count", "sum", "cross"}
+        if "corr" in ops:
+            want |= {"count", "sum", "sumsq", "cross"}
+        bits = (_lib.MOM_COUNT if "count" in want else 0) | (_lib.MOM_SUM if "sum" in want else 0) | (_lib.MOM_SUMSQ if "sumsq" in want else 0) | \
+               (_lib.MOM_CROSS if "cross" in want else 0)
+        res = {k: torch.empty((n, nwin, D), dtype=torch.int64, device=self.device) for k in ("sum", "sumsq", "cross") if k in want}
+        cnt32 = torch.empty((n, nwin), dtype=torch.int32, device=self.device) if "count" in want else None
+        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        with self._on():
+            _lib.check(_lib.moments_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                         self.chunk_len, D, mask.data_ptr() if mask is not None else None, kw, bits,
+                                         int(ref) if "cross" in want else 0, _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                         cnt32.data_ptr() if cnt32 is not None else None,
+                                         res["sum"].data_ptr() if "sum" in res else None,
+                                         res["sumsq"].data_ptr() if "sumsq" in res else None,
+                                         res["cross"].data_ptr() if "cross" in res else None,
+                                         rets.data_ptr() if rets is not None else None, self._stream()))
+        if check and n:
+            bad = (rets < 0).nonzero()
+            if bad.numel():
+                c = int(bad[0, 0].item())
+                raise _lib.SprintzError(int(rets[c].item()), f"moments_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if cnt32 is not None:
+            res["count"] = cnt32.to(torch.int64)
+        if per_chunk:
+            out = res
+        else:
+            rows = -(-batch.total_len // D)
+            nw = -(-rows // W)
+            if fold == 1:                                   # chunk windows are global windows: chunk c holds rows [c R, (c+1) R)
+                out = {k: (v.reshape(n * nwin) if k == "count" else v.reshape(n * nwin, D))[:nw] for k, v in res.items()}
+            else:                                           # `fold` consecutive chunks a window: integer sums add
+                pad = nw * fold - n
+                out = {}
+                for k, v in res.items():
+                    if k == "count":
+                        out[k] = torch.cat([v.reshape(n), v.new_zeros(pad)]).reshape(nw, fold).sum(dim=1)
+                    else:
+                        out[k] = torch.cat([v.reshape(n, D), v.new_zeros((pad, D))]).reshape(nw, fold, D).sum(dim=1)
+        if set(ops) & set(self._MOM_DERIVED):
+            f64 = torch.float64
+            cnt = out["count"].unsqueeze(-1)                # [..., 1]
+            n1 = cnt.clamp(min=1)
+            nf = cnt.to(f64)
+            nd = (cnt - ddof).to(f64)
+            S = out["sum"]
+            m = S // n1                                     # the integer pivot, and what it leaves: 0 <= r < n
+            r = S - cnt * m
+            nan = torch.full((), float("nan"), dtype=f64, device=self.device)
+
+            def centred2():                                 # C = sum (x - m)^2, exact (see above)
+                return out["sumsq"] - 2 * m * S + cnt * m * m
+
+            def centred_xy():                               # Cxy = sum (x - m_x)(x_ref - m_ref), exact
+                j = int(ref)
+                return out["cross"] - m * S[..., j:j + 1] - m[..., j:j + 1] * S + cnt * m * m[..., j:j + 1]
+
+            if "mean" in ops:
+                out["mean"] = torch.where(cnt > 0, S.to(f64) / nf, nan)
+            if set(ops) & {"var", "std"}:
+                var = centred2().to(f64) / nd - (r.to(f64) / nf) * (r.to(f64) / nd)
+                var = torch.where(cnt > ddof, var, nan)
+                if "var" in ops:
+                    out["var"] = var
+                if "std" in ops:
+                    out["std"] = var.clamp(min=0.0).sqrt()   # (a variance below its own rounding error may come out as -1e-16)
+            if "cov" in ops:
+                j = int(ref)
+                rf = r.to(f64)
+                cov = centred_xy().to(f64) / nd - (rf / nf) * (rf[..., j:j + 1] / nd)
+                out["cov"] = torch.where(cnt > ddof, cov, nan)
+            if "corr" in ops:
+                j = int(ref)
+                rf = r.to(f64)
+                C = centred2()
+                v0 = C.to(f64) / nf - (rf / nf) * (rf / nf)
+                c0 = centred_xy().to(f64) / nf - (rf / nf) * (rf[..., j:j + 1] / nf)
+                ok = (cnt > 0) & (C != 0) & (C[..., j:j + 1] != 0)
+                out["corr"] = torch.where(ok, c0 / (v0 * v0[..., j:j + 1]).sqrt(), nan)
+        return {k: v for k, v in out.items() if k in ops}
+
+    def moments_where(self, batch, lo, hi, mode="all", **kw):
+        """SELECT count(*), sum(x), var(x), corr(x, y), ... WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and
+        moments_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: moments_rows' other arguments."""
+        if self.chunk_len % self.ndims:
+            raise ValueError(f"moments_where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
+        return self.moments_rows(batch, mask=f["mask"], **kw)
+
+    def corr(self, batch, cols=None, mask=None, window_rows=None):
+        """The correlation matrix of the columns `cols` (default: all) per window, straight from the compressed data: [nwindows,
+        len(cols), len(cols)] float64, one moments_rows launch per reference column.  Symmetric, 1 on the diagonal; NaN where a window
+        is empty or one of the two columns is constant in it."""
+        torch = self.torch
+        cols = list(range(self.ndims)) if cols is None else [int(c) for c in cols]
+        if not cols or any(not 0 <= c < self.ndims for c in cols):
+            raise ValueError(f"cols must be columns of the batch, 0 .. {self.ndims - 1}")
+        idx = torch.tensor(cols, dtype=torch.int64, device=self.device)
+        parts = [self.moments_rows(batch, mask=mask, window_rows=window_rows, ref=c, ops=("corr",))["corr"].index_select(-1, idx) for c in cols]
+        return torch.stack(parts, dim=-1)
+
     def read_rows(self, batch, lo, hi):
         """batch rows [lo, hi) -> [hi - lo, ndims]: one range of gather_rows, its chunks decoded side by side in the same launch"""
         lo, hi = int(lo), int(hi)

@@ -293,6 +293,7 @@ hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, 
 {
     const auto unit = q == kQueryGather ? decode_generic_gather : q == kQueryFilter ? decode_generic_filter : q == kQuerySelect ? decode_generic_select
                     : q == kQueryAggregate ? decode_generic_aggregate : q == kQueryHistogram ? decode_generic_histogram
+                    : q == kQueryMoments ? decode_generic_moments
                     : w == 8 ? decode_generic_w8 : decode_generic_w16;
     return unit(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
@@ -300,6 +301,7 @@ hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int
 {
     const auto unit = q == kQueryGather ? decode_fast_gather : q == kQueryFilter ? decode_fast_filter : q == kQuerySelect ? decode_fast_select
                     : q == kQueryAggregate ? decode_fast_aggregate : q == kQueryHistogram ? decode_fast_histogram
+                    : q == kQueryMoments ? decode_fast_moments
                     : w == 8 ? decode_fast_w8 : decode_fast_w16;
     return unit(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
@@ -332,7 +334,7 @@ int check_common(int codec, int esz, uint16_t ndims)
     return 0;
 }
 
-// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows) check alike, behind check_common; the refusals that
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
                  const char* rle_only, const char* op = nullptr)
@@ -390,7 +392,7 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryHistogram (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryMoments (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -400,6 +402,7 @@ struct QuerySpec {
     SelectArgs select{};        // kQuerySelect
     AggregateArgs agg{};        // kQueryAggregate (with win)
     HistogramArgs hist{};       // kQueryHistogram (table_off and wg_chunks come from the plan)
+    MomentArgs mom{};           // kQueryMoments (with win)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -470,6 +473,7 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.hist = qs.hist;
     a.hist.table_off = p.hist_table_off;
     a.hist.wg_chunks = p.hist_wg_chunks;
+    a.mom = qs.mom;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -1741,6 +1745,45 @@ int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp,
     qs.win.max = (ops & SPRINTZ_AGG_MAX) ? d_max : nullptr;
     qs.win.sum = (ops & SPRINTZ_AGG_SUM) ? d_sum : nullptr;
     qs.agg = AggregateArgs{d_mask, (ops & SPRINTZ_AGG_COUNT) ? d_count : nullptr, (rows + 7) / 8};
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- moments rows
+int sprintz_mi355x_moments_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t window_rows,
+                                uint32_t ops, uint32_t ref_col, uint32_t flags, uint32_t* d_count, uint64_t* d_sum,
+                                uint64_t* d_sumsq, uint64_t* d_cross, int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "moments_rows: more than 512 columns", "moments_rows: the RLE codecs (delta, xff) only",
+                           "moments_rows"))) return rc;
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "moments_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if (window_rows < 8 || window_rows % 8) return fail(SPRINTZ_E_INVALID, "moments_rows: window_rows must be a multiple of 8, at least 8");
+    if (ops < 1 || ops > 15) return fail(SPRINTZ_E_INVALID, "moments_rows: ops must be a non-empty OR of SPRINTZ_MOM_COUNT / _SUM / _SUMSQ / _CROSS");
+    if (((ops & SPRINTZ_MOM_COUNT) && !d_count) || ((ops & SPRINTZ_MOM_SUM) && !d_sum) || ((ops & SPRINTZ_MOM_SUMSQ) && !d_sumsq) || ((ops & SPRINTZ_MOM_CROSS) && !d_cross))
+        return fail(SPRINTZ_E_INVALID, "moments_rows: a selected op without its output buffer");
+    if (((ops & SPRINTZ_MOM_COUNT) && (uintptr_t)d_count % 4) || ((ops & SPRINTZ_MOM_SUM) && (uintptr_t)d_sum % 8) || ((ops & SPRINTZ_MOM_SUMSQ) && (uintptr_t)d_sumsq % 8) ||
+        ((ops & SPRINTZ_MOM_CROSS) && (uintptr_t)d_cross % 8) || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "moments_rows: count must be aligned to 4 bytes, sum, sumsq, cross and d_rets to 8");
+    if ((ops & SPRINTZ_MOM_CROSS) && ref_col >= ndims) return fail(SPRINTZ_E_INVALID, "moments_rows: ref_col must be a column of the batch");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    const uint32_t rows = chunk_len / ndims;
+    QuerySpec qs;
+    qs.q = kQueryMoments;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.win.rows = window_rows;
+    qs.win.count = (rows + window_rows - 1) / window_rows;
+    qs.win.ops = 0;
+    qs.win.sum = (ops & SPRINTZ_MOM_SUM) ? d_sum : nullptr;
+    qs.mom.mask = d_mask;
+    qs.mom.mask_stride = (rows + 7) / 8;
+    qs.mom.count = (ops & SPRINTZ_MOM_COUNT) ? d_count : nullptr;
+    qs.mom.sumsq = (ops & SPRINTZ_MOM_SUMSQ) ? d_sumsq : nullptr;
+    qs.mom.cross = (ops & SPRINTZ_MOM_CROSS) ? d_cross : nullptr;
+    qs.mom.ref = (ops & SPRINTZ_MOM_CROSS) ? ref_col : 0u;
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }

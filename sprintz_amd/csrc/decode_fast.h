@@ -140,6 +140,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // mask bytes come through select's read-ahead window.  The workgroup's lanes meet at two barriers, so no lane leaves early.
     constexpr bool HIST = Q == kQueryHistogram;
     static_assert(!HIST || (!CM && !SPLIT && DS == 0), "histogram: plain mappings");
+    // MOM (sprintz_mi355x_moments_rows): per window the number of rows the caller's mask names (or of every row) and per column their
+    // sum, sum of squares and sum of products with ONE reference column.  That column is decoded in one slot of one lane, so a lane
+    // keeps the block's rows of all its slots and forms the products behind the slot loop, when the reference lane can hand its 8
+    // rows over (decode_ops.h: moments_ref_rows).  Windows, mask read-ahead and run shortcut are aggregate's.
+    constexpr bool MOM = Q == kQueryMoments;
+    static_assert(!MOM || (!CM && !SPLIT && DS == 0), "moments: plain mappings");
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -358,6 +364,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t arow[8];
     uint32_t acnt = 0;
     uint8_t* fmb = nullptr;
+    // moments rows: the block's rows of every slot of the lane, and the lane's accumulators (acnt: the window's selected rows)
+    uint32_t mrow[CPL][8];
+    MomentAcc macc[CPL];
+    if constexpr (MOM) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) macc[k] = MomentAcc{0, 0, 0};
+    }
     // histogram rows: the lane's columns and where the samples are counted
     HistCol hcol[CPL];
     HistCtx hctx{};
@@ -376,6 +389,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
         } else if constexpr (AGG || HIST) {                // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
+        } else if constexpr (MOM) {                        // every slot's rows wait for q_window: the reference column's may come last
+            mrow[k][i] = pv[k];
         } else if constexpr (Q != 0) {
             if constexpr (W == 16) {
                 asm("v_max_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
@@ -409,6 +424,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         } else if constexpr (HIST) {                       // (a lane column past the last one counts nothing)
             if (sm != 0 && col_ok[k]) hist_rows8<W>(hctx, hcol[k], arow, sm);
+        } else if constexpr (MOM) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
     // after every block of 8 rows: the group's lanes combine, one lane stores the block's byte (fb < chunk_len / blk_elems <=
@@ -430,6 +446,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         wi++;
         wleft = a.win.rows;
     };
+    auto mom_flush_all = [&]() {                           // the same for the moments' entries
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (col_ok[k]) moments_flush(a, (wbase + wi) * (uint64_t)D + (uint64_t)genk[k], macc[k]);
+        moments_count_flush(a, wbase + wi, acnt, lane_d);
+        wi++;
+        wleft = a.win.rows;
+    };
     auto q_window = [&]() {                                // after every block of 8 rows
         if constexpr (Q == kQueryWindow) {
             wleft -= 8;
@@ -442,6 +466,21 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             if (wleft == 0) win_flush_all();
         }
         if constexpr (HIST) fb++;
+        if constexpr (MOM) {
+            // sm is the group's: every lane of it takes part in the exchange, a lane whose columns are past the last one too (its
+            // own sums are never flushed)
+            if (sm != 0) {
+                uint32_t xr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                const bool cross = a.mom.cross != nullptr;
+                if (cross) moments_ref_rows<W, CPL>(a.mom.ref, DP, [&](int k, int i) { return mrow[k][i]; }, xr);
+#pragma unroll
+                for (int k = 0; k < CPL; k++) moments_rows8<W>(macc[k], [&](int i) { return mrow[k][i]; }, xr, sm, cross);
+            }
+            acnt += (uint32_t)__popc(sm);
+            fb++;
+            wleft -= 8;
+            if (wleft == 0) mom_flush_all();
+        }
     };
     uint32_t ovo = 0;                                      // output cursor (byte offset from this wave's out_base)
     // gather: the chunk-relative row of the next block, and the row of the block each of this lane's 16-byte store pieces lies in
@@ -467,6 +506,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto sel_stride = [&]() -> uint32_t {
         if constexpr (AGG) return a.agg.mask_stride;
         else if constexpr (HIST) return a.hist.mask_stride;
+        else if constexpr (MOM) return a.mom.mask_stride;
         else return a.select.mask_stride;
     };
     auto sel_byte = [&](uint32_t b) -> uint32_t {
@@ -713,6 +753,34 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             return;
         }
+        if constexpr (MOM && !FIRE) {
+            // a delta run repeats the previous row 8 len times: per window it touches, c = the selected rows among them -- the set bits of
+            // the run's mask bytes in that window, spread over the group's lanes; all of them without a mask -- and each sum takes its
+            // term times c.  The reference column's value is one exchange a run.  (The bytes lie inside the chunk's: the run fits the slot.)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            const uint32_t xr = moments_ref_value<W, CPL>(a.mom.ref, DP, pv);
+            uint32_t blocks = len;
+            while (blocks > 0) {
+                const uint32_t nb = blocks < (wleft >> 3) ? blocks : (wleft >> 3);
+                uint32_t c = 8u * nb;
+                if (smb) {
+                    c = 0;
+                    for (uint32_t j = (uint32_t)lane_d; j < nb; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
+                    c = group_sum(c, DP);
+                }
+                if (c != 0) {
+#pragma unroll
+                    for (int k = 0; k < CPL; k++) moments_value(macc[k], pv[k] & MASK, xr, c);
+                    acnt += c;
+                }
+                blocks -= nb;
+                fb += nb;
+                wleft -= 8u * nb;
+                if (wleft == 0) mom_flush_all();
+            }
+            return;
+        }
         if constexpr (HIST && !FIRE) {
             // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows -- the set
             // bits of its mask bytes, spread over the group's lanes; 8 len without a mask.  (The bytes lie inside the chunk's: the run
@@ -762,7 +830,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
             }
             if constexpr (AGG) sm = sel_byte(fb);          // (a FIRE run is replayed for its state, block by block, as the window mode does)
-            if constexpr (HIST) sm = smb ? sel_byte(fb) : 0xffu;
+            if constexpr (HIST || MOM) sm = smb ? sel_byte(fb) : 0xffu;
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -884,7 +952,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
         if constexpr (SELECT || AGG) sm = sel_byte(fb);    // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
-        if constexpr (HIST) sm = smb ? sel_byte(fb) : 0xffu;
+        if constexpr (HIST || MOM) sm = smb ? sel_byte(fb) : 0xffu;
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -1002,6 +1070,16 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             wi = 0;
             wleft = a.win.rows;
             wbase = chunk * (uint64_t)a.win.count;
+        }
+        if constexpr (MOM) {
+#pragma unroll
+            for (int k = 0; k < CPL; k++) macc[k] = MomentAcc{0, 0, 0};
+            wi = 0;
+            wleft = a.win.rows;
+            wbase = chunk * (uint64_t)a.win.count;
+            fb = 0; sm = 0; acnt = 0;
+            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
+            smb = a.mom.mask ? a.mom.mask + chunk * (uint64_t)a.mom.mask_stride : nullptr;
         }
         if constexpr (Q == kQueryFilter) {
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
@@ -1200,6 +1278,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (!corrupt)
             aggregate_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
                                    [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (MOM) {
+        // fb blocks = 8 fb rows lie in front of the tail
+        if (!corrupt)
+            moments_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, macc, acnt, lane_d,
+                                 [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (HIST) {
         // fb blocks = 8 fb rows lie in front of the tail
         if (!corrupt)

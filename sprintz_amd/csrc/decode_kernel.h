@@ -135,6 +135,19 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         wleft = a.win.rows;
         wbase = chunk * (uint64_t)a.win.count;
     }
+    // moments rows (MOM): the lane's accumulators, the chunk's mask bytes (null: every row), the mask byte of the block being decoded and
+    // the selected rows of the window so far; the windows are the windowed query's
+    constexpr bool MOM = Q == kQueryMoments;
+    MomentAcc macc[CPL];
+    const uint8_t* mmb = nullptr;
+    uint32_t mm = 0xffu, mcnt = 0;
+    if constexpr (MOM) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) macc[k] = MomentAcc{0, 0, 0};
+        wleft = a.win.rows;
+        wbase = chunk * (uint64_t)a.win.count;
+        if (a.mom.mask) mmb = a.mom.mask + chunk * (uint64_t)a.mom.mask_stride;
+    }
     // filter rows: each lane's columns' bounds, loaded once; the group ORs its lanes' block masks with wave shuffles (groups of up to
     // 64 lanes, both layouts), lane 0 stores the block's byte -- runs are replayed block by block here, as the decode does
     FilterCol fc[CPL];
@@ -290,6 +303,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         // (block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride: checked above; all 8 rows of a block exist)
         if constexpr (Q == kQueryAggregate) am = amb[out_elems / blk_elems];
         if constexpr (HIST) hm = hmb ? (uint32_t)hmb[out_elems / blk_elems] : 0xffu;
+        if constexpr (MOM) mm = mmb ? (uint32_t)mmb[out_elems / blk_elems] : 0xffu;
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -331,6 +345,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     for (int i = 0; i < 8; i++) xs[i] = v[i][k];
                     hist_rows8<W>(hctx, hcol[k], xs, hm);
                 }
+            } else if constexpr (MOM) {          // (the products wait for the reference column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
 #pragma unroll
@@ -340,6 +355,27 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     bs += v[i][k];
                 }
                 qsum[k] += bs;
+            }
+        }
+        if constexpr (MOM) {
+            // the reference column's 8 rows come from the lane that decoded them -- every lane of the group takes part, mm is the group's --
+            // then each column's rows are multiplied and added; the block's 8 rows lie in one window: flush it when they complete it
+            if (mm != 0) {
+                uint32_t xr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                const bool cross = a.mom.cross != nullptr;
+                if (cross) moments_ref_rows<W, CPL>(a.mom.ref, DP, [&](int k, int i) { return v[i][k]; }, xr);
+#pragma unroll
+                for (int k = 0; k < CPL; k++) moments_rows8<W>(macc[k], [&](int i) { return v[i][k]; }, xr, mm, cross);
+            }
+            mcnt += (uint32_t)__popc(mm);
+            wleft -= 8;
+            if (wleft == 0) {
+#pragma unroll
+                for (int k = 0; k < CPL; k++)
+                    if (genk[k]) moments_flush(a, (wbase + wi) * (uint64_t)D + (uint64_t)colk[k], macc[k]);
+                moments_count_flush(a, wbase + wi, mcnt, lane_d);
+                wi++;
+                wleft = a.win.rows;
             }
         }
         if constexpr (Q == kQueryWindow || Q == kQueryAggregate) {       // the block's 8 rows lie in one window: flush it when they complete it
@@ -474,6 +510,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     } else if constexpr (Q == kQueryAggregate) {
         if (!corrupt) aggregate_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
                                              [&](uint32_t b) { return (uint32_t)amb[b]; });
+    } else if constexpr (MOM) {
+        if (!corrupt) moments_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, macc, mcnt, lane_d,
+                                           [&](uint32_t b) { return (uint32_t)mmb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) reduce_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, colk, genk, qmax, qsum);      // (out_elems is a multiple of 8*D)
     }

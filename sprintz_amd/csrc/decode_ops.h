@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate and histogram rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
+// aggregate, histogram and moments rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
 // its lane's columns (`col`, with `genuine` false for a lane column past the last one), its place in the group (`lane_d` of `DP`
 // lanes) and the mode's running state; decode_uni.h is the lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane
 // mapping -- how a block's rows reach the accumulators, the staging and the stores -- stays in that kernel.
@@ -72,6 +72,18 @@ struct HistogramArgs {
     uint32_t table_off;
     uint32_t wg_chunks;
 };
+// moments rows (Q == kQueryMoments; sprintz_mi355x_moments_rows): over the rows whose bits are set in chunk c's mask bytes mask[c *
+// mask_stride ...] (filter_rows' layout; no mask: every existing row), per chunk-relative window w (WindowArgs' rows and count) their
+// number in count[c * win.count + w] and, per column d at (c * win.count + w) * D + d, the sum of x_d in win.sum, of x_d^2 in sumsq and
+// of x_d * x_ref in cross.  An output that is null is not selected
+struct MomentArgs {
+    const uint8_t* mask;        // [nchunks][mask_stride], or null: a run-time, wave-uniform switch, as hist.mask is
+    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
+    uint32_t* count;            // optional (SPRINTZ_MOM_COUNT)
+    uint64_t* sumsq;            // optional (SPRINTZ_MOM_SUMSQ)
+    uint64_t* cross;            // optional (SPRINTZ_MOM_CROSS)
+    uint32_t ref;               // the reference column (< D; 0 where cross is null)
+};
 
 struct DecodeArgs {
     const uint8_t* comp;        // compressed bytes
@@ -113,6 +125,7 @@ struct DecodeArgs {
     SelectArgs select;
     AggregateArgs agg;
     HistogramArgs hist;
+    MomentArgs mom;
 };
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
@@ -365,6 +378,127 @@ __device__ __forceinline__ void hist_tail(const DecodeArgs& a, const HistCtx& c,
         for (int k = 0; k < CPL; k++)
             if (genuine[k]) hist_value<W>(c, h[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), 1u);
     }
+}
+
+// ---- moments rows.  Every value is an exact unsigned integer: a factor is below 2^16, so a product is below 2^32; a chunk slot has
+// fewer than 2^30 rows, so every sum of a chunk is below 2^62.  A lane keeps three 64-bit accumulators a column.
+struct MomentAcc { uint64_t sum, sumsq, cross; };
+// the reference column's 8 rows of a block, in every lane of the group: column lane * CPL + k lives in slot k of lane `lane`, so lane
+// ref / CPL hands over its slot ref % CPL.  at(k, i) is this lane's row i of slot k (garbage above bit W allowed); EVERY lane of the
+// group must come here -- a lane whose columns are all past the last one too.  (The slot is picked with wave-uniform AND masks: a
+// chain of selects on the slot number is turned into an indexed read of a copy of the rows in scratch memory.)
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void moments_ref_rows(uint32_t ref, int DP, F at, uint32_t (&xr)[8])
+{
+    const uint32_t slot = ref % (uint32_t)CPL;
+    const int lane = (int)(ref / (uint32_t)CPL);
+    uint32_t pick[CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; k++) pick[k] = slot == (uint32_t)k ? Elem<W>::MASK : 0u;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint32_t mine = at(0, i) & pick[0];
+#pragma unroll
+        for (int k = 1; k < CPL; k++) mine |= at(k, i) & pick[k];
+        xr[i] = (uint32_t)__shfl((int)mine, lane, DP);
+    }
+}
+// one value of the reference column, the same way (a delta run's constant row)
+template <int W, int CPL>
+__device__ __forceinline__ uint32_t moments_ref_value(uint32_t ref, int DP, const uint32_t (&pv)[CPL])
+{
+    const uint32_t slot = ref % (uint32_t)CPL;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) mine |= pv[k] & (slot == (uint32_t)k ? Elem<W>::MASK : 0u);
+    return (uint32_t)__shfl((int)mine, (int)(ref / (uint32_t)CPL), DP);
+}
+// a column's 8 rows of one block; bit i of m: row i is selected.  x(i) may carry garbage above bit W, xr is clean; `cross` is
+// wave-uniform (is the output selected?)
+template <int W, typename F>
+__device__ __forceinline__ void moments_rows8(MomentAcc& acc, F x, const uint32_t (&xr)[8], uint32_t m, bool cross)
+{
+    uint32_t t[8], bs = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        t[i] = x(i) & (((m >> i) & 1u) ? Elem<W>::MASK : 0u);
+        bs += t[i];
+    }
+    acc.sum += bs;
+    if constexpr (W == 8) {
+        uint32_t bq = 0, bx = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) bq += t[i] * t[i];
+        acc.sumsq += bq;
+        if (cross) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) bx += t[i] * xr[i];
+            acc.cross += bx;
+        }
+    } else {
+        // (each product is one 64-bit multiply-add, v_mad_u64_u32; profiles/moments_rows.txt has what else was tried)
+#pragma unroll
+        for (int i = 0; i < 8; i++) acc.sumsq += (uint64_t)t[i] * t[i];
+        if (cross) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) acc.cross += (uint64_t)t[i] * xr[i];
+        }
+    }
+}
+// one value x that `c` selected rows hold, beside the reference column's xr (a delta run's constant row: c < 2^30; a row of the tail)
+__device__ __forceinline__ void moments_value(MomentAcc& acc, uint32_t x, uint32_t xr, uint32_t c)
+{
+    acc.sum += (uint64_t)x * c;
+    acc.sumsq += (uint64_t)(x * x) * c;
+    acc.cross += (uint64_t)(x * xr) * c;
+}
+// one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the accumulators start over from 0
+__device__ __forceinline__ void moments_flush(const DecodeArgs& a, uint64_t idx, MomentAcc& acc)
+{
+    if (a.win.sum) a.win.sum[idx] = acc.sum;
+    if (a.mom.sumsq) a.mom.sumsq[idx] = acc.sumsq;
+    if (a.mom.cross) a.mom.cross[idx] = acc.cross;
+    acc = MomentAcc{0, 0, 0};
+}
+// one window's count leaves with the window's other entries (one lane of the group), and starts over
+__device__ __forceinline__ void moments_count_flush(const DecodeArgs& a, uint64_t widx, uint32_t& cnt, int lane_d)
+{
+    if (a.mom.count && lane_d == 0) a.mom.count[widx] = cnt;
+    cnt = 0;
+}
+// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
+// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  Window `wi` of the chunk (the first of
+// them at entry `wbase`) still takes `wleft` rows; a window edge can fall inside the tail.  Then the partial window leaves, and the
+// zeros of the slot's windows past the data.  mask_at(b) is the chunk's mask byte b (asked only where there is a mask).  The reference
+// column's element is read from the tail itself: no lane needs another's.
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void moments_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0, const int (&col)[CPL],
+                                             const bool (&genuine)[CPL], uint64_t wbase, uint32_t wi, uint32_t wleft, MomentAcc (&acc)[CPL], uint32_t cnt,
+                                             int lane_d, F mask_at)
+{
+    const uint32_t nfull = remaining / D;
+    uint32_t w = wi, left = wleft;
+    auto flush = [&]() {
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) moments_flush(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], acc[k]);
+        moments_count_flush(a, wbase + w, cnt, lane_d);
+        w++;
+        left = a.win.rows;
+    };
+    uint32_t m = 0xffu;
+    for (uint32_t r = 0; r < nfull; r++) {
+        if (left == 0) flush();
+        left--;
+        if ((r & 7u) == 0 && a.mom.mask) m = mask_at((row0 + r) >> 3);
+        if (!((m >> (r & 7u)) & 1u)) continue;
+        cnt++;
+        const uint32_t xr = tail_elem<W>(t, r * D + a.mom.ref);
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) moments_value(acc[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), xr, 1u);
+    }
+    while (w < a.win.count) flush();
 }
 
 // ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the

@@ -27,13 +27,14 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 5 = filter: one bit per row -- does the row satisfy the per-column bounds? -- and the chunk's count of them, reduce only;
 // 6 = select: a chunk is decoded once and only the rows whose bit is set in the caller's mask are stored, packed densely behind the chunk's base;
 // 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only;
-// 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only
+// 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only;
+// 9 = moments: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names (or of every row), reduce only
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7, kQueryHistogram = 8;
+              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
-    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram;
+    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments;
 }
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB

@@ -268,8 +268,8 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram: those shapes go to the generic kernel)
-    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
+    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments: those shapes go to the generic kernel)
+    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
     if (s.q == kQueryHistogram) {                              // nothing is staged: the table is the launch's LDS
         p.hist_wg_chunks = hist_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D);
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, hist_bytes);
