@@ -51,7 +51,7 @@ extern "C" {
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
- *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_* */
+ *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -155,7 +155,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -668,6 +668,48 @@ int sprintz_mi355x_moments_rows(int codec, int elem_bytes, const void* d_comp, c
                                 uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */, uint32_t window_rows,
                                 uint32_t ops, uint32_t ref_col, uint32_t flags, uint32_t* d_count, uint64_t* d_sum,
                                 uint64_t* d_sumsq, uint64_t* d_cross, int64_t* d_rets, void* hip_stream);
+/* Group-by rows: per bin of ONE key column's value, the number of the rows a mask names and their per-column sums -- what conditional
+ * means ("mean of every sensor per value of the state channel", a profile plot, a per-class mean where one column is a label) rest on --
+ * fused into the decode: only the tables leave the chip.
+ *
+ * The batch, the flags, the mask and d_rets are sprintz_mi355x_histogram_rows' (flags: SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else;
+ * chunk_len % ndims == 0 is required).  With D = ndims, R = chunk_len / D, MB = ceil(R / 8), W = 8 * elem_bytes:
+ *   d_mask : [nchunks][MB] bytes in the layout filter_rows writes, or NULL: every existing row.  A bit is ignored if its row does not
+ *            exist: rows >= R in the last byte, rows past what the chunk's stream holds, and a partial last row is not a row.
+ *   key_col, key_lo, shift, nbins : a selected row whose column key_col holds x has b = ((x - key_lo) mod 2^W) >> shift.  If b >= nbins
+ *            the whole row is dropped; otherwise the row belongs to bin b.  key_col < D, key_lo < 2^W, 0 <= shift < W,
+ *            1 <= nbins <= 2^(W - shift).
+ *   table_chunks : H.  Chunks [t*H, (t+1)*H) share result table t, ntables = ceil(nchunks / H); 0: the whole batch is one table.
+ *   d_count[t*nbins + b]          : the number of rows of table t in bin b, uint64                  (ops & SPRINTZ_GBY_COUNT)
+ *   d_sum  [(t*nbins + b)*D + d]  : the sum of x_d over those rows, uint64 (the key column's too)   (ops & SPRINTZ_GBY_SUM)
+ *            bin-major: the D sums of one bin lie side by side.  The values are those decompress_batch writes under the same options
+ *            (SPRINTZ_OPT_REF_DECODER_QUIRK included).  The call zeroes the selected outputs on the stream, then adds: every entry is
+ *            written and nothing else is.  Integer adds: the result is exact and the same on every run although atomics are used.  A sum
+ *            is below 2^16 * 2^30 * H (values below 2^16, fewer than 2^30 rows a chunk, H chunks a table; the batch's chunks for H = 0):
+ *            no 64-bit entry wraps in a table of up to 2^18 chunks of any shape.  An output not selected may be NULL and is not touched.
+ * One call holds at most SPRINTZ_GBY_MAX_COUNTERS = 16384 table entries, nbins * (D + 1) (a workgroup's table in LDS).  A wider request
+ * is split by the caller with key_lo: bins [k*nbins, (k+1)*nbins) of the same shift are one call with key_lo + ((k*nbins) << shift) in
+ * place of key_lo -- rows outside a call's bins are dropped, so the calls' results lie side by side.
+ * d_rets (optional) as in histogram_rows: elements decoded, or < 0 for a damaged chunk, whose own table is then unspecified -- nothing
+ * is written outside the outputs, and every other table is exact.
+ * The call does not read the mask on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST
+ * (csrc/decode_fast.h: the shapes the windowed query takes there whose table fits the launch's LDS next to the groups' carves) or
+ * DEC_GENERIC (csrc/decode_kernel.h: everything else, the low-dimension layouts included -- csrc/decode_uni.h is not taught the mode).
+ * A workgroup adds in a table of 32-bit entries, so the table is used only where the rows of a workgroup's chunks times 2^W - 1 fit 32
+ * bits.  A workgroup of any other shape, and one whose chunks lie in more than one table (small H), adds every row to d_count / d_sum
+ * directly: correct, and much slower.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, key_col >= ndims,
+ * key_lo >= 2^W, shift >= W, nbins outside 1..2^(W - shift), ops == 0 or an unknown op bit, a selected output that is NULL, a NULL
+ * d_comp / d_offsets, d_count / d_sum / d_rets not aligned to 8 bytes, an unknown flag, more than 2^40 entries of d_sum (ntables *
+ * nbins * D); SPRINTZ_E_UNSUPPORTED for more than 512 columns, for the non-RLE codecs and for nbins * (ndims + 1) above
+ * SPRINTZ_GBY_MAX_COUNTERS.  nchunks == 0 returns 0 and launches nothing. */
+#define SPRINTZ_GBY_COUNT 1u
+#define SPRINTZ_GBY_SUM   2u
+#define SPRINTZ_GBY_MAX_COUNTERS 16384u      /* nbins * (ndims + 1) */
+int sprintz_mi355x_groupby_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */,
+                                uint32_t key_col, uint32_t key_lo, uint32_t shift, uint32_t nbins, uint64_t table_chunks,
+                                uint32_t ops, uint32_t flags, uint64_t* d_count, uint64_t* d_sum, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -971,6 +971,77 @@ class ChunkedCodec:
         f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
         return self.moments_rows(batch, mask=f["mask"], **kw)
 
+    def groupby_rows(self, batch, key, nbins=256, key_lo=0, shift=None, mask=None, ops=("count", "sum"), chunks_per_table=0, general_layout=False,
+                     check=True):
+        """SELECT bin(x_key), count(*), sum(x_0), ..., sum(x_{D-1}) WHERE mask GROUP BY bin(x_key), fused into the decode (one launch; only
+        the tables leave the chip): what conditional means rest on.
+
+        key: the key column.  A row the mask names (mask: uint8 [nchunks, MB] in filter_rows' layout, MB = ceil(R / 8), R = chunk_len /
+        ndims: chunk_len must be a multiple of ndims; None: every row; bits of rows that do not exist are ignored) whose key column holds
+        x belongs to bin ((x - key_lo) mod 2^W) >> shift if that is below nbins, and is dropped otherwise.  shift=None: the one that
+        makes nbins bins cover the element range, W - ceil(log2(nbins)) (W - 1 for one bin).  nbins * (ndims + 1) is at most 16384 a
+        call: split wider requests with key_lo.
+        chunks_per_table = H: chunks [t H, (t + 1) H) share table t; 0: one table for the batch.
+        ops: "count", "sum" or both.  -> {"count": int64 [ntables, nbins], "sum": int64 [ntables, nbins, ndims]} and, where both are
+        selected, "mean": float64 sum / count, NaN where count is 0.  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        D, n, W = self.ndims, batch.nchunks, 8 * self.esz
+        ops = (ops,) if isinstance(ops, str) else tuple(ops)
+        if not ops or set(ops) - {"count", "sum"}:
+            raise ValueError(f'ops must be a non-empty subset of "count" / "sum", not {ops}')
+        if self.chunk_len % D:
+            raise ValueError(f"groupby_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        key, nbins, key_lo, H = int(key), int(nbins), int(key_lo), int(chunks_per_table)
+        if not 0 <= key < D:
+            raise ValueError(f"key must be a column of the batch, 0 .. {D - 1}")
+        if nbins < 1 or H < 0:
+            raise ValueError("nbins must be positive and chunks_per_table must not be negative")
+        if not 0 <= key_lo < (1 << W):
+            raise ValueError(f"key_lo must be in 0..{(1 << W) - 1}")
+        if shift is None:
+            shift = min(max(W - max(nbins - 1, 0).bit_length(), 0), W - 1)
+        shift = int(shift)
+        R = self.chunk_len // D
+        MB = -(-R // 8)
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
+                raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
+            mask = mask.contiguous()
+        ntables = (-(-n // H) if H else 1) if n else 0
+        out = {}
+        if "count" in ops:
+            out["count"] = torch.empty((ntables, nbins), dtype=torch.int64, device=self.device)
+        if "sum" in ops:
+            out["sum"] = torch.empty((ntables, nbins, D), dtype=torch.int64, device=self.device)
+        if n:
+            rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+            with self._on():
+                _lib.check(_lib.groupby_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                             self.chunk_len, D, mask.data_ptr() if mask is not None else None, key, key_lo, shift, nbins, H,
+                                             (_lib.GBY_COUNT if "count" in ops else 0) | (_lib.GBY_SUM if "sum" in ops else 0),
+                                             _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                             out["count"].data_ptr() if "count" in out else None,
+                                             out["sum"].data_ptr() if "sum" in out else None,
+                                             rets.data_ptr() if rets is not None else None, self._stream()))
+            if check:
+                bad = (rets < 0).nonzero()
+                if bad.numel():
+                    c = int(bad[0, 0].item())
+                    raise _lib.SprintzError(int(rets[c].item()), f"groupby_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if "count" in out and "sum" in out:
+            cnt = out["count"].unsqueeze(-1)
+            nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
+            out["mean"] = torch.where(cnt > 0, out["sum"].to(torch.float64) / cnt.to(torch.float64), nan)
+        return out
+
+    def groupby_where(self, batch, lo, hi, mode="all", **kw):
+        """SELECT bin(x_key), count(*), sum(x) WHERE <bounds> GROUP BY bin(x_key): filter_rows (its lo / hi / mode) and groupby_rows on its
+        mask -- two decode-speed launches; the batch is never materialised.  kw: groupby_rows' other arguments (key among them)."""
+        if self.chunk_len % self.ndims:
+            raise ValueError(f"groupby_where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
+        return self.groupby_rows(batch, mask=f["mask"], **kw)
+
     def corr(self, batch, cols=None, mask=None, window_rows=None):
         """The correlation matrix of the columns `cols` (default: all) per window, straight from the compressed data: [nwindows,
         len(cols), len(cols)] float64, one moments_rows launch per reference column.  Symmetric, 1 on the diagonal; NaN where a window

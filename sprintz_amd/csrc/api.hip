@@ -293,7 +293,7 @@ hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, 
 {
     const auto unit = q == kQueryGather ? decode_generic_gather : q == kQueryFilter ? decode_generic_filter : q == kQuerySelect ? decode_generic_select
                     : q == kQueryAggregate ? decode_generic_aggregate : q == kQueryHistogram ? decode_generic_histogram
-                    : q == kQueryMoments ? decode_generic_moments
+                    : q == kQueryMoments ? decode_generic_moments : q == kQueryGroupBy ? decode_generic_groupby
                     : w == 8 ? decode_generic_w8 : decode_generic_w16;
     return unit(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
@@ -301,7 +301,7 @@ hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int
 {
     const auto unit = q == kQueryGather ? decode_fast_gather : q == kQueryFilter ? decode_fast_filter : q == kQuerySelect ? decode_fast_select
                     : q == kQueryAggregate ? decode_fast_aggregate : q == kQueryHistogram ? decode_fast_histogram
-                    : q == kQueryMoments ? decode_fast_moments
+                    : q == kQueryMoments ? decode_fast_moments : q == kQueryGroupBy ? decode_fast_groupby
                     : w == 8 ? decode_fast_w8 : decode_fast_w16;
     return unit(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
@@ -334,7 +334,7 @@ int check_common(int codec, int esz, uint16_t ndims)
     return 0;
 }
 
-// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows) check alike, behind check_common; the refusals that
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
                  const char* rle_only, const char* op = nullptr)
@@ -392,7 +392,7 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryMoments (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryGroupBy (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -403,6 +403,7 @@ struct QuerySpec {
     AggregateArgs agg{};        // kQueryAggregate (with win)
     HistogramArgs hist{};       // kQueryHistogram (table_off and wg_chunks come from the plan)
     MomentArgs mom{};           // kQueryMoments (with win)
+    GroupByArgs gby{};          // kQueryGroupBy (table_off and wg_chunks come from the plan)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -437,6 +438,7 @@ Shape decode_shape(int codec, int esz, const void* d_comp, uint64_t nchunks, uin
     s.comp_lo = low4(d_comp); s.out_lo = low4(d_out);
     s.capacity = qs.select.capacity;
     s.hist_bins = qs.hist.nbins;
+    s.gby_bins = qs.gby.nbins;
     return s;
 }
 
@@ -474,6 +476,9 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.hist.table_off = p.hist_table_off;
     a.hist.wg_chunks = p.hist_wg_chunks;
     a.mom = qs.mom;
+    a.gby = qs.gby;
+    a.gby.table_off = p.gby_table_off;
+    a.gby.wg_chunks = p.gby_wg_chunks;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -1820,6 +1825,48 @@ int sprintz_mi355x_histogram_rows(int codec, int elem_bytes, const void* d_comp,
     const Plan p = plan_decode(decode_shape(codec, elem_bytes, d_comp, nchunks, chunk_len, ndims, nullptr, 0, qs), snapshot());
     if (p.err) return fail(p.err, p.what);
     HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)(ngroups * ndims * nbins * 8), st));
+    return decode_launch(p, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, st, 0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- group-by rows
+int sprintz_mi355x_groupby_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t key_col, uint32_t key_lo, uint32_t shift,
+                                uint32_t nbins, uint64_t table_chunks, uint32_t ops, uint32_t flags, uint64_t* d_count, uint64_t* d_sum,
+                                int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "groupby_rows: more than 512 columns", "groupby_rows: the RLE codecs (delta, xff) only",
+                           "groupby_rows"))) return rc;
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "groupby_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    const uint32_t W = 8u * (uint32_t)elem_bytes;
+    if (key_col >= ndims) return fail(SPRINTZ_E_INVALID, "groupby_rows: key_col must be a column of the batch");
+    if (key_lo >= (1u << W)) return fail(SPRINTZ_E_INVALID, "groupby_rows: key_lo must be below 2^W");
+    if (shift >= W) return fail(SPRINTZ_E_INVALID, "groupby_rows: shift must be below the element width");
+    if (nbins < 1 || nbins > (1u << (W - shift))) return fail(SPRINTZ_E_INVALID, "groupby_rows: nbins must be in 1..2^(W - shift)");
+    if (ops == 0 || (ops & ~(SPRINTZ_GBY_COUNT | SPRINTZ_GBY_SUM))) return fail(SPRINTZ_E_INVALID, "groupby_rows: ops must be a non-empty OR of SPRINTZ_GBY_COUNT / _SUM");
+    if (((ops & SPRINTZ_GBY_COUNT) && !d_count) || ((ops & SPRINTZ_GBY_SUM) && !d_sum))
+        return fail(SPRINTZ_E_INVALID, "groupby_rows: a selected op without its output buffer");
+    if (((ops & SPRINTZ_GBY_COUNT) && (uintptr_t)d_count % 8) || ((ops & SPRINTZ_GBY_SUM) && (uintptr_t)d_sum % 8) || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "groupby_rows: d_count, d_sum and d_rets must be aligned to 8 bytes");
+    if ((uint64_t)nbins * ((uint64_t)ndims + 1) > SPRINTZ_GBY_MAX_COUNTERS)
+        return fail(SPRINTZ_E_UNSUPPORTED, "groupby_rows: nbins x (ndims + 1) above SPRINTZ_GBY_MAX_COUNTERS: split the bins with key_lo");
+    const uint64_t ntables = table_chunks ? (nchunks + table_chunks - 1) / table_chunks : 1;
+    if (ntables > (1ull << 40) / ((uint64_t)ndims * nbins))
+        return fail(SPRINTZ_E_INVALID, "groupby_rows: too many tables for one call (ntables x nbins x ndims above 2^40 entries)");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    QuerySpec qs;
+    qs.q = kQueryGroupBy;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.gby = GroupByArgs{d_mask, (chunk_len / ndims + 7) / 8, (ops & SPRINTZ_GBY_COUNT) ? d_count : nullptr, (ops & SPRINTZ_GBY_SUM) ? d_sum : nullptr,
+                         table_chunks, key_col, key_lo, shift, nbins, 0, 0};
+    // planned first: a call the planner refuses leaves the outputs as they were
+    const Plan p = plan_decode(decode_shape(codec, elem_bytes, d_comp, nchunks, chunk_len, ndims, nullptr, 0, qs), snapshot());
+    if (p.err) return fail(p.err, p.what);
+    if (qs.gby.count) HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)(ntables * nbins * 8), st));
+    if (qs.gby.sum) HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)(ntables * nbins * ndims * 8), st));
     return decode_launch(p, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, st, 0, 0, 0, qs);
 }
 

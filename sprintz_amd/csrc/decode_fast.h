@@ -146,6 +146,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // rows over (decode_ops.h: moments_ref_rows).  Windows, mask read-ahead and run shortcut are aggregate's.
     constexpr bool MOM = Q == kQueryMoments;
     static_assert(!MOM || (!CM && !SPLIT && DS == 0), "moments: plain mappings");
+    // GBY (sprintz_mi355x_groupby_rows): per bin of ONE key column's value, the count and the per-column sums of the rows the caller's mask
+    // names (or of every row).  Where a sample is added depends on another column's value: a lane keeps the block's rows of all its slots,
+    // as the moments do, until the key column's lane has handed its 8 rows over; the entries are added up in the workgroup's LDS table
+    // behind the groups' carves (decode_ops.h: groupby_begin .. groupby_end), so, as for the histogram, no lane leaves early.
+    constexpr bool GBY = Q == kQueryGroupBy;
+    static_assert(!GBY || (!CM && !SPLIT && DS == 0), "group-by: plain mappings");
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -185,9 +191,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         c_sel = gp.chunk;
     }
     const uint64_t c_first = c_sel;
-    if constexpr (!HIST) {
+    if constexpr (!HIST && !GBY) {
         if (c_first >= a.nchunks) return;
-    }                                                      // (histogram: c_end <= c_first below, and the chunk loop does not run)
+    }                                                      // (histogram, group-by: c_end <= c_first below, and the chunk loop does not run)
     const uint64_t c_end = GATHER ? c_first + 1 : (c_first + a.chunks_per_group < a.nchunks) ? c_first + a.chunks_per_group : a.nchunks;
 
     // LDS carve per group: [ring RB | apron APRON | block staging]
@@ -379,6 +385,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         for (int k = 0; k < CPL; k++) hcol[k] = hist_col<W>(a, genk[k], col_ok[k]);
         hctx = hist_begin(a, smem);
     }
+    // group-by rows: where the rows are added up (the block's rows wait in mrow)
+    GroupByCtx gctx{};
+    if constexpr (GBY) gctx = groupby_begin(a, smem);
     if constexpr (Q == kQueryFilter) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) fc[k] = filter_col<W>(a, genk[k], col_ok[k]);
@@ -389,7 +398,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
         } else if constexpr (AGG || HIST) {                // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
-        } else if constexpr (MOM) {                        // every slot's rows wait for q_window: the reference column's may come last
+        } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
         } else if constexpr (Q != 0) {
             if constexpr (W == 16) {
@@ -424,7 +433,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         } else if constexpr (HIST) {                       // (a lane column past the last one counts nothing)
             if (sm != 0 && col_ok[k]) hist_rows8<W>(hctx, hcol[k], arow, sm);
-        } else if constexpr (MOM) {
+        } else if constexpr (MOM || GBY) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
     // after every block of 8 rows: the group's lanes combine, one lane stores the block's byte (fb < chunk_len / blk_elems <=
@@ -481,6 +490,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             wleft -= 8;
             if (wleft == 0) mom_flush_all();
         }
+        if constexpr (GBY) {
+            // sm is the group's: every lane of it takes part in the exchange of the key column's rows
+            if (sm != 0) {
+                uint32_t xk[8];
+                moments_ref_rows<W, CPL>(a.gby.key, DP, [&](int k, int i) { return mrow[k][i]; }, xk);
+                groupby_rows8<W, CPL>(gctx, [&](int k, int i) { return mrow[k][i]; }, xk, sm, genk, col_ok, lane_d);
+            }
+            fb++;
+        }
     };
     uint32_t ovo = 0;                                      // output cursor (byte offset from this wave's out_base)
     // gather: the chunk-relative row of the next block, and the row of the block each of this lane's 16-byte store pieces lies in
@@ -507,6 +525,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (AGG) return a.agg.mask_stride;
         else if constexpr (HIST) return a.hist.mask_stride;
         else if constexpr (MOM) return a.mom.mask_stride;
+        else if constexpr (GBY) return a.gby.mask_stride;
         else return a.select.mask_stride;
     };
     auto sel_byte = [&](uint32_t b) -> uint32_t {
@@ -781,6 +800,22 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             return;
         }
+        if constexpr (GBY && !FIRE) {
+            // a delta run repeats the previous row 8 len times: its key, and so its bin, is one -- each column adds its value times the
+            // run's selected rows (the set bits of its mask bytes, spread over the group's lanes; 8 len without a mask), one lane adds
+            // their number.  The key column's value is one exchange a run.  (The bytes lie inside the chunk's: the run fits the slot.)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            uint32_t c = 8u * len;
+            if (smb) {
+                c = 0;
+                for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
+                c = group_sum(c, DP);
+            }
+            groupby_value<W, CPL>(gctx, pv, moments_ref_value<W, CPL>(a.gby.key, DP, pv), c, genk, col_ok, lane_d);
+            fb += len;
+            return;
+        }
         if constexpr (HIST && !FIRE) {
             // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows -- the set
             // bits of its mask bytes, spread over the group's lanes; 8 len without a mask.  (The bytes lie inside the chunk's: the run
@@ -830,7 +865,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
             }
             if constexpr (AGG) sm = sel_byte(fb);          // (a FIRE run is replayed for its state, block by block, as the window mode does)
-            if constexpr (HIST || MOM) sm = smb ? sel_byte(fb) : 0xffu;
+            if constexpr (HIST || MOM || GBY) sm = smb ? sel_byte(fb) : 0xffu;
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -952,7 +987,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
         if constexpr (SELECT || AGG) sm = sel_byte(fb);    // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
-        if constexpr (HIST || MOM) sm = smb ? sel_byte(fb) : 0xffu;
+        if constexpr (HIST || MOM || GBY) sm = smb ? sel_byte(fb) : 0xffu;
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -1095,6 +1130,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             mwin0 = 0x80000000u;                           // no window yet: the first block loads one
             smb = a.hist.mask ? a.hist.mask + chunk * (uint64_t)a.hist.mask_stride : nullptr;
             hctx.g = hist_of_chunk(a, chunk);
+        }
+        if constexpr (GBY) {
+            fb = 0; sm = 0;
+            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
+            smb = a.gby.mask ? a.gby.mask + chunk * (uint64_t)a.gby.mask_stride : nullptr;
+            groupby_of_chunk(a, gctx, chunk);
         }
         if constexpr (SELECT) {
             fb = 0; srank = 0; sm = 0;
@@ -1287,6 +1328,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // fb blocks = 8 fb rows lie in front of the tail
         if (!corrupt)
             hist_tail<W, CPL>(a, hctx, hcol, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (GBY) {
+        // fb blocks = 8 fb rows lie in front of the tail
+        if (!corrupt)
+            groupby_tail<W, CPL>(a, gctx, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, lane_d, [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) {
             const uint8_t* t = a.comp + gabs + rp;
@@ -1324,6 +1369,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
     }   // chunk loop
     if constexpr (HIST) hist_end(a, hctx);
+    if constexpr (GBY) groupby_end(a, gctx);
 }
 
 }  // namespace sprintz

@@ -26,6 +26,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // the table's merge (decode_ops.h: hist_begin, hist_end) -- so in this mode no lane leaves early: a group past the last chunk
     // (hlive false) and a chunk whose header is refused (hbad) walk on as empty streams.
     constexpr bool HIST = Q == kQueryHistogram;
+    // GBY (sprintz_mi355x_groupby_rows): the same two barriers around its table (groupby_begin, groupby_end), so the same rule -- TAB is
+    // either mode.  The block's rows of every column wait behind the column loop for the key column's, as the moments' do.
+    constexpr bool GBY = Q == kQueryGroupBy;
+    constexpr bool TAB = HIST || GBY;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int DP = 1 << a.log2DP;
@@ -44,13 +48,15 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     }
     bool hlive = true, hbad = false;
     HistCtx hctx{};
-    if constexpr (HIST) {
-        hctx = hist_begin(a, smem);
+    GroupByCtx gctx{};
+    if constexpr (TAB) {
+        if constexpr (HIST) hctx = hist_begin(a, smem);
+        else gctx = groupby_begin(a, smem);
         hlive = chunk_sel < a.nchunks;
         if (!hlive) chunk_sel = a.nchunks - 1;      // (any stream will do: none of it is read)
     }
     const uint64_t chunk = chunk_sel;
-    if constexpr (!HIST) {
+    if constexpr (!TAB) {
         if (chunk >= a.nchunks) return;             // whole groups leave together
     }
 
@@ -67,7 +73,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
     // ---- 8-byte stream header (format.h:48-62)
     uint32_t groups_left, remaining, pos;
-    if (HIST && !hlive) {
+    if (TAB && !hlive) {
         groups_left = 0; remaining = 0; pos = 0;
     } else if (a.norle) {                                   // format.h:65-86; sprintz_delta.cpp:803-807, :832
         // norle == 2: compress8b_rowmajor_xff's 8-byte header, a u64 len whose bytes 6..7 hold ndims (sprintz_xff.cpp:58-63)
@@ -77,7 +83,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)nd != D || len > a.chunk_len) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
-            if constexpr (HIST) hbad = true; else return;
+            if constexpr (TAB) hbad = true; else return;
         }
         groups_left = len < 128u ? 0u : len / (16u * (uint32_t)D);
         remaining = len - groups_left * 16u * (uint32_t)D;
@@ -90,7 +96,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)(w1 >> 16) != D) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
-            if constexpr (HIST) hbad = true; else return;
+            if constexpr (TAB) hbad = true; else return;
         }
     } else {
         groups_left = a.nh_ngroups;
@@ -103,7 +109,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // a damaged header must not make the loop spin: every group of a valid stream holds at
     // least one non-empty slot, except the one that closes the stream
     bool corrupt = groups_left > a.chunk_len / blk_elems + 2u || pos > stream_len;
-    if (HIST && hbad) corrupt = true;
+    if (TAB && hbad) corrupt = true;
     if (corrupt) groups_left = 0;
 
     // per-column predictor state (all start at 0: sprintz_xff_rle.cpp:149-152)
@@ -182,6 +188,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         hctx.g = hist_of_chunk(a, chunk);
         if (a.hist.mask) hmb = a.hist.mask + chunk * (uint64_t)a.hist.mask_stride;
     }
+    // group-by rows: the chunk's table and mask bytes (null: every row), the mask byte of the block being decoded
+    const uint8_t* gmb = nullptr;
+    uint32_t gm = 0xffu;
+    if constexpr (GBY) {
+        groupby_of_chunk(a, gctx, chunk);
+        if (a.gby.mask) gmb = a.gby.mask + chunk * (uint64_t)a.gby.mask_stride;
+    }
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -257,6 +270,23 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                         }
                         continue;
                     }
+                    if constexpr (GBY && !FIRE) {
+                        // a delta run repeats the previous row 8 len times: its key, and so its bin, is one -- each column adds its value
+                        // times the run's selected rows, one lane their number; the key column's value is one exchange a run
+                        if (len > 0) {
+                            if ((uint64_t)out_elems + (uint64_t)len * blk_elems > a.chunk_len) { corrupt = true; break; }
+                            const uint32_t b0r = out_elems / blk_elems;
+                            uint32_t c = 8u * len;
+                            if (gmb) {
+                                c = 0;
+                                for (uint32_t j = (uint32_t)lane_d; j < len; j += (uint32_t)DP) c += (uint32_t)__popc((uint32_t)gmb[b0r + j]);
+                                c = group_sum(c, DP);
+                            }
+                            groupby_value<W, CPL>(gctx, pv, moments_ref_value<W, CPL>(a.gby.key, DP, pv), c, colk, genk, lane_d);
+                            out_elems += len * blk_elems;
+                        }
+                        continue;
+                    }
                     if (len > 0) { run_left = len - 1; have = true; run_block = true; break; }
                     // len == 0: padding slot, look at the next one
                 } else {                         // packed block
@@ -304,6 +334,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if constexpr (Q == kQueryAggregate) am = amb[out_elems / blk_elems];
         if constexpr (HIST) hm = hmb ? (uint32_t)hmb[out_elems / blk_elems] : 0xffu;
         if constexpr (MOM) mm = mmb ? (uint32_t)mmb[out_elems / blk_elems] : 0xffu;
+        if constexpr (GBY) gm = gmb ? (uint32_t)gmb[out_elems / blk_elems] : 0xffu;
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -345,7 +376,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     for (int i = 0; i < 8; i++) xs[i] = v[i][k];
                     hist_rows8<W>(hctx, hcol[k], xs, hm);
                 }
-            } else if constexpr (MOM) {          // (the products wait for the reference column's rows: behind the column loop)
+            } else if constexpr (MOM || GBY) {   // (the products / the adds wait for the reference / key column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
 #pragma unroll
@@ -376,6 +407,14 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 moments_count_flush(a, wbase + wi, mcnt, lane_d);
                 wi++;
                 wleft = a.win.rows;
+            }
+        }
+        if constexpr (GBY) {
+            // the key column's 8 rows come from the lane that decoded them -- every lane of the group takes part, gm is the group's
+            if (gm != 0) {
+                uint32_t xk[8];
+                moments_ref_rows<W, CPL>(a.gby.key, DP, [&](int k, int i) { return v[i][k]; }, xk);
+                groupby_rows8<W, CPL>(gctx, [&](int k, int i) { return v[i][k]; }, xk, gm, colk, genk, lane_d);
             }
         }
         if constexpr (Q == kQueryWindow || Q == kQueryAggregate) {       // the block's 8 rows lie in one window: flush it when they complete it
@@ -521,6 +560,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                                         [&](uint32_t b) { return (uint32_t)hmb[b]; });
         if (hlive && lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         hist_end(a, hctx);
+        return;
+    }
+    if constexpr (GBY) {
+        if (!corrupt) groupby_tail<W, CPL>(a, gctx, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, lane_d,
+                                           [&](uint32_t b) { return (uint32_t)gmb[b]; });
+        if (hlive && lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        groupby_end(a, gctx);
         return;
     }
     if constexpr (Q == kQueryGather) {

@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram and moments rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
+// aggregate, histogram, moments and group-by rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
 // its lane's columns (`col`, with `genuine` false for a lane column past the last one), its place in the group (`lane_d` of `DP`
 // lanes) and the mode's running state; decode_uni.h is the lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane
 // mapping -- how a block's rows reach the accumulators, the staging and the stores -- stays in that kernel.
@@ -84,6 +84,22 @@ struct MomentArgs {
     uint64_t* cross;            // optional (SPRINTZ_MOM_CROSS)
     uint32_t ref;               // the reference column (< D; 0 where cross is null)
 };
+// group-by rows (Q == kQueryGroupBy; sprintz_mi355x_groupby_rows): a row whose bit is set in chunk c's mask bytes (filter_rows' layout; no
+// mask: every existing row) and whose key column holds x belongs to bin b = ((x - key_lo) mod 2^W) >> shift of table c / table_chunks if
+// b < nbins, and to none otherwise: count[t * nbins + b] takes 1 and sum[(t * nbins + b) * D + d] takes x_d, every column d.  A workgroup
+// decodes the wg_chunks consecutive chunks from blockIdx.x * wg_chunks on and adds them up in its own table of uint32 -- nbins * D sums, then
+// nbins counts -- at byte table_off of its dynamic LDS, if they all lie in one table; if not (or wg_chunks == 0: the planner found that a
+// sum could wrap) every add goes to `count` / `sum` directly.  An output that is null is not selected
+struct GroupByArgs {
+    const uint8_t* mask;        // [nchunks][mask_stride], or null: a run-time, wave-uniform switch, as hist.mask is
+    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
+    uint64_t* count;            // optional (SPRINTZ_GBY_COUNT): [ntables][nbins], zeroed on the stream in front of the launch
+    uint64_t* sum;              // optional (SPRINTZ_GBY_SUM): [ntables][nbins][D], the same
+    uint64_t table_chunks;      // H; 0: the whole batch is one table
+    uint32_t key, key_lo, shift, nbins;
+    uint32_t table_off;
+    uint32_t wg_chunks;
+};
 
 struct DecodeArgs {
     const uint8_t* comp;        // compressed bytes
@@ -126,6 +142,7 @@ struct DecodeArgs {
     AggregateArgs agg;
     HistogramArgs hist;
     MomentArgs mom;
+    GroupByArgs gby;
 };
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
@@ -499,6 +516,152 @@ __device__ __forceinline__ void moments_tail(const DecodeArgs& a, const uint8_t*
             if (genuine[k]) moments_value(acc[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), xr, 1u);
     }
     while (w < a.win.count) flush();
+}
+
+// ---- group-by rows.  The bin of a row is the histogram's test on the key column's value (hist_bin); the key column's rows reach every
+// lane of the group as the moments' reference column does (moments_ref_rows / moments_ref_value).  The entries are a table in the
+// workgroup's LDS (non-returning ds_add_u32: nbins * D sums, bin-major, then nbins counts; GroupByCtx::bin.tab) or, for a workgroup whose
+// chunks lie in more than one table, the caller's 64-bit entries themselves (gsum / gcount: the table of the chunk being decoded).
+#ifndef SPRINTZ_GBY_MERGE
+// what a block's 8 rows cost in atomics, both forms measured in profiles/groupby_rows.txt -- 1 (kept): where all 8 rows are valid and
+// share a bin, a column does one add of the block's sum and the count lane one add of 8, an add a row otherwise; 0: an add a row
+#define SPRINTZ_GBY_MERGE 1
+#endif
+struct GroupByCtx {
+    HistCtx bin;                // tab (null: every add goes to gsum / gcount), shift and nbins: hist_bin's view of the key column
+    HistCol key;                // lo = key_lo
+    uint64_t* gsum;             // null: the sums are not selected
+    uint64_t* gcount;           // null: the counts are not selected
+    uint32_t D;
+};
+__device__ __forceinline__ void groupby_of_chunk(const DecodeArgs& a, GroupByCtx& c, uint64_t chunk)
+{
+    const uint64_t t = a.gby.table_chunks ? chunk / a.gby.table_chunks : 0;
+    c.gsum = a.gby.sum ? a.gby.sum + t * ((uint64_t)a.gby.nbins * (uint32_t)a.D) : nullptr;
+    c.gcount = a.gby.count ? a.gby.count + t * (uint64_t)a.gby.nbins : nullptr;
+}
+// v: one row's value, a block's sum (8 rows: below 2^19) or a run's value times its rows (the planner's rule keeps every table entry
+// below 2^32; the direct path adds all 64 bits)
+__device__ __forceinline__ void groupby_add_sum(const GroupByCtx& c, uint32_t b, uint32_t col, uint64_t v)
+{
+    const uint32_t idx = b * c.D + col;
+    if (c.bin.tab) (void)__hip_atomic_fetch_add(c.bin.tab + idx, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else (void)__hip_atomic_fetch_add(c.gsum + idx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void groupby_add_count(const GroupByCtx& c, uint32_t b, uint32_t n)
+{
+    if (c.bin.tab) (void)__hip_atomic_fetch_add(c.bin.tab + c.bin.nbins * c.D + b, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else (void)__hip_atomic_fetch_add(c.gcount + b, (uint64_t)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// a block's 8 rows: at(k, i) is this lane's row i of slot k (garbage above bit W allowed), xk the key column's rows (clean: every lane of
+// the group has them from moments_ref_rows), bit i of m: row i is selected.  One lane of the group adds the counts
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void groupby_rows8(const GroupByCtx& c, F at, const uint32_t (&xk)[8], uint32_t m, const int (&col)[CPL],
+                                              const bool (&genuine)[CPL], int lane_d)
+{
+    uint32_t b[8], diff = 0, valid = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        b[i] = hist_bin<W>(c.bin, c.key, xk[i]);
+        diff |= b[i] ^ b[0];
+        valid |= (b[i] < c.bin.nbins ? 1u : 0u) << i;
+    }
+    valid &= m;
+    if (valid == 0) return;
+    if (SPRINTZ_GBY_MERGE == 1 && valid == 0xffu && diff == 0) {
+        if (c.gsum) {
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                if (!genuine[k]) continue;
+                uint32_t bs = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) bs += at(k, i) & Elem<W>::MASK;
+                groupby_add_sum(c, b[0], (uint32_t)col[k], bs);
+            }
+        }
+        if (c.gcount && lane_d == 0) groupby_add_count(c, b[0], 8u);
+        return;
+    }
+    if (c.gsum) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!genuine[k]) continue;
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if ((valid >> i) & 1u) groupby_add_sum(c, b[i], (uint32_t)col[k], at(k, i) & Elem<W>::MASK);
+        }
+    }
+    if (c.gcount && lane_d == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if ((valid >> i) & 1u) groupby_add_count(c, b[i], 1u);
+    }
+}
+// one row that `n` selected rows repeat (a delta run's constant row): xk is the key column's value, pv the lane's slots
+template <int W, int CPL>
+__device__ __forceinline__ void groupby_value(const GroupByCtx& c, const uint32_t (&pv)[CPL], uint32_t xk, uint32_t n, const int (&col)[CPL],
+                                              const bool (&genuine)[CPL], int lane_d)
+{
+    const uint32_t b = hist_bin<W>(c.bin, c.key, xk);
+    if (b >= c.bin.nbins || n == 0) return;
+    if (c.gsum) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) groupby_add_sum(c, b, (uint32_t)col[k], (uint64_t)(pv[k] & Elem<W>::MASK) * n);
+    }
+    if (c.gcount && lane_d == 0) groupby_add_count(c, b, n);
+}
+// At the kernel's start, every lane of the workgroup: does the workgroup add in its table?  (Workgroup-uniform, as hist_begin: its chunks
+// [blockIdx.x * wg_chunks, + wg_chunks) -- those that exist -- lie in one table.)  The table is zeroed, behind a barrier.
+__device__ __forceinline__ GroupByCtx groupby_begin(const DecodeArgs& a, uint8_t* smem)
+{
+    GroupByCtx c{HistCtx{nullptr, nullptr, a.gby.shift, a.gby.nbins}, HistCol{a.gby.key_lo, 0u}, a.gby.sum, a.gby.count, (uint32_t)a.D};
+    const uint64_t first = (uint64_t)blockIdx.x * a.gby.wg_chunks;
+    if (a.gby.wg_chunks == 0 || first >= a.nchunks) return c;
+    const uint64_t last = (first + a.gby.wg_chunks < a.nchunks ? first + a.gby.wg_chunks : a.nchunks) - 1;
+    if (a.gby.table_chunks && first / a.gby.table_chunks != last / a.gby.table_chunks) return c;
+    c.bin.tab = (hist_lds_u32*)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + a.gby.table_off);
+    const uint32_t n = a.gby.nbins * ((uint32_t)a.D + 1u);
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) c.bin.tab[i] = 0;
+    __syncthreads();
+    return c;
+}
+// At the kernel's end, every lane of the workgroup (none has left): behind a barrier the table's nonzero entries of the selected outputs
+// are added to the workgroup's table in global memory, spread over all lanes -- device-scope 64-bit adds: integer sums, exact in any order.
+__device__ __forceinline__ void groupby_end(const DecodeArgs& a, const GroupByCtx& c)
+{
+    if (!c.bin.tab) return;
+    __syncthreads();
+    GroupByCtx g = c;
+    groupby_of_chunk(a, g, (uint64_t)blockIdx.x * a.gby.wg_chunks);
+    const uint32_t ns = a.gby.nbins * (uint32_t)a.D, n = ns + a.gby.nbins;
+    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+        uint64_t* const dst = i < ns ? g.gsum : g.gcount;
+        const uint32_t v = c.bin.tab[i];
+        if (v != 0 && dst) (void)__hip_atomic_fetch_add(dst + (i < ns ? i : i - ns), (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
+// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  mask_at(b) is the chunk's mask byte b
+// (asked only where there is a mask).  The key column's element is read from the tail itself: no lane needs another's.
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void groupby_tail(const DecodeArgs& a, const GroupByCtx& c, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0,
+                                             const int (&col)[CPL], const bool (&genuine)[CPL], int lane_d, F mask_at)
+{
+    const uint32_t nfull = remaining / D;
+    uint32_t m = 0xffu;
+    for (uint32_t r = 0; r < nfull; r++) {
+        if ((r & 7u) == 0 && a.gby.mask) m = mask_at((row0 + r) >> 3);
+        if (!((m >> (r & 7u)) & 1u)) continue;
+        const uint32_t b = hist_bin<W>(c.bin, c.key, tail_elem<W>(t, r * D + a.gby.key));
+        if (b >= c.bin.nbins) continue;
+        if (c.gsum) {
+#pragma unroll
+            for (int k = 0; k < CPL; k++)
+                if (genuine[k]) groupby_add_sum(c, b, (uint32_t)col[k], tail_elem<W>(t, r * D + (uint32_t)col[k]));
+        }
+        if (c.gcount && lane_d == 0) groupby_add_count(c, b, 1u);
+    }
 }
 
 // ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the

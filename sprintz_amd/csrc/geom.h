@@ -28,17 +28,20 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 6 = select: a chunk is decoded once and only the rows whose bit is set in the caller's mask are stored, packed densely behind the chunk's base;
 // 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only;
 // 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only;
-// 9 = moments: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names (or of every row), reduce only
+// 9 = moments: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names (or of every row), reduce only;
+// 10 = group-by: per bin of ONE key column's value, the count and the per-column sums of the rows a mask names (or of every row), added up in an LDS table a workgroup, reduce only
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9;
+              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
-    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments;
+    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments || q == kQueryGroupBy;
 }
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB
 constexpr uint32_t kHistMaxCounters = 16384;
+// group-by rows: the entries of one call's table, nbins x (ndims + 1) (SPRINTZ_GBY_MAX_COUNTERS), under the same LDS budget
+constexpr uint32_t kGroupByMaxCounters = 16384;
 constexpr uint32_t kHistFastLdsBudget = 80u * 1024u;
 
 // sprintz_mi355x_compress_bound: the longest stream a chunk of chunk_len elements can have, a multiple of SPRINTZ_BOUND_ALIGN

@@ -18,15 +18,15 @@
 
 namespace sprintz {
 
-// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryMoments).  Each forwards to the
+// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryGroupBy).  Each forwards to the
 // translation unit that holds the instantiation -- decode_w8.hip / decode_w16.hip for the plain decode and the reduce / window
-// queries, decode_gather.hip, decode_filter.hip, decode_select.hip, decode_aggregate.hip, decode_histogram.hip, decode_moments.hip for those modes -- so that every unit keeps its compile flags.
+// queries, decode_gather.hip, decode_filter.hip, decode_select.hip, decode_aggregate.hip, decode_histogram.hip, decode_moments.hip, decode_groupby.hip for those modes -- so that every unit keeps its compile flags.
 // generic lane mapping, both layouts, up to 512 columns (decode_kernel.h)
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h); gather and select for rows of whole 16-byte pieces
 // (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram and moments
+// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments and group-by
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // internal -- the units' own entry points, reached through the three launchers above alone (api.hip).  A unit refuses a width or
 // a mode it does not hold; the decode_uni units size their grid themselves (decode_uni_threads) and ignore `grid`
@@ -38,6 +38,7 @@ hipError_t decode_generic_select(int w, bool fire, bool lowdim, int cpl, int q, 
 hipError_t decode_generic_aggregate(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_generic_histogram(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_generic_moments(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_generic_groupby(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_fast_w8(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_fast_w16(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_fast_gather(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
@@ -46,6 +47,7 @@ hipError_t decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, int
 hipError_t decode_fast_aggregate(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_fast_histogram(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_fast_moments(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+hipError_t decode_fast_groupby(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_filter(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);

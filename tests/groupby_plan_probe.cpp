@@ -1,0 +1,50 @@
+// groupby_plan_probe.cpp -- plan_decode (sprintz_amd/csrc/plan.h) for the group-by-rows mode on a host compiler, for
+// tests/test_groupby_cpu.py: histogram_plan_probe.cpp's queries with the one Shape field that mode adds.  One query per line on stdin,
+//     esz=.. D=.. chunk_len=.. nchunks=.. codec=.. nbins=.. no_fast=.. general=.. chunks_per_group=.. q=..   (q defaults to kQueryGroupBy)
+// and one answer per line: the family's name, the launch's dynamic LDS bytes, the table's offset in it and the chunks a workgroup
+// adds up in its table (0: none, every row goes to global memory) -- or the error.
+#include <cstdio>
+#include <cstdlib>
+#include <sstream>
+#include <string>
+
+#include "../sprintz_amd/csrc/plan.h"
+
+using namespace sprintz;
+
+int main()
+{
+    char line[1024];
+    while (fgets(line, sizeof line, stdin)) {
+        std::istringstream in(line);
+        std::string tok;
+        Shape s;
+        Knobs k;
+        s.q = kQueryGroupBy;
+        s.gby_bins = 256;
+        bool any = false;
+        while (in >> tok) {
+            const size_t eq = tok.find('=');
+            if (eq == std::string::npos) { printf("bad token %s\n", tok.c_str()); return 2; }
+            const std::string key = tok.substr(0, eq);
+            const unsigned long long v = strtoull(tok.c_str() + eq + 1, nullptr, 0);
+            any = true;
+            if (key == "esz") s.esz = (int)v;
+            else if (key == "D") s.D = (int)v;
+            else if (key == "codec") s.codec = (int)v;
+            else if (key == "chunk_len") s.chunk_len = (uint32_t)v;
+            else if (key == "nchunks") s.nchunks = v;
+            else if (key == "nbins") s.gby_bins = (uint32_t)v;
+            else if (key == "general") s.general = (int)v;
+            else if (key == "q") s.q = (int)v;
+            else if (key == "no_fast") k.no_fast = (int)v;
+            else if (key == "chunks_per_group") k.chunks_per_group = (int)v;
+            else { printf("bad key %s\n", key.c_str()); return 2; }
+        }
+        if (!any) continue;
+        const Plan p = plan_decode(s, k);
+        if (p.err) printf("error=%d\n", p.err);
+        else printf("%s lds=%llu table_off=%u wg_chunks=%u\n", kFamilyNames[p.family], (unsigned long long)p.lds, p.gby_table_off, p.gby_wg_chunks);
+    }
+    return 0;
+}
