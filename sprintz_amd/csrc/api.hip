@@ -288,22 +288,27 @@ hipError_t launch_size_scan(const uint32_t* d_sizes, uint64_t n, uint32_t align,
 }
 
 // The lane-per-column decoders' launchers (launch.h): each forwards to the translation unit that holds the instantiation -- the row
-// operation's own unit, else the width's
+// operation's own unit, else the width's.  kDecodeUnits[q][w == 16]
+struct DecodeUnit {
+    decltype(&decode_generic_w8) generic;
+    decltype(&decode_fast_w8) fast;
+};
+#define SPRINTZ_WIDTH_UNITS {{decode_generic_w8, decode_fast_w8}, {decode_generic_w16, decode_fast_w16}}
+#define SPRINTZ_ROW_OP_UNIT_ROW(NAME) {{decode_generic_##NAME, decode_fast_##NAME}, {decode_generic_##NAME, decode_fast_##NAME}},
+const DecodeUnit kDecodeUnits[][2] = {SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS,   // kQueryOff .. kQueryWindow
+                                      SPRINTZ_ROW_OP_UNITS(SPRINTZ_ROW_OP_UNIT_ROW)};
+#undef SPRINTZ_ROW_OP_UNIT_ROW
+#undef SPRINTZ_WIDTH_UNITS
+static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryGroupBy + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    const auto unit = q == kQueryGather ? decode_generic_gather : q == kQueryFilter ? decode_generic_filter : q == kQuerySelect ? decode_generic_select
-                    : q == kQueryAggregate ? decode_generic_aggregate : q == kQueryHistogram ? decode_generic_histogram
-                    : q == kQueryMoments ? decode_generic_moments : q == kQueryGroupBy ? decode_generic_groupby
-                    : w == 8 ? decode_generic_w8 : decode_generic_w16;
-    return unit(w, fire, lowdim, cpl, q, grid, shmem, st, a);
+    if (q < 0 || q > kQueryGroupBy) return hipErrorInvalidValue;
+    return kDecodeUnits[q][w == 16].generic(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    const auto unit = q == kQueryGather ? decode_fast_gather : q == kQueryFilter ? decode_fast_filter : q == kQuerySelect ? decode_fast_select
-                    : q == kQueryAggregate ? decode_fast_aggregate : q == kQueryHistogram ? decode_fast_histogram
-                    : q == kQueryMoments ? decode_fast_moments : q == kQueryGroupBy ? decode_fast_groupby
-                    : w == 8 ? decode_fast_w8 : decode_fast_w16;
-    return unit(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
+    if (q < 0 || q > kQueryGroupBy) return hipErrorInvalidValue;
+    return kDecodeUnits[q][w == 16].fast(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
 {
@@ -334,17 +339,20 @@ int check_common(int codec, int esz, uint16_t ndims)
     return 0;
 }
 
+// a refusal in the words several operations share, with the operation's name in front
+int fail_op(int code, const char* op, const char* what)
+{
+    const std::string named = std::string(op) + ": " + what;
+    return fail(code, named.c_str());
+}
+
 // what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
                  const char* rle_only, const char* op = nullptr)
 {
     // (op != null: the operation's name in front of the shared messages)
-    auto shared = [&](const char* what) {
-        if (!op) return fail(SPRINTZ_E_INVALID, what);
-        const std::string named = std::string(op) + ": " + what;
-        return fail(SPRINTZ_E_INVALID, named.c_str());
-    };
+    auto shared = [&](const char* what) { return op ? fail_op(SPRINTZ_E_INVALID, op, what) : fail(SPRINTZ_E_INVALID, what); };
     if (flags & ~(uint32_t)SPRINTZ_QUERY_GENERAL_LAYOUT) return shared("unknown flag");
     if (chunk_len == 0 || chunk_len > (1u << 30)) return shared("chunk_len must be in 1..2^30");
     if (!d_comp || !d_offsets) return shared("null device pointer");
@@ -399,11 +407,13 @@ struct QuerySpec {
     WindowArgs win{};           // kQueryWindow
     GatherArgs gather{};        // kQueryGather
     FilterArgs filter{};        // kQueryFilter
-    SelectArgs select{};        // kQuerySelect
-    AggregateArgs agg{};        // kQueryAggregate (with win)
-    HistogramArgs hist{};       // kQueryHistogram (table_off and wg_chunks come from the plan)
+    SelectArgs select{};        // kQuerySelect (with rows)
+    RowMaskArgs rows{};         // kQuerySelect, kQueryAggregate (with win), and the three below
+    BinTableArgs table{};       // kQueryHistogram, kQueryGroupBy (table_off and wg_chunks come from the plan)
+    uint32_t table_row_max = 0; // ... the most one row can add to an entry of the table (plan.h: Shape::table_row_max)
+    HistogramArgs hist{};       // kQueryHistogram
     MomentArgs mom{};           // kQueryMoments (with win)
-    GroupByArgs gby{};          // kQueryGroupBy (table_off and wg_chunks come from the plan)
+    GroupByArgs gby{};          // kQueryGroupBy
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -437,8 +447,8 @@ Shape decode_shape(int codec, int esz, const void* d_comp, uint64_t nchunks, uin
     s.noheader = noheader; s.q = qs.q; s.general = qs.general; s.col_stride = qs.col_stride; s.host_call = qs.hc != nullptr;
     s.comp_lo = low4(d_comp); s.out_lo = low4(d_out);
     s.capacity = qs.select.capacity;
-    s.hist_bins = qs.hist.nbins;
-    s.gby_bins = qs.gby.nbins;
+    s.table_entries = qs.table.entries;
+    s.table_row_max = qs.table_row_max;
     return s;
 }
 
@@ -471,14 +481,13 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.gather = qs.gather;
     a.filter = qs.filter;
     a.select = qs.select;
-    a.agg = qs.agg;
+    a.rows = qs.rows;
+    a.table = qs.table;
+    a.table.table_off = p.table_off;
+    a.table.wg_chunks = p.wg_chunks;
     a.hist = qs.hist;
-    a.hist.table_off = p.hist_table_off;
-    a.hist.wg_chunks = p.hist_wg_chunks;
     a.mom = qs.mom;
     a.gby = qs.gby;
-    a.gby.table_off = p.gby_table_off;
-    a.gby.wg_chunks = p.gby_wg_chunks;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -543,6 +552,60 @@ int decode_batch(const Knobs& k, int codec, int esz, const void* d_comp, const u
     if (nchunks == 0) return 0;
     return decode_launch(plan_decode(decode_shape(codec, esz, d_comp, nchunks, chunk_len, ndims, d_out, noheader, qs), k), esz, d_comp, d_offsets, nchunks,
                          chunk_len, ndims, d_out, d_rets, st, noheader, nh_ngroups, nh_remaining, qs);
+}
+
+// ---- what aggregate_rows, moments_rows, histogram_rows and groupby_rows check and fill alike.  Each refusal carries the operation's
+// name `op` (fail_op), and each helper is called where its refusals stand among the operation's own.
+// the four masked operations, in front of their own checks: the common refusals, whole rows a chunk; then the mode, the layout and the
+// row mask (null: every row, where the operation allows it).  *rows: rows of a chunk slot
+int masked_row_op(const char* op, int q, int codec, int esz, const void* d_comp, const void* d_offsets, uint32_t chunk_len, uint16_t ndims, uint32_t flags,
+                  const uint8_t* d_mask, QuerySpec& qs, uint32_t* rows)
+{
+    int rc = check_common(codec, esz, ndims);
+    if (rc) return rc;
+    const std::string many = std::string(op) + ": more than 512 columns", rle = std::string(op) + ": the RLE codecs (delta, xff) only";
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, many.c_str(), rle.c_str(), op))) return rc;
+    if (chunk_len % ndims) return fail_op(SPRINTZ_E_INVALID, op, "chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    *rows = chunk_len / ndims;
+    qs.q = q;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.rows = RowMaskArgs{d_mask, (*rows + 7) / 8};
+    return 0;
+}
+// the windowed pair (aggregate, moments): the windows of a chunk slot of `rows` rows
+int windowed_row_op(const char* op, uint32_t window_rows, uint32_t rows, QuerySpec& qs)
+{
+    if (window_rows < 8 || window_rows % 8) return fail_op(SPRINTZ_E_INVALID, op, "window_rows must be a multiple of 8, at least 8");
+    qs.win.rows = window_rows;
+    qs.win.count = (rows + window_rows - 1) / window_rows;
+    return 0;
+}
+// the binned pair (histogram, group-by): the bins ...
+int binned_row_op(const char* op, int esz, uint32_t shift, uint32_t nbins)
+{
+    const uint32_t W = 8u * (uint32_t)esz;
+    if (shift >= W) return fail_op(SPRINTZ_E_INVALID, op, "shift must be below the element width");
+    if (nbins < 1 || nbins > (1u << (W - shift))) return fail_op(SPRINTZ_E_INVALID, op, "nbins must be in 1..2^(W - shift)");
+    return 0;
+}
+// ... the tables of the outputs, span_chunks consecutive chunks each (0: one for the batch), ndims x nbins 64-bit entries the largest
+// output of a table: at most 2^40 entries a call (`too_many`: the refusal, in the operation's words) ...
+int binned_tables(uint64_t nchunks, uint64_t span_chunks, uint16_t ndims, uint32_t nbins, const char* too_many, uint64_t* ntables)
+{
+    *ntables = span_chunks ? (nchunks + span_chunks - 1) / span_chunks : 1;
+    if (*ntables > (1ull << 40) / ((uint64_t)ndims * nbins)) return fail(SPRINTZ_E_INVALID, too_many);
+    return 0;
+}
+// ... and the launch.  Planned first: a call the planner refuses leaves the outputs as they were; zero_outputs(st) then zeroes them on
+// the stream, in front of the kernel that adds to them
+template <typename Z>
+int binned_launch(int codec, int esz, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, int64_t* d_rets,
+                  hipStream_t st, const QuerySpec& qs, Z zero_outputs)
+{
+    const Plan p = plan_decode(decode_shape(codec, esz, d_comp, nchunks, chunk_len, ndims, nullptr, 0, qs), snapshot());
+    if (p.err) return fail(p.err, p.what);
+    if (int rc = zero_outputs(st)) return rc;
+    return decode_launch(p, esz, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, st, 0, 0, 0, qs);
 }
 
 // where the encode launch builds the dense container itself (compact_tail.h; Plan::fused)
@@ -1713,7 +1776,8 @@ int sprintz_mi355x_select_rows(int codec, int elem_bytes, const void* d_comp, co
     QuerySpec qs;
     qs.q = kQuerySelect;
     qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.select = SelectArgs{d_mask, d_bases, capacity, d_ids, rows, (rows + 7) / 8};
+    qs.select = SelectArgs{d_bases, capacity, d_ids, rows};
+    qs.rows = RowMaskArgs{d_mask, (rows + 7) / 8};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_out, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }
@@ -1724,12 +1788,11 @@ int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp,
                                   uint32_t flags, void* d_min, void* d_max, uint64_t* d_sum, uint32_t* d_count, int64_t* d_rets,
                                   void* hip_stream)
 {
-    int rc = check_common(codec, elem_bytes, ndims);
+    QuerySpec qs;
+    uint32_t rows;
+    int rc = masked_row_op("aggregate_rows", kQueryAggregate, codec, elem_bytes, d_comp, d_offsets, chunk_len, ndims, flags, d_mask, qs, &rows);
     if (rc) return rc;
-    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "aggregate_rows: more than 512 columns", "aggregate_rows: the RLE codecs (delta, xff) only",
-                           "aggregate_rows"))) return rc;
-    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "aggregate_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
-    if (window_rows < 8 || window_rows % 8) return fail(SPRINTZ_E_INVALID, "aggregate_rows: window_rows must be a multiple of 8, at least 8");
+    if ((rc = windowed_row_op("aggregate_rows", window_rows, rows, qs))) return rc;
     if (ops < 1 || ops > 15) return fail(SPRINTZ_E_INVALID, "aggregate_rows: ops must be a non-empty OR of SPRINTZ_AGG_MIN / _MAX / _SUM / _COUNT");
     if (!d_mask) return fail(SPRINTZ_E_INVALID, "aggregate_rows: null device pointer");
     if (((ops & SPRINTZ_AGG_MIN) && !d_min) || ((ops & SPRINTZ_AGG_MAX) && !d_max) || ((ops & SPRINTZ_AGG_SUM) && !d_sum) || ((ops & SPRINTZ_AGG_COUNT) && !d_count))
@@ -1739,17 +1802,11 @@ int sprintz_mi355x_aggregate_rows(int codec, int elem_bytes, const void* d_comp,
         return fail(SPRINTZ_E_INVALID, "aggregate_rows: min / max must be aligned to the element size, count to 4 bytes, sum and d_rets to 8");
     if (nchunks == 0) return 0;
     if ((rc = ensure_device())) return rc;
-    const uint32_t rows = chunk_len / ndims;
-    QuerySpec qs;
-    qs.q = kQueryAggregate;
-    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.win.rows = window_rows;
-    qs.win.count = (rows + window_rows - 1) / window_rows;
     qs.win.ops = ops & 7u;
     qs.win.min = (ops & SPRINTZ_AGG_MIN) ? d_min : nullptr;
     qs.win.max = (ops & SPRINTZ_AGG_MAX) ? d_max : nullptr;
     qs.win.sum = (ops & SPRINTZ_AGG_SUM) ? d_sum : nullptr;
-    qs.agg = AggregateArgs{d_mask, (ops & SPRINTZ_AGG_COUNT) ? d_count : nullptr, (rows + 7) / 8};
+    qs.win.row_count = (ops & SPRINTZ_AGG_COUNT) ? d_count : nullptr;
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }
@@ -1760,12 +1817,11 @@ int sprintz_mi355x_moments_rows(int codec, int elem_bytes, const void* d_comp, c
                                 uint32_t ops, uint32_t ref_col, uint32_t flags, uint32_t* d_count, uint64_t* d_sum,
                                 uint64_t* d_sumsq, uint64_t* d_cross, int64_t* d_rets, void* hip_stream)
 {
-    int rc = check_common(codec, elem_bytes, ndims);
+    QuerySpec qs;
+    uint32_t rows;
+    int rc = masked_row_op("moments_rows", kQueryMoments, codec, elem_bytes, d_comp, d_offsets, chunk_len, ndims, flags, d_mask, qs, &rows);
     if (rc) return rc;
-    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "moments_rows: more than 512 columns", "moments_rows: the RLE codecs (delta, xff) only",
-                           "moments_rows"))) return rc;
-    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "moments_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
-    if (window_rows < 8 || window_rows % 8) return fail(SPRINTZ_E_INVALID, "moments_rows: window_rows must be a multiple of 8, at least 8");
+    if ((rc = windowed_row_op("moments_rows", window_rows, rows, qs))) return rc;
     if (ops < 1 || ops > 15) return fail(SPRINTZ_E_INVALID, "moments_rows: ops must be a non-empty OR of SPRINTZ_MOM_COUNT / _SUM / _SUMSQ / _CROSS");
     if (((ops & SPRINTZ_MOM_COUNT) && !d_count) || ((ops & SPRINTZ_MOM_SUM) && !d_sum) || ((ops & SPRINTZ_MOM_SUMSQ) && !d_sumsq) || ((ops & SPRINTZ_MOM_CROSS) && !d_cross))
         return fail(SPRINTZ_E_INVALID, "moments_rows: a selected op without its output buffer");
@@ -1775,17 +1831,9 @@ int sprintz_mi355x_moments_rows(int codec, int elem_bytes, const void* d_comp, c
     if ((ops & SPRINTZ_MOM_CROSS) && ref_col >= ndims) return fail(SPRINTZ_E_INVALID, "moments_rows: ref_col must be a column of the batch");
     if (nchunks == 0) return 0;
     if ((rc = ensure_device())) return rc;
-    const uint32_t rows = chunk_len / ndims;
-    QuerySpec qs;
-    qs.q = kQueryMoments;
-    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.win.rows = window_rows;
-    qs.win.count = (rows + window_rows - 1) / window_rows;
     qs.win.ops = 0;
     qs.win.sum = (ops & SPRINTZ_MOM_SUM) ? d_sum : nullptr;
-    qs.mom.mask = d_mask;
-    qs.mom.mask_stride = (rows + 7) / 8;
-    qs.mom.count = (ops & SPRINTZ_MOM_COUNT) ? d_count : nullptr;
+    qs.win.row_count = (ops & SPRINTZ_MOM_COUNT) ? d_count : nullptr;
     qs.mom.sumsq = (ops & SPRINTZ_MOM_SUMSQ) ? d_sumsq : nullptr;
     qs.mom.cross = (ops & SPRINTZ_MOM_CROSS) ? d_cross : nullptr;
     qs.mom.ref = (ops & SPRINTZ_MOM_CROSS) ? ref_col : 0u;
@@ -1798,34 +1846,28 @@ int sprintz_mi355x_histogram_rows(int codec, int elem_bytes, const void* d_comp,
                                   uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, const void* d_lo, uint32_t shift, uint32_t nbins,
                                   uint64_t hist_chunks, uint32_t flags, uint64_t* d_hist, int64_t* d_rets, void* hip_stream)
 {
-    int rc = check_common(codec, elem_bytes, ndims);
+    QuerySpec qs;
+    uint32_t rows;
+    int rc = masked_row_op("histogram_rows", kQueryHistogram, codec, elem_bytes, d_comp, d_offsets, chunk_len, ndims, flags, d_mask, qs, &rows);
     if (rc) return rc;
-    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "histogram_rows: more than 512 columns", "histogram_rows: the RLE codecs (delta, xff) only",
-                           "histogram_rows"))) return rc;
-    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "histogram_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
-    const uint32_t W = 8u * (uint32_t)elem_bytes;
-    if (shift >= W) return fail(SPRINTZ_E_INVALID, "histogram_rows: shift must be below the element width");
-    if (nbins < 1 || nbins > (1u << (W - shift))) return fail(SPRINTZ_E_INVALID, "histogram_rows: nbins must be in 1..2^(W - shift)");
+    if ((rc = binned_row_op("histogram_rows", elem_bytes, shift, nbins))) return rc;
     if (!d_hist) return fail(SPRINTZ_E_INVALID, "histogram_rows: null device pointer");
     if ((uintptr_t)d_hist % 8 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "histogram_rows: d_hist and d_rets must be aligned to 8 bytes");
     if (d_lo && (uintptr_t)d_lo % (uintptr_t)elem_bytes) return fail(SPRINTZ_E_INVALID, "histogram_rows: d_lo must be aligned to the element size");
     if ((uint64_t)ndims * nbins > SPRINTZ_HIST_MAX_COUNTERS)
         return fail(SPRINTZ_E_UNSUPPORTED, "histogram_rows: ndims x nbins above SPRINTZ_HIST_MAX_COUNTERS: split the bins with d_lo");
-    const uint64_t ngroups = hist_chunks ? (nchunks + hist_chunks - 1) / hist_chunks : 1;
-    if (ngroups > (1ull << 40) / ((uint64_t)ndims * nbins))
-        return fail(SPRINTZ_E_INVALID, "histogram_rows: too many histograms for one call (ngroups x ndims x nbins above 2^40 entries)");
+    uint64_t ngroups;
+    if ((rc = binned_tables(nchunks, hist_chunks, ndims, nbins, "histogram_rows: too many histograms for one call (ngroups x ndims x nbins above 2^40 entries)", &ngroups)))
+        return rc;
     if (nchunks == 0) return 0;
     if ((rc = ensure_device())) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    QuerySpec qs;
-    qs.q = kQueryHistogram;
-    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.hist = HistogramArgs{d_mask, d_lo, d_hist, hist_chunks, shift, nbins, (chunk_len / ndims + 7) / 8, 0, 0};
-    // planned first: a call the planner refuses leaves d_hist as it was
-    const Plan p = plan_decode(decode_shape(codec, elem_bytes, d_comp, nchunks, chunk_len, ndims, nullptr, 0, qs), snapshot());
-    if (p.err) return fail(p.err, p.what);
-    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)(ngroups * ndims * nbins * 8), st));
-    return decode_launch(p, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, st, 0, 0, 0, qs);
+    qs.table = BinTableArgs{hist_chunks, shift, nbins, 0, 0, (uint32_t)ndims * nbins};
+    qs.table_row_max = 1;
+    qs.hist = HistogramArgs{d_lo, d_hist};
+    return binned_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_rets, (hipStream_t)hip_stream, qs, [&](hipStream_t st) {
+        HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)(ngroups * ndims * nbins * 8), st));
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- group-by rows
@@ -1834,16 +1876,13 @@ int sprintz_mi355x_groupby_rows(int codec, int elem_bytes, const void* d_comp, c
                                 uint32_t nbins, uint64_t table_chunks, uint32_t ops, uint32_t flags, uint64_t* d_count, uint64_t* d_sum,
                                 int64_t* d_rets, void* hip_stream)
 {
-    int rc = check_common(codec, elem_bytes, ndims);
+    QuerySpec qs;
+    uint32_t rows;
+    int rc = masked_row_op("groupby_rows", kQueryGroupBy, codec, elem_bytes, d_comp, d_offsets, chunk_len, ndims, flags, d_mask, qs, &rows);
     if (rc) return rc;
-    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "groupby_rows: more than 512 columns", "groupby_rows: the RLE codecs (delta, xff) only",
-                           "groupby_rows"))) return rc;
-    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "groupby_rows: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
-    const uint32_t W = 8u * (uint32_t)elem_bytes;
     if (key_col >= ndims) return fail(SPRINTZ_E_INVALID, "groupby_rows: key_col must be a column of the batch");
-    if (key_lo >= (1u << W)) return fail(SPRINTZ_E_INVALID, "groupby_rows: key_lo must be below 2^W");
-    if (shift >= W) return fail(SPRINTZ_E_INVALID, "groupby_rows: shift must be below the element width");
-    if (nbins < 1 || nbins > (1u << (W - shift))) return fail(SPRINTZ_E_INVALID, "groupby_rows: nbins must be in 1..2^(W - shift)");
+    if (key_lo >= (1u << (8 * elem_bytes))) return fail(SPRINTZ_E_INVALID, "groupby_rows: key_lo must be below 2^W");
+    if ((rc = binned_row_op("groupby_rows", elem_bytes, shift, nbins))) return rc;
     if (ops == 0 || (ops & ~(SPRINTZ_GBY_COUNT | SPRINTZ_GBY_SUM))) return fail(SPRINTZ_E_INVALID, "groupby_rows: ops must be a non-empty OR of SPRINTZ_GBY_COUNT / _SUM");
     if (((ops & SPRINTZ_GBY_COUNT) && !d_count) || ((ops & SPRINTZ_GBY_SUM) && !d_sum))
         return fail(SPRINTZ_E_INVALID, "groupby_rows: a selected op without its output buffer");
@@ -1851,23 +1890,19 @@ int sprintz_mi355x_groupby_rows(int codec, int elem_bytes, const void* d_comp, c
         return fail(SPRINTZ_E_INVALID, "groupby_rows: d_count, d_sum and d_rets must be aligned to 8 bytes");
     if ((uint64_t)nbins * ((uint64_t)ndims + 1) > SPRINTZ_GBY_MAX_COUNTERS)
         return fail(SPRINTZ_E_UNSUPPORTED, "groupby_rows: nbins x (ndims + 1) above SPRINTZ_GBY_MAX_COUNTERS: split the bins with key_lo");
-    const uint64_t ntables = table_chunks ? (nchunks + table_chunks - 1) / table_chunks : 1;
-    if (ntables > (1ull << 40) / ((uint64_t)ndims * nbins))
-        return fail(SPRINTZ_E_INVALID, "groupby_rows: too many tables for one call (ntables x nbins x ndims above 2^40 entries)");
+    uint64_t ntables;
+    if ((rc = binned_tables(nchunks, table_chunks, ndims, nbins, "groupby_rows: too many tables for one call (ntables x nbins x ndims above 2^40 entries)", &ntables)))
+        return rc;
     if (nchunks == 0) return 0;
     if ((rc = ensure_device())) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    QuerySpec qs;
-    qs.q = kQueryGroupBy;
-    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
-    qs.gby = GroupByArgs{d_mask, (chunk_len / ndims + 7) / 8, (ops & SPRINTZ_GBY_COUNT) ? d_count : nullptr, (ops & SPRINTZ_GBY_SUM) ? d_sum : nullptr,
-                         table_chunks, key_col, key_lo, shift, nbins, 0, 0};
-    // planned first: a call the planner refuses leaves the outputs as they were
-    const Plan p = plan_decode(decode_shape(codec, elem_bytes, d_comp, nchunks, chunk_len, ndims, nullptr, 0, qs), snapshot());
-    if (p.err) return fail(p.err, p.what);
-    if (qs.gby.count) HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)(ntables * nbins * 8), st));
-    if (qs.gby.sum) HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)(ntables * nbins * ndims * 8), st));
-    return decode_launch(p, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, st, 0, 0, 0, qs);
+    qs.table = BinTableArgs{table_chunks, shift, nbins, 0, 0, nbins * ((uint32_t)ndims + 1u)};
+    qs.table_row_max = (1u << (8 * elem_bytes)) - 1u;
+    qs.gby = GroupByArgs{(ops & SPRINTZ_GBY_COUNT) ? d_count : nullptr, (ops & SPRINTZ_GBY_SUM) ? d_sum : nullptr, key_col, key_lo};
+    return binned_launch(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, d_rets, (hipStream_t)hip_stream, qs, [&](hipStream_t st) {
+        if (qs.gby.count) HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)(ntables * nbins * 8), st));
+        if (qs.gby.sum) HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)(ntables * nbins * ndims * 8), st));
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- gather rows

@@ -1,22 +1,3 @@
-// decode_aggregate.hip -- the aggregate-rows instantiations (Q = kQueryAggregate) of the generic decoder and of decode_fast, both
-// widths, both codecs.  A translation unit of their own, as decode_select.hip: the kernels of decode_w8.hip / decode_w16.hip keep the
-// code and the flags they had.  decode_uni.h is not taught the mode: its shapes go to the generic kernel.
+// decode_aggregate.hip -- the aggregate-rows unit (launch.h: SPRINTZ_ROW_OP_UNIT).  decode_uni.h is not taught the mode: its shapes go to the generic kernel.
 #include "launch.h"
-namespace sprintz {
-hipError_t decode_generic_aggregate(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
-{
-    if (q != kQueryAggregate) return hipErrorInvalidValue;
-    shmem = 0;                                             // whatever the plan carved: nothing is staged
-    if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, kQueryAggregate) }
-    if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, kQueryAggregate) }
-    return hipErrorInvalidValue;
-}
-// reduce only: every mapping the windowed query has
-hipError_t decode_fast_aggregate(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
-{
-    if (q != kQueryAggregate || ds != 0 || a.col_stride) return hipErrorInvalidValue;
-    if (w == 16) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 16, kQueryAggregate, false) }
-    if (w == 8) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 8, kQueryAggregate, false) }
-    return hipErrorInvalidValue;
-}
-}  // namespace sprintz
+SPRINTZ_ROW_OP_UNIT(aggregate, sprintz::kQueryAggregate, SPRINTZ_DISPATCH_DECODE_FAST_ROWS)

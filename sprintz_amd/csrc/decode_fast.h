@@ -152,6 +152,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // behind the groups' carves (decode_ops.h: groupby_begin .. groupby_end), so, as for the histogram, no lane leaves early.
     constexpr bool GBY = Q == kQueryGroupBy;
     static_assert(!GBY || (!CM && !SPLIT && DS == 0), "group-by: plain mappings");
+    // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select and aggregate take a null mask for "every row"
+    constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY;
+    constexpr bool MASK_GIVEN = SELECT || AGG;             // (no test for a null mask where there always is one: select measured 1 % slower with it)
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -447,21 +450,26 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fb++;
         }
     };
+    // the windowed query's own form of window_advance (decode_ops.h), kept local as its tail below is: through the shared walk the
+    // delta kernels of Q = kQueryWindow came out with other schedules (tools/kernel_diff.py), and this mode keeps its code
     auto win_flush_all = [&]() {                           // window wi of this chunk leaves, every genuine column of the lane
 #pragma unroll
         for (int k = 0; k < CPL; k++)
             if (col_ok[k]) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
-        if constexpr (AGG) aggregate_count_flush(a, wbase + wi, acnt, lane_d);
         wi++;
         wleft = a.win.rows;
     };
-    auto mom_flush_all = [&]() {                           // the same for the moments' entries
+    // aggregate and moments rows: `n` rows of window wi of this chunk are done (window_advance); a window that leaves takes the
+    // entries of every genuine column of the lane along, and its count of selected rows
+    auto window_rows_done = [&](uint32_t n) {
+        window_advance<true>(a, n, wbase, wi, wleft, acnt, lane_d, [&](uint64_t w) {
 #pragma unroll
-        for (int k = 0; k < CPL; k++)
-            if (col_ok[k]) moments_flush(a, (wbase + wi) * (uint64_t)D + (uint64_t)genk[k], macc[k]);
-        moments_count_flush(a, wbase + wi, acnt, lane_d);
-        wi++;
-        wleft = a.win.rows;
+            for (int k = 0; k < CPL; k++) {
+                if (!col_ok[k]) continue;
+                if constexpr (MOM) moments_flush(a, w * (uint64_t)D + (uint64_t)genk[k], macc[k]);
+                else win_flush<W>(a, w * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
+            }
+        });
     };
     auto q_window = [&]() {                                // after every block of 8 rows
         if constexpr (Q == kQueryWindow) {
@@ -471,8 +479,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (AGG) {                               // the block's selected rows are counted, then as above
             acnt += (uint32_t)__popc(sm);
             fb++;
-            wleft -= 8;
-            if (wleft == 0) win_flush_all();
+            window_rows_done(8u);
         }
         if constexpr (HIST) fb++;
         if constexpr (MOM) {
@@ -487,8 +494,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             acnt += (uint32_t)__popc(sm);
             fb++;
-            wleft -= 8;
-            if (wleft == 0) mom_flush_all();
+            window_rows_done(8u);
         }
         if constexpr (GBY) {
             // sm is the group's: every lane of it takes part in the exchange of the key column's rows
@@ -521,24 +527,17 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // load from memory sits between a block's header and its stores.  (A chunk's mask starts at any address, and its last dword may be
     // short: those bytes are read one by one.)
     uint32_t mwin = 0, mwin0 = 0x80000000u;
-    auto sel_stride = [&]() -> uint32_t {
-        if constexpr (AGG) return a.agg.mask_stride;
-        else if constexpr (HIST) return a.hist.mask_stride;
-        else if constexpr (MOM) return a.mom.mask_stride;
-        else if constexpr (GBY) return a.gby.mask_stride;
-        else return a.select.mask_stride;
-    };
     auto sel_byte = [&](uint32_t b) -> uint32_t {
         if (b - mwin0 >= 4u * DP) {
             mwin0 = b & ~3u;
             const uint32_t o = mwin0 + 4u * (uint32_t)lane_d;
             mwin = 0;
-            if (o + 4u <= sel_stride()) {
+            if (o + 4u <= a.rows.stride) {
                 mwin = *(const u32_unaligned*)(smb + o);
             } else {
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; j++)
-                    if (o + j < sel_stride()) mwin |= (uint32_t)smb[o + j] << (8u * j);
+                    if (o + j < a.rows.stride) mwin |= (uint32_t)smb[o + j] << (8u * j);
             }
         }
         const uint32_t i = b - mwin0;
@@ -744,17 +743,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             return;
         }
         if constexpr (AGG && !FIRE) {
-            // a delta run repeats the previous row 8 len times: per window it touches, the selected rows among them are counted -- the set
-            // bits of the run's mask bytes in that window, spread over the group's lanes -- min / max take the row once if there is one,
-            // and the sum takes it times their number.  (The bytes lie inside the chunk's: the run fits the chunk slot.)
+            // a delta run repeats the previous row 8 len times: per window it touches, the selected rows among them are counted
+            // (run_selected_rows), min / max take the row once if there is one, and the sum takes it times their number
             if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
             out_left -= len * blk_elems;
             uint32_t blocks = len;
             while (blocks > 0) {
                 const uint32_t nb = blocks < (wleft >> 3) ? blocks : (wleft >> 3);
-                uint32_t c = 0;
-                for (uint32_t j = (uint32_t)lane_d; j < nb; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
-                c = group_sum(c, DP);
+                const uint32_t c = run_selected_rows(smb, fb, nb, lane_d, DP);
                 if (c != 0) {
 #pragma unroll
                     for (int k = 0; k < CPL; k++) {
@@ -767,27 +763,20 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 }
                 blocks -= nb;
                 fb += nb;
-                wleft -= 8u * nb;
-                if (wleft == 0) win_flush_all();
+                window_rows_done(8u * nb);
             }
             return;
         }
         if constexpr (MOM && !FIRE) {
-            // a delta run repeats the previous row 8 len times: per window it touches, c = the selected rows among them -- the set bits of
-            // the run's mask bytes in that window, spread over the group's lanes; all of them without a mask -- and each sum takes its
-            // term times c.  The reference column's value is one exchange a run.  (The bytes lie inside the chunk's: the run fits the slot.)
+            // a delta run repeats the previous row 8 len times: per window it touches, c = the selected rows among them (run_selected_rows),
+            // and each sum takes its term times c.  The reference column's value is one exchange a run.
             if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
             out_left -= len * blk_elems;
             const uint32_t xr = moments_ref_value<W, CPL>(a.mom.ref, DP, pv);
             uint32_t blocks = len;
             while (blocks > 0) {
                 const uint32_t nb = blocks < (wleft >> 3) ? blocks : (wleft >> 3);
-                uint32_t c = 8u * nb;
-                if (smb) {
-                    c = 0;
-                    for (uint32_t j = (uint32_t)lane_d; j < nb; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
-                    c = group_sum(c, DP);
-                }
+                const uint32_t c = run_selected_rows(smb, fb, nb, lane_d, DP);
                 if (c != 0) {
 #pragma unroll
                     for (int k = 0; k < CPL; k++) moments_value(macc[k], pv[k] & MASK, xr, c);
@@ -795,39 +784,25 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 }
                 blocks -= nb;
                 fb += nb;
-                wleft -= 8u * nb;
-                if (wleft == 0) mom_flush_all();
+                window_rows_done(8u * nb);
             }
             return;
         }
         if constexpr (GBY && !FIRE) {
             // a delta run repeats the previous row 8 len times: its key, and so its bin, is one -- each column adds its value times the
-            // run's selected rows (the set bits of its mask bytes, spread over the group's lanes; 8 len without a mask), one lane adds
-            // their number.  The key column's value is one exchange a run.  (The bytes lie inside the chunk's: the run fits the slot.)
+            // run's selected rows (run_selected_rows), one lane adds their number.  The key column's value is one exchange a run.
             if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
             out_left -= len * blk_elems;
-            uint32_t c = 8u * len;
-            if (smb) {
-                c = 0;
-                for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
-                c = group_sum(c, DP);
-            }
+            const uint32_t c = run_selected_rows(smb, fb, len, lane_d, DP);
             groupby_value<W, CPL>(gctx, pv, moments_ref_value<W, CPL>(a.gby.key, DP, pv), c, genk, col_ok, lane_d);
             fb += len;
             return;
         }
         if constexpr (HIST && !FIRE) {
-            // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows -- the set
-            // bits of its mask bytes, spread over the group's lanes; 8 len without a mask.  (The bytes lie inside the chunk's: the run
-            // fits the chunk slot.)
+            // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows (run_selected_rows)
             if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
             out_left -= len * blk_elems;
-            uint32_t c = 8u * len;
-            if (smb) {
-                c = 0;
-                for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) c += (uint32_t)__popc((uint32_t)smb[fb + j]);
-                c = group_sum(c, DP);
-            }
+            const uint32_t c = run_selected_rows(smb, fb, len, lane_d, DP);
 #pragma unroll
             for (int k = 0; k < CPL; k++)
                 if (col_ok[k]) hist_value<W>(hctx, hcol[k], pv[k], c);
@@ -864,8 +839,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 sm = sel_byte(fb);
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
             }
-            if constexpr (AGG) sm = sel_byte(fb);          // (a FIRE run is replayed for its state, block by block, as the window mode does)
-            if constexpr (HIST || MOM || GBY) sm = smb ? sel_byte(fb) : 0xffu;
+            if constexpr (MASKED && !SELECT) sm = (MASK_GIVEN || smb) ? sel_byte(fb) : 0xffu;   // (a FIRE run is replayed for its state, block by block, as the window mode does)
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -986,8 +960,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto packed_block = [&](const int (&e)[CPL][8], int slot) {   // forecast recurrence (:993-1150)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
-        if constexpr (SELECT || AGG) sm = sel_byte(fb);    // (block fb < chunk_len / blk_elems <= mask_stride: the guard has passed)
-        if constexpr (HIST || MOM || GBY) sm = smb ? sel_byte(fb) : 0xffu;
+        if constexpr (MASKED) sm = (MASK_GIVEN || smb) ? sel_byte(fb) : 0xffu;   // (block fb < chunk_len / blk_elems <= rows.stride: the guard has passed)
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -1112,35 +1085,20 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             wi = 0;
             wleft = a.win.rows;
             wbase = chunk * (uint64_t)a.win.count;
+        }
+        if constexpr (MASKED) {                            // the chunk's mask bytes (null: every row), its blocks done, its window's selected rows
             fb = 0; sm = 0; acnt = 0;
             mwin0 = 0x80000000u;                           // no window yet: the first block loads one
-            smb = a.mom.mask ? a.mom.mask + chunk * (uint64_t)a.mom.mask_stride : nullptr;
+            smb = (MASK_GIVEN || a.rows.mask) ? a.rows.mask + chunk * (uint64_t)a.rows.stride : nullptr;
         }
         if constexpr (Q == kQueryFilter) {
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
             fmb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
         }
-        if constexpr (AGG) {
-            fb = 0; sm = 0; acnt = 0;
-            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
-            smb = a.agg.mask + chunk * (uint64_t)a.agg.mask_stride;
-        }
-        if constexpr (HIST) {
-            fb = 0; sm = 0;
-            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
-            smb = a.hist.mask ? a.hist.mask + chunk * (uint64_t)a.hist.mask_stride : nullptr;
-            hctx.g = hist_of_chunk(a, chunk);
-        }
-        if constexpr (GBY) {
-            fb = 0; sm = 0;
-            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
-            smb = a.gby.mask ? a.gby.mask + chunk * (uint64_t)a.gby.mask_stride : nullptr;
-            groupby_of_chunk(a, gctx, chunk);
-        }
+        if constexpr (HIST) hctx.g = hist_of_chunk(a, chunk);
+        if constexpr (GBY) groupby_of_chunk(a, gctx, chunk);
         if constexpr (SELECT) {
-            fb = 0; srank = 0; sm = 0;
-            mwin0 = 0x80000000u;                           // no window yet: the first block loads one
-            smb = a.select.mask + chunk * (uint64_t)a.select.mask_stride;
+            srank = 0;
             sbase = a.select.bases[chunk];
             srow0 = chunk * (uint64_t)a.select.rpc;
         }

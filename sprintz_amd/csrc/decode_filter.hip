@@ -1,22 +1,8 @@
-// decode_filter.hip -- the filter-rows instantiations (Q = kQueryFilter) of the three decoder families, both widths, and the kernel
-// that turns a mask into row numbers.  A translation unit of their own, as decode_gather.hip: the kernels of decode_w8.hip /
-// decode_w16.hip keep the code and the flags they had.
+// decode_filter.hip -- the filter-rows unit (launch.h: SPRINTZ_ROW_OP_UNIT), decode_uni's instantiations of the mode and the kernel
+// that turns a mask into row numbers.
 #include "launch.h"
+SPRINTZ_ROW_OP_UNIT(filter, sprintz::kQueryFilter, SPRINTZ_DISPATCH_DECODE_FAST_ROWS)
 namespace sprintz {
-hipError_t decode_generic_filter(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
-{
-    if (q != kQueryFilter) return hipErrorInvalidValue;
-    if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, kQueryFilter) }
-    if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, kQueryFilter) }
-    return hipErrorInvalidValue;
-}
-hipError_t decode_fast_filter(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
-{
-    if (q != kQueryFilter || ds != 0 || a.col_stride) return hipErrorInvalidValue;
-    if (w == 8) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 8, kQueryFilter, false) }
-    if (w == 16) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 16, kQueryFilter, false) }
-    return hipErrorInvalidValue;
-}
 #define SPRINTZ_UNI_FILTER_CASE(WV, NDV)                                                                              \
     if (w == WV && nd == NDV) {                                                                                       \
         constexpr int tpb = decode_uni_threads(WV, NDV);                                                              \

@@ -1,22 +1,3 @@
-// decode_histogram.hip -- the histogram-rows instantiations (Q == kQueryHistogram) of the generic decoder and of decode_fast, both
-// widths, both codecs.  A translation unit of their own, as decode_aggregate.hip: the kernels of decode_w8.hip / decode_w16.hip keep the
-// code and the flags they had.  decode_uni.h is not taught the mode: its shapes go to the generic kernel.
+// decode_histogram.hip -- the histogram-rows unit (launch.h: SPRINTZ_ROW_OP_UNIT).  decode_uni.h is not taught the mode: its shapes go to the generic kernel.
 #include "launch.h"
-namespace sprintz {
-// shmem is the workgroup's table of counters alone: nothing is staged (plan.h)
-hipError_t decode_generic_histogram(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
-{
-    if (q != kQueryHistogram) return hipErrorInvalidValue;
-    if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, kQueryHistogram) }
-    if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, kQueryHistogram) }
-    return hipErrorInvalidValue;
-}
-// reduce only: every mapping the windowed query has; shmem is the groups' carves with the table behind them
-hipError_t decode_fast_histogram(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
-{
-    if (q != kQueryHistogram || ds != 0 || a.col_stride) return hipErrorInvalidValue;
-    if (w == 16) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 16, kQueryHistogram, false) }
-    if (w == 8) { SPRINTZ_DISPATCH_DECODE_FAST_Q(decode_fast_kernel, 8, kQueryHistogram, false) }
-    return hipErrorInvalidValue;
-}
-}  // namespace sprintz
+SPRINTZ_ROW_OP_UNIT(histogram, sprintz::kQueryHistogram, SPRINTZ_DISPATCH_DECODE_FAST_ROWS)

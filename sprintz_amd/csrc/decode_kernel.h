@@ -23,13 +23,17 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     constexpr uint32_t MASK = Elem<W>::MASK;
     constexpr int ESZ = W / 8;
     // HIST (sprintz_mi355x_histogram_rows): the workgroup's lanes meet at two barriers -- behind the zeroing of its table and in front of
-    // the table's merge (decode_ops.h: hist_begin, hist_end) -- so in this mode no lane leaves early: a group past the last chunk
+    // the table's merge (decode_ops.h: table_begin, table_end) -- so in this mode no lane leaves early: a group past the last chunk
     // (hlive false) and a chunk whose header is refused (hbad) walk on as empty streams.
     constexpr bool HIST = Q == kQueryHistogram;
-    // GBY (sprintz_mi355x_groupby_rows): the same two barriers around its table (groupby_begin, groupby_end), so the same rule -- TAB is
+    // GBY (sprintz_mi355x_groupby_rows): the same two barriers around its table, so the same rule -- TAB is
     // either mode.  The block's rows of every column wait behind the column loop for the key column's, as the moments' do.
     constexpr bool GBY = Q == kQueryGroupBy;
     constexpr bool TAB = HIST || GBY;
+    constexpr bool MOM = Q == kQueryMoments;
+    // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs), and those of them that count a window's selected rows
+    constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY;
+    constexpr bool COUNTED = Q == kQueryAggregate || MOM;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int DP = 1 << a.log2DP;
@@ -141,18 +145,20 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         wleft = a.win.rows;
         wbase = chunk * (uint64_t)a.win.count;
     }
-    // moments rows (MOM): the lane's accumulators, the chunk's mask bytes (null: every row), the mask byte of the block being decoded and
-    // the selected rows of the window so far; the windows are the windowed query's
-    constexpr bool MOM = Q == kQueryMoments;
+    // moments rows (MOM): the lane's accumulators; the windows are the windowed query's
     MomentAcc macc[CPL];
-    const uint8_t* mmb = nullptr;
-    uint32_t mm = 0xffu, mcnt = 0;
     if constexpr (MOM) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) macc[k] = MomentAcc{0, 0, 0};
         wleft = a.win.rows;
         wbase = chunk * (uint64_t)a.win.count;
-        if (a.mom.mask) mmb = a.mom.mask + chunk * (uint64_t)a.mom.mask_stride;
+    }
+    // the masked modes: the chunk's mask bytes (null: every row), the mask byte of the block being decoded and the selected rows of the
+    // window so far
+    const uint8_t* smb = nullptr;
+    uint32_t sm = 0xffu, acnt = 0;
+    if constexpr (MASKED) {
+        if (a.rows.mask) smb = a.rows.mask + chunk * (uint64_t)a.rows.stride;
     }
     // filter rows: each lane's columns' bounds, loaded once; the group ORs its lanes' block masks with wave shuffles (groups of up to
     // 64 lanes, both layouts), lane 0 stores the block's byte -- runs are replayed block by block here, as the decode does
@@ -166,35 +172,19 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if (a.filter.mask) fmb = a.filter.mask + chunk * (uint64_t)a.filter.mask_stride;
     }
 
-    // select rows: the chunk's mask bytes, its first output row and the set bits of the blocks done so far
-    const uint8_t* smb = nullptr;
+    // select rows: the chunk's first output row and the set bits of the blocks done so far
     uint64_t sbase = 0;
     uint32_t srank = 0;
-    if constexpr (Q == kQuerySelect) {
-        smb = a.select.mask + chunk * (uint64_t)a.select.mask_stride;
-        sbase = a.select.bases[chunk];
-    }
-    // aggregate rows: the chunk's mask bytes, the mask byte of the block being decoded and the selected rows of the window so far
-    const uint8_t* amb = nullptr;
-    uint32_t am = 0, acnt = 0;
-    if constexpr (Q == kQueryAggregate) amb = a.agg.mask + chunk * (uint64_t)a.agg.mask_stride;
-    // histogram rows: the lane's columns, the chunk's histogram and mask bytes (null: every row), the mask byte of the block being decoded
+    if constexpr (Q == kQuerySelect) sbase = a.select.bases[chunk];
+    // histogram rows: the lane's columns and the chunk's histogram
     HistCol hcol[CPL];
-    const uint8_t* hmb = nullptr;
-    uint32_t hm = 0xffu;
     if constexpr (HIST) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) hcol[k] = hist_col<W>(a, colk[k], genk[k]);
         hctx.g = hist_of_chunk(a, chunk);
-        if (a.hist.mask) hmb = a.hist.mask + chunk * (uint64_t)a.hist.mask_stride;
     }
-    // group-by rows: the chunk's table and mask bytes (null: every row), the mask byte of the block being decoded
-    const uint8_t* gmb = nullptr;
-    uint32_t gm = 0xffu;
-    if constexpr (GBY) {
-        groupby_of_chunk(a, gctx, chunk);
-        if (a.gby.mask) gmb = a.gby.mask + chunk * (uint64_t)a.gby.mask_stride;
-    }
+    // group-by rows: the chunk's table
+    if constexpr (GBY) groupby_of_chunk(a, gctx, chunk);
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -252,17 +242,11 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     else pos += 1;
                     slot++;
                     if constexpr (HIST && !FIRE) {
-                        // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows --
-                        // the set bits of its mask bytes, spread over the group's lanes (they lie inside the chunk's: the run fits the slot)
+                        // a delta run repeats the previous row 8 len times: each column's value takes ONE add of the run's selected rows
+                        // (run_selected_rows: every lane of the group comes by)
                         if (len > 0) {
                             if ((uint64_t)out_elems + (uint64_t)len * blk_elems > a.chunk_len) { corrupt = true; break; }
-                            const uint32_t b0r = out_elems / blk_elems;
-                            uint32_t c = 8u * len;
-                            if (hmb) {
-                                c = 0;
-                                for (uint32_t j = (uint32_t)lane_d; j < len; j += (uint32_t)DP) c += (uint32_t)__popc((uint32_t)hmb[b0r + j]);
-                                c = group_sum(c, DP);
-                            }
+                            const uint32_t c = run_selected_rows(smb, out_elems / blk_elems, len, lane_d, DP);
 #pragma unroll
                             for (int k = 0; k < CPL; k++)
                                 if (genk[k]) hist_value<W>(hctx, hcol[k], pv[k], c);
@@ -275,13 +259,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                         // times the run's selected rows, one lane their number; the key column's value is one exchange a run
                         if (len > 0) {
                             if ((uint64_t)out_elems + (uint64_t)len * blk_elems > a.chunk_len) { corrupt = true; break; }
-                            const uint32_t b0r = out_elems / blk_elems;
-                            uint32_t c = 8u * len;
-                            if (gmb) {
-                                c = 0;
-                                for (uint32_t j = (uint32_t)lane_d; j < len; j += (uint32_t)DP) c += (uint32_t)__popc((uint32_t)gmb[b0r + j]);
-                                c = group_sum(c, DP);
-                            }
+                            const uint32_t c = run_selected_rows(smb, out_elems / blk_elems, len, lane_d, DP);
                             groupby_value<W, CPL>(gctx, pv, moments_ref_value<W, CPL>(a.gby.key, DP, pv), c, colk, genk, lane_d);
                             out_elems += len * blk_elems;
                         }
@@ -331,10 +309,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         uint32_t v[8][CPL];
         uint32_t fl = 0;                         // filter: this lane's columns' rows, inverted domain
         // (block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride: checked above; all 8 rows of a block exist)
-        if constexpr (Q == kQueryAggregate) am = amb[out_elems / blk_elems];
-        if constexpr (HIST) hm = hmb ? (uint32_t)hmb[out_elems / blk_elems] : 0xffu;
-        if constexpr (MOM) mm = mmb ? (uint32_t)mmb[out_elems / blk_elems] : 0xffu;
-        if constexpr (GBY) gm = gmb ? (uint32_t)gmb[out_elems / blk_elems] : 0xffu;
+        // (select and aggregate rows always have a mask: no test for them)
+        if constexpr (MASKED) sm = (Q == kQuerySelect || Q == kQueryAggregate || smb) ? (uint32_t)smb[out_elems / blk_elems] : 0xffu;
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -363,18 +339,18 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 for (int i = 0; i < 8; i++) cm |= filter_hit<W>(fc[k], v[i][k]) << i;
                 fl |= genk[k] ? (cm ^ finv) & 0xffu : 0u;
             } else if constexpr (Q == kQueryAggregate) {
-                if (am) {                        // (a block none of whose rows the mask names only moves the predictor on)
+                if (sm) {                        // (a block none of whose rows the mask names only moves the predictor on)
                     uint32_t bs = 0;
 #pragma unroll
-                    for (int i = 0; i < 8; i++) aggregate_row<W>(v[i][k], aggregate_sel<W>(am, i), qmin[k], qmax[k], bs);
+                    for (int i = 0; i < 8; i++) aggregate_row<W>(v[i][k], aggregate_sel<W>(sm, i), qmin[k], qmax[k], bs);
                     qsum[k] += bs;
                 }
             } else if constexpr (HIST) {
-                if (hm != 0 && genk[k]) {
+                if (sm != 0 && genk[k]) {
                     uint32_t xs[8];
 #pragma unroll
                     for (int i = 0; i < 8; i++) xs[i] = v[i][k];
-                    hist_rows8<W>(hctx, hcol[k], xs, hm);
+                    hist_rows8<W>(hctx, hcol[k], xs, sm);
                 }
             } else if constexpr (MOM || GBY) {   // (the products / the adds wait for the reference / key column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
@@ -389,44 +365,38 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             }
         }
         if constexpr (MOM) {
-            // the reference column's 8 rows come from the lane that decoded them -- every lane of the group takes part, mm is the group's --
-            // then each column's rows are multiplied and added; the block's 8 rows lie in one window: flush it when they complete it
-            if (mm != 0) {
+            // the reference column's 8 rows come from the lane that decoded them -- every lane of the group takes part, sm is the group's --
+            // then each column's rows are multiplied and added
+            if (sm != 0) {
                 uint32_t xr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
                 const bool cross = a.mom.cross != nullptr;
                 if (cross) moments_ref_rows<W, CPL>(a.mom.ref, DP, [&](int k, int i) { return v[i][k]; }, xr);
 #pragma unroll
-                for (int k = 0; k < CPL; k++) moments_rows8<W>(macc[k], [&](int i) { return v[i][k]; }, xr, mm, cross);
-            }
-            mcnt += (uint32_t)__popc(mm);
-            wleft -= 8;
-            if (wleft == 0) {
-#pragma unroll
-                for (int k = 0; k < CPL; k++)
-                    if (genk[k]) moments_flush(a, (wbase + wi) * (uint64_t)D + (uint64_t)colk[k], macc[k]);
-                moments_count_flush(a, wbase + wi, mcnt, lane_d);
-                wi++;
-                wleft = a.win.rows;
+                for (int k = 0; k < CPL; k++) moments_rows8<W>(macc[k], [&](int i) { return v[i][k]; }, xr, sm, cross);
             }
         }
         if constexpr (GBY) {
-            // the key column's 8 rows come from the lane that decoded them -- every lane of the group takes part, gm is the group's
-            if (gm != 0) {
+            // the key column's 8 rows come from the lane that decoded them -- every lane of the group takes part, sm is the group's
+            if (sm != 0) {
                 uint32_t xk[8];
                 moments_ref_rows<W, CPL>(a.gby.key, DP, [&](int k, int i) { return v[i][k]; }, xk);
-                groupby_rows8<W, CPL>(gctx, [&](int k, int i) { return v[i][k]; }, xk, gm, colk, genk, lane_d);
+                groupby_rows8<W, CPL>(gctx, [&](int k, int i) { return v[i][k]; }, xk, sm, colk, genk, lane_d);
             }
         }
-        if constexpr (Q == kQueryWindow || Q == kQueryAggregate) {       // the block's 8 rows lie in one window: flush it when they complete it
-            if constexpr (Q == kQueryAggregate) acnt += (uint32_t)__popc(am);
+        if constexpr (Q == kQueryWindow || COUNTED) {
+            // the block's 8 rows lie in one window: it leaves when they complete it.  This is window_advance (decode_ops.h) written out:
+            // called here, hipcc gave three of the aggregate kernels with 8 columns a lane scratch or a wave less (tools/kernel_regs.sh)
+            if constexpr (COUNTED) acnt += (uint32_t)__popc(sm);
             wleft -= 8;
             if (wleft == 0) {
 #pragma unroll
                 for (int k = 0; k < CPL; k++) {
                     const int col = lane_d * CPL + k;
-                    if (col < D) win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
+                    if (col >= D) continue;
+                    if constexpr (MOM) moments_flush(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, macc[k]);
+                    else win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
                 }
-                if constexpr (Q == kQueryAggregate) aggregate_count_flush(a, wbase + wi, acnt, lane_d);
+                if constexpr (COUNTED) window_count_flush(a, wbase + wi, acnt, lane_d);
                 wi++;
                 wleft = a.win.rows;
             }
@@ -462,7 +432,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             // chunk_len / blk_elems <= mask_stride: checked above); 64-bit addresses, a place >= capacity is dropped
             (void)ob;
             const uint32_t r0 = out_elems / (uint32_t)D;
-            const uint32_t m = smb[r0 >> 3];
+            const uint32_t m = sm;
             const uint64_t first = sbase + srank;
             if (m) {
 #pragma unroll
@@ -548,23 +518,23 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if (!corrupt) window_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum);
     } else if constexpr (Q == kQueryAggregate) {
         if (!corrupt) aggregate_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
-                                             [&](uint32_t b) { return (uint32_t)amb[b]; });
+                                             [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (MOM) {
-        if (!corrupt) moments_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, macc, mcnt, lane_d,
-                                           [&](uint32_t b) { return (uint32_t)mmb[b]; });
+        if (!corrupt) moments_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, macc, acnt, lane_d,
+                                           [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) reduce_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, colk, genk, qmax, qsum);      // (out_elems is a multiple of 8*D)
     }
     if constexpr (HIST) {
         if (!corrupt) hist_tail<W, CPL>(a, hctx, hcol, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk,
-                                        [&](uint32_t b) { return (uint32_t)hmb[b]; });
+                                        [&](uint32_t b) { return (uint32_t)smb[b]; });
         if (hlive && lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         hist_end(a, hctx);
         return;
     }
     if constexpr (GBY) {
         if (!corrupt) groupby_tail<W, CPL>(a, gctx, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, lane_d,
-                                           [&](uint32_t b) { return (uint32_t)gmb[b]; });
+                                           [&](uint32_t b) { return (uint32_t)smb[b]; });
         if (hlive && lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         groupby_end(a, gctx);
         return;

@@ -1,8 +1,11 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments and group-by rows): each one's arguments, its per-block helpers and its verbatim tail, written once for every lane mapping.  A kernel hands over
-// its lane's columns (`col`, with `genuine` false for a lane column past the last one), its place in the group (`lane_d` of `DP`
-// lanes) and the mode's running state; decode_uni.h is the lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane
-// mapping -- how a block's rows reach the accumulators, the staging and the stores -- stays in that kernel.
+// aggregate, histogram, moments and group-by rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
+// run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
+// bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
+// column past the last one), its place in the group (`lane_d` of `DP` lanes) and the mode's running state; decode_uni.h is the
+// lane_d = 0, DP = 1, CPL = D = ND case.  What depends on a kernel's lane mapping -- how a block's rows reach the accumulators, the
+// staging and the stores -- stays in that kernel.
 #pragma once
 
 #include "sprintz_device.h"
@@ -10,7 +13,8 @@
 namespace sprintz {
 
 // windowed query (Q == kQueryWindow; sprintz_mi355x_query_windows): chunk c, window w (rows [w*W, (w+1)*W) of the chunk
-// slot) and column d land at entry (c*count + w)*D + d of each selected output
+// slot) and column d land at entry (c*count + w)*D + d of each selected output.  Aggregate and moments rows walk the same windows
+// and may count each one's selected rows: chunk c's window w in row_count[c * count + w]
 struct WindowArgs {
     uint32_t rows;              // W, a multiple of 8: a block of 8 rows never straddles a window edge
     uint32_t count;             // windows per chunk slot: ceil(ceil(chunk_len / D) / W)
@@ -18,6 +22,7 @@ struct WindowArgs {
     void* min;                  // element type
     void* max;                  // element type
     uint64_t* sum;
+    uint32_t* row_count;        // optional (SPRINTZ_AGG_COUNT, SPRINTZ_MOM_COUNT)
 };
 // gather rows (Q == kQueryGather; sprintz_mi355x_gather_rows): range i is batch rows [starts[i], starts[i] + rows), batch row g
 // being row g % rpc of chunk g / rpc; piece slot s = i * pieces + k decodes chunk starts[i] / rpc + k (gather_piece below)
@@ -38,67 +43,55 @@ struct FilterArgs {
     uint32_t* counts;           // optional
     uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
 };
-// select rows (Q == kQuerySelect; sprintz_mi355x_select_rows): the i-th set bit of chunk c's mask bytes mask[c * mask_stride ...]
-// (filter_rows' layout), row r, lands at row bases[c] + i of `out` and c * rpc + r at the same place of ids; a place
-// >= capacity is dropped
+// the rows that select, aggregate, histogram, moments and group-by rows take: those whose bits are set in chunk c's mask bytes
+// mask[c * stride ...] (filter_rows' layout).  mask == null -- where the operation allows it -- is every existing row: a run-time,
+// wave-uniform switch, as filter.mode is
+struct RowMaskArgs {
+    const uint8_t* mask;        // [nchunks][stride]
+    uint32_t stride;            // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
+};
+// the table of bins that histogram and group-by rows fill: bin b = ((x - lo) mod 2^W) >> shift of a column's value x takes an add if
+// b < nbins, in table c / span_chunks of the outputs.  A workgroup decodes the wg_chunks consecutive chunks from blockIdx.x * wg_chunks
+// on and adds them up in its own table of `entries` uint32 at byte table_off of its dynamic LDS -- if they all lie in one table of the
+// outputs; if not (or wg_chunks == 0: the planner found that an entry could wrap) every add goes to the outputs directly
+struct BinTableArgs {
+    uint64_t span_chunks;       // H; 0: the whole batch is one table
+    uint32_t shift, nbins;
+    uint32_t table_off;
+    uint32_t wg_chunks;
+    uint32_t entries;           // histogram: D * nbins counters; group-by: nbins * D sums, then nbins counts
+};
+// select rows (Q == kQuerySelect; sprintz_mi355x_select_rows): the i-th set bit of chunk c's mask bytes, row r, lands at row
+// bases[c] + i of `out` and c * rpc + r at the same place of ids; a place >= capacity is dropped
 struct SelectArgs {
-    const uint8_t* mask;        // [nchunks][mask_stride]
     const uint64_t* bases;      // [nchunks]
     uint64_t capacity;          // rows of `out` (and entries of ids)
     uint64_t* ids;              // optional
     uint32_t rpc;               // rows of a chunk slot, chunk_len / D
-    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rpc / 8)
 };
-// aggregate rows (Q == kQueryAggregate; sprintz_mi355x_aggregate_rows): the windowed query over the rows whose bits are set in chunk c's
-// mask bytes mask[c * mask_stride ...] (filter_rows' layout) alone.  The windows, the selected ops and the min / max / sum outputs are
-// WindowArgs' (`win`); the number of selected rows of chunk c's window w lands in count[c * win.count + w]
-struct AggregateArgs {
-    const uint8_t* mask;        // [nchunks][mask_stride]
-    uint32_t* count;            // optional (SPRINTZ_AGG_COUNT)
-    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
-};
-// histogram rows (Q == kQueryHistogram; sprintz_mi355x_histogram_rows): value x of column d, in a row whose bit is set in chunk c's mask
-// bytes (filter_rows' layout; no mask: every existing row), counts in bin b = ((x - lo[d]) mod 2^W) >> shift of histogram c / group_chunks
-// if b < nbins, and nowhere otherwise: hist[(g * D + d) * nbins + b].  A workgroup decodes the wg_chunks consecutive chunks from
-// blockIdx.x * wg_chunks on and counts them in its own table of D * nbins uint32 at byte table_off of its dynamic LDS -- if they all lie
-// in one histogram; if not (or wg_chunks == 0: the planner found that a counter could wrap) every sample goes to `hist` directly
+// aggregate rows (Q == kQueryAggregate; sprintz_mi355x_aggregate_rows) is the windowed query over the mask's rows alone: the windows,
+// the selected ops, the min / max / sum outputs and the count are WindowArgs', the rows RowMaskArgs'
+// histogram rows (Q == kQueryHistogram; sprintz_mi355x_histogram_rows): value x of column d, in a row the mask names, counts in bin b of
+// lo[d] (BinTableArgs) of histogram g = c / span_chunks: hist[(g * D + d) * nbins + b]
 struct HistogramArgs {
-    const uint8_t* mask;        // [nchunks][mask_stride], or null: a run-time, wave-uniform switch, as filter.mode is
     const void* lo;             // [D], element type, on the device, or null: all zero
     uint64_t* hist;             // [ngroups][D][nbins], zeroed on the stream in front of the launch
-    uint64_t group_chunks;      // H; 0: the whole batch is one histogram
-    uint32_t shift, nbins;
-    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
-    uint32_t table_off;
-    uint32_t wg_chunks;
 };
-// moments rows (Q == kQueryMoments; sprintz_mi355x_moments_rows): over the rows whose bits are set in chunk c's mask bytes mask[c *
-// mask_stride ...] (filter_rows' layout; no mask: every existing row), per chunk-relative window w (WindowArgs' rows and count) their
-// number in count[c * win.count + w] and, per column d at (c * win.count + w) * D + d, the sum of x_d in win.sum, of x_d^2 in sumsq and
-// of x_d * x_ref in cross.  An output that is null is not selected
+// moments rows (Q == kQueryMoments; sprintz_mi355x_moments_rows): over the rows the mask names, per chunk-relative window w
+// (WindowArgs' rows, count and row_count) and per column d at (c * win.count + w) * D + d, the sum of x_d in win.sum, of x_d^2 in sumsq
+// and of x_d * x_ref in cross.  An output that is null is not selected
 struct MomentArgs {
-    const uint8_t* mask;        // [nchunks][mask_stride], or null: a run-time, wave-uniform switch, as hist.mask is
-    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
-    uint32_t* count;            // optional (SPRINTZ_MOM_COUNT)
     uint64_t* sumsq;            // optional (SPRINTZ_MOM_SUMSQ)
     uint64_t* cross;            // optional (SPRINTZ_MOM_CROSS)
     uint32_t ref;               // the reference column (< D; 0 where cross is null)
 };
-// group-by rows (Q == kQueryGroupBy; sprintz_mi355x_groupby_rows): a row whose bit is set in chunk c's mask bytes (filter_rows' layout; no
-// mask: every existing row) and whose key column holds x belongs to bin b = ((x - key_lo) mod 2^W) >> shift of table c / table_chunks if
-// b < nbins, and to none otherwise: count[t * nbins + b] takes 1 and sum[(t * nbins + b) * D + d] takes x_d, every column d.  A workgroup
-// decodes the wg_chunks consecutive chunks from blockIdx.x * wg_chunks on and adds them up in its own table of uint32 -- nbins * D sums, then
-// nbins counts -- at byte table_off of its dynamic LDS, if they all lie in one table; if not (or wg_chunks == 0: the planner found that a
-// sum could wrap) every add goes to `count` / `sum` directly.  An output that is null is not selected
+// group-by rows (Q == kQueryGroupBy; sprintz_mi355x_groupby_rows): a row the mask names whose key column holds x belongs to bin b of
+// key_lo (BinTableArgs) of table t = c / span_chunks, and to none if b >= nbins: count[t * nbins + b] takes 1 and
+// sum[(t * nbins + b) * D + d] takes x_d, every column d.  An output that is null is not selected
 struct GroupByArgs {
-    const uint8_t* mask;        // [nchunks][mask_stride], or null: a run-time, wave-uniform switch, as hist.mask is
-    uint32_t mask_stride;       // mask bytes of a chunk slot, ceil(rows of a chunk slot / 8)
     uint64_t* count;            // optional (SPRINTZ_GBY_COUNT): [ntables][nbins], zeroed on the stream in front of the launch
     uint64_t* sum;              // optional (SPRINTZ_GBY_SUM): [ntables][nbins][D], the same
-    uint64_t table_chunks;      // H; 0: the whole batch is one table
-    uint32_t key, key_lo, shift, nbins;
-    uint32_t table_off;
-    uint32_t wg_chunks;
+    uint32_t key, key_lo;
 };
 
 struct DecodeArgs {
@@ -134,16 +127,23 @@ struct DecodeArgs {
     uint64_t one_off0, one_off1;
     uint64_t* host_flag;
     uint64_t host_ticket;
-    // the row operations: appended, a mode behind the other, so that no field above moves
+    // the row operations, behind everything above so that no field there moves.  hipcc's code for the kernels that read nothing of this
+    // block -- the plain decode, the reduce queries -- and for gather and filter still follows where the block's fields lie and how long
+    // the struct is: tools/kernel_diff.py shows their register choices and schedules moving when gather and filter shift by anything
+    // but a multiple of 64 bytes, or when sizeof(DecodeArgs) changes.  So the two stay put modulo 64 (the windows' and the table's
+    // arguments in front of them), and the struct keeps the length it has had since group-by rows: those kernels keep their code.
     WindowArgs win;
+    MomentArgs mom;
+    BinTableArgs table;
     GatherArgs gather;
     FilterArgs filter;
     SelectArgs select;
-    AggregateArgs agg;
+    RowMaskArgs rows;
     HistogramArgs hist;
-    MomentArgs mom;
     GroupByArgs gby;
+    uint64_t keep_size[10];
 };
+static_assert(sizeof(DecodeArgs) == 496 && offsetof(DecodeArgs, gather) % 64 == 184 % 64, "see the row operations' block");
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
 typedef uint16_t __attribute__((aligned(1), may_alias)) u16_unaligned;
@@ -183,9 +183,9 @@ __device__ __forceinline__ void win_flush(const DecodeArgs& a, uint64_t idx, uin
     qmax = 0;
     qsum = 0;
 }
-// The verbatim tail: element e is in column e % D, one row further on than the column's previous one, so a window edge can fall
-// inside the tail.  Window `wi` of the chunk (the first of them at entry `wbase`) still takes `wleft` rows.  Then the partial window
-// leaves, and the identities of the slot's windows past the data.
+// The verbatim tail, column by column: element e is in column e % D, one row further on than the column's previous one, so a window
+// edge can fall inside the tail.  Window `wi` of the chunk (the first of them at entry `wbase`) still takes `wleft` rows.  Then the
+// partial window leaves, and the identities of the slot's windows past the data.
 template <int W, int CPL>
 __device__ __forceinline__ void window_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, const int (&col)[CPL], const bool (&genuine)[CPL],
                                             uint64_t wbase, uint32_t wi, uint32_t wleft, uint32_t (&qmin)[CPL], uint32_t (&qmax)[CPL], uint64_t (&qsum)[CPL])
@@ -207,6 +207,73 @@ __device__ __forceinline__ void window_tail(const DecodeArgs& a, const uint8_t* 
             qsum[k] += x;
         }
         for (; w < a.win.count; w++) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
+    }
+}
+
+// ---- the windows' walk, shared by the windowed query, aggregate rows and moments rows.
+// one window's count of selected rows leaves with the window's other entries (one lane of the group: one writer an entry), and starts over
+__device__ __forceinline__ void window_count_flush(const DecodeArgs& a, uint64_t widx, uint32_t& cnt, int lane_d)
+{
+    if (a.win.row_count && lane_d == 0) a.win.row_count[widx] = cnt;
+    cnt = 0;
+}
+// Window `wi` of the chunk (the first of them at entry `wbase`) still takes `wleft` rows, and `n` of them -- a block's 8, a delta run's
+// share, a row of the tail; never more than wleft -- are done.  If they complete the window it leaves: flush_cols(w) stores this lane's
+// columns' entries of window entry w and starts their accumulators over, the count follows where the mode has one (COUNT), and the
+// next window begins.
+template <bool COUNT, typename F>
+__device__ __forceinline__ void window_advance(const DecodeArgs& a, uint32_t n, uint64_t wbase, uint32_t& wi, uint32_t& wleft, uint32_t& cnt, int lane_d,
+                                               F flush_cols)
+{
+    wleft -= n;
+    if (wleft == 0) {
+        flush_cols(wbase + wi);
+        if constexpr (COUNT) window_count_flush(a, wbase + wi, cnt, lane_d);
+        wi++;
+        wleft = a.win.rows;
+    }
+}
+
+// ---- the row mask.  The selected rows among the 8 * nblocks that a delta run repeats from block first_block of the chunk on: the set
+// bits of those mask bytes, spread over the group's lanes and summed -- or all of them where mask_bytes (the chunk's) is null.  EVERY
+// lane of the group must come here: the sum is a group reduction.  (The bytes lie inside the chunk's: the callers check that the run
+// fits the chunk slot.)
+__device__ __forceinline__ uint32_t run_selected_rows(const uint8_t* mask_bytes, uint32_t first_block, uint32_t nblocks, int lane_d, int DP)
+{
+    if (!mask_bytes) return 8u * nblocks;
+    uint32_t c = 0;
+    for (uint32_t j = (uint32_t)lane_d; j < nblocks; j += (uint32_t)DP) c += (uint32_t)__popc((uint32_t)mask_bytes[first_block + j]);
+    return group_sum(c, DP);
+}
+// The verbatim tail of the masked modes: `nfull` whole rows, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in
+// front).  A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  mask_at(b) is the chunk's mask
+// byte b, asked only where the chunk has one (`masked`).  row(r, on) sees every whole row r of the tail, `on`: the mask names it.
+template <typename M, typename R>
+__device__ __forceinline__ void masked_tail_rows(uint32_t nfull, uint32_t row0, bool masked, M mask_at, R row)
+{
+    uint32_t m = 0xffu;
+    for (uint32_t r = 0; r < nfull; r++) {
+        if ((r & 7u) == 0 && masked) m = mask_at((row0 + r) >> 3);
+        row(r, ((m >> (r & 7u)) & 1u) != 0);
+    }
+}
+// The same walk for the windowed modes: a window edge can fall inside the tail, so every row moves the chunk's window on
+// (window_advance); the selected ones are counted and go to row(r).  Then the partial window leaves, and the identities of the slot's
+// windows past the data.
+template <typename M, typename F, typename R>
+__device__ __forceinline__ void window_tail_rows(const DecodeArgs& a, uint32_t nfull, uint32_t row0, bool masked, M mask_at, uint64_t wbase, uint32_t wi,
+                                                 uint32_t wleft, uint32_t cnt, int lane_d, F flush_cols, R row)
+{
+    masked_tail_rows(nfull, row0, masked, mask_at, [&](uint32_t r, bool on) {
+        if (on) {
+            cnt++;
+            row(r);
+        }
+        window_advance<true>(a, 1u, wbase, wi, wleft, cnt, lane_d, flush_cols);
+    });
+    for (; wi < a.win.count; wi++) {
+        flush_cols(wbase + wi);
+        window_count_flush(a, wbase + wi, cnt, lane_d);
     }
 }
 
@@ -232,38 +299,18 @@ __device__ __forceinline__ void aggregate_row(uint32_t x, const AggregateSel& s,
     else
         asm("v_min_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(qmin) : "v"(qmin), "v"(u));
 }
-// one window's count leaves with the window's other entries (one lane of the group: one writer an entry), and starts over
-__device__ __forceinline__ void aggregate_count_flush(const DecodeArgs& a, uint64_t widx, uint32_t& acnt, int lane_d)
-{
-    if (a.agg.count && lane_d == 0) a.agg.count[widx] = acnt;
-    acnt = 0;
-}
-// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
-// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  Window `wi` of the chunk (the first of
-// them at entry `wbase`) still takes `wleft` rows; a window edge can fall inside the tail.  Then the partial window leaves, and the
-// identities of the slot's windows past the data.  mask_at(b) is the chunk's mask byte b.
+// The verbatim tail (window_tail_rows): a selected row's elements reach the accumulators of the lane's genuine columns
 template <int W, int CPL, typename F>
 __device__ __forceinline__ void aggregate_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0, const int (&col)[CPL],
                                                const bool (&genuine)[CPL], uint64_t wbase, uint32_t wi, uint32_t wleft, uint32_t (&qmin)[CPL],
                                                uint32_t (&qmax)[CPL], uint64_t (&qsum)[CPL], uint32_t acnt, int lane_d, F mask_at)
 {
-    const uint32_t nfull = remaining / D;
-    uint32_t w = wi, left = wleft;
-    auto flush = [&]() {
+    auto flush_cols = [&](uint64_t w) {
 #pragma unroll
         for (int k = 0; k < CPL; k++)
-            if (genuine[k]) win_flush<W>(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
-        aggregate_count_flush(a, wbase + w, acnt, lane_d);
-        w++;
-        left = a.win.rows;
+            if (genuine[k]) win_flush<W>(a, w * (uint64_t)D + (uint64_t)col[k], qmin[k], qmax[k], qsum[k]);
     };
-    uint32_t m = 0;
-    for (uint32_t r = 0; r < nfull; r++) {
-        if (left == 0) flush();
-        left--;
-        if ((r & 7u) == 0) m = mask_at((row0 + r) >> 3);
-        if (!((m >> (r & 7u)) & 1u)) continue;
-        acnt++;
+    window_tail_rows(a, remaining / D, row0, true, mask_at, wbase, wi, wleft, acnt, lane_d, flush_cols, [&](uint32_t r) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             if (!genuine[k]) continue;
@@ -272,12 +319,11 @@ __device__ __forceinline__ void aggregate_tail(const DecodeArgs& a, const uint8_
             qmax[k] = x > qmax[k] ? x : qmax[k];
             qsum[k] += x;
         }
-    }
-    while (w < a.win.count) flush();
+    });
 }
 
 // ---- histogram rows.  A sample's test is filter_hit's shape: one masked subtract, one shift, one compare.  The counters are a table in
-// the workgroup's LDS (non-returning ds_add_u32; HistCtx::tab) or, for a workgroup whose chunks lie in more than one histogram, the
+// the workgroup's LDS (non-returning ds_add_u32; BinTable::tab) or, for a workgroup whose chunks lie in more than one histogram, the
 // caller's 64-bit entries themselves (HistCtx::g: the histogram of the chunk being decoded).
 #ifndef SPRINTZ_HIST_MERGE
 // what a column's 8 rows of one block cost in atomics, all three forms measured in profiles/histogram_rows.txt -- 2 (kept): one add of 8
@@ -285,36 +331,69 @@ __device__ __forceinline__ void aggregate_tail(const DecodeArgs& a, const uint8_
 // length; 0: an add a sample
 #define SPRINTZ_HIST_MERGE 2
 #endif
-typedef __attribute__((address_space(3))) uint32_t hist_lds_u32;
-struct HistCtx {
-    hist_lds_u32* tab;          // the workgroup's table, or null: every add goes to g
-    uint64_t* g;
+// ---- the workgroup's table of bins (BinTableArgs), the histogram's and group-by's alike
+typedef __attribute__((address_space(3))) uint32_t table_lds_u32;
+struct BinTable {
+    table_lds_u32* tab;         // the workgroup's table, or null: every add goes to the outputs
     uint32_t shift, nbins;
+};
+// the table of the outputs that `chunk` belongs to
+__device__ __forceinline__ uint64_t table_of_chunk(const DecodeArgs& a, uint64_t chunk) { return a.table.span_chunks ? chunk / a.table.span_chunks : 0; }
+// v to entry idx of the workgroup's table (the planner's rule keeps every entry below 2^32), or to the output's entry g[gidx] (all 64 bits)
+__device__ __forceinline__ void table_add(const BinTable& t, uint32_t idx, uint64_t* g, uint32_t gidx, uint64_t v)
+{
+    if (t.tab) (void)__hip_atomic_fetch_add(t.tab + idx, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else (void)__hip_atomic_fetch_add(g + gidx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// At the kernel's start, every lane of the workgroup: does the workgroup add in its table?  (Workgroup-uniform: its chunks
+// [blockIdx.x * wg_chunks, + wg_chunks) -- those that exist -- lie in one table of the outputs.)  The table is zeroed, behind a barrier.
+__device__ __forceinline__ BinTable table_begin(const DecodeArgs& a, uint8_t* smem)
+{
+    BinTable t{nullptr, a.table.shift, a.table.nbins};
+    const uint64_t first = (uint64_t)blockIdx.x * a.table.wg_chunks;
+    if (a.table.wg_chunks == 0 || first >= a.nchunks) return t;
+    const uint64_t last = (first + a.table.wg_chunks < a.nchunks ? first + a.table.wg_chunks : a.nchunks) - 1;
+    if (table_of_chunk(a, first) != table_of_chunk(a, last)) return t;
+    t.tab = (table_lds_u32*)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + a.table.table_off);
+    for (uint32_t i = threadIdx.x; i < a.table.entries; i += kThreads) t.tab[i] = 0;
+    __syncthreads();
+    return t;
+}
+// At the kernel's end, every lane of the workgroup (none has left): behind a barrier the table's nonzero entries are added to the
+// outputs, spread over all lanes -- device-scope 64-bit adds: integer sums, exact in any order.  The first n0 entries go to dst0, the
+// rest to dst1: the places in the outputs of the workgroup's table (table_of_chunk of its first chunk); one that is null is not selected.
+__device__ __forceinline__ void table_end(const DecodeArgs& a, const BinTable& t, uint64_t* dst0, uint32_t n0, uint64_t* dst1)
+{
+    if (!t.tab) return;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < a.table.entries; i += kThreads) {
+        uint64_t* const dst = i < n0 ? dst0 : dst1;
+        const uint32_t v = t.tab[i];
+        if (v != 0 && dst) (void)__hip_atomic_fetch_add(dst + (i < n0 ? i : i - n0), (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the histogram's counters: the workgroup's table or the caller's 64-bit entries themselves (g: the histogram of the chunk being decoded)
+struct HistCtx {
+    BinTable bin;
+    uint64_t* g;
 };
 struct HistCol { uint32_t lo, base; };    // the column's lo and the index of its bin 0 inside a histogram, column * nbins
 template <int W>
 __device__ __forceinline__ HistCol hist_col(const DecodeArgs& a, int col, bool genuine)
 {
     using U = typename Elem<W>::U;
-    return HistCol{genuine && a.hist.lo ? (uint32_t)((const U*)a.hist.lo)[col] : 0u, (uint32_t)col * a.hist.nbins};
+    return HistCol{genuine && a.hist.lo ? (uint32_t)((const U*)a.hist.lo)[col] : 0u, (uint32_t)col * a.table.nbins};
 }
-__device__ __forceinline__ uint64_t* hist_of_chunk(const DecodeArgs& a, uint64_t chunk)
-{
-    const uint64_t g = a.hist.group_chunks ? chunk / a.hist.group_chunks : 0;
-    return a.hist.hist + g * ((uint64_t)a.D * a.hist.nbins);
-}
-__device__ __forceinline__ void hist_add(const HistCtx& c, uint32_t idx, uint32_t n)
-{
-    if (c.tab) (void)__hip_atomic_fetch_add(c.tab + idx, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else (void)__hip_atomic_fetch_add(c.g + idx, (uint64_t)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ __forceinline__ uint64_t* hist_of_chunk(const DecodeArgs& a, uint64_t chunk) { return a.hist.hist + table_of_chunk(a, chunk) * a.table.entries; }
+__device__ __forceinline__ void hist_add(const HistCtx& c, uint32_t idx, uint32_t n) { table_add(c.bin, idx, c.g, idx, n); }
 // (x may carry garbage above bit W: only its low W bits reach the masked difference)
-template <int W> __device__ __forceinline__ uint32_t hist_bin(const HistCtx& c, const HistCol& h, uint32_t x) { return ((x - h.lo) & Elem<W>::MASK) >> c.shift; }
+template <int W> __device__ __forceinline__ uint32_t hist_bin(const BinTable& t, const HistCol& h, uint32_t x) { return ((x - h.lo) & Elem<W>::MASK) >> t.shift; }
 // one value that `n` selected rows hold (a delta run's constant row, a row of the tail)
 template <int W> __device__ __forceinline__ void hist_value(const HistCtx& c, const HistCol& h, uint32_t x, uint32_t n)
 {
-    const uint32_t b = hist_bin<W>(c, h, x);
-    if (b < c.nbins && n != 0) hist_add(c, h.base + b, n);
+    const uint32_t b = hist_bin<W>(c.bin, h, x);
+    if (b < c.bin.nbins && n != 0) hist_add(c, h.base + b, n);
 }
 // a column's 8 rows of one block; bit i of m: row i is selected
 template <int W>
@@ -324,8 +403,8 @@ __device__ __forceinline__ void hist_rows8(const HistCtx& c, const HistCol& h, c
     uint32_t pb = 0, pc = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        const uint32_t b = hist_bin<W>(c, h, x[i]);
-        const bool on = b < c.nbins && ((m >> i) & 1u);
+        const uint32_t b = hist_bin<W>(c.bin, h, x[i]);
+        const bool on = b < c.bin.nbins && ((m >> i) & 1u);
         if (on && pc != 0 && b == pb) {
             pc++;
         } else {
@@ -339,62 +418,35 @@ __device__ __forceinline__ void hist_rows8(const HistCtx& c, const HistCol& h, c
     uint32_t b[8], diff = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        b[i] = hist_bin<W>(c, h, x[i]);
+        b[i] = hist_bin<W>(c.bin, h, x[i]);
         diff |= b[i] ^ b[0];
     }
     if (SPRINTZ_HIST_MERGE == 2 && diff == 0 && m == 0xffu) {     // 2: only a block whose 8 rows are selected and share a bin is one add
-        if (b[0] < c.nbins) hist_add(c, h.base + b[0], 8u);
+        if (b[0] < c.bin.nbins) hist_add(c, h.base + b[0], 8u);
         return;
     }
 #pragma unroll
     for (int i = 0; i < 8; i++)
-        if (b[i] < c.nbins && ((m >> i) & 1u)) hist_add(c, h.base + b[i], 1u);
+        if (b[i] < c.bin.nbins && ((m >> i) & 1u)) hist_add(c, h.base + b[i], 1u);
 #endif
 }
-// At the kernel's start, every lane of the workgroup: does the workgroup count in its table?  (Workgroup-uniform: its chunks
-// [blockIdx.x * wg_chunks, + wg_chunks) -- those that exist -- lie in one histogram.)  The table is zeroed, behind a barrier.
-__device__ __forceinline__ HistCtx hist_begin(const DecodeArgs& a, uint8_t* smem)
-{
-    HistCtx c{nullptr, a.hist.hist, a.hist.shift, a.hist.nbins};
-    const uint64_t first = (uint64_t)blockIdx.x * a.hist.wg_chunks;
-    if (a.hist.wg_chunks == 0 || first >= a.nchunks) return c;
-    const uint64_t last = (first + a.hist.wg_chunks < a.nchunks ? first + a.hist.wg_chunks : a.nchunks) - 1;
-    if (a.hist.group_chunks && first / a.hist.group_chunks != last / a.hist.group_chunks) return c;
-    c.tab = (hist_lds_u32*)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + a.hist.table_off);
-    const uint32_t n = (uint32_t)a.D * a.hist.nbins;
-    for (uint32_t i = threadIdx.x; i < n; i += kThreads) c.tab[i] = 0;
-    __syncthreads();
-    return c;
-}
-// At the kernel's end, every lane of the workgroup (none has left): behind a barrier the table's nonzero counters are added to the
-// workgroup's histogram, spread over all lanes -- device-scope 64-bit adds: integer sums, exact in any order.
+// the workgroup's table holds its histogram's D * nbins counters (table_begin .. table_end)
+__device__ __forceinline__ HistCtx hist_begin(const DecodeArgs& a, uint8_t* smem) { return HistCtx{table_begin(a, smem), a.hist.hist}; }
 __device__ __forceinline__ void hist_end(const DecodeArgs& a, const HistCtx& c)
 {
-    if (!c.tab) return;
-    __syncthreads();
-    uint64_t* const g = hist_of_chunk(a, (uint64_t)blockIdx.x * a.hist.wg_chunks);
-    const uint32_t n = (uint32_t)a.D * a.hist.nbins;
-    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
-        const uint32_t v = c.tab[i];
-        if (v != 0) (void)__hip_atomic_fetch_add(g + i, (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    table_end(a, c.bin, hist_of_chunk(a, (uint64_t)blockIdx.x * a.table.wg_chunks), a.table.entries, nullptr);
 }
-// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
-// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  mask_at(b) is the chunk's mask byte b
-// (asked only where there is a mask).
+// The verbatim tail (masked_tail_rows): a selected row's elements are counted, a column each
 template <int W, int CPL, typename F>
 __device__ __forceinline__ void hist_tail(const DecodeArgs& a, const HistCtx& c, const HistCol (&h)[CPL], const uint8_t* t, uint32_t remaining, uint32_t D,
                                           uint32_t row0, const int (&col)[CPL], const bool (&genuine)[CPL], F mask_at)
 {
-    const uint32_t nfull = remaining / D;
-    uint32_t m = 0xffu;
-    for (uint32_t r = 0; r < nfull; r++) {
-        if ((r & 7u) == 0 && a.hist.mask) m = mask_at((row0 + r) >> 3);
-        if (!((m >> (r & 7u)) & 1u)) continue;
+    masked_tail_rows(remaining / D, row0, a.rows.mask != nullptr, mask_at, [&](uint32_t r, bool on) {
+        if (!on) return;
 #pragma unroll
         for (int k = 0; k < CPL; k++)
             if (genuine[k]) hist_value<W>(c, h[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), 1u);
-    }
+    });
 }
 
 // ---- moments rows.  Every value is an exact unsigned integer: a factor is below 2^16, so a product is below 2^32; a chunk slot has
@@ -477,50 +529,29 @@ __device__ __forceinline__ void moments_flush(const DecodeArgs& a, uint64_t idx,
     if (a.mom.cross) a.mom.cross[idx] = acc.cross;
     acc = MomentAcc{0, 0, 0};
 }
-// one window's count leaves with the window's other entries (one lane of the group), and starts over
-__device__ __forceinline__ void moments_count_flush(const DecodeArgs& a, uint64_t widx, uint32_t& cnt, int lane_d)
-{
-    if (a.mom.count && lane_d == 0) a.mom.count[widx] = cnt;
-    cnt = 0;
-}
-// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
-// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  Window `wi` of the chunk (the first of
-// them at entry `wbase`) still takes `wleft` rows; a window edge can fall inside the tail.  Then the partial window leaves, and the
-// zeros of the slot's windows past the data.  mask_at(b) is the chunk's mask byte b (asked only where there is a mask).  The reference
-// column's element is read from the tail itself: no lane needs another's.
+// The verbatim tail (window_tail_rows): a selected row's elements reach the sums of the lane's genuine columns.  The reference column's
+// element is read from the tail itself: no lane needs another's.
 template <int W, int CPL, typename F>
 __device__ __forceinline__ void moments_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0, const int (&col)[CPL],
                                              const bool (&genuine)[CPL], uint64_t wbase, uint32_t wi, uint32_t wleft, MomentAcc (&acc)[CPL], uint32_t cnt,
                                              int lane_d, F mask_at)
 {
-    const uint32_t nfull = remaining / D;
-    uint32_t w = wi, left = wleft;
-    auto flush = [&]() {
+    auto flush_cols = [&](uint64_t w) {
 #pragma unroll
         for (int k = 0; k < CPL; k++)
-            if (genuine[k]) moments_flush(a, (wbase + w) * (uint64_t)D + (uint64_t)col[k], acc[k]);
-        moments_count_flush(a, wbase + w, cnt, lane_d);
-        w++;
-        left = a.win.rows;
+            if (genuine[k]) moments_flush(a, w * (uint64_t)D + (uint64_t)col[k], acc[k]);
     };
-    uint32_t m = 0xffu;
-    for (uint32_t r = 0; r < nfull; r++) {
-        if (left == 0) flush();
-        left--;
-        if ((r & 7u) == 0 && a.mom.mask) m = mask_at((row0 + r) >> 3);
-        if (!((m >> (r & 7u)) & 1u)) continue;
-        cnt++;
+    window_tail_rows(a, remaining / D, row0, a.rows.mask != nullptr, mask_at, wbase, wi, wleft, cnt, lane_d, flush_cols, [&](uint32_t r) {
         const uint32_t xr = tail_elem<W>(t, r * D + a.mom.ref);
 #pragma unroll
         for (int k = 0; k < CPL; k++)
             if (genuine[k]) moments_value(acc[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), xr, 1u);
-    }
-    while (w < a.win.count) flush();
+    });
 }
 
 // ---- group-by rows.  The bin of a row is the histogram's test on the key column's value (hist_bin); the key column's rows reach every
 // lane of the group as the moments' reference column does (moments_ref_rows / moments_ref_value).  The entries are a table in the
-// workgroup's LDS (non-returning ds_add_u32: nbins * D sums, bin-major, then nbins counts; GroupByCtx::bin.tab) or, for a workgroup whose
+// workgroup's LDS (non-returning ds_add_u32: nbins * D sums, bin-major, then nbins counts; BinTable::tab) or, for a workgroup whose
 // chunks lie in more than one table, the caller's 64-bit entries themselves (gsum / gcount: the table of the chunk being decoded).
 #ifndef SPRINTZ_GBY_MERGE
 // what a block's 8 rows cost in atomics, both forms measured in profiles/groupby_rows.txt -- 1 (kept): where all 8 rows are valid and
@@ -528,7 +559,7 @@ __device__ __forceinline__ void moments_tail(const DecodeArgs& a, const uint8_t*
 #define SPRINTZ_GBY_MERGE 1
 #endif
 struct GroupByCtx {
-    HistCtx bin;                // tab (null: every add goes to gsum / gcount), shift and nbins: hist_bin's view of the key column
+    BinTable bin;               // hist_bin's view of the key column
     HistCol key;                // lo = key_lo
     uint64_t* gsum;             // null: the sums are not selected
     uint64_t* gcount;           // null: the counts are not selected
@@ -536,23 +567,13 @@ struct GroupByCtx {
 };
 __device__ __forceinline__ void groupby_of_chunk(const DecodeArgs& a, GroupByCtx& c, uint64_t chunk)
 {
-    const uint64_t t = a.gby.table_chunks ? chunk / a.gby.table_chunks : 0;
-    c.gsum = a.gby.sum ? a.gby.sum + t * ((uint64_t)a.gby.nbins * (uint32_t)a.D) : nullptr;
-    c.gcount = a.gby.count ? a.gby.count + t * (uint64_t)a.gby.nbins : nullptr;
+    const uint64_t t = table_of_chunk(a, chunk);
+    c.gsum = a.gby.sum ? a.gby.sum + t * ((uint64_t)a.table.nbins * (uint32_t)a.D) : nullptr;
+    c.gcount = a.gby.count ? a.gby.count + t * (uint64_t)a.table.nbins : nullptr;
 }
-// v: one row's value, a block's sum (8 rows: below 2^19) or a run's value times its rows (the planner's rule keeps every table entry
-// below 2^32; the direct path adds all 64 bits)
-__device__ __forceinline__ void groupby_add_sum(const GroupByCtx& c, uint32_t b, uint32_t col, uint64_t v)
-{
-    const uint32_t idx = b * c.D + col;
-    if (c.bin.tab) (void)__hip_atomic_fetch_add(c.bin.tab + idx, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else (void)__hip_atomic_fetch_add(c.gsum + idx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void groupby_add_count(const GroupByCtx& c, uint32_t b, uint32_t n)
-{
-    if (c.bin.tab) (void)__hip_atomic_fetch_add(c.bin.tab + c.bin.nbins * c.D + b, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else (void)__hip_atomic_fetch_add(c.gcount + b, (uint64_t)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// v: one row's value, a block's sum (8 rows: below 2^19) or a run's value times its rows
+__device__ __forceinline__ void groupby_add_sum(const GroupByCtx& c, uint32_t b, uint32_t col, uint64_t v) { table_add(c.bin, b * c.D + col, c.gsum, b * c.D + col, v); }
+__device__ __forceinline__ void groupby_add_count(const GroupByCtx& c, uint32_t b, uint32_t n) { table_add(c.bin, c.bin.nbins * c.D + b, c.gcount, b, n); }
 // a block's 8 rows: at(k, i) is this lane's row i of slot k (garbage above bit W allowed), xk the key column's rows (clean: every lane of
 // the group has them from moments_ref_rows), bit i of m: row i is selected.  One lane of the group adds the counts
 template <int W, int CPL, typename F>
@@ -611,57 +632,33 @@ __device__ __forceinline__ void groupby_value(const GroupByCtx& c, const uint32_
     }
     if (c.gcount && lane_d == 0) groupby_add_count(c, b, n);
 }
-// At the kernel's start, every lane of the workgroup: does the workgroup add in its table?  (Workgroup-uniform, as hist_begin: its chunks
-// [blockIdx.x * wg_chunks, + wg_chunks) -- those that exist -- lie in one table.)  The table is zeroed, behind a barrier.
+// the workgroup's table holds its nbins * D sums, then its nbins counts (table_begin .. table_end)
 __device__ __forceinline__ GroupByCtx groupby_begin(const DecodeArgs& a, uint8_t* smem)
 {
-    GroupByCtx c{HistCtx{nullptr, nullptr, a.gby.shift, a.gby.nbins}, HistCol{a.gby.key_lo, 0u}, a.gby.sum, a.gby.count, (uint32_t)a.D};
-    const uint64_t first = (uint64_t)blockIdx.x * a.gby.wg_chunks;
-    if (a.gby.wg_chunks == 0 || first >= a.nchunks) return c;
-    const uint64_t last = (first + a.gby.wg_chunks < a.nchunks ? first + a.gby.wg_chunks : a.nchunks) - 1;
-    if (a.gby.table_chunks && first / a.gby.table_chunks != last / a.gby.table_chunks) return c;
-    c.bin.tab = (hist_lds_u32*)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + a.gby.table_off);
-    const uint32_t n = a.gby.nbins * ((uint32_t)a.D + 1u);
-    for (uint32_t i = threadIdx.x; i < n; i += kThreads) c.bin.tab[i] = 0;
-    __syncthreads();
-    return c;
+    return GroupByCtx{table_begin(a, smem), HistCol{a.gby.key_lo, 0u}, a.gby.sum, a.gby.count, (uint32_t)a.D};
 }
-// At the kernel's end, every lane of the workgroup (none has left): behind a barrier the table's nonzero entries of the selected outputs
-// are added to the workgroup's table in global memory, spread over all lanes -- device-scope 64-bit adds: integer sums, exact in any order.
 __device__ __forceinline__ void groupby_end(const DecodeArgs& a, const GroupByCtx& c)
 {
-    if (!c.bin.tab) return;
-    __syncthreads();
     GroupByCtx g = c;
-    groupby_of_chunk(a, g, (uint64_t)blockIdx.x * a.gby.wg_chunks);
-    const uint32_t ns = a.gby.nbins * (uint32_t)a.D, n = ns + a.gby.nbins;
-    for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
-        uint64_t* const dst = i < ns ? g.gsum : g.gcount;
-        const uint32_t v = c.bin.tab[i];
-        if (v != 0 && dst) (void)__hip_atomic_fetch_add(dst + (i < ns ? i : i - ns), (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    groupby_of_chunk(a, g, (uint64_t)blockIdx.x * a.table.wg_chunks);
+    table_end(a, c.bin, g.gsum, a.table.nbins * (uint32_t)a.D, g.gcount);
 }
-// The verbatim tail: `remaining` elements at t, row-major from chunk row `row0` (a multiple of 8: the rows of the blocks in front).
-// A partial last row is not a row, and a mask bit of a row the tail does not hold is not read.  mask_at(b) is the chunk's mask byte b
-// (asked only where there is a mask).  The key column's element is read from the tail itself: no lane needs another's.
+// The verbatim tail (masked_tail_rows).  The key column's element is read from the tail itself: no lane needs another's.
 template <int W, int CPL, typename F>
 __device__ __forceinline__ void groupby_tail(const DecodeArgs& a, const GroupByCtx& c, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0,
                                              const int (&col)[CPL], const bool (&genuine)[CPL], int lane_d, F mask_at)
 {
-    const uint32_t nfull = remaining / D;
-    uint32_t m = 0xffu;
-    for (uint32_t r = 0; r < nfull; r++) {
-        if ((r & 7u) == 0 && a.gby.mask) m = mask_at((row0 + r) >> 3);
-        if (!((m >> (r & 7u)) & 1u)) continue;
+    masked_tail_rows(remaining / D, row0, a.rows.mask != nullptr, mask_at, [&](uint32_t r, bool on) {
+        if (!on) return;
         const uint32_t b = hist_bin<W>(c.bin, c.key, tail_elem<W>(t, r * D + a.gby.key));
-        if (b >= c.bin.nbins) continue;
+        if (b >= c.bin.nbins) return;
         if (c.gsum) {
 #pragma unroll
             for (int k = 0; k < CPL; k++)
                 if (genuine[k]) groupby_add_sum(c, b, (uint32_t)col[k], tail_elem<W>(t, r * D + (uint32_t)col[k]));
         }
         if (c.gcount && lane_d == 0) groupby_add_count(c, b, 1u);
-    }
+    });
 }
 
 // ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the

@@ -29,7 +29,8 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only;
 // 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only;
 // 9 = moments: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names (or of every row), reduce only;
-// 10 = group-by: per bin of ONE key column's value, the count and the per-column sums of the rows a mask names (or of every row), added up in an LDS table a workgroup, reduce only
+// 10 = group-by: per bin of ONE key column's value, the count and the per-column sums of the rows a mask names (or of every row), added up in an LDS table a workgroup, reduce only.
+// 6 .. 10 read one row mask (decode_ops.h: RowMaskArgs), 3, 7 and 9 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
               kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10;
 // the modes that never store a decoded sample

@@ -20,7 +20,7 @@ namespace sprintz {
 
 // The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryGroupBy).  Each forwards to the
 // translation unit that holds the instantiation -- decode_w8.hip / decode_w16.hip for the plain decode and the reduce / window
-// queries, decode_gather.hip, decode_filter.hip, decode_select.hip, decode_aggregate.hip, decode_histogram.hip, decode_moments.hip, decode_groupby.hip for those modes -- so that every unit keeps its compile flags.
+// queries, a unit of its own for every other mode (SPRINTZ_ROW_OP_UNITS below) -- so that every unit keeps its compile flags.
 // generic lane mapping, both layouts, up to 512 columns (decode_kernel.h)
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h); gather and select for rows of whole 16-byte pieces
@@ -30,24 +30,14 @@ hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // internal -- the units' own entry points, reached through the three launchers above alone (api.hip).  A unit refuses a width or
 // a mode it does not hold; the decode_uni units size their grid themselves (decode_uni_threads) and ignore `grid`
-hipError_t decode_generic_w8(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_w16(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_gather(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_filter(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_select(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_aggregate(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_histogram(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_moments(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_generic_groupby(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_w8(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_w16(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_gather(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_filter(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_select(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_aggregate(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_histogram(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_moments(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-hipError_t decode_fast_groupby(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+#define SPRINTZ_DECODE_UNIT_DECL(NAME)                                                                                                                          \
+    hipError_t decode_generic_##NAME(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);          \
+    hipError_t decode_fast_##NAME(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
+SPRINTZ_DECODE_UNIT_DECL(w8)
+SPRINTZ_DECODE_UNIT_DECL(w16)
+// the row operations' units, a mode each, in the order of their kQuery* numbers (api.hip builds its table of units from this list)
+#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby)
+SPRINTZ_ROW_OP_UNITS(SPRINTZ_DECODE_UNIT_DECL)
 hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_filter(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
@@ -190,15 +180,43 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
     if (q == kQueryWindow) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryWindow, false) }         \
     return hipErrorInvalidValue;
 
-// gather (kQueryGather): row-major destination, rows of whole 16-byte pieces -- 16 columns and more (8 columns of 16 bits: decode_gather.hip)
-#define SPRINTZ_DISPATCH_DECODE_FAST_GATHER(KERNEL, W)                                                \
-    if (a.col_stride) return hipErrorInvalidValue;                                                    \
-    SPRINTZ_FAST_CASE(KERNEL, W, 16, 1, kQueryGather, false)                                          \
-    SPRINTZ_FAST_CASE(KERNEL, W, 32, 1, kQueryGather, false)                                          \
-    SPRINTZ_FAST_CASE(KERNEL, W, 64, 1, kQueryGather, false)                                          \
-    SPRINTZ_FAST_CASE(KERNEL, W, 64, 2, kQueryGather, false)                                          \
-    SPRINTZ_FAST_CASE(KERNEL, W, 64, 4, kQueryGather, false)                                          \
+// every mapping the windowed query has, row-major: the row operations that store no rows (filter, aggregate, histogram, moments, group-by)
+#define SPRINTZ_DISPATCH_DECODE_FAST_ROWS(KERNEL, W, Q) SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, Q, false)
+// gather and select: row-major destination, rows of whole 16-byte store pieces -- 16 columns and more, or 8 columns of 16 bits
+#define SPRINTZ_FAST_PIECES_8(KERNEL, Q)
+#define SPRINTZ_FAST_PIECES_16(KERNEL, Q) SPRINTZ_FAST_CASE(KERNEL, 16, 8, 1, Q, false)
+#define SPRINTZ_DISPATCH_DECODE_FAST_PIECES(KERNEL, W, Q)                                             \
+    SPRINTZ_FAST_PIECES_##W(KERNEL, Q)                                                                \
+    SPRINTZ_FAST_CASE(KERNEL, W, 16, 1, Q, false)                                                     \
+    SPRINTZ_FAST_CASE(KERNEL, W, 32, 1, Q, false)                                                     \
+    SPRINTZ_FAST_CASE(KERNEL, W, 64, 1, Q, false)                                                     \
+    SPRINTZ_FAST_CASE(KERNEL, W, 64, 2, Q, false)                                                     \
+    SPRINTZ_FAST_CASE(KERNEL, W, 64, 4, Q, false)                                                     \
     return hipErrorInvalidValue;
+
+// A row operation's translation unit: the instantiations of the generic decoder and of decode_fast for Q, both widths, both codecs.
+// The kernels of decode_w8.hip / decode_w16.hip keep the code and the flags they had, and hipcc builds the units in parallel.
+// FAST_DISPATCH(KERNEL, W, Q) is the set of decode_fast mappings the mode has.  The generic kernel stages nothing in these modes:
+// whatever the plan carved, its launch asks for LDS only where that is the workgroup's table (histogram, group-by) -- and for the
+// filter, which keeps the launch it always had.
+#define SPRINTZ_ROW_OP_UNIT(NAME, Q, FAST_DISPATCH)                                                                                                             \
+    namespace sprintz {                                                                                                                                         \
+    hipError_t decode_generic_##NAME(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)           \
+    {                                                                                                                                                           \
+        if (q != Q) return hipErrorInvalidValue;                                                                                                                \
+        if (Q != kQueryFilter && Q != kQueryHistogram && Q != kQueryGroupBy) shmem = 0;                                                                         \
+        if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, Q) }                                                                                                 \
+        if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, Q) }                                                                                               \
+        return hipErrorInvalidValue;                                                                                                                            \
+    }                                                                                                                                                           \
+    hipError_t decode_fast_##NAME(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a) \
+    {                                                                                                                                                           \
+        if (q != Q || ds != 0 || a.col_stride) return hipErrorInvalidValue;                                                                                     \
+        if (w == 16) { FAST_DISPATCH(decode_fast_kernel, 16, Q) }                                                                                               \
+        if (w == 8) { FAST_DISPATCH(decode_fast_kernel, 8, Q) }                                                                                                 \
+        return hipErrorInvalidValue;                                                                                                                            \
+    }                                                                                                                                                           \
+    }
 
 #define SPRINTZ_ENC_FAST_CASE(KERNEL, W, DPV, CMV)                                                   \
     case DPV:                                                                                         \

@@ -43,8 +43,9 @@ struct Shape {
     uint64_t nranges = 0;                  // gather
     uint32_t rows = 0;
     uint64_t capacity = 0;                 // select: rows of the output
-    uint32_t hist_bins = 0;                // histogram: nbins (D x nbins counters, at most kHistMaxCounters)
-    uint32_t gby_bins = 0;                 // group-by: nbins (nbins x (D + 1) counters, at most kGroupByMaxCounters)
+    // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
+    // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
+    uint32_t table_entries = 0, table_row_max = 0;
 };
 
 struct Plan {
@@ -60,11 +61,9 @@ struct Plan {
     bool fused = false;                    // the encoder builds the container itself: grid + 1 zeroed words of d_tmp in front of it
     bool plain_memory = false;             // the output / the slots must be ordinary device memory (checked BEFORE err is reported, as the launch sites did)
     bool counters = false;                 // FIRE counters in stream-ordered scratch, nchunks x D x 4 bytes
-    // histogram: where a workgroup's table of D x nbins uint32 counters starts in its dynamic LDS (behind the groups' carves), and the
-    // consecutive chunks a workgroup decodes -- 0 where their rows could wrap a 32-bit counter: such a launch counts in global memory
-    uint32_t hist_table_off = 0, hist_wg_chunks = 0;
-    // group-by: the same for its table of nbins x D sums and nbins counts -- 0 chunks where a 32-bit sum could wrap
-    uint32_t gby_table_off = 0, gby_wg_chunks = 0;
+    // histogram, group-by: where a workgroup's table of uint32 entries starts in its dynamic LDS (behind the groups' carves), and the
+    // consecutive chunks a workgroup decodes -- 0 where their rows could wrap a 32-bit entry: such a launch adds in global memory
+    uint32_t table_off = 0, wg_chunks = 0;
     RowDecGeom row{};
     BlkDecGeom blkd{};
     BlkEncGeom blke{};
@@ -142,18 +141,13 @@ inline bool big_counters(Plan& p, const Shape& s)
 }
 
 static_assert(kHistMaxCounters == SPRINTZ_HIST_MAX_COUNTERS, "the table's size is the header's cap");
-// histogram rows: a table counter takes at most one add a row of the workgroup's chunks -- wg_chunks x (chunk_len / D) of them, which must
-// fit 32 bits; the table is merged once, at the kernel's end
-inline uint32_t hist_wg_chunks(uint64_t wg_chunks, uint32_t chunk_len, int D)
-{
-    return wg_chunks * (uint64_t)(chunk_len / (uint32_t)D) <= 0xffffffffull ? (uint32_t)wg_chunks : 0u;
-}
 static_assert(kGroupByMaxCounters == SPRINTZ_GBY_MAX_COUNTERS, "the table's size is the header's cap");
-// group-by rows: a table entry takes at most one add a row of the workgroup's chunks, a count of 1 and a sum of at most 2^W - 1 (a delta
-// run's value x rows is the same bound), so wg_chunks x (chunk_len / D) x (2^W - 1) must fit 32 bits
-inline uint32_t gby_wg_chunks(uint64_t wg_chunks, uint32_t chunk_len, int D, int esz)
+// histogram, group-by rows: a table entry takes at most one add a row of the workgroup's chunks, of at most row_max -- a count of 1, a
+// sum of at most 2^W - 1 (a delta run's value x rows is the same bound) -- so wg_chunks x (chunk_len / D) x row_max must fit 32 bits;
+// the table is merged once, at the kernel's end
+inline uint32_t table_wg_chunks(uint64_t wg_chunks, uint32_t chunk_len, int D, uint32_t row_max)
 {
-    return wg_chunks * (uint64_t)(chunk_len / (uint32_t)D) * ((1ull << (8 * esz)) - 1) <= 0xffffffffull ? (uint32_t)wg_chunks : 0u;
+    return wg_chunks * (uint64_t)(chunk_len / (uint32_t)D) * row_max <= 0xffffffffull ? (uint32_t)wg_chunks : 0u;
 }
 
 inline Plan plan_decode(const Shape& s, const Knobs& k)
@@ -258,10 +252,9 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
             return plan_take(p, SPRINTZ_KF_DEC_BLK, (nchunks + g.CPW - 1) / g.CPW, g.total);
         }
     }
-    // histogram rows: the workgroup's table sits behind the groups' carves, and both must fit the launch's LDS budget
-    // (group-by rows: the same, a table of nbins x (D + 1) entries)
-    const uint64_t hist_bytes = s.q == kQueryHistogram ? 4ull * (uint64_t)D * s.hist_bins : s.q == kQueryGroupBy ? 4ull * s.gby_bins * ((uint64_t)D + 1) : 0;
-    if (fast && (hist_bytes == 0 || (uint64_t)f.ring * (kThreads / f.dp) + hist_bytes <= kHistFastLdsBudget)) {
+    // histogram, group-by rows: the workgroup's table sits behind the groups' carves, and both must fit the launch's LDS budget
+    const uint64_t table_bytes = 4ull * s.table_entries;
+    if (fast && (table_bytes == 0 || (uint64_t)f.ring * (kThreads / f.dp) + table_bytes <= kHistFastLdsBudget)) {
         p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
         p.exact = D == f.dp * f.cpl;
         p.log2DP = f.log2dp;
@@ -271,27 +264,19 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
         // than four staggered ones, so the default stays at one chunk per group (env knob for tuning).
         p.chunks_per_group = (uint32_t)k.chunks_per_group;
         const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
-        if (s.q == kQueryHistogram) {
-            p.hist_table_off = f.ring * (uint32_t)(kThreads / f.dp);
-            p.hist_wg_chunks = hist_wg_chunks((uint64_t)(kThreads / f.dp) * p.chunks_per_group, chunk_len, D);
+        if (table_bytes) {
+            p.table_off = f.ring * (uint32_t)(kThreads / f.dp);
+            p.wg_chunks = table_wg_chunks((uint64_t)(kThreads / f.dp) * p.chunks_per_group, chunk_len, D, s.table_row_max);
         }
-        if (s.q == kQueryGroupBy) {
-            p.gby_table_off = f.ring * (uint32_t)(kThreads / f.dp);
-            p.gby_wg_chunks = gby_wg_chunks((uint64_t)(kThreads / f.dp) * p.chunks_per_group, chunk_len, D, esz);
-        }
-        return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * (kThreads / f.dp) + hist_bytes);
+        return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * (kThreads / f.dp) + table_bytes);
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
     // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by: those shapes go to the generic kernel)
     if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && s.q != kQueryGroupBy && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
-    if (s.q == kQueryHistogram) {                              // nothing is staged: the table is the launch's LDS
-        p.hist_wg_chunks = hist_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D);
-        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, hist_bytes);
-    }
-    if (s.q == kQueryGroupBy) {                                // the same
-        p.gby_wg_chunks = gby_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D, esz);
-        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, hist_bytes);
+    if (table_bytes) {                                         // nothing is staged: the table is the launch's LDS
+        p.wg_chunks = table_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D, s.table_row_max);
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, table_bytes);
     }
     return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, shmem);
 }

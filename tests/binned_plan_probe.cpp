@@ -1,8 +1,9 @@
-// groupby_plan_probe.cpp -- plan_decode (sprintz_amd/csrc/plan.h) for the group-by-rows mode on a host compiler, for
-// tests/test_groupby_cpu.py: histogram_plan_probe.cpp's queries with the one Shape field that mode adds.  One query per line on stdin,
-//     esz=.. D=.. chunk_len=.. nchunks=.. codec=.. nbins=.. no_fast=.. general=.. chunks_per_group=.. q=..   (q defaults to kQueryGroupBy)
-// and one answer per line: the family's name, the launch's dynamic LDS bytes, the table's offset in it and the chunks a workgroup
-// adds up in its table (0: none, every row goes to global memory) -- or the error.
+// binned_plan_probe.cpp -- plan_decode (sprintz_amd/csrc/plan.h) for the modes that fill a workgroup's table of bins (histogram and
+// group-by rows) on a host compiler, for tests/test_histogram_cpu.py and tests/test_groupby_cpu.py: select_plan_probe.cpp's queries with
+// the two Shape fields those modes add.  One query per line on stdin,
+//     esz=.. D=.. chunk_len=.. nchunks=.. codec=.. table_entries=.. table_row_max=.. no_fast=.. general=.. chunks_per_group=.. q=..
+// (a mode without a table leaves both out) and one answer per line: the family's name, the launch's dynamic LDS bytes, the table's
+// offset in it and the chunks a workgroup adds up in its table (0: none, every add goes to global memory) -- or the error.
 #include <cstdio>
 #include <cstdlib>
 #include <sstream>
@@ -20,8 +21,6 @@ int main()
         std::string tok;
         Shape s;
         Knobs k;
-        s.q = kQueryGroupBy;
-        s.gby_bins = 256;
         bool any = false;
         while (in >> tok) {
             const size_t eq = tok.find('=');
@@ -34,7 +33,8 @@ int main()
             else if (key == "codec") s.codec = (int)v;
             else if (key == "chunk_len") s.chunk_len = (uint32_t)v;
             else if (key == "nchunks") s.nchunks = v;
-            else if (key == "nbins") s.gby_bins = (uint32_t)v;
+            else if (key == "table_entries") s.table_entries = (uint32_t)v;
+            else if (key == "table_row_max") s.table_row_max = (uint32_t)v;
             else if (key == "general") s.general = (int)v;
             else if (key == "q") s.q = (int)v;
             else if (key == "no_fast") k.no_fast = (int)v;
@@ -44,7 +44,7 @@ int main()
         if (!any) continue;
         const Plan p = plan_decode(s, k);
         if (p.err) printf("error=%d\n", p.err);
-        else printf("%s lds=%llu table_off=%u wg_chunks=%u\n", kFamilyNames[p.family], (unsigned long long)p.lds, p.gby_table_off, p.gby_wg_chunks);
+        else printf("%s lds=%llu table_off=%u wg_chunks=%u\n", kFamilyNames[p.family], (unsigned long long)p.lds, p.table_off, p.wg_chunks);
     }
     return 0;
 }

@@ -1,7 +1,7 @@
 """CPU tests of group-by rows (sprintz_mi355x_groupby_rows): the symbol and its binding are there, every validation return comes before
 the device is touched and names the operation, the numpy model the GPU tier compares with (tests/groupby_model.py) equals brute force and
 satisfies the identities that tie it to the column sums and to the histogram of the key column, and the planner (sprintz_amd/csrc/plan.h,
-built with g++: tests/groupby_plan_probe.cpp) sends the mode to decode_fast.h where the windowed query goes AND the table fits the
+built with g++: tests/binned_plan_probe.cpp) sends the mode to decode_fast.h where the windowed query goes AND the table fits the
 launch's LDS next to the groups' carves, to the generic kernel otherwise -- never to decode_uni.h -- and gives a workgroup its 32-bit
 table only where no sum can wrap."""
 import ctypes as C
@@ -207,11 +207,14 @@ def plan(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("no g++")
     exe = tmp_path_factory.mktemp("groupby_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "groupby_plan_probe.cpp"), "-o", str(exe)])
+    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "binned_plan_probe.cpp"), "-o", str(exe)])
 
     def ask(**fields):
         q = dict(codec=1, nchunks=4096, q=Q_GROUPBY)
         q.update(fields)
+        nbins = q.pop("nbins", 256)
+        if q["q"] == Q_GROUPBY:                  # the table: nbins x (D + 1) entries, a row adds at most 2^W - 1 to one
+            q.update(table_entries=nbins * (q["D"] + 1), table_row_max=(1 << (8 * q["esz"])) - 1)
         text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
         out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
         return out[0], {k: int(v) for k, v in (t.split("=") for t in out[1:])}

@@ -1,6 +1,6 @@
 """CPU tests of histogram rows (sprintz_mi355x_histogram_rows): the symbol and its binding are there, every validation return comes
 before the device is touched and names the operation, the numpy model the GPU tier compares with (tests/histogram_model.py) equals
-np.bincount / np.sort brute force, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/histogram_plan_probe.cpp) sends the
+np.bincount / np.sort brute force, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/binned_plan_probe.cpp) sends the
 mode to decode_fast.h where the windowed query goes AND the table fits the launch's LDS next to the groups' carves, to the generic
 kernel otherwise -- never to decode_uni.h."""
 import ctypes as C
@@ -196,11 +196,14 @@ def plan(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("no g++")
     exe = tmp_path_factory.mktemp("histogram_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "histogram_plan_probe.cpp"), "-o", str(exe)])
+    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "binned_plan_probe.cpp"), "-o", str(exe)])
 
     def ask(**fields):
         q = dict(codec=1, nchunks=4096, q=Q_HISTOGRAM)
         q.update(fields)
+        nbins = q.pop("nbins", 256)
+        if q["q"] == Q_HISTOGRAM:                # the table: D x nbins counters, a row adds at most 1 to one
+            q.update(table_entries=q["D"] * nbins, table_row_max=1)
         text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
         out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
         return out[0], {k: int(v) for k, v in (t.split("=") for t in out[1:])}
