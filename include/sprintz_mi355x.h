@@ -353,7 +353,8 @@ int sprintz_mi355x_decompress_batch(int codec, int elem_bytes,
 size_t sprintz_mi355x_huf_tmp_bytes(uint64_t nchunks);
 size_t sprintz_mi355x_huf_bound(uint64_t total_stream_bytes, uint64_t nchunks);
 /* container (d_dense, d_offsets[nchunks+1], d_sizes[nchunks] = exact stream bytes)
- * -> Huffman records at d_huf + d_huf_offsets[c] (d_huf_offsets[nchunks] = total) */
+ * -> Huffman records at d_huf + d_huf_offsets[c] (d_huf_offsets[nchunks] = total).
+ * A segment's byte counts are added in 32 bits (the oracle's in 64): 64 consecutive chunks must total less than 4 GiB. */
 int sprintz_mi355x_huf_compress_batch(const void* d_dense, const uint64_t* d_offsets, const uint32_t* d_sizes,
                                       uint64_t nchunks, void* d_huf, uint64_t* d_huf_offsets, void* d_tables,
                                       void* d_tmp, void* hip_stream);

@@ -839,25 +839,30 @@ def test_huffman_stage_matches_oracle_and_roundtrips(sz, oracle, step):
 
 
 def test_huffman_odd_batches(sz, oracle):
-    """chunk counts around the 64-chunk segment size, tiny and empty streams, byte-dense containers"""
+    """chunk counts around the 64-chunk segment size, tiny and empty streams, 16-byte aligned and byte-dense containers (on both sides
+    of the stage: the Sprintz container that goes in and the one that comes back)"""
     import torch
     rng = np.random.default_rng(77)
     for codec, esz, ndims, chunk_len, nchunks in (("delta", 1, 3, 40, 1), ("xff", 2, 8, 5120, 63), ("xff", 2, 8, 5120, 65),
                                                   ("delta", 1, 80, 1024, 129), ("xff", 1, 8, 16 * 8 + 5, 200)):
         data = gen_walk(rng, nchunks * chunk_len - chunk_len // 2, ndims, esz, 3, flat_every=3)
-        cd = sz.ChunkedCodec(codec, esz, ndims, chunk_len, device="cuda:0")
-        batch = cd.compress(torch.from_numpy(data).cuda())
-        hb = sz.huf_compress(batch)
-        dense, offs = batch.data.cpu().numpy(), batch.offsets.cpu().numpy().astype(np.uint64)
-        sizes = batch.sizes.cpu().numpy().astype(np.uint32)
-        want, want_offs, want_tables = oracle.huf_compress(dense, offs, sizes)
-        assert np.array_equal(hb.offsets.cpu().numpy().astype(np.uint64), want_offs), (codec, nchunks)
-        assert np.array_equal(hb.tables.cpu().numpy(), want_tables), (codec, nchunks)
-        assert np.array_equal(hb.data.cpu().numpy()[:want.size], want), (codec, nchunks)
-        rets = torch.empty(nchunks, dtype=torch.int64, device="cuda:0")
-        back = sz.huf_decompress(hb, int(offs[-1]), rets=rets)
-        assert np.array_equal(rets.cpu().numpy(), sizes.astype(np.int64))
-        assert np.array_equal(cd.decompress(back).cpu().numpy(), data), (codec, nchunks)
+        for align in (16, 1):
+            cd = sz.ChunkedCodec(codec, esz, ndims, chunk_len, device="cuda:0", align=align)
+            batch = cd.compress(torch.from_numpy(data).cuda())
+            hb = sz.huf_compress(batch)
+            dense, offs = batch.data.cpu().numpy(), batch.offsets.cpu().numpy().astype(np.uint64)
+            sizes = batch.sizes.cpu().numpy().astype(np.uint32)
+            if align == 1:
+                assert np.array_equal(offs[1:], np.cumsum(sizes.astype(np.uint64))), (codec, nchunks)
+            want, want_offs, want_tables = oracle.huf_compress(dense, offs, sizes)
+            assert np.array_equal(hb.offsets.cpu().numpy().astype(np.uint64), want_offs), (codec, nchunks, align)
+            assert np.array_equal(hb.tables.cpu().numpy(), want_tables), (codec, nchunks, align)
+            assert np.array_equal(hb.data.cpu().numpy()[:want.size], want), (codec, nchunks, align)
+            rets = torch.empty(nchunks, dtype=torch.int64, device="cuda:0")
+            back = sz.huf_decompress(hb, int(offs[-1]), align=align, rets=rets)
+            assert np.array_equal(rets.cpu().numpy(), sizes.astype(np.int64))
+            assert np.array_equal(back.offsets.cpu().numpy().astype(np.uint64), offs), (codec, nchunks, align)
+            assert np.array_equal(cd.decompress(back).cpu().numpy(), data), (codec, nchunks, align)
 
 
 def test_huffman_decoder_survives_damaged_containers(sz):
