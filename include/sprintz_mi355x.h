@@ -795,7 +795,9 @@ int sprintz_mi355x_huf0_compress_batch_exact(const void* d_dense, const uint64_t
  * over 128 KB tiles on persistent workgroups -- for 16-bit streams whose
  * rows are 1 .. 8 whole 16-byte pieces (or 2 / 4 / 8 bytes), two passes otherwise (env
  * SPRINTZ_MI355X_TRANSFORM_CHAIN: 0 = two passes always, n = one pass from n tiles on;
- * A/B runs, tests).  The scratch is zeroed by the call (hipMemsetAsync on the stream).
+ * A/B runs, tests).  What d_tmp holds on entry does not matter (the one-pass form zeroes
+ * the words it polls itself, hipMemsetAsync on the stream; every other array is written
+ * before it is read), and it may be reused by the next call on the stream as it is.
  * SPRINTZ_TRANSFORM_XFF is the FIRE forecaster with no packing (errors out), with
  * predict.cpp's own constants (not the codec's); only whole 8-row blocks that its
  * vector stores cannot spill past the end are forecast, the rest is plain delta
@@ -803,7 +805,11 @@ int sprintz_mi355x_huf0_compress_batch_exact(const void* d_dense, const uint64_t
  * sequential in both directions: a lane per column, latency-bound (transforms.hip).
  *   kind        : SPRINTZ_TRANSFORM_DELTA / SPRINTZ_TRANSFORM_DOUBLEDELTA / SPRINTZ_TRANSFORM_XFF
  * Device forms: len elements in, len elements out, no header;
- *   d_tmp: sprintz_mi355x_transform_tmp_bytes(kind, elem_bytes, len, ndims).
+ *   d_tmp: sprintz_mi355x_transform_tmp_bytes(kind, elem_bytes, len, ndims) bytes, 16-byte
+ *   aligned: the most that any form of the decode takes for this shape, whatever the
+ *   alignment of d_src and d_dest and whatever SPRINTZ_MI355X_TRANSFORM_CHAIN says -- it is
+ *   derived from the launcher's own layout (csrc/transform_plan.h), so a caller can size
+ *   the scratch before it knows either.
  * Host forms: the reference's container -- a 6-byte header {u32 len; u16 ndims}
  * (format.h:65-86) before the transformed elements; encode returns len + header
  * length in elements (6 @8b, 3 @16b; delta.cpp:120), decode returns len.  decode

@@ -1218,7 +1218,9 @@ def decode_xff_rowmajor_16b(src, dest, len=0, ndims=0):  # noqa: A002 (predict.h
 def transform_device(kind, x, ndims, inverse=False, out=None):
     """delta ("delta") / double delta ("doubledelta") / FIRE errors ("xff", predict.h) of one
     row-major stream resident in HBM (torch uint8/uint16 tensor); inverse=True undoes it (delta
-    kinds: a multi-level scan over the rows; xff: a lane per column, sequential in the rows)."""
+    kinds: a multi-level scan over the rows; xff: a lane per column, sequential in the rows).
+    The decode's scratch is sprintz_mi355x_transform_tmp_bytes: enough for every form of the scan at any
+    alignment of `x` and `out`, its contents on entry do not matter."""
     import torch
     k = {"delta": _lib.TRANSFORM_DELTA, "doubledelta": _lib.TRANSFORM_DOUBLEDELTA, "xff": _lib.TRANSFORM_XFF}[kind]
     esz = x.dtype.itemsize

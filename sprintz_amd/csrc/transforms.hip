@@ -24,6 +24,7 @@
 // reference exists behind one boundary.  Many independent series belong in the batched codec.
 #include "../../include/sprintz_mi355x.h"
 #include "dispatch.h"
+#include "transform_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -35,8 +36,9 @@
 
 namespace {
 
-constexpr int R = 16;            // rows (or lower-level runs) folded by one thread
-constexpr int kTB = 256;
+using namespace sprintz;         // transform_plan.h: the decode's host-side decisions and the constants they share with the kernels
+constexpr int R = kTrR;          // rows (or lower-level runs) folded by one thread
+constexpr int kTB = kTrTB;
 
 template <typename U> struct Level {
     const U* s1;                 // level 0: the input y itself
@@ -151,7 +153,7 @@ __global__ void __launch_bounds__(kTB) apply_kernel(Level<U> lo, uint64_t len, u
 // (rocprofv3 kernel trace).  One workgroup does it: thread (g, c) composes the runs of its slice g of column c, the slices' compositions
 // meet in LDS, every thread folds the slices before its own and walks its runs again writing their incoming states.
 // Same arithmetic as reduce_kernel / apply_kernel (composition (S1, S2, n) o (S1', S2', n') = (S1 + S1', S2 + n' S1 + S2', n + n')).
-constexpr int kTopT = 1024;
+constexpr int kTopT = kTrTopT;
 template <typename U, int KIND>
 __global__ void __launch_bounds__(kTopT) scan_runs_kernel(Level<U> lo, uint32_t D, uint64_t rows0, uint32_t G)
 {
@@ -197,17 +199,13 @@ __global__ void __launch_bounds__(kTopT) scan_runs_kernel(Level<U> lo, uint32_t 
 // kRowsPerLane consecutive rows of its column piece in registers, the lane summaries are scanned
 // across lanes at stride Dv with the composition above (the right operand of step s covers exactly
 // kRowsPerLane * 2^s rows), every lane advances the carried state over the rows before its own,
-// finishes its rows, stores, and the last lane's state is carried into the next load.  A run of kRunLoads loads per wavefront is one "row"
+// finishes its rows, stores, and the last lane's state is carried into the next load.  A run of run_loads loads per wavefront is one "row"
 // of level 1; the levels above it reuse reduce_kernel / apply_kernel on the summaries, which
 // have the layout of the stream's rows (packed lanes ARE elements).
-#ifndef TR_RUN_LOADS
-#define TR_RUN_LOADS 16
-#endif
 #ifndef TR_PREFETCH
 #define TR_PREFETCH 1                      // the next load of a run is requested before this one is folded (one more load in flight a wave)
 #endif
-constexpr int kRunLoads = TR_RUN_LOADS;
-constexpr int kRowsPerLane = 4;
+constexpr int kRowsPerLane = kTrRowsPerLane;
 
 // LDS hand-off between lanes of one wavefront (DS ops of a wave execute in issue order)
 __device__ __forceinline__ void wave_sync()
@@ -442,16 +440,10 @@ __global__ void __launch_bounds__(kTB) wave_scan_kernel(const typename E::T* y, 
 // LDS -- so that one step covers 512 / dv predecessors: every tile older than the ones in flight has its state out, one step finds it.
 // The composition is the one at the top of this file; a published state (x, d) is the summary (S1, S2) = (d, x) of everything before it.
 // Column pieces are independent scans: each finds its own nearest state.
-#ifndef TR_CHAIN_LOADS
-#define TR_CHAIN_LOADS 4
-#endif
 #ifndef TR_CHAIN_PREFETCH
 #define TR_CHAIN_PREFETCH 1
 #endif
-#ifndef TR_CHAIN_WAVES
-#define TR_CHAIN_WAVES 8
-#endif
-constexpr int kChainWaves = TR_CHAIN_WAVES, kChainT = 64 * kChainWaves, kChainLoads = TR_CHAIN_LOADS, kChainMaxDv = 8;
+constexpr int kChainWaves = kTrChainWaves, kChainT = 64 * kChainWaves, kChainLoads = kTrChainLoads, kChainMaxDv = kTrChainMaxDv;
 
 // What crosses workgroups: 64-bit words of 32 data bits under a 32-bit tag (0: not there yet -- the scratch is zeroed before the launch),
 // written and read with relaxed agent-scope atomics, summary and state in arrays of their own.  A word is there or not, whole: no flag beside
@@ -821,15 +813,6 @@ namespace sprintz { int set_error(int code, const char* what); }   // api.hip: t
 namespace {
 int fail(int code, const char* what) { return sprintz::set_error(code, what); }
 
-#ifndef TR_CHAIN_WGS_PER_CU
-#define TR_CHAIN_WGS_PER_CU 1
-#endif
-#ifndef TR_CHAIN_MIN_TILES
-#define TR_CHAIN_MIN_TILES 1                  // (from the first tile on: 9.6 against 13.7 us at 32 KB, 13 against 52 at 0.5 MB, 64 against 90 at 128 MB -- tools/chain_sizes.py)
-#endif
-// scratch of the one-pass decode: the ticket + two (delta) or four arrays of dv x 1 or 4 tagged 64-bit words per tile.  A tile is >= 8 waves
-// x 2 loads x 56 pieces x 4 rows, dv <= 8: below 12 % of the stream for 1-byte pieces (unaligned streams), 1.5 % for 16-byte ones
-size_t chain_tmp_bound(uint64_t stream_bytes) { return (size_t)(stream_bytes / 8) + 8192; }
 // workgroups of the one-pass decode: one per CU (each takes tiles until there are none)
 int chain_resident_wgs()
 {
@@ -847,52 +830,28 @@ uint64_t chain_min_tiles()
     const char* e = getenv("SPRINTZ_MI355X_TRANSFORM_CHAIN");
     if (!e || !e[0]) return TR_CHAIN_MIN_TILES;
     const long v = strtol(e, nullptr, 10);
-    return v <= 0 ? ~0ull : (uint64_t)v;
+    return v <= 0 ? kTrChainNever : (uint64_t)v;
 }
 
-struct Plan {
-    std::vector<uint64_t> rows;      // rows[k] = runs at level k (rows[0] = input rows)
-    std::vector<uint64_t> span;
-    size_t tmp_bytes = 0;
-};
-
-Plan make_plan(int kind, int esz, uint64_t len, uint32_t D)
+// Everything below launches what transform_plan.h's tr_plan decided: the form, the pieces, the runs, the levels and the place of every array
+// in d_tmp are read from the plan, never worked out a second time -- sprintz_mi355x_transform_tmp_bytes prices the same plan.
+template <typename U> U* at(uint8_t* tmp, uint64_t off) { return off == kTrNone ? nullptr : (U*)(tmp + off); }
+template <typename U> Level<U> level_of(const TrLevel& l, uint8_t* tmp)
 {
-    Plan p;
-    uint64_t rows = (len + D - 1) / D, span = 1;
-    p.rows.push_back(rows);
-    p.span.push_back(span);
-    while (rows > 1) {                                   // the top level is a single run
-        rows = (rows + R - 1) / R;
-        span *= R;
-        p.rows.push_back(rows);
-        p.span.push_back(span);
-    }
-    const size_t arrays = kind ? 4 : 2;                  // s1 [, s2], xin [, din] per level >= 1
-    for (size_t k = 1; k < p.rows.size(); k++) p.tmp_bytes += ((p.rows[k] * D * (size_t)esz + 63) & ~(size_t)63) * arrays;
-    return p;
+    return Level<U>{at<U>(tmp, l.s1), at<U>(tmp, l.s2), at<U>(tmp, l.xin), at<U>(tmp, l.din), l.rows, l.span};
 }
 
-// levels above `base` (base.rows runs of base.span original rows each, summaries already in base.s1/s2):
+// levels above `base` (base.rows runs of base.span original rows each, summaries already in base.s1/s2), up[0 .. nup) of the plan:
 // fills base.xin / base.din with every run's incoming state.  With base = the input itself
 // (span 1) the last apply writes x into dest instead.
 template <typename U, int KIND>
-int scan_levels(Level<U> base, uint64_t len, uint32_t D, uint64_t rows0, U* dest, uint8_t* tmp, hipStream_t st)
+int scan_levels(Level<U> base, const TrLevel* up, int nup, uint64_t len, uint32_t D, uint64_t rows0, U* dest, uint8_t* tmp, hipStream_t st)
 {
     std::vector<Level<U>> lv;
     lv.push_back(base);
-    uint8_t* t = tmp;
-    auto take = [&](uint64_t n) { U* q = (U*)t; t += (n * D * sizeof(U) + 63) & ~(size_t)63; return q; };
-    while (lv.back().rows > 1) {
-        const uint64_t rows = (lv.back().rows + R - 1) / R;
-        U* s1 = take(rows);
-        U* s2 = KIND ? take(rows) : nullptr;
-        U* xi = take(rows);
-        U* di = KIND ? take(rows) : nullptr;
-        lv.push_back(Level<U>{s1, s2, xi, di, rows, lv.back().span * R});
-    }
+    for (int k = 0; k < nup; k++) lv.push_back(level_of<U>(up[k], tmp));
     const size_t L = lv.size();
-    for (size_t k = 0; k + 1 < L; k++) {
+    for (size_t k = 0; k + 2 < L; k++) {                 // (not into the top level: a single run whose summary nothing reads, no arrays)
         const uint64_t threads = lv[k + 1].rows * D;
         hipLaunchKernelGGL((reduce_kernel<U, KIND>), dim3((unsigned)((threads + kTB - 1) / kTB)), dim3(kTB), 0, st, lv[k], len, D, rows0,
                            (U*)lv[k + 1].s1, (U*)lv[k + 1].s2, lv[k + 1].rows);
@@ -910,97 +869,50 @@ int scan_levels(Level<U> base, uint64_t len, uint32_t D, uint64_t rows0, U* dest
     return hipGetLastError() == hipSuccess ? 0 : fail(SPRINTZ_E_HIP, "transform decode launch");
 }
 
-// piece size of the wave-scan path for this stream: 16, 4 or sizeof(U) bytes -- the largest that
-// divides the row, the stream and the pointers' alignment, with a power-of-two piece count <= 64
-template <typename U>
-int wave_piece_bytes(const void* y, const void* dest, uint64_t len, uint32_t D)
-{
-    const uint64_t row_bytes = (uint64_t)D * sizeof(U), total = len * sizeof(U);
-    for (int pb : {16, 4, (int)sizeof(U)}) {
-        if (pb < (int)sizeof(U) || row_bytes % pb || total % pb) continue;
-        if (((uintptr_t)y | (uintptr_t)dest) % pb) continue;
-        const uint64_t dv = row_bytes / pb;
-        // any piece count up to 64 (64 / dv whole rows per load); 1 and 2 go through the LDS hand-over, which is laid out for 64 pieces
-        if (dv <= 64 && ((dv & (dv - 1)) == 0 || dv >= 3)) return pb;
-    }
-    return 0;
-}
-
 template <typename U, typename E, int KIND>
-int decode_wave(const U* y, uint64_t len, uint32_t D_real, U* dest, uint8_t* tmp, hipStream_t st)
+int decode_wave(const TrPlan& p, const U* y, uint64_t len, U* dest, uint8_t* tmp, hipStream_t st)
 {
     typedef typename E::T T;
-    // (rows shorter than a piece, E::M > 1: the levels above see the replicated 16-byte pieces as rows of 16 / sizeof(U) columns)
-    const uint32_t D = E::M > 1 ? (uint32_t)(sizeof(T) / sizeof(U)) : D_real;
-    const uint32_t dv = E::M > 1 ? 1u : (uint32_t)((uint64_t)D * sizeof(U) / sizeof(T));
-    const uint64_t len_e = len * sizeof(U) / sizeof(T);
-    const uint64_t rows0 = (len + D_real - 1) / D_real;                  // real rows
-    // loads a run: 16 where there are runs enough to fill the chip; short streams take 4 or 1 -- a run's loads are a serial chain, and a stream of
-    // eight 16-load runs was two passes of 16 dependent round trips on eight waves: 52 us for 0.5 MB (tools/chain_sizes.py) -- as long as the
-    // runs' states still come from the one workgroup of scan_runs_kernel (<= 4 096 runs)
-    int run_loads = kRunLoads;
-    {
-        const uint64_t rows16 = (uint64_t)kRunLoads * kRowsPerLane * (64 / dv) * E::M, n16 = (rows0 + rows16 - 1) / rows16;
-        if (n16 * 16 <= 4096) run_loads = 1;
-        else if (n16 * 4 <= 4096) run_loads = 4;
-    }
-    const uint64_t run_rows = (uint64_t)run_loads * kRowsPerLane * (64 / dv) * E::M;
-    const uint64_t nruns = (rows0 + run_rows - 1) / run_rows;
-    const unsigned grid = (unsigned)((nruns * 64 + kTB - 1) / kTB);
-    // ---- streams of at least TR_CHAIN_MIN_TILES tiles, rows of at most kChainMaxDv pieces: one pass (chain_scan_kernel)
-    // (16-bit elements only: at 8 bits the packed arithmetic is five instructions an add where v_pk_add_u16 is one, the tile's fold and walk
-    //  run on one workgroup a CU, and the form measured SLOWER than the two passes on every column count -- tools/transforms_shapes.py:
-    //  delta 0.126 - 0.167 against 0.103 - 0.143 ms on 128 MiB, double delta 0.28 - 0.48 against 0.15 - 0.26; at 16 bits 0.063 - 0.074 against 0.090 - 0.124.
-    //  And 16-byte pieces only: with 4- or 2-byte pieces (rows that are not multiples of 16 bytes) a tile is 32 / 16 KB and the look-back is the kernel:
-    //  3 / 5 / 7 / 10 / 12 uint16 columns 0.199 / 0.284 / 0.220 / 0.147 / 0.133 against 0.160 / 0.158 / 0.154 / 0.125 / 0.121 ms.)
-    if constexpr (sizeof(U) == 2 && sizeof(T) == 16)
-    if (dv <= (uint32_t)kChainMaxDv) {
-        const uint64_t tile_e = (uint64_t)kChainWaves * kChainLoads * (uint64_t)((64 / dv) * dv) * kRowsPerLane;
-        const uint64_t ntiles = (len_e + tile_e - 1) / tile_e;
-        auto up = [](size_t v, size_t a) { return (v + a - 1) & ~(a - 1); };
-        const size_t arr = up((size_t)ntiles * dv * ChainWs<T>::kWords * 8, 256), need = 256 + (KIND ? 4 : 2) * arr;
-        if (ntiles >= chain_min_tiles() && ntiles < 0x7fffffffull && need <= chain_tmp_bound(len * sizeof(U))) {
+    static_assert(E::M == 1 || sizeof(T) == 16, "rows inside a piece: 16-byte pieces");
+    const uint32_t dv = p.dv;
+    const unsigned grid = (unsigned)p.grid;
+    // ---- the one-pass decode (chain_scan_kernel): 16-bit elements in 16-byte pieces only, which is all tr_plan gives it
+    if (p.family == SPRINTZ_KF_TR_CHAIN) {
+        if constexpr (sizeof(U) == 2 && sizeof(T) == 16) {
             ChainWs<T> ws;
-            ws.ticket = (uint32_t*)tmp;
-            ws.agg1 = (uint64_t*)(tmp + 256);
-            ws.inc1 = (uint64_t*)(tmp + 256 + arr);
-            ws.agg2 = KIND ? (uint64_t*)(tmp + 256 + 2 * arr) : nullptr;
-            ws.inc2 = KIND ? (uint64_t*)(tmp + 256 + 3 * arr) : nullptr;
-            if (hipMemsetAsync(tmp, 0, need, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode: hipMemsetAsync of the tiles' words");
-            const uint64_t wgs = ntiles < (uint64_t)chain_resident_wgs() ? ntiles : (uint64_t)chain_resident_wgs();
-            hipLaunchKernelGGL((chain_scan_kernel<E, KIND>), dim3((unsigned)wgs), dim3(kChainT), 0, st, (const T*)y, len_e, dv, ws, (T*)dest, (uint32_t)ntiles);
+            ws.ticket = (uint32_t*)(tmp + p.ticket);
+            ws.agg1 = at<uint64_t>(tmp, p.agg1);
+            ws.inc1 = at<uint64_t>(tmp, p.inc1);
+            ws.agg2 = at<uint64_t>(tmp, p.agg2);
+            ws.inc2 = at<uint64_t>(tmp, p.inc2);
+            if (hipMemsetAsync(tmp, 0, p.need, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode: hipMemsetAsync of the tiles' words");
+            hipLaunchKernelGGL((chain_scan_kernel<E, KIND>), dim3((unsigned)p.wgs), dim3(kChainT), 0, st, (const T*)y, p.len_e, dv, ws, (T*)dest, (uint32_t)p.ntiles);
             if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode launch");
             sprintz::dispatched(SPRINTZ_KF_TR_CHAIN);
             return 0;
+        } else {
+            return fail(SPRINTZ_E_UNSUPPORTED, "transform decode: the one-pass form planned for pieces it does not have");
         }
     }
-    if (nruns == 1) {
-        hipLaunchKernelGGL((wave_scan_kernel<E, KIND, true>), dim3(grid), dim3(kTB), 0, st, (const T*)y, len_e, dv, nruns,
-                           (const T*)nullptr, (const T*)nullptr, (T*)nullptr, (T*)nullptr, (T*)dest, run_loads);
+    if (p.nruns == 1) {
+        hipLaunchKernelGGL((wave_scan_kernel<E, KIND, true>), dim3(grid), dim3(kTB), 0, st, (const T*)y, p.len_e, dv, p.nruns,
+                           (const T*)nullptr, (const T*)nullptr, (T*)nullptr, (T*)nullptr, (T*)dest, p.run_loads);
         if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode launch");
         sprintz::dispatched(SPRINTZ_KF_TR_WAVE);
         return 0;
     }
     // level 1 = one summary per run, laid out like rows of the stream
-    uint8_t* t = tmp;
-    auto take = [&](uint64_t n) { U* q = (U*)t; t += (n * D * sizeof(U) + 63) & ~(size_t)63; return q; };
-    U* s1 = take(nruns);
-    U* s2 = KIND ? take(nruns) : nullptr;
-    U* xi = take(nruns);
-    U* di = KIND ? take(nruns) : nullptr;
-    hipLaunchKernelGGL((wave_scan_kernel<E, KIND, false>), dim3(grid), dim3(kTB), 0, st, (const T*)y, len_e, dv, nruns, (const T*)nullptr,
-                       (const T*)nullptr, (T*)s1, (T*)s2, (T*)nullptr, run_loads);
-    const Level<U> base{s1, s2, xi, di, nruns, run_rows};
-    if (D <= 64 && nruns <= 4096) {                      // (wide rows, or streams long enough that six ~4.6 us launches do not matter: the generic levels --
-                                                         //  with 16 384 runs the one workgroup measured slower than they are: 0.72 against 0.66 ms at 512 Mi samples)
-        const uint32_t Gmax = (uint32_t)kTopT / D, G = (uint32_t)(nruns < Gmax ? nruns : Gmax);
-        hipLaunchKernelGGL((scan_runs_kernel<U, KIND>), dim3(1), dim3(kTopT), 0, st, base, D, rows0, G);
+    const Level<U> base = level_of<U>(p.lv[0], tmp);
+    hipLaunchKernelGGL((wave_scan_kernel<E, KIND, false>), dim3(grid), dim3(kTB), 0, st, (const T*)y, p.len_e, dv, p.nruns, (const T*)nullptr,
+                       (const T*)nullptr, (T*)base.s1, (T*)base.s2, (T*)nullptr, p.run_loads);
+    if (p.top == kTrTopRuns) {
+        hipLaunchKernelGGL((scan_runs_kernel<U, KIND>), dim3(1), dim3(kTopT), 0, st, base, p.D, p.rows0, p.G);
     } else {
-        int rc = scan_levels<U, KIND>(base, len, D, rows0, dest, t, st);
+        int rc = scan_levels<U, KIND>(base, p.lv + 1, p.nlevels - 1, len, p.D, p.rows0, dest, tmp, st);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL((wave_scan_kernel<E, KIND, true>), dim3(grid), dim3(kTB), 0, st, (const T*)y, len_e, dv, nruns, (const T*)xi,
-                       (const T*)di, (T*)nullptr, (T*)nullptr, (T*)dest, run_loads);
+    hipLaunchKernelGGL((wave_scan_kernel<E, KIND, true>), dim3(grid), dim3(kTB), 0, st, (const T*)y, p.len_e, dv, p.nruns, (const T*)base.xin,
+                       (const T*)base.din, (T*)nullptr, (T*)nullptr, (T*)dest, p.run_loads);
     if (hipGetLastError() != hipSuccess) return fail(SPRINTZ_E_HIP, "transform decode launch");
     sprintz::dispatched(SPRINTZ_KF_TR_WAVE);
     return 0;
@@ -1010,26 +922,32 @@ template <typename U, int KIND>
 int decode_device(const U* y, uint64_t len, uint32_t D, U* dest, uint8_t* tmp, hipStream_t st)
 {
     typedef typename std::conditional<sizeof(U) == 1, P8, P16>::type P;
-    const uint64_t rb = (uint64_t)D * sizeof(U);
-    if (rb < 16 && 16 % rb == 0 && (len * sizeof(U)) % 16 == 0 && (((uintptr_t)y | (uintptr_t)dest) % 16) == 0) {
-        switch ((int)rb) {                               // rows shorter than a piece
-            case 1: if constexpr (sizeof(U) == 1) return decode_wave<U, Sub<P, 1>, KIND>(y, len, D, dest, tmp, st); else break;
-            case 2: return decode_wave<U, Sub<P, 2>, KIND>(y, len, D, dest, tmp, st);
-            case 4: return decode_wave<U, Sub<P, 4>, KIND>(y, len, D, dest, tmp, st);
-            case 8: return decode_wave<U, Sub<P, 8>, KIND>(y, len, D, dest, tmp, st);
+    TrShape s;
+    s.kind = KIND; s.esz = (int)sizeof(U); s.len = len; s.D = D;
+    s.src_lo = (unsigned)((uintptr_t)y & 15u); s.dst_lo = (unsigned)((uintptr_t)dest & 15u);
+    s.chain_min = chain_min_tiles();
+    if (sizeof(U) == 2) s.cus = (uint32_t)chain_resident_wgs();      // (only 16-bit streams have the one-pass form)
+    const TrPlan p = tr_plan(s);
+    if (p.family == SPRINTZ_KF_TR_LEVELS) {
+        const int rc = scan_levels<U, KIND>(Level<U>{y, y, nullptr, nullptr, p.rows0, 1}, p.lv, p.nlevels, len, D, p.rows0, dest, tmp, st);
+        if (!rc) sprintz::dispatched(SPRINTZ_KF_TR_LEVELS);
+        return rc;
+    }
+    if (p.M > 1) {                                       // rows shorter than a piece
+        switch (16 / p.M) {
+            case 1: if constexpr (sizeof(U) == 1) return decode_wave<U, Sub<P, 1>, KIND>(p, y, len, dest, tmp, st); else break;
+            case 2: return decode_wave<U, Sub<P, 2>, KIND>(p, y, len, dest, tmp, st);
+            case 4: return decode_wave<U, Sub<P, 4>, KIND>(p, y, len, dest, tmp, st);
+            case 8: return decode_wave<U, Sub<P, 8>, KIND>(p, y, len, dest, tmp, st);
             default: break;
         }
+        return fail(SPRINTZ_E_UNSUPPORTED, "transform decode: rows inside a piece of a size no kernel has");
     }
-    switch (wave_piece_bytes<U>(y, dest, len, D)) {
-        case 16: return decode_wave<U, V4<P>, KIND>(y, len, D, dest, tmp, st);
-        case 4: return decode_wave<U, P, KIND>(y, len, D, dest, tmp, st);
-        case 1: case 2: return decode_wave<U, S1x<U>, KIND>(y, len, D, dest, tmp, st);
-        default: break;
+    switch (p.piece) {
+        case 16: return decode_wave<U, V4<P>, KIND>(p, y, len, dest, tmp, st);
+        case 4: return decode_wave<U, P, KIND>(p, y, len, dest, tmp, st);
+        default: return decode_wave<U, S1x<U>, KIND>(p, y, len, dest, tmp, st);
     }
-    const uint64_t rows0 = (len + D - 1) / D;
-    const int rc = scan_levels<U, KIND>(Level<U>{y, y, nullptr, nullptr, rows0, 1}, len, D, rows0, dest, tmp, st);
-    if (!rc) sprintz::dispatched(SPRINTZ_KF_TR_LEVELS);
-    return rc;
 }
 
 template <typename U, int KIND>
@@ -1172,7 +1090,7 @@ size_t sprintz_mi355x_transform_tmp_bytes(int kind, int elem_bytes, uint64_t len
 {
     if (ndims == 0 || (elem_bytes != 1 && elem_bytes != 2)) return 0;
     if (kind == SPRINTZ_TRANSFORM_XFF) return 64;              // no scratch: a lane per column
-    return make_plan(kind, elem_bytes, len, ndims).tmp_bytes + chain_tmp_bound(len * (uint64_t)elem_bytes) + 64;
+    return (size_t)tr_tmp_bytes(kind, elem_bytes, len, ndims);
 }
 
 int sprintz_mi355x_transform_encode_device(int kind, int elem_bytes, const void* d_src, uint64_t len, uint16_t ndims, void* d_dest,
