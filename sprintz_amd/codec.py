@@ -17,7 +17,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _lib, rowops
 
 _NP = {1: np.uint8, 2: np.uint16}
 _CODEC_ID = {"delta": _lib.CODEC_DELTA, "xff": _lib.CODEC_XFF,
@@ -173,12 +173,18 @@ class ChunkedCodec:
                                            ws["sizes"].data_ptr(), ws["rets"].data_ptr(), self._stream()))
         return ws
 
-    def compact(self, ws, nchunks, dense=None, offsets=None):
+    def _new_container(self, nchunks, dense=None, offsets=None):
+        """the dense container of nchunks chunks at their bound, readable READ_SLACK bytes past it, and its offsets (what the caller
+        brought stays)"""
         t = self.torch
         if dense is None:
             dense = t.empty(nchunks * self.slot_stride + _lib.READ_SLACK, dtype=t.uint8, device=self.device)
         if offsets is None:
             offsets = t.empty(nchunks + 1, dtype=t.int64, device=self.device)
+        return dense, offsets
+
+    def compact(self, ws, nchunks, dense=None, offsets=None):
+        dense, offsets = self._new_container(nchunks, dense, offsets)
         with self._on():
             _lib.check(_lib.compact(ws["slots"].data_ptr(), self.slot_stride, ws["sizes"].data_ptr(), nchunks, self.align,
                                     dense.data_ptr(), offsets.data_ptr(), ws["tmp"].data_ptr(), self._stream()))
@@ -187,15 +193,11 @@ class ChunkedCodec:
     def compress_dense(self, src_padded_u8, total_len, ws=None, dense=None, offsets=None):
         """the whole write path in one call (what the bench times): src -> dense container + offsets.  For the shapes
         the fast encoder takes this is ONE launch (the container is built inside it, csrc/compact_tail.h); align 16 only."""
-        t = self.torch
         if self.align != 16:
             raise ValueError("compress_dense builds the 16-byte aligned container; use compress_to_slots + compact for another alignment")
         nchunks = int(_lib.num_chunks(total_len, self.chunk_len))
         ws = ws or self.workspace(nchunks)
-        if dense is None:
-            dense = t.empty(nchunks * self.slot_stride + _lib.READ_SLACK, dtype=t.uint8, device=self.device)
-        if offsets is None:
-            offsets = t.empty(nchunks + 1, dtype=t.int64, device=self.device)
+        dense, offsets = self._new_container(nchunks, dense, offsets)
         with self._on():
             _lib.check(_lib.compress_batch_dense(_CODEC_ID[self.codec], self.esz, src_padded_u8.data_ptr(), total_len,
                                                  self.chunk_len, self.ndims, ws["slots"].data_ptr(), self.slot_stride,
@@ -239,7 +241,6 @@ class ChunkedCodec:
     def compress_colmajor(self, cols, nrows=None):
         """cols[d, r] = sample r of variable d.  Chunk = chunk_len/ndims rows of all variables; the
         streams are what the reference produces for the row-major flattening of those rows."""
-        t = self.torch
         if cols.dim() != 2 or cols.shape[0] != self.ndims or cols.dtype.itemsize != self.esz or not cols.is_contiguous():
             raise ValueError("cols must be a contiguous [ndims, col_stride] tensor of the codec's element type")
         if self.chunk_len % self.ndims:
@@ -250,8 +251,7 @@ class ChunkedCodec:
         nchunks = (nrows + rows_per_chunk - 1) // rows_per_chunk
         ws = self.workspace(nchunks)
         if self.align == 16:                                # encode + container in one call (one launch where the encoder carries the tail)
-            dense = t.empty(nchunks * self.slot_stride + _lib.READ_SLACK, dtype=t.uint8, device=self.device)
-            offsets = t.empty(nchunks + 1, dtype=t.int64, device=self.device)
+            dense, offsets = self._new_container(nchunks)
             with self._on():
                 _lib.check(_lib.compress_batch_colmajor_dense(_CODEC_ID[self.codec], self.esz, cols.data_ptr(), nrows, col_stride, rows_per_chunk,
                                                               self.ndims, ws["slots"].data_ptr(), self.slot_stride, ws["sizes"].data_ptr(),
@@ -302,6 +302,12 @@ class ChunkedCodec:
                 _lib.check(_lib.query_reduce(opid, partials.data_ptr(), n, self.ndims, res.data_ptr(), self._stream()))
         return res, (out[: batch.total_len] if materialize else None)
 
+    def _general(self, general_layout):
+        return _lib.QUERY_GENERAL_LAYOUT if general_layout else 0
+
+    def _rets(self, n, check):
+        return self.torch.empty(n, dtype=self.torch.int64, device=self.device) if check else None
+
     def query_windows(self, batch, window_rows, ops=("min", "max", "sum"), general_layout=False, per_chunk=False, check=True):
         """Per-window min / max / sum of every column, fused into the decode (nothing but the results leaves the chip).
 
@@ -309,34 +315,21 @@ class ChunkedCodec:
         nwin = ceil(ceil(chunk_len / ndims) / window_rows); window_rows a multiple of 8.
         Default: windows over the batch's rows -- window w covers rows [w*W, min((w+1)*W, rows)), rows =
         ceil(total_len / ndims) -- as {op: [nwindows, ndims]}.  That needs chunk_len % ndims == 0 and R = chunk_len / ndims
-        either a multiple of W or a divisor of it (then the kernel takes one window a chunk and W / R chunks fold here).
+        either a multiple of W or a divisor of it (then the kernel takes one window a chunk and W / R chunks fold here; W == R counts as
+        a divisor, as in aggregate_rows and moments_rows, so it is served whether or not R is a multiple of 8 -- rowops.plan_windows).
+        window_rows below 1 is a ValueError in either mode.
         ops: any of "min", "max" (codec dtype), "sum" (int64) and, global windows only, "count" (int64) and "mean" (float64).
         Empty windows hold the identities (min all ones, max 0, sum 0).  check=True raises SprintzError naming the first
         damaged chunk."""
         torch = self.torch
-        ops = (ops,) if isinstance(ops, str) else tuple(ops)
-        unknown = set(ops) - {"min", "max", "sum", "count", "mean"}
-        if unknown or not ops:
-            raise ValueError(f"ops must be a non-empty subset of min / max / sum / count / mean, not {ops}")
+        ops = rowops.normalise_ops(ops, ("min", "max", "sum", "count", "mean"), "min / max / sum / count / mean")
         if per_chunk and set(ops) & {"count", "mean"}:
             raise ValueError("count and mean exist for global windows only (per_chunk=False)")
         W, D, n = int(window_rows), self.ndims, batch.nchunks
-        R = -(-self.chunk_len // D)
-        if per_chunk:
-            kw = W
-        else:
-            if W < 1:
-                raise ValueError("window_rows must be positive")
-            if self.chunk_len % D:
-                raise ValueError(f"global windows need chunk_len % ndims == 0 ({self.chunk_len} % {D}): use per_chunk=True")
-            if R % W == 0:
-                kw = W
-            elif W % R == 0:
-                kw = -(-R // 8) * 8                         # one window a chunk (any multiple of 8 >= R), folded below
-            else:
-                raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: "
-                                 "use per_chunk=True")
-        nwin = -(-R // kw) if kw > 0 else 0
+        if not per_chunk and self.chunk_len % D:
+            raise ValueError(f"global windows need chunk_len % ndims == 0 ({self.chunk_len} % {D}): use per_chunk=True")
+        R, _ = rowops.chunk_rows(self.chunk_len, D)
+        kw, fold, nwin = rowops.plan_windows(R, W, per_chunk)
         bits = (_lib.QUERY_WIN_MIN if "min" in ops else 0) | (_lib.QUERY_WIN_MAX if "max" in ops else 0) | \
                (_lib.QUERY_WIN_SUM if set(ops) & {"sum", "mean"} else 0)
         if bits == 0:                                       # count alone: no decode needed
@@ -349,41 +342,22 @@ class ChunkedCodec:
             res["max"] = torch.empty(shape, dtype=self.dtype, device=self.device)
         if bits & _lib.QUERY_WIN_SUM:
             res["sum"] = torch.empty(shape, dtype=torch.int64, device=self.device)
-        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        rets = self._rets(n, check)
         with self._on():
             _lib.check(_lib.query_windows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
-                                          self.chunk_len, D, kw, bits,
-                                          _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                          self.chunk_len, D, kw, bits, self._general(general_layout),
                                           res["min"].data_ptr() if "min" in res else None,
                                           res["max"].data_ptr() if "max" in res else None,
                                           res["sum"].data_ptr() if "sum" in res else None,
                                           rets.data_ptr() if rets is not None else None, self._stream()))
-        if check and n:
-            bad = (rets < 0).nonzero()
-            if bad.numel():
-                c = int(bad[0, 0].item())
-                raise _lib.SprintzError(int(rets[c].item()), f"query_windows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if check:
+            rowops.raise_damaged("query_windows", rets, n, _lib.SprintzError)
         if per_chunk:
             return {k: v for k, v in res.items() if k in ops}
-        rows = -(-batch.total_len // D)
-        nw = -(-rows // W)
-        if R % W == 0:                                      # chunk windows are global windows: chunk c holds rows [c R, (c+1) R)
-            out = {k: v.reshape(n * nwin, D)[:nw] for k, v in res.items()}
-        else:                                               # f = W / R consecutive chunks a window (int32: torch's uint16 lacks most reductions)
-            f = W // R
-            pad = nw * f - n
-            out = {}
-            for k, v in res.items():
-                v = v.reshape(n, D)
-                if k == "sum":
-                    out[k] = torch.cat([v, v.new_zeros((pad, D))]).reshape(nw, f, D).sum(dim=1)
-                else:
-                    ident = (1 << (8 * self.esz)) - 1 if k == "min" else 0
-                    v32 = torch.cat([v.to(torch.int32), torch.full((pad, D), ident, dtype=torch.int32, device=self.device)])
-                    v32 = v32.reshape(nw, f, D)
-                    out[k] = (v32.amin(dim=1) if k == "min" else v32.amax(dim=1)).to(self.dtype)
+        out = rowops.fold_windows(res, n, nwin, D, W, fold, batch.total_len, self.esz, self.dtype)
         if set(ops) & {"count", "mean"}:
             # column d of window w: the full rows of the window, plus the partial last row where it reaches column d
+            nw = -(-(-(-batch.total_len // D)) // W)
             full, part = divmod(batch.total_len, D)
             w0 = torch.arange(nw, dtype=torch.int64, device=self.device) * W
             cnt = (torch.clamp(torch.clamp(w0 + W, max=full) - w0, min=0))[:, None].expand(nw, D).clone()
@@ -425,45 +399,16 @@ class ChunkedCodec:
             _lib.check(_lib.gather_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), batch.nchunks,
                                         self.chunk_len, D, starts.data_ptr(), n, rows, out.data_ptr(),
                                         rets.data_ptr() if rets is not None else None, self._stream()))
-        if check:
-            bad = (rets[:n] < 0).nonzero()
-            if bad.numel():
-                i = int(bad[0, 0].item())
-                code = int(rets[i].item())
-                what = "needs a row the batch does not hold" if code == _lib.E_INVALID else "touches a damaged chunk"
-                raise _lib.SprintzError(code, f"gather_rows: range {i} (start {int(starts[i].item())}) {what} (decoder returned {code})")
+        i = rowops.first_bad(rets, n) if check else None
+        if i is not None:
+            code = int(rets[i].item())
+            what = "needs a row the batch does not hold" if code == _lib.E_INVALID else "touches a damaged chunk"
+            raise _lib.SprintzError(code, f"gather_rows: range {i} (start {int(starts[i].item())}) {what} (decoder returned {code})")
         return out.view(n, rows, D)
 
     def _filter_bounds(self, lo, hi, mode):
         """lo / hi: a scalar, a sequence of ndims entries (None = open end) or a device tensor -> two contiguous device tensors [ndims]"""
-        torch = self.torch
-        D, top = self.ndims, (1 << (8 * self.esz)) - 1
-
-        def entries(v, name):
-            if torch.is_tensor(v):
-                if v.dtype != self.dtype or v.numel() != D:
-                    raise ValueError(f"{name} must hold {D} entries of {self.dtype}")
-                return None
-            vals = [v] * D if v is None or np.isscalar(v) else list(v)
-            if len(vals) != D:
-                raise ValueError(f"{name} must be a scalar or have {D} entries, not {len(vals)}")
-            if any(e is not None and not 0 <= int(e) <= top for e in vals):
-                raise ValueError(f"{name} entries must be in 0..{top}")
-            return vals
-
-        lo_l, hi_l = entries(lo, "lo"), entries(hi, "hi")
-        if lo_l is not None and hi_l is not None and mode == "any":      # a column without any bound never matches: an empty interval
-            for d in range(D):
-                if lo_l[d] is None and hi_l[d] is None:
-                    lo_l[d], hi_l[d] = top, 0
-
-        def tensor(v, vals, open_end):
-            if vals is None:
-                return v.to(self.device).reshape(-1).contiguous()
-            a = np.array([open_end if e is None else int(e) for e in vals], np.uint8 if self.esz == 1 else np.uint16)
-            return torch.from_numpy(a.view(np.int8 if self.esz == 1 else np.int16)).to(self.device).view(self.dtype)
-
-        return tensor(lo, lo_l, 0), tensor(hi, hi_l, top)
+        return rowops.filter_bounds(lo, hi, mode, self.ndims, self.esz, self.dtype, self.device)
 
     def filter_rows(self, batch, lo, hi, mode="all", general_layout=False, ids=False, check=True):
         """Which rows satisfy a condition on their columns, straight from the compressed batch (one launch, no sample leaves the chip).
@@ -483,25 +428,18 @@ class ChunkedCodec:
         if mode not in ("all", "any"):
             raise ValueError("mode must be 'all' or 'any'")
         D, n = self.ndims, batch.nchunks
-        if ids and self.chunk_len % D:
-            raise ValueError(f"ids need chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "ids" if ids else None, verb="need")
         lo_t, hi_t = self._filter_bounds(lo, hi, mode)
-        R = -(-self.chunk_len // D)
-        MB = -(-R // 8)
         mask = torch.empty((n, MB), dtype=torch.uint8, device=self.device)
         counts = torch.empty(n, dtype=torch.int32, device=self.device)
-        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        rets = self._rets(n, check)
         with self._on():
             _lib.check(_lib.filter_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
                                         self.chunk_len, D, lo_t.data_ptr(), hi_t.data_ptr(),
-                                        _lib.FILTER_ALL if mode == "all" else _lib.FILTER_ANY,
-                                        _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                        _lib.FILTER_ALL if mode == "all" else _lib.FILTER_ANY, self._general(general_layout),
                                         mask.data_ptr(), counts.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
-        if check and n:
-            bad = (rets < 0).nonzero()
-            if bad.numel():
-                c = int(bad[0, 0].item())
-                raise _lib.SprintzError(int(rets[c].item()), f"filter_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if check:
+            rowops.raise_damaged("filter_rows", rets, n, _lib.SprintzError)
         res = {"mask": mask, "counts": counts}
         if ids:
             incl = torch.cumsum(counts.to(torch.int64), 0)
@@ -513,6 +451,15 @@ class ChunkedCodec:
                     _lib.check(_lib.filter_row_ids(mask.data_ptr(), bases.data_ptr(), n, self.chunk_len, D, out.data_ptr(), total, self._stream()))
             res["ids"] = out
         return res
+
+    def _where(self, op, method, batch, lo, hi, mode, /, counts=False, **kw):
+        """filter_rows (lo / hi / mode), then `method` on its mask (counts=True: and its counts).  Whole rows are asked for before the
+        filter launches."""
+        rowops.chunk_rows(self.chunk_len, self.ndims, op)
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
+        if counts:
+            kw["counts"] = f["counts"]
+        return method(batch, mask=f["mask"], **kw)
 
     def select_rows(self, batch, mask, counts=None, out=None, ids=False, general_layout=False, check=True):
         """The rows a mask names, packed densely: every chunk decoded once, only the selected rows stored (one launch).
@@ -527,13 +474,8 @@ class ChunkedCodec:
         check=True raises SprintzError naming the first damaged chunk."""
         torch = self.torch
         D, n = self.ndims, batch.nchunks
-        if self.chunk_len % D:
-            raise ValueError(f"select_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
-        R = self.chunk_len // D
-        MB = -(-R // 8)
-        if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
-            raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
-        mask = mask.contiguous()
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "select_rows")
+        mask = rowops.check_mask(mask, n, MB, self.device)
         if counts is None:
             m = mask.view(n, MB).to(torch.int32)
             if R % 8:
@@ -554,28 +496,22 @@ class ChunkedCodec:
         if n == 0:
             return res
         bases = (incl - counts).contiguous()
-        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        rets = self._rets(n, check)
         dest = out if out.numel() else torch.empty(D, dtype=self.dtype, device=self.device)   # (no row selected: the chunks are still checked)
         with self._on():
             _lib.check(_lib.select_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
-                                        self.chunk_len, D, mask.data_ptr(), bases.data_ptr(), total,
-                                        _lib.QUERY_GENERAL_LAYOUT if general_layout else 0, dest.data_ptr(),
-                                        res["ids"].data_ptr() if ids else None, rets.data_ptr() if rets is not None else None, self._stream()))
+                                        self.chunk_len, D, mask.data_ptr(), bases.data_ptr(), total, self._general(general_layout),
+                                        dest.data_ptr(), res["ids"].data_ptr() if ids else None,
+                                        rets.data_ptr() if rets is not None else None, self._stream()))
         if check:
-            bad = (rets < 0).nonzero()
-            if bad.numel():
-                c = int(bad[0, 0].item())
-                raise _lib.SprintzError(int(rets[c].item()), f"select_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+            rowops.raise_damaged("select_rows", rets, n, _lib.SprintzError)
         return res
 
     def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False):
         """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
         filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.
         -> {"rows": [total, ndims], and with ids=True "ids": int64 [total]}, in ascending batch row order."""
-        if self.chunk_len % self.ndims:
-            raise ValueError(f"where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
-        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=general_layout, check=True)
-        return self.select_rows(batch, f["mask"], counts=f["counts"], ids=ids, general_layout=general_layout)
+        return self._where("where", self.select_rows, batch, lo, hi, mode, counts=True, ids=ids, general_layout=general_layout)
 
     def aggregate_rows(self, batch, mask, window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False, per_chunk=False,
                        check=True):
@@ -586,37 +522,16 @@ class ChunkedCodec:
         not exist are ignored.  window_rows=None: one window a chunk.
         per_chunk=True: the kernel's chunk-relative windows, {op: [nchunks, nwin, ndims]} and "count": [nchunks, nwin], nwin =
         ceil(R / window_rows), window_rows a multiple of 8.  Default: windows over the batch's rows, as query_windows folds them --
-        {op: [nwindows, ndims]}, "count": [nwindows] -- which needs R to be a multiple or a divisor of window_rows.
+        {op: [nwindows, ndims]}, "count": [nwindows] -- which needs R to be a multiple of window_rows or a divisor of it.
         ops: any of "min", "max" (codec dtype), "sum", "count" (int64) and "mean" (float64: sum / count, NaN where count is 0).  A window
         with no selected row holds the identities (min all ones, max 0, sum 0, count 0).  check=True raises SprintzError naming the
         first damaged chunk."""
         torch = self.torch
-        ops = (ops,) if isinstance(ops, str) else tuple(ops)
-        unknown = set(ops) - {"min", "max", "sum", "count", "mean"}
-        if unknown or not ops:
-            raise ValueError(f"ops must be a non-empty subset of min / max / sum / count / mean, not {ops}")
+        ops = rowops.normalise_ops(ops, ("min", "max", "sum", "count", "mean"), "min / max / sum / count / mean")
         D, n = self.ndims, batch.nchunks
-        if self.chunk_len % D:
-            raise ValueError(f"aggregate_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
-        R = self.chunk_len // D
-        MB = -(-R // 8)
-        r8 = MB * 8
-        if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
-            raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
-        mask = mask.contiguous()
-        W = R if window_rows is None else int(window_rows)
-        if W < 1:
-            raise ValueError("window_rows must be positive")
-        fold = 1
-        if per_chunk:
-            kw = r8 if window_rows is None else W
-        elif W % R == 0:
-            kw, fold = r8, W // R                           # one window a chunk (any multiple of 8 >= R), folded below
-        elif R % W == 0:
-            kw = W
-        else:
-            raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: use per_chunk=True")
-        nwin = -(-R // kw) if kw > 0 else 0
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "aggregate_rows")
+        mask = rowops.check_mask(mask, n, MB, self.device)
+        kw, fold, nwin = rowops.plan_windows(R, window_rows, per_chunk)
         want = set(ops) | ({"sum", "count"} if "mean" in ops else set())
         bits = (_lib.AGG_MIN if "min" in want else 0) | (_lib.AGG_MAX if "max" in want else 0) | (_lib.AGG_SUM if "sum" in want else 0) | \
                (_lib.AGG_COUNT if "count" in want else 0)
@@ -628,43 +543,23 @@ class ChunkedCodec:
         if bits & _lib.AGG_SUM:
             res["sum"] = torch.empty((n, nwin, D), dtype=torch.int64, device=self.device)
         cnt32 = torch.empty((n, nwin), dtype=torch.int32, device=self.device) if bits & _lib.AGG_COUNT else None
-        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        rets = self._rets(n, check)
         with self._on():
             _lib.check(_lib.aggregate_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
-                                           self.chunk_len, D, mask.data_ptr(), kw, bits,
-                                           _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                           self.chunk_len, D, mask.data_ptr(), kw, bits, self._general(general_layout),
                                            res["min"].data_ptr() if "min" in res else None,
                                            res["max"].data_ptr() if "max" in res else None,
                                            res["sum"].data_ptr() if "sum" in res else None,
                                            cnt32.data_ptr() if cnt32 is not None else None,
                                            rets.data_ptr() if rets is not None else None, self._stream()))
-        if check and n:
-            bad = (rets < 0).nonzero()
-            if bad.numel():
-                c = int(bad[0, 0].item())
-                raise _lib.SprintzError(int(rets[c].item()), f"aggregate_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if check:
+            rowops.raise_damaged("aggregate_rows", rets, n, _lib.SprintzError)
         if cnt32 is not None:
             res["count"] = cnt32.to(torch.int64)
-        if per_chunk:
-            out = res
-        else:
-            rows = -(-batch.total_len // D)
-            nw = -(-rows // W)
-            if fold == 1:                                   # chunk windows are global windows: chunk c holds rows [c R, (c+1) R)
-                out = {k: (v.reshape(n * nwin) if k == "count" else v.reshape(n * nwin, D))[:nw] for k, v in res.items()}
-            else:                                           # `fold` consecutive chunks a window (int32: torch's uint16 lacks most reductions)
-                pad = nw * fold - n
-                out = {}
-                for k, v in res.items():
-                    if k == "count":
-                        out[k] = torch.cat([v.reshape(n), v.new_zeros(pad)]).reshape(nw, fold).sum(dim=1)
-                    elif k == "sum":
-                        out[k] = torch.cat([v.reshape(n, D), v.new_zeros((pad, D))]).reshape(nw, fold, D).sum(dim=1)
-                    else:
-                        ident = (1 << (8 * self.esz)) - 1 if k == "min" else 0
-                        v32 = torch.cat([v.reshape(n, D).to(torch.int32), torch.full((pad, D), ident, dtype=torch.int32, device=self.device)])
-                        v32 = v32.reshape(nw, fold, D)
-                        out[k] = (v32.amin(dim=1) if k == "min" else v32.amax(dim=1)).to(self.dtype)
+        out = res
+        if not per_chunk:
+            W = R if window_rows is None else int(window_rows)
+            out = rowops.fold_windows(res, n, nwin, D, W, fold, batch.total_len, self.esz, self.dtype)
         if "mean" in ops:                                   # 0 / 0 is NaN: a window with no selected row has no mean
             out["mean"] = out["sum"].to(torch.float64) / out["count"].to(torch.float64).unsqueeze(-1)
         return {k: v for k, v in out.items() if k in ops}
@@ -672,31 +567,8 @@ class ChunkedCodec:
     def aggregate_where(self, batch, lo, hi, mode="all", window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False):
         """SELECT count(*), min(x), max(x), sum(x) WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and aggregate_rows
         on its mask -- two decode-speed launches; the batch is never materialised.  -> aggregate_rows' global windows."""
-        if self.chunk_len % self.ndims:
-            raise ValueError(f"aggregate_where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
-        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=general_layout, check=True)
-        return self.aggregate_rows(batch, f["mask"], window_rows=window_rows, ops=ops, general_layout=general_layout)
-
-    def _elem_tensor(self, v, name):
-        """a scalar, a sequence of ndims entries, or a tensor of ndims integers -> a contiguous device tensor [ndims] of the codec's
-        dtype (tensors are taken modulo 2^W)"""
-        torch = self.torch
-        D, W = self.ndims, 8 * self.esz
-        if torch.is_tensor(v):
-            if v.numel() != D:
-                raise ValueError(f"{name} must hold {D} entries")
-            if v.dtype == self.dtype:
-                return v.to(self.device).reshape(-1).contiguous()
-            half = 1 << (W - 1)                             # through the signed type of the same width: torch's uint16 lacks arithmetic
-            s = ((v.to(self.device).reshape(-1).to(torch.int64) + half) % (1 << W)) - half
-            return s.to(torch.int8 if self.esz == 1 else torch.int16).view(self.dtype).contiguous()
-        vals = [v] * D if np.isscalar(v) else list(v)
-        if len(vals) != D:
-            raise ValueError(f"{name} must be a scalar or have {D} entries, not {len(vals)}")
-        if any(not 0 <= int(e) < (1 << W) for e in vals):
-            raise ValueError(f"{name} entries must be in 0..{(1 << W) - 1}")
-        a = np.array([int(e) for e in vals], np.uint8 if self.esz == 1 else np.uint16)
-        return torch.from_numpy(a.view(np.int8 if self.esz == 1 else np.int16)).to(self.device).view(self.dtype)
+        return self._where("aggregate_where", self.aggregate_rows, batch, lo, hi, mode, window_rows=window_rows, ops=ops,
+                           general_layout=general_layout)
 
     def histogram_rows(self, batch, mask=None, nbins=256, lo=None, shift=None, chunks_per_hist=0, general_layout=False, check=True):
         """Per-column value counts of the rows a mask names, fused into the decode (one launch; only the counts leave the chip).
@@ -710,37 +582,26 @@ class ChunkedCodec:
         -> int64 [ngroups, ndims, nbins].  check=True raises SprintzError naming the first damaged chunk."""
         torch = self.torch
         D, n, W = self.ndims, batch.nchunks, 8 * self.esz
-        if self.chunk_len % D:
-            raise ValueError(f"histogram_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "histogram_rows")
         nbins, H = int(nbins), int(chunks_per_hist)
         if nbins < 1 or H < 0:
             raise ValueError("nbins must be positive and chunks_per_hist must not be negative")
-        if shift is None:
-            shift = min(max(W - max(nbins - 1, 0).bit_length(), 0), W - 1)
-        shift = int(shift)
-        R = self.chunk_len // D
-        MB = -(-R // 8)
+        shift = rowops.default_shift(W, nbins) if shift is None else int(shift)
         if mask is not None:
-            if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
-                raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
-            mask = mask.contiguous()
-        lo_t = None if lo is None else self._elem_tensor(lo, "lo")
+            mask = rowops.check_mask(mask, n, MB, self.device)
+        lo_t = None if lo is None else rowops.elem_tensor(lo, D, self.esz, self.dtype, self.device, "lo")
         ngroups = -(-n // H) if H else 1
         hist = torch.empty((ngroups if n else 0, D, nbins), dtype=torch.int64, device=self.device)
         if n == 0:
             return hist
-        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        rets = self._rets(n, check)
         with self._on():
             _lib.check(_lib.histogram_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
                                            self.chunk_len, D, mask.data_ptr() if mask is not None else None,
-                                           lo_t.data_ptr() if lo_t is not None else None, shift, nbins, H,
-                                           _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                           lo_t.data_ptr() if lo_t is not None else None, shift, nbins, H, self._general(general_layout),
                                            hist.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
-        if check and n:
-            bad = (rets < 0).nonzero()
-            if bad.numel():
-                c = int(bad[0, 0].item())
-                raise _lib.SprintzError(int(rets[c].item()), f"histogram_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if check:
+            rowops.raise_damaged("histogram_rows", rets, n, _lib.SprintzError)
         return hist
 
     def histogram_where(self, batch, lo, hi, mode="all", **kw):
@@ -749,8 +610,7 @@ class ChunkedCodec:
         shift, chunks_per_hist, general_layout)."""
         if "hist_lo" in kw:
             kw["lo"] = kw.pop("hist_lo")
-        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
-        return self.histogram_rows(batch, mask=f["mask"], **kw)
+        return self._where("histogram_where", self.histogram_rows, batch, lo, hi, mode, **kw)
 
     def _hist_span(self, batch, mask, shift, total_bins, lo64=None):
         """one histogram of the batch, total_bins bins of 2^shift values from lo64 [ndims] (int64 device tensor; None: 0) on, as int64
@@ -831,21 +691,10 @@ class ChunkedCodec:
         ref.  ddof (0 or 1) divides var / std / cov by n - ddof.  A window with no selected row holds zeros; derived values are NaN
         where n == 0 or n <= ddof, and corr also where either variance is 0.
 
-        Derived values are NOT formed as n Q - S^2 in float64: that difference reaches 2^94 and cancels.  With the integer pivot
-        m = S // n and r = S - n m (0 <= r < n),
-            C = Q - 2 m S + n m^2 = sum (x - m)^2
-        in wrapping int64 arithmetic on the device: intermediates may wrap, but two's-complement arithmetic is exact modulo 2^64 and
-        0 <= C <= Q < 2^63, so C is exact.  Then n var = C - r^2 / n, i.e.
-            var = C / (n - ddof) - (r / n) (r / (n - ddof))
-        in float64: the second term is at most 1 and the first is never smaller than the result, so nothing cancels badly.  Likewise
-        with two pivots, Cxy = P - m_x S_y - m_y S_x + n m_x m_y = sum (x - m_x)(y - m_y) (|Cxy| < 2^62: exact as a signed int64) and
-            cov = Cxy / (n - ddof) - (r_x / n) (r_y / (n - ddof)),     corr = cov_0 / sqrt(var_0(x) var_0(y))   (ddof = 0 throughout).
-        A variance is 0 exactly where C == 0.  check=True raises SprintzError naming the first damaged chunk."""
+        Derived values rest on an integer pivot, not on n Q - S^2 in float64, which cancels: rowops.derive_moments.
+        check=True raises SprintzError naming the first damaged chunk."""
         torch = self.torch
-        ops = (ops,) if isinstance(ops, str) else tuple(ops)
-        unknown = set(ops) - set(self._MOM_INT) - set(self._MOM_DERIVED)
-        if unknown or not ops:
-            raise ValueError(f"ops must be a non-empty subset of count / sum / sumsq / cross / mean / var / std / cov / corr, not {ops}")
+        ops = rowops.normalise_ops(ops, self._MOM_INT + self._MOM_DERIVED, "count / sum / sumsq / cross / mean / var / std / cov / corr")
         if ddof not in (0, 1):
             raise ValueError("ddof must be 0 or 1")
         D, n = self.ndims, batch.nchunks
@@ -854,28 +703,10 @@ class ChunkedCodec:
                 raise ValueError('"cross", "cov" and "corr" need ref, the reference column')
             if not 0 <= int(ref) < D:
                 raise ValueError(f"ref must be a column of the batch, 0 .. {D - 1}")
-        if self.chunk_len % D:
-            raise ValueError(f"moments_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
-        R = self.chunk_len // D
-        MB = -(-R // 8)
-        r8 = MB * 8
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "moments_rows")
         if mask is not None:
-            if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
-                raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
-            mask = mask.contiguous()
-        W = R if window_rows is None else int(window_rows)
-        if W < 1:
-            raise ValueError("window_rows must be positive")
-        fold = 1
-        if per_chunk:
-            kw = r8 if window_rows is None else W
-        elif W % R == 0:
-            kw, fold = r8, W // R                           # one window a chunk (any multiple of 8 >= R), folded below
-        elif R % W == 0:
-            kw = W
-        else:
-            raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: use per_chunk=True")
-        nwin = -(-R // kw) if kw > 0 else 0
+            mask = rowops.check_mask(mask, n, MB, self.device)
+        kw, fold, nwin = rowops.plan_windows(R, window_rows, per_chunk)
         want = set(ops) & set(self._MOM_INT)
         if "mean" in ops:
             want |= {"count", "sum"}
@@ -889,87 +720,32 @@ class ChunkedCodec:
                (_lib.MOM_CROSS if "cross" in want else 0)
         res = {k: torch.empty((n, nwin, D), dtype=torch.int64, device=self.device) for k in ("sum", "sumsq", "cross") if k in want}
         cnt32 = torch.empty((n, nwin), dtype=torch.int32, device=self.device) if "count" in want else None
-        rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+        rets = self._rets(n, check)
         with self._on():
             _lib.check(_lib.moments_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
                                          self.chunk_len, D, mask.data_ptr() if mask is not None else None, kw, bits,
-                                         int(ref) if "cross" in want else 0, _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                         int(ref) if "cross" in want else 0, self._general(general_layout),
                                          cnt32.data_ptr() if cnt32 is not None else None,
                                          res["sum"].data_ptr() if "sum" in res else None,
                                          res["sumsq"].data_ptr() if "sumsq" in res else None,
                                          res["cross"].data_ptr() if "cross" in res else None,
                                          rets.data_ptr() if rets is not None else None, self._stream()))
-        if check and n:
-            bad = (rets < 0).nonzero()
-            if bad.numel():
-                c = int(bad[0, 0].item())
-                raise _lib.SprintzError(int(rets[c].item()), f"moments_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+        if check:
+            rowops.raise_damaged("moments_rows", rets, n, _lib.SprintzError)
         if cnt32 is not None:
             res["count"] = cnt32.to(torch.int64)
-        if per_chunk:
-            out = res
-        else:
-            rows = -(-batch.total_len // D)
-            nw = -(-rows // W)
-            if fold == 1:                                   # chunk windows are global windows: chunk c holds rows [c R, (c+1) R)
-                out = {k: (v.reshape(n * nwin) if k == "count" else v.reshape(n * nwin, D))[:nw] for k, v in res.items()}
-            else:                                           # `fold` consecutive chunks a window: integer sums add
-                pad = nw * fold - n
-                out = {}
-                for k, v in res.items():
-                    if k == "count":
-                        out[k] = torch.cat([v.reshape(n), v.new_zeros(pad)]).reshape(nw, fold).sum(dim=1)
-                    else:
-                        out[k] = torch.cat([v.reshape(n, D), v.new_zeros((pad, D))]).reshape(nw, fold, D).sum(dim=1)
+        out = res
+        if not per_chunk:
+            W = R if window_rows is None else int(window_rows)
+            out = rowops.fold_windows(res, n, nwin, D, W, fold, batch.total_len, self.esz, self.dtype)
         if set(ops) & set(self._MOM_DERIVED):
-            f64 = torch.float64
-            cnt = out["count"].unsqueeze(-1)                # [..., 1]
-            n1 = cnt.clamp(min=1)
-            nf = cnt.to(f64)
-            nd = (cnt - ddof).to(f64)
-            S = out["sum"]
-            m = S // n1                                     # the integer pivot, and what it leaves: 0 <= r < n
-            r = S - cnt * m
-            nan = torch.full((), float("nan"), dtype=f64, device=self.device)
-
-            def centred2():                                 # C = sum (x - m)^2, exact (see above)
-                return out["sumsq"] - 2 * m * S + cnt * m * m
-
-            def centred_xy():                               # Cxy = sum (x - m_x)(x_ref - m_ref), exact
-                j = int(ref)
-                return out["cross"] - m * S[..., j:j + 1] - m[..., j:j + 1] * S + cnt * m * m[..., j:j + 1]
-
-            if "mean" in ops:
-                out["mean"] = torch.where(cnt > 0, S.to(f64) / nf, nan)
-            if set(ops) & {"var", "std"}:
-                var = centred2().to(f64) / nd - (r.to(f64) / nf) * (r.to(f64) / nd)
-                var = torch.where(cnt > ddof, var, nan)
-                if "var" in ops:
-                    out["var"] = var
-                if "std" in ops:
-                    out["std"] = var.clamp(min=0.0).sqrt()   # (a variance below its own rounding error may come out as -1e-16)
-            if "cov" in ops:
-                j = int(ref)
-                rf = r.to(f64)
-                cov = centred_xy().to(f64) / nd - (rf / nf) * (rf[..., j:j + 1] / nd)
-                out["cov"] = torch.where(cnt > ddof, cov, nan)
-            if "corr" in ops:
-                j = int(ref)
-                rf = r.to(f64)
-                C = centred2()
-                v0 = C.to(f64) / nf - (rf / nf) * (rf / nf)
-                c0 = centred_xy().to(f64) / nf - (rf / nf) * (rf[..., j:j + 1] / nf)
-                ok = (cnt > 0) & (C != 0) & (C[..., j:j + 1] != 0)
-                out["corr"] = torch.where(ok, c0 / (v0 * v0[..., j:j + 1]).sqrt(), nan)
+            out.update(rowops.derive_moments(out, ops, ref, ddof))
         return {k: v for k, v in out.items() if k in ops}
 
     def moments_where(self, batch, lo, hi, mode="all", **kw):
         """SELECT count(*), sum(x), var(x), corr(x, y), ... WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and
         moments_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: moments_rows' other arguments."""
-        if self.chunk_len % self.ndims:
-            raise ValueError(f"moments_where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
-        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
-        return self.moments_rows(batch, mask=f["mask"], **kw)
+        return self._where("moments_where", self.moments_rows, batch, lo, hi, mode, **kw)
 
     def groupby_rows(self, batch, key, nbins=256, key_lo=0, shift=None, mask=None, ops=("count", "sum"), chunks_per_table=0, general_layout=False,
                      check=True):
@@ -986,11 +762,8 @@ class ChunkedCodec:
         selected, "mean": float64 sum / count, NaN where count is 0.  check=True raises SprintzError naming the first damaged chunk."""
         torch = self.torch
         D, n, W = self.ndims, batch.nchunks, 8 * self.esz
-        ops = (ops,) if isinstance(ops, str) else tuple(ops)
-        if not ops or set(ops) - {"count", "sum"}:
-            raise ValueError(f'ops must be a non-empty subset of "count" / "sum", not {ops}')
-        if self.chunk_len % D:
-            raise ValueError(f"groupby_rows needs chunk_len % ndims == 0 ({self.chunk_len} % {D}): rows must not straddle chunks")
+        ops = rowops.normalise_ops(ops, ("count", "sum"), '"count" / "sum"')
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "groupby_rows")
         key, nbins, key_lo, H = int(key), int(nbins), int(key_lo), int(chunks_per_table)
         if not 0 <= key < D:
             raise ValueError(f"key must be a column of the batch, 0 .. {D - 1}")
@@ -998,15 +771,9 @@ class ChunkedCodec:
             raise ValueError("nbins must be positive and chunks_per_table must not be negative")
         if not 0 <= key_lo < (1 << W):
             raise ValueError(f"key_lo must be in 0..{(1 << W) - 1}")
-        if shift is None:
-            shift = min(max(W - max(nbins - 1, 0).bit_length(), 0), W - 1)
-        shift = int(shift)
-        R = self.chunk_len // D
-        MB = -(-R // 8)
+        shift = rowops.default_shift(W, nbins) if shift is None else int(shift)
         if mask is not None:
-            if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != n * MB:
-                raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {self.device}")
-            mask = mask.contiguous()
+            mask = rowops.check_mask(mask, n, MB, self.device)
         ntables = (-(-n // H) if H else 1) if n else 0
         out = {}
         if "count" in ops:
@@ -1014,20 +781,17 @@ class ChunkedCodec:
         if "sum" in ops:
             out["sum"] = torch.empty((ntables, nbins, D), dtype=torch.int64, device=self.device)
         if n:
-            rets = torch.empty(n, dtype=torch.int64, device=self.device) if check else None
+            rets = self._rets(n, check)
             with self._on():
                 _lib.check(_lib.groupby_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
                                              self.chunk_len, D, mask.data_ptr() if mask is not None else None, key, key_lo, shift, nbins, H,
                                              (_lib.GBY_COUNT if "count" in ops else 0) | (_lib.GBY_SUM if "sum" in ops else 0),
-                                             _lib.QUERY_GENERAL_LAYOUT if general_layout else 0,
+                                             self._general(general_layout),
                                              out["count"].data_ptr() if "count" in out else None,
                                              out["sum"].data_ptr() if "sum" in out else None,
                                              rets.data_ptr() if rets is not None else None, self._stream()))
             if check:
-                bad = (rets < 0).nonzero()
-                if bad.numel():
-                    c = int(bad[0, 0].item())
-                    raise _lib.SprintzError(int(rets[c].item()), f"groupby_rows: chunk {c} is damaged (decoder returned {int(rets[c].item())})")
+                rowops.raise_damaged("groupby_rows", rets, n, _lib.SprintzError)
         if "count" in out and "sum" in out:
             cnt = out["count"].unsqueeze(-1)
             nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
@@ -1037,10 +801,7 @@ class ChunkedCodec:
     def groupby_where(self, batch, lo, hi, mode="all", **kw):
         """SELECT bin(x_key), count(*), sum(x) WHERE <bounds> GROUP BY bin(x_key): filter_rows (its lo / hi / mode) and groupby_rows on its
         mask -- two decode-speed launches; the batch is never materialised.  kw: groupby_rows' other arguments (key among them)."""
-        if self.chunk_len % self.ndims:
-            raise ValueError(f"groupby_where needs chunk_len % ndims == 0 ({self.chunk_len} % {self.ndims}): rows must not straddle chunks")
-        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
-        return self.groupby_rows(batch, mask=f["mask"], **kw)
+        return self._where("groupby_where", self.groupby_rows, batch, lo, hi, mode, **kw)
 
     def corr(self, batch, cols=None, mask=None, window_rows=None):
         """The correlation matrix of the columns `cols` (default: all) per window, straight from the compressed data: [nwindows,

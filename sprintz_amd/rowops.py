@@ -1,0 +1,191 @@
+"""The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows,
+moments_rows, groupby_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+fold of its results into windows over the batch's rows, the first damaged chunk, the default bin shift, bounds and offsets as tensors, and
+the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
+them (tests/test_rowops_cpu.py)."""
+import numpy as np
+import torch
+
+
+def normalise_ops(ops, allowed, what):
+    """one name or several -> a tuple of names out of `allowed` (`what`: how the refusal lists them)"""
+    ops = (ops,) if isinstance(ops, str) else tuple(ops)
+    if not ops or set(ops) - set(allowed):
+        raise ValueError(f"ops must be a non-empty subset of {what}, not {ops}")
+    return ops
+
+
+def chunk_rows(chunk_len, ndims, op=None, verb="needs"):
+    """-> (R rows a chunk slot, MB mask bytes a chunk slot).  op: the operation that needs whole rows (None: a partial last row counts
+    as a row of the slot)"""
+    if op is not None and chunk_len % ndims:
+        raise ValueError(f"{op} {verb} chunk_len % ndims == 0 ({chunk_len} % {ndims}): rows must not straddle chunks")
+    R = -(-chunk_len // ndims)
+    return R, -(-R // 8)
+
+
+def check_mask(mask, n, MB, device):
+    """a row mask in filter_rows' layout, n x MB bytes -> the same, contiguous"""
+    if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.device != device or mask.numel() != n * MB:
+        raise ValueError(f"mask must be a uint8 tensor of {n} x {MB} bytes on {device}")
+    return mask.contiguous()
+
+
+def plan_windows(R, window_rows, per_chunk):
+    """The window the kernel is asked for -> (kw, fold, nwin): kw rows a kernel window, nwin = ceil(R / kw) of them a chunk, and `fold`
+    consecutive chunks to a window of window_rows batch rows (fold_windows).  window_rows=None: one window a chunk.
+    per_chunk=True: window_rows as it is.  Otherwise R must be a multiple of window_rows (the chunk's windows are the batch's) or a divisor
+    of it (one window a chunk -- any multiple of 8 that holds R rows -- and window_rows / R chunks fold)."""
+    r8 = -(-R // 8) * 8
+    W = R if window_rows is None else int(window_rows)
+    if W < 1:
+        raise ValueError("window_rows must be positive")
+    if per_chunk:
+        kw, fold = r8 if window_rows is None else W, 1
+    elif W % R == 0:
+        kw, fold = r8, W // R
+    elif R % W == 0:
+        kw, fold = W, 1
+    else:
+        raise ValueError(f"global windows need chunk rows {R} to be a multiple or a divisor of window_rows {W}: use per_chunk=True")
+    return kw, fold, -(-R // kw)
+
+
+def fold_windows(res, n, nwin, D, W, fold, total_len, esz, dtype):
+    """The kernel's per-chunk windows {op: [n, nwin, D]}, "count": [n, nwin] -> windows of W rows over the batch's rows {op: [nw, D]},
+    "count": [nw], nw = ceil(ceil(total_len / D) / W).  fold == 1: chunk c holds batch rows [c R, (c + 1) R), so its windows are the
+    batch's.  fold > 1: one window a chunk, `fold` consecutive chunks a window; the chunks the last window lacks hold the identities (min
+    all ones, max 0, sums 0).  min / max reduce as int32: torch's uint16 lacks most reductions."""
+    nw = -(-(-(-total_len // D)) // W)
+    out = {}
+    for k, v in res.items():
+        tail = tuple(v.shape[2:])                           # (D,), or () for "count"
+        if fold == 1:
+            out[k] = v.reshape((n * nwin,) + tail)[:nw]
+            continue
+        v = v.reshape((n,) + tail)
+        if k in ("min", "max"):
+            v = v.to(torch.int32)
+        ident = (1 << (8 * esz)) - 1 if k == "min" else 0
+        v = torch.cat([v, v.new_full((nw * fold - n,) + tail, ident)]).reshape((nw, fold) + tail)
+        out[k] = v.amin(dim=1).to(dtype) if k == "min" else v.amax(dim=1).to(dtype) if k == "max" else v.sum(dim=1)
+    return out
+
+
+def first_bad(rets, n):
+    """the first of rets[:n] that is negative, or None"""
+    bad = (rets[:n] < 0).nonzero()
+    return int(bad[0, 0].item()) if bad.numel() else None
+
+
+def raise_damaged(op, rets, n, error):
+    """raise error(code, message) naming the first chunk whose decoder returned a negative code, if there is one"""
+    c = first_bad(rets, n)
+    if c is not None:
+        code = int(rets[c].item())
+        raise error(code, f"{op}: chunk {c} is damaged (decoder returned {code})")
+
+
+def default_shift(W, nbins):
+    """the shift that makes nbins bins cover the range of W-bit elements, W - ceil(log2(nbins)) (one bin: the largest there is, W - 1)"""
+    return min(max(W - max(nbins - 1, 0).bit_length(), 0), W - 1)
+
+
+def _entries(v, ndims, name):
+    """a scalar (None is one) or a sequence -> a list of ndims entries"""
+    vals = [v] * ndims if v is None or np.isscalar(v) else list(v)
+    if len(vals) != ndims:
+        raise ValueError(f"{name} must be a scalar or have {ndims} entries, not {len(vals)}")
+    return vals
+
+
+def elem_tensor(v, ndims, esz, dtype, device, name, open_end=None):
+    """a scalar, a sequence of ndims entries or a tensor of ndims integers -> a contiguous tensor [ndims] of `dtype` on `device`.
+    open_end: what a None entry stands for -- v is a bound then, which is compared as it is: entries may be None, and a tensor must be of
+    `dtype`.  Without it v is an offset: a tensor of another dtype is taken modulo 2^W."""
+    W = 8 * esz
+    bound = open_end is not None
+    if torch.is_tensor(v):
+        if v.numel() != ndims or (bound and v.dtype != dtype):
+            raise ValueError(f"{name} must hold {ndims} entries" + (f" of {dtype}" if bound else ""))
+        v = v.to(device).reshape(-1)
+        if v.dtype == dtype:
+            return v.contiguous()
+        half = 1 << (W - 1)                                 # through the signed type of the same width: torch's uint16 lacks arithmetic
+        s = ((v.to(torch.int64) + half) % (1 << W)) - half
+        return s.to(torch.int8 if esz == 1 else torch.int16).view(dtype).contiguous()
+    vals = [open_end if bound and e is None else e for e in _entries(v, ndims, name)]
+    if any(not 0 <= int(e) < (1 << W) for e in vals):
+        raise ValueError(f"{name} entries must be in 0..{(1 << W) - 1}")
+    a = np.array([int(e) for e in vals], np.uint8 if esz == 1 else np.uint16)
+    return torch.from_numpy(a.view(np.int8 if esz == 1 else np.int16)).to(device).view(dtype)
+
+
+def filter_bounds(lo, hi, mode, ndims, esz, dtype, device):
+    """filter_rows' lo / hi -- a scalar, a sequence of ndims entries (None: an open end) or a tensor of `dtype` -- as two contiguous tensors
+    [ndims].  A column with neither bound is unconstrained: it always matches under "all" and never -- an empty interval -- under "any"."""
+    top = (1 << (8 * esz)) - 1
+    if mode == "any" and not torch.is_tensor(lo) and not torch.is_tensor(hi):
+        lo, hi = _entries(lo, ndims, "lo"), _entries(hi, ndims, "hi")
+        for d in range(ndims):
+            if lo[d] is None and hi[d] is None:
+                lo[d], hi[d] = top, 0
+    return elem_tensor(lo, ndims, esz, dtype, device, "lo", 0), elem_tensor(hi, ndims, esz, dtype, device, "hi", top)
+
+
+def derive_moments(out, ops, ref, ddof):
+    """The derived moments among `ops` -- "mean", "var", "std", "cov", "corr" -- of the integer sums out["count"] [...], out["sum"],
+    out["sumsq"], out["cross"] [..., D] (int64; only what the ops need), as float64 [..., D].  NaN where n == 0 or n <= ddof, and corr
+    also where either variance is 0.
+
+    They are NOT formed as n Q - S^2 in float64: that difference reaches 2^94 and cancels.  With the integer pivot m = S // n and
+    r = S - n m (0 <= r < n),
+        C = Q - 2 m S + n m^2 = sum (x - m)^2
+    in wrapping int64 arithmetic: intermediates may wrap, but two's-complement arithmetic is exact modulo 2^64 and 0 <= C <= Q < 2^63,
+    so C is exact.  Then n var = C - r^2 / n, i.e.
+        var = C / (n - ddof) - (r / n) (r / (n - ddof))
+    in float64: the second term is at most 1 and the first is never smaller than the result, so nothing cancels badly.  Likewise with
+    two pivots, Cxy = P - m_x S_y - m_y S_x + n m_x m_y = sum (x - m_x)(y - m_y) (|Cxy| < 2^62: exact as a signed int64) and
+        cov = Cxy / (n - ddof) - (r_x / n) (r_y / (n - ddof)),     corr = cov_0 / sqrt(var_0(x) var_0(y))   (ddof = 0 throughout).
+    A variance is 0 exactly where C == 0."""
+    f64 = torch.float64
+    cnt = out["count"].unsqueeze(-1)                        # [..., 1]
+    n1 = cnt.clamp(min=1)
+    nf = cnt.to(f64)
+    nd = (cnt - ddof).to(f64)
+    S = out["sum"]
+    m = S // n1                                             # the integer pivot, and what it leaves: 0 <= r < n
+    r = S - cnt * m
+    nan = torch.full((), float("nan"), dtype=f64, device=cnt.device)
+    der = {}
+
+    def centred2():                                         # C = sum (x - m)^2, exact (see above)
+        return out["sumsq"] - 2 * m * S + cnt * m * m
+
+    def centred_xy():                                       # Cxy = sum (x - m_x)(x_ref - m_ref), exact
+        j = int(ref)
+        return out["cross"] - m * S[..., j:j + 1] - m[..., j:j + 1] * S + cnt * m * m[..., j:j + 1]
+
+    if "mean" in ops:
+        der["mean"] = torch.where(cnt > 0, S.to(f64) / nf, nan)
+    if set(ops) & {"var", "std"}:
+        var = centred2().to(f64) / nd - (r.to(f64) / nf) * (r.to(f64) / nd)
+        var = torch.where(cnt > ddof, var, nan)
+        if "var" in ops:
+            der["var"] = var
+        if "std" in ops:
+            der["std"] = var.clamp(min=0.0).sqrt()          # (a variance below its own rounding error may come out as -1e-16)
+    if "cov" in ops:
+        j = int(ref)
+        rf = r.to(f64)
+        cov = centred_xy().to(f64) / nd - (rf / nf) * (rf[..., j:j + 1] / nd)
+        der["cov"] = torch.where(cnt > ddof, cov, nan)
+    if "corr" in ops:
+        j = int(ref)
+        rf = r.to(f64)
+        C = centred2()
+        v0 = C.to(f64) / nf - (rf / nf) * (rf / nf)
+        c0 = centred_xy().to(f64) / nf - (rf / nf) * (rf[..., j:j + 1] / nf)
+        ok = (cnt > 0) & (C != 0) & (C[..., j:j + 1] != 0)
+        der["corr"] = torch.where(ok, c0 / (v0 * v0[..., j:j + 1]).sqrt(), nan)
+    return der

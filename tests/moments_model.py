@@ -14,6 +14,8 @@ import numpy as np
 import aggregate_model as am
 import filter_model as fm
 
+U = 2.0 ** -53                  # float64's unit roundoff
+
 
 def all_rows(n, chunk_len, D):
     """the mask of mask=None: every bit set (aggregate_model.selected drops the rows that do not exist)"""
@@ -118,3 +120,9 @@ def corr_float(e):
     f = e["corr2"]
     root = Fraction(math.isqrt((f.numerator << 400) // f.denominator), 1 << 200)
     return e["sign"] * float(root)
+
+
+def corr_bound(vx, vy):
+    """the bound on |corr - exact| for exact variances vx, vy that test_moments_derived_values derives in its docstring"""
+    v = min(vx, vy)
+    return 32 * U if v >= 1 else (12 * (1 + 1 / float(v)) + 3) * U

@@ -12,7 +12,7 @@ import pytest
 
 import filter_model as fm
 import histogram_model as hm
-from dispatch import ran
+from dispatch import DECODERS, ran
 from harness import DTYPES
 from test_gpu_filter import bound_sets
 from test_gpu_query_windows import gen_data, lowdim, make_batch
@@ -388,6 +388,8 @@ def test_histogram_rows_and_where_python(sz, oracle):
     rb = ragged.compress(torch.randint(0, 255, (1024 * 4,), dtype=torch.uint8, device="cuda:0"))
     with pytest.raises(ValueError):
         ragged.histogram_rows(rb, nbins=16)
+    with ran(never=DECODERS), pytest.raises(ValueError):    # refused before the filter launches
+        ragged.histogram_where(rb, 0, 100, nbins=16)
 
 
 Q = [0, 0.01, 0.5, 0.99, 1]

@@ -17,6 +17,7 @@ import filter_model as fm
 import moments_model as mm
 from dispatch import ran
 from harness import DTYPES
+from moments_model import U, corr_bound
 from test_gpu_aggregate import FAST_SHAPES, NDIMS, PARITY_FAST, SHAPES, DATA, rows_for, sentinel, windows_for
 from test_gpu_filter import bound_sets
 from test_gpu_query_windows import gen_data, lowdim, make_batch
@@ -26,7 +27,6 @@ pytestmark = pytest.mark.gpu
 
 PAD = 1024                      # entries behind every output that must keep the sentinel
 OPS = {"count": 1, "sum": 2, "sumsq": 4, "cross": 8}
-U = 2.0 ** -53                  # float64's unit roundoff
 
 
 @pytest.fixture(scope="module")
@@ -463,12 +463,6 @@ def derived_batch(rng, rows, D):
     x[:, 2] = 4660
     x[:, 3] = 65535 - x[:, 4]
     return x.astype(np.uint16).ravel()
-
-
-def corr_bound(vx, vy):
-    """test_moments_derived_values' bound on |corr - exact| for exact variances vx, vy"""
-    v = min(vx, vy)
-    return 32 * U if v >= 1 else (12 * (1 + 1 / float(v)) + 3) * U
 
 
 def test_moments_derived_values(sz, oracle):

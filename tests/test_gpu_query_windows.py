@@ -233,6 +233,8 @@ def test_query_windows_damaged_chunk(sz, oracle, no_fast, codec, esz, D, chunk_l
     ("delta", 1, 1, 1024, 3072, 1024 * 20 + 17),         # univariate, W = 3 R
     ("delta", 1, 80, 10240, 32, 10240 * 6 + 80 * 9),     # cfg3's shape
     ("delta", 2, 3, 300, 500, 300 * 12 + 2),             # R = 100 is no multiple of 8: one kernel window of 104 rows a chunk
+    ("delta", 2, 3, 36, 12, 36 * 5 + 3 * 4 + 2),         # W = R = 12, no multiple of 8: one kernel window of 16 rows a chunk, nothing folds
+    ("xff", 1, 5, 60, 12, 60 * 4 + 5 * 7 + 3),           # the same with five columns
 ])
 def test_query_windows_global(sz, oracle, codec, esz, D, chunk_len, W, n):
     rng = np.random.default_rng(n)
