@@ -51,7 +51,8 @@ extern "C" {
  *   7  round 6: SPRINTZ_OPT_BLK_CHUNKS (block-parallel delta kernels); the batched entry points refuse shapes whose tail outgrows remaining_len;
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
- *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_* */
+ *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
+ *      extrema_rows, SPRINTZ_EXT_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -155,7 +156,7 @@ int sprintz_mi355x_set_option(int option, int value);
  * a call that fails before its launch (SPRINTZ_E_INVALID, SPRINTZ_E_NO_DEVICE, ...) moves none.  Calls made during stream capture
  * count at capture time: replaying the graph launches the kernels again and counts nothing.  Host only -- one relaxed add per launch,
  * nothing inside a kernel -- and never reset: read them before and after, and look at the difference.
- *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows, the column-major form):
+ *   decompress_batch and every call that decodes through it (the single calls, query_batch, query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows, extrema_rows, the column-major form):
  *     DEC_BIG (more than 2047 columns)  DEC_ANY (513 .. 2047)  DEC_VERBATIM (chunks shorter than a group: header check + copy)
  *     DEC_LAT (csrc/decode_lat.h)  DEC_ROW (decode_row.h)  DEC_BLK (decode_blk.h)  DEC_FAST (decode_fast.h)  DEC_UNI (decode_uni.h)
  *     DEC_GENERIC (decode_kernel.h)
@@ -711,6 +712,54 @@ int sprintz_mi355x_groupby_rows(int codec, int elem_bytes, const void* d_comp, c
                                 uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */,
                                 uint32_t key_col, uint32_t key_lo, uint32_t shift, uint32_t nbins, uint64_t table_chunks,
                                 uint32_t ops, uint32_t flags, uint64_t* d_count, uint64_t* d_sum, int64_t* d_rets, void* hip_stream);
+/* Extrema rows: per-window min / max of the rows a mask names WITH the rows they stand in, and the window's first and last selected
+ * sample -- "when did the peak happen?", and the M4 reduction a line chart of a long series is drawn from (per pixel column the first,
+ * last, minimum and maximum sample, each with its time stamp) -- fused into the decode: only the results leave the chip.
+ *
+ * The batch, the flags, the windows and the mask are sprintz_mi355x_aggregate_rows' (chunk_len % ndims == 0 is required; D = ndims,
+ * R = chunk_len / D, MB = ceil(R / 8), W = window_rows, a multiple of 8, at least 8, nwin = ceil(R / W): windows are relative to the
+ * chunk), except that d_mask may be NULL: every existing row, as in sprintz_mi355x_moments_rows.  A mask bit is ignored if its row
+ * does not exist, and a partial last row is not a row.
+ * For chunk c, window w and column d the call writes, at index (c*nwin + w)*D + d, over the selected existing rows of that window,
+ *   d_min   : the unsigned minimum, element type (uint8 / uint16)                         (ops & SPRINTZ_EXT_MIN)
+ *   d_max   : the unsigned maximum, element type                                          (ops & SPRINTZ_EXT_MAX)
+ *   d_argmin: the chunk-relative row (0 .. R-1, uint32) of the FIRST selected row that holds the minimum   (ops & SPRINTZ_EXT_ARGMIN)
+ *   d_argmax: the same for the maximum -- numpy's tie rule                                (ops & SPRINTZ_EXT_ARGMAX)
+ *   d_first : column d's value in the window's first selected row, element type          (ops & SPRINTZ_EXT_FIRST)
+ *   d_last  : column d's value in the window's last selected row, element type           (ops & SPRINTZ_EXT_LAST)
+ * at index (c*nwin + w)*2
+ *   d_rows  : the chunk-relative rows of that first and that last selected row, uint32   (ops & SPRINTZ_EXT_ROWS)
+ * and at index c*nwin + w
+ *   d_count : the number of selected rows, uint32                                         (ops & SPRINTZ_EXT_COUNT)
+ * on the values decompress_batch writes under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK included).  A window with no selected
+ * row holds min 0xFF / 0xFFFF, max 0, argmin = argmax = both d_rows entries = SPRINTZ_EXT_NO_ROW, first = last = 0, count 0.  Every
+ * entry of every selected output is written, one writer an entry, no atomics: the output is deterministic.  An output not selected
+ * may be NULL and is not touched; SPRINTZ_EXT_ARGMIN without SPRINTZ_EXT_MIN (and the like) is legal.  Value and row are kept apart
+ * in the kernels: window_rows has no upper limit.
+ * d_rets (optional) as in aggregate_rows: elements decoded, or < 0 for a damaged chunk, whose own entries are then unspecified --
+ * nothing is written outside them, and every other chunk is exact.
+ * The call does not read the mask on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST
+ * (csrc/decode_fast.h: the shapes aggregate_rows takes there) or DEC_GENERIC (csrc/decode_kernel.h: everything else, the
+ * low-dimension layouts included -- csrc/decode_uni.h is not taught the mode).
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, a window_rows that
+ * is not a multiple of 8 >= 8, ops outside 1..255, a selected output that is NULL, a NULL d_comp / d_offsets, a selected d_min / d_max /
+ * d_first / d_last not aligned to the element size, a selected d_argmin / d_argmax / d_rows / d_count not aligned to 4 bytes, d_rets
+ * not aligned to 8 bytes, an unknown flag; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0
+ * returns 0 and launches nothing. */
+#define SPRINTZ_EXT_MIN 1u
+#define SPRINTZ_EXT_MAX 2u
+#define SPRINTZ_EXT_ARGMIN 4u
+#define SPRINTZ_EXT_ARGMAX 8u
+#define SPRINTZ_EXT_FIRST 16u
+#define SPRINTZ_EXT_LAST 32u
+#define SPRINTZ_EXT_ROWS 64u
+#define SPRINTZ_EXT_COUNT 128u
+#define SPRINTZ_EXT_NO_ROW 0xFFFFFFFFu
+int sprintz_mi355x_extrema_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask /* may be NULL */, uint32_t window_rows, uint32_t ops,
+                                uint32_t flags, void* d_min, void* d_max, uint32_t* d_argmin, uint32_t* d_argmax,
+                                void* d_first, void* d_last, uint32_t* d_rows, uint32_t* d_count, int64_t* d_rets,
+                                void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -146,6 +146,10 @@ moments_rows = _sig("sprintz_mi355x_moments_rows", _i, _i, _i, _vp, _vp, _u64, _
 GBY_COUNT, GBY_SUM = 1, 2
 GBY_MAX_COUNTERS = 16384
 groupby_rows = _sig("sprintz_mi355x_groupby_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _u32, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp)
+# per-window min / max with their rows, first / last selected sample, their rows and the count of the rows a mask names (include/sprintz_mi355x.h)
+EXT_MIN, EXT_MAX, EXT_ARGMIN, EXT_ARGMAX, EXT_FIRST, EXT_LAST, EXT_ROWS, EXT_COUNT = 1, 2, 4, 8, 16, 32, 64, 128
+EXT_NO_ROW = 0xFFFFFFFF
+extrema_rows = _sig("sprintz_mi355x_extrema_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 query = {
     ("delta", 1): _sig("sprintz_mi355x_query_delta_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
     ("xff", 1): _sig("sprintz_mi355x_query_xff_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
@@ -216,7 +220,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_huf0_exact_tmp_bytes", "sprintz_mi355x_huf0_compress_batch_exact",
     "sprintz_mi355x_query_batch", "sprintz_mi355x_query_reduce", "sprintz_mi355x_query_windows",
     "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids", "sprintz_mi355x_select_rows",
-    "sprintz_mi355x_aggregate_rows", "sprintz_mi355x_histogram_rows", "sprintz_mi355x_moments_rows", "sprintz_mi355x_groupby_rows",
+    "sprintz_mi355x_aggregate_rows", "sprintz_mi355x_histogram_rows", "sprintz_mi355x_moments_rows", "sprintz_mi355x_groupby_rows", "sprintz_mi355x_extrema_rows",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",
     "sprintz_mi355x_compress_batch_colmajor", "sprintz_mi355x_compress_batch_colmajor_dense", "sprintz_mi355x_decompress_batch_colmajor",

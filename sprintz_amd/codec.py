@@ -747,6 +747,85 @@ class ChunkedCodec:
         moments_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: moments_rows' other arguments."""
         return self._where("moments_where", self.moments_rows, batch, lo, hi, mode, **kw)
 
+    _EXT_OPS = ("min", "max", "argmin", "argmax", "first", "last", "rows", "count")
+
+    def extrema_rows(self, batch, mask=None, window_rows=None, ops=("min", "argmin", "max", "argmax"), general_layout=False, per_chunk=False,
+                     check=True):
+        """Per-window min / max of the rows a mask names WITH the rows they stand in, and the window's first and last selected sample, fused
+        into the decode (one launch; only the results leave the chip): "when did the peak happen?".
+
+        mask, window_rows, general_layout, per_chunk, check: as in aggregate_rows, except that mask=None means every existing row.
+        per_chunk=True: the kernel's chunk-relative windows, {op: [nchunks, nwin, ndims]}; default: windows over the batch's rows,
+        {op: [nwindows, ndims]}, which needs the chunk's rows to be a multiple or a divisor of window_rows.
+        ops: any of "min", "max" (codec dtype); "argmin", "argmax" (int64: the BATCH row, chunk * R + row, of the FIRST selected row that
+        holds the minimum / maximum -- numpy's tie rule; -1 where the window has no selected row); "first", "last" (codec dtype: the
+        column's value in the window's first / last selected row, 0 where there is none); "rows" (returned as "first_row" and "last_row":
+        int64 [...] batch rows of those two rows, -1 where there is none); "count" (int64 [...]).  A window with no selected row holds min
+        all ones and max 0.  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        ops = rowops.normalise_ops(ops, self._EXT_OPS, "min / max / argmin / argmax / first / last / rows / count")
+        D, n = self.ndims, batch.nchunks
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "extrema_rows")
+        if mask is not None:
+            mask = rowops.check_mask(mask, n, MB, self.device)
+        kw, fold, nwin = rowops.plan_windows(R, window_rows, per_chunk)
+        want = set(ops)
+        if fold > 1:                                        # what the fold compares: the values beside their rows, the rows beside first / last
+            want |= ({"min"} if "argmin" in want else set()) | ({"max"} if "argmax" in want else set()) | ({"rows"} if want & {"first", "last"} else set())
+        bit = dict(zip(self._EXT_OPS, (_lib.EXT_MIN, _lib.EXT_MAX, _lib.EXT_ARGMIN, _lib.EXT_ARGMAX, _lib.EXT_FIRST, _lib.EXT_LAST, _lib.EXT_ROWS, _lib.EXT_COUNT)))
+        bits = sum(bit[k] for k in want)
+        raw = {k: torch.empty((n, nwin, D), dtype=self.dtype, device=self.device) for k in ("min", "max", "first", "last") if k in want}
+        raw.update({k: torch.empty((n, nwin, D), dtype=torch.int32, device=self.device) for k in ("argmin", "argmax") if k in want})
+        if "rows" in want:
+            raw["rows"] = torch.empty((n, nwin, 2), dtype=torch.int32, device=self.device)
+        if "count" in want:
+            raw["count"] = torch.empty((n, nwin), dtype=torch.int32, device=self.device)
+        rets = self._rets(n, check)
+        ptr = lambda k: raw[k].data_ptr() if k in raw else None
+        with self._on():
+            _lib.check(_lib.extrema_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                         self.chunk_len, D, mask.data_ptr() if mask is not None else None, kw, bits, self._general(general_layout),
+                                         ptr("min"), ptr("max"), ptr("argmin"), ptr("argmax"), ptr("first"), ptr("last"), ptr("rows"), ptr("count"),
+                                         rets.data_ptr() if rets is not None else None, self._stream()))
+        if check:
+            rowops.raise_damaged("extrema_rows", rets, n, _lib.SprintzError)
+        # chunk-relative uint32 rows (all ones: none) -> int64 batch rows (-1: none)
+        base = (torch.arange(n, dtype=torch.int64, device=self.device) * R).reshape(n, 1, 1)
+
+        def batch_rows(v):
+            v = v.to(torch.int64)                           # int32 -1 is SPRINTZ_EXT_NO_ROW
+            return torch.where(v >= 0, v + base, v)
+
+        res = {k: v for k, v in raw.items() if k in ("min", "max", "first", "last")}
+        for k in ("argmin", "argmax"):
+            if k in raw:
+                res[k] = batch_rows(raw[k])
+        if "rows" in raw:
+            fl = batch_rows(raw["rows"])
+            res["first_row"], res["last_row"] = fl[..., 0], fl[..., 1]
+        if "count" in raw:
+            res["count"] = raw["count"].to(torch.int64)
+        out = res
+        if not per_chunk:
+            W = R if window_rows is None else int(window_rows)
+            out = rowops.fold_extrema(res, n, nwin, D, W, fold, batch.total_len, self.esz, self.dtype)
+        keep = set(ops) - {"rows"} | ({"first_row", "last_row"} if "rows" in ops else set())
+        return {k: v for k, v in out.items() if k in keep}
+
+    def extrema_where(self, batch, lo, hi, mode="all", **kw):
+        """SELECT min(x), argmin(x), max(x), argmax(x), ... WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and
+        extrema_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: extrema_rows' other arguments."""
+        return self._where("extrema_where", self.extrema_rows, batch, lo, hi, mode, **kw)
+
+    def m4(self, batch, window_rows, mask=None):
+        """The M4 reduction of the batch: per window of window_rows batch rows (a pixel column of a line chart) the first, the last, the
+        minimum and the maximum sample with their time stamps -- the loss-free downsampling for line charts -- in one extrema_rows launch.
+        -> {"t_first", "t_last": int64 [nw] batch rows; "v_first", "v_last", "v_min", "v_max": [nw, ndims] of the codec's dtype; "t_min",
+        "t_max": int64 [nw, ndims]}; a time stamp is -1 where the window has no (selected) row.  Window rules: extrema_rows' global windows."""
+        e = self.extrema_rows(batch, mask=mask, window_rows=window_rows, ops=("min", "argmin", "max", "argmax", "first", "last", "rows"))
+        return {"t_first": e["first_row"], "v_first": e["first"], "t_min": e["argmin"], "v_min": e["min"],
+                "t_max": e["argmax"], "v_max": e["max"], "t_last": e["last_row"], "v_last": e["last"]}
+
     def groupby_rows(self, batch, key, nbins=256, key_lo=0, shift=None, mask=None, ops=("count", "sum"), chunks_per_table=0, general_layout=False,
                      check=True):
         """SELECT bin(x_key), count(*), sum(x_0), ..., sum(x_{D-1}) WHERE mask GROUP BY bin(x_key), fused into the decode (one launch; only

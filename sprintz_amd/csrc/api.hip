@@ -299,15 +299,15 @@ const DecodeUnit kDecodeUnits[][2] = {SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS, 
                                       SPRINTZ_ROW_OP_UNITS(SPRINTZ_ROW_OP_UNIT_ROW)};
 #undef SPRINTZ_ROW_OP_UNIT_ROW
 #undef SPRINTZ_WIDTH_UNITS
-static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryGroupBy + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
+static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryExtrema + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryGroupBy) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryExtrema) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].generic(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryGroupBy) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryExtrema) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].fast(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
@@ -346,7 +346,7 @@ int fail_op(int code, const char* op, const char* what)
     return fail(code, named.c_str());
 }
 
-// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows) check alike, behind check_common; the refusals that
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows, extrema_rows) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
                  const char* rle_only, const char* op = nullptr)
@@ -400,7 +400,7 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryGroupBy (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryExtrema (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -414,6 +414,7 @@ struct QuerySpec {
     HistogramArgs hist{};       // kQueryHistogram
     MomentArgs mom{};           // kQueryMoments (with win)
     GroupByArgs gby{};          // kQueryGroupBy
+    ExtremaArgs ext{};          // kQueryExtrema (with win and rows)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -488,6 +489,7 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.hist = qs.hist;
     a.mom = qs.mom;
     a.gby = qs.gby;
+    a.ext = qs.ext;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -554,7 +556,7 @@ int decode_batch(const Knobs& k, int codec, int esz, const void* d_comp, const u
                          chunk_len, ndims, d_out, d_rets, st, noheader, nh_ngroups, nh_remaining, qs);
 }
 
-// ---- what aggregate_rows, moments_rows, histogram_rows and groupby_rows check and fill alike.  Each refusal carries the operation's
+// ---- what aggregate_rows, moments_rows, histogram_rows, groupby_rows and extrema_rows check and fill alike.  Each refusal carries the operation's
 // name `op` (fail_op), and each helper is called where its refusals stand among the operation's own.
 // the four masked operations, in front of their own checks: the common refusals, whole rows a chunk; then the mode, the layout and the
 // row mask (null: every row, where the operation allows it).  *rows: rows of a chunk slot
@@ -572,12 +574,12 @@ int masked_row_op(const char* op, int q, int codec, int esz, const void* d_comp,
     qs.rows = RowMaskArgs{d_mask, (*rows + 7) / 8};
     return 0;
 }
-// the windowed pair (aggregate, moments): the windows of a chunk slot of `rows` rows
+// the windowed three (aggregate, moments, extrema): the windows of a chunk slot of `rows` rows
 int windowed_row_op(const char* op, uint32_t window_rows, uint32_t rows, QuerySpec& qs)
 {
     if (window_rows < 8 || window_rows % 8) return fail_op(SPRINTZ_E_INVALID, op, "window_rows must be a multiple of 8, at least 8");
     qs.win.rows = window_rows;
-    qs.win.count = (rows + window_rows - 1) / window_rows;
+    qs.win.count = (uint32_t)(((uint64_t)rows + window_rows - 1) / window_rows);      // (64 bits: rows + window_rows may pass 2^32)
     return 0;
 }
 // the binned pair (histogram, group-by): the bins ...
@@ -1837,6 +1839,45 @@ int sprintz_mi355x_moments_rows(int codec, int elem_bytes, const void* d_comp, c
     qs.mom.sumsq = (ops & SPRINTZ_MOM_SUMSQ) ? d_sumsq : nullptr;
     qs.mom.cross = (ops & SPRINTZ_MOM_CROSS) ? d_cross : nullptr;
     qs.mom.ref = (ops & SPRINTZ_MOM_CROSS) ? ref_col : 0u;
+    return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
+                        0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- extrema rows
+int sprintz_mi355x_extrema_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t window_rows, uint32_t ops,
+                                uint32_t flags, void* d_min, void* d_max, uint32_t* d_argmin, uint32_t* d_argmax,
+                                void* d_first, void* d_last, uint32_t* d_rows, uint32_t* d_count, int64_t* d_rets,
+                                void* hip_stream)
+{
+    QuerySpec qs;
+    uint32_t rows;
+    int rc = masked_row_op("extrema_rows", kQueryExtrema, codec, elem_bytes, d_comp, d_offsets, chunk_len, ndims, flags, d_mask, qs, &rows);
+    if (rc) return rc;
+    if ((rc = windowed_row_op("extrema_rows", window_rows, rows, qs))) return rc;
+    if (ops < 1 || ops > 255) return fail(SPRINTZ_E_INVALID, "extrema_rows: ops must be a non-empty OR of SPRINTZ_EXT_MIN / _MAX / _ARGMIN / _ARGMAX / _FIRST / _LAST / _ROWS / _COUNT");
+    // the eight outputs in the order of their op bits.  One counts only where its op is selected: the others may be NULL or lie anywhere,
+    // and reach the kernels as null -- not touched
+    static_assert(SPRINTZ_EXT_MIN == 1u && SPRINTZ_EXT_MAX == 2u && SPRINTZ_EXT_ARGMIN == 4u && SPRINTZ_EXT_ARGMAX == 8u && SPRINTZ_EXT_FIRST == 16u &&
+                  SPRINTZ_EXT_LAST == 32u && SPRINTZ_EXT_ROWS == 64u && SPRINTZ_EXT_COUNT == 128u && SPRINTZ_EXT_NO_ROW == kExtNoRow, "out[i] is op bit i");
+    const uintptr_t esz = (uintptr_t)elem_bytes;
+    struct { void* p; uintptr_t align; } out[8] = {{d_min, esz}, {d_max, esz}, {d_argmin, 4}, {d_argmax, 4}, {d_first, esz}, {d_last, esz}, {d_rows, 4}, {d_count, 4}};
+    for (int i = 0; i < 8; i++) {
+        if (!(ops & (1u << i))) out[i].p = nullptr;
+        else if (!out[i].p) return fail(SPRINTZ_E_INVALID, "extrema_rows: a selected op without its output buffer");
+    }
+    for (int i = 0; i < 8; i++) {
+        if ((uintptr_t)out[i].p % out[i].align)
+            return fail(SPRINTZ_E_INVALID, "extrema_rows: min / max / first / last must be aligned to the element size, argmin / argmax / rows / count to 4 bytes");
+    }
+    if ((uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "extrema_rows: d_rets must be aligned to 8 bytes");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    qs.win.ops = ops;
+    qs.win.min = out[0].p;
+    qs.win.max = out[1].p;
+    qs.win.row_count = (uint32_t*)out[7].p;
+    qs.ext = ExtremaArgs{(uint32_t*)out[2].p, (uint32_t*)out[3].p, out[4].p, out[5].p, (uint32_t*)out[6].p};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
 }

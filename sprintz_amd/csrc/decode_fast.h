@@ -152,8 +152,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // behind the groups' carves (decode_ops.h: groupby_begin .. groupby_end), so, as for the histogram, no lane leaves early.
     constexpr bool GBY = Q == kQueryGroupBy;
     static_assert(!GBY || (!CM && !SPLIT && DS == 0), "group-by: plain mappings");
+    // EXT (sprintz_mi355x_extrema_rows): per window and column the minimum and the maximum of the rows the caller's mask names (or of every
+    // row) with the rows they stand in, the column's value in the window's first and last selected row, those two rows and the count.
+    // Windows, mask read-ahead and the shape of the run shortcut are aggregate's; value and row stay apart (decode_ops.h: ExtremaAcc).
+    constexpr bool EXT = Q == kQueryExtrema;
+    static_assert(!EXT || (!CM && !SPLIT && DS == 0), "extrema: plain mappings");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select and aggregate take a null mask for "every row"
-    constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY;
+    constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT;
     constexpr bool MASK_GIVEN = SELECT || AGG;             // (no test for a null mask where there always is one: select measured 1 % slower with it)
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
@@ -380,6 +385,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
         for (int k = 0; k < CPL; k++) macc[k] = MomentAcc{0, 0, 0};
     }
+    // extrema rows: the lane's accumulators, the window's first / last selected rows (acnt: its selected rows), are first / last asked for
+    ExtremaAcc eacc[CPL];
+    ExtremaRows erows{kExtNoRow, kExtNoRow};
+    bool eends = false;
+    if constexpr (EXT) eends = a.ext.first != nullptr || a.ext.last != nullptr;
     // histogram rows: the lane's columns and where the samples are counted
     HistCol hcol[CPL];
     HistCtx hctx{};
@@ -399,7 +409,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST) {                // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT) {         // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -436,6 +446,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         } else if constexpr (HIST) {                       // (a lane column past the last one counts nothing)
             if (sm != 0 && col_ok[k]) hist_rows8<W>(hctx, hcol[k], arow, sm);
+        } else if constexpr (EXT) {                        // fb blocks = 8 fb rows lie in front of the block
+            if (sm != 0) extrema_rows8<W>(eacc[k], [&](int i) { return arow[i]; }, sm, 8u * fb, erows.first == kExtNoRow, eends);
         } else if constexpr (MOM || GBY) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
@@ -467,8 +479,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             for (int k = 0; k < CPL; k++) {
                 if (!col_ok[k]) continue;
                 if constexpr (MOM) moments_flush(a, w * (uint64_t)D + (uint64_t)genk[k], macc[k]);
+                else if constexpr (EXT) extrema_flush<W>(a, w * (uint64_t)D + (uint64_t)genk[k], eacc[k]);
                 else win_flush<W>(a, w * (uint64_t)D + (uint64_t)genk[k], qmin[k], qmax[k], qsum[k]);
             }
+            if constexpr (EXT) extrema_rows_flush(a, w, erows, lane_d);
         });
     };
     auto q_window = [&]() {                                // after every block of 8 rows
@@ -482,6 +496,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             window_rows_done(8u);
         }
         if constexpr (HIST) fb++;
+        if constexpr (EXT) {                               // the window's first / last selected rows move behind the columns, then as aggregate
+            if (sm != 0) extrema_rows8_done(erows, sm, 8u * fb);
+            acnt += (uint32_t)__popc(sm);
+            fb++;
+            window_rows_done(8u);
+        }
         if constexpr (MOM) {
             // sm is the group's: every lane of it takes part in the exchange, a lane whose columns are past the last one too (its
             // own sums are never flushed)
@@ -759,6 +779,30 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                         qmax[k] = x > qmax[k] ? x : qmax[k];
                         qsum[k] += (uint64_t)x * c;
                     }
+                    acnt += c;
+                }
+                blocks -= nb;
+                fb += nb;
+                window_rows_done(8u * nb);
+            }
+            return;
+        }
+        if constexpr (EXT && !FIRE && SPRINTZ_EXT_RUN_SHORTCUT) {
+            // a delta run repeats the previous row 8 len times: per window it touches, the selected rows among them are counted and the
+            // first and the last of them found (run_selected_span); if there is one, min and max take the row once, at that first row, the
+            // window's first row takes it if it had none, and its last row is the run's last -- O(windows), not O(rows)
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            uint32_t blocks = len;
+            while (blocks > 0) {
+                const uint32_t nb = blocks < (wleft >> 3) ? blocks : (wleft >> 3);
+                uint32_t f, l;
+                const uint32_t c = run_selected_span(smb, fb, nb, lane_d, DP, f, l);
+                if (c != 0) {
+                    const bool fresh = erows.first == kExtNoRow;
+#pragma unroll
+                    for (int k = 0; k < CPL; k++) extrema_value(eacc[k], pv[k] & MASK, f, fresh);
+                    extrema_value_done(erows, f, l);
                     acnt += c;
                 }
                 blocks -= nb;
@@ -1086,6 +1130,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             wleft = a.win.rows;
             wbase = chunk * (uint64_t)a.win.count;
         }
+        if constexpr (EXT) {
+#pragma unroll
+            for (int k = 0; k < CPL; k++) eacc[k] = extrema_identity();
+            erows = ExtremaRows{kExtNoRow, kExtNoRow};
+            wi = 0;
+            wleft = a.win.rows;
+            wbase = chunk * (uint64_t)a.win.count;
+        }
         if constexpr (MASKED) {                            // the chunk's mask bytes (null: every row), its blocks done, its window's selected rows
             fb = 0; sm = 0; acnt = 0;
             mwin0 = 0x80000000u;                           // no window yet: the first block loads one
@@ -1281,6 +1333,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // fb blocks = 8 fb rows lie in front of the tail
         if (!corrupt)
             moments_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, macc, acnt, lane_d,
+                                 [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (EXT) {
+        // fb blocks = 8 fb rows lie in front of the tail
+        if (!corrupt)
+            extrema_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, eacc, erows, acnt, lane_d,
                                  [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (HIST) {
         // fb blocks = 8 fb rows lie in front of the tail

@@ -31,9 +31,11 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     constexpr bool GBY = Q == kQueryGroupBy;
     constexpr bool TAB = HIST || GBY;
     constexpr bool MOM = Q == kQueryMoments;
+    // EXT (sprintz_mi355x_extrema_rows): aggregate's windows, mask and count; a column keeps min / max with their rows and its first / last value
+    constexpr bool EXT = Q == kQueryExtrema;
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs), and those of them that count a window's selected rows
-    constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY;
-    constexpr bool COUNTED = Q == kQueryAggregate || MOM;
+    constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT;
+    constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int DP = 1 << a.log2DP;
@@ -150,6 +152,17 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (MOM) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) macc[k] = MomentAcc{0, 0, 0};
+        wleft = a.win.rows;
+        wbase = chunk * (uint64_t)a.win.count;
+    }
+    // extrema rows (EXT): the lane's accumulators and the window's first / last selected rows; the windows are the windowed query's
+    ExtremaAcc eacc[CPL];
+    ExtremaRows erows{kExtNoRow, kExtNoRow};
+    bool eends = false;
+    if constexpr (EXT) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) eacc[k] = extrema_identity();
+        eends = a.ext.first != nullptr || a.ext.last != nullptr;
         wleft = a.win.rows;
         wbase = chunk * (uint64_t)a.win.count;
     }
@@ -352,6 +365,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     for (int i = 0; i < 8; i++) xs[i] = v[i][k];
                     hist_rows8<W>(hctx, hcol[k], xs, sm);
                 }
+            } else if constexpr (EXT) {
+                if (sm) extrema_rows8<W>(eacc[k], [&](int i) { return v[i][k]; }, sm, out_elems / (uint32_t)D, erows.first == kExtNoRow, eends);
             } else if constexpr (MOM || GBY) {   // (the products / the adds wait for the reference / key column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
@@ -387,6 +402,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             // the block's 8 rows lie in one window: it leaves when they complete it.  This is window_advance (decode_ops.h) written out:
             // called here, hipcc gave three of the aggregate kernels with 8 columns a lane scratch or a wave less (tools/kernel_regs.sh)
             if constexpr (COUNTED) acnt += (uint32_t)__popc(sm);
+            if constexpr (EXT) {
+                if (sm) extrema_rows8_done(erows, sm, out_elems / (uint32_t)D);
+            }
             wleft -= 8;
             if (wleft == 0) {
 #pragma unroll
@@ -394,8 +412,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     const int col = lane_d * CPL + k;
                     if (col >= D) continue;
                     if constexpr (MOM) moments_flush(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, macc[k]);
+                    else if constexpr (EXT) extrema_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, eacc[k]);
                     else win_flush<W>(a, (wbase + wi) * (uint64_t)D + (uint64_t)col, qmin[k], qmax[k], qsum[k]);
                 }
+                if constexpr (EXT) extrema_rows_flush(a, wbase + wi, erows, lane_d);
                 if constexpr (COUNTED) window_count_flush(a, wbase + wi, acnt, lane_d);
                 wi++;
                 wleft = a.win.rows;
@@ -521,6 +541,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                                              [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (MOM) {
         if (!corrupt) moments_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, macc, acnt, lane_d,
+                                           [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (EXT) {
+        if (!corrupt) extrema_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, eacc, erows, acnt, lane_d,
                                            [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (Q == kQueryMaterialize || Q == kQueryReduceOnly) {
         if (!corrupt) reduce_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, colk, genk, qmax, qsum);      // (out_elems is a multiple of 8*D)

@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments and group-by rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by and extrema rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -43,7 +43,7 @@ struct FilterArgs {
     uint32_t* counts;           // optional
     uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
 };
-// the rows that select, aggregate, histogram, moments and group-by rows take: those whose bits are set in chunk c's mask bytes
+// the rows that select, aggregate, histogram, moments, group-by and extrema rows take: those whose bits are set in chunk c's mask bytes
 // mask[c * stride ...] (filter_rows' layout).  mask == null -- where the operation allows it -- is every existing row: a run-time,
 // wave-uniform switch, as filter.mode is
 struct RowMaskArgs {
@@ -93,6 +93,18 @@ struct GroupByArgs {
     uint64_t* sum;              // optional (SPRINTZ_GBY_SUM): [ntables][nbins][D], the same
     uint32_t key, key_lo;
 };
+// extrema rows (Q == kQueryExtrema; sprintz_mi355x_extrema_rows): over the rows the mask names, per chunk-relative window w (WindowArgs'
+// rows, count, min, max and row_count) and per column d at (c * win.count + w) * D + d, the minimum and the maximum with the
+// chunk-relative row of the FIRST selected row that holds each, and the column's value in the window's first and last selected row; those
+// two rows themselves at (c * win.count + w) * 2.  An output that is null is not selected
+constexpr uint32_t kExtNoRow = 0xffffffffu;     // SPRINTZ_EXT_NO_ROW: the window has no selected row
+struct ExtremaArgs {
+    uint32_t* argmin;           // optional (SPRINTZ_EXT_ARGMIN)
+    uint32_t* argmax;           // optional (SPRINTZ_EXT_ARGMAX)
+    void* first;                // optional (SPRINTZ_EXT_FIRST), element type
+    void* last;                 // optional (SPRINTZ_EXT_LAST), element type
+    uint32_t* rows;             // optional (SPRINTZ_EXT_ROWS): [.. ][2]
+};
 
 struct DecodeArgs {
     const uint8_t* comp;        // compressed bytes
@@ -132,6 +144,7 @@ struct DecodeArgs {
     // the struct is: tools/kernel_diff.py shows their register choices and schedules moving when gather and filter shift by anything
     // but a multiple of 64 bytes, or when sizeof(DecodeArgs) changes.  So the two stay put modulo 64 (the windows' and the table's
     // arguments in front of them), and the struct keeps the length it has had since group-by rows: those kernels keep their code.
+    // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.)
     WindowArgs win;
     MomentArgs mom;
     BinTableArgs table;
@@ -141,9 +154,11 @@ struct DecodeArgs {
     RowMaskArgs rows;
     HistogramArgs hist;
     GroupByArgs gby;
-    uint64_t keep_size[10];
+    ExtremaArgs ext;
+    uint64_t keep_size[5];
 };
-static_assert(sizeof(DecodeArgs) == 496 && offsetof(DecodeArgs, gather) % 64 == 184 % 64, "see the row operations' block");
+static_assert(sizeof(DecodeArgs) == 496 && offsetof(DecodeArgs, gather) % 64 == 184 % 64 && offsetof(DecodeArgs, ext) == 416 && sizeof(ExtremaArgs) == 40,
+              "see the row operations' block");
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
 typedef uint16_t __attribute__((aligned(1), may_alias)) u16_unaligned;
@@ -658,6 +673,152 @@ __device__ __forceinline__ void groupby_tail(const DecodeArgs& a, const GroupByC
                 if (genuine[k]) groupby_add_sum(c, b, (uint32_t)col[k], tail_elem<W>(t, r * D + (uint32_t)col[k]));
         }
         if (c.gcount && lane_d == 0) groupby_add_count(c, b, 1u);
+    });
+}
+
+// ---- extrema rows.  A column keeps the window's minimum and maximum with the chunk-relative rows of their first occurrences, and its
+// values in the window's first and last selected rows.  The running minimum starts above every element (all ones in 32 bits) and the
+// running maximum below every element (-1), so that the first selected row always takes both positions -- a selected 0xFFFF is a
+// minimum with a row, a selected 0 a maximum with a row; the flush turns them into the identities the outputs hold (min all ones of
+// the element type, max 0).  Value and position stay apart: no window is too long for them.
+#ifndef SPRINTZ_EXT_RUN_SHORTCUT
+// 1 (kept): decode_fast.h crosses a delta run in O(windows) (run_selected_span); 0: it replays the run block by block, as FIRE runs are
+// -- both measured in profiles/extrema_rows.txt
+#define SPRINTZ_EXT_RUN_SHORTCUT 1
+#endif
+struct ExtremaAcc {
+    uint32_t mn, amin;
+    int32_t mx;
+    uint32_t amax;
+    uint32_t first, last;
+};
+// the window's first and last selected rows (chunk-relative): the same in every lane of the group
+struct ExtremaRows { uint32_t first, last; };
+__device__ __forceinline__ ExtremaAcc extrema_identity() { return ExtremaAcc{0xffffffffu, kExtNoRow, -1, kExtNoRow, 0u, 0u}; }
+// A column's 8 rows of one block that starts at chunk row `row0`; bit i of m != 0: row i is selected; x(i) may carry garbage above bit
+// W.  Inside the block value and row share one 32-bit key under an unsigned minimum -- (x << (32 - W)) | i for the minimum,
+// (~x << (32 - W)) | i for the maximum: one shift-or and one v_min_u32 a sample each, and the first occurrence wins a tie -- and the
+// block's winner meets the window's under a strict compare, so an earlier block keeps a tie too.  (The row inside a BLOCK needs 3 bits:
+// unlike a key that holds the row inside the window, this one sets no limit on the window's length.)
+// `fresh`: the window has no selected row yet (w.first == kExtNoRow); `ends`: first / last are selected (wave-uniform).
+template <int W, typename F>
+__device__ __forceinline__ void extrema_rows8(ExtremaAcc& acc, F x, uint32_t m, uint32_t row0, bool fresh, bool ends)
+{
+    constexpr int S = 32 - W;                               // the shift drops the garbage above bit W
+    uint32_t kmin = 0xffffffffu, kmax = 0xffffffffu;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        // a row's constant: its number, or all ones where it is not selected -- the identity of both minima (once a block, whatever the columns)
+        const uint32_t c = ((m >> i) & 1u) ? (uint32_t)i : 0xffffffffu;
+        const uint32_t lo = (x(i) << S) | c;
+        const uint32_t hi = (~x(i) << S) | c;                // the maximum as the minimum of the complement: the first occurrence wins there too
+        kmin = lo < kmin ? lo : kmin;
+        kmax = hi < kmax ? hi : kmax;
+    }
+    const uint32_t bmin = kmin >> S, bmax = Elem<W>::MASK - (kmax >> S);
+    if (bmin < acc.mn) { acc.mn = bmin; acc.amin = row0 + (kmin & 7u); }
+    if ((int32_t)bmax > acc.mx) { acc.mx = (int32_t)bmax; acc.amax = row0 + (kmax & 7u); }
+    if (ends) {
+        // the highest set bit's row is the last one so far; the lowest set bit's row is the first one, if the window had none
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if ((m >> i) & 1u) acc.last = x(i) & Elem<W>::MASK;
+        if (fresh) {
+#pragma unroll
+            for (int i = 7; i >= 0; i--)
+                if ((m >> i) & 1u) acc.first = x(i) & Elem<W>::MASK;
+        }
+    }
+}
+// the window's first / last selected rows after a block of 8 rows at row0 whose mask byte is m != 0
+__device__ __forceinline__ void extrema_rows8_done(ExtremaRows& w, uint32_t m, uint32_t row0)
+{
+    if (w.first == kExtNoRow) w.first = row0 + (uint32_t)__ffs((int)m) - 1u;
+    w.last = row0 + 31u - (uint32_t)__clz((int)m);
+}
+// one value x (clean) that selected rows hold of which the first is row `f` and the last row `l` (a delta run's constant row in one
+// window; a row of the tail: f == l); `fresh` as above
+__device__ __forceinline__ void extrema_value(ExtremaAcc& acc, uint32_t x, uint32_t f, bool fresh)
+{
+    if (x < acc.mn) { acc.mn = x; acc.amin = f; }
+    if ((int32_t)x > acc.mx) { acc.mx = (int32_t)x; acc.amax = f; }
+    if (fresh) acc.first = x;
+    acc.last = x;
+}
+__device__ __forceinline__ void extrema_value_done(ExtremaRows& w, uint32_t f, uint32_t l)
+{
+    if (w.first == kExtNoRow) w.first = f;
+    w.last = l;
+}
+// The selected rows among the 8 * nblocks that a delta run repeats from block first_block of the chunk on (run_selected_rows), and the
+// chunk-relative rows of the first and the last of them (valid where the count is not 0): a group-wide find-first-set / find-last-set
+// over those mask bytes -- or the run's first and last rows where mask_bytes is null.  EVERY lane of the group must come here.
+__device__ __forceinline__ uint32_t run_selected_span(const uint8_t* mask_bytes, uint32_t first_block, uint32_t nblocks, int lane_d, int DP, uint32_t& f, uint32_t& l)
+{
+    if (!mask_bytes) {
+        f = 8u * first_block;
+        l = 8u * (first_block + nblocks) - 1u;
+        return 8u * nblocks;
+    }
+    uint32_t c = 0, lo = kExtNoRow, hi = 0;
+    for (uint32_t j = (uint32_t)lane_d; j < nblocks; j += (uint32_t)DP) {
+        const uint32_t m = (uint32_t)mask_bytes[first_block + j];
+        if (m == 0) continue;
+        c += (uint32_t)__popc(m);
+        const uint32_t r0 = 8u * (first_block + j);
+        const uint32_t a = r0 + (uint32_t)__ffs((int)m) - 1u, b = r0 + 31u - (uint32_t)__clz((int)m);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    for (int off = DP >> 1; off > 0; off >>= 1) {
+        const uint32_t a = (uint32_t)__shfl_xor((int)lo, off, DP), b = (uint32_t)__shfl_xor((int)hi, off, DP);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    f = lo;
+    l = hi;
+    return group_sum(c, DP);
+}
+// one column's entries of one window leave (each entry has exactly one writer -- no atomics), and the accumulators start over
+template <int W>
+__device__ __forceinline__ void extrema_flush(const DecodeArgs& a, uint64_t idx, ExtremaAcc& acc)
+{
+    using U = typename Elem<W>::U;
+    if (a.win.min) ((U*)a.win.min)[idx] = (U)acc.mn;
+    if (a.win.max) ((U*)a.win.max)[idx] = (U)(acc.mx < 0 ? 0 : acc.mx);
+    if (a.ext.argmin) a.ext.argmin[idx] = acc.amin;
+    if (a.ext.argmax) a.ext.argmax[idx] = acc.amax;
+    if (a.ext.first) ((U*)a.ext.first)[idx] = (U)acc.first;
+    if (a.ext.last) ((U*)a.ext.last)[idx] = (U)acc.last;
+    acc = extrema_identity();
+}
+// the window's two rows leave with its other entries (one lane of the group), and start over
+__device__ __forceinline__ void extrema_rows_flush(const DecodeArgs& a, uint64_t widx, ExtremaRows& w, int lane_d)
+{
+    if (a.ext.rows && lane_d == 0) {
+        a.ext.rows[2 * widx] = w.first;
+        a.ext.rows[2 * widx + 1] = w.last;
+    }
+    w = ExtremaRows{kExtNoRow, kExtNoRow};
+}
+// The verbatim tail (window_tail_rows): a selected row's elements reach the lane's genuine columns, its number the window's rows
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void extrema_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0, const int (&col)[CPL],
+                                             const bool (&genuine)[CPL], uint64_t wbase, uint32_t wi, uint32_t wleft, ExtremaAcc (&acc)[CPL], ExtremaRows& wr,
+                                             uint32_t cnt, int lane_d, F mask_at)
+{
+    auto flush_cols = [&](uint64_t w) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) extrema_flush<W>(a, w * (uint64_t)D + (uint64_t)col[k], acc[k]);
+        extrema_rows_flush(a, w, wr, lane_d);
+    };
+    window_tail_rows(a, remaining / D, row0, a.rows.mask != nullptr, mask_at, wbase, wi, wleft, cnt, lane_d, flush_cols, [&](uint32_t r) {
+        const bool fresh = wr.first == kExtNoRow;
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) extrema_value(acc[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), row0 + r, fresh);
+        extrema_value_done(wr, row0 + r, row0 + r);
     });
 }
 

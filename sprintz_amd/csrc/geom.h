@@ -29,14 +29,15 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 7 = aggregate: per-window min / max / sum / count of the rows whose bit is set in the caller's mask, reduce only;
 // 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only;
 // 9 = moments: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names (or of every row), reduce only;
-// 10 = group-by: per bin of ONE key column's value, the count and the per-column sums of the rows a mask names (or of every row), added up in an LDS table a workgroup, reduce only.
-// 6 .. 10 read one row mask (decode_ops.h: RowMaskArgs), 3, 7 and 9 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
+// 10 = group-by: per bin of ONE key column's value, the count and the per-column sums of the rows a mask names (or of every row), added up in an LDS table a workgroup, reduce only;
+// 11 = extrema: per-window min / max with the rows they stand in, the first and the last selected row and the count, of the rows a mask names (or of every row), reduce only.
+// 6 .. 11 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10;
+              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
-    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments || q == kQueryGroupBy;
+    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments || q == kQueryGroupBy || q == kQueryExtrema;
 }
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB

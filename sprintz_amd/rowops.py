@@ -1,5 +1,5 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+moments_rows, groupby_rows, extrema_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
 fold of its results into windows over the batch's rows, the first damaged chunk, the default bin shift, bounds and offsets as tensors, and
 the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
@@ -69,6 +69,57 @@ def fold_windows(res, n, nwin, D, W, fold, total_len, esz, dtype):
         ident = (1 << (8 * esz)) - 1 if k == "min" else 0
         v = torch.cat([v, v.new_full((nw * fold - n,) + tail, ident)]).reshape((nw, fold) + tail)
         out[k] = v.amin(dim=1).to(dtype) if k == "min" else v.amax(dim=1).to(dtype) if k == "max" else v.sum(dim=1)
+    return out
+
+
+def fold_extrema(res, n, nwin, D, W, fold, total_len, esz, dtype):
+    """extrema_rows' per-chunk windows -> windows of W rows over the batch's rows, as fold_windows does for the aggregates.  res: "min",
+    "max", "first", "last": [n, nwin, D] of `dtype`; "argmin", "argmax": int64 [n, nwin, D] and "first_row", "last_row": int64 [n, nwin] --
+    BATCH rows, -1 where the window has no selected row; "count": int64 [n, nwin]; any subset, but "argmin" needs "min", "argmax" needs
+    "max" and "first" / "last" need "first_row" / "last_row".  fold == 1: the chunks' windows are the batch's.  fold > 1: one window a
+    chunk, `fold` consecutive chunks a window: min / argmin come from the FIRST chunk that holds the window's minimum in a selected row
+    (chunks lie in batch row order, so that is the first occurrence), max / argmax likewise; first / first_row from the first chunk with
+    a selected row, last / last_row from the last one; the chunks the last window lacks hold the identities (min all ones, max 0,
+    first = last = 0, rows -1, count 0)."""
+    nw = -(-(-(-total_len // D)) // W)
+    if fold == 1:
+        return {k: v.reshape((n * nwin,) + tuple(v.shape[2:]))[:nw] for k, v in res.items()}
+    ident = {"min": (1 << (8 * esz)) - 1, "max": 0, "first": 0, "last": 0, "count": 0}
+    g = {}
+    for k, v in res.items():
+        tail = tuple(v.shape[2:])
+        v = v.reshape((n,) + tail)
+        if v.dtype == dtype:
+            v = v.to(torch.int32)                           # torch's uint16 lacks most reductions
+        g[k] = torch.cat([v, v.new_full((nw * fold - n,) + tail, ident.get(k, -1))]).reshape((nw, fold) + tail)
+    out = {}
+
+    def pick(v, ok, last=False):
+        """v[w, j] at the first (last) j along dim 1 where ok[w, j]; -> (picked, found)"""
+        j = torch.arange(fold, device=ok.device).reshape((1, fold) + (1,) * (ok.dim() - 2))
+        key = torch.where(ok, j, -1).amax(dim=1) if last else torch.where(ok, j, fold).amin(dim=1)
+        found = key >= 0 if last else key < fold
+        return v.gather(1, key.clamp(0, fold - 1).unsqueeze(1)).squeeze(1), found
+
+    for val, arg, red in (("min", "argmin", torch.amin), ("max", "argmax", torch.amax)):
+        if val not in g:
+            continue
+        best = red(g[val], dim=1)
+        out[val] = best.to(dtype)
+        if arg in g:
+            a, found = pick(g[arg], (g[val] == best.unsqueeze(1)) & (g[arg] >= 0))
+            out[arg] = torch.where(found, a, -1)
+    for val, row, last in (("first", "first_row", False), ("last", "last_row", True)):
+        if row not in g:
+            continue
+        ok = g[row] >= 0
+        r, found = pick(g[row], ok, last)
+        out[row] = torch.where(found, r, -1)
+        if val in g:
+            v, found = pick(g[val], ok.unsqueeze(-1).expand_as(g[val]), last)
+            out[val] = torch.where(found, v, 0).to(dtype)
+    if "count" in g:
+        out["count"] = g["count"].sum(dim=1)
     return out
 
 
