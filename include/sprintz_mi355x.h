@@ -52,7 +52,7 @@ extern "C" {
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
- *      extrema_rows, SPRINTZ_EXT_* */
+ *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -498,6 +498,38 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
 int sprintz_mi355x_filter_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                uint32_t chunk_len, uint16_t ndims, const void* d_lo, const void* d_hi, uint32_t mode,
                                uint32_t flags, uint8_t* d_mask, uint32_t* d_counts, int64_t* d_rets, void* hip_stream);
+/* Linear filter rows: the second producer of a row mask.  filter_rows' predicate is a box, column by column; this one relates
+ * columns ("a > b", "x + y + z > t") and a row to the row in front of it ("|x[r] - x[r-1]| > t", "state[r] != state[r-1]") -- one
+ * linear form over a row and its predecessor, tested against an interval.  The batch is given as to filter_rows, with
+ * chunk_len % ndims == 0: chunk c holds batch rows [c R, (c + 1) R), R = chunk_len / ndims; a partial last row of the batch is not a
+ * row.  For batch row g, with x the unsigned element widened to 32 bits:
+ *
+ *     s(g) = bias + sum_d w[d] x[g, d] + sum_d u[d] x[p(g), d],   p(g) = g - 1 for g > 0, p(0) = 0
+ *     row g matches  <=>  lo <= s(g) <= hi
+ *
+ * Row 0 is its own predecessor (numpy.diff(..., prepend=x[0])).  w = d_weights and u = d_lag_weights are device arrays of ndims
+ * int32; d_lag_weights == NULL means no lag term.  bias, lo and hi are int32; the comparison is signed and inclusive, and lo > hi
+ * matches nothing.  THE WRAPPING RULE: s is computed in wrapping 32-bit two's-complement arithmetic.  The library cannot see weights
+ * that live on the device, so it cannot refuse a form that wraps: s is the exact integer wherever
+ *     B = |bias| + (2^W - 1) sum_d (|w[d]| + |u[d]|) < 2^31        (W = 8 elem_bytes),
+ * and a caller who wants exact answers keeps B below 2^31 (the Python layer refuses the others).
+ * d_mask, d_counts, d_rets: filter_rows' outputs, in its layout -- MB = ceil(R / 8) bytes a chunk, 0 for rows that do not exist;
+ * d_mask or d_counts may be NULL, not both.  The masks of both filters combine bytewise (AND, OR) and feed select_rows and the
+ * other mask consumers unchanged.
+ * d_tmp: with d_lag_weights, sprintz_mi355x_filter_linear_tmp_bytes(elem_bytes, nchunks, ndims) bytes of device scratch, aligned to 8
+ * (the layout is the library's own; the contents need not be kept); else ignored.  Inside the decode launch a chunk's first row is
+ * its own predecessor; a second small launch on the same stream then gives row 0 of every chunk behind the first its true
+ * predecessor, the last row of the chunk in front.  Row 0 of a chunk that follows a damaged chunk is unspecified; d_rets names the
+ * damaged one.  The launch counts under DEC_FAST or DEC_GENERIC.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for an unknown flag, a NULL d_comp / d_offsets / d_weights, both outputs
+ * NULL, chunk_len % ndims != 0 (or outside 1..2^30), d_weights / d_lag_weights / d_counts not aligned to 4 bytes, d_rets not aligned
+ * to 8, d_tmp NULL or not aligned to 8 while d_lag_weights is given; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the
+ * non-RLE codecs.  nchunks == 0 returns 0 and launches nothing.  _tmp_bytes returns 0 for bad arguments. */
+int sprintz_mi355x_filter_linear(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                 uint32_t chunk_len, uint16_t ndims, const int32_t* d_weights, const int32_t* d_lag_weights,
+                                 int32_t bias, int32_t lo, int32_t hi, uint32_t flags, void* d_tmp, uint8_t* d_mask, uint32_t* d_counts,
+                                 int64_t* d_rets, void* hip_stream);
+uint64_t sprintz_mi355x_filter_linear_tmp_bytes(int elem_bytes, uint64_t nchunks, uint16_t ndims);
 /* A mask of filter_rows as batch row numbers.  Needs chunk_len % ndims == 0, as gather_rows does: with R = chunk_len / D, batch row g
  * is row g % R of chunk g / R, and d_mask holds MB = ceil(R / 8) bytes a chunk.  d_bases[c] is the exclusive prefix sum of the
  * chunks' counts, computed by the caller (torch.cumsum, hipcub, ...).  The i-th set bit of chunk c, in ascending row order, writes

@@ -131,6 +131,9 @@ gather_rows = _sig("sprintz_mi355x_gather_rows", _i, _i, _i, _vp, _vp, _u64, _u3
 FILTER_ALL, FILTER_ANY = 0, 1
 filter_rows = _sig("sprintz_mi355x_filter_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp)
 filter_row_ids = _sig("sprintz_mi355x_filter_row_ids", _i, _vp, _vp, _u64, _u32, _u16, _vp, _u64, _vp)
+# a row mask from a linear form over a row and its predecessor, tested against an interval (include/sprintz_mi355x.h)
+filter_linear = _sig("sprintz_mi355x_filter_linear", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _u32, _vp, _vp, _vp, _vp, _vp)
+filter_linear_tmp_bytes = _sig("sprintz_mi355x_filter_linear_tmp_bytes", _u64, _i, _u64, _u16)
 # the rows a mask names, each chunk decoded once, packed densely behind the chunk's base (include/sprintz_mi355x.h)
 select_rows = _sig("sprintz_mi355x_select_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
 # per-window min / max / sum / count of the rows a mask names (include/sprintz_mi355x.h)
@@ -219,7 +222,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_huf0_tmp_bytes", "sprintz_mi355x_huf0_bound", "sprintz_mi355x_huf0_compress_batch",
     "sprintz_mi355x_huf0_exact_tmp_bytes", "sprintz_mi355x_huf0_compress_batch_exact",
     "sprintz_mi355x_query_batch", "sprintz_mi355x_query_reduce", "sprintz_mi355x_query_windows",
-    "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids", "sprintz_mi355x_select_rows",
+    "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids", "sprintz_mi355x_filter_linear", "sprintz_mi355x_filter_linear_tmp_bytes", "sprintz_mi355x_select_rows",
     "sprintz_mi355x_aggregate_rows", "sprintz_mi355x_histogram_rows", "sprintz_mi355x_moments_rows", "sprintz_mi355x_groupby_rows", "sprintz_mi355x_extrema_rows",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",

@@ -442,15 +442,70 @@ class ChunkedCodec:
             rowops.raise_damaged("filter_rows", rets, n, _lib.SprintzError)
         res = {"mask": mask, "counts": counts}
         if ids:
-            incl = torch.cumsum(counts.to(torch.int64), 0)
-            total = int(incl[-1].item()) if n else 0
-            out = torch.empty(total, dtype=torch.int64, device=self.device)
-            if total:
-                bases = (incl - counts).contiguous()
-                with self._on():
-                    _lib.check(_lib.filter_row_ids(mask.data_ptr(), bases.data_ptr(), n, self.chunk_len, D, out.data_ptr(), total, self._stream()))
-            res["ids"] = out
+            res["ids"] = self._mask_ids(mask, counts)
         return res
+
+    def _mask_ids(self, mask, counts):
+        """a filter's mask and counts -> int64 [total]: the matching batch rows in ascending order (a prefix sum of the counts and the
+        filter_row_ids launch)"""
+        torch = self.torch
+        n = counts.numel()
+        incl = torch.cumsum(counts.to(torch.int64), 0)
+        total = int(incl[-1].item()) if n else 0
+        out = torch.empty(total, dtype=torch.int64, device=self.device)
+        if total:
+            bases = (incl - counts).contiguous()
+            with self._on():
+                _lib.check(_lib.filter_row_ids(mask.data_ptr(), bases.data_ptr(), n, self.chunk_len, self.ndims, out.data_ptr(), total, self._stream()))
+        return out
+
+    def filter_linear(self, batch, weights, lo=None, hi=None, lag_weights=None, bias=0, general_layout=False, ids=False, check=True):
+        """Which rows satisfy a condition that RELATES columns, or a row to the row in front of it -- filter_rows' second kind of
+        predicate, straight from the compressed batch.  Batch row g (row g % R of chunk g // R, R = chunk_len / ndims: chunk_len must be
+        a multiple of ndims) matches if
+
+            lo <= bias + sum_d weights[d] x[g, d] + sum_d lag_weights[d] x[g - 1, d] <= hi
+
+        with x the unsigned samples as integers; row 0 is its own predecessor (numpy.diff(..., prepend=x[0])).  weights / lag_weights:
+        a scalar (every column), a sequence of ndims entries, a dict {column: weight} or an integer tensor; lag_weights=None: no lag
+        term.  lo / hi: signed, inclusive, None = open.  The sum is exact: a form that could pass 2^31 in magnitude is a ValueError
+        (rowops.linear_terms).
+        -> filter_rows' dict, in its layout: {"mask": uint8 [nchunks, MB], "counts": int32 [nchunks]} and, with ids=True, "ids".  The masks
+        of both filters combine with & / | in torch and feed select_rows, aggregate_rows and the other mask consumers unchanged:
+
+            m = codec.filter_linear(batch, {0: 1, 1: -1}, lo=1)["mask"]                  # WHERE a > b
+            rows = codec.select_rows(batch, m & codec.filter_rows(batch, lo, hi)["mask"])["rows"]
+
+        check=True raises SprintzError naming the first damaged chunk; ids=True checks too (as filter_rows)."""
+        torch = self.torch
+        check = check or ids
+        D, n = self.ndims, batch.nchunks
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "filter_linear")
+        w, u, bias, lo, hi = rowops.linear_terms(weights, lag_weights, bias, lo, hi, D, self.esz, self.device)
+        mask = torch.empty((n, MB), dtype=torch.uint8, device=self.device)
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        rets = self._rets(n, check)
+        tmp = torch.empty(max(_lib.filter_linear_tmp_bytes(self.esz, n, D) // 8, 1), dtype=torch.int64, device=self.device) if u is not None else None
+        with self._on():
+            _lib.check(_lib.filter_linear(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                          self.chunk_len, D, w.data_ptr(), u.data_ptr() if u is not None else None, bias, lo, hi,
+                                          self._general(general_layout), tmp.data_ptr() if tmp is not None else None,
+                                          mask.data_ptr(), counts.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
+        if check:
+            rowops.raise_damaged("filter_linear", rets, n, _lib.SprintzError)
+        res = {"mask": mask, "counts": counts}
+        if ids:
+            res["ids"] = self._mask_ids(mask, counts)
+        return res
+
+    def filter_change(self, batch, col, lo=None, hi=None, **kw):
+        """Which rows CHANGE: lo <= x[g, col] - x[g - 1, col] <= hi (filter_linear with weights e_col and lag_weights -e_col; row 0
+        changes by 0).  Spikes and steps are two calls, the change log of a state column one:
+
+            up, down = codec.filter_change(batch, 3, lo=t + 1)["mask"], codec.filter_change(batch, 3, hi=-t - 1)["mask"]   # |dx| > t: up | down
+            log = codec.filter_change(batch, 0, lo=0, hi=0)      # state[r] == state[r-1]: ~mask over the rows that exist is the event log
+            events = codec.filter_change(batch, 0, lo=1, ids=True)["ids"]      # ... or the rows where the state went up, by number"""
+        return self.filter_linear(batch, {int(col): 1}, lo=lo, hi=hi, lag_weights={int(col): -1}, **kw)
 
     def _where(self, op, method, batch, lo, hi, mode, /, counts=False, **kw):
         """filter_rows (lo / hi / mode), then `method` on its mask (counts=True: and its counts).  Whole rows are asked for before the

@@ -299,15 +299,15 @@ const DecodeUnit kDecodeUnits[][2] = {SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS, 
                                       SPRINTZ_ROW_OP_UNITS(SPRINTZ_ROW_OP_UNIT_ROW)};
 #undef SPRINTZ_ROW_OP_UNIT_ROW
 #undef SPRINTZ_WIDTH_UNITS
-static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryExtrema + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
+static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryLinear + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryExtrema) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryLinear) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].generic(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryExtrema) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryLinear) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].fast(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
@@ -346,7 +346,7 @@ int fail_op(int code, const char* op, const char* what)
     return fail(code, named.c_str());
 }
 
-// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows, extrema_rows) check alike, behind check_common; the refusals that
+// what the row operations (query_windows, gather_rows, filter_rows, select_rows, aggregate_rows, histogram_rows, moments_rows, groupby_rows, extrema_rows, filter_linear) check alike, behind check_common; the refusals that
 // name the operation come in its own words (rle_only == null: every codec is taken)
 int check_row_op(int codec, uint32_t chunk_len, uint16_t ndims, uint32_t flags, const void* d_comp, const void* d_offsets, const char* many_columns,
                  const char* rle_only, const char* op = nullptr)
@@ -400,7 +400,7 @@ struct HostCall {
 };
 
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryExtrema (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryLinear (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -415,6 +415,7 @@ struct QuerySpec {
     MomentArgs mom{};           // kQueryMoments (with win)
     GroupByArgs gby{};          // kQueryGroupBy
     ExtremaArgs ext{};          // kQueryExtrema (with win and rows)
+    LinearArgs lin{};           // kQueryLinear (with filter: the mask, the counts and the mask's stride)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;
@@ -490,6 +491,7 @@ int decode_launch(const Plan& p, int esz, const void* d_comp, const uint64_t* d_
     a.mom = qs.mom;
     a.gby = qs.gby;
     a.ext = qs.ext;
+    a.lin = qs.lin;
     a.norle = p.norle;
     a.raw = p.raw;
     a.col_stride = qs.col_stride;
@@ -1742,6 +1744,49 @@ int sprintz_mi355x_filter_rows(int codec, int elem_bytes, const void* d_comp, co
     qs.filter = FilterArgs{d_lo, d_hi, mode, d_mask, d_counts, (rows + 7) / 8};
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- linear filter rows
+uint64_t sprintz_mi355x_filter_linear_tmp_bytes(int elem_bytes, uint64_t nchunks, uint16_t ndims)
+{
+    if ((elem_bytes != 1 && elem_bytes != 2) || ndims == 0 || ndims > 512 || nchunks == 0) return 0;
+    const uint64_t stride = linear_tmp_stride(elem_bytes, ndims);
+    return nchunks > (1ull << 62) / stride ? 0 : nchunks * stride;
+}
+
+int sprintz_mi355x_filter_linear(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                 uint32_t chunk_len, uint16_t ndims, const int32_t* d_weights, const int32_t* d_lag_weights,
+                                 int32_t bias, int32_t lo, int32_t hi, uint32_t flags, void* d_tmp, uint8_t* d_mask, uint32_t* d_counts,
+                                 int64_t* d_rets, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if ((rc = check_row_op(codec, chunk_len, ndims, flags, d_comp, d_offsets, "more than 512 columns: no filter", "filter_linear: the RLE codecs (delta, xff) only"))) return rc;
+    if (!d_weights) return fail(SPRINTZ_E_INVALID, "null device pointer");
+    if (!d_mask && !d_counts) return fail(SPRINTZ_E_INVALID, "filter_linear: neither a mask nor counts asked for");
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "filter_linear: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if ((uintptr_t)d_weights % 4 || (uintptr_t)d_lag_weights % 4) return fail(SPRINTZ_E_INVALID, "filter_linear: d_weights / d_lag_weights must be aligned to 4 bytes");
+    if ((uintptr_t)d_counts % 4 || (uintptr_t)d_rets % 8) return fail(SPRINTZ_E_INVALID, "filter_linear: d_counts must be aligned to 4 bytes, d_rets to 8");
+    if (d_lag_weights && (!d_tmp || (uintptr_t)d_tmp % 8))
+        return fail(SPRINTZ_E_INVALID, "filter_linear: with d_lag_weights, d_tmp must hold sprintz_mi355x_filter_linear_tmp_bytes bytes, aligned to 8");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    const uint32_t rows = chunk_len / ndims;
+    QuerySpec qs;
+    qs.q = kQueryLinear;
+    qs.general = (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) ? 1 : 0;
+    qs.filter = FilterArgs{nullptr, nullptr, 0u, d_mask, d_counts, (rows + 7) / 8};
+    qs.lin = LinearArgs{d_weights, d_lag_weights, d_lag_weights ? d_tmp : nullptr, lo, hi, bias, 0u};
+    rc = decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream, 0, 0, 0, qs);
+    if (rc || !d_lag_weights || nchunks < 2) return rc;
+    // the seam pass, behind the decode on the same stream: row 0 of every chunk behind the first takes its true predecessor
+    DecodeArgs a{};
+    a.nchunks = nchunks;
+    a.D = ndims;
+    a.filter = qs.filter;
+    a.lin = qs.lin;
+    if (launch_linear_seam(elem_bytes, a, (hipStream_t)hip_stream) != hipSuccess) return fail(SPRINTZ_E_HIP, "filter_linear seam kernel launch");
+    return 0;
 }
 
 int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases, uint64_t nchunks, uint32_t chunk_len,

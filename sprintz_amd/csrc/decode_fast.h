@@ -157,6 +157,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // Windows, mask read-ahead and the shape of the run shortcut are aggregate's; value and row stay apart (decode_ops.h: ExtremaAcc).
     constexpr bool EXT = Q == kQueryExtrema;
     static_assert(!EXT || (!CM && !SPLIT && DS == 0), "extrema: plain mappings");
+    // LIN (sprintz_mi355x_filter_linear): the filter's outputs -- a mask byte a block, the chunk's count -- for a predicate on a linear form
+    // over the row and the row in front of it.  A lane adds its columns' terms into the block's eight partial sums, the group adds those up
+    // once a block (decode_ops.h: linear_rows8, linear_block).
+    constexpr bool LIN = Q == kQueryLinear;
+    static_assert(!LIN || (!CM && !SPLIT && DS == 0), "linear filter: plain mappings");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select and aggregate take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT;
     constexpr bool MASK_GIVEN = SELECT || AGG;             // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -406,10 +411,23 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         for (int k = 0; k < CPL; k++) fc[k] = filter_col<W>(a, genk[k], col_ok[k]);
         finv = filter_inv(a);
     }
+    // linear filter rows: this lane's columns' weights, loaded once; lacc the block's eight partial sums over the lane's columns, lcarry what
+    // the previous block's row 7 hands to this block's row 0, lfirst: no row of the chunk is done (fb, fcnt and fmb are the filter's)
+    LinearCol lc[CPL];
+    LinearCtx lctx{};
+    uint32_t lacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t lself = 0, lcarry = 0, lnext = 0;
+    uint32_t lfirst = 1;
+    uint64_t lchunk = 0;
+    if constexpr (LIN) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) lc[k] = linear_col(a, genk[k], col_ok[k]);
+        lctx = linear_ctx(a);
+    }
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST || EXT) {         // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT || LIN) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -448,6 +466,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             if (sm != 0 && col_ok[k]) hist_rows8<W>(hctx, hcol[k], arow, sm);
         } else if constexpr (EXT) {                        // fb blocks = 8 fb rows lie in front of the block
             if (sm != 0) extrema_rows8<W>(eacc[k], [&](int i) { return arow[i]; }, sm, 8u * fb, erows.first == kExtNoRow, eends);
+        } else if constexpr (LIN) {                        // (a lane column past the last one has weights 0; the chunk's first row leaves for the seam pass)
+            if (lctx.lag && lfirst && col_ok[k]) linear_slot<W>(a, lchunk, (uint32_t)D).first[genk[k]] = (U)arow[0];
+            linear_rows8<W>(lc[k], [&](int i) { return arow[i]; }, lctx.lag, lfirst, lacc, lself, lnext);
         } else if constexpr (MOM || GBY) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
@@ -457,6 +478,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (Q == kQueryFilter) {
             const uint32_t m = (group_or<DP>(fl) ^ finv) & 0xffu;
             fl = 0;
+            if (fmb && lane_d == 0) fmb[fb] = (uint8_t)m;
+            fcnt += (uint32_t)__popc(m);
+            fb++;
+        }
+        if constexpr (LIN) {
+            const uint32_t m = linear_block(lctx, lacc, lfirst, lself, lcarry, lnext, [](uint32_t v) { return group_add<DP>(v); });
             if (fmb && lane_d == 0) fmb[fb] = (uint8_t)m;
             fcnt += (uint32_t)__popc(m);
             fb++;
@@ -739,6 +766,32 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
             fcnt += hit ? 8u * len : 0u;
             fb += len;
+            return;
+        }
+        if constexpr (LIN && !FIRE && SPRINTZ_LIN_RUN_SHORTCUT) {
+            // a delta run repeats the previous row 8 len times, and the row in front of the run equals it (at the chunk's start: the zero
+            // row, its own predecessor): every row of the run has s = bias + sum (w + u) pv -- one evaluation, then len bytes of 0x00 or
+            // 0xFF spread over the group's lanes.  What the run's last row hands on is sum u pv.
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            out_left -= len * blk_elems;
+            if (len == 0) return;                          // (a padding slot holds no row)
+            uint32_t sw = 0, su = 0;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                const uint32_t x = pv[k] & MASK;
+                sw += lc[k].w * x;
+                su += lc[k].u * x;
+                if (lctx.lag && lfirst && col_ok[k]) linear_slot<W>(a, lchunk, (uint32_t)D).first[genk[k]] = (U)x;
+            }
+            const uint32_t hit = linear_hit(lctx, group_add<DP>(sw + su));
+            if (fmb) {
+                const uint8_t byte = hit ? 0xffu : 0u;
+                for (uint32_t j = (uint32_t)lane_d; j < len; j += DP) fmb[fb + j] = byte;
+            }
+            fcnt += hit ? 8u * len : 0u;
+            fb += len;
+            lcarry = su;
+            lfirst = 0;
             return;
         }
         if constexpr (Q == kQueryWindow && !FIRE) {
@@ -1147,6 +1200,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
             fmb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
         }
+        if constexpr (LIN) {
+            fb = 0; fcnt = 0;
+            fmb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
+#pragma unroll
+            for (int i = 0; i < 8; i++) lacc[i] = 0;
+            lself = 0; lcarry = 0; lnext = 0;
+            lfirst = 1;
+            lchunk = chunk;
+        }
         if constexpr (HIST) hctx.g = hist_of_chunk(a, chunk);
         if constexpr (GBY) groupby_of_chunk(a, gctx, chunk);
         if constexpr (SELECT) {
@@ -1299,6 +1361,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     if (!corrupt && gabs + rp + (uint64_t)remaining * ESZ > off_c + stream_len) corrupt = true;
     if constexpr (Q == kQueryFilter) {
         if (!corrupt) filter_tail<W, CPL>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, fb, lane_d, DP, fc, genk, col_ok, fcnt);
+        if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
+    } else if constexpr (LIN) {
+        // fb blocks lie in front of the tail; a damaged chunk has no row the seam pass may use
+        if (!corrupt) linear_tail<W, CPL>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, fb, lane_d, DP, lc, genk, col_ok, lctx, lcarry, pv, fcnt);
+        else linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
         if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
     } else if constexpr (Q == kQueryWindow) {
         // window_tail and reduce_tail (decode_ops.h), kept local: through the shared helpers these kernels were scheduled differently

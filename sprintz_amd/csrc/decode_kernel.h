@@ -33,6 +33,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     constexpr bool MOM = Q == kQueryMoments;
     // EXT (sprintz_mi355x_extrema_rows): aggregate's windows, mask and count; a column keeps min / max with their rows and its first / last value
     constexpr bool EXT = Q == kQueryExtrema;
+    // LIN (sprintz_mi355x_filter_linear): the filter's outputs for a predicate on a linear form over the row and the row in front of it; runs
+    // are replayed block by block, as for the filter
+    constexpr bool LIN = Q == kQueryLinear;
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs), and those of them that count a window's selected rows
     constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT;
     constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
@@ -89,6 +92,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)nd != D || len > a.chunk_len) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
+            if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (TAB) hbad = true; else return;
         }
         groups_left = len < 128u ? 0u : len / (16u * (uint32_t)D);
@@ -102,6 +106,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)(w1 >> 16) != D) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
+            if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (TAB) hbad = true; else return;
         }
     } else {
@@ -182,6 +187,20 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 #pragma unroll
         for (int k = 0; k < CPL; k++) fc[k] = filter_col<W>(a, colk[k], genk[k]);
         finv = filter_inv(a);
+        if (a.filter.mask) fmb = a.filter.mask + chunk * (uint64_t)a.filter.mask_stride;
+    }
+
+    // linear filter rows: each lane's columns' weights, loaded once; the block's eight partial sums over the lane's columns and what the
+    // previous block's row 7 hands to this block's row 0 (decode_ops.h: linear_rows8, linear_block); fcnt and fmb are the filter's
+    LinearCol lc[CPL];
+    LinearCtx lctx{};
+    uint32_t lacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t lself = 0, lcarry = 0, lnext = 0;
+    uint32_t lfirst = 1;
+    if constexpr (LIN) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) lc[k] = linear_col(a, colk[k], genk[k]);
+        lctx = linear_ctx(a);
         if (a.filter.mask) fmb = a.filter.mask + chunk * (uint64_t)a.filter.mask_stride;
     }
 
@@ -367,6 +386,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 }
             } else if constexpr (EXT) {
                 if (sm) extrema_rows8<W>(eacc[k], [&](int i) { return v[i][k]; }, sm, out_elems / (uint32_t)D, erows.first == kExtNoRow, eends);
+            } else if constexpr (LIN) {          // (a lane column past the last one has weights 0; the chunk's first row leaves for the seam pass)
+                if (lctx.lag && lfirst && genk[k]) linear_slot<W>(a, chunk, (uint32_t)D).first[colk[k]] = (U)v[0][k];
+                linear_rows8<W>(lc[k], [&](int i) { return v[i][k]; }, lctx.lag, lfirst, lacc, lself, lnext);
             } else if constexpr (MOM || GBY) {   // (the products / the adds wait for the reference / key column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
@@ -424,6 +446,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride (checked above)
             const uint32_t m = (group_or_any(fl, DP) ^ finv) & 0xffu;
+            if (fmb && lane_d == 0) fmb[out_elems / blk_elems] = (uint8_t)m;
+            fcnt += (uint32_t)__popc(m);
+        }
+
+        if constexpr (LIN) {                     // the same place as the filter's byte
+            const uint32_t m = linear_block(lctx, lacc, lfirst, lself, lcarry, lnext, [&](uint32_t x) { return group_sum(x, DP); });
             if (fmb && lane_d == 0) fmb[out_elems / blk_elems] = (uint8_t)m;
             fcnt += (uint32_t)__popc(m);
         }
@@ -533,6 +561,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if (!corrupt && (out_elems + remaining > a.chunk_len || (uint64_t)remaining * ESZ > (uint64_t)(stream_len - pos))) corrupt = true;
     if constexpr (Q == kQueryFilter) {
         if (!corrupt) filter_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, fc, colk, genk, fcnt);
+        if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
+    } else if constexpr (LIN) {
+        if (!corrupt) linear_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, lc, colk, genk, lctx, lcarry, pv, fcnt);
+        else linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
         if (lane_d == 0 && a.filter.counts) a.filter.counts[chunk] = fcnt;
     } else if constexpr (Q == kQueryWindow) {
         if (!corrupt) window_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum);

@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments, group-by and extrema rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by, extrema and linear filter rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -105,6 +105,18 @@ struct ExtremaArgs {
     void* last;                 // optional (SPRINTZ_EXT_LAST), element type
     uint32_t* rows;             // optional (SPRINTZ_EXT_ROWS): [.. ][2]
 };
+// linear filter rows (Q == kQueryLinear; sprintz_mi355x_filter_linear): batch row g matches if lo <= s(g) <= hi, signed, with
+// s(g) = bias + sum_d w[d] x[g, d] + sum_d lag[d] x[p(g), d] in wrapping 32-bit arithmetic, x the unsigned element, p(g) = g - 1 and
+// p(0) = 0.  The mask, the counts and the mask's stride travel in FilterArgs (filter.mask, filter.counts, filter.mask_stride; its lo / hi
+// null), as aggregate rows reuses WindowArgs.  Inside the decode launch a chunk's first row is its own predecessor; with lag given the
+// decode leaves every chunk's first and last existing row in tmp (LinearSlot) and the seam pass puts row 0 of the chunks behind the first right
+struct LinearArgs {
+    const int32_t* w;           // [D], on the device
+    const int32_t* lag;         // [D], or null: no lag term
+    void* tmp;                  // nchunks x linear_tmp_stride (geom.h) bytes where lag is given
+    int32_t lo, hi, bias;
+    uint32_t pad;
+};
 
 struct DecodeArgs {
     const uint8_t* comp;        // compressed bytes
@@ -144,7 +156,9 @@ struct DecodeArgs {
     // the struct is: tools/kernel_diff.py shows their register choices and schedules moving when gather and filter shift by anything
     // but a multiple of 64 bytes, or when sizeof(DecodeArgs) changes.  So the two stay put modulo 64 (the windows' and the table's
     // arguments in front of them), and the struct keeps the length it has had since group-by rows: those kernels keep their code.
-    // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.)
+    // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.  The linear filter's took the
+    //  other 40: the spare bytes are used up, and the next mode's arguments have to share a struct that is here, as the linear filter shares
+    //  FilterArgs, or move the kernels named above.)
     WindowArgs win;
     MomentArgs mom;
     BinTableArgs table;
@@ -155,9 +169,10 @@ struct DecodeArgs {
     HistogramArgs hist;
     GroupByArgs gby;
     ExtremaArgs ext;
-    uint64_t keep_size[5];
+    LinearArgs lin;
 };
-static_assert(sizeof(DecodeArgs) == 496 && offsetof(DecodeArgs, gather) % 64 == 184 % 64 && offsetof(DecodeArgs, ext) == 416 && sizeof(ExtremaArgs) == 40,
+static_assert(sizeof(DecodeArgs) == 496 && offsetof(DecodeArgs, gather) % 64 == 184 % 64 && offsetof(DecodeArgs, ext) == 416 && sizeof(ExtremaArgs) == 40 &&
+                  offsetof(DecodeArgs, lin) == 456 && sizeof(LinearArgs) == 40,
               "see the row operations' block");
 
 // the verbatim tail starts at any byte: element e of it, one 1- or 2-byte load
@@ -913,6 +928,141 @@ __device__ __forceinline__ void filter_tail(const DecodeArgs& a, uint64_t chunk,
     }
     if (mb) {
         for (uint32_t j = blocks_done + tbytes + (uint32_t)lane_d; j < a.filter.mask_stride; j += (uint32_t)DP) mb[j] = 0;
+    }
+}
+
+// ---- linear filter rows.  All arithmetic is on uint32_t: the sum wraps as two's complement does, and lo <= s <= hi, signed, is
+// (s - lo) <= (hi - lo), unsigned, wherever lo <= hi.  A lane keeps the partial sums of the block's 8 rows over its own columns; the
+// group adds them up once a block.  The lag term u x[g - 1] of a sample belongs to the NEXT row's sum: rows 0 .. 6 of a block hand it on
+// inside the block, row 7's waits in one register a lane (`carry`) for the next block's row 0.  A chunk's first row is its own predecessor.
+#ifndef SPRINTZ_LIN_RUN_SHORTCUT
+// 1 (kept): a delta run is one evaluation and len bytes of 0x00 / 0xFF in decode_fast.h; 0: it is replayed block by block
+// (profiles/filter_linear.txt)
+#define SPRINTZ_LIN_RUN_SHORTCUT 1
+#endif
+struct LinearCol { uint32_t w, u; };      // a lane column past the last one: 0, 0 -- it contributes nothing, and no weight is loaded for it
+struct LinearCtx {
+    uint32_t base, span;        // bias - lo, hi - lo
+    uint32_t never, lag;        // lo > hi; a lag term is given (words, not bools: hipcc kept bools of this mode in scratch)
+};
+__device__ __forceinline__ LinearCol linear_col(const DecodeArgs& a, int col, bool genuine)
+{
+    LinearCol c{0u, 0u};
+    if (genuine) {
+        c.w = (uint32_t)a.lin.w[col];
+        if (a.lin.lag) c.u = (uint32_t)a.lin.lag[col];
+    }
+    return c;
+}
+__device__ __forceinline__ LinearCtx linear_ctx(const DecodeArgs& a)
+{
+    return LinearCtx{(uint32_t)a.lin.bias - (uint32_t)a.lin.lo, (uint32_t)a.lin.hi - (uint32_t)a.lin.lo, a.lin.lo > a.lin.hi ? 1u : 0u, a.lin.lag != nullptr ? 1u : 0u};
+}
+// sum: the row's sum without the bias
+__device__ __forceinline__ uint32_t linear_hit(const LinearCtx& c, uint32_t sum) { return (!c.never && sum + c.base <= c.span) ? 1u : 0u; }
+// what chunk `chunk` leaves for the seam pass (geom.h: linear_tmp_stride): the library's own layout
+template <int W> struct LinearSlot {
+    uint32_t* has;
+    typename Elem<W>::U* first;
+    typename Elem<W>::U* last;
+};
+template <int W> __device__ __forceinline__ LinearSlot<W> linear_slot(const DecodeArgs& a, uint64_t chunk, uint32_t D)
+{
+    using U = typename Elem<W>::U;
+    uint8_t* const p = (uint8_t*)a.lin.tmp + chunk * linear_tmp_stride(W / 8, (int)D);
+    return LinearSlot<W>{(uint32_t*)p, (U*)(p + 8), (U*)(p + 8) + D};
+}
+// a column's 8 rows of one block, x(i) (garbage above bit W allowed).  first: the block is the chunk's first -- `self` collects what row 0,
+// as its own predecessor, hands to itself; next: what row 7 hands to the next block's row 0
+template <int W, typename F>
+__device__ __forceinline__ void linear_rows8(const LinearCol& c, F x, uint32_t lag, uint32_t first, uint32_t (&acc)[8], uint32_t& self, uint32_t& next)
+{
+    uint32_t xs[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        xs[i] = x(i) & Elem<W>::MASK;
+        acc[i] += c.w * xs[i];
+    }
+    if (lag) {
+        if (first) self += c.u * xs[0];
+#pragma unroll
+        for (int i = 0; i < 7; i++) acc[i + 1] += c.u * xs[i];
+        next += c.u * xs[7];
+    }
+}
+// behind a block's columns, every lane of the group: gsum(v) is v summed over the group's lanes.  -> the block's mask byte; the partial
+// sums start over and row 7's lag term moves into `carry`
+template <typename S>
+__device__ __forceinline__ uint32_t linear_block(const LinearCtx& c, uint32_t (&acc)[8], uint32_t& first, uint32_t& self, uint32_t& carry, uint32_t& next, S gsum)
+{
+    acc[0] += first ? self : carry;
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        m |= linear_hit(c, gsum(acc[i])) << i;
+        acc[i] = 0;
+    }
+    carry = next;
+    next = 0;
+    self = 0;
+    first = 0;
+    return m;
+}
+// one lane of the group says whether the chunk has a row (a damaged chunk has none the seam pass may use)
+__device__ __forceinline__ void linear_mark(const DecodeArgs& a, uint64_t chunk, uint32_t D, int W, uint32_t has, int lane_d)
+{
+    if (a.lin.lag && lane_d == 0) *(uint32_t*)((uint8_t*)a.lin.tmp + chunk * linear_tmp_stride(W / 8, (int)D)) = has;
+}
+// The verbatim tail, as filter_tail: `remaining` elements at t, row-major from the row behind the chunk's `blocks_done` blocks, 32 rows a
+// trip, then the mask bytes of the slot's rows past the data are zeroed.  The tail's first row takes the last decoded row as its
+// predecessor -- `carry`, each lane's share -- or, in a chunk that is all tail, itself; the rows behind it take the tail's previous row.
+// Then, with a lag term, the chunk's last existing row leaves for the seam pass (the tail's last whole row, or pv: the last decoded one),
+// its first one too where no block held it, and whether it has a row at all.
+template <int W, int CPL>
+__device__ __forceinline__ void linear_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t blocks_done,
+                                            int lane_d, int DP, const LinearCol (&lc)[CPL], const int (&col)[CPL], const bool (&genuine)[CPL],
+                                            const LinearCtx& c, uint32_t carry, const uint32_t (&pv)[CPL], uint32_t& count)
+{
+    using U = typename Elem<W>::U;
+    const uint32_t nfull = remaining / D, tbytes = (nfull + 7u) >> 3;
+    uint8_t* const mb = a.filter.mask ? a.filter.mask + chunk * (uint64_t)a.filter.mask_stride : nullptr;
+    for (uint32_t r0 = 0; r0 < nfull; r0 += 32u) {
+        const uint32_t n = nfull - r0 < 32u ? nfull - r0 : 32u;
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < n; j++) {
+            const uint32_t r = r0 + j;
+            uint32_t p = (r == 0 && blocks_done != 0) ? carry : 0u;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                if (!genuine[k]) continue;
+                const uint32_t x = tail_elem<W>(t, r * D + (uint32_t)col[k]);
+                p += lc[k].w * x;
+                if (c.lag && (r != 0 || blocks_done == 0)) p += lc[k].u * (r != 0 ? tail_elem<W>(t, (r - 1u) * D + (uint32_t)col[k]) : x);
+            }
+            v |= linear_hit(c, group_sum(p, DP)) << j;
+        }
+        count += (uint32_t)__popc(v);
+        if (mb) {
+            for (uint32_t b = (uint32_t)lane_d; b < 4u; b += (uint32_t)DP)
+                if ((r0 >> 3) + b < tbytes) mb[blocks_done + (r0 >> 3) + b] = (uint8_t)(v >> (8u * b));
+        }
+    }
+    if (mb) {
+        for (uint32_t j = blocks_done + tbytes + (uint32_t)lane_d; j < a.filter.mask_stride; j += (uint32_t)DP) mb[j] = 0;
+    }
+    if (c.lag) {
+        const LinearSlot<W> s = linear_slot<W>(a, chunk, D);
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!genuine[k]) continue;
+            if (nfull != 0) {
+                if (blocks_done == 0) s.first[col[k]] = (U)tail_elem<W>(t, (uint32_t)col[k]);
+                s.last[col[k]] = (U)tail_elem<W>(t, (nfull - 1u) * D + (uint32_t)col[k]);
+            } else if (blocks_done != 0) {
+                s.last[col[k]] = (U)(pv[k] & Elem<W>::MASK);
+            }
+        }
+        if (lane_d == 0) *s.has = (nfull != 0 || blocks_done != 0) ? 1u : 0u;
     }
 }
 

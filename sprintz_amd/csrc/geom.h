@@ -30,14 +30,16 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 8 = histogram: per-column value counts of the rows a mask names (or of every row), counted in an LDS table a workgroup, reduce only;
 // 9 = moments: per-window count, sum, sum of squares and sum of products with one reference column of the rows a mask names (or of every row), reduce only;
 // 10 = group-by: per bin of ONE key column's value, the count and the per-column sums of the rows a mask names (or of every row), added up in an LDS table a workgroup, reduce only;
-// 11 = extrema: per-window min / max with the rows they stand in, the first and the last selected row and the count, of the rows a mask names (or of every row), reduce only.
+// 11 = extrema: per-window min / max with the rows they stand in, the first and the last selected row and the count, of the rows a mask names (or of every row), reduce only;
+// 12 = linear filter: one bit per row -- does bias + sum_d w[d] x[g, d] + sum_d u[d] x[g - 1, d], in wrapping 32-bit arithmetic, lie in [lo, hi]? -- and the
+// chunk's count of them, in the filter's mask layout, reduce only.
 // 6 .. 11 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11;
+              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
-    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments || q == kQueryGroupBy || q == kQueryExtrema;
+    return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments || q == kQueryGroupBy || q == kQueryExtrema || q == kQueryLinear;
 }
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB
@@ -45,6 +47,9 @@ constexpr uint32_t kHistMaxCounters = 16384;
 // group-by rows: the entries of one call's table, nbins x (ndims + 1) (SPRINTZ_GBY_MAX_COUNTERS), under the same LDS budget
 constexpr uint32_t kGroupByMaxCounters = 16384;
 constexpr uint32_t kHistFastLdsBudget = 80u * 1024u;
+// linear filter rows with a lag term: the scratch one chunk leaves for the seam pass (decode_ops.h: LinearSlot) -- a word that says whether the
+// chunk has a row, a word of padding, its first and its last existing row in the element type; a multiple of 8 bytes
+constexpr uint64_t linear_tmp_stride(int esz, int D) { return (8ull + 2ull * (uint64_t)D * (uint64_t)esz + 7ull) & ~7ull; }
 
 // sprintz_mi355x_compress_bound: the longest stream a chunk of chunk_len elements can have, a multiple of SPRINTZ_BOUND_ALIGN
 inline size_t compress_bound(int elem_bytes, uint32_t chunk_len, uint16_t ndims)

@@ -93,4 +93,18 @@ __device__ __forceinline__ uint32_t group_or(uint32_t x)
     return t;
 }
 
+// Sum (modulo 2^32) over a group of DP adjacent lanes, the result in every lane of the group: group_or's butterflies with an add.
+// Every lane of the group must be active.
+template <int DP>
+__device__ __forceinline__ uint32_t group_add(uint32_t x)
+{
+    uint32_t t = x + dpp<DPP_QUAD_PERM(1, 0, 3, 2)>(0, x);
+    t += dpp<DPP_QUAD_PERM(2, 3, 0, 1)>(0, t);
+    if constexpr (DP >= 8) t += dpp<DPP_ROW_HALF_MIRROR>(0, t);
+    if constexpr (DP >= 16) t += dpp<DPP_ROW_MIRROR>(0, t);
+    if constexpr (DP >= 32) t += (uint32_t)__shfl_xor((int)t, 16, DP);
+    if constexpr (DP >= 64) t += (uint32_t)__shfl_xor((int)t, 32, DP);
+    return t;
+}
+
 }  // namespace sprintz

@@ -1,7 +1,7 @@
-"""The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, select_rows, aggregate_rows, histogram_rows,
+"""The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
 moments_rows, groupby_rows, extrema_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the first damaged chunk, the default bin shift, bounds and offsets as tensors, and
-the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
+fold of its results into windows over the batch's rows, the first damaged chunk, the default bin shift, bounds and offsets as tensors, the
+linear filter's weights and exactness bound, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
 import torch
@@ -182,6 +182,49 @@ def filter_bounds(lo, hi, mode, ndims, esz, dtype, device):
             if lo[d] is None and hi[d] is None:
                 lo[d], hi[d] = top, 0
     return elem_tensor(lo, ndims, esz, dtype, device, "lo", 0), elem_tensor(hi, ndims, esz, dtype, device, "hi", top)
+
+
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def _weights(v, ndims, name):
+    """a scalar (every column), a sequence of ndims entries, a dict {column: weight} (the others 0) or a tensor of ndims integers ->
+    a list of ndims Python ints"""
+    if torch.is_tensor(v):
+        if v.numel() != ndims or v.dtype.is_floating_point or v.dtype == torch.bool:
+            raise ValueError(f"{name} must hold {ndims} integers")
+        return [int(e) for e in v.reshape(-1).cpu().tolist()]
+    if isinstance(v, dict):
+        vals = [0] * ndims
+        for d, e in v.items():
+            if not 0 <= int(d) < ndims:
+                raise ValueError(f"{name}: column {d} outside 0..{ndims - 1}")
+            vals[int(d)] = int(e)
+        return vals
+    return [int(e) for e in _entries(v, ndims, name)]
+
+
+def linear_terms(weights, lag_weights, bias, lo, hi, ndims, esz, device):
+    """filter_linear's arguments -> (w, u, bias, lo, hi): w and u contiguous int32 tensors [ndims] on `device` (u None where
+    lag_weights is None: no lag term), bias / lo / hi Python ints that fit int32.  weights / lag_weights: a scalar (every column), a
+    sequence of ndims entries, a dict {column: weight} or a tensor of ndims integers.  lo / hi of None are the open ends of int32.
+    The kernel's sum wraps modulo 2^32; it is the exact integer wherever
+        B = |bias| + (2^W - 1) sum_d (|w[d]| + |u[d]|) < 2^31,     W = 8 esz,
+    so a form with B >= 2^31 is refused, as is a bound that does not fit int32."""
+    w = _weights(weights, ndims, "weights")
+    u = None if lag_weights is None else _weights(lag_weights, ndims, "lag_weights")
+    bias = int(bias)
+    lo = INT32_MIN if lo is None else int(lo)
+    hi = INT32_MAX if hi is None else int(hi)
+    for name, v in (("lo", lo), ("hi", hi)):
+        if not INT32_MIN <= v <= INT32_MAX:
+            raise ValueError(f"{name} = {v} does not fit int32")
+    B = abs(bias) + ((1 << (8 * esz)) - 1) * (sum(abs(e) for e in w) + sum(abs(e) for e in u or ()))
+    if B >= 1 << 31:
+        raise ValueError(f"the linear form can reach {B} in magnitude: |bias| + (2^{8 * esz} - 1) sum(|w| + |u|) must stay below 2^31, "
+                         "or the 32-bit sum wraps")
+    as_t = lambda vals: torch.from_numpy(np.array(vals, np.int32)).to(device)      # noqa: E731
+    return as_t(w), None if u is None else as_t(u), bias, lo, hi
 
 
 def derive_moments(out, ops, ref, ddof):
