@@ -149,6 +149,10 @@ const char* sprintz_mi355x_last_error(void);     /* thread-local, never NULL; de
 #define SPRINTZ_OPT_BLK_CHUNKS 11
 #define SPRINTZ_OPT_BLK_KERNELS 12
 int sprintz_mi355x_set_option(int option, int value);
+/* The value an option has now -- what the environment gave it or the last successful sprintz_mi355x_set_option -- or SPRINTZ_E_INVALID for an
+ * unknown option (no option's value is negative).  What holds only under the options it was built with, such as a zone map and
+ * SPRINTZ_OPT_REF_DECODER_QUIRK, records them from here. */
+int sprintz_mi355x_get_option(int option);
 
 /* Which kernel family served a call (per process, atomic).  Every family writes the same bytes as every other, so the output of a call
  * cannot tell which one ran; these counters can.  A family is one of the alternatives a launch site chooses between: by shape,
@@ -539,6 +543,76 @@ uint64_t sprintz_mi355x_filter_linear_tmp_bytes(int elem_bytes, uint64_t nchunks
  * NULL pointers with nchunks > 0, d_bases / d_ids not aligned to 8 bytes.  nchunks == 0 returns 0 and launches nothing. */
 int sprintz_mi355x_filter_row_ids(const uint8_t* d_mask, const uint64_t* d_bases, uint64_t nchunks, uint32_t chunk_len,
                                   uint16_t ndims, uint64_t* d_ids, uint64_t capacity, void* hip_stream);
+/* Zone maps: skip the chunks a filter's bounds already decide.  A filter decodes every chunk, however selective it is; a chunk's
+ * per-column minimum and maximum prove, for most range predicates on slowly drifting series, that none of its rows can match or that
+ * all of them do.  Build the map once (zone_map), then for every query: prune (classify the chunks and compact the offsets of those that
+ * still need the decoder), run sprintz_mi355x_filter_rows / _filter_linear on (d_comp, d_surv_offsets, n') into compact outputs, and
+ * expand them into the filter's own layout.  The result is bit for bit the unpruned call's.  The compacted offsets are a valid container
+ * for every decoder: a chunk's stream is read as offsets[c+1] - offsets[c] bytes, the header allows padding behind a stream, and the
+ * skipped chunks are that padding.
+ *
+ * zone_map: for chunk c and column d, d_zmin / d_zmax [nchunks][ndims] (element type) take the unsigned minimum and maximum over every
+ * element sprintz_mi355x_decompress_batch would write for the chunk (the verbatim tail and a partial last row count; a chunk without
+ * elements holds the identities, min 0xFF / 0xFFFF and max 0), and d_zlen[c] (int64) the chunk's element count, or < 0 for a damaged
+ * chunk, whose entries are unspecified.  It is exactly sprintz_mi355x_query_windows with one window a chunk (window_rows = the rows of
+ * a chunk slot rounded up to 8), ops MIN | MAX and d_rets = d_zlen -- a contract of its own so that a later encoder can fill it while
+ * it compresses.  A zone map describes the container as it was when the map was built, under the flags (SPRINTZ_QUERY_GENERAL_LAYOUT)
+ * and the SPRINTZ_OPT_REF_DECODER_QUIRK state it was built with: pruning a changed container, or under another layout or quirk state,
+ * is the caller's error and goes unnoticed.  Returns as query_windows does, and SPRINTZ_E_INVALID for a NULL output or a d_zlen not
+ * aligned to 8 bytes -- all before the device is touched.
+ *
+ * zone_prune_box (filter_rows' predicate: d_lo, d_hi, mode) and zone_prune_linear (filter_linear's without a lag term: d_weights, bias,
+ * lo, hi; chunk_len % ndims == 0) share one output set:
+ *   d_class[nchunks] uint8   : 0 NONE -- no row of the chunk matches; 1 ALL -- every existing row matches; 2 DECODE -- the decoder must look.
+ *   d_pos[nchunks + 1] uint64: the number of DECODE chunks in front of chunk c; d_pos[nchunks] = n', the survivors.
+ *   d_surv_offsets[nchunks + 1] uint64: entry d_pos[c] = d_offsets[c] for every DECODE chunk, ascending; entries n' .. nchunks =
+ *                              d_offsets[nchunks], so (d_comp, d_surv_offsets, n') is a container of the survivors.
+ * With rows_c = zlen[c] / ndims: zlen[c] < 0 is DECODE (its place among the survivors keeps every other chunk's place; expand reports it with the map's code); else rows_c == 0 is NONE; else
+ *   box, unsigned and inclusive: column d is DISJOINT if lo[d] > hi[d], zmax < lo[d] or zmin > hi[d], and INSIDE if lo[d] <= zmin and
+ *     zmax <= hi[d].  SPRINTZ_FILTER_ALL: NONE if some column is disjoint, else ALL if every column is inside.  SPRINTZ_FILTER_ANY: ALL if
+ *     some column is inside, else NONE if every column is disjoint.  Otherwise DECODE.
+ *   linear: in 64-bit arithmetic smin = bias + sum_d (w[d] >= 0 ? w[d] zmin[d] : w[d] zmax[d]) and smax its mirror.  A range that leaves
+ *     int32 is DECODE (filter_linear's 32-bit sum may wrap there, and only the decoder knows what it yields); else NONE if lo > hi,
+ *     smax < lo or smin > hi; ALL if lo <= smin and smax <= hi; otherwise DECODE.
+ * THE 4 GiB RULE: the decoders address the streams of one wavefront as 32-bit offsets from the wavefront's first stream, and compaction
+ * can put distant chunks into one wavefront: if d_offsets[nchunks] - d_offsets[0] >= 0xf0000000, every chunk is DECODE and the call
+ * degrades to the unpruned one.
+ * The prune calls read the bounds, the weights and the zone map on the device and never read the container; they do not synchronise
+ * and do not allocate; the survivors' order is the batch's, and no atomic decides a place.  d_tmp: sprintz_mi355x_zone_prune_tmp_bytes(nchunks)
+ * bytes of device scratch, aligned to 8 (0 for nchunks == 0).  Classify, the size scan (one launch up to 16 384 chunks, three above) and compact on the stream: three or
+ * five launches, none of which counts under a kernel family.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for elem_bytes other than 1 or 2, ndims == 0, chunk_len outside 1..2^30, an
+ * unknown mode, a NULL pointer, d_zmin / d_zmax / d_lo / d_hi not aligned to the element size, d_weights not to 4 bytes, d_offsets / d_zlen
+ * / d_pos / d_surv_offsets / d_tmp not to 8, and for zone_prune_linear chunk_len % ndims != 0; SPRINTZ_E_UNSUPPORTED for more than 512
+ * columns.  nchunks == 0 returns 0 and launches nothing.
+ *
+ * zone_expand: the compact results of a filter run on (d_comp, d_surv_offsets, n') -- d_cmask [n'][MB], d_ccounts [n'], d_crets [n'], MB =
+ * ceil(ceil(chunk_len / ndims) / 8) -- into filter_rows' outputs d_mask [nchunks][MB], d_counts [nchunks], d_rets [nchunks].  A DECODE chunk
+ * copies slot d_pos[c] -- but its ret is zlen[c] where zlen[c] < 0, its mask bytes and count then unspecified as in filter_rows: a truncated
+ * stream is told by its length alone, and among the survivors a chunk's length runs on over the skipped chunks behind it, so the
+ * decoder's own verdict on a chunk the map found damaged is not to be trusted; a NONE chunk gets mask 0, count 0, ret zlen[c]; an ALL chunk the bits of rows r < rows_c set and the rest 0 (the
+ * padding bits of its last mask byte included), count rows_c, ret zlen[c].  Every byte of every output is written, each by one writer.
+ * d_mask or d_counts may be NULL, not both (then d_cmask / d_ccounts is not read); d_rets is optional (then d_crets is not read); the
+ * compact inputs may be NULL where no chunk is DECODE.  One launch, any MB >= 1, any alignment of the masks.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for ndims == 0, chunk_len outside 1..2^30, a NULL d_class / d_pos / d_zlen, both
+ * outputs NULL, d_pos / d_zlen / d_crets / d_rets not aligned to 8 bytes, d_ccounts / d_counts not to 4.  nchunks == 0 returns 0 and
+ * launches nothing. */
+#define SPRINTZ_ZONE_NONE 0u
+#define SPRINTZ_ZONE_ALL 1u
+#define SPRINTZ_ZONE_DECODE 2u
+int sprintz_mi355x_zone_map(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks, uint32_t chunk_len,
+                            uint16_t ndims, uint32_t flags, void* d_zmin, void* d_zmax, int64_t* d_zlen, void* hip_stream);
+size_t sprintz_mi355x_zone_prune_tmp_bytes(uint64_t nchunks);
+int sprintz_mi355x_zone_prune_box(int elem_bytes, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, const uint64_t* d_offsets,
+                                  const void* d_zmin, const void* d_zmax, const int64_t* d_zlen, const void* d_lo, const void* d_hi,
+                                  uint32_t mode, uint8_t* d_class, uint64_t* d_pos, uint64_t* d_surv_offsets, void* d_tmp, void* hip_stream);
+int sprintz_mi355x_zone_prune_linear(int elem_bytes, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, const uint64_t* d_offsets,
+                                     const void* d_zmin, const void* d_zmax, const int64_t* d_zlen, const int32_t* d_weights, int32_t bias,
+                                     int32_t lo, int32_t hi, uint8_t* d_class, uint64_t* d_pos, uint64_t* d_surv_offsets, void* d_tmp,
+                                     void* hip_stream);
+int sprintz_mi355x_zone_expand(uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, const uint8_t* d_class, const uint64_t* d_pos,
+                               const int64_t* d_zlen, const uint8_t* d_cmask, const uint32_t* d_ccounts, const int64_t* d_crets,
+                               uint8_t* d_mask, uint32_t* d_counts, int64_t* d_rets, void* hip_stream);
 /* Gather rows: N row ranges of a compressed batch, decoded in one launch into a dense [N][rows][ndims] array -- the read
  * the chunked format exists for ("so that queries over arbitrary time intervals are cheap", communicate/intro.tex:55).
  *

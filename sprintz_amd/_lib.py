@@ -58,6 +58,14 @@ if abi_version() < ABI_REQUIRED:      # a stale build would otherwise die below 
 _last_error = _sig("sprintz_mi355x_last_error", C.c_char_p)
 OPT_NO_FAST, OPT_CHUNKS_PER_GROUP, OPT_DENSE_MODE, OPT_HUF0_BIG_BATCH, OPT_SPLIT_LANES, OPT_ENC_PAIR, OPT_HOST_WAIT, OPT_LAT_CHUNKS, OPT_HOST_STREAMS, OPT_REF_DECODER_QUIRK, OPT_HUF0_SYNC_CHUNKS, OPT_BLK_CHUNKS, OPT_BLK_KERNELS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 set_option = _sig("sprintz_mi355x_set_option", _i, _i, _i)
+get_option = _sig("sprintz_mi355x_get_option", _i, _i)
+
+
+def ref_decoder_quirk():
+    """the SPRINTZ_OPT_REF_DECODER_QUIRK state this process decodes under (0 / 1), read from the library: a zone map holds for the state it
+    was built under (ChunkedCodec.zone_map records it)"""
+    return check(get_option(OPT_REF_DECODER_QUIRK))
+
 
 # which kernel family served a call: per-process counters behind every launch site (include/sprintz_mi355x.h, SPRINTZ_KF_*)
 _dispatch_counts = _sig("sprintz_mi355x_dispatch_counts", _i, C.POINTER(C.c_uint64), _i)
@@ -134,6 +142,16 @@ filter_row_ids = _sig("sprintz_mi355x_filter_row_ids", _i, _vp, _vp, _u64, _u32,
 # a row mask from a linear form over a row and its predecessor, tested against an interval (include/sprintz_mi355x.h)
 filter_linear = _sig("sprintz_mi355x_filter_linear", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _u32, _vp, _vp, _vp, _vp, _vp)
 filter_linear_tmp_bytes = _sig("sprintz_mi355x_filter_linear_tmp_bytes", _u64, _i, _u64, _u16)
+# zone maps: a chunk's per-column min / max and element count, the chunks a filter's bounds leave to the decoder, and a compact filter
+# result back in filter_rows' layout (include/sprintz_mi355x.h)
+ZONE_NONE, ZONE_ALL, ZONE_DECODE = 0, 1, 2
+ZONE_SPAN_LIMIT = 0xF0000000
+zone_map = _sig("sprintz_mi355x_zone_map", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _u32, _vp, _vp, _vp, _vp)
+zone_prune_tmp_bytes = _sig("sprintz_mi355x_zone_prune_tmp_bytes", _sz, _u64)
+zone_prune_box = _sig("sprintz_mi355x_zone_prune_box", _i, _i, _u64, _u32, _u16, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp)
+zone_prune_linear = _sig("sprintz_mi355x_zone_prune_linear", _i, _i, _u64, _u32, _u16, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                         _vp, _vp, _vp, _vp, _vp)
+zone_expand = _sig("sprintz_mi355x_zone_expand", _i, _u64, _u32, _u16, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 # the rows a mask names, each chunk decoded once, packed densely behind the chunk's base (include/sprintz_mi355x.h)
 select_rows = _sig("sprintz_mi355x_select_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
 # per-window min / max / sum / count of the rows a mask names (include/sprintz_mi355x.h)
@@ -200,7 +218,7 @@ compress_chunked_host = _sig("sprintz_mi355x_compress_chunked_host", _i64, _i, _
 decompress_chunked_host = _sig("sprintz_mi355x_decompress_chunked_host", _i64, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp)
 
 EXPORTED_SYMBOLS = [
-    "sprintz_mi355x_abi_version", "sprintz_mi355x_last_error", "sprintz_mi355x_set_option",
+    "sprintz_mi355x_abi_version", "sprintz_mi355x_last_error", "sprintz_mi355x_set_option", "sprintz_mi355x_get_option",
     "sprintz_mi355x_dispatch_counts", "sprintz_mi355x_dispatch_name",
     "sprintz_mi355x_compress_delta_8b", "sprintz_mi355x_compress_xff_8b",
     "sprintz_mi355x_compress_delta_16b", "sprintz_mi355x_compress_xff_16b",
@@ -223,6 +241,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_huf0_exact_tmp_bytes", "sprintz_mi355x_huf0_compress_batch_exact",
     "sprintz_mi355x_query_batch", "sprintz_mi355x_query_reduce", "sprintz_mi355x_query_windows",
     "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids", "sprintz_mi355x_filter_linear", "sprintz_mi355x_filter_linear_tmp_bytes", "sprintz_mi355x_select_rows",
+    "sprintz_mi355x_zone_map", "sprintz_mi355x_zone_prune_tmp_bytes", "sprintz_mi355x_zone_prune_box", "sprintz_mi355x_zone_prune_linear", "sprintz_mi355x_zone_expand",
     "sprintz_mi355x_aggregate_rows", "sprintz_mi355x_histogram_rows", "sprintz_mi355x_moments_rows", "sprintz_mi355x_groupby_rows", "sprintz_mi355x_extrema_rows",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",

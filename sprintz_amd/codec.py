@@ -25,6 +25,11 @@ _CODEC_ID = {"delta": _lib.CODEC_DELTA, "xff": _lib.CODEC_XFF,
              "xff_norle": _lib.CODEC_XFF_NORLE}                                             # sprintz_xff.cpp:35-626, 8-bit only
 
 
+def _ptr(t):
+    """a tensor's device address, or NULL for None"""
+    return t.data_ptr() if t is not None else None
+
+
 def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -108,6 +113,17 @@ class CompressedBatch:
         return int(self.sizes.to("cpu", dtype=__import__("torch").int64).sum().item())
 
 
+@dataclass
+class ZoneMap:
+    """A batch's zone map (ChunkedCodec.zone_map): every chunk's per-column minimum and maximum and its element count.  It describes the
+    container as it was when the map was built, under the layout flag and the SPRINTZ_OPT_REF_DECODER_QUIRK state recorded here."""
+    min: "torch.Tensor"        # codec dtype [nchunks, ndims], device  # noqa: A003
+    max: "torch.Tensor"        # codec dtype [nchunks, ndims], device  # noqa: A003
+    len: "torch.Tensor"        # int64 [nchunks], device: elements, or < 0 for a damaged chunk  # noqa: A003
+    general_layout: bool
+    quirk: int
+
+
 class ChunkedCodec:
     """Batched Sprintz codec on one GPU.
 
@@ -133,6 +149,7 @@ class ChunkedCodec:
         self.dtype = torch.uint8 if elem_bytes == 1 else torch.uint16
         self.slot_stride = int(_lib.compress_bound(elem_bytes, self.chunk_len, self.ndims))
         self._ws = {}
+        self.last_prune = None             # what the last filter call with zones= pruned (filter_rows)
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -410,7 +427,61 @@ class ChunkedCodec:
         """lo / hi: a scalar, a sequence of ndims entries (None = open end) or a device tensor -> two contiguous device tensors [ndims]"""
         return rowops.filter_bounds(lo, hi, mode, self.ndims, self.esz, self.dtype, self.device)
 
-    def filter_rows(self, batch, lo, hi, mode="all", general_layout=False, ids=False, check=True):
+    def zone_map(self, batch, general_layout=False):
+        """The batch's zone map: every chunk's per-column minimum and maximum and its element count, in one launch (query_windows with one
+        window a chunk) -> ZoneMap.  Build it once and pass it as zones= to filter_rows, filter_linear and the *_where operations: the
+        chunks whose bounds already decide the predicate are then not decoded.  The map holds for the container as it is now, for this
+        general_layout and for the SPRINTZ_OPT_REF_DECODER_QUIRK state of the moment; a damaged chunk is recorded (len < 0), not raised."""
+        torch = self.torch
+        n, D = batch.nchunks, self.ndims
+        zmin = torch.empty((n, D), dtype=self.dtype, device=self.device)
+        zmax = torch.empty((n, D), dtype=self.dtype, device=self.device)
+        zlen = torch.empty(n, dtype=torch.int64, device=self.device)
+        with self._on():
+            _lib.check(_lib.zone_map(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n, self.chunk_len, D,
+                                     self._general(general_layout), zmin.data_ptr(), zmax.data_ptr(), zlen.data_ptr(), self._stream()))
+        return ZoneMap(zmin, zmax, zlen, bool(general_layout), _lib.ref_decoder_quirk())
+
+    def _filter_launch(self, op, batch, MB, zones, general_layout, check, prune, launch):
+        """A filter's outputs {"mask", "counts"} in batch order, pruned by `zones` where they are given.  launch(offsets_ptr, n, mask, counts,
+        rets) is the filter's entry point on a container of n chunks; prune(cls, pos, surv, tmp) the prune call of its predicate, or None
+        where the predicate cannot be pruned: the zones are then checked and not used.  self.last_prune is what THIS call pruned.  With zones:
+        prune, read the survivor count n' (8 bytes: the call's one synchronisation), then the plain call if every chunk survived, else the
+        filter on the survivors' offsets into compact buffers (nothing if n' == 0) and the expand launch."""
+        torch = self.torch
+        n = batch.nchunks
+        mask = torch.empty((n, MB), dtype=torch.uint8, device=self.device)
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        rets = self._rets(n, check)
+        self.last_prune = None
+        if zones is not None:
+            rowops.check_zones(zones, n, self.ndims, general_layout, _lib.ref_decoder_quirk())
+        with self._on():
+            ns = n
+            if zones is not None and prune is not None and n:
+                cls = torch.empty(n, dtype=torch.uint8, device=self.device)
+                pos = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                surv = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                tmp = torch.empty(_lib.zone_prune_tmp_bytes(n) // 8, dtype=torch.int64, device=self.device)
+                _lib.check(prune(cls, pos, surv, tmp))
+                ns = int(pos[n].item())
+                self.last_prune = {"nchunks": n, "survivors": ns, "class": cls}
+            if ns == n:
+                _lib.check(launch(batch.offsets.data_ptr(), n, mask, counts, rets))
+            else:
+                cmask = ccounts = crets = None
+                if ns:
+                    cmask = torch.empty((ns, MB), dtype=torch.uint8, device=self.device)
+                    ccounts = torch.empty(ns, dtype=torch.int32, device=self.device)
+                    crets = self._rets(ns, check)
+                    _lib.check(launch(surv.data_ptr(), ns, cmask, ccounts, crets))
+                _lib.check(_lib.zone_expand(n, self.chunk_len, self.ndims, cls.data_ptr(), pos.data_ptr(), zones.len.data_ptr(), _ptr(cmask),
+                                            _ptr(ccounts), _ptr(crets), mask.data_ptr(), counts.data_ptr(), _ptr(rets), self._stream()))
+        if check:
+            rowops.raise_damaged(op, rets, n, _lib.SprintzError)
+        return {"mask": mask, "counts": counts}
+
+    def filter_rows(self, batch, lo, hi, mode="all", general_layout=False, ids=False, check=True, zones=None):
         """Which rows satisfy a condition on their columns, straight from the compressed batch (one launch, no sample leaves the chip).
 
         A row matches under mode="all" if every column d has lo[d] <= x <= hi[d] (unsigned, inclusive), under mode="any" if some
@@ -422,27 +493,34 @@ class ChunkedCodec:
         ids=True adds "ids": int64 [total], the matching batch rows in ascending order (row g is row g % R of chunk g // R, R =
         chunk_len / ndims: chunk_len must be a multiple of ndims) -- what gather_rows takes as starts.
         check=True raises SprintzError naming the first damaged chunk.  ids=True checks too, whatever check says: a damaged chunk's
-        count is unspecified, and it would size the ids and place every later chunk's."""
-        torch = self.torch
+        count is unspecified, and it would size the ids and place every later chunk's.
+        zones: the batch's ZoneMap (zone_map).  The results are the same bit for bit; the chunks whose minimum and maximum already decide
+        the predicate -- no row can match, or every row does -- are not decoded: a prune launch classifies the chunks, the filter runs on
+        the survivors alone and an expand launch puts its results back in batch order.  That costs one 8-byte read of the survivor
+        count, the call's single synchronisation (check=False does not avoid it).  A damaged chunk is named by its batch number, as
+        without zones.  A map built under another general_layout or SPRINTZ_OPT_REF_DECODER_QUIRK state is a ValueError.
+        self.last_prune then holds {"nchunks": n, "survivors": n', "class": uint8 [n] of 0 NONE / 1 ALL / 2 DECODE}; after a filter call that
+        pruned nothing -- no zones, an empty batch, filter_linear with a lag term -- it is None."""
         check = check or ids
         if mode not in ("all", "any"):
             raise ValueError("mode must be 'all' or 'any'")
-        D, n = self.ndims, batch.nchunks
+        D = self.ndims
         R, MB = rowops.chunk_rows(self.chunk_len, D, "ids" if ids else None, verb="need")
         lo_t, hi_t = self._filter_bounds(lo, hi, mode)
-        mask = torch.empty((n, MB), dtype=torch.uint8, device=self.device)
-        counts = torch.empty(n, dtype=torch.int32, device=self.device)
-        rets = self._rets(n, check)
-        with self._on():
-            _lib.check(_lib.filter_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
-                                        self.chunk_len, D, lo_t.data_ptr(), hi_t.data_ptr(),
-                                        _lib.FILTER_ALL if mode == "all" else _lib.FILTER_ANY, self._general(general_layout),
-                                        mask.data_ptr(), counts.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
-        if check:
-            rowops.raise_damaged("filter_rows", rets, n, _lib.SprintzError)
-        res = {"mask": mask, "counts": counts}
+        cid, flags, fmode, st = _CODEC_ID[self.codec], self._general(general_layout), _lib.FILTER_ALL if mode == "all" else _lib.FILTER_ANY, self._stream()
+
+        def launch(offsets, n, mask, counts, rets):
+            return _lib.filter_rows(cid, self.esz, batch.data.data_ptr(), offsets, n, self.chunk_len, D, lo_t.data_ptr(), hi_t.data_ptr(), fmode,
+                                    flags, mask.data_ptr(), counts.data_ptr(), _ptr(rets), st)
+
+        def prune(cls, pos, surv, tmp):
+            return _lib.zone_prune_box(self.esz, batch.nchunks, self.chunk_len, D, batch.offsets.data_ptr(), zones.min.data_ptr(),
+                                       zones.max.data_ptr(), zones.len.data_ptr(), lo_t.data_ptr(), hi_t.data_ptr(), fmode, cls.data_ptr(),
+                                       pos.data_ptr(), surv.data_ptr(), tmp.data_ptr(), st)
+
+        res = self._filter_launch("filter_rows", batch, MB, zones, general_layout, check, prune, launch)
         if ids:
-            res["ids"] = self._mask_ids(mask, counts)
+            res["ids"] = self._mask_ids(res["mask"], res["counts"])
         return res
 
     def _mask_ids(self, mask, counts):
@@ -459,7 +537,7 @@ class ChunkedCodec:
                 _lib.check(_lib.filter_row_ids(mask.data_ptr(), bases.data_ptr(), n, self.chunk_len, self.ndims, out.data_ptr(), total, self._stream()))
         return out
 
-    def filter_linear(self, batch, weights, lo=None, hi=None, lag_weights=None, bias=0, general_layout=False, ids=False, check=True):
+    def filter_linear(self, batch, weights, lo=None, hi=None, lag_weights=None, bias=0, general_layout=False, ids=False, check=True, zones=None):
         """Which rows satisfy a condition that RELATES columns, or a row to the row in front of it -- filter_rows' second kind of
         predicate, straight from the compressed batch.  Batch row g (row g % R of chunk g // R, R = chunk_len / ndims: chunk_len must be
         a multiple of ndims) matches if
@@ -476,26 +554,31 @@ class ChunkedCodec:
             m = codec.filter_linear(batch, {0: 1, 1: -1}, lo=1)["mask"]                  # WHERE a > b
             rows = codec.select_rows(batch, m & codec.filter_rows(batch, lo, hi)["mask"])["rows"]
 
-        check=True raises SprintzError naming the first damaged chunk; ids=True checks too (as filter_rows)."""
+        check=True raises SprintzError naming the first damaged chunk; ids=True checks too (as filter_rows).
+        zones: the batch's ZoneMap, as in filter_rows -- the form's range over a chunk follows from the chunk's minima and maxima, and a chunk
+        whose range lies outside [lo, hi], or inside it, is not decoded; the results are the same bit for bit.  With lag_weights the
+        zones are checked as always (a map of another batch, layout or quirk state is a ValueError) and then ignored, and the call runs unpruned: the seam pass takes each chunk's predecessor from its neighbour in launch order,
+        and a launch on the survivors alone has other neighbours."""
         torch = self.torch
         check = check or ids
         D, n = self.ndims, batch.nchunks
         R, MB = rowops.chunk_rows(self.chunk_len, D, "filter_linear")
         w, u, bias, lo, hi = rowops.linear_terms(weights, lag_weights, bias, lo, hi, D, self.esz, self.device)
-        mask = torch.empty((n, MB), dtype=torch.uint8, device=self.device)
-        counts = torch.empty(n, dtype=torch.int32, device=self.device)
-        rets = self._rets(n, check)
         tmp = torch.empty(max(_lib.filter_linear_tmp_bytes(self.esz, n, D) // 8, 1), dtype=torch.int64, device=self.device) if u is not None else None
-        with self._on():
-            _lib.check(_lib.filter_linear(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
-                                          self.chunk_len, D, w.data_ptr(), u.data_ptr() if u is not None else None, bias, lo, hi,
-                                          self._general(general_layout), tmp.data_ptr() if tmp is not None else None,
-                                          mask.data_ptr(), counts.data_ptr(), rets.data_ptr() if rets is not None else None, self._stream()))
-        if check:
-            rowops.raise_damaged("filter_linear", rets, n, _lib.SprintzError)
-        res = {"mask": mask, "counts": counts}
+        cid, flags, st = _CODEC_ID[self.codec], self._general(general_layout), self._stream()
+
+        def launch(offsets, n, mask, counts, rets):
+            return _lib.filter_linear(cid, self.esz, batch.data.data_ptr(), offsets, n, self.chunk_len, D, w.data_ptr(), _ptr(u), bias, lo, hi,
+                                      flags, _ptr(tmp), mask.data_ptr(), counts.data_ptr(), _ptr(rets), st)
+
+        def prune(cls, pos, surv, ztmp):                    # (no lag term)
+            return _lib.zone_prune_linear(self.esz, batch.nchunks, self.chunk_len, D, batch.offsets.data_ptr(), zones.min.data_ptr(),
+                                          zones.max.data_ptr(), zones.len.data_ptr(), w.data_ptr(), bias, lo, hi, cls.data_ptr(),
+                                          pos.data_ptr(), surv.data_ptr(), ztmp.data_ptr(), st)
+
+        res = self._filter_launch("filter_linear", batch, MB, zones, general_layout, check, prune if u is None else None, launch)
         if ids:
-            res["ids"] = self._mask_ids(mask, counts)
+            res["ids"] = self._mask_ids(res["mask"], res["counts"])
         return res
 
     def filter_change(self, batch, col, lo=None, hi=None, **kw):
@@ -507,11 +590,11 @@ class ChunkedCodec:
             events = codec.filter_change(batch, 0, lo=1, ids=True)["ids"]      # ... or the rows where the state went up, by number"""
         return self.filter_linear(batch, {int(col): 1}, lo=lo, hi=hi, lag_weights={int(col): -1}, **kw)
 
-    def _where(self, op, method, batch, lo, hi, mode, /, counts=False, **kw):
+    def _where(self, op, method, batch, lo, hi, mode, /, counts=False, zones=None, **kw):
         """filter_rows (lo / hi / mode), then `method` on its mask (counts=True: and its counts).  Whole rows are asked for before the
-        filter launches."""
+        filter launches.  zones: the batch's ZoneMap for the filter step -- that half alone is pruned, `method` decodes every chunk."""
         rowops.chunk_rows(self.chunk_len, self.ndims, op)
-        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True)
+        f = self.filter_rows(batch, lo, hi, mode=mode, general_layout=kw.get("general_layout", False), check=True, zones=zones)
         if counts:
             kw["counts"] = f["counts"]
         return method(batch, mask=f["mask"], **kw)
@@ -562,11 +645,12 @@ class ChunkedCodec:
             rowops.raise_damaged("select_rows", rets, n, _lib.SprintzError)
         return res
 
-    def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False):
+    def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False, zones=None):
         """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
         filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.
-        -> {"rows": [total, ndims], and with ids=True "ids": int64 [total]}, in ascending batch row order."""
-        return self._where("where", self.select_rows, batch, lo, hi, mode, counts=True, ids=ids, general_layout=general_layout)
+        -> {"rows": [total, ndims], and with ids=True "ids": int64 [total]}, in ascending batch row order.
+        zones: the batch's ZoneMap (zone_map) for the filter step -- that half alone is pruned, the select launch decodes every chunk."""
+        return self._where("where", self.select_rows, batch, lo, hi, mode, counts=True, ids=ids, general_layout=general_layout, zones=zones)
 
     def aggregate_rows(self, batch, mask, window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False, per_chunk=False,
                        check=True):
@@ -619,11 +703,12 @@ class ChunkedCodec:
             out["mean"] = out["sum"].to(torch.float64) / out["count"].to(torch.float64).unsqueeze(-1)
         return {k: v for k, v in out.items() if k in ops}
 
-    def aggregate_where(self, batch, lo, hi, mode="all", window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False):
+    def aggregate_where(self, batch, lo, hi, mode="all", window_rows=None, ops=("count", "min", "max", "sum"), general_layout=False, zones=None):
         """SELECT count(*), min(x), max(x), sum(x) WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and aggregate_rows
-        on its mask -- two decode-speed launches; the batch is never materialised.  -> aggregate_rows' global windows."""
+        on its mask -- two decode-speed launches; the batch is never materialised.  -> aggregate_rows' global windows.
+        zones: the batch's ZoneMap (zone_map) for the filter step -- that half alone is pruned, the aggregate launch decodes every chunk."""
         return self._where("aggregate_where", self.aggregate_rows, batch, lo, hi, mode, window_rows=window_rows, ops=ops,
-                           general_layout=general_layout)
+                           general_layout=general_layout, zones=zones)
 
     def histogram_rows(self, batch, mask=None, nbins=256, lo=None, shift=None, chunks_per_hist=0, general_layout=False, check=True):
         """Per-column value counts of the rows a mask names, fused into the decode (one launch; only the counts leave the chip).
@@ -662,7 +747,7 @@ class ChunkedCodec:
     def histogram_where(self, batch, lo, hi, mode="all", **kw):
         """The distribution of the rows that satisfy a condition: filter_rows (its lo / hi / mode) and histogram_rows on its mask -- two
         decode-speed launches; the batch is never materialised.  kw: histogram_rows' other arguments (nbins, its own lo as hist_lo,
-        shift, chunks_per_hist, general_layout)."""
+        shift, chunks_per_hist, general_layout) and zones, the batch's ZoneMap (zone_map) for the filter step -- that half alone is pruned."""
         if "hist_lo" in kw:
             kw["lo"] = kw.pop("hist_lo")
         return self._where("histogram_where", self.histogram_rows, batch, lo, hi, mode, **kw)
@@ -799,7 +884,8 @@ class ChunkedCodec:
 
     def moments_where(self, batch, lo, hi, mode="all", **kw):
         """SELECT count(*), sum(x), var(x), corr(x, y), ... WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and
-        moments_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: moments_rows' other arguments."""
+        moments_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: moments_rows' other arguments, and zones, the batch's
+        ZoneMap (zone_map) for the filter step -- that half alone is pruned."""
         return self._where("moments_where", self.moments_rows, batch, lo, hi, mode, **kw)
 
     _EXT_OPS = ("min", "max", "argmin", "argmax", "first", "last", "rows", "count")
@@ -869,7 +955,8 @@ class ChunkedCodec:
 
     def extrema_where(self, batch, lo, hi, mode="all", **kw):
         """SELECT min(x), argmin(x), max(x), argmax(x), ... WHERE <bounds> [GROUP BY window]: filter_rows (its lo / hi / mode) and
-        extrema_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: extrema_rows' other arguments."""
+        extrema_rows on its mask -- two decode-speed launches; the batch is never materialised.  kw: extrema_rows' other arguments, and zones, the batch's
+        ZoneMap (zone_map) for the filter step -- that half alone is pruned."""
         return self._where("extrema_where", self.extrema_rows, batch, lo, hi, mode, **kw)
 
     def m4(self, batch, window_rows, mask=None):
@@ -934,7 +1021,8 @@ class ChunkedCodec:
 
     def groupby_where(self, batch, lo, hi, mode="all", **kw):
         """SELECT bin(x_key), count(*), sum(x) WHERE <bounds> GROUP BY bin(x_key): filter_rows (its lo / hi / mode) and groupby_rows on its
-        mask -- two decode-speed launches; the batch is never materialised.  kw: groupby_rows' other arguments (key among them)."""
+        mask -- two decode-speed launches; the batch is never materialised.  kw: groupby_rows' other arguments (key among them), and zones, the
+        batch's ZoneMap (zone_map) for the filter step -- that half alone is pruned."""
         return self._where("groupby_where", self.groupby_rows, batch, lo, hi, mode, **kw)
 
     def corr(self, batch, cols=None, mask=None, window_rows=None):

@@ -1439,6 +1439,27 @@ int sprintz_mi355x_set_option(int option, int value)
     }
     return fail(SPRINTZ_E_INVALID, "unknown option");
 }
+int sprintz_mi355x_get_option(int option)
+{
+    const Process& p = process();
+    auto ld = [](const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); };
+    switch (option) {
+        case SPRINTZ_OPT_NO_FAST: return ld(p.no_fast);
+        case SPRINTZ_OPT_CHUNKS_PER_GROUP: return ld(p.chunks_per_group);
+        case SPRINTZ_OPT_DENSE_MODE: return ld(p.dense_mode);
+        case SPRINTZ_OPT_HUF0_BIG_BATCH: return (int)sprintz::huf0_big_batch().load(std::memory_order_relaxed);
+        case SPRINTZ_OPT_SPLIT_LANES: return ld(p.split_lanes);
+        case SPRINTZ_OPT_ENC_PAIR: return ld(p.enc_pair);
+        case SPRINTZ_OPT_HOST_WAIT: return ld(p.host_wait);
+        case SPRINTZ_OPT_LAT_CHUNKS: return ld(p.lat_chunks);
+        case SPRINTZ_OPT_HOST_STREAMS: return ld(p.host_streams);
+        case SPRINTZ_OPT_REF_DECODER_QUIRK: return ld(p.ref_quirk);
+        case SPRINTZ_OPT_HUF0_SYNC_CHUNKS: return (int)sprintz::huf0_sync_chunks().load(std::memory_order_relaxed);
+        case SPRINTZ_OPT_BLK_CHUNKS: return ld(p.blk_chunks);
+        case SPRINTZ_OPT_BLK_KERNELS: return ld(p.blk_kernels);
+    }
+    return fail(SPRINTZ_E_INVALID, "unknown option");
+}
 const char* sprintz_mi355x_last_error(void) { return g_last_error.c_str(); }
 
 int sprintz_mi355x_dispatch_counts(uint64_t* counts, int capacity)
@@ -1719,6 +1740,20 @@ int sprintz_mi355x_query_windows(int codec, int elem_bytes, const void* d_comp, 
     qs.win.sum = (ops & SPRINTZ_QUERY_WIN_SUM) ? d_sum : nullptr;
     return decode_batch(snapshot(), codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, nullptr, d_rets, (hipStream_t)hip_stream,
                         0, 0, 0, qs);
+}
+
+// ---------------------------------------------------------------- zone map (its consumers: zone.hip)
+int sprintz_mi355x_zone_map(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks, uint32_t chunk_len,
+                            uint16_t ndims, uint32_t flags, void* d_zmin, void* d_zmax, int64_t* d_zlen, void* hip_stream)
+{
+    int rc = check_common(codec, elem_bytes, ndims);
+    if (rc) return rc;
+    if (!d_zmin || !d_zmax || !d_zlen) return fail(SPRINTZ_E_INVALID, "zone_map: null device pointer");
+    if ((uintptr_t)d_zlen % 8) return fail(SPRINTZ_E_INVALID, "zone_map: d_zlen must be aligned to 8 bytes");
+    // one window a chunk: the rows of a chunk slot rounded up to the window's granule (an unusable chunk_len is query_windows' to refuse)
+    const uint64_t rows = ((uint64_t)chunk_len + ndims - 1) / ndims, window = rows ? (rows + 7) / 8 * 8 : 8;
+    return sprintz_mi355x_query_windows(codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims, (uint32_t)window,
+                                        SPRINTZ_QUERY_WIN_MIN | SPRINTZ_QUERY_WIN_MAX, flags, d_zmin, d_zmax, nullptr, d_zlen, hip_stream);
 }
 
 // ---------------------------------------------------------------- filter rows

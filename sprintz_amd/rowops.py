@@ -1,7 +1,7 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
 moments_rows, groupby_rows, extrema_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
 fold of its results into windows over the batch's rows, the first damaged chunk, the default bin shift, bounds and offsets as tensors, the
-linear filter's weights and exactness bound, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
+linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
 import torch
@@ -225,6 +225,87 @@ def linear_terms(weights, lag_weights, bias, lo, hi, ndims, esz, device):
                          "or the 32-bit sum wraps")
     as_t = lambda vals: torch.from_numpy(np.array(vals, np.int32)).to(device)      # noqa: E731
     return as_t(w), None if u is None else as_t(u), bias, lo, hi
+
+
+ZONE_NONE, ZONE_ALL, ZONE_DECODE = 0, 1, 2
+ZONE_SPAN_LIMIT = 0xF0000000
+
+
+def check_zones(zones, nchunks, ndims, general_layout, quirk):
+    """a ZoneMap against the call it is to prune: the batch's chunks and columns, and the layout flag and SPRINTZ_OPT_REF_DECODER_QUIRK
+    state it was built under -- a map built under another decodes other values, so it is refused"""
+    if tuple(zones.min.shape) != (nchunks, ndims) or tuple(zones.max.shape) != (nchunks, ndims) or zones.len.numel() != nchunks:
+        raise ValueError(f"zones describe {zones.len.numel()} chunks of {tuple(zones.min.shape)[-1:]} columns, the batch has {nchunks} of {ndims}")
+    if bool(zones.general_layout) != bool(general_layout):
+        raise ValueError(f"zones were built with general_layout={bool(zones.general_layout)}, the call has general_layout={bool(general_layout)}")
+    if int(zones.quirk) != int(quirk):
+        raise ValueError(f"zones were built with SPRINTZ_OPT_REF_DECODER_QUIRK = {int(zones.quirk)}, the process now decodes under {int(quirk)}")
+
+
+def zone_rows(zlen, chunk_len, ndims):
+    """existing rows of chunks whose decoder returned zlen >= 0 elements: int64, like zlen"""
+    return torch.clamp(zlen.to(torch.int64) // ndims, max=chunk_len // ndims)
+
+
+def _zone_finish(verdict, zlen, chunk_len, ndims, span):
+    """what the element count and the container's span decide, over the bounds' verdict"""
+    zlen = zlen.to(torch.int64).reshape(-1)
+    cls = torch.where(zone_rows(zlen, chunk_len, ndims) == 0, ZONE_NONE, verdict)
+    if span >= ZONE_SPAN_LIMIT:                             # the 4 GiB rule: the container is not pruned
+        cls = torch.full_like(cls, ZONE_DECODE)
+    return torch.where(zlen < 0, ZONE_DECODE, cls).to(torch.uint8)
+
+
+def zone_classify_box(zmin, zmax, zlen, lo, hi, mode, chunk_len, ndims, span=0):
+    """The host reference of sprintz_mi355x_zone_prune_box's classes (include/sprintz_mi355x.h).  zmin / zmax: [n, ndims], zlen: [n], lo / hi:
+    [ndims], integer tensors of any dtype; mode "all" / "any"; span = offsets[n] - offsets[0].  -> uint8 [n] of ZONE_NONE / _ALL / _DECODE"""
+    zmin, zmax = zmin.to(torch.int64).reshape(-1, ndims), zmax.to(torch.int64).reshape(-1, ndims)
+    lo, hi = lo.to(torch.int64).reshape(1, ndims), hi.to(torch.int64).reshape(1, ndims)
+    disjoint = (lo > hi) | (zmax < lo) | (zmin > hi)
+    inside = (lo <= zmin) & (zmax <= hi)
+    none, every, decode = (torch.full((zmin.shape[0],), k, dtype=torch.int64, device=zmin.device) for k in (ZONE_NONE, ZONE_ALL, ZONE_DECODE))
+    if mode == "all":
+        verdict = torch.where(disjoint.any(dim=1), none, torch.where(inside.all(dim=1), every, decode))
+    elif mode == "any":
+        verdict = torch.where(inside.any(dim=1), every, torch.where(disjoint.all(dim=1), none, decode))
+    else:
+        raise ValueError("mode must be 'all' or 'any'")
+    return _zone_finish(verdict, zlen, chunk_len, ndims, span)
+
+
+def zone_classify_linear(zmin, zmax, zlen, weights, bias, lo, hi, chunk_len, ndims, span=0):
+    """The host reference of sprintz_mi355x_zone_prune_linear's classes: the form's range over a chunk in int64, left to the decoder where
+    it leaves int32.  weights: [ndims] integers; bias, lo, hi: Python ints.  -> uint8 [n]"""
+    zmin, zmax = zmin.to(torch.int64).reshape(-1, ndims), zmax.to(torch.int64).reshape(-1, ndims)
+    w = weights.to(torch.int64).reshape(1, ndims)
+    smin = int(bias) + torch.where(w >= 0, w * zmin, w * zmax).sum(dim=1)
+    smax = int(bias) + torch.where(w >= 0, w * zmax, w * zmin).sum(dim=1)
+    lo, hi = int(lo), int(hi)
+    none, every, decode = (torch.full_like(smin, k) for k in (ZONE_NONE, ZONE_ALL, ZONE_DECODE))
+    verdict = torch.where((smax < lo) | (smin > hi), none, torch.where((smin >= lo) & (smax <= hi), every, decode))
+    if lo > hi:
+        verdict = none
+    verdict = torch.where((smin < INT32_MIN) | (smax > INT32_MAX), decode, verdict)
+    return _zone_finish(verdict, zlen, chunk_len, ndims, span)
+
+
+def zone_expand(cls, zlen, cmask, ccounts, crets, chunk_len, ndims):
+    """The host reference of sprintz_mi355x_zone_expand: a filter's compact results over the ZONE_DECODE chunks, in batch order -- cmask
+    uint8 [n', MB], ccounts [n'], crets [n'] -- into filter_rows' layout -> (mask uint8 [n, MB], counts int64 [n], rets int64 [n]).  A
+    ZONE_NONE chunk matches nowhere; a ZONE_ALL chunk has the bits of its existing rows set and the padding bits of its last byte 0; a chunk with zlen < 0 keeps zlen as its ret."""
+    R, MB = chunk_rows(chunk_len, ndims)
+    cls, zlen = cls.reshape(-1), zlen.to(torch.int64).reshape(-1)
+    n = cls.numel()
+    dec = cls == ZONE_DECODE
+    rows = torch.where(cls == ZONE_ALL, zone_rows(zlen, chunk_len, ndims), 0)
+    bit = torch.arange(MB * 8, device=cls.device).reshape(1, MB, 8)
+    mask = ((bit < rows.reshape(n, 1, 1)).to(torch.int64) << torch.arange(8, device=cls.device)).sum(dim=2).to(torch.uint8)
+    counts, rets = rows.clone(), zlen.clone()
+    mask[dec] = cmask.reshape(-1, MB).to(torch.uint8)
+    counts[dec] = ccounts.reshape(-1).to(torch.int64)
+    rets[dec] = crets.reshape(-1).to(torch.int64)
+    rets = torch.where(zlen < 0, zlen, rets)                # a chunk the map found damaged keeps the map's code, whatever the decoder made of it
+    return mask, counts, rets
 
 
 def derive_moments(out, ops, ref, ddof):
