@@ -17,7 +17,7 @@
 #include <mutex>
 #include <string>
 
-namespace sprintz { int set_error(int code, const char* what); }
+namespace sprintz { int fail(int code, const char* what, hipError_t e = hipSuccess); }   // entry.h: the library's one error sink
 
 namespace {
 
@@ -76,7 +76,7 @@ int nccl_fail(const char* what, ncclResult_t e)
     msg = what;
     const Rccl& r = rccl();
     if (r.GetErrorString) { msg += ": "; msg += r.GetErrorString(e); }
-    return sprintz::set_error(SPRINTZ_E_HIP, msg.c_str());
+    return sprintz::fail(SPRINTZ_E_HIP, msg.c_str());
 }
 
 }  // namespace
@@ -85,9 +85,9 @@ extern "C" {
 
 int sprintz_mi355x_comm_unique_id(void* id_out)
 {
-    if (!id_out) return sprintz::set_error(SPRINTZ_E_INVALID, "comm_unique_id: null pointer");
+    if (!id_out) return sprintz::fail(SPRINTZ_E_INVALID, "comm_unique_id: null pointer");
     const Rccl& r = rccl();
-    if (!r.handle) return sprintz::set_error(SPRINTZ_E_UNSUPPORTED, r.why.c_str());
+    if (!r.handle) return sprintz::fail(SPRINTZ_E_UNSUPPORTED, r.why.c_str());
     static_assert(sizeof(ncclUniqueId) == SPRINTZ_MI355X_COMM_ID_BYTES, "id size");
     ncclUniqueId id;
     const ncclResult_t e = r.GetUniqueId(&id);
@@ -98,12 +98,12 @@ int sprintz_mi355x_comm_unique_id(void* id_out)
 
 int sprintz_mi355x_comm_init(const void* id_in, int rank, int world, void** comm_out)
 {
-    if (!id_in || !comm_out || world < 1 || rank < 0 || rank >= world) return sprintz::set_error(SPRINTZ_E_INVALID, "comm_init: bad argument");
+    if (!id_in || !comm_out || world < 1 || rank < 0 || rank >= world) return sprintz::fail(SPRINTZ_E_INVALID, "comm_init: bad argument");
     const Rccl& r = rccl();
-    if (!r.handle) return sprintz::set_error(SPRINTZ_E_UNSUPPORTED, r.why.c_str());
+    if (!r.handle) return sprintz::fail(SPRINTZ_E_UNSUPPORTED, r.why.c_str());
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return sprintz::set_error(SPRINTZ_E_NO_DEVICE, "comm_init: no usable HIP device (there is no CPU fallback)");
+        return sprintz::fail(SPRINTZ_E_NO_DEVICE, "comm_init: no usable HIP device (there is no CPU fallback)");
     ncclUniqueId id;
     memcpy(&id, id_in, sizeof id);
     Comm* c = new Comm();
@@ -117,7 +117,7 @@ int sprintz_mi355x_comm_init(const void* id_in, int rank, int world, void** comm
 
 int sprintz_mi355x_gather_layout(void* comm, const uint64_t* d_local_total, uint64_t* d_all, void* hip_stream)
 {
-    if (!comm || !d_local_total || !d_all) return sprintz::set_error(SPRINTZ_E_INVALID, "gather_layout: null pointer");
+    if (!comm || !d_local_total || !d_all) return sprintz::fail(SPRINTZ_E_INVALID, "gather_layout: null pointer");
     Comm* c = (Comm*)comm;
     const ncclResult_t e = rccl().AllGather(d_local_total, d_all, 1, ncclUint64, c->comm, (hipStream_t)hip_stream);
     if (e != ncclSuccess) return nccl_fail("ncclAllGather", e);
@@ -126,11 +126,11 @@ int sprintz_mi355x_gather_layout(void* comm, const uint64_t* d_local_total, uint
 
 int sprintz_mi355x_layout_bases(const uint64_t* d_all, int world, uint64_t* bases_out, void* hip_stream)
 {
-    if (!d_all || !bases_out || world < 1 || world > 4096) return sprintz::set_error(SPRINTZ_E_INVALID, "layout_bases: bad argument");
+    if (!d_all || !bases_out || world < 1 || world > 4096) return sprintz::fail(SPRINTZ_E_INVALID, "layout_bases: bad argument");
     uint64_t counts[4096];
     if (hipMemcpyAsync(counts, d_all, (size_t)world * 8, hipMemcpyDeviceToHost, (hipStream_t)hip_stream) != hipSuccess ||
         hipStreamSynchronize((hipStream_t)hip_stream) != hipSuccess)
-        return sprintz::set_error(SPRINTZ_E_HIP, "layout_bases: reading the gathered counts back failed");
+        return sprintz::fail(SPRINTZ_E_HIP, "layout_bases: reading the gathered counts back failed");
     uint64_t acc = 0;
     for (int r = 0; r < world; r++) { bases_out[r] = acc; acc += counts[r]; }
     bases_out[world] = acc;

@@ -1,6 +1,6 @@
 // dropin.cpp -- the reference's public functions, defined with the reference's own C++ signatures
 // (and therefore its own mangled names: _Z25sprintz_compress_delta_8bPKhjPatb ...) on top of the
-// C-ABI.  No codec logic here: every function is a one-line hand-over to api.hip / transforms.hip.
+// C-ABI.  No codec logic here: every function is a one-line hand-over to host_call.hip / transforms.hip.
 // An object file compiled against dblalock/sprintz cpp/Compress/{sprintz,sprintz_delta,sprintz_xff,
 // delta,predict}.h links against libsprintz_mi355x.so without recompilation.
 #include "../../include/sprintz_dropin.hpp"

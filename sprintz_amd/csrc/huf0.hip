@@ -23,15 +23,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "lds_attr.h"
-#include "dispatch.h"
+#include "entry.h"
 
 #include <cstdlib>
 #include <string>
 #include <atomic>
 #include <type_traits>
-
-namespace sprintz { int set_error(int code, const char* what); }   // api.hip: the library's one error sink
 
 namespace sprintz {
 // chunks from which the one-table stream kernel runs as workgroups of HUF0_BIG_WG (built: 2) waves with 2^HUF0_BIG_PLOG (built: 64) byte pieces (SPRINTZ_OPT_HUF0_BIG_BATCH)
@@ -1848,12 +1845,12 @@ int sprintz_mi355x_huf0_decompress_batch_hint(const void* d_blocks, const uint64
                                               const uint64_t* d_out_offsets, int64_t* d_rets, void* d_tmp, uint32_t max_block_bytes, void* hip_stream)
 {
     if (!d_blocks || !d_block_offsets || !d_out || !d_out_offsets || ((uintptr_t)d_blocks & 15) || (nchunks && (!d_tmp || ((uintptr_t)d_tmp & 15))))
-        return sprintz::set_error(SPRINTZ_E_INVALID, "Huff0 stage: invalid argument (null pointer, alignment or size)");
+        return sprintz::fail(SPRINTZ_E_INVALID, "Huff0 stage: invalid argument (null pointer, alignment or size)");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sprintz::set_error(SPRINTZ_E_NO_DEVICE, "Huff0 stage: no usable HIP device (there is no CPU fallback)");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sprintz::fail(SPRINTZ_E_NO_DEVICE, "Huff0 stage: no usable HIP device (there is no CPU fallback)");
     if (nchunks == 0) return 0;
     const uint64_t grid1 = (nchunks + 63) / 64, grid2 = (nchunks + 15) / 16, nleaders = grid1;
-    if (grid2 > 0x7fffffffull) return sprintz::set_error(SPRINTZ_E_INVALID, "Huff0 stage: invalid argument (null pointer, alignment or size)");
+    if (grid2 > 0x7fffffffull) return sprintz::fail(SPRINTZ_E_INVALID, "Huff0 stage: invalid argument (null pointer, alignment or size)");
     hipStream_t st = (hipStream_t)hip_stream;
     uint8_t* const desc = (uint8_t*)d_tmp;
     uint8_t* const follow = desc + (((size_t)nchunks * kDescStride + 255) & ~(size_t)255);
@@ -1907,12 +1904,12 @@ int sprintz_mi355x_huf0_decompress_batch_hint(const void* d_blocks, const uint64
         const uint64_t per_wg = (uint64_t)kWpb * cpw;
         if (sprintz::launch_with_lds(huf0_sync_kernel<kWpb>, (unsigned)((nchunks + per_wg - 1) / per_wg), 64u * kWpb, lds, st, blk, d_block_offsets, nchunks,
                                      (uint8_t*)d_out, d_out_offsets, d_rets, (const uint8_t*)desc, (const uint8_t*)share, img, cpw) != hipSuccess)
-            return sprintz::set_error(SPRINTZ_E_HIP, "Huff0 stage: the self-synchronising stream kernel's launch failed");
+            return sprintz::fail(SPRINTZ_E_HIP, "Huff0 stage: the self-synchronising stream kernel's launch failed");
     } else {
         hipLaunchKernelGGL(huf0_stream_small_kernel, dim3((unsigned)grid2), dim3(64), 0, st, blk, d_block_offsets, nchunks,
                            (uint8_t*)d_out, d_out_offsets, d_rets, (const uint8_t*)desc, (const uint8_t*)share, 0);
     }
-    if (hipGetLastError() != hipSuccess) return sprintz::set_error(SPRINTZ_E_HIP, "Huff0 stage: a HIP call or kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return sprintz::fail(SPRINTZ_E_HIP, "Huff0 stage: a HIP call or kernel launch failed");
     sprintz::dispatched(family);
     return 0;
 }
@@ -1926,13 +1923,13 @@ int sprintz_mi355x_huf0_decompress_batch(const void* d_blocks, const uint64_t* d
                                          const uint64_t* d_out_offsets, int64_t* d_rets, void* hip_stream)
 {
     if (!d_blocks || !d_block_offsets || !d_out || !d_out_offsets || ((uintptr_t)d_blocks & 15))
-        return sprintz::set_error(SPRINTZ_E_INVALID, "Huff0 stage: invalid argument (null pointer, alignment or size)");
+        return sprintz::fail(SPRINTZ_E_INVALID, "Huff0 stage: invalid argument (null pointer, alignment or size)");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sprintz::set_error(SPRINTZ_E_NO_DEVICE, "Huff0 stage: no usable HIP device (there is no CPU fallback)");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sprintz::fail(SPRINTZ_E_NO_DEVICE, "Huff0 stage: no usable HIP device (there is no CPU fallback)");
     if (nchunks == 0) return 0;
     void* tmp = nullptr;
     if (hipMallocAsync(&tmp, sprintz_mi355x_huf0_decode_tmp_bytes(nchunks), (hipStream_t)hip_stream) != hipSuccess)
-        return sprintz::set_error(SPRINTZ_E_HIP, "Huff0 stage: hipMallocAsync of the descriptor workspace failed");
+        return sprintz::fail(SPRINTZ_E_HIP, "Huff0 stage: hipMallocAsync of the descriptor workspace failed");
     const int rc = sprintz_mi355x_huf0_decompress_batch_ws(d_blocks, d_block_offsets, nchunks, d_out, d_out_offsets, d_rets, tmp, hip_stream);
     (void)hipFreeAsync(tmp, (hipStream_t)hip_stream);
     return rc;

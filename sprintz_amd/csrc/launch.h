@@ -5,8 +5,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "lds_attr.h"
 #include "decode_kernel.h"
 #include "decode_fast.h"
@@ -68,20 +66,6 @@ hipError_t launch_encode_fast_w8(bool fire, int dp, bool exact, unsigned grid, s
 hipError_t launch_encode_fast_w16(bool fire, int dp, bool exact, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
 hipError_t launch_encode_w8(bool fire, bool lowdim, int cpl, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
 hipError_t launch_encode_w16(bool fire, bool lowdim, int cpl, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
-
-// records `what` as this thread's last error (sprintz_mi355x_last_error) and returns `code`: every
-// failing return of every translation unit goes through it, so the message is never stale
-int set_error(int code, const char* what);
-
-// the calling thread's pooled scratch for host-pointer entry points (api.hip: acquire_scratch): buffers only grow, the
-// stream is private and non-blocking; valid until the thread's next host_scratch() call
-struct HostScratch { hipStream_t stream; uint8_t* dev; uint8_t* pin; };
-int host_scratch(size_t dev_bytes, size_t pin_bytes, HostScratch* out);
-bool have_device();                       // probed once per process
-std::atomic<long long>& huf0_sync_chunks(); // huf0.hip: batch size up to which the stream stage runs as a wave per chunk with self-synchronising decoders (huf0_sync.h)
-std::atomic<long long>& huf0_big_batch(); // huf0.hip: batch size from which the one-table stream kernel runs as workgroups of HUF0_BIG_WG (2) waves
-
-hipError_t launch_size_scan(const uint32_t* d_sizes, uint64_t n, uint32_t align, uint64_t* d_offsets, void* d_tmp, hipStream_t st);
 
 template <typename K, typename A>
 inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t st, const A& a)

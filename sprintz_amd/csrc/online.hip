@@ -21,8 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "launch.h"
-#include "dispatch.h"
+#include "entry.h"
 
 using namespace sprintz;
 
@@ -782,7 +781,6 @@ __global__ void check_len_kernel(const uint8_t* src, uint32_t len, int64_t* ret)
     if (have != len && ret) *ret = SPRINTZ_E_CORRUPT;
 }
 
-int fail(int code, const char* what) { return sprintz::set_error(code, what); }
 unsigned grid_for(uint64_t items) { return (unsigned)((items + kT - 1) / kT); }
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 unsigned tiles_for(uint64_t blocks) { return (unsigned)((blocks + kTile - 1) / kTile); }
@@ -959,7 +957,7 @@ int sprintz_mi355x_online_unpack_device(int kind, const void* d_src, uint32_t le
 }
 
 // ---- single-call forms over host buffers (the reference's signatures are in include/sprintz_dropin.hpp)
-// Like api.hip's single calls: the thread's pooled scratch (one device buffer [source | destination | tmp | ret], one
+// Like host_call.hip's single calls: the thread's pooled scratch (one device buffer [source | destination | tmp | ret], one
 // pinned staging buffer, one private non-blocking stream) -- no hipMalloc / hipFree per call, no device-wide
 // synchronisation that would stall other threads' streams.
 

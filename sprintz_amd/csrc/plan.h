@@ -37,7 +37,7 @@ struct Shape {
     uint64_t col_stride = 0;
     int write_size = 1;                    // encode
     bool dense = false;                    // encode: a container was asked for (compact_tail.h)
-    bool host_call = false;                // a single call that a workgroup-per-chunk kernel must end (api.hip: HostCall)
+    bool host_call = false;                // a single call that a workgroup-per-chunk kernel must end (entry.h: HostCall)
     unsigned src_lo = 0, slots_lo = 0, out_lo = 0, comp_lo = 0;   // the low four bits of the source, slot, output and container addresses
     uint64_t slot_stride = 0;
     uint64_t nranges = 0;                  // gather

@@ -23,7 +23,7 @@
 // ("replicas only") and is here so that the whole transform surface of the
 // reference exists behind one boundary.  Many independent series belong in the batched codec.
 #include "../../include/sprintz_mi355x.h"
-#include "dispatch.h"
+#include "entry.h"
 #include "transform_plan.h"
 
 #include <hip/hip_runtime.h>
@@ -808,11 +808,6 @@ __global__ void __launch_bounds__(kChainT) __attribute__((amdgpu_waves_per_eu(KI
     }
 }
 
-}  // namespace
-namespace sprintz { int set_error(int code, const char* what); }   // api.hip: the library's one error sink
-namespace {
-int fail(int code, const char* what) { return sprintz::set_error(code, what); }
-
 // workgroups of the one-pass decode: one per CU (each takes tiles until there are none)
 int chain_resident_wgs()
 {
@@ -1072,12 +1067,6 @@ int check(int kind, int esz, uint64_t len, uint16_t ndims)
     if (kind == SPRINTZ_TRANSFORM_XFF && len > 0xffffffffull) return fail(SPRINTZ_E_INVALID, "xff: len is 32 bits in the reference (predict.h:15)");
     if (len / 64 > 0x7fffffffull) return fail(SPRINTZ_E_INVALID, "len too large for one launch");
     return 0;
-}
-
-bool have_device()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
 }
 
 }  // namespace

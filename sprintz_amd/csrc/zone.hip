@@ -8,7 +8,7 @@
 
 #include <string>
 
-#include "launch.h"
+#include "entry.h"
 #include "zone.h"
 
 namespace sprintz {
@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(kThreads) zone_expand_kernel(uint64_t nchunks,
 int zone_fail(const char* op, const char* what)
 {
     const std::string named = std::string(op) + ": " + what;
-    return set_error(SPRINTZ_E_INVALID, named.c_str());
+    return fail(SPRINTZ_E_INVALID, named.c_str());
 }
 
 // what the two prune entry points check alike, before the device is touched
@@ -165,7 +165,7 @@ int check_prune(const char* op, int elem_bytes, uint32_t chunk_len, uint16_t ndi
 {
     if (elem_bytes != 1 && elem_bytes != 2) return zone_fail(op, "elem_bytes must be 1 or 2");
     if (ndims == 0) return zone_fail(op, "ndims == 0");
-    if (ndims > 512) return set_error(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no zone map");
+    if (ndims > 512) return fail(SPRINTZ_E_UNSUPPORTED, "more than 512 columns: no zone map");
     if (chunk_len == 0 || chunk_len > (1u << 30)) return zone_fail(op, "chunk_len must be in 1..2^30");
     if (!d_offsets || !d_zmin || !d_zmax || !d_zlen || !d_class || !d_pos || !d_surv_offsets || !d_tmp) return zone_fail(op, "null device pointer");
     if ((uintptr_t)d_zmin % (uintptr_t)elem_bytes || (uintptr_t)d_zmax % (uintptr_t)elem_bytes) return zone_fail(op, "d_zmin / d_zmax must be aligned to the element size");
@@ -179,7 +179,7 @@ int prune(const char* op, bool linear, int elem_bytes, uint64_t nchunks, uint32_
           const void* d_zmax, const int64_t* d_zlen, const ZonePredicate& p, uint8_t* d_class, uint64_t* d_pos, uint64_t* d_surv_offsets, void* d_tmp,
           hipStream_t st)
 {
-    if (!have_device()) return set_error(SPRINTZ_E_NO_DEVICE, "no usable HIP device (libsprintz_mi355x has no CPU fallback)");
+    if (!have_device()) return fail(SPRINTZ_E_NO_DEVICE, "no usable HIP device (libsprintz_mi355x has no CPU fallback)");
     int log2G = 0;                                                   // 1 .. 64 lanes a chunk: as many as it has columns
     while (log2G < 6 && (1u << log2G) < ndims) log2G++;
     const uint64_t grid = ((nchunks << log2G) + kThreads - 1) / kThreads, grid2 = (nchunks + 1 + kThreads - 1) / kThreads;
@@ -205,7 +205,7 @@ int prune(const char* op, bool linear, int elem_bytes, uint64_t nchunks, uint32_
     }
     if (e != hipSuccess) {
         const std::string named = std::string(op) + ": a kernel launch failed: " + hipGetErrorString(e);
-        return set_error(SPRINTZ_E_HIP, named.c_str());
+        return fail(SPRINTZ_E_HIP, named.c_str());
     }
     return 0;
 }
@@ -266,7 +266,7 @@ int sprintz_mi355x_zone_expand(uint64_t nchunks, uint32_t chunk_len, uint16_t nd
         return zone_fail(op, "d_pos, d_zlen, d_crets and d_rets must be aligned to 8 bytes");
     if ((uintptr_t)d_ccounts % 4 || (uintptr_t)d_counts % 4) return zone_fail(op, "d_ccounts and d_counts must be aligned to 4 bytes");
     if (nchunks == 0) return 0;
-    if (!have_device()) return set_error(SPRINTZ_E_NO_DEVICE, "no usable HIP device (libsprintz_mi355x has no CPU fallback)");
+    if (!have_device()) return fail(SPRINTZ_E_NO_DEVICE, "no usable HIP device (libsprintz_mi355x has no CPU fallback)");
     const uint32_t rows = (chunk_len + ndims - 1) / ndims, MB = (rows + 7) / 8;
     const uint64_t dwords = d_mask ? (nchunks * (uint64_t)MB + 3 + 3) / 4 : 0;       // the mask's bytes and up to 3 in front of them
     const uint64_t threads = dwords > nchunks ? dwords : nchunks, grid = (threads + kThreads - 1) / kThreads;
@@ -276,7 +276,7 @@ int sprintz_mi355x_zone_expand(uint64_t nchunks, uint32_t chunk_len, uint16_t nd
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         const std::string named = std::string(op) + ": kernel launch failed: " + hipGetErrorString(e);
-        return set_error(SPRINTZ_E_HIP, named.c_str());
+        return fail(SPRINTZ_E_HIP, named.c_str());
     }
     return 0;
 }

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """tools/kernel_diff.py <build dir A> <build dir B> [name-filter]: compares the gfx950 code of every kernel symbol present
-in the object files of both build directories (sprintz_amd/csrc/build of two trees): identical / differing only in the
+in the object files of both build directories (sprintz_amd/csrc/build of two trees), paired by symbol over all the objects of
+a directory -- a kernel that moved to another unit is still the same kernel; one that two objects of a directory hold is
+reported ("twice"), and compared as the first holds it: identical / differing only in the
 offsets of kernel-argument loads (a DecodeArgs field appended or moved) / differing only in the order of the two sources
 of a commutative VALU instruction (same opcode, same registers) / differing otherwise.  Prints the counts and the names of
 the last three classes.  Needs no GPU."""
@@ -28,7 +30,7 @@ def kernels(obj, tmp):
         m = re.match(r"^[0-9a-f]* ?<(\S+)>:$", line.strip())
         if m:
             cur = out.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":      # ("...": the zero padding between two symbols, which depends on what follows)
             cur.append(re.sub(r"\s*//.*$", "", line.strip()))
     return out
 
@@ -47,37 +49,43 @@ def commute(ins):
     return out
 
 
+def directory(d, filt):
+    """{symbol: instructions} over every object file of `d` (a symbol may change its unit between two builds), and the
+    symbols that more than one object of `d` holds, with those objects"""
+    out, where = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for obj in sorted(glob.glob(os.path.join(d, "*.o"))):
+            for k, ins in kernels(obj, tmp).items():
+                if filt.search(k):
+                    where.setdefault(k, []).append(os.path.basename(obj))
+                    out.setdefault(k, ins)
+    return out, {k: w for k, w in where.items() if len(w) > 1}
+
+
 def main():
     a_dir, b_dir = sys.argv[1], sys.argv[2]
     filt = re.compile(sys.argv[3] if len(sys.argv) > 3 else ".")
-    same, karg, comm, other, only_a, only_b = 0, [], [], [], 0, 0
-    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        for oa in sorted(glob.glob(os.path.join(a_dir, "*.o"))):
-            ob = os.path.join(b_dir, os.path.basename(oa))
-            if not os.path.exists(ob):
-                continue
-            ka, kb = kernels(oa, ta), kernels(ob, tb)
-            only_a += len([k for k in ka if k not in kb and filt.search(k)])
-            only_b += len([k for k in kb if k not in ka and filt.search(k)])
-            for k in sorted(set(ka) & set(kb)):
-                if not filt.search(k):
-                    continue
-                if ka[k] == kb[k]:
-                    same += 1
-                elif strip_karg(ka[k]) == strip_karg(kb[k]):
-                    karg.append(k)
-                elif commute(strip_karg(ka[k])) == commute(strip_karg(kb[k])):
-                    comm.append(k)
-                else:
-                    other.append(k)
+    (ka, twice_a), (kb, twice_b) = directory(a_dir, filt), directory(b_dir, filt)
+    same, karg, comm, other = 0, [], [], []
+    only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
+    for k in sorted(set(ka) & set(kb)):
+        if ka[k] == kb[k]:
+            same += 1
+        elif strip_karg(ka[k]) == strip_karg(kb[k]):
+            karg.append(k)
+        elif commute(strip_karg(ka[k])) == commute(strip_karg(kb[k])):
+            comm.append(k)
+        else:
+            other.append(k)
     print(f"symbols in both: {same + len(karg) + len(comm) + len(other)}; identical: {same}; kernel-argument offsets only: {len(karg)}; "
-          f"commuted sources only: {len(comm)}; differ otherwise: {len(other)}; only in A: {only_a}; only in B: {only_b}")
-    for k in karg:
-        print("  karg ", k)
-    for k in comm:
-        print("  comm ", k)
-    for k in other:
-        print("  OTHER", k)
+          f"commuted sources only: {len(comm)}; differ otherwise: {len(other)}; only in A: {len(only_a)}; only in B: {len(only_b)}; "
+          f"twice in A: {len(twice_a)}; twice in B: {len(twice_b)}")
+    for tag, names in (("karg ", karg), ("comm ", comm), ("OTHER", other), ("only A", only_a), ("only B", only_b)):
+        for k in names:
+            print(f"  {tag}", k)
+    for tag, twice in (("twice A", twice_a), ("twice B", twice_b)):
+        for k, w in sorted(twice.items()):
+            print(f"  {tag}", k, "in", ", ".join(w))
 
 
 if __name__ == "__main__":
