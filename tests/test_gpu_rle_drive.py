@@ -13,7 +13,8 @@ value, nothing outside; then the ORACLE's container through the same decoder, so
 way cannot agree with each other; and the kernel family on both sides from the dispatch counters (tests/dispatch.py), as literals that
 tests/test_rle_drive_cpu.py replays through the planner without a device.  A batch's first chunk is the golden fixture's case
 (tests/golden/golden_rledrive_v1, minted from the compiled reference by oracle/gen_golden_rledrive.py) where there is one.  Then the
-row operations over the same batches, against the numpy models applied to the raw samples.  Nothing here needs the reference."""
+row operations over the same batches, against the numpy models applied to the raw samples, at one and at three chunks a lane group of
+decode_fast.h (SPRINTZ_OPT_CHUNKS_PER_GROUP); the later ones are in tests/test_gpu_rowop_drive.py.  Nothing here needs the reference."""
 import json
 import os
 import zlib
@@ -245,12 +246,16 @@ def test_the_cap(sz, oracle, case, codec):
 
 # w, ndims -> the decoder family of: windows, filter, select, aggregate (csrc/plan.h: the reduce-only modes do not need rows of whole
 # 16-byte pieces, select and gather do), and the gather family
+# ... and of the later reduce-only modes -- histogram, moments, group-by, extrema, the linear filter -- with the tables of
+# tests/test_gpu_rowop_drive.py (at most 128 x (D + 1) entries: 17 KB behind the groups' carves)
+LATER = dict(histogram="dec_fast", moments="dec_fast", groupby="dec_fast", extrema="dec_fast", linear="dec_fast")
 ROWOP_SHAPES = {
-    (16, 8): dict(window="dec_fast", filter="dec_fast", select="dec_fast", aggregate="dec_fast", gather="gather_fast"),
-    (8, 32): dict(window="dec_fast", filter="dec_fast", select="dec_fast", aggregate="dec_fast", gather="gather_fast"),
-    (16, 12): dict(window="dec_fast", filter="dec_fast", select="dec_generic", aggregate="dec_fast", gather="gather_generic"),
+    (16, 8): dict(window="dec_fast", filter="dec_fast", select="dec_fast", aggregate="dec_fast", gather="gather_fast", **LATER),
+    (8, 32): dict(window="dec_fast", filter="dec_fast", select="dec_fast", aggregate="dec_fast", gather="gather_fast", **LATER),
+    (16, 12): dict(window="dec_fast", filter="dec_fast", select="dec_generic", aggregate="dec_fast", gather="gather_generic", **LATER),
 }
-ROWOP_CASES = [(codec, w, D, kind) for codec in BOTH for (w, D) in ROWOP_SHAPES for kind in ("lengths", "tails")]
+ROWOP_KINDS = ("lengths", "start", "alternate", "tails")
+ROWOP_CASES = [(codec, w, D, kind) for codec in BOTH for (w, D) in ROWOP_SHAPES for kind in ROWOP_KINDS]
 ROWOP_IDS = [f"{c}-u{w}x{D}-{k}" for c, w, D, k in ROWOP_CASES]
 WINDOWS = (8, 24)                                       # window_rows is a multiple of 8 at every entry point: one block a window, and
                                                         # three -- runs of 1, 2, 4, 5 ... blocks start and end inside windows
@@ -264,6 +269,17 @@ def no_fast():
         _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
     yield setter
     _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
+
+
+@pytest.fixture
+def chunks_per_group():
+    """set_option(OPT_CHUNKS_PER_GROUP) for the duration of a test, restored afterwards"""
+    from sprintz_amd import _lib
+
+    def setter(k):
+        _lib.check(_lib.set_option(_lib.OPT_CHUNKS_PER_GROUP, int(k)))
+    yield setter
+    _lib.set_option(_lib.OPT_CHUNKS_PER_GROUP, int(os.environ.get("SPRINTZ_MI355X_CHUNKS_PER_GROUP", 1)))
 
 
 def rowop_batch(sz, oracle, codec, w, D, kind):
@@ -280,6 +296,19 @@ def families(w, D, op):
     return [(0, first)] + ([(1, generic)] if first != generic else [])
 
 
+CPGS = (1, 3)                                          # chunks a lane group of decode_fast.h: at 3 the 16 chunks fall to groups of 3, 3, 3, 3, 3 and 1
+
+
+def legs(w, D, op):
+    """(NO_FAST, chunks_per_group, family): the planner's family at one and at three chunks a lane group -- the chunk loop of
+    decode_fast.h resets every mode's per-chunk state and reads ahead across the seam -- then decode_kernel.h, which ignores the
+    option, once"""
+    out = []
+    for fam, family in families(w, D, op):
+        out += [(fam, cpg, family) for cpg in (CPGS if family in ("dec_fast", "gather_fast") else CPGS[:1])]
+    return out
+
+
 def run_masks(zero, seed):
     """uint8 [nchunks, MB] in filter_rows' layout (8 rows a byte: a block a byte): pseudo-random rows, exactly the rows inside runs,
     exactly the rows outside"""
@@ -289,59 +318,63 @@ def run_masks(zero, seed):
 
 
 @pytest.mark.parametrize("codec,w,D,kind", ROWOP_CASES, ids=ROWOP_IDS)
-def test_query_windows_over_runs(sz, oracle, no_fast, codec, w, D, kind):
+def test_query_windows_over_runs(sz, oracle, no_fast, chunks_per_group, codec, w, D, kind):
     cd, batch, data, chunk_len, _ = rowop_batch(sz, oracle, codec, w, D, kind)
     with options(**OLD):
         for W in WINDOWS:
             mn, mx, sums = wm.chunk_windows(data, chunk_len, D, W)
-            for fam, family in families(w, D, "window"):
+            for fam, cpg, family in legs(w, D, "window"):
                 no_fast(fam)
+                chunks_per_group(cpg)
                 with ran(only=[family], **{family: 1}):
                     got = cd.query_windows(batch, W, per_chunk=True)
-                msg = (codec, w, D, kind, W, family)
+                msg = (codec, w, D, kind, W, family, cpg)
                 assert np.array_equal(got["min"].cpu().numpy(), mn) and np.array_equal(got["max"].cpu().numpy(), mx), msg
                 assert np.array_equal(got["sum"].cpu().numpy().view(np.uint64), sums), msg
 
 
 @pytest.mark.parametrize("codec,w,D,kind", ROWOP_CASES, ids=ROWOP_IDS)
-def test_filter_rows_over_runs(sz, oracle, no_fast, codec, w, D, kind):
+def test_filter_rows_over_runs(sz, oracle, no_fast, chunks_per_group, codec, w, D, kind):
     cd, batch, data, chunk_len, _ = rowop_batch(sz, oracle, codec, w, D, kind)
     sets, _ = bound_sets(data, chunk_len, w // 8, D)
     with options(**OLD):
         for name, mode, lo, hi, _ in sets:
             want = fm.filter_rows(data, chunk_len, D, lo, hi, mode)
-            for fam, family in families(w, D, "filter"):
+            for fam, cpg, family in legs(w, D, "filter"):
                 no_fast(fam)
+                chunks_per_group(cpg)
                 with ran(only=[family], **{family: 1}):
                     mask, counts = run_filter(cd, batch, lo, hi, mode)
-                assert np.array_equal(counts, want[1]) and np.array_equal(mask, want[0]), (codec, w, D, kind, name, family)
+                assert np.array_equal(counts, want[1]) and np.array_equal(mask, want[0]), (codec, w, D, kind, name, family, cpg)
 
 
 @pytest.mark.parametrize("codec,w,D,kind", ROWOP_CASES, ids=ROWOP_IDS)
-def test_select_rows_over_runs(sz, oracle, no_fast, codec, w, D, kind):
+def test_select_rows_over_runs(sz, oracle, no_fast, chunks_per_group, codec, w, D, kind):
     cd, batch, data, chunk_len, zero = rowop_batch(sz, oracle, codec, w, D, kind)
     with options(**OLD):
         for name, mask in run_masks(zero, 11):
             cnt = sm.counts(mask, data.size, chunk_len, D)
             total = int(cnt.sum())
             assert 0 < total < data.size // D
-            for fam, family in families(w, D, "select"):
+            for fam, cpg, family in legs(w, D, "select"):
                 no_fast(fam)
+                chunks_per_group(cpg)
                 with ran(only=[family], **{family: 1}):
-                    check_select(data, batch, codec, w // 8, D, chunk_len, mask, sm.prefix_bases(cnt), total, total, (codec, w, D, kind, name, family))
+                    check_select(data, batch, codec, w // 8, D, chunk_len, mask, sm.prefix_bases(cnt), total, total, (codec, w, D, kind, name, family, cpg))
 
 
 @pytest.mark.parametrize("codec,w,D,kind", ROWOP_CASES, ids=ROWOP_IDS)
-def test_aggregate_rows_over_runs(sz, oracle, no_fast, codec, w, D, kind):
+def test_aggregate_rows_over_runs(sz, oracle, no_fast, chunks_per_group, codec, w, D, kind):
     cd, batch, data, chunk_len, zero = rowop_batch(sz, oracle, codec, w, D, kind)
     with options(**OLD):
         for name, mask in run_masks(zero, 12):
             for W in WINDOWS:
                 want = am.aggregate_rows(data, chunk_len, D, mask, W)
-                for fam, family in families(w, D, "aggregate"):
+                for fam, cpg, family in legs(w, D, "aggregate"):
                     no_fast(fam)
+                    chunks_per_group(cpg)
                     with ran(only=[family], **{family: 1}):
-                        check_agg(data, batch, codec, w // 8, D, chunk_len, mask, W, (codec, w, D, kind, name, W, family), want)
+                        check_agg(data, batch, codec, w // 8, D, chunk_len, mask, W, (codec, w, D, kind, name, W, family, cpg), want)
 
 
 def run_edge_starts(zero, rows):
@@ -357,7 +390,7 @@ def run_edge_starts(zero, rows):
 
 
 @pytest.mark.parametrize("codec,w,D,kind", ROWOP_CASES, ids=ROWOP_IDS)
-def test_gather_rows_over_runs(sz, oracle, no_fast, codec, w, D, kind):
+def test_gather_rows_over_runs(sz, oracle, no_fast, chunks_per_group, codec, w, D, kind):
     import torch
     cd, batch, data, chunk_len, zero = rowop_batch(sz, oracle, codec, w, D, kind)
     x = data.reshape(-1, D)
@@ -367,11 +400,12 @@ def test_gather_rows_over_runs(sz, oracle, no_fast, codec, w, D, kind):
             assert starts.size >= 4 * NCHUNKS
             want, ok = gm.expected(x, starts, rows)
             assert ok.all()
-            for fam, family in families(w, D, "gather"):
+            for fam, cpg, family in legs(w, D, "gather"):          # (a gather's lane group serves one piece: the option must not reach it)
                 no_fast(fam)
+                chunks_per_group(cpg)
                 rets = torch.full((starts.size,), -77, dtype=torch.int64, device="cuda:0")
                 with ran(only=[family], **{family: 1}):
                     got = cd.gather_rows(batch, starts, rows, rets=rets)
-                assert (rets.cpu().numpy() == rows).all(), (codec, w, D, kind, rows, family)
+                assert (rets.cpu().numpy() == rows).all(), (codec, w, D, kind, rows, family, cpg)
                 bad = np.nonzero((got.cpu().numpy() != want).reshape(starts.size, -1).any(axis=1))[0]
-                assert bad.size == 0, (codec, w, D, kind, rows, family, "ranges that begin at batch rows", starts[bad][:8].tolist())
+                assert bad.size == 0, (codec, w, D, kind, rows, family, cpg, "ranges that begin at batch rows", starts[bad][:8].tolist())
