@@ -52,7 +52,7 @@ extern "C" {
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
- *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes */
+ *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -866,6 +866,62 @@ int sprintz_mi355x_extrema_rows(int codec, int elem_bytes, const void* d_comp, c
                                 uint32_t flags, void* d_min, void* d_max, uint32_t* d_argmin, uint32_t* d_argmax,
                                 void* d_first, void* d_last, uint32_t* d_rows, uint32_t* d_count, int64_t* d_rets,
                                 void* hip_stream);
+/* Segment rows: a row mask's own structure -- per run of selected rows its start, its length and the min / max / sum of every column
+ * over it ("for each excursion above the threshold: when did it start, how long did it last, what was the peak and the integral?"), or
+ * the same per stretch between two set bits ("for each interval between state changes ...": the change log sprintz_mi355x_filter_linear
+ * writes for a state column is that mask) -- fused into the decode: a few bytes a segment leave the chip.
+ *
+ * The batch, the flags and the mask's layout are sprintz_mi355x_aggregate_rows' (chunk_len % ndims == 0 is required; D = ndims,
+ * R = chunk_len / D, MB = ceil(R / 8)); d_mask is required.  rows_c is the number of whole rows chunk c's stream holds, and b[r] is bit
+ * r & 7 of d_mask[c*MB + (r >> 3)] for r < rows_c and 0 for every other r: padding bits and the bits of rows the stream does not hold
+ * are ignored whatever they contain.  `mode` decides for every row r < rows_c whether it is a MEMBER of a segment and whether it STARTS one:
+ *   SPRINTZ_SEG_RUNS  : member = b[r]; start = b[r] && !b[r-1], with b[-1] = 0 -- the segments are the maximal runs of selected rows,
+ *                       and the rows between them belong to none
+ *   SPRINTZ_SEG_SPLITS: every row is a member; start = b[r] || r == 0 -- the segments tile the chunk's rows, a set bit opens a new one
+ * Segment i of chunk c is its i-th start s_i in ascending order and covers rows [s_i, e_i), e_i the first row behind s_i that is not a
+ * member or is a start, else rows_c.  Segments are relative to the chunk: one that goes on in the next chunk is two segments here
+ * (the second starts at that chunk's row 0).  Its place is p = d_bases[c] + i; a place >= capacity is dropped (compared in 64 bits) and
+ * nothing else is written.  The call writes, over the rows of the segment,
+ *   d_min  : the unsigned minimum of column d, element type (uint8 / uint16), at p*D + d   (ops & SPRINTZ_SEG_MIN)
+ *   d_max  : the unsigned maximum, element type, at p*D + d                                (ops & SPRINTZ_SEG_MAX)
+ *   d_sum  : the sum, uint64, at p*D + d                                                   (ops & SPRINTZ_SEG_SUM)
+ *   d_rows : e_i - s_i, uint32, at p                                                       (ops & SPRINTZ_SEG_ROWS)
+ *   d_start: the batch row c*R + s_i, uint64, at p                                         (ops & SPRINTZ_SEG_START)
+ * on the values decompress_batch writes under the same options (SPRINTZ_OPT_REF_DECODER_QUIRK included).  An output not selected may
+ * be NULL and is not touched.  Every entry has one writer and there are no atomics: the output is deterministic.  d_bases may come in
+ * any order and with gaps; sprintz_mi355x_segment_count gives every chunk's number of segments, of which the caller forms the exclusive
+ * prefix sum, as for sprintz_mi355x_select_rows.
+ * d_rets (optional) as in aggregate_rows: elements decoded, or < 0 for a damaged chunk.  Of such a chunk only the places
+ * [d_bases[c], d_bases[c] + the starts of its mask over rows 0 .. R-1) are unspecified -- nothing is written outside them, and every
+ * other chunk is exact.
+ * The call does not read the mask on the host, does not synchronise and does not allocate.  Its launch counts under DEC_FAST
+ * (csrc/decode_fast.h: the shapes aggregate_rows takes there) or DEC_GENERIC (csrc/decode_kernel.h: everything else, the
+ * low-dimension layouts included -- csrc/decode_uni.h is not taught the mode).
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown mode, ops
+ * outside 1..31, a selected output that is NULL, a NULL d_comp / d_offsets / d_mask / d_bases, a selected d_min / d_max not aligned to
+ * the element size, a selected d_rows not aligned to 4 bytes, a selected d_sum / d_start, d_bases or d_rets not aligned to 8 bytes, an
+ * unknown flag; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0 returns 0 and launches nothing. */
+#define SPRINTZ_SEG_RUNS   0u
+#define SPRINTZ_SEG_SPLITS 1u
+#define SPRINTZ_SEG_MIN   1u
+#define SPRINTZ_SEG_MAX   2u
+#define SPRINTZ_SEG_SUM   4u
+#define SPRINTZ_SEG_ROWS  8u
+#define SPRINTZ_SEG_START 16u
+int sprintz_mi355x_segment_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t mode, const uint64_t* d_bases,
+                                uint64_t capacity, uint32_t ops, uint32_t flags, void* d_min, void* d_max, uint64_t* d_sum,
+                                uint32_t* d_rows, uint64_t* d_start, int64_t* d_rets, void* hip_stream);
+/* The segments of every chunk's mask, for sprintz_mi355x_segment_rows' bases: d_counts[c] (uint32) is the number of starts under `mode`
+ * among the rows r < rows_c of chunk c.  The call reads the mask alone, never the container: rows_c is R = chunk_len / ndims where d_lens
+ * is NULL, and min(R, d_lens[c] / ndims) -- 0 for a negative entry -- where it is given: a chunk's element count as any earlier call's
+ * d_rets or sprintz_mi355x_zone_map's d_zlen holds it.  With the true lengths the count is what segment_rows writes for every undamaged
+ * chunk.  The mask may start at any address; padding bits and the bits of rows >= rows_c are not trusted.  One launch (it does not count
+ * under a SPRINTZ_KF_* family), no synchronisation, no allocation.
+ * Returns SPRINTZ_E_INVALID for ndims == 0, chunk_len outside 1..2^30, chunk_len % ndims != 0, an unknown mode, a NULL d_mask / d_counts
+ * (with nchunks > 0), d_counts not aligned to 4 bytes or d_lens not aligned to 8.  nchunks == 0 returns 0 and launches nothing. */
+int sprintz_mi355x_segment_count(const uint8_t* d_mask, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, uint32_t mode,
+                                 const int64_t* d_lens, uint32_t* d_counts, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -171,6 +171,12 @@ groupby_rows = _sig("sprintz_mi355x_groupby_rows", _i, _i, _i, _vp, _vp, _u64, _
 EXT_MIN, EXT_MAX, EXT_ARGMIN, EXT_ARGMAX, EXT_FIRST, EXT_LAST, EXT_ROWS, EXT_COUNT = 1, 2, 4, 8, 16, 32, 64, 128
 EXT_NO_ROW = 0xFFFFFFFF
 extrema_rows = _sig("sprintz_mi355x_extrema_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+# per run of rows a mask names (or per stretch between two set bits) its start, length and min / max / sum, placed behind the chunk's base;
+# and every chunk's number of them (include/sprintz_mi355x.h)
+SEG_RUNS, SEG_SPLITS = 0, 1
+SEG_MIN, SEG_MAX, SEG_SUM, SEG_ROWS, SEG_START = 1, 2, 4, 8, 16
+segment_rows = _sig("sprintz_mi355x_segment_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _vp, _u32, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+segment_count = _sig("sprintz_mi355x_segment_count", _i, _vp, _u64, _u32, _u16, _u32, _vp, _vp, _vp)
 query = {
     ("delta", 1): _sig("sprintz_mi355x_query_delta_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
     ("xff", 1): _sig("sprintz_mi355x_query_xff_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
@@ -243,6 +249,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_gather_rows", "sprintz_mi355x_filter_rows", "sprintz_mi355x_filter_row_ids", "sprintz_mi355x_filter_linear", "sprintz_mi355x_filter_linear_tmp_bytes", "sprintz_mi355x_select_rows",
     "sprintz_mi355x_zone_map", "sprintz_mi355x_zone_prune_tmp_bytes", "sprintz_mi355x_zone_prune_box", "sprintz_mi355x_zone_prune_linear", "sprintz_mi355x_zone_expand",
     "sprintz_mi355x_aggregate_rows", "sprintz_mi355x_histogram_rows", "sprintz_mi355x_moments_rows", "sprintz_mi355x_groupby_rows", "sprintz_mi355x_extrema_rows",
+    "sprintz_mi355x_segment_rows", "sprintz_mi355x_segment_count",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",
     "sprintz_mi355x_compress_batch_colmajor", "sprintz_mi355x_compress_batch_colmajor_dense", "sprintz_mi355x_decompress_batch_colmajor",

@@ -968,6 +968,77 @@ class ChunkedCodec:
         return {"t_first": e["first_row"], "v_first": e["first"], "t_min": e["argmin"], "v_min": e["min"],
                 "t_max": e["argmax"], "v_max": e["max"], "t_last": e["last_row"], "v_last": e["last"]}
 
+    _SEG_OPS = ("min", "max", "sum")
+
+    def segment_rows(self, batch, mask, mode="runs", ops=("min", "max", "sum"), min_rows=1, general_layout=False, check=True):
+        """A row mask's own structure, fused into the decode: per segment its first batch row, its length and the min / max / sum of every
+        column over it -- a few bytes a segment leave the chip.
+
+        mask: uint8 [nchunks, MB] in filter_rows' layout (MB = ceil(R / 8), R = chunk_len / ndims: chunk_len must be a multiple of
+        ndims); bits of rows that do not exist are ignored, whatever they hold.
+        mode="runs": the segments are the maximal runs of selected rows -- event detection: for each excursion, when it started, how
+        long it lasted, its peak ("max") and its integral ("sum").  mode="splits": every row belongs to a segment and a set bit opens a new
+        one -- sessionisation: the mask is a change log (sessions).
+        The kernel's segments are relative to the chunk; they are stitched over the chunk seams here (rowops.fold_segments), so the result
+        is what one chunk holding the whole batch would give.  Then segments shorter than min_rows are dropped.
+        -> {"start": int64 [S] batch rows, "rows": int64 [S], and the selected ops: "min", "max" [S, ndims] of the codec's dtype, "sum"
+        int64 [S, ndims]}, in ascending batch row order.  The call is segment_count (with the lengths total_len gives), a prefix sum, one
+        read of the total, segment_rows and the fold.  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        if mode not in rowops.SEGMENT_MODES:
+            raise ValueError("mode must be 'runs' or 'splits'")
+        ops = rowops.normalise_ops(ops, self._SEG_OPS, "min / max / sum") if ops else ()
+        D, n = self.ndims, batch.nchunks
+        R, MB = rowops.chunk_rows(self.chunk_len, D, "segment_rows")
+        mask = rowops.check_mask(mask, n, MB, self.device)
+        seg_mode = _lib.SEG_RUNS if mode == "runs" else _lib.SEG_SPLITS
+        i64 = dict(dtype=torch.int64, device=self.device)
+        lens = (batch.total_len - torch.arange(n, **i64) * self.chunk_len).clamp(min=0, max=self.chunk_len)
+        counts = torch.zeros(n, dtype=torch.int32, device=self.device)
+        with self._on():
+            _lib.check(_lib.segment_count(mask.data_ptr(), n, self.chunk_len, D, seg_mode, lens.data_ptr(), counts.data_ptr(), self._stream()))
+        counts = counts.to(torch.int64)
+        incl = torch.cumsum(counts, 0)
+        total = int(incl[-1].item()) if n else 0
+        raw = {"start": torch.zeros(total, **i64), "rows32": torch.zeros(total, dtype=torch.int32, device=self.device)}
+        raw.update({k: torch.empty((total, D), dtype=self.dtype, device=self.device) for k in ("min", "max") if k in ops})
+        if "sum" in ops:
+            raw["sum"] = torch.empty((total, D), **i64)
+        if n:
+            bits = _lib.SEG_ROWS | _lib.SEG_START | (_lib.SEG_MIN if "min" in ops else 0) | (_lib.SEG_MAX if "max" in ops else 0) | \
+                   (_lib.SEG_SUM if "sum" in ops else 0)
+            bases = (incl - counts).contiguous()
+            rets = self._rets(n, check)
+            # (no segment at all: the chunks are still checked, and a selected output must be there)
+            hold = {k: v if v.numel() else v.new_empty(D) for k, v in raw.items()}
+            ptr = lambda k: hold[k].data_ptr() if k in hold else None
+            with self._on():
+                _lib.check(_lib.segment_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                             self.chunk_len, D, mask.data_ptr(), seg_mode, bases.data_ptr(), total, bits,
+                                             self._general(general_layout), ptr("min"), ptr("max"), ptr("sum"), ptr("rows32"), ptr("start"),
+                                             rets.data_ptr() if rets is not None else None, self._stream()))
+            if check:
+                rowops.raise_damaged("segment_rows", rets, n, _lib.SprintzError)
+        raw["rows"] = raw.pop("rows32").to(torch.int64)
+        return rowops.fold_segments(raw, mask.view(n, MB), R, mode, min_rows, self.dtype)
+
+    def segments_where(self, batch, lo, hi, mode="all", **kw):
+        """Event detection with event statistics: filter_rows (its lo / hi / mode) and segment_rows(mode="runs") on its mask -- for each
+        excursion into the bounds its start, its length and the min / max / sum of every column over it; two decode-speed launches, the
+        batch is never materialised.  kw: segment_rows' other arguments (ops, min_rows, general_layout, check), and zones, the batch's
+        ZoneMap (zone_map) for the filter step -- that half alone is pruned."""
+        seg = lambda b, mask, **k: self.segment_rows(b, mask, mode="runs", **k)      # noqa: E731
+        return self._where("segments_where", seg, batch, lo, hi, mode, **kw)
+
+    def sessions(self, batch, col, ops=("min", "max", "sum"), min_rows=1, general_layout=False, check=True):
+        """Sessionisation on a state column: for each interval between two changes of column `col` its start, its duration ("rows") and
+        the min / max / sum of every column over it.  filter_change on `col` marks the rows that do NOT change (x[g] == x[g - 1], over the
+        chunk seams too), the mask is inverted in torch -- the change log; its padding bits and the bits of rows that do not exist come out
+        set, which segment_rows ignores -- and segment_rows(mode="splits") cuts the batch at every set bit.  -> segment_rows' result."""
+        same = self.filter_change(batch, col, lo=0, hi=0, general_layout=general_layout, check=check)["mask"]
+        return self.segment_rows(batch, self.torch.bitwise_not(same), mode="splits", ops=ops, min_rows=min_rows, general_layout=general_layout,
+                                 check=check)
+
     def groupby_rows(self, batch, key, nbins=256, key_lo=0, shift=None, mask=None, ops=("count", "sum"), chunks_per_table=0, general_layout=False,
                      check=True):
         """SELECT bin(x_key), count(*), sum(x_0), ..., sum(x_{D-1}) WHERE mask GROUP BY bin(x_key), fused into the decode (one launch; only

@@ -162,9 +162,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // once a block (decode_ops.h: linear_rows8, linear_block).
     constexpr bool LIN = Q == kQueryLinear;
     static_assert(!LIN || (!CM && !SPLIT && DS == 0), "linear filter: plain mappings");
-    // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select and aggregate take a null mask for "every row"
-    constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT;
-    constexpr bool MASK_GIVEN = SELECT || AGG;             // (no test for a null mask where there always is one: select measured 1 % slower with it)
+    // SEG (sprintz_mi355x_segment_rows): aggregate's accumulators over windows whose edges come from the caller's mask -- a run of set bits, or
+    // the stretch between two of them -- placed as select places rows, behind the chunk's base (decode_ops.h: SegState, segment_rows8).
+    // Nothing is stored but the segments' entries; mask read-ahead and the column's 8 waiting rows are aggregate's.
+    constexpr bool SEG = Q == kQuerySegment;
+    static_assert(!SEG || (!CM && !SPLIT && DS == 0), "segments: plain mappings");
+    // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
+    constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
+    constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
     constexpr int DSZ = DS ? DS : DCAP;                    // columns the LDS carve is sized for
     static_assert(DSZ <= DCAP, "sizing columns");
     constexpr uint32_t HDRMAX = (2 * DSZ * HB + 7) / 8;
@@ -383,6 +388,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t arow[8];
     uint32_t acnt = 0;
     uint8_t* fmb = nullptr;
+    // segment rows: the group's walk over its chunk's segments, the block being decoded under the rule, the chunk's base and its first batch
+    // row; seg_loop: some group of the wavefront has a start or an end in its block, so all of them walk their block's rows (wave-uniform)
+    SegState sst{0, 0, 0};
+    SegBlock sblk{0, 0, 0};
+    uint64_t gbase = 0, grow0 = 0;
+    bool seg_loop = false;
     // moments rows: the block's rows of every slot of the lane, and the lane's accumulators (acnt: the window's selected rows)
     uint32_t mrow[CPL][8];
     MomentAcc macc[CPL];
@@ -427,7 +438,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST || EXT || LIN) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT || LIN || SEG) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -460,6 +471,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 uint32_t bs = 0;
 #pragma unroll
                 for (int i = 0; i < 8; i++) aggregate_row<W>(arow[i], aggregate_sel<W>(sm, i), qmin[k], qmax[k], bs);
+                qsum[k] += bs;
+            }
+        } else if constexpr (SEG) {                        // a block with no start and no end takes all 8 rows or none: no row loop
+            if (seg_loop) {
+                segment_rows8<W>(a, sblk, sst, gbase, (uint32_t)D, (uint32_t)genk[k], col_ok[k], [&](int i) { return arow[i]; }, qmin[k], qmax[k], qsum[k]);
+            } else if (sblk.members != 0) {
+                uint32_t bs = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) aggregate_row<W>(arow[i], AggregateSel{MASK, 0u}, qmin[k], qmax[k], bs);
                 qsum[k] += bs;
             }
         } else if constexpr (HIST) {                       // (a lane column past the last one counts nothing)
@@ -523,6 +543,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             window_rows_done(8u);
         }
         if constexpr (HIST) fb++;
+        if constexpr (SEG) {                               // the ended segments' rows and starts leave, the group's state moves on (fb blocks = 8 fb rows in front)
+            segment_block_done(a, sblk, sst, gbase, grow0, 8u * fb, lane_d);
+            fb++;
+        }
         if constexpr (EXT) {                               // the window's first / last selected rows move behind the columns, then as aggregate
             if (sm != 0) extrema_rows8_done(erows, sm, 8u * fb);
             acnt += (uint32_t)__popc(sm);
@@ -597,6 +621,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             if (sm) select_ids(a, sbase + srank, sm, srow0 + 8u * fb, lane_d, DP);
             srank += (uint32_t)__popc(sm);
             fb++;
+        }
+    };
+
+    // segment rows, in front of a block's columns: the block under the rule, and whether any group of the wavefront (of its lanes that are
+    // here) must walk its rows -- one branch a wave instead of both sides of a divergent one
+    auto seg_begin = [&]() {
+        if constexpr (SEG) {
+            sblk = segment_block(a.win.rows, sm, sst.open);
+            seg_loop = __any(segment_block_plain(sblk) ? 0 : 1) != 0;
         }
     };
 
@@ -906,6 +939,26 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fb += len;
             return;
         }
+        if constexpr (SEG && !FIRE && SPRINTZ_SEG_RUN_SHORTCUT) {
+            // a delta run repeats the previous row 8 len times.  One pass over its mask bytes (segment_run_plain): if they hold no start and
+            // no end the run is O(1) -- inside the open segment min / max take the row once and the sum takes it times the run's rows, outside
+            // any nothing happens.  If not, the run is replayed block by block below, on the constant row.
+            if ((uint64_t)len * blk_elems > out_left) { corrupt = true; return; }
+            if (len != 0 && segment_run_plain(a.win.rows, smb, fb, len, sst.open, lane_d, DP)) {
+                out_left -= len * blk_elems;
+                if (sst.open) {
+#pragma unroll
+                    for (int k = 0; k < CPL; k++) {
+                        const uint32_t x = pv[k] & MASK;
+                        qmin[k] = x < qmin[k] ? x : qmin[k];
+                        qmax[k] = x > qmax[k] ? x : qmax[k];
+                        qsum[k] += (uint64_t)x * (8u * len);
+                    }
+                }
+                fb += len;
+                return;
+            }
+        }
         if constexpr (SELECT && !FIRE) {
             // a delta run repeats the previous row and changes no state: a run none of whose rows the mask wants is stepped over
             // (its mask bytes lie inside the chunk's: the run fits the chunk slot)
@@ -937,6 +990,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
             }
             if constexpr (MASKED && !SELECT) sm = (MASK_GIVEN || smb) ? sel_byte(fb) : 0xffu;   // (a FIRE run is replayed for its state, block by block, as the window mode does)
+            seg_begin();
             auto run_step = [&](int k, int coef) {
                 if constexpr (W == 16 && FIRE) {            // pd[k] holds X (delta in its high half), see packed_block
                     pd[k] = mad_i16_hi(pd[k], coef, 0);
@@ -1058,6 +1112,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
         if constexpr (MASKED) sm = (MASK_GIVEN || smb) ? sel_byte(fb) : 0xffu;   // (block fb < chunk_len / blk_elems <= rows.stride: the guard has passed)
+        seg_begin();
         auto col_step = [&](int k, int i, int coef, int& grad) {
             if constexpr (W == 16 && FIRE) {
                 // X = prev_delta*coef + E; delta = hi16(X): pd[k] carries X, never the shifted delta
@@ -1195,6 +1250,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             fb = 0; sm = 0; acnt = 0;
             mwin0 = 0x80000000u;                           // no window yet: the first block loads one
             smb = (MASK_GIVEN || a.rows.mask) ? a.rows.mask + chunk * (uint64_t)a.rows.stride : nullptr;
+        }
+        if constexpr (SEG) {                               // no segment is open, the accumulators hold the identities
+#pragma unroll
+            for (int k = 0; k < CPL; k++) qmin[k] = MASK;
+            sst = SegState{0, 0, 0};
+            sblk = SegBlock{0, 0, 0};
+            seg_loop = false;
+            gbase = a.select.bases[chunk];
+            grow0 = chunk * (uint64_t)a.select.rpc;
         }
         if constexpr (Q == kQueryFilter) {
             fb = 0; fcnt = 0; fl = 0; fcm = 0;
@@ -1396,6 +1460,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if (!corrupt)
             aggregate_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
                                    [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (SEG) {
+        // fb blocks = 8 fb rows lie in front of the tail; the segment open behind the chunk's last row ends there
+        if (!corrupt)
+            segment_tail<W, CPL>(a, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, genk, col_ok, sst, gbase, grow0, qmin, qmax, qsum, lane_d,
+                                 [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (MOM) {
         // fb blocks = 8 fb rows lie in front of the tail
         if (!corrupt)

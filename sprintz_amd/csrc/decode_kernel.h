@@ -37,7 +37,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // are replayed block by block, as for the filter
     constexpr bool LIN = Q == kQueryLinear;
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs), and those of them that count a window's selected rows
-    constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT;
+    // SEG (sprintz_mi355x_segment_rows): aggregate's accumulators over windows whose edges come from the mask, placed behind the chunk's base
+    // (decode_ops.h: SegState, segment_rows8); runs are replayed block by block
+    constexpr bool SEG = Q == kQuerySegment;
+    constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT || SEG;
     constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
@@ -208,6 +211,17 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     uint64_t sbase = 0;
     uint32_t srank = 0;
     if constexpr (Q == kQuerySelect) sbase = a.select.bases[chunk];
+    // segment rows: the group's walk over the chunk's segments (no segment is open, the accumulators hold the identities), the block being
+    // decoded under the rule and the chunk's first batch row
+    SegState sst{0, 0, 0};
+    SegBlock sblk{0, 0, 0};
+    uint64_t grow0 = 0;
+    if constexpr (SEG) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) qmin[k] = MASK;
+        sbase = a.select.bases[chunk];
+        grow0 = chunk * (uint64_t)a.select.rpc;
+    }
     // histogram rows: the lane's columns and the chunk's histogram
     HistCol hcol[CPL];
     if constexpr (HIST) {
@@ -342,7 +356,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         uint32_t fl = 0;                         // filter: this lane's columns' rows, inverted domain
         // (block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride: checked above; all 8 rows of a block exist)
         // (select and aggregate rows always have a mask: no test for them)
-        if constexpr (MASKED) sm = (Q == kQuerySelect || Q == kQueryAggregate || smb) ? (uint32_t)smb[out_elems / blk_elems] : 0xffu;
+        if constexpr (MASKED) sm = (Q == kQuerySelect || Q == kQueryAggregate || SEG || smb) ? (uint32_t)smb[out_elems / blk_elems] : 0xffu;
+        if constexpr (SEG) sblk = segment_block(a.win.rows, sm, sst.open);
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
             int coef = FIRE ? fire_coef<W, LOWDIM>(ctr[k]) : 0;
@@ -377,6 +392,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     for (int i = 0; i < 8; i++) aggregate_row<W>(v[i][k], aggregate_sel<W>(sm, i), qmin[k], qmax[k], bs);
                     qsum[k] += bs;
                 }
+            } else if constexpr (SEG) {          // (a block with no start, no end and no member only moves the predictor on)
+                if ((sblk.members | sblk.ends) != 0)
+                    segment_rows8<W>(a, sblk, sst, sbase, (uint32_t)D, (uint32_t)colk[k], genk[k], [&](int i) { return v[i][k]; }, qmin[k], qmax[k], qsum[k]);
             } else if constexpr (HIST) {
                 if (sm != 0 && genk[k]) {
                     uint32_t xs[8];
@@ -443,6 +461,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 wleft = a.win.rows;
             }
         }
+
+        if constexpr (SEG) segment_block_done(a, sblk, sst, sbase, grow0, out_elems / (uint32_t)D, lane_d);   // behind the block's columns
 
         if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride (checked above)
             const uint32_t m = (group_or_any(fl, DP) ^ finv) & 0xffu;
@@ -571,6 +591,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     } else if constexpr (Q == kQueryAggregate) {
         if (!corrupt) aggregate_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, qmin, qmax, qsum, acnt, lane_d,
                                              [&](uint32_t b) { return (uint32_t)smb[b]; });
+    } else if constexpr (SEG) {
+        if (!corrupt) segment_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, sst, sbase, grow0, qmin, qmax, qsum, lane_d,
+                                           [&](uint32_t b) { return (uint32_t)smb[b]; });
     } else if constexpr (MOM) {
         if (!corrupt) moments_tail<W, CPL>(a, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, colk, genk, wbase, wi, wleft, macc, acnt, lane_d,
                                            [&](uint32_t b) { return (uint32_t)smb[b]; });

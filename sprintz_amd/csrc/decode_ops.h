@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments, group-by, extrema and linear filter rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by, extrema, linear filter and segment rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -835,6 +835,158 @@ __device__ __forceinline__ void extrema_tail(const DecodeArgs& a, const uint8_t*
             if (genuine[k]) extrema_value(acc[k], tail_elem<W>(t, r * D + (uint32_t)col[k]), row0 + r, fresh);
         extrema_value_done(wr, row0 + r, row0 + r);
     });
+}
+
+// ---- segment rows (Q == kQuerySegment; sprintz_mi355x_segment_rows): the aggregate mode with windows whose edges come from the mask.  Its
+// arguments share structs that are here: the mask is RowMaskArgs'; min / max / sum, the per-segment row count (win.row_count) and the
+// selected ops are WindowArgs', whose `rows` carries the segmentation rule (this mode has no W) and whose `count` is unused; the places
+// are SelectArgs' -- segment i of chunk c at bases[c] + i, dropped at or above capacity, its first batch row c * rpc + s_i in ids.
+// The rule (kSegRuns: the maximal runs of set bits; kSegSplits: every row belongs to a segment and a set bit opens a new one) decides
+// per row whether it is a member and whether it starts a segment; a segment ends in front of the first row behind its start that is
+// not a member or is a start, or with the chunk's rows.  What a lane group knows of its chunk's walk (the same in every lane):
+constexpr uint32_t kSegRuns = 0, kSegSplits = 1;
+#ifndef SPRINTZ_SEG_RUN_SHORTCUT
+// 1 (kept): decode_fast.h crosses a delta run whose mask bytes hold no start and no end in O(1) (segment_run_plain); 0: it replays every
+// run block by block, as FIRE runs are -- both measured in profiles/segment_rows.txt
+#define SPRINTZ_SEG_RUN_SHORTCUT 1
+#endif
+struct SegState {
+    uint32_t open;              // a segment is open: it started at chunk row `start`, and has had no end yet
+    uint32_t start;
+    uint32_t rank;              // the segments of the chunk that have ended = the open one's number
+};
+// 8 rows under mask byte m behind state `open`: bit i of members -- row i belongs to a segment; of starts -- it starts one; of ends -- the
+// segment open in front of row i ends there
+struct SegBlock { uint32_t members, starts, ends; };
+__device__ __forceinline__ SegBlock segment_block(uint32_t mode, uint32_t m, uint32_t open)
+{
+    if (mode == kSegSplits) return SegBlock{0xffu, m | (open ? 0u : 1u), m & (open ? 0xffu : 0xfeu)};
+    const uint32_t prev = ((m << 1) | (open ? 1u : 0u)) & 0xffu;                // bit i: row i - 1 is a member
+    return SegBlock{m, m & ~prev, ~m & prev};
+}
+// a block with no start and no end, of members alone or of none: the accumulators take all 8 rows, or nothing happens at all
+__device__ __forceinline__ bool segment_block_plain(const SegBlock& b) { return (b.starts | b.ends) == 0 && (b.members == 0xffu || b.members == 0); }
+// one column's entries of the segment at `place` leave (each entry has one writer -- no atomics), and the accumulators start over from the
+// identities: what they hold while no segment is open
+template <int W>
+__device__ __forceinline__ void segment_flush(const DecodeArgs& a, uint64_t place, uint32_t D, uint32_t col, uint32_t& qmin, uint32_t& qmax, uint64_t& qsum)
+{
+    using U = typename Elem<W>::U;
+    if (place < a.select.capacity) {
+        const uint64_t idx = place * (uint64_t)D + col;
+        if (a.win.ops & 1u) ((U*)a.win.min)[idx] = (U)qmin;
+        if (a.win.ops & 2u) ((U*)a.win.max)[idx] = (U)qmax;
+        if (a.win.ops & 4u) a.win.sum[idx] = qsum;
+    }
+    qmin = Elem<W>::MASK;
+    qmax = 0;
+    qsum = 0;
+}
+// the segment's length and its first batch row leave with its other entries (one lane of the group: one writer an entry)
+__device__ __forceinline__ void segment_flush_rows(const DecodeArgs& a, uint64_t place, uint64_t start, uint32_t rows, int lane_d)
+{
+    if (lane_d != 0 || place >= a.select.capacity) return;
+    if (a.win.row_count) a.win.row_count[place] = rows;
+    if (a.select.ids) a.select.ids[place] = start;
+}
+// one column's 8 rows x(i) (garbage above bit W allowed) of the block `b`, behind the columns of the group's state `st` (which
+// segment_block_done moves on once, behind all columns): every end inside the block is a flush of the column's entries, at the places
+// base + st.rank, + 1, ...; the rows between belong to the accumulators where they are members (aggregate_row)
+template <int W, typename F>
+__device__ __forceinline__ void segment_rows8(const DecodeArgs& a, const SegBlock& b, const SegState& st, uint64_t base, uint32_t D, uint32_t col, bool genuine,
+                                              F x, uint32_t& qmin, uint32_t& qmax, uint64_t& qsum)
+{
+    using U = typename Elem<W>::U;
+    uint32_t bs = 0;
+    const uint64_t place = base + st.rank;
+    // the places the block's ends may still take below capacity, and the first one's entry: an end moves on by one place and D entries
+    uint32_t room = place < a.select.capacity ? (uint32_t)(a.select.capacity - place < 8u ? a.select.capacity - place : 8u) : 0u;
+    if (!genuine) room = 0;
+    uint64_t idx = place * (uint64_t)D + col;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        if ((b.ends >> i) & 1u) {
+            qsum += bs;
+            bs = 0;
+            if (room != 0) {
+                if (a.win.ops & 1u) ((U*)a.win.min)[idx] = (U)qmin;
+                if (a.win.ops & 2u) ((U*)a.win.max)[idx] = (U)qmax;
+                if (a.win.ops & 4u) a.win.sum[idx] = qsum;
+                room--;
+            }
+            idx += D;
+            qmin = Elem<W>::MASK;
+            qmax = 0;
+            qsum = 0;
+        }
+        aggregate_row<W>(x(i), aggregate_sel<W>(b.members, i), qmin, qmax, bs);
+    }
+    qsum += bs;
+}
+// behind a block's columns: the ended segments' lengths and starts leave, and the state moves over the 8 rows from chunk row row0 on
+// (srow0: the batch row of the chunk's row 0)
+__device__ __forceinline__ void segment_block_done(const DecodeArgs& a, const SegBlock& b, SegState& st, uint64_t base, uint64_t srow0, uint32_t row0, int lane_d)
+{
+    if ((b.starts | b.ends) == 0) return;
+    for (uint32_t i = 0; i < 8u; i++) {
+        if ((b.ends >> i) & 1u) {
+            segment_flush_rows(a, base + st.rank, srow0 + st.start, row0 + i - st.start, lane_d);
+            st.rank++;
+            st.open = 0;
+        }
+        if ((b.starts >> i) & 1u) {
+            st.start = row0 + i;
+            st.open = 1;
+        }
+    }
+}
+// Do the 8 * nblocks rows that a delta run repeats from block first_block of the chunk on hold no start and no end -- all of them members
+// of the open segment, or none a member of any?  One strided pass over those mask bytes, spread over the group's lanes.  EVERY lane of
+// the group must come here: the answer is a group reduction.
+__device__ __forceinline__ bool segment_run_plain(uint32_t mode, const uint8_t* mask_bytes, uint32_t first_block, uint32_t nblocks, uint32_t open, int lane_d, int DP)
+{
+    if (mode == kSegSplits && !open) return false;             // the chunk's row 0 starts a segment
+    const uint32_t want = (mode == kSegRuns && open) ? 0xffu : 0u;
+    uint32_t diff = 0;
+    for (uint32_t j = (uint32_t)lane_d; j < nblocks; j += (uint32_t)DP) diff |= (uint32_t)mask_bytes[first_block + j] ^ want;
+    for (int off = DP >> 1; off > 0; off >>= 1) diff |= (uint32_t)__shfl_xor((int)diff, off, DP);
+    return diff == 0;
+}
+// The verbatim tail (masked_tail_rows) and the chunk's end: every whole row of the tail walks the rule -- an end flushes, a start opens, a
+// member's elements reach the accumulators of the lane's genuine columns -- and then the segment still open ends with the chunk's rows.
+template <int W, int CPL, typename F>
+__device__ __forceinline__ void segment_tail(const DecodeArgs& a, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t row0, const int (&col)[CPL],
+                                             const bool (&genuine)[CPL], SegState st, uint64_t base, uint64_t srow0, uint32_t (&qmin)[CPL], uint32_t (&qmax)[CPL],
+                                             uint64_t (&qsum)[CPL], int lane_d, F mask_at)
+{
+    const uint32_t mode = a.win.rows, nfull = remaining / D;
+    auto close = [&](uint32_t end) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++)
+            if (genuine[k]) segment_flush<W>(a, base + st.rank, D, (uint32_t)col[k], qmin[k], qmax[k], qsum[k]);
+        segment_flush_rows(a, base + st.rank, srow0 + st.start, end - st.start, lane_d);
+        st.rank++;
+        st.open = 0;
+    };
+    masked_tail_rows(nfull, row0, true, mask_at, [&](uint32_t r, bool on) {
+        const bool member = mode == kSegSplits || on;
+        const bool start = mode == kSegSplits ? (on || !st.open) : (on && !st.open);
+        if (st.open && (start || !member)) close(row0 + r);
+        if (start) {
+            st.start = row0 + r;
+            st.open = 1;
+        }
+        if (!member) return;
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!genuine[k]) continue;
+            const uint32_t x = tail_elem<W>(t, r * D + (uint32_t)col[k]);
+            qmin[k] = x < qmin[k] ? x : qmin[k];
+            qmax[k] = x > qmax[k] ? x : qmax[k];
+            qsum[k] += x;
+        }
+    });
+    if (st.open) close(row0 + nfull);
 }
 
 // ---- select rows: the places of the rows of one 8-row block (or of 8 rows of the tail) whose bits are set in m, behind `first` -- the

@@ -16,7 +16,7 @@
 
 namespace sprintz {
 
-// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryLinear).  Each forwards to the
+// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQuerySegment).  Each forwards to the
 // translation unit that holds the instantiation -- decode_w8.hip / decode_w16.hip for the plain decode and the reduce / window
 // queries, a unit of its own for every other mode (SPRINTZ_ROW_OP_UNITS below) -- so that every unit keeps its compile flags.
 // generic lane mapping, both layouts, up to 512 columns (decode_kernel.h)
@@ -24,7 +24,7 @@ hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, 
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h); gather and select for rows of whole 16-byte pieces
 // (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments, group-by, extrema and the linear filter
+// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments, group-by, extrema, the linear filter and segments
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // internal -- the units' own entry points, reached through the three launchers above alone (api.hip).  A unit refuses a width or
 // a mode it does not hold; the decode_uni units size their grid themselves (decode_uni_threads) and ignore `grid`
@@ -34,13 +34,15 @@ hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hip
 SPRINTZ_DECODE_UNIT_DECL(w8)
 SPRINTZ_DECODE_UNIT_DECL(w16)
 // the row operations' units, a mode each, in the order of their kQuery* numbers (api.hip builds its table of units from this list)
-#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby) X(extrema) X(linear)
+#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby) X(extrema) X(linear) X(segment)
 SPRINTZ_ROW_OP_UNITS(SPRINTZ_DECODE_UNIT_DECL)
 hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_filter(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // filter_row_ids: a mask of filter_rows into ascending batch row numbers, a lane group per chunk (decode_filter.hip)
 hipError_t launch_filter_row_ids(const uint8_t* mask, const uint64_t* bases, uint64_t nchunks, uint32_t rows, uint64_t* ids, uint64_t capacity, hipStream_t st);
+// segment_count: the segments of every chunk's mask under rule `mode`, over the rows lens (optional: element counts) says the chunk holds (decode_segment.hip)
+hipError_t launch_segment_count(const uint8_t* mask, uint64_t nchunks, uint32_t rows, uint32_t D, uint32_t mode, const int64_t* lens, uint32_t* counts, hipStream_t st);
 // filter_linear's seam pass: row 0 of every chunk behind the first takes the last row of the chunk in front as its predecessor (decode_linear.hip)
 hipError_t launch_linear_seam(int esz, const DecodeArgs& a, hipStream_t st);
 // small batches: one workgroup per chunk, both layouts, 1 .. 64 columns (decode_lat.h); bound_bytes = the longest stream a chunk can have
@@ -166,7 +168,7 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
     if (q == kQueryWindow) { SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, kQueryWindow, false) }         \
     return hipErrorInvalidValue;
 
-// every mapping the windowed query has, row-major: the row operations that store no rows (filter, aggregate, histogram, moments, group-by, extrema, linear filter)
+// every mapping the windowed query has, row-major: the row operations that store no rows (filter, aggregate, histogram, moments, group-by, extrema, linear filter, segments)
 #define SPRINTZ_DISPATCH_DECODE_FAST_ROWS(KERNEL, W, Q) SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, Q, false)
 // gather and select: row-major destination, rows of whole 16-byte store pieces -- 16 columns and more, or 8 columns of 16 bits
 #define SPRINTZ_FAST_PIECES_8(KERNEL, Q)

@@ -272,8 +272,8 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by, nor the extrema, nor the linear filter: those shapes go to the generic kernel)
-    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && s.q != kQueryGroupBy && s.q != kQueryExtrema && s.q != kQueryLinear && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
+    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by, nor the extrema, nor the linear filter, nor the segments: those shapes go to the generic kernel)
+    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && s.q != kQueryGroupBy && s.q != kQueryExtrema && s.q != kQueryLinear && s.q != kQuerySegment && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
     if (table_bytes) {                                         // nothing is staged: the table is the launch's LDS
         p.wg_chunks = table_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D, s.table_row_max);
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, table_bytes);

@@ -1,5 +1,5 @@
 // row_ops.hip -- the row operations of the C-ABI (include/sprintz_mi355x.h): queries, the zone map, filters, select, aggregate,
-// moments, extrema, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
+// moments, extrema, segments, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
 // fills its QuerySpec and hands over to decode_batch (entry.h); what the decoders then do with a row is decode_ops.h's.
 #include "entry.h"
 
@@ -388,6 +388,54 @@ int sprintz_mi355x_extrema_rows(int codec, int elem_bytes, const void* d_comp, c
     qs.win.row_count = (uint32_t*)out[7].p;
     qs.ext = ExtremaArgs{(uint32_t*)out[2].p, (uint32_t*)out[3].p, out[4].p, out[5].p, (uint32_t*)out[6].p};
     return decode_batch(b, nullptr, d_rets, (hipStream_t)hip_stream, qs);
+}
+
+// ---------------------------------------------------------------- segment rows
+int sprintz_mi355x_segment_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, uint32_t mode, const uint64_t* d_bases,
+                                uint64_t capacity, uint32_t ops, uint32_t flags, void* d_min, void* d_max, uint64_t* d_sum,
+                                uint32_t* d_rows, uint64_t* d_start, int64_t* d_rets, void* hip_stream)
+{
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims};
+    QuerySpec qs;
+    int rc = masked_row_op("segment_rows", kQuerySegment, b, flags, d_mask, qs);
+    if (rc) return rc;
+    static_assert(SPRINTZ_SEG_RUNS == kSegRuns && SPRINTZ_SEG_SPLITS == kSegSplits, "the rule travels as it is given");
+    if (mode != SPRINTZ_SEG_RUNS && mode != SPRINTZ_SEG_SPLITS) return fail(SPRINTZ_E_INVALID, "segment_rows: mode must be SPRINTZ_SEG_RUNS or SPRINTZ_SEG_SPLITS");
+    if (ops < 1 || ops > 31) return fail(SPRINTZ_E_INVALID, "segment_rows: ops must be a non-empty OR of SPRINTZ_SEG_MIN / _MAX / _SUM / _ROWS / _START");
+    if (!d_mask || !d_bases) return fail(SPRINTZ_E_INVALID, "segment_rows: null device pointer");
+    static_assert(SPRINTZ_SEG_MIN == 1u && SPRINTZ_SEG_MAX == 2u && SPRINTZ_SEG_SUM == 4u && SPRINTZ_SEG_ROWS == 8u && SPRINTZ_SEG_START == 16u, "out[i] is op bit i");
+    OpOutput out[5] = {{d_min, elem_bytes}, {d_max, elem_bytes}, {d_sum, 8}, {d_rows, 4}, {d_start, 8}};
+    if ((rc = check_op_outputs("segment_rows", ops, out, d_rets, "min / max must be aligned to the element size, rows to 4 bytes, sum, start and d_rets to 8"))) return rc;
+    if ((uintptr_t)d_bases % 8) return fail(SPRINTZ_E_INVALID, "segment_rows: d_bases must be aligned to 8 bytes");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    // the mode has no struct of its own (decode_ops.h, segment rows): the rule rides where the windowed modes keep W, the places are select's
+    qs.win.rows = mode;
+    qs.win.count = 0;
+    qs.win.ops = ops & 7u;
+    qs.win.min = out[0].p;
+    qs.win.max = out[1].p;
+    qs.win.sum = (uint64_t*)out[2].p;
+    qs.win.row_count = (uint32_t*)out[3].p;
+    qs.select = SelectArgs{d_bases, capacity, (uint64_t*)out[4].p, chunk_len / ndims};
+    return decode_batch(b, nullptr, d_rets, (hipStream_t)hip_stream, qs);
+}
+
+int sprintz_mi355x_segment_count(const uint8_t* d_mask, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, uint32_t mode,
+                                 const int64_t* d_lens, uint32_t* d_counts, void* hip_stream)
+{
+    if (ndims == 0 || chunk_len == 0 || chunk_len > (1u << 30)) return fail(SPRINTZ_E_INVALID, "segment_count: ndims == 0 or chunk_len outside 1..2^30");
+    if (chunk_len % ndims) return fail(SPRINTZ_E_INVALID, "segment_count: chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    if (mode != SPRINTZ_SEG_RUNS && mode != SPRINTZ_SEG_SPLITS) return fail(SPRINTZ_E_INVALID, "segment_count: mode must be SPRINTZ_SEG_RUNS or SPRINTZ_SEG_SPLITS");
+    if (nchunks > 0 && (!d_mask || !d_counts)) return fail(SPRINTZ_E_INVALID, "segment_count: null device pointer");
+    if ((uintptr_t)d_counts % 4 || (uintptr_t)d_lens % 8) return fail(SPRINTZ_E_INVALID, "segment_count: d_counts must be aligned to 4 bytes, d_lens to 8");
+    if (nchunks == 0) return 0;
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (launch_segment_count(d_mask, nchunks, chunk_len / ndims, ndims, mode, d_lens, d_counts, (hipStream_t)hip_stream) != hipSuccess)
+        return fail(SPRINTZ_E_HIP, "segment_count kernel launch");
+    return 0;
 }
 
 // ---------------------------------------------------------------- histogram rows

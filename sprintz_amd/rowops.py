@@ -1,6 +1,6 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, extrema_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the first damaged chunk, the default bin shift, bounds and offsets as tensors, the
+moments_rows, groupby_rows, extrema_rows, segment_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, the default bin shift, bounds and offsets as tensors, the
 linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
@@ -121,6 +121,47 @@ def fold_extrema(res, n, nwin, D, W, fold, total_len, esz, dtype):
     if "count" in g:
         out["count"] = g["count"].sum(dim=1)
     return out
+
+
+SEGMENT_MODES = ("runs", "splits")
+
+
+def fold_segments(res, mask, R, mode, min_rows, dtype):
+    """segment_rows' chunk-relative segments, stitched over the chunk seams on batch rows: what the segment model yields for the batch
+    taken as ONE chunk.  res: "start", "rows": int64 [S] -- a segment's first batch row and its length, in ascending batch row order (the
+    order of the places when the bases are the counts' prefix sum) -- and any of "min", "max": [S, D] of `dtype`, "sum": int64 [S, D].
+    mask: the call's mask, uint8 [nchunks, MB]; R: rows of a chunk slot; mode: "runs" / "splits".
+    Segment p continues p - 1 iff it starts where p - 1 ends and that row is a chunk's row 0 -- and, under "splits", bit 0 of that chunk's
+    mask is clear (a set bit opens a new segment there whatever lies in front).  Continued segments combine by min of mins, max of
+    maxes, sums and rows added; then segments shorter than min_rows are dropped.  -> the same keys, [S'] / [S', D]."""
+    if mode not in SEGMENT_MODES:
+        raise ValueError("mode must be 'runs' or 'splits'")
+    start, rows = res["start"].to(torch.int64).reshape(-1), res["rows"].to(torch.int64).reshape(-1)
+    S = start.numel()
+    if S == 0:
+        return dict(res)
+    cont = torch.zeros(S, dtype=torch.bool, device=start.device)
+    cont[1:] = (start[1:] == start[:-1] + rows[:-1]) & (start[1:] % R == 0)
+    if mode == "splits":
+        bit0 = mask.reshape(-1, -(-R // 8))[start // R, 0] & 1
+        cont &= bit0 == 0
+    head = ~cont
+    gid = torch.cumsum(head.to(torch.int64), 0) - 1         # the stitched segment each chunk-relative one belongs to
+    G = int(gid[-1].item()) + 1
+    out = {"start": start[head], "rows": torch.zeros(G, dtype=torch.int64, device=start.device).index_add_(0, gid, rows)}
+    for k in ("min", "max", "sum"):
+        if k not in res:
+            continue
+        v = res[k]
+        D = v.shape[-1]
+        idx = gid.reshape(S, 1).expand(S, D)
+        if k == "sum":
+            out[k] = torch.zeros((G, D), dtype=torch.int64, device=v.device).scatter_add_(0, idx, v.to(torch.int64))
+        else:                                               # (as int32: torch's uint16 lacks most reductions)
+            out[k] = torch.zeros((G, D), dtype=torch.int32, device=v.device).scatter_reduce_(
+                0, idx, v.to(torch.int32), "amin" if k == "min" else "amax", include_self=False)
+    keep = out["rows"] >= int(min_rows)
+    return {k: v[keep].to(dtype) if k in ("min", "max") else v[keep] for k, v in out.items()}
 
 
 def first_bad(rets, n):
