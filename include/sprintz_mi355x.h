@@ -52,7 +52,8 @@ extern "C" {
  *      later, additively: huf0_exact_tmp_bytes / huf0_compress_batch_exact; query_windows, SPRINTZ_QUERY_WIN_MIN / _MAX / _SUM; gather_rows;
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
- *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_* */
+ *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
+ *      float_rows, SPRINTZ_FLOAT_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -922,6 +923,34 @@ int sprintz_mi355x_segment_rows(int codec, int elem_bytes, const void* d_comp, c
  * (with nchunks > 0), d_counts not aligned to 4 bytes or d_lens not aligned to 8.  nchunks == 0 returns 0 and launches nothing. */
 int sprintz_mi355x_segment_count(const uint8_t* d_mask, uint64_t nchunks, uint32_t chunk_len, uint16_t ndims, uint32_t mode,
                                  const int64_t* d_lens, uint32_t* d_counts, void* hip_stream);
+/* Float rows: the batch decoded straight into scaled float32 / float16 / bfloat16 -- the integer tensor never exists.  The batch is given
+ * as to sprintz_mi355x_select_rows (chunk_len % ndims == 0; the RLE codecs; at most 512 columns; a short last chunk may end mid-row).
+ * For element e of chunk c, in column d = e % ndims, with x the decoded element:
+ *   v   = x, unsigned -- or x sign-extended from 8 / 16 bits with SPRINTZ_FLOAT_SIGNED in flags
+ *   z   = fl32(fl32((float)v * d_scale[d]) + d_offset[d])     two IEEE float32 roundings to nearest even, never one fused multiply-add
+ *   out = z                                    SPRINTZ_FLOAT_F32
+ *       = z rounded to nearest even, binary16  SPRINTZ_FLOAT_F16   (overflow gives +-inf, subnormals are kept)
+ *       = z rounded to nearest even, bfloat16  SPRINTZ_FLOAT_BF16  (subnormals are kept)
+ * which is, bit for bit, (x.to(float32) * scale + offset).to(dtype) of PyTorch on the CPU.  float32 subnormals are kept too.
+ *   d_scale, d_offset: float32 [ndims] on the device.  A NULL d_scale is all 1, a NULL d_offset all 0, with the bits of the explicit arrays.
+ *                With finite parameters no NaN can arise; with others the arithmetic is still IEEE float32, and a NaN becomes some quiet NaN.
+ *   flags      : SPRINTZ_QUERY_GENERAL_LAYOUT, SPRINTZ_FLOAT_SIGNED and nothing else
+ *   d_out      : nchunks * chunk_len elements of the output type; element e of chunk c at d_out[c * chunk_len + e], as decompress_batch places
+ *                it, and nothing is written past a chunk's decoded count
+ *   d_rets     : (optional) exactly what sprintz_mi355x_decompress_batch writes for the same batch, damaged chunks included
+ * One launch (SPRINTZ_KF_DEC_FAST for rows of whole 16-byte pieces, ndims * elem_bytes % 16 == 0, with d_out 16-byte aligned and the other
+ * conditions of the plain decode's fast path, counted in OUTPUT bytes; SPRINTZ_KF_DEC_GENERIC otherwise), no synchronisation, no allocation.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown flag or
+ * out_format, a NULL d_comp / d_offsets / d_out, d_out not aligned to the output element size, d_scale / d_offset not aligned to 4 bytes,
+ * d_rets not aligned to 8; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0 returns 0 and
+ * launches nothing. */
+#define SPRINTZ_FLOAT_F32  0
+#define SPRINTZ_FLOAT_F16  1
+#define SPRINTZ_FLOAT_BF16 2
+#define SPRINTZ_FLOAT_SIGNED 2u   /* in flags, next to SPRINTZ_QUERY_GENERAL_LAYOUT */
+int sprintz_mi355x_float_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                              uint32_t chunk_len, uint16_t ndims, int out_format, const float* d_scale, const float* d_offset,
+                              uint32_t flags, void* d_out, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -645,6 +645,41 @@ class ChunkedCodec:
             rowops.raise_damaged("select_rows", rets, n, _lib.SprintzError)
         return res
 
+    def float_rows(self, batch, dtype=None, scale=None, offset=None, signed=False, out=None, rets=None, general_layout=False, check=True):
+        """The batch decoded straight into floats: element x of column d leaves as (x.to(float32) * scale[d] + offset[d]).to(dtype), bit
+        for bit what torch computes on the CPU, in one launch -- the integer tensor never exists.
+
+        dtype: torch.float32 (the default), torch.float16 or torch.bfloat16.  scale / offset: a number, a sequence of ndims numbers or
+        a tensor of ndims elements (host values must be finite); None is all 1 / all 0.  signed=True reads the elements as int8 / int16.
+        chunk_len must be a multiple of ndims.  datasets.dequantize_params gives the scale and offset that invert datasets.quantize.
+        -> a tensor of batch.total_len elements of dtype (chunk c at c * chunk_len), viewed [rows, ndims] when total_len % ndims == 0.
+        out: a contiguous tensor of dtype with at least nchunks * chunk_len elements to write into; rets: an int64 tensor of nchunks
+        entries for the per-chunk element counts.  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        fmt = rowops.float_format(dtype)
+        D, n = self.ndims, batch.nchunks
+        rowops.chunk_rows(self.chunk_len, D, "float_rows")
+        scale = rowops.float_params(scale, D, "scale", self.device)
+        offset = rowops.float_params(offset, D, "offset", self.device)
+        if out is None:
+            out = torch.empty(n * self.chunk_len, dtype=dtype, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != dtype or out.device != self.device or out.numel() < n * self.chunk_len or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor of at least {n} x {self.chunk_len} elements on {self.device}")
+        if rets is None:
+            rets = self._rets(n, check)
+        if n:
+            with self._on():
+                _lib.check(_lib.float_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n,
+                                           self.chunk_len, D, fmt, scale.data_ptr() if scale is not None else None,
+                                           offset.data_ptr() if offset is not None else None,
+                                           self._general(general_layout) | (_lib.FLOAT_SIGNED if signed else 0), out.data_ptr(),
+                                           rets.data_ptr() if rets is not None else None, self._stream()))
+            if check:
+                rowops.raise_damaged("float_rows", rets, n, _lib.SprintzError)
+        res = out.view(-1)[: batch.total_len]
+        return res.view(-1, D) if batch.total_len % D == 0 else res
+
     def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False, zones=None):
         """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
         filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.

@@ -167,6 +167,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // Nothing is stored but the segments' entries; mask read-ahead and the column's 8 waiting rows are aggregate's.
     constexpr bool SEG = Q == kQuerySegment;
     static_assert(!SEG || (!CM && !SPLIT && DS == 0), "segments: plain mappings");
+    // FLT (sprintz_mi355x_float_rows): a plain decode whose store pieces convert.  Staging and held[][] stay in the element type -- the LDS
+    // carve and the registers a block waits in are the plain decode's -- and a piece becomes float32 / float16 / bfloat16 where it is stored:
+    // 16 input bytes leave as OSZ / ESZ 16-byte stores.  The launch takes only rows of whole 16-byte INPUT pieces, so a lane's piece q holds the
+    // same columns in every block and their scales and offsets are loaded once (fsc / fof).  Everything counted in output bytes -- the
+    // descriptor's base and span, the cursor ovo -- uses the output element's size OSZ, not ESZ.
+    constexpr bool FLT = Q == kQueryFloat;
+    static_assert(!FLT || (!CM && !SPLIT && DS == 0), "float rows: row-major destination, plain mappings");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
     constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -246,10 +253,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // (column-major: the descriptor starts at this wave's first ROW of column 0 and runs to the
     //  end of the last column; offsets are column*col_stride + row, in bytes)
     const uint32_t rows_per_chunk = CM ? a.chunk_len / (uint32_t)(EXACT ? DCAP : a.D) : 0u;
-    const uint64_t out_base = CM ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)rows_per_chunk * ESZ
+    // float rows: the output element's bytes, and the shift that turns a byte offset among decoded elements into one among converted ones
+    const uint32_t OSZ = FLT ? (uint32_t)float_out_bytes(a.filter.mode) : (uint32_t)ESZ;
+    const uint32_t fshift = FLT ? (OSZ == 4u ? (ESZ == 1 ? 2u : 1u) : (ESZ == 1 ? 1u : 0u)) : 0u;
+    const uint64_t out_base = FLT ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * OSZ
+                            : CM ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)rows_per_chunk * ESZ
                             : SELECT ? 0
                                  : (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * ESZ;
-    const uint64_t out_span = CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
+    const uint64_t out_span = FLT ? a.nchunks * (uint64_t)a.chunk_len * OSZ - out_base
+                            : CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
                             : GATHER ? a.gather.nranges * (uint64_t)a.gather.rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
                             : SELECT ? a.select.capacity * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
                                  : a.nchunks * (uint64_t)a.chunk_len * ESZ - out_base;
@@ -590,6 +602,29 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t pcol[PIECES];
 #pragma unroll
     for (int q = 0; q < PIECES; q++) pcol[q] = SELECT ? lane16 + (uint32_t)q * ROW16 - prow[q] * row_stride : 0u;
+    // float rows: the scale and the offset of every element of each of this lane's store pieces (a row is a whole number of pieces, so piece
+    // q starts in the same column of its row in every block); a piece past the block's end (never stored) reads some row's columns too
+    constexpr int FNE = 128 / W;                           // elements of a 16-byte piece
+    float fsc[FLT ? PIECES : 1][FNE], fof[FLT ? PIECES : 1][FNE];
+    if constexpr (FLT) {
+#pragma unroll
+        for (int q = 0; q < PIECES; q++) {
+            const uint32_t c0 = ((lane16 + (uint32_t)q * ROW16) % row_stride) / ESZ;
+#pragma unroll
+            for (int j = 0; j < FNE; j++) {
+                fsc[q][j] = float_scale(a, c0 + (uint32_t)j);
+                fof[q][j] = float_offset(a, c0 + (uint32_t)j);
+            }
+        }
+    }
+    // a held or immediate piece leaves converted: output piece j of it 16 j bytes behind vo, or nowhere
+    auto float_store = [&](const uint4& t, int q, uint32_t vo) {
+        if constexpr (FLT) {
+            float_piece<W>(t, a.filter.mode, fsc[q], fof[q], [&](int j, const uint4& p) {
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, p), orsrc, vo == kDropStore ? kDropStore : vo + 16u * (uint32_t)j, 0, kStoreAux);
+            });
+        }
+    };
     const uint8_t* smb = nullptr;
     uint64_t sbase = 0, srow0 = 0;
     uint32_t srank = 0;
@@ -759,7 +794,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 in = in && ((sm >> prow[q]) & 1u) && p < a.select.capacity;
                 vo = (uint32_t)p * row_stride + pcol[q];   // (select.capacity rows fit 32-bit offsets: the launch checks)
             }
+            if constexpr (FLT) vo = ovo + (u << fshift);   // ovo counts output bytes; the piece's OSZ / ESZ output pieces follow each other
             const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
+            if constexpr (FLT) {
+                if (slot >= 0) { held[slot][q] = t; held_vo[slot][q] = in ? vo : kDropStore; }
+                else float_store(t, q, in ? vo : kDropStore);
+            } else
             if (slot >= 0) {
                 held[slot][q] = t;
 #ifdef SPRINTZ_ABL_NO_GSTORE
@@ -781,7 +821,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
         wave_lds_sync();
-        ovo += blk_bytes;
+        ovo += FLT ? blk_bytes << fshift : blk_bytes;
     };
     auto run_blocks = [&](uint32_t len) {                  // RUN slot: `len` blocks of zero error (:828-958)
         if constexpr (Q == kQueryFilter && !FIRE) {
@@ -1281,7 +1321,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             srow0 = chunk * (uint64_t)a.select.rpc;
         }
         out_left = a.chunk_len;
-        ovo = CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
+        ovo = FLT ? (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * OSZ)
+          : CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
           : GATHER ? (uint32_t)(uint64_t)(gp.obase * ESZ)  // where the chunk's row 0 would land: only rows [lo, hi) are stored, and those lie in `out`
                  : (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * ESZ);
         corrupt = (int)nd_hdr != D;
@@ -1391,6 +1432,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
                 for (int k = 0; k < CPL; k++) store_col(cheld[s2][k], cheld_vo[s2][k]);
+        } else if constexpr (FLT) {                        // the held pieces are converted here, where they are stored
+#pragma unroll
+            for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+                for (int q = 0; q < PIECES; q++) float_store(held[s2][q], q, held_vo[s2][q]);
         } else if constexpr (!query_reduce_only(Q)) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
@@ -1498,7 +1544,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
     }
-    if constexpr (SELECT) {
+    if constexpr (FLT) {
+        // the tail converts element by element, at plain 64-bit addresses (decode_ops.h: float_tail)
+        if (!corrupt && remaining > 0) float_tail<W>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP);
+    } else if constexpr (SELECT) {
         // fb blocks = 8 fb rows lie in front of the tail
         if (!corrupt && remaining > 0)
             select_tail<W>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, 8u * fb, sbase, srank, lane_d, DP, [&](uint32_t b) { return (uint32_t)smb[b]; });

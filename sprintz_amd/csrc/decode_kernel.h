@@ -231,6 +231,18 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     }
     // group-by rows: the chunk's table
     if constexpr (GBY) groupby_of_chunk(a, gctx, chunk);
+    // float rows: each of the lane's columns' scale and offset, loaded once; the format and the sign bit (decode_ops.h: float_value)
+    float fsc[CPL], fof[CPL];
+    uint32_t ffmt = 0, fsb = 0;
+    if constexpr (Q == kQueryFloat) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            fsc[k] = genk[k] ? float_scale(a, (uint32_t)colk[k]) : 1.0f;
+            fof[k] = genk[k] ? float_offset(a, (uint32_t)colk[k]) : 0.0f;
+        }
+        ffmt = a.filter.mode & 3u;
+        fsb = float_sign_bit<W>(a.filter.mode);
+    }
 
     for (;;) {
         uint32_t z[8][CPL];
@@ -517,6 +529,19 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                 select_ids(a, first, m, chunk * (uint64_t)a.select.rpc + r0, lane_d, DP);
             }
             srank += (uint32_t)__popc(m);
+        } else if constexpr (Q == kQueryFloat) {
+            // every sample converted, at the plain decode's place (out_elems + blk_elems <= chunk_len: checked above); 64-bit addresses, so
+            // this kernel takes every layout, every row length and every alignment of the output the element size allows
+            (void)ob;
+            const uint64_t eb = chunk * (uint64_t)a.chunk_len + out_elems;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                const int col = lane_d * CPL + k;
+                if (col < D) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) float_put(a.out, ffmt, eb + (uint64_t)(i * D + col), float_value(v[i][k], fsb, fsc[k], fof[k]));
+                }
+            }
         } else if (cs) {
             const uint32_t r0 = out_elems / (uint32_t)D;
 #pragma unroll
@@ -624,6 +649,11 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (Q == kQuerySelect) {
         if (!corrupt) select_tail<W>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, sbase, srank, lane_d, DP,
                                      [&](uint32_t b) { return (uint32_t)smb[b]; });
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        return;
+    }
+    if constexpr (Q == kQueryFloat) {
+        if (!corrupt) float_tail<W>(a, chunk, s + pos, out_elems, remaining, (uint32_t)D, lane_d, DP);
         if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }

@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments, group-by, extrema, linear filter and segment rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by, extrema, linear filter, segment and float rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -36,9 +36,9 @@ struct GatherArgs {
 // filter rows (Q == kQueryFilter; sprintz_mi355x_filter_rows): row r of chunk c matches if every (mode 0) / some (mode 1) column d
 // has lo[d] <= x <= hi[d], unsigned; bit r & 7 of mask[c * mask_stride + (r >> 3)], the chunk's matches in counts[c]
 struct FilterArgs {
-    const void* lo;             // [D], element type, on the device
-    const void* hi;
-    uint32_t mode;              // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter
+    const void* lo;             // [D], element type, on the device (float rows: the scale, float32 [D] or null)
+    const void* hi;             // (float rows: the offset)
+    uint32_t mode;              // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter (float rows: format | kFloatSignedBit)
     uint8_t* mask;              // optional
     uint32_t* counts;           // optional
     uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
@@ -158,7 +158,7 @@ struct DecodeArgs {
     // arguments in front of them), and the struct keeps the length it has had since group-by rows: those kernels keep their code.
     // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.  The linear filter's took the
     //  other 40: the spare bytes are used up, and the next mode's arguments have to share a struct that is here, as the linear filter shares
-    //  FilterArgs, or move the kernels named above.)
+    //  FilterArgs, or move the kernels named above.  Float rows do: scale, offset and format ride in FilterArgs' lo, hi and mode.)
     WindowArgs win;
     MomentArgs mom;
     BinTableArgs table;
@@ -1274,6 +1274,82 @@ __device__ __forceinline__ void gather_tail(const DecodeArgs& a, const GatherPie
     const uint32_t e_hi = gp.hi * D - out_elems;                              // <= remaining, checked above
     U* const d = (U*)a.out + (gp.obase + (int64_t)out_elems);
     for (uint32_t e = e_lo + (uint32_t)lane_d; e < e_hi; e += (uint32_t)DP) d[e] = (U)tail_elem<W>(t, e);
+}
+
+// ---- float rows (Q == kQueryFloat; sprintz_mi355x_float_rows): a plain decode whose stores convert.  Element e of chunk c, in column
+// d = e % D, leaves at out[c * chunk_len + e] as z = fl32(fl32((float)v * scale[d]) + offset[d]) -- v the unsigned element, or the
+// element sign-extended from W bits -- in float32, or rounded to nearest even to float16 / bfloat16.  The arguments travel in FilterArgs,
+// as the linear filter's outputs do: filter.lo is the scale (float32 [D], null: all 1), filter.hi the offset (null: all 0), filter.mode the
+// format (kFloatF32 / kFloatF16 / kFloatBF16, geom.h) and kFloatSignedBit.  Both roundings are IEEE float32 operations and never one fma.
+__device__ __forceinline__ float float_scale(const DecodeArgs& a, uint32_t col) { return a.filter.lo ? ((const float*)a.filter.lo)[col] : 1.0f; }
+__device__ __forceinline__ float float_offset(const DecodeArgs& a, uint32_t col) { return a.filter.hi ? ((const float*)a.filter.hi)[col] : 0.0f; }
+// the sign bit of the element where the mode is signed, else 0: (x ^ sb) - sb sign-extends a clean x, or leaves it
+template <int W> __device__ __forceinline__ uint32_t float_sign_bit(uint32_t mode) { return (mode & kFloatSignedBit) ? 1u << (W - 1) : 0u; }
+// x is clean (nothing above bit W); the int -> float conversion is exact (|v| < 2^16)
+__device__ __forceinline__ float float_value(uint32_t x, uint32_t sb, float s, float o)
+{
+#pragma clang fp contract(off)
+    const float f = (float)(int)((x ^ sb) - sb);
+    const float m = f * s;
+    return m + o;
+}
+// round to nearest even on the float32 bits; a NaN (non-finite parameters alone) becomes the quiet NaN 0x7FC0
+__device__ __forceinline__ uint32_t float_to_bf16(float z)
+{
+    const uint32_t u = __float_as_uint(z);
+    const uint32_t r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    return (u & 0x7fffffffu) > 0x7f800000u ? 0x7fc0u : r;
+}
+// v_cvt_f16_f32: round to nearest even, overflow to infinity, subnormals kept
+__device__ __forceinline__ uint32_t float_to_f16(float z)
+{
+    const _Float16 h = (_Float16)z;
+    return (uint32_t)__builtin_bit_cast(uint16_t, h);
+}
+// one converted element to its place, plain 64-bit addresses (the generic kernel's blocks, every kernel's tail); fmt is wave-uniform
+__device__ __forceinline__ void float_put(void* out, uint32_t fmt, uint64_t idx, float z)
+{
+    if (fmt == kFloatF32) ((float*)out)[idx] = z;
+    else ((uint16_t*)out)[idx] = (uint16_t)(fmt == kFloatF16 ? float_to_f16(z) : float_to_bf16(z));
+}
+// The verbatim tail: `remaining` elements at t behind the chunk's `out_elems` (a multiple of 8 * D: element e of the tail is in column
+// e % D), spread over the group's lanes
+template <int W>
+__device__ __forceinline__ void float_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t out_elems, uint32_t remaining, uint32_t D, int lane_d, int DP)
+{
+    const uint32_t fmt = a.filter.mode & 3u, sb = float_sign_bit<W>(a.filter.mode);
+    const uint64_t base = chunk * (uint64_t)a.chunk_len + out_elems;
+    for (uint32_t e = (uint32_t)lane_d; e < remaining; e += (uint32_t)DP) {
+        const uint32_t d = e % D;
+        float_put(a.out, fmt, base + e, float_value(tail_elem<W>(t, e), sb, float_scale(a, d), float_offset(a, d)));
+    }
+}
+// One 16-byte piece of decoded elements (8 of 16 bits, 16 of 8) whose columns' scales and offsets the lane holds in sc / of: converted, it
+// is NE / 4 pieces of float32 or NE / 8 of a 16-bit format -- store(j, piece) takes output piece j, 16 j bytes behind the first
+template <int W, typename ST>
+__device__ __forceinline__ void float_piece(const uint4& t, uint32_t mode, const float (&sc)[128 / W], const float (&of)[128 / W], ST store)
+{
+    constexpr int NE = 128 / W;
+    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+    const uint32_t sb = float_sign_bit<W>(mode), fmt = mode & 3u;
+    float z[NE];
+#pragma unroll
+    for (int j = 0; j < NE; j++) {
+        const uint32_t x = W == 16 ? (w[j >> 1] >> (16 * (j & 1))) & 0xffffu : (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+        z[j] = float_value(x, sb, sc[j], of[j]);
+    }
+    if (fmt == kFloatF32) {
+#pragma unroll
+        for (int q = 0; q < NE / 4; q++)
+            store(q, make_uint4(__float_as_uint(z[4 * q]), __float_as_uint(z[4 * q + 1]), __float_as_uint(z[4 * q + 2]), __float_as_uint(z[4 * q + 3])));
+    } else {
+        uint32_t h[NE / 2];
+#pragma unroll
+        for (int j = 0; j < NE / 2; j++)
+            h[j] = fmt == kFloatF16 ? float_to_f16(z[2 * j]) | (float_to_f16(z[2 * j + 1]) << 16) : float_to_bf16(z[2 * j]) | (float_to_bf16(z[2 * j + 1]) << 16);
+#pragma unroll
+        for (int q = 0; q < NE / 8; q++) store(q, make_uint4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]));
+    }
 }
 
 }  // namespace sprintz

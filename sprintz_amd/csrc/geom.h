@@ -33,15 +33,20 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 11 = extrema: per-window min / max with the rows they stand in, the first and the last selected row and the count, of the rows a mask names (or of every row), reduce only;
 // 12 = linear filter: one bit per row -- does bias + sum_d w[d] x[g, d] + sum_d u[d] x[g - 1, d], in wrapping 32-bit arithmetic, lie in [lo, hi]? -- and the
 // chunk's count of them, in the filter's mask layout, reduce only;
-// 13 = segment: per run of rows that a mask names (or per stretch between two set bits) its start, length and min / max / sum, placed behind the chunk's base, reduce only.
+// 13 = segment: per run of rows that a mask names (or per stretch between two set bits) its start, length and min / max / sum, placed behind the chunk's base, reduce only;
+// 14 = float: a plain decode whose stores convert -- every sample leaves as fl32(fl32(x * scale[d]) + offset[d]) in float32, float16 or bfloat16, never as an integer.
 // 6 .. 11 and 13 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13;
+              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
     return q == kQueryReduceOnly || q == kQueryWindow || q == kQueryFilter || q == kQueryAggregate || q == kQueryHistogram || q == kQueryMoments || q == kQueryGroupBy || q == kQueryExtrema || q == kQueryLinear || q == kQuerySegment;
 }
+// float rows: the output format (SPRINTZ_FLOAT_F32 / _F16 / _BF16) and the signed bit travel in one word (FilterArgs::mode, decode_ops.h);
+// an output element's bytes
+constexpr uint32_t kFloatF32 = 0, kFloatF16 = 1, kFloatBF16 = 2, kFloatSignedBit = 4;
+constexpr int float_out_bytes(uint32_t mode) { return (mode & 3u) == kFloatF32 ? 4 : 2; }
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB
 constexpr uint32_t kHistMaxCounters = 16384;

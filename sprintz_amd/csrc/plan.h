@@ -46,6 +46,9 @@ struct Shape {
     // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
     // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
     uint32_t table_entries = 0, table_row_max = 0;
+    // float rows: the bytes of an output element (4, or 2 for float16 / bfloat16) -- what every bound on output BYTES counts in; 0: the mode
+    // stores elements of esz bytes, or nothing
+    int out_esz = 0;
 };
 
 struct Plan {
@@ -167,6 +170,9 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     p.norle = norle ? (codec == SPRINTZ_CODEC_XFF_NORLE ? 2 : 1) : 0;
     p.raw = codec == SPRINTZ_CODEC_BITPACK_NORLE ? 1 : 0;
     p.quirk = decode_ref_quirk(codec, esz, lowdim, k) ? 1 : 0;
+    // float rows store elements of another size: the bytes a chunk slot of the output has are chunk_len x osz
+    const bool flt = s.q == kQueryFloat;
+    const int osz = flt ? s.out_esz : esz;
 
     // 513 .. 2047 columns: one workgroup per chunk (any_ndims.hip) -- the RLE codecs, row-major, plain decode
     if (D > 512) {
@@ -207,7 +213,10 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     // column-major: a lane's 8 samples per block are one aligned 16-byte (8-byte) piece of its column
     const bool fast = cs ? fast_common && s.q == kQueryOff && cs % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0 &&
                                (s.out_lo % 16) == 0 && (uint64_t)D * cs * esz < 0xf0000000ull
-                         : fast_common && p.vec_store && (uint64_t)chunk_len * esz * 64 * 64 < 0xf0000000ull &&
+                         : fast_common && p.vec_store && (uint64_t)chunk_len * osz * 64 * 64 < 0xf0000000ull &&
+                               // float rows: rows of whole 16-byte INPUT pieces, so that a lane's store piece holds the same columns in every block
+                               // (the 16-byte aligned output is vec_store's term; the reach above counts OUTPUT bytes)
+                               (!flt || ((uint64_t)D * esz) % 16 == 0) &&
                                // select rows: the shapes a filter takes here, with rows of whole 16-byte store pieces (a piece lies in ONE row, as
                                // for the gather) and an output -- `capacity` rows from a 16-byte aligned start -- within reach of the store
                                // descriptor's 32-bit offsets (the quotient: capacity is any 64-bit number)
@@ -272,11 +281,16 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by, nor the extrema, nor the linear filter, nor the segments: those shapes go to the generic kernel)
-    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && s.q != kQueryGroupBy && s.q != kQueryExtrema && s.q != kQueryLinear && s.q != kQuerySegment && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
+    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by, nor the extrema, nor the linear filter, nor the segments, nor float rows: those shapes go to the generic kernel)
+    if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && s.q != kQueryGroupBy && s.q != kQueryExtrema && s.q != kQueryLinear && s.q != kQuerySegment && s.q != kQueryFloat && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
     if (table_bytes) {                                         // nothing is staged: the table is the launch's LDS
         p.wg_chunks = table_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D, s.table_row_max);
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, table_bytes);
+    }
+    if (flt) {                                                 // every sample leaves converted, at a plain 64-bit address: nothing is staged
+        p.vec_store = 0;
+        p.lds_group_stride = 0;
+        shmem = 0;
     }
     return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, shmem);
 }

@@ -1,5 +1,5 @@
 // row_ops.hip -- the row operations of the C-ABI (include/sprintz_mi355x.h): queries, the zone map, filters, select, aggregate,
-// moments, extrema, segments, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
+// moments, extrema, segments, float rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
 // fills its QuerySpec and hands over to decode_batch (entry.h); what the decoders then do with a row is decode_ops.h's.
 #include "entry.h"
 
@@ -436,6 +436,34 @@ int sprintz_mi355x_segment_count(const uint8_t* d_mask, uint64_t nchunks, uint32
     if (launch_segment_count(d_mask, nchunks, chunk_len / ndims, ndims, mode, d_lens, d_counts, (hipStream_t)hip_stream) != hipSuccess)
         return fail(SPRINTZ_E_HIP, "segment_count kernel launch");
     return 0;
+}
+
+// ---------------------------------------------------------------- float rows
+int sprintz_mi355x_float_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                              uint32_t chunk_len, uint16_t ndims, int out_format, const float* d_scale, const float* d_offset,
+                              uint32_t flags, void* d_out, int64_t* d_rets, void* hip_stream)
+{
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims};
+    QuerySpec qs;
+    // (the signed bit is this operation's own flag: the shared checks see the rest)
+    int rc = masked_row_op("float_rows", kQueryFloat, b, flags & ~(uint32_t)SPRINTZ_FLOAT_SIGNED, nullptr, qs);
+    if (rc) return rc;
+    static_assert(SPRINTZ_FLOAT_F32 == (int)kFloatF32 && SPRINTZ_FLOAT_F16 == (int)kFloatF16 && SPRINTZ_FLOAT_BF16 == (int)kFloatBF16, "the format travels as it is given");
+    if (out_format != SPRINTZ_FLOAT_F32 && out_format != SPRINTZ_FLOAT_F16 && out_format != SPRINTZ_FLOAT_BF16)
+        return fail(SPRINTZ_E_INVALID, "float_rows: out_format must be SPRINTZ_FLOAT_F32, SPRINTZ_FLOAT_F16 or SPRINTZ_FLOAT_BF16");
+    if (!d_out) return fail(SPRINTZ_E_INVALID, "float_rows: null device pointer");
+    const uint32_t mode = (uint32_t)out_format | ((flags & SPRINTZ_FLOAT_SIGNED) ? kFloatSignedBit : 0u);
+    if ((uintptr_t)d_out % (uintptr_t)float_out_bytes(mode)) return fail(SPRINTZ_E_INVALID, "float_rows: d_out must be aligned to the output element size");
+    if ((uintptr_t)d_scale % 4 || (uintptr_t)d_offset % 4 || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "float_rows: d_scale and d_offset must be aligned to 4 bytes, d_rets to 8");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    // the mode shares FilterArgs, as the linear filter does (decode_ops.h, float rows): lo is the scale, hi the offset, mode the format and the signed bit
+    qs.rows = RowMaskArgs{};
+    qs.filter.lo = d_scale;
+    qs.filter.hi = d_offset;
+    qs.filter.mode = mode;
+    return decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
 }
 
 // ---------------------------------------------------------------- histogram rows

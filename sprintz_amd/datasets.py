@@ -26,6 +26,23 @@ def quantize(mat, dtype, axis=0):
     return (m * _MAX[dt]).astype(dt)
 
 
+def dequantize_params(mat, dtype, axis=0):
+    """The way back from quantize(mat, dtype, axis): -> (scale, offset), float32 per variable, with
+    q * scale + offset within one quantisation step (scale) of mat -- quantize truncates, so the value
+    lies at most one step below.  scale = max(1, max - min) / MAX, offset = min.  They are what
+    ChunkedCodec.float_rows takes to decode a quantised batch straight into floats."""
+    dt = np.dtype(dtype)
+    if dt not in _MAX:
+        raise ValueError(f"Invalid dtype '{dtype}'")
+    m = np.asarray(mat, dtype=np.float64)
+    if m.ndim == 1:
+        m = m[:, None]
+    lo = np.min(m, axis=axis)
+    span = (np.max(m, axis=axis) - lo).astype(np.float32)
+    scale = np.maximum(np.float32(1), span) / np.float32(_MAX[dt])
+    return scale.astype(np.float32).reshape(-1), lo.astype(np.float32).reshape(-1)
+
+
 def dump(mat, path, order="c"):
     """write [nsamples, nvariables] as a raw little-endian .dat: order 'c' = row-major, 'f' =
     column-major (compress_bench.py:111-115)"""

@@ -1,6 +1,6 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, extrema_rows, segment_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, the default bin shift, bounds and offsets as tensors, the
+moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, the default bin shift, bounds and offsets as tensors, the
 linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
@@ -176,6 +176,35 @@ def raise_damaged(op, rets, n, error):
     if c is not None:
         code = int(rets[c].item())
         raise error(code, f"{op}: chunk {c} is damaged (decoder returned {code})")
+
+
+def float_format(dtype):
+    """float_rows' output dtype -> SPRINTZ_FLOAT_F32 / _F16 / _BF16"""
+    fmt = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}.get(dtype)
+    if fmt is None:
+        raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.bfloat16, not {dtype}")
+    return fmt
+
+
+def float_params(v, ndims, name, device):
+    """float_rows' scale / offset: None -> None (the library's all 1 / all 0); a number, a sequence of ndims numbers or a tensor of ndims
+    elements -> a contiguous float32 tensor [ndims] on `device`.  Host values must be finite."""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        if v.numel() != ndims:
+            raise ValueError(f"{name} must have {ndims} entries, not {v.numel()}")
+        return v.reshape(-1).to(device=device, dtype=torch.float32).contiguous()
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, ndims)
+    if a.size != ndims:
+        raise ValueError(f"{name} must be a number or have {ndims} entries, not {a.size}")
+    with np.errstate(over="ignore"):
+        a32 = a.astype(np.float32)
+    if not np.all(np.isfinite(a)) or not np.all(np.isfinite(a32)):
+        raise ValueError(f"{name} must be finite in float32")
+    return torch.from_numpy(a32).to(device)
 
 
 def default_shift(W, nbins):
