@@ -1,8 +1,9 @@
-// plan_probe.cpp -- the planner (sprintz_amd/csrc/plan.h) on a host compiler, for tests/test_plan_cpu.py: that this file builds with
-// g++ is itself the check that plan.h and geom.h contain no HIP.  Reads one query per line from stdin,
+// plan_probe.cpp -- the planner (sprintz_amd/csrc/plan.h) on a host compiler, for tests/planner.py and through it every test that asks
+// the planner: that this file builds with g++ is itself the check that plan.h and geom.h contain no HIP.  Reads one query per line from stdin,
 //     decode|encode|dense|gather  key=value ...      (Shape fields and Knobs fields by name; what is not named keeps its default)
 // and prints the plan -- the family by sprintz_mi355x_dispatch_name's table and every field -- or the error.  `sweep` runs the
-// property sweep of the module's docstring inside the probe and prints one line per violation, then the number of shapes.
+// property sweep of tests/test_plan_cpu.py's docstring inside the probe and prints one line per violation, then the number of shapes;
+// `modes` prints every kQuery* constant of geom.h as name=value.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,10 +19,12 @@ static std::string show(const Plan& p)
     char b[1024];
     if (p.err) { snprintf(b, sizeof b, "error=%d what=%s", p.err, p.what); return b; }
     snprintf(b, sizeof b, "family=%s grid=%llu lds=%llu dp=%d cpl=%d exact=%d ds=%d log2DP=%d lds_group_stride=%u vec_store=%d cap=%u chunks_per_group=%u "
-             "lat_bound=%u norle=%d raw=%d quirk=%d lowdim=%d fire=%d fused=%d plain_memory=%d counters=%d row=%u/%u/%u blkd=%u/%u/%u/%u blke=%u/%u/%u/%u",
+             "lat_bound=%u norle=%d raw=%d quirk=%d lowdim=%d fire=%d fused=%d plain_memory=%d counters=%d table_off=%u wg_chunks=%u row=%u/%u/%u "
+             "blkd=%u/%u/%u/%u blke=%u/%u/%u/%u",
              kFamilyNames[p.family], (unsigned long long)p.grid, (unsigned long long)p.lds, p.dp, p.cpl, (int)p.exact, p.ds, p.log2DP, p.lds_group_stride,
              p.vec_store, p.cap, p.chunks_per_group, p.lat_bound, p.norle, p.raw, p.quirk, (int)p.lowdim, (int)p.fire, (int)p.fused, (int)p.plain_memory,
-             (int)p.counters, p.row.U, p.row.G, p.row.ok, p.blkd.T, p.blkd.CPW, p.blkd.total, p.blkd.ok, p.blke.T, p.blke.CPW, p.blke.total, p.blke.ok);
+             (int)p.counters, p.table_off, p.wg_chunks, p.row.U, p.row.G, p.row.ok, p.blkd.T, p.blkd.CPW, p.blkd.total, p.blkd.ok, p.blke.T, p.blke.CPW,
+             p.blke.total, p.blke.ok);
     return b;
 }
 
@@ -29,7 +32,7 @@ static bool set(Shape& s, Knobs& k, const std::string& key, unsigned long long v
 {
 #define F(obj, name) if (key == #name) { obj.name = (decltype(obj.name))v; return true; }
     F(s, codec) F(s, esz) F(s, D) F(s, nchunks) F(s, chunk_len) F(s, total_len) F(s, noheader) F(s, q) F(s, general) F(s, col_stride) F(s, write_size)
-    F(s, dense) F(s, host_call) F(s, src_lo) F(s, slots_lo) F(s, out_lo) F(s, comp_lo) F(s, slot_stride) F(s, nranges) F(s, rows)
+    F(s, dense) F(s, host_call) F(s, src_lo) F(s, slots_lo) F(s, out_lo) F(s, comp_lo) F(s, slot_stride) F(s, nranges) F(s, rows) F(s, capacity) F(s, table_entries) F(s, table_row_max) F(s, out_esz)
     F(k, no_fast) F(k, lat_chunks) F(k, blk_chunks) F(k, blk_kernels) F(k, enc_pair) F(k, split_lanes) F(k, chunks_per_group) F(k, dense_mode) F(k, ref_quirk)
 #undef F
     return false;
@@ -88,6 +91,16 @@ static void sweep()
     printf("sweep shapes=%llu violations=%llu\n", shapes, g_bad);
 }
 
+// every kQuery* of geom.h on one line, for tests/planner.py's QUERY
+static void modes()
+{
+#define M(name) printf(#name "=%d ", kQuery##name);
+    M(Off) M(Materialize) M(ReduceOnly) M(Window) M(Gather) M(Filter) M(Select) M(Aggregate) M(Histogram) M(Moments) M(GroupBy) M(Extrema) M(Linear)
+    M(Segment) M(Float)
+#undef M
+    printf("\n");
+}
+
 int main()
 {
     char line[4096];
@@ -96,6 +109,7 @@ int main()
         std::string op, tok;
         if (!(in >> op)) continue;
         if (op == "sweep") { sweep(); continue; }
+        if (op == "modes") { modes(); continue; }
         Shape s;
         Knobs k;
         while (in >> tok) {

@@ -1,12 +1,9 @@
 """CPU tests of aggregate rows (sprintz_mi355x_aggregate_rows): the symbol and its binding are there, every validation return comes
 before the device is touched and names the operation, the numpy model the GPU tier compares with (tests/aggregate_model.py) equals a
 one-row-at-a-time brute force, the windowed query's model under an all-ones mask and the filter model's counts, and the planner
-(sprintz_amd/csrc/plan.h, built with g++: tests/select_plan_probe.cpp, which takes any mode) sends the mode where the windowed query
+(sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp) sends the mode where the windowed query
 goes -- except that decode_uni.h never gets it."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,21 +11,14 @@ import pytest
 import aggregate_model as am
 import filter_model as fm
 import window_model as wm
+from fixtures import buf_fixture, lib, random_mask, refusals  # noqa: F401  (fixtures)
+from planner import QUERY, family, plan_fixture
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-Q_WINDOW, Q_AGGREGATE = 3, 7
+Q_WINDOW, Q_AGGREGATE = QUERY["window"], QUERY["aggregate"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 16384)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(16384)
 
 
 def test_symbol_and_binding(lib):
@@ -56,13 +46,7 @@ def test_validation_comes_before_the_device(lib, buf):
         return lib.aggregate_rows(a["codec"], a["esz"], a["comp"], a["offs"], a["n"], a["cl"], a["D"], a["mask"], a["W"], a["ops"],
                                   a["flags"], a["mn"], a["mx"], a["sm"], a["cnt"], a["rets"], None)
 
-    def invalid(**kw):
-        assert call(**kw) == E.E_INVALID, kw
-        assert "aggregate_rows" in lib.last_error(), (kw, lib.last_error())
-
-    def unsupported(**kw):
-        assert call(**kw) == E.E_UNSUPPORTED, kw
-        assert "aggregate_rows" in lib.last_error(), (kw, lib.last_error())
+    invalid, unsupported = refusals(lib, call, "aggregate_rows")
 
     invalid(cl=5121)                                                             # chunk_len % ndims != 0
     invalid(D=7)
@@ -113,10 +97,6 @@ SHAPES = [
     (2, 8, 8 * 64, 8 * 64 * 3),
     (1, 7, 7 * 5, 7 * 5 * 6 + 7),
 ]
-
-
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
 
 
 def windows_for(R):
@@ -203,19 +183,7 @@ def test_global_model_folds_the_chunk_windows():
                 assert np.all(g["min"][w] == 255) and np.all(g["max"][w] == 0) and np.all(np.isnan(g["mean"][w]))
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("aggregate_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "select_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        q = dict(codec=1, nchunks=4096, q=Q_AGGREGATE)
-        q.update(fields)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        return subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.strip()
-    return ask
+plan = plan_fixture(shape=family, codec=1, nchunks=4096, q=Q_AGGREGATE)
 
 
 def test_planner_edges(plan):

@@ -1,13 +1,10 @@
 """CPU tests of extrema rows (sprintz_mi355x_extrema_rows): the symbol and its binding are there, every validation return comes before
 the device is touched and names the operation, the numpy model the GPU tier compares with (tests/extrema_model.py) equals brute force
 and satisfies the identities that tie it to aggregate rows and to plain indexing, rowops.fold_extrema folds per-chunk windows into the
-model's windows over the batch's rows, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/extrema_plan_probe.cpp) sends the
+model's windows over the batch's rows, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp) sends the
 mode to decode_fast.h exactly where aggregate rows go, to the generic kernel otherwise -- never to decode_uni.h or the plain decode's
 kernels.  The kernels keep value and row apart, so there is no window limit to probe."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,21 +12,14 @@ import pytest
 import aggregate_model as am
 import extrema_model as em
 import filter_model as fm
+from fixtures import buf_fixture, lib, random_mask, refusals  # noqa: F401  (fixtures)
+from planner import QUERY, plan_fixture, split
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-Q_WINDOW, Q_AGGREGATE, Q_EXTREMA = 3, 7, 11
+Q_WINDOW, Q_AGGREGATE, Q_EXTREMA = QUERY["window"], QUERY["aggregate"], QUERY["extrema"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 65536)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(65536)
 
 
 def test_symbol_and_binding(lib):
@@ -66,13 +56,7 @@ def test_validation_comes_before_the_device(lib, buf):
         return lib.extrema_rows(a["codec"], a["esz"], a["comp"], a["offs"], a["n"], a["cl"], a["D"], a["mask"], a["W"], a["ops"], a["flags"],
                                 *[a[k] for k in OUTS], a["rets"], None)
 
-    def invalid(**kw):
-        assert call(**kw) == E.E_INVALID, kw
-        assert "extrema_rows" in lib.last_error(), (kw, lib.last_error())
-
-    def unsupported(**kw):
-        assert call(**kw) == E.E_UNSUPPORTED, kw
-        assert "extrema_rows" in lib.last_error(), (kw, lib.last_error())
+    invalid, unsupported = refusals(lib, call, "extrema_rows")
 
     invalid(cl=5121)                                                             # chunk_len % ndims != 0
     invalid(D=7)
@@ -132,10 +116,6 @@ SHAPES = [
     (1, 7, 7 * 5, 7 * 5 * 6 + 7),
 ]
 KEYS = ("min", "max", "argmin", "argmax", "first", "last", "rows", "count")
-
-
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
 
 
 def windows_of(R):
@@ -292,20 +272,7 @@ def test_fold_extrema_tie_across_chunks():
     assert as_numpy(got["first"], np.uint16).tolist() == [[0xFFFF]] and got["last_row"].tolist() == [23]
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("extrema_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "extrema_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        q = dict(codec=1, nchunks=4096, q=Q_EXTREMA)
-        q.update(fields)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
-        return out[0], {k: int(v) for k, v in (t.split("=") for t in out[1:])}
-    return ask
+plan = plan_fixture(shape=split, codec=1, nchunks=4096, q=Q_EXTREMA)
 
 
 PLAN_SHAPES = [(1, 16, 16 * 512), (2, 8, 5120), (2, 24, 24 * 200), (1, 8, 4096), (2, 4, 4096), (1, 24, 24 * 200), (2, 5, 5 * 1024), (2, 3, 3000),

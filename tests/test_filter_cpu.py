@@ -1,24 +1,15 @@
 """CPU tests of filter rows (sprintz_mi355x_filter_rows, sprintz_mi355x_filter_row_ids): every validation return comes before the
 device is touched, the constants and bindings are there, and the numpy model the GPU tier compares with (tests/filter_model.py)
 equals a one-element-at-a-time brute force of the definition on ragged shapes."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import filter_model as fm
+from fixtures import buf_fixture, lib  # noqa: F401  (fixtures)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 4096)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(4096)
 
 
 def test_constants_and_bindings(lib):

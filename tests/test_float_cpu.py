@@ -1,36 +1,23 @@
 """CPU tier of float rows (sprintz_mi355x_float_rows, ChunkedCodec.float_rows): the symbol and its binding are there, every validation
 return comes before the device is touched, the numpy model the GPU tier compares with (tests/float_model.py) equals torch's
 (x.to(float32) * scale + offset).to(dtype) on the CPU bit for bit and a one-element-at-a-time brute force, the planner
-(sprintz_amd/csrc/plan.h, built with g++: tests/float_plan_probe.cpp) sends the mode to decode_fast.h or to the generic kernel where the
+(sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp) sends the mode to decode_fast.h or to the generic kernel where the
 header says, and datasets.dequantize_params inverts datasets.quantize within one step."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import float_model as fm
-from test_select_cpu import SHAPES
+from fixtures import buf_fixture, lib  # noqa: F401  (fixtures)
+from planner import QUERY, plan_fixture
+from rowdata import FLOAT_FAST_SHAPES as FAST_SHAPES, GENERIC_SHAPES, RAGGED_SHAPES as SHAPES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DTYPES = {1: np.uint8, 2: np.uint16}
-# the shapes the issue names: rows of whole 16-byte pieces, and rows that are not (the low-dim layouts among them)
-FAST_SHAPES = [(2, 8), (2, 16), (2, 24), (2, 64), (2, 128), (1, 16), (1, 80), (1, 256)]
-GENERIC_SHAPES = [(2, 1), (2, 2), (2, 3), (2, 5), (2, 12), (1, 1), (1, 4), (1, 7)]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 8192)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(8192)
 
 
 def test_symbol_and_binding(lib):
@@ -160,20 +147,7 @@ def test_model_equals_brute_force(esz, D, chunk_len, n):
 
 # ------------------------------------------------------------------ the planner
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("float_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "float_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        q = dict(dict(codec=1, nchunks=4096), **fields)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
-        assert len(out) == 1
-        return out[0].split()
-    return ask
+plan = plan_fixture(codec=1, nchunks=4096, q=QUERY["float"], out_esz=4)
 
 
 def rows16(D, esz=2):
@@ -189,20 +163,20 @@ def test_planner_sends_the_mode_to_decode_fast_or_the_generic_kernel(plan):
             for nchunks in (5, 4096, 131072):                                    # (small batches too: no workgroup-per-chunk kernel takes the mode)
                 for codec in (0, 1):
                     got = plan(esz=esz, D=D, chunk_len=rows16(D, esz), out_esz=out_esz, nchunks=nchunks, codec=codec)
-                    assert got[0] == "dec_fast", (esz, D, out_esz, nchunks, got)
-                    families.add(got[0])
+                    assert got["family"] == "dec_fast", (esz, D, out_esz, nchunks, got)
+                    families.add(got["family"])
             # the output off by one element, OPT_NO_FAST: the generic kernel, which stages nothing
             for kw in (dict(out_lo=out_esz), dict(no_fast=1)):
                 got = plan(esz=esz, D=D, chunk_len=rows16(D, esz), out_esz=out_esz, **kw)
-                assert got[0] == "dec_generic" and "lds=0" in got and "vec=0" in got, (esz, D, out_esz, kw, got)
+                assert got["family"] == "dec_generic" and got["lds"] == 0 and got["vec_store"] == 0, (esz, D, out_esz, kw, got)
     head = plan(esz=2, D=8, chunk_len=5120, out_esz=2, nchunks=131072)
-    assert head[0] == "dec_fast" and "dp=8" in head and "cpl=1" in head and "exact=1" in head
+    assert head["family"] == "dec_fast" and head["dp"] == 8 and head["cpl"] == 1 and head["exact"] == 1
     for esz, D in GENERIC_SHAPES:
         for general in (0, 1):
             for out_esz in (4, 2):
                 got = plan(esz=esz, D=D, chunk_len=rows16(D, esz), out_esz=out_esz, general=general)
-                assert got[0] == "dec_generic" and "lds=0" in got, (esz, D, general, got)   # decode_uni.h is not taught the mode
-                families.add(got[0])
+                assert got["family"] == "dec_generic" and got["lds"] == 0, (esz, D, general, got)   # decode_uni.h is not taught the mode
+                families.add(got["family"])
     assert families == {"dec_fast", "dec_generic"}
 
 
@@ -212,14 +186,14 @@ def test_planner_counts_the_reach_in_output_bytes(plan):
     for esz, D, out_esz in ((1, 16, 4), (1, 16, 2), (2, 8, 4)):
         cl = ((limit - 1) // (out_esz * 4096)) // (16 * D) * (16 * D)                 # the largest whole-group chunk that still fits
         assert cl * out_esz * 4096 < limit
-        assert plan(esz=esz, D=D, chunk_len=cl, out_esz=out_esz, nchunks=64)[0] == "dec_fast"
+        assert plan(esz=esz, D=D, chunk_len=cl, out_esz=out_esz, nchunks=64)["family"] == "dec_fast"
         cl += 16 * D
         assert cl * out_esz * 4096 >= limit and cl * esz * 4096 < limit
-        assert plan(esz=esz, D=D, chunk_len=cl, out_esz=out_esz, nchunks=64)[0] == "dec_generic"
+        assert plan(esz=esz, D=D, chunk_len=cl, out_esz=out_esz, nchunks=64)["family"] == "dec_generic"
     # uint16 -> 16-bit floats: the output's bytes are the input's, and the plain decode's bound holds
     cl = ((limit - 1) // (2 * 4096)) // 128 * 128
-    assert plan(esz=2, D=8, chunk_len=cl, out_esz=2, nchunks=64)[0] == "dec_fast"
-    assert plan(esz=2, D=8, chunk_len=cl + 128, out_esz=2, nchunks=64)[0] == "dec_generic"
+    assert plan(esz=2, D=8, chunk_len=cl, out_esz=2, nchunks=64)["family"] == "dec_fast"
+    assert plan(esz=2, D=8, chunk_len=cl + 128, out_esz=2, nchunks=64)["family"] == "dec_generic"
 
 
 # ------------------------------------------------------------------ dequantize_params

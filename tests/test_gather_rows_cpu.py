@@ -7,18 +7,9 @@ import numpy as np
 import pytest
 
 import gather_model as gm
+from fixtures import lib  # noqa: F401  (fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    p = os.path.join(ROOT, "sprintz_amd", "libsprintz_mi355x.so")
-    if not os.path.exists(p):
-        import __graft_entry__
-        __graft_entry__.build()
-    from sprintz_amd import _lib
-    return _lib
 
 
 def test_gather_rows_validation(lib):

@@ -3,8 +3,6 @@ min / max / sum / count of the rows a mask names, fused into the decode, in deco
 always tests/aggregate_model.py applied to the ORIGINAL input -- decode is lossless and pinned elsewhere.  Every launch's kernel family
 is asserted, every output lies in a sentinel-filled buffer whose padding must keep the sentinel, and rets[nchunks] must stay untouched.
 Every batch ends in a short last chunk of whole rows."""
-import ctypes as C
-import os
 import zlib
 
 import numpy as np
@@ -14,118 +12,12 @@ import aggregate_model as am
 import filter_model as fm
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_filter import bound_sets
-from test_gpu_query_windows import gen_data, lowdim, make_batch
-from test_gpu_select import parity_masks, short_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import (FAST_SHAPES, PARITY_FAST, bound_sets, gen_data, lowdim, make_batch, masked_parity_cases as parity_cases, parity_masks, rows_for,
+                     short_batch, windows_for)
+from rowop_runners import check_agg
 
 pytestmark = pytest.mark.gpu
-
-PAD = 1024                      # entries behind every output that must keep the sentinel
-NDIMS = [1, 2, 3, 4, 5, 8, 16, 33, 80, 128, 256, 300, 512]
-SHAPES = ["r16", "tail", "nogroups"]
-DATA = ["walk", "uniform", "constant", "sparse"]
-OPS = {"min": 1, "max": 2, "sum": 4, "count": 8}
-# the parity shapes decode_fast.h takes, as (esz, D, general layout asked for); the planner's edges are pinned in test_aggregate_cpu.py
-PARITY_FAST = {(1, 4, True), (1, 16, False), (2, 4, False), (2, 16, False)}
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def rows_for(shape, D):
-    r16 = 16 * max(2, 2048 // (16 * D))
-    return {"r16": r16, "tail": r16 + 1 + D % 15, "nogroups": 13}[shape]     # whole groups; a verbatim tail of 1 .. 15 rows; no groups
-
-
-def windows_for(R):
-    r8 = -(-R // 8) * 8
-    return sorted({8, 24, 64, r8, r8 + 8})
-
-
-def sentinel(esz, byte):
-    return int.from_bytes(bytes([byte]) * esz, "little")
-
-
-def run_agg(batch, codec, esz, D, chunk_len, mask, W, ops=15, byte=0x5A, general=False, mask_shift=0, null_unselected=False):
-    """the C entry point on sentinel-filled outputs of nchunks * nwin (* D) entries + PAD -> ({op: numpy incl. padding}, rets [nchunks])"""
-    import torch
-    from sprintz_amd import _lib
-    n = batch.nchunks
-    R = chunk_len // D
-    nwin = -(-R // W)
-    m = n * nwin
-    elem = sentinel(esz, byte)
-    bufs = {
-        "min": torch.from_numpy(np.full(m * D + PAD, elem, DTYPES[esz]).view(np.int8 if esz == 1 else np.int16)).cuda(),
-        "max": torch.from_numpy(np.full(m * D + PAD, elem, DTYPES[esz]).view(np.int8 if esz == 1 else np.int16)).cuda(),
-        "sum": torch.from_numpy(np.full(m * D + PAD, sentinel(8, byte), np.uint64).view(np.int64)).cuda(),
-        "count": torch.from_numpy(np.full(m + PAD, sentinel(4, byte), np.uint32).view(np.int32)).cuda(),
-    }
-    rets_t = torch.full((n + 1,), -77, dtype=torch.int64, device="cuda")
-    flat = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-    mask_t = torch.from_numpy(np.concatenate([np.full(mask_shift, 0xFF, np.uint8), flat, np.full(16, 0xFF, np.uint8)])).cuda()
-
-    def ptr(k):
-        return None if null_unselected and not ops & OPS[k] else bufs[k].data_ptr()
-    _lib.check(_lib.aggregate_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                   n, chunk_len, D, mask_t.data_ptr() + mask_shift, W, ops, _lib.QUERY_GENERAL_LAYOUT if general else 0,
-                                   ptr("min"), ptr("max"), ptr("sum"), ptr("count"), rets_t.data_ptr(),
-                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    r = rets_t.cpu().numpy()
-    assert r[n] == -77, "rets written past nchunks"
-    got = {"min": bufs["min"].cpu().numpy().view(DTYPES[esz]), "max": bufs["max"].cpu().numpy().view(DTYPES[esz]),
-           "sum": bufs["sum"].cpu().numpy().view(np.uint64), "count": bufs["count"].cpu().numpy().view(np.uint32)}
-    return got, r[:n]
-
-
-def check_agg(x, batch, codec, esz, D, chunk_len, mask, W, msg, want=None, ops=15, byte=0x5A, skip_chunk=None, **kw):
-    """every selected output, the unselected ones, the padding and rets against the model; skip_chunk: a damaged chunk, whose own entries
-    are unspecified"""
-    want = am.aggregate_rows(x, chunk_len, D, mask, W) if want is None else want
-    got, rets = run_agg(batch, codec, esz, D, chunk_len, mask, W, ops, byte, **kw)
-    lens = np.array(fm.chunk_counts(x.size, chunk_len))
-    keep = np.arange(batch.nchunks) != (-1 if skip_chunk is None else skip_chunk)
-    assert np.array_equal(rets[keep], lens[keep]), ("rets",) + msg
-    if skip_chunk is not None:
-        assert rets[skip_chunk] < 0, ("rets of the damaged chunk",) + msg
-    for k in ("min", "max", "sum", "count"):
-        w = want[k]
-        sent = sentinel({"sum": 8, "count": 4}.get(k, esz), byte)
-        g = got[k]
-        assert np.all(g[w.size:] == sent), (k, "padding") + msg
-        g = g[:w.size].reshape(w.shape)
-        if ops & OPS[k]:
-            assert np.array_equal(g[keep], w[keep]), (k,) + msg
-        else:
-            assert np.all(g == sent), (k, "an unselected output was written") + msg
-    return want
-
-
-def parity_cases():
-    """codec x esz x ndims in full; per (codec, esz) the ndims walk the three chunk shapes and the four kinds of data"""
-    cases = []
-    for codec in ("delta", "xff"):
-        for esz in (1, 2):
-            for j, D in enumerate(NDIMS):
-                cases.append((codec, esz, D, SHAPES[j % 3], DATA[(j + (1 if codec == "xff" else 0) + 2 * (esz - 1)) % 4]))
-    return cases
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data", parity_cases())
@@ -151,14 +43,6 @@ def test_aggregate_rows_parity(sz, oracle, no_fast, codec, esz, D, shape, data):
                                   want[(name, W)], general=general)
     assert int(want[("no row", 8)]["count"].sum()) == 0
     assert int(want[("every bit", 8)]["count"].sum()) == x.size // D and int(want[("row 0", 8)]["count"].sum()) == 5
-
-
-FAST_SHAPES = [
-    # (codec, esz, D, chunk_len): decode_fast.h's lane mappings -- 4 .. 64 lanes a chunk, 1 / 2 / 4 columns a lane, full and partly filled groups
-    ("xff", 2, 8, 5120), ("delta", 2, 8, 8 * 648), ("delta", 2, 5, 5 * 1000), ("xff", 1, 8, 8 * 1024), ("delta", 1, 24, 24 * 200),
-    ("xff", 2, 24, 24 * 200), ("xff", 1, 64, 64 * 160), ("delta", 1, 80, 10240), ("xff", 2, 80, 80 * 128), ("delta", 2, 128, 128 * 80),
-    ("xff", 1, 200, 200 * 104), ("delta", 1, 256, 256 * 80),
-]
 
 
 @pytest.mark.parametrize("codec,esz,D,chunk_len", FAST_SHAPES)

@@ -11,39 +11,14 @@ import sys
 
 import numpy as np
 import pytest
+from fixtures import sz  # noqa: F401  (fixtures)
+from rowdata import bench_input
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-def bench_input(name, device):
-    """exactly what bench.py's run_config(name) / headline generates on rank 0 of 1"""
-    import torch
-    from synth import synth_torch
-    if name == "cfg2":
-        return ("xff", 2, 8, 5120, 131072), synth_torch("walk", 2, 131072, 640, 8, device, seed=123, step=8, chunk0=0)
-    if name.startswith("cfg2_"):               # bench.py's data_sweep: the headline shape on SURVEY 8d's other generators
-        kind, step = {"cfg2_uniform": ("uniform", 0), "cfg2_walk300": ("walk", 300), "cfg2_walkflat": ("walkflat", 8)}[name]
-        return ("xff", 2, 8, 5120, 131072), synth_torch(kind, 2, 131072, 640, 8, device, seed=123, step=step, chunk0=0)
-    if name == "cfg1":
-        return ("delta", 1, 1, 1024, 524288), synth_torch("walk", 1, 524288, 1024, 1, device, seed=123, step=2, chunk0=0)
-    if name == "cfg3_10k":
-        return ("delta", 1, 80, 10240, 52429), synth_torch("walk", 1, 52429, 128, 80, device, seed=123, step=2, chunk0=0)
-    if name == "cfg3_1k":                      # 1024 elements do not hold whole rows of 80: 64-row series, cut every 1024
-        from synth import synth_cut_rows
-        return ("delta", 1, 80, 1024, 524288), synth_cut_rows("walk", 1, 524288, 1024, 80, device, seed=123, step=2)
-    raise ValueError(name)
 
 
 @pytest.mark.parametrize("name", ["cfg2", "cfg2_uniform", "cfg2_walk300", "cfg2_walkflat", "cfg1", "cfg3_1k", "cfg3_10k"])

@@ -12,16 +12,9 @@ import pytest
 
 from dispatch import OLD_DECODERS, OLD_ENCODERS, ROUND6, ran
 from harness import DTYPES, gen_walk
+from fixtures import sz  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 @pytest.fixture(params=["blk", "row", "old"])

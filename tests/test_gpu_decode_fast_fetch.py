@@ -21,6 +21,7 @@ import pytest
 
 from dispatch import ran
 from harness import DTYPES
+from fixtures import sz  # noqa: F401  (fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -30,14 +31,6 @@ pytestmark = pytest.mark.gpu
 NCHUNKS = 67
 FAST_LENS = [1280, 384, 304]          # decode_fast.h: 10 steps / 3 steps / 2 steps + a tail
 SHORT_LENS = [128, 256]               # 1 / 2 steps: below the planner's bound for decode_fast.h (module docstring)
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 @pytest.fixture(autouse=True)
@@ -52,7 +45,7 @@ def lane_per_column_kernels(sz, request):
     request.addfinalizer(restore)
 
 
-def chunks_per_group(k):
+def set_chunks_per_group(k):
     from sprintz_amd import _lib
     _lib.check(_lib.set_option(_lib.OPT_CHUNKS_PER_GROUP, k))
 
@@ -173,7 +166,7 @@ def test_bytes_outside_a_stream_do_not_matter(sz, oracle, chunk_len, cpg):
     family = "dec_fast" if chunk_len in FAST_LENS else "dec_generic"
     streams, want, want_rets = prepared(oracle, "xff", "walk8", 2, 8, chunk_len, NCHUNKS)
     gaps = [GAPS[c % len(GAPS)] for c in range(NCHUNKS)]
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     got = []
     for fill in (0, 0xA5):
         comp, offs = lay_out(streams, gaps=gaps, fill=fill)
@@ -199,7 +192,7 @@ def test_every_phase_of_the_container_against_the_cache_lines(sz, oracle, delta,
     comp, offs = lay_out(streams, align=align, fill=0xA5)
     total = int(offs[-1])
     assert comp.size == total + _lib.READ_SLACK
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     for k in range(8):
         start = 16 * k + delta
         buf = torch.full((start + comp.size,), 0xA5, dtype=torch.uint8, device="cuda:0")     # ends READ_SLACK behind the last stream
@@ -223,7 +216,7 @@ def test_steps_that_take_more_than_one_unit(sz, oracle, kind, chunk_len, cpg):
     if kind == "runend":
         assert all(s.size < 600 for s in streams)                       # 16 rows of payload and the run, not 1 072 rows of payload
     comp, offs = lay_out(streams, align=16, fill=0xA5)
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     out, rets = decode(sz, "xff", 2, 8, chunk_len, on_device(comp), offs, NCHUNKS)
     check(out, rets, want, want_rets, chunk_len, kind)
 
@@ -238,7 +231,7 @@ def test_a_verbatim_tail_then_the_next_chunk(sz, oracle, align, cpg):
     chunk_len = 1320
     streams, want, want_rets = prepared(oracle, "xff", "walk8", 2, 8, chunk_len, NCHUNKS)
     comp, offs = lay_out(streams, align=align, fill=0xA5)
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     out, rets = decode(sz, "xff", 2, 8, chunk_len, on_device(comp), offs, NCHUNKS)
     check(out, rets, want, want_rets, chunk_len)
 
@@ -254,7 +247,7 @@ def test_a_short_last_chunk(sz, oracle, last, cpg):
         assert streams[-1].size == 8 + 2 * 24
     assert want_rets[-1] == last
     comp, offs = lay_out(streams, align=1, fill=0xA5)
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     out, rets = decode(sz, "xff", 2, 8, chunk_len, on_device(comp), offs, NCHUNKS)
     check(out, rets, want, want_rets, chunk_len)
 
@@ -281,7 +274,7 @@ def test_streams_that_end_at_every_distance_from_a_line_boundary(sz, oracle, cpg
         assert (128 - (offs[c] + s.size) % 128) % 128 == LINE_ENDS[c % len(LINE_ENDS)]
     t = on_device(comp)
     assert t.data_ptr() % 128 == 0
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     out, rets = decode(sz, "xff", 2, 8, chunk_len, t, offs, NCHUNKS)
     check(out, rets, want, want_rets, chunk_len)
 
@@ -297,7 +290,7 @@ def test_streams_that_end_at_every_distance_from_a_line_boundary(sz, oracle, cpg
 ], ids=["u8x80_delta_split", "u8x16_fire", "u16x3", "u16x8_uniform_19"])
 def test_other_instantiations(sz, oracle, codec, esz, D, chunk_len, nchunks, kind, cpg):
     streams, want, want_rets = prepared(oracle, codec, kind, esz, D, chunk_len, nchunks)
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     for align, lead in ((16, 0), (1, 0), (1, 37)):
         comp, offs = lay_out(streams, align=align, fill=0xA5, lead=lead)
         out, rets = decode(sz, codec, esz, D, chunk_len, on_device(comp), offs, nchunks)
@@ -373,7 +366,7 @@ def test_damaged_streams_are_reported_and_their_neighbours_decode(sz, oracle, da
         else:
             streams[c][:4] = np.frombuffer(np.uint32(streams[c].size).tobytes(), np.uint8)       # ngroups: 10 bytes a group would not fit
     comp, offs = lay_out(streams, align=1, fill=0xA5)
-    chunks_per_group(cpg)
+    set_chunks_per_group(cpg)
     out, rets = decode(sz, "xff", 2, 8, chunk_len, on_device(comp), offs, NCHUNKS)
     good = np.setdiff1d(np.arange(NCHUNKS), bad)
     assert (rets[bad] == _lib.E_CORRUPT).all(), rets[bad]

@@ -17,16 +17,10 @@ import pytest
 from dispatch import ran
 from dispatch_cases import CASES, ENC, GATHER_EDGES
 from harness import DTYPES, gen_walk
+from fixtures import sz  # noqa: F401  (fixtures)
+from streams import check_streams
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 @contextmanager
@@ -51,14 +45,6 @@ def make_batch(sz, codec, esz, D, chunk_len, nchunks, align=16, seed=0):
     cd = sz.ChunkedCodec(codec, esz, D, chunk_len, device="cuda:0", align=align)
     t = torch.from_numpy(data.view(np.int8 if esz == 1 else np.int16)).cuda().view(cd.dtype)
     return data, cd, t
-
-
-def check_streams(oracle, codec, data, chunk_len, D, comp, offs, sizes, tag):
-    want = oracle.compress_chunks(codec, data, chunk_len, D)
-    assert len(want) == sizes.size
-    for c, w in enumerate(want):
-        assert sizes[c] == w.size, (tag, c, int(sizes[c]), w.size)
-        assert np.array_equal(comp[offs[c]:offs[c] + sizes[c]], w), (tag, "chunk", c, "differs from the oracle's stream")
 
 
 def roundtrip(sz, oracle, codec, esz, D, chunk_len, nchunks, enc=None, dec=None, align=16, src_shift=0, out_shift=0, comp_shift=0, tag=""):

@@ -224,7 +224,7 @@ def test_layer_below_sprintz_h(caller, oracle):
             assert cret == wret and np.array_equal(stream, trimmed(want))
             continue
         if kind in (8, 9):
-            from test_online_cpu import oracle_pack
+            from codec_helpers import oracle_pack
             import ctypes as C
             from harness import ORACLE_SO
             lib = C.CDLL(ORACLE_SO)

@@ -4,8 +4,6 @@ decode_fast.h and decode_kernel.h.  The expected value is always tests/extrema_m
 lossless and pinned elsewhere.  Every launch's kernel family is asserted, every output lies in a sentinel-filled buffer whose padding
 must keep the sentinel, and rets[nchunks] must stay untouched.  Every batch ends in a short last chunk of whole rows.  The kernels keep
 value and row apart: there is no window limit, so no position edge to drive."""
-import ctypes as C
-import os
 import zlib
 
 import numpy as np
@@ -15,98 +13,12 @@ import extrema_model as em
 import filter_model as fm
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_aggregate import FAST_SHAPES, PARITY_FAST, parity_cases, rows_for, sentinel, windows_for
-from test_gpu_filter import bound_sets
-from test_gpu_query_windows import gen_data, lowdim, make_batch
-from test_gpu_select import parity_masks, short_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import (FAST_SHAPES, PARITY_FAST, bound_sets, gen_data, lowdim, make_batch, masked_parity_cases as parity_cases, parity_masks, rows_for,
+                     short_batch, windows_for)
+from rowop_runners import OUTS, check_ext
 
 pytestmark = pytest.mark.gpu
-
-PAD = 1024                      # entries behind every output that must keep the sentinel
-OUTS = ("min", "max", "argmin", "argmax", "first", "last", "rows", "count")       # in the order of their op bits
-OPS = {k: 1 << i for i, k in enumerate(OUTS)}
-ELEM = ("min", "max", "first", "last")
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def run_ext(batch, codec, esz, D, chunk_len, mask, W, ops=255, byte=0x5A, general=False, mask_shift=0, null_unselected=False, stream=None):
-    """the C entry point on sentinel-filled outputs of nchunks * nwin (* D, * 2) entries + PAD -> ({op: numpy incl. padding}, rets [nchunks])"""
-    import torch
-    from sprintz_amd import _lib
-    n = batch.nchunks
-    R = chunk_len // D
-    nwin = -(-R // W)
-    m = n * nwin
-    size = {k: m * D for k in OUTS}
-    size.update(rows=2 * m, count=m)
-    bufs = {}
-    for k in OUTS:
-        if k in ELEM:
-            bufs[k] = torch.from_numpy(np.full(size[k] + PAD, sentinel(esz, byte), DTYPES[esz]).view(np.int8 if esz == 1 else np.int16)).cuda()
-        else:
-            bufs[k] = torch.from_numpy(np.full(size[k] + PAD, sentinel(4, byte), np.uint32).view(np.int32)).cuda()
-    rets_t = torch.full((n + 1,), -77, dtype=torch.int64, device="cuda")
-    mask_t = None
-    if mask is not None:
-        flat = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        mask_t = torch.from_numpy(np.concatenate([np.full(mask_shift, 0xFF, np.uint8), flat, np.full(16, 0xFF, np.uint8)])).cuda()
-
-    def ptr(k):
-        return None if null_unselected and not ops & OPS[k] else bufs[k].data_ptr()
-    st = torch.cuda.current_stream() if stream is None else stream
-    with torch.cuda.stream(st):
-        _lib.check(_lib.extrema_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                     n, chunk_len, D, mask_t.data_ptr() + mask_shift if mask_t is not None else None, W, ops,
-                                     _lib.QUERY_GENERAL_LAYOUT if general else 0, *[ptr(k) for k in OUTS], rets_t.data_ptr(),
-                                     C.c_void_p(st.cuda_stream)))
-    torch.cuda.synchronize()
-    r = rets_t.cpu().numpy()
-    assert r[n] == -77, "rets written past nchunks"
-    got = {k: bufs[k].cpu().numpy().view(DTYPES[esz] if k in ELEM else np.uint32) for k in OUTS}
-    return got, r[:n]
-
-
-def check_ext(x, batch, codec, esz, D, chunk_len, mask, W, msg, want=None, ops=255, byte=0x5A, skip_chunk=None, **kw):
-    """every selected output, the unselected ones, the padding and rets against the model; skip_chunk: a damaged chunk, whose own entries
-    are unspecified"""
-    want = em.extrema_rows(x, chunk_len, D, mask, W) if want is None else want
-    got, rets = run_ext(batch, codec, esz, D, chunk_len, mask, W, ops, byte, **kw)
-    lens = np.array(fm.chunk_counts(x.size, chunk_len))
-    keep = np.arange(batch.nchunks) != (-1 if skip_chunk is None else skip_chunk)
-    assert np.array_equal(rets[keep], lens[keep]), ("rets",) + msg
-    if skip_chunk is not None:
-        assert rets[skip_chunk] < 0, ("rets of the damaged chunk",) + msg
-    for k in OUTS:
-        w = want[k]
-        sent = sentinel(esz if k in ELEM else 4, byte)
-        g = got[k]
-        assert np.all(g[w.size:] == sent), (k, "padding") + msg
-        g = g[:w.size].reshape(w.shape)
-        if ops & OPS[k]:
-            if not np.array_equal(g[keep], w[keep]):
-                bad = np.argwhere(g[keep] != w[keep])[0]
-                raise AssertionError((k,) + msg + ("first difference at", tuple(bad), "got", g[keep][tuple(bad)], "want", w[keep][tuple(bad)]))
-        else:
-            assert np.all(g == sent), (k, "an unselected output was written") + msg
-    return want
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data", parity_cases())

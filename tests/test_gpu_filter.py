@@ -10,64 +10,11 @@ import pytest
 import filter_model as fm
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_query_windows import chunk_len_for, gen_data, make_batch, parity_cases
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import bound_sets, chunk_len_for, gen_data, make_batch, parity_cases
+from rowop_runners import run_filter
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    import os
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def existing_rows(x, chunk_len, D):
-    """[rows, D]: the rows that exist, chunk by chunk (columns are relative to the chunk: element e of a chunk is column e % D)"""
-    parts = []
-    for c, ne in enumerate(fm.chunk_counts(x.size, chunk_len)):
-        parts.append(x[c * chunk_len:c * chunk_len + ne // D * D].reshape(-1, D))
-    return np.concatenate(parts)
-
-
-def bound_sets(x, chunk_len, esz, D):
-    """-> [(name, mode, lo, hi, expectation)]; expectation: "some" (strictly between no row and every row), "all", "none" or None"""
-    top = (1 << (8 * esz)) - 1
-    rows = existing_rows(x, chunk_len, D).astype(np.int64)
-    sets = []
-    lo, hi = np.zeros(D, np.int64), np.full(D, top, np.int64)              # band: columns 0 and D - 1 inside their own quartiles
-    for d in (0, D - 1):
-        lo[d], hi[d] = np.quantile(rows[:, d], 0.25, method="lower"), np.quantile(rows[:, d], 0.75, method="lower")
-    sets.append(("band", fm.ALL, lo, hi, "some"))
-    t = int(np.quantile(x.astype(np.int64), 1.0 - 1.0 / (4 * D), method="higher"))   # alarm: some channel in the top 1 / (4 D) of the input
-    sets.append(("alarm", fm.ANY, np.full(D, t, np.int64), np.full(D, top, np.int64), "some"))
-    sets.append(("all rows", fm.ALL, np.zeros(D, np.int64), np.full(D, top, np.int64), "all"))
-    sets.append(("no row", fm.ANY, np.full(D, top, np.int64), np.zeros(D, np.int64), "none"))
-    lo, hi = np.zeros(D, np.int64), np.full(D, top, np.int64)              # one column never, under ALL: no row
-    lo[D // 2], hi[D // 2] = 1, 0
-    sets.append(("one never", fm.ALL, lo, hi, "none"))
-    lo, hi = np.full(D, top, np.int64), np.zeros(D, np.int64)              # one column always, under ANY: every existing row
-    lo[D // 2], hi[D // 2] = 0, top
-    sets.append(("one always", fm.ANY, lo, hi, "all"))
-    return sets, rows.shape[0]
-
-
-def run_filter(cd, batch, lo, hi, mode, general=False):
-    got = cd.filter_rows(batch, [int(v) for v in lo], [int(v) for v in hi], mode="all" if mode == fm.ALL else "any", general_layout=general)
-    return got["mask"].cpu().numpy(), got["counts"].cpu().numpy().astype(np.int64)
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data,general", parity_cases())
@@ -360,7 +307,7 @@ def test_filter_rows_python_bounds(sz, oracle):
 def test_filter_rows_bench_size(sz):
     """the bench's headline input at full size, once: the band set against torch's comparison of the device-decoded batch"""
     import torch
-    from test_gpu_bench_data import bench_input
+    from rowdata import bench_input
     (codec, esz, D, chunk_len, nchunks), x = bench_input("cfg2", "cuda:0")
     cd = sz.ChunkedCodec(codec, esz, D, chunk_len, device="cuda:0")
     batch = cd.compress(x)

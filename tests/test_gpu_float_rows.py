@@ -3,24 +3,22 @@ float32 / float16 / bfloat16.
 
 The expected value is always the numpy model (tests/float_model.py) on the ORIGINAL input, compared as bits; column d takes parameter
 pair d % 8 of the model's list, so a value converted with another column's parameters shows.  Every launch asserts its kernel family
-(tests/dispatch.py), as the planner probe (tests/float_plan_probe.cpp) gives it for the shape."""
+(tests/dispatch.py), as the planner probe (tests/plan_probe.cpp) gives it for the shape."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
 import float_model as fm
-import test_gpu_fire_extremes as fx
+import planner
+from drive_tables import ROWOP_CASES, ROWOP_IDS, rowop_batch
+from fixtures import chunks_per_group, no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import FLOAT_FAST_SHAPES as FAST_SHAPES, GENERIC_SHAPES, chunk_len_for, gen_data, make_batch, parity_cases
+from streams import GENERIC, OLD, fire_batch_of as batch_of, fire_oracle_batch as oracle_batch, options
 from dispatch import ran
 from harness import DTYPES
-from test_float_cpu import FAST_SHAPES, GENERIC_SHAPES
-from test_gpu_fire_extremes import GENERIC, OLD, options
-from test_gpu_query_windows import chunk_len_for, gen_data, make_batch, no_fast, parity_cases, sz  # noqa: F401  (fixtures)
-from test_gpu_rle_drive import ROWOP_CASES, ROWOP_IDS, chunks_per_group, rowop_batch  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,17 +29,14 @@ CODEC_ID = {"delta": 0, "xff": 1}
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
+def plan():
     """the planner on a host compiler: -> f(**fields) -> the family's name"""
-    assert shutil.which("g++"), "the planner probe needs g++"
-    exe = tmp_path_factory.mktemp("float_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "float_plan_probe.cpp"), "-o", str(exe)])
+    planner.available(required=True)
 
     def ask(**fields):
-        text = " ".join(f"{k}={int(v)}" for k, v in fields.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
-        assert out[0] in ("dec_fast", "dec_generic"), out
-        return out[0]
+        got = planner.ask("decode", q=planner.QUERY["float"], **fields)
+        assert got.get("family") in ("dec_fast", "dec_generic"), got
+        return got["family"]
     return ask
 
 
@@ -230,8 +225,8 @@ FIRE_SHAPES = {(8, 8): 7, (16, 1): 5, (8, 16): 4}        # (w, D): chunks -- the
 def test_float_rows_on_the_fire_drive(sz, oracle, chunks_per_group, w, D):
     """tests/fire_drive.py's batches: FIRE counters through their int16 wrap, runs replayed at frozen extreme coefficients"""
     nchunks = FIRE_SHAPES[(w, D)]
-    data, chunk_len = fx.batch_of(w, D, nchunks)
-    batch = fx.oracle_batch(sz, oracle, D, data, chunk_len)
+    data, chunk_len = batch_of(w, D, nchunks)
+    batch = oracle_batch(sz, oracle, D, data, chunk_len)
     drive(batch, data, "xff", w, D, chunk_len, nchunks, chunks_per_group, f"fire{w}{D}")
 
 

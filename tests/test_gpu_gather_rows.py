@@ -13,6 +13,7 @@ import pytest
 import gather_model as gm
 from dispatch import ran
 from harness import DTYPES, gen_sparse
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
@@ -23,25 +24,6 @@ NDIMS = [1, 2, 3, 4, 5, 8, 16, 33, 80, 128, 200, 256, 300, 512]
 SHAPES = ["r16", "tail", "nogroups"]
 DATA = ["walk", "uniform", "constant", "sparse"]
 ROWS = ["1", "7", "8", "R-1", "R", "R+1", "3R+5"]
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
 
 
 def gathers_on(fam, fast_shape=None):
@@ -406,7 +388,7 @@ def test_read_rows_over_3000_chunks(sz, no_fast, fam):
 def test_gather_rows_bench_sizes(sz, name, nranges, rows):
     """the bench's own inputs at full size, random starts, every range compared with the input's rows"""
     import torch
-    from test_gpu_bench_data import bench_input
+    from rowdata import bench_input
     (codec, esz, D, chunk_len, nchunks), x = bench_input(name, "cuda:0")
     cd = sz.ChunkedCodec(codec, esz, D, chunk_len, device="cuda:0")
     batch = cd.compress(x)

@@ -3,8 +3,6 @@ column's value, the count and the per-column sums of the rows a mask names, fuse
 The expected value is always tests/groupby_model.py applied to the ORIGINAL input -- decode is lossless and pinned elsewhere.  Every
 launch's kernel family is asserted, d_count and d_sum lie in sentinel-filled buffers whose padding must keep the sentinel, and
 rets[nchunks] must stay untouched.  Every batch ends in a short last chunk of whole rows."""
-import ctypes as C
-import os
 import zlib
 
 import numpy as np
@@ -14,35 +12,14 @@ import filter_model as fm
 import groupby_model as gm
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_filter import bound_sets
-from test_gpu_histogram import HS, PARITY_FAST, parity_cases, rows_for
-from test_gpu_query_windows import gen_data, lowdim, make_batch
-from test_gpu_select import parity_masks, short_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import (HS, PARITY_FAST, bound_sets, gen_data, lowdim, make_batch, masked_parity_cases as parity_cases, parity_masks, rows_for,
+                     short_batch)
+from rowop_runners import check_gby
 
 pytestmark = pytest.mark.gpu
 
-PAD = 1024                      # entries behind d_count and behind d_sum that must keep the sentinel
-SENT = 0x5A5A5A5A5A5A5A5A
 CAP = 16384
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
 
 
 def bins_for(D):
@@ -71,51 +48,6 @@ def binnings(rng, x, esz, D, key):
     med = int(np.median(x[:x.size // D * D].reshape(-1, D)[:, key].astype(np.int64)))
     return [("cover", cover, nb, 0), ("no power of two", cover, nb * 3 // 4 + 1, 0), ("random key_lo", cover, nb // 2 + 3, int(rng.integers(1, top))),
             ("around the median", 0, nb, (med - nb // 3) % top), ("one bin", W - 1, 1, int(rng.integers(1, top)))]
-
-
-def run_gby(batch, codec, esz, D, chunk_len, key, mask, key_lo, shift, nbins, H, ops=3, general=False, mask_shift=0, pass_unselected=False):
-    """the C entry point on sentinel-filled d_count of ntables * nbins entries + PAD and d_sum of ntables * nbins * D + PAD; an output that
-    ops does not select is NULL, or (pass_unselected) a sentinel-filled buffer that must come back untouched
-    -> (count incl. padding or None, sum incl. padding or None, rets [nchunks])"""
-    import torch
-    from sprintz_amd import _lib
-    n = batch.nchunks
-    nt = -(-n // H) if H else 1
-    cnt_t = torch.from_numpy(np.full(nt * nbins + PAD, SENT, np.uint64).view(np.int64)).cuda() if (ops & 1) or pass_unselected else None
-    sum_t = torch.from_numpy(np.full(nt * nbins * D + PAD, SENT, np.uint64).view(np.int64)).cuda() if (ops & 2) or pass_unselected else None
-    rets_t = torch.full((n + 1,), -77, dtype=torch.int64, device="cuda")
-    mask_ptr = None
-    if mask is not None:
-        flat = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        mask_t = torch.from_numpy(np.concatenate([np.full(mask_shift, 0xFF, np.uint8), flat, np.full(16, 0xFF, np.uint8)])).cuda()
-        mask_ptr = mask_t.data_ptr() + mask_shift
-    _lib.check(_lib.groupby_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                 n, chunk_len, D, mask_ptr, key, key_lo, shift, nbins, H, ops, _lib.QUERY_GENERAL_LAYOUT if general else 0,
-                                 cnt_t.data_ptr() if cnt_t is not None else None, sum_t.data_ptr() if sum_t is not None else None,
-                                 rets_t.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    r = rets_t.cpu().numpy()
-    assert r[n] == -77, "rets written past nchunks"
-    return (None if cnt_t is None else cnt_t.cpu().numpy().view(np.uint64), None if sum_t is None else sum_t.cpu().numpy().view(np.uint64), r[:n])
-
-
-def check_gby(x, batch, codec, esz, D, chunk_len, key, mask, key_lo, shift, nbins, H, msg, want=None, skip_table=None, bad_chunk=None, ops=3, **kw):
-    """d_count, d_sum, their padding and rets against the model; skip_table: a damaged chunk's table, which is unspecified"""
-    want = gm.groupby_rows(x, chunk_len, D, key, mask, key_lo, shift, nbins, H) if want is None else want
-    cnt, tot, rets = run_gby(batch, codec, esz, D, chunk_len, key, mask, key_lo, shift, nbins, H, ops=ops, **kw)
-    lens = np.array(fm.chunk_counts(x.size, chunk_len))
-    keep_c = np.arange(batch.nchunks) != (-1 if bad_chunk is None else bad_chunk)
-    assert np.array_equal(rets[keep_c], lens[keep_c]), ("rets",) + msg
-    if bad_chunk is not None:
-        assert rets[bad_chunk] < 0, ("rets of the damaged chunk",) + msg
-    keep_t = np.arange(want[0].shape[0]) != (-1 if skip_table is None else skip_table)
-    for name, got, w, bit in (("count", cnt, want[0], 1), ("sum", tot, want[1], 2)):
-        if ops & bit:
-            assert np.all(got[w.size:] == SENT), (name, "padding") + msg
-            assert np.array_equal(got[:w.size].reshape(w.shape)[keep_t], w[keep_t]), (name,) + msg
-        elif got is not None:
-            assert np.all(got == SENT), (name, "not selected, and written") + msg
-    return want
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data", parity_cases())

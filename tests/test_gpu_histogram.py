@@ -3,8 +3,6 @@ per-column value counts of the rows a mask names, fused into the decode, in deco
 always tests/histogram_model.py applied to the ORIGINAL input -- decode is lossless and pinned elsewhere.  Every launch's kernel family
 is asserted, d_hist lies in a sentinel-filled buffer whose padding must keep the sentinel, and rets[nchunks] must stay untouched.
 Every batch ends in a short last chunk of whole rows."""
-import ctypes as C
-import os
 import zlib
 
 import numpy as np
@@ -14,45 +12,14 @@ import filter_model as fm
 import histogram_model as hm
 from dispatch import DECODERS, ran
 from harness import DTYPES
-from test_gpu_filter import bound_sets
-from test_gpu_query_windows import gen_data, lowdim, make_batch
-from test_gpu_select import parity_masks, short_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import (HS, PARITY_FAST, bound_sets, gen_data, lowdim, make_batch, masked_parity_cases as parity_cases, parity_masks, rows_for,
+                     short_batch)
+from rowop_runners import check_hist
 
 pytestmark = pytest.mark.gpu
 
-PAD = 1024                      # entries behind d_hist that must keep the sentinel
-SENT = 0x5A5A5A5A5A5A5A5A
 CAP = 16384
-NDIMS = [1, 2, 3, 4, 5, 8, 16, 33, 80, 128, 256, 300, 512]
-SHAPES = ["r16", "tail", "nogroups"]
-DATA = ["walk", "uniform", "constant", "sparse"]
-HS = (0, 1, 2, 3)               # one histogram; one a chunk; two chunks; three: cuts every workgroup's chunk range in the middle
-# the parity shapes decode_fast.h takes, as (esz, D, general layout asked for); the planner's edges are pinned in test_histogram_cpu.py
-PARITY_FAST = {(1, 4, True), (1, 16, False), (2, 4, False), (2, 16, False)}
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def rows_for(shape, D):
-    r16 = 16 * max(2, 2048 // (16 * D))
-    return {"r16": r16, "tail": r16 + 1 + D % 15, "nogroups": 13}[shape]     # whole groups; a verbatim tail of 1 .. 15 rows; no groups
 
 
 def bins_for(D):
@@ -75,58 +42,6 @@ def binnings(rng, x, esz, D):
     return [("cover", cover, nb, None), ("no power of two", cover, nb * 3 // 4 + 1, None),
             ("random lo", cover, nb // 2 + 3, rng.integers(1, top, D)), ("around the median", 0, nb, np.mod(med - nb // 3, top)),
             ("one bin", W - 1, 1, rng.integers(1, top, D))]
-
-
-def run_hist(batch, codec, esz, D, chunk_len, mask, lo, shift, nbins, H, general=False, mask_shift=0):
-    """the C entry point on a sentinel-filled d_hist of ngroups * D * nbins entries + PAD -> (numpy uint64 incl. padding, rets [nchunks])"""
-    import torch
-    from sprintz_amd import _lib
-    n = batch.nchunks
-    ngroups = -(-n // H) if H else 1
-    hist_t = torch.from_numpy(np.full(ngroups * D * nbins + PAD, SENT, np.uint64).view(np.int64)).cuda()
-    rets_t = torch.full((n + 1,), -77, dtype=torch.int64, device="cuda")
-    mask_ptr = None
-    if mask is not None:
-        flat = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        mask_t = torch.from_numpy(np.concatenate([np.full(mask_shift, 0xFF, np.uint8), flat, np.full(16, 0xFF, np.uint8)])).cuda()
-        mask_ptr = mask_t.data_ptr() + mask_shift
-    lo_ptr = None
-    if lo is not None:
-        lo_t = torch.from_numpy(np.asarray(lo).astype(DTYPES[esz]).view(np.int8 if esz == 1 else np.int16)).cuda()
-        lo_ptr = lo_t.data_ptr()
-    _lib.check(_lib.histogram_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                   n, chunk_len, D, mask_ptr, lo_ptr, shift, nbins, H, _lib.QUERY_GENERAL_LAYOUT if general else 0,
-                                   hist_t.data_ptr(), rets_t.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    r = rets_t.cpu().numpy()
-    assert r[n] == -77, "rets written past nchunks"
-    return hist_t.cpu().numpy().view(np.uint64), r[:n]
-
-
-def check_hist(x, batch, codec, esz, D, chunk_len, mask, lo, shift, nbins, H, msg, want=None, skip_group=None, bad_chunk=None, **kw):
-    """d_hist, its padding and rets against the model; skip_group: a damaged chunk's histogram, which is unspecified"""
-    want = hm.histogram_rows(x, chunk_len, D, mask, lo, shift, nbins, H) if want is None else want
-    got, rets = run_hist(batch, codec, esz, D, chunk_len, mask, lo, shift, nbins, H, **kw)
-    lens = np.array(fm.chunk_counts(x.size, chunk_len))
-    keep_c = np.arange(batch.nchunks) != (-1 if bad_chunk is None else bad_chunk)
-    assert np.array_equal(rets[keep_c], lens[keep_c]), ("rets",) + msg
-    if bad_chunk is not None:
-        assert rets[bad_chunk] < 0, ("rets of the damaged chunk",) + msg
-    assert np.all(got[want.size:] == SENT), ("padding",) + msg
-    g = got[:want.size].reshape(want.shape)
-    keep_g = np.arange(want.shape[0]) != (-1 if skip_group is None else skip_group)
-    assert np.array_equal(g[keep_g], want[keep_g]), ("hist",) + msg
-    return want
-
-
-def parity_cases():
-    """codec x esz x ndims in full; per (codec, esz) the ndims walk the three chunk shapes and the four kinds of data"""
-    cases = []
-    for codec in ("delta", "xff"):
-        for esz in (1, 2):
-            for j, D in enumerate(NDIMS):
-                cases.append((codec, esz, D, SHAPES[j % 3], DATA[(j + (1 if codec == "xff" else 0) + 2 * (esz - 1)) % 4]))
-    return cases
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data", parity_cases())

@@ -10,8 +10,8 @@ from harness import DTYPES
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=["sync form", "sync form, hinted", "single-wave form", "big-batch form"])
-def sz(request):
+@pytest.fixture(name="sz", scope="module", params=["sync form", "sync form, hinted", "single-wave form", "big-batch form"])
+def package_on_every_stream_kernel(request):
     """every test on every stream kernel: the one-wave-per-chunk form with self-synchronising decoders (huf0_sync.h: what batches up to
     8 192 chunks get; without a size hint its blocks above 4 KB are read from global memory, with one they sit in LDS), the single-wave form
     it replaced there (a wave per 16 chunks), and the bandwidth-sized form forced (2-wave workgroups around one table, 64-byte pieces).  All three

@@ -13,21 +13,14 @@ import pytest
 
 import huf_drive as hd
 from harness import Zstd
-from test_huf_drive_cpu import check_case, decode_sample
+from codec_helpers import check_case, decode_sample
+from fixtures import gpu_lib as lib  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 SENT, POISON, GUARD = 0xEE, 0xCD, 4096
 BATCHES = list(hd.batches())
 _cache = {}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from sprintz_amd import _lib
-    return _lib
 
 
 def dev(a):

@@ -12,65 +12,11 @@ import filter_model as fm
 import linear_model as lm
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_filter import no_fast, sz  # noqa: F401  (fixtures)
-from test_gpu_query_windows import gen_data, make_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import gen_data, make_batch, quartiles, weight_sets
+from rowop_runners import raw_linear, run_linear
 
 pytestmark = pytest.mark.gpu
-
-
-def run_linear(cd, batch, w, lo, hi, u=None, bias=0, **kw):
-    got = cd.filter_linear(batch, [int(v) for v in w], lo=lo, hi=hi, lag_weights=None if u is None else [int(v) for v in u], bias=bias, **kw)
-    return got["mask"].cpu().numpy(), got["counts"].cpu().numpy().astype(np.int64)
-
-
-def raw_linear(sz, cd, batch, codec, esz, D, chunk_len, w, u, bias, lo, hi, mask, counts, rets, tmp=None):
-    """the C entry point itself, on the current stream"""
-    import torch
-    from sprintz_amd import _lib, rowops
-    w_t, u_t, bias, lo, hi = rowops.linear_terms(w, u, bias, lo, hi, D, esz, torch.device("cuda:0"))
-    if u_t is not None and tmp is None:
-        tmp = torch.empty(_lib.filter_linear_tmp_bytes(esz, batch.nchunks, D) // 8, dtype=torch.int64, device="cuda")
-    _lib.check(_lib.filter_linear(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                  batch.nchunks, chunk_len, D, w_t.data_ptr(), u_t.data_ptr() if u_t is not None else None, bias, lo, hi, 0,
-                                  tmp.data_ptr() if tmp is not None else None, mask.data_ptr() if mask is not None else None,
-                                  counts.data_ptr() if counts is not None else None, rets.data_ptr() if rets is not None else None,
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-
-
-def quartiles(s):
-    return int(np.quantile(s, 0.25, method="lower")), int(np.quantile(s, 0.75, method="lower"))
-
-
-def weight_sets(rng, x, esz, D, lag):
-    """-> [(name, w, u, bias, lo, hi)]: the issue's six, with (lag) or without a lag term.  Bounds are quantiles of the model's sums, so
-    that a predicate splits the rows; they are inputs, not tolerances."""
-    top = (1 << (8 * esz)) - 1
-    e = np.eye(D, dtype=np.int64)
-    sets = []
-    w = e[D - 1]
-    u = -w if lag else None
-    sets.append(("single", w, u, 0) + quartiles(lm.sums(x, D, w, u)))
-    w = e[0] - e[D - 1] if D > 1 else e[0]
-    u = -w if lag else None
-    sets.append(("a - b", w, u, 0, 1, None))                                   # a > b (lag: a - b grew)
-    w = np.ones(D, np.int64)
-    u = -w if lag else None
-    sets.append(("ones", w, u, 0) + quartiles(lm.sums(x, D, w, u)))
-    terms = D * (2 if lag else 1)
-    wmax = ((1 << 31) - 1) // (top * terms)
-    w = rng.integers(-wmax, wmax + 1, D)
-    u = rng.integers(-wmax, wmax + 1, D) if lag else None
-    bias = (1 << 31) - 1 - lm.bound_B(esz, w, u)                               # what is left of the bound goes into the bias: B = 2^31 - 1
-    bias = -bias if rng.integers(2) else bias
-    assert lm.bound_B(esz, w, u, bias) == (1 << 31) - 1
-    sets.append(("random", w, u, bias) + quartiles(lm.sums(x, D, w, u, bias)))
-    w = e[D // 2]
-    u = -w if lag else None
-    v = int(np.quantile(lm.sums(x, D, w, u), 0.5, method="lower"))
-    sets.append(("equal", w, u, 0, v, v))
-    sets.append(("nothing", np.ones(D, np.int64), u, 3, 5, 4))
-    return sets
 
 
 PARITY = [

@@ -4,103 +4,23 @@ decode_fast.h and decode_kernel.h.  The expected value is always tests/moments_m
 lossless and pinned elsewhere.  Every launch's kernel family is asserted, every output lies in a sentinel-filled buffer whose padding
 must keep the sentinel, and rets[nchunks] must stay untouched.  Integer outputs are compared for equality.  Every batch of the parity
 tiers ends in a short last chunk of whole rows."""
-import ctypes as C
-import os
 import zlib
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-import aggregate_model as am
 import filter_model as fm
 import moments_model as mm
 from dispatch import ran
 from harness import DTYPES
 from moments_model import U, corr_bound
-from test_gpu_aggregate import FAST_SHAPES, NDIMS, PARITY_FAST, SHAPES, DATA, rows_for, sentinel, windows_for
-from test_gpu_filter import bound_sets
-from test_gpu_query_windows import gen_data, lowdim, make_batch
-from test_gpu_select import parity_masks, short_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import (DATA, FAST_SHAPES, MASKED_NDIMS as NDIMS, MASKED_SHAPES as SHAPES, PARITY_FAST, bound_sets, gen_data, lowdim, make_batch,
+                     parity_masks, rows_for, short_batch, windows_for)
+from rowop_runners import check_mom
 
 pytestmark = pytest.mark.gpu
-
-PAD = 1024                      # entries behind every output that must keep the sentinel
-OPS = {"count": 1, "sum": 2, "sumsq": 4, "cross": 8}
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def run_mom(batch, codec, esz, D, chunk_len, mask, W, ref, ops=15, byte=0x5A, general=False, mask_shift=0, null_unselected=False):
-    """the C entry point on sentinel-filled outputs of nchunks * nwin (* D) entries + PAD -> ({op: numpy incl. padding}, rets [nchunks]);
-    mask None: a NULL d_mask"""
-    import torch
-    from sprintz_amd import _lib
-    n = batch.nchunks
-    R = chunk_len // D
-    nwin = -(-R // W)
-    m = n * nwin
-    bufs = {k: torch.from_numpy(np.full(m * D + PAD, sentinel(8, byte), np.uint64).view(np.int64)).cuda() for k in ("sum", "sumsq", "cross")}
-    bufs["count"] = torch.from_numpy(np.full(m + PAD, sentinel(4, byte), np.uint32).view(np.int32)).cuda()
-    rets_t = torch.full((n + 1,), -77, dtype=torch.int64, device="cuda")
-    mask_ptr = None
-    if mask is not None:
-        flat = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        mask_t = torch.from_numpy(np.concatenate([np.full(mask_shift, 0xFF, np.uint8), flat, np.full(16, 0xFF, np.uint8)])).cuda()
-        mask_ptr = mask_t.data_ptr() + mask_shift
-
-    def ptr(k):
-        return None if null_unselected and not ops & OPS[k] else bufs[k].data_ptr()
-    _lib.check(_lib.moments_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                 n, chunk_len, D, mask_ptr, W, ops, ref, _lib.QUERY_GENERAL_LAYOUT if general else 0,
-                                 ptr("count"), ptr("sum"), ptr("sumsq"), ptr("cross"), rets_t.data_ptr(),
-                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    r = rets_t.cpu().numpy()
-    assert r[n] == -77, "rets written past nchunks"
-    got = {k: bufs[k].cpu().numpy().view(np.uint64) for k in ("sum", "sumsq", "cross")}
-    got["count"] = bufs["count"].cpu().numpy().view(np.uint32)
-    return got, r[:n]
-
-
-def check_mom(x, batch, codec, esz, D, chunk_len, mask, W, ref, msg, want=None, ops=15, byte=0x5A, skip_chunk=None, **kw):
-    """every selected output, the unselected ones, the padding and rets against the model; skip_chunk: a damaged chunk, whose own entries
-    are unspecified"""
-    want = mm.moments_rows(x, chunk_len, D, mask, W, ref) if want is None else want
-    got, rets = run_mom(batch, codec, esz, D, chunk_len, mask, W, ref, ops, byte, **kw)
-    lens = np.array(fm.chunk_counts(x.size, chunk_len))
-    keep = np.arange(batch.nchunks) != (-1 if skip_chunk is None else skip_chunk)
-    assert np.array_equal(rets[keep], lens[keep]), ("rets",) + msg
-    if skip_chunk is not None:
-        assert rets[skip_chunk] < 0, ("rets of the damaged chunk",) + msg
-    for k in ("count", "sum", "sumsq", "cross"):
-        w = want[k]
-        sent = sentinel(4 if k == "count" else 8, byte)
-        g = got[k]
-        assert np.all(g[w.size:] == sent), (k, "padding") + msg
-        g = g[:w.size].reshape(w.shape)
-        if ops & OPS[k]:
-            assert np.array_equal(g[keep], w[keep]), (k,) + msg
-        else:
-            assert np.all(g == sent), (k, "an unselected output was written") + msg
-    return want
 
 
 def refs_for(D):

@@ -3,23 +3,16 @@ containers byte-exact with the golden ones minted from the compiled reference (a
 long streams), decoders invert them; device forms and the single-call forms; the reference's own names through
 the drop-in symbols are covered by tests/test_gpu_dropin.py."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 
 from dispatch import ran
 from harness import gen_fuzz, gen_walk
-from test_online_cpu import oracle_pack, oracle_unpack, orc, golden_online  # noqa: F401  (fixtures)
+from codec_helpers import golden_online, oracle_pack, orc  # noqa: F401  (fixtures)
+from fixtures import lib  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
 
 
 def gpu_pack_host(lib, kind, x):

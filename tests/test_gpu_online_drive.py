@@ -26,7 +26,8 @@ import pytest
 
 import online_drive as od
 from dispatch import ran
-from test_online_cpu import oracle_pack, orc  # noqa: F401  (fixtures)
+from codec_helpers import oracle_pack, orc  # noqa: F401  (fixtures)
+from fixtures import lib  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +35,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV = "SPRINTZ_MI355X_ONLINE_CHAIN"
 GUARD = 256                    # bytes behind dest, and behind out
 CHAIN, THREE = dict(on_chain=1, on_three=0), dict(on_chain=0, on_three=1)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
 
 
 @pytest.fixture(scope="module")

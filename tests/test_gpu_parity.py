@@ -10,16 +10,9 @@ import pytest
 
 from dispatch import ran
 from harness import DTYPES, REF_TEST_SIZES, gen_fuzz, gen_patterns, gen_sparse, gen_walk
+from fixtures import sz  # noqa: F401  (fixtures)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("decode_path")]
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 def gpu_compress(sz, codec, data, ndims, write_size=True):

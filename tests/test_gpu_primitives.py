@@ -8,17 +8,10 @@ import numpy as np
 import pytest
 
 import kat
-from test_primitives_cpu import SHAPES, check_kat_streams
+from codec_helpers import KAT_SHAPES as SHAPES, check_kat_streams
+from fixtures import sz  # noqa: F401  (fixtures)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("decode_path")]
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 def split(comp, offs):

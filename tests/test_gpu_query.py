@@ -7,16 +7,9 @@ import numpy as np
 import pytest
 
 from harness import DTYPES
+from fixtures import sz  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 def _col_reduce(x, D, op):

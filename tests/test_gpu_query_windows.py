@@ -9,51 +9,15 @@ import numpy as np
 import pytest
 
 import window_model as wm
-from harness import DTYPES, gen_sparse
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import chunk_len_for, gen_data, make_batch, parity_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
 
 pytestmark = pytest.mark.gpu
 
-NDIMS = [1, 2, 3, 4, 5, 8, 16, 33, 80, 128, 200, 256, 300, 512]
-SHAPES = ["r16", "tail", "nogroups", "ragged"]
 WKINDS = ["8", "24", "64", "R", ">R"]
-DATA = ["walk", "uniform", "constant", "sparse"]
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def lowdim(esz, D):
-    return D <= (4 if esz == 1 else 2)
-
-
-def chunk_len_for(shape, D):
-    r16 = 16 * max(2, 2048 // (16 * D))
-    if shape == "r16":
-        return D * r16
-    if shape == "tail":                                   # a verbatim tail of 1 .. 15 rows
-        return D * (r16 + 1 + D % 15)
-    if shape == "nogroups":                               # shorter than one group of 16 rows
-        return 16 * D - 3 if D > 1 else 13
-    return D * r16 + max(1, D // 3)                       # chunk_len % ndims != 0 (for D = 1: one more row)
 
 
 def window_for(kind, chunk_len, D):
@@ -62,62 +26,11 @@ def window_for(kind, chunk_len, D):
     return {"8": 8, "24": 24, "64": 64, "R": r8, ">R": r8 + 8}[kind]
 
 
-def gen_data(kind, rng, n, esz, D):
-    top = 1 << (8 * esz)
-    if kind == "uniform":
-        return rng.integers(0, top, n).astype(DTYPES[esz])
-    if kind == "constant":
-        return np.full(n, 0xA5 if esz == 1 else 0x1234, DTYPES[esz])
-    if kind == "sparse":
-        return gen_sparse(rng, n, esz, 0.05)
-    # walk of +-8 with flat spans of 150 rows (longer than a window): delta runs that cross window edges
-    rows = -(-n // D)
-    steps = rng.integers(-8, 9, size=(rows, D), dtype=np.int64)
-    steps[(np.arange(rows) // 150) % 3 == 1] = 0
-    x = np.cumsum(steps, axis=0) + rng.integers(0, top, size=(1, D))
-    return np.mod(x, top).astype(DTYPES[esz]).ravel()[:n]
-
-
-def make_batch(sz, oracle, codec, esz, D, chunk_len, x, general):
-    """the container as ChunkedCodec.compress builds it; general layout for low-dim shapes from the oracle's
-    *_rowmajor_*_rle_* writer (the batched encoders write sprintz.h's layout, which is the general one from 5 / 3 columns on)"""
-    import torch
-    cd = sz.ChunkedCodec(codec, esz, D, chunk_len, device="cuda:0")
-    if not (general and lowdim(esz, D)):
-        return cd, cd.compress(torch.from_numpy(x.view(np.int8 if esz == 1 else np.int16)).cuda().view(cd.dtype))
-    n = x.size
-    nchunks = -(-n // chunk_len)
-    streams = [oracle.compress_rowmajor(codec, x[c * chunk_len:(c + 1) * chunk_len], D)[0] for c in range(nchunks)]
-    offs = np.zeros(nchunks + 1, np.int64)
-    for c, s in enumerate(streams):
-        offs[c + 1] = (offs[c] + s.size + 15) & ~15
-    data = np.zeros(int(offs[-1]) + sz._lib.READ_SLACK, np.uint8)
-    for c, s in enumerate(streams):
-        data[offs[c]:offs[c] + s.size] = s
-    batch = sz.CompressedBatch(torch.from_numpy(data).cuda(), torch.from_numpy(offs).cuda(),
-                               torch.tensor([s.size for s in streams], dtype=torch.int32).cuda(), nchunks, n, chunk_len, D)
-    return cd, batch
-
-
 def assert_windows(got, want, msg):
     mn, mx, sm = want
     assert np.array_equal(got["min"].cpu().numpy().astype(np.int64), mn.astype(np.int64)), ("min",) + msg
     assert np.array_equal(got["max"].cpu().numpy().astype(np.int64), mx.astype(np.int64)), ("max",) + msg
     assert np.array_equal(got["sum"].cpu().numpy().view(np.uint64), sm), ("sum",) + msg
-
-
-def parity_cases():
-    """codec x esz x ndims in full; per (codec, esz) the 14 ndims walk the chunk shapes, data and layouts so that every
-    value of every axis meets both codecs and both widths; each case is queried at all five windows on both families"""
-    cases = []
-    for codec in ("delta", "xff"):
-        for esz in (1, 2):
-            for j, D in enumerate(NDIMS):
-                shape = SHAPES[j % 4]
-                data = DATA[(j + (1 if codec == "xff" else 0) + 2 * (esz - 1)) % 4]
-                general = (j // 2 + esz) % 2 == 1
-                cases.append((codec, esz, D, shape, data, general))
-    return cases
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data,general", parity_cases())
@@ -272,7 +185,7 @@ def test_query_windows_global_refuses_unaligned_shapes(sz):
 def test_query_windows_bench_sizes(sz, name, W):
     """the bench's own inputs at full size: every entry equals torch's reductions of the device-decoded batch"""
     import torch
-    from test_gpu_bench_data import bench_input
+    from rowdata import bench_input
     (codec, esz, D, chunk_len, nchunks), x = bench_input(name, "cuda:0")
     cd = sz.ChunkedCodec(codec, esz, D, chunk_len, device="cuda:0")
     batch = cd.compress(x)

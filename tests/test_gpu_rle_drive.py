@@ -18,7 +18,6 @@ decode_fast.h (SPRINTZ_OPT_CHUNKS_PER_GROUP); the later ones are in tests/test_g
 import json
 import os
 import zlib
-from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -31,24 +30,16 @@ import select_model as sm
 import window_model as wm
 from dispatch import ROUND6, ran
 from harness import DTYPES
-from test_gpu_aggregate import check_agg
-from test_gpu_dispatch import check_streams
-from test_gpu_filter import bound_sets, run_filter
-from test_gpu_fire_extremes import DEF, DENSE, GENERIC, OLD, options, to_device
-from test_gpu_select import check_select
+from drive_tables import (BOTH, CAP_CASES, CASES, LAT_SINGLE, NB, NCHUNKS, ROWOP_CASES, ROWOP_IDS, WINDOWS, batch_of, family_of, legs, oracle_batch,
+                          rowop_batch, run_masks)
+from fixtures import chunks_per_group, no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import bound_sets
+from rowop_runners import check_agg, check_select, run_filter
+from streams import DEF, DENSE, OLD, check_streams, options, to_device
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_rledrive_v1")
-NCHUNKS, NB = 16, 256            # the fixture's batch: 16 rotations of 256 blocks (a 129-block run and every prefix)
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 @pytest.fixture(scope="module")
@@ -57,36 +48,6 @@ def golden():
         manifest = json.load(f)["cases"]
     arrays = np.load(GOLDEN + ".npz")
     return {(m["codec"], m["w"], m["ndims"], m["kind"]): (m, arrays[m["name"]]) for m in manifest}
-
-
-@lru_cache(maxsize=None)
-def batch_of(codec, w, D, kind, nchunks, nblocks, r=0):
-    """(flat samples, chunk_len, all-zero flags); read-only, shared by the cases of the module"""
-    x, chunk_len, zero = rd.batch(codec, w, D, kind, nchunks, nblocks, r)
-    x.setflags(write=False)
-    return x, chunk_len, zero
-
-
-def oracle_batch(sz, oracle, codec, D, data, chunk_len):
-    """the ORACLE's streams as a container (16-byte aligned, as ChunkedCodec.compress builds it)"""
-    import torch
-    streams = oracle.compress_chunks(codec, data, chunk_len, D)
-    offs = np.zeros(len(streams) + 1, np.int64)
-    for c, s in enumerate(streams):
-        offs[c + 1] = (offs[c] + s.size + 15) & ~15
-    comp = np.zeros(int(offs[-1]) + sz._lib.READ_SLACK, np.uint8)
-    for c, s in enumerate(streams):
-        comp[offs[c]:offs[c] + s.size] = s
-    return sz.CompressedBatch(torch.from_numpy(comp).cuda(), torch.from_numpy(offs).cuda(), torch.tensor([s.size for s in streams], dtype=torch.int32).cuda(),
-                              len(streams), data.size, chunk_len, D)
-
-
-def family_of(f):
-    """a family literal, or ("falls through: why", the older family that must run instead)"""
-    if isinstance(f, tuple):
-        assert f[0].startswith("falls through: ") and f[1] not in ROUND6, f
-        return f[1], True
-    return f, False
 
 
 def decode_checked(cd, batch, data, chunk_len, nchunks, dec, fell, tag):
@@ -128,66 +89,6 @@ def roundtrip(sz, oracle, golden, codec, w, D, kind, nchunks, nblocks, r, enc, d
     roundtrip_data(sz, oracle, codec, w, D, data, chunk_len, nchunks, enc, dec, f"{tag} [{codec} {kind} r={r}]", fixture)
 
 
-BLK = dict(lat=0, blk_chunks=1, mask=7)                # encode_blk.h, decode_blk.h, encode_blk_uni
-ROW = dict(lat=0, blk_chunks=1, mask=25)               # encode_blk.h, decode_row.h on every shape it fits
-BOTH, DELTA = ("delta", "xff"), ("delta",)
-PIECES = "falls through: encode_blk.h takes rows of whole 16-byte pieces"
-TASKS = "falls through: encode_blk.h takes at most 256 (block, piece) tasks a chunk: 48 blocks x 16 pieces"
-LOWDIM_DEC = "falls through: the low-dim layout has no block-parallel decoder (decode_uni.h)"
-
-# id, codecs, options, w, ndims, chunks, blocks a chunk, elements behind the last whole block, encoder, decoder
-CASES = [
-    # ---- a workgroup per chunk (encode_lat.h: the scan formulation; decode_lat.h)
-    ("lat u8 D=1", BOTH, DEF, 8, 1, NCHUNKS, NB, 0, "enc_lat", "dec_lat"),
-    ("lat u16 D=8", BOTH, DEF, 16, 8, NCHUNKS, NB, 0, "enc_lat", "dec_lat"),
-    ("lat u8 D=16: 192 blocks (24 KB: what the carve of 150 KB takes)", BOTH, DEF, 8, 16, NCHUNKS, 192, 0, "enc_lat", "dec_lat"),
-    # ---- the low-dim layout, a lane per chunk (encode_uni.h, decode_uni.h)
-    ("uni u8 D=1", BOTH, OLD, 8, 1, NCHUNKS, NB, 0, "enc_uni", "dec_uni"),
-    ("uni u8 D=1 r=1", BOTH, OLD, 8, 1, NCHUNKS, NB, 1, "enc_uni", "dec_uni"),
-    ("uni u8 D=1 r=7", BOTH, OLD, 8, 1, NCHUNKS, NB, 7, "enc_uni", "dec_uni"),
-    ("uni u8 D=2", BOTH, OLD, 8, 2, NCHUNKS, NB, 0, "enc_uni", "dec_uni"),
-    ("uni u8 D=3", BOTH, OLD, 8, 3, NCHUNKS, NB, 0, "enc_uni", "dec_uni"),
-    ("uni u8 D=3 r=23", BOTH, OLD, 8, 3, NCHUNKS, NB, 23, "enc_uni", "dec_uni"),
-    ("uni u8 D=4", BOTH, OLD, 8, 4, NCHUNKS, NB, 0, "enc_uni", "dec_uni"),
-    ("uni u16 D=1", BOTH, OLD, 16, 1, NCHUNKS, NB, 0, "enc_uni", "dec_uni"),
-    ("uni u16 D=2", BOTH, OLD, 16, 2, NCHUNKS, NB, 0, "enc_uni", "dec_uni"),
-    ("uni u16 D=2 r=1", BOTH, OLD, 16, 2, NCHUNKS, NB, 1, "enc_uni", "dec_uni"),
-    ("uni u16 D=2 r=15", BOTH, OLD, 16, 2, NCHUNKS, NB, 15, "enc_uni", "dec_uni"),
-    # ---- the general layout, a lane per column or column pair (encode_wide.h, encode_fast.h; decode_fast.h)
-    ("pair u16 D=8", BOTH, OLD, 16, 8, NCHUNKS, NB, 0, "enc_pair", "dec_fast"),
-    ("fast u16 D=8 (ENC_PAIR 0)", BOTH, dict(OLD, pair=0), 16, 8, NCHUNKS, NB, 0, "enc_fast", "dec_fast"),
-    ("pair u8 D=6", BOTH, OLD, 8, 6, NCHUNKS, NB, 0, "enc_pair", "dec_fast"),
-    ("fast u8 D=6 (ENC_PAIR 0)", BOTH, dict(OLD, pair=0), 8, 6, NCHUNKS, NB, 0, "enc_fast", "dec_fast"),
-    ("pair u8 D=32", BOTH, OLD, 8, 32, NCHUNKS, NB, 0, "enc_pair", "dec_fast"),
-    ("fast u8 D=32 (ENC_PAIR 0)", BOTH, dict(OLD, pair=0), 8, 32, NCHUNKS, NB, 0, "enc_fast", "dec_fast"),
-    ("split u8 D=80", BOTH, OLD, 8, 80, NCHUNKS, 51, 0, "enc_split", "dec_fast"),
-    ("wide u8 D=96", BOTH, OLD, 8, 96, NCHUNKS, 48, 0, "enc_wide", "dec_fast"),
-    ("wide u16 D=80", BOTH, OLD, 16, 80, NCHUNKS, 48, 0, "enc_wide", "dec_fast"),
-    # ---- encode_kernel.h / decode_kernel.h: rows that are no whole 16-byte pieces, and everything under NO_FAST
-    ("generic u8 D=5", BOTH, OLD, 8, 5, NCHUNKS, NB, 0, "enc_generic", "dec_generic"),
-    ("generic u8 D=5 r=1", BOTH, OLD, 8, 5, NCHUNKS, NB, 1, "enc_generic", "dec_generic"),
-    ("generic u8 D=5 r=39", BOTH, OLD, 8, 5, NCHUNKS, NB, 39, "enc_generic", "dec_generic"),
-    ("generic u8 D=1 (NO_FAST)", BOTH, GENERIC, 8, 1, NCHUNKS, NB, 0, "enc_generic", "dec_generic"),
-    ("generic u8 D=1 r=7 (NO_FAST)", BOTH, GENERIC, 8, 1, NCHUNKS, NB, 7, "enc_generic", "dec_generic"),
-    ("generic u8 D=8 (NO_FAST)", BOTH, GENERIC, 8, 8, NCHUNKS, NB, 0, "enc_generic", "dec_generic"),
-    ("generic u8 D=8 r=63 (NO_FAST)", BOTH, GENERIC, 8, 8, NCHUNKS, NB, 63, "enc_generic", "dec_generic"),
-    # ---- more than 512 columns: a workgroup per chunk (any_ndims.hip); 2 chunks of 48 blocks
-    ("any u8 D=600", BOTH, OLD, 8, 600, 2, 48, 0, "enc_any", "dec_any"),
-    ("big u8 D=2048", BOTH, OLD, 8, 2048, 2, 48, 0, "enc_big", "dec_big"),
-    # ---- the block-parallel delta kernels: rle_walk_scan over per-lane pieces (encode_blk.h), decode_blk.h, decode_row.h
-    ("blk u8 D=16: 256 tasks", DELTA, BLK, 8, 16, NCHUNKS, NB, 0, "enc_blk", "dec_blk"),
-    ("blk u8 D=80: 255 tasks", DELTA, BLK, 8, 80, NCHUNKS, 51, 0, "enc_blk", "dec_blk"),
-    ("blk u16 D=8: 256 tasks", DELTA, BLK, 16, 8, NCHUNKS, NB, 0, "enc_blk", "dec_blk"),
-    ("row u8 D=16", DELTA, ROW, 8, 16, NCHUNKS, NB, 0, "enc_blk", "dec_row"),
-    ("row u8 D=80", DELTA, ROW, 8, 80, NCHUNKS, 51, 0, "enc_blk", "dec_row"),
-    ("row u16 D=8", DELTA, ROW, 16, 8, NCHUNKS, NB, 0, "enc_blk", "dec_row"),
-    ("row u8 D=12", DELTA, ROW, 8, 12, NCHUNKS, NB, 0, (PIECES, "enc_pair"), "dec_row"),
-    ("row u8 D=256", DELTA, ROW, 8, 256, NCHUNKS, 48, 0, (TASKS, "enc_generic"), "dec_row"),
-    ("blk_uni u8 D=1", DELTA, BLK, 8, 1, NCHUNKS, NB, 0, "enc_blk_uni", (LOWDIM_DEC, "dec_uni")),
-    ("blk_uni u16 D=1", DELTA, BLK, 16, 1, NCHUNKS, NB, 0, "enc_blk_uni", (LOWDIM_DEC, "dec_uni")),
-]
-
-
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_runs_through_every_edge_on_every_kernel(sz, oracle, golden, case):
     tag, codecs, opts, w, D, nchunks, nblocks, r, enc, dec = case
@@ -195,11 +96,6 @@ def test_runs_through_every_edge_on_every_kernel(sz, oracle, golden, case):
         for codec in codecs:
             for kind in rd.KINDS:
                 roundtrip(sz, oracle, golden, codec, w, D, kind, nchunks, nblocks, r, enc, dec, tag)
-
-
-# In a batch of more than one chunk, encode_lat.h and decode_lat.h take chunks of whole 16-byte pieces only (every chunk starts 16-byte
-# aligned); a single chunk may end anywhere.  So r = 1 and r = 8 D - 1 reach them one chunk a call: w, ndims, blocks, r
-LAT_SINGLE = [(8, 1, NB, 1), (8, 1, NB, 7), (16, 8, NB, 1), (16, 8, NB, 63), (8, 16, 192, 127)]
 
 
 @pytest.mark.parametrize("w,D,nblocks,r", LAT_SINGLE)
@@ -212,13 +108,6 @@ def test_workgroup_per_chunk_kernels_on_chunks_that_are_no_whole_blocks(sz, orac
                 for c in range(NCHUNKS):
                     roundtrip_data(sz, oracle, codec, w, D, data[c * chunk_len:(c + 1) * chunk_len], chunk_len, 1, "enc_lat", "dec_lat",
                                    f"lat w={w} D={D} [{codec} {kind} r={r} chunk {c}]")
-
-
-# id, options, w, ndims, encoder, decoder: 3 chunks of 70 000 all-zero blocks and two packed ones, on the family the planner assigns
-CAP_CASES = [
-    ("cap u8 D=1", OLD, 8, 1, "enc_uni", "dec_uni"),
-    ("cap u8 D=5", OLD, 8, 5, "enc_generic", "dec_generic"),
-]
 
 
 @pytest.mark.parametrize("codec", BOTH)
@@ -244,77 +133,7 @@ def test_the_cap(sz, oracle, case, codec):
 
 # ------------------------------------------------------------------ row operations over the same batches
 
-# w, ndims -> the decoder family of: windows, filter, select, aggregate (csrc/plan.h: the reduce-only modes do not need rows of whole
-# 16-byte pieces, select and gather do), and the gather family
-# ... and of the later reduce-only modes -- histogram, moments, group-by, extrema, the linear filter -- with the tables of
-# tests/test_gpu_rowop_drive.py (at most 128 x (D + 1) entries: 17 KB behind the groups' carves)
-LATER = dict(histogram="dec_fast", moments="dec_fast", groupby="dec_fast", extrema="dec_fast", linear="dec_fast")
-ROWOP_SHAPES = {
-    (16, 8): dict(window="dec_fast", filter="dec_fast", select="dec_fast", aggregate="dec_fast", gather="gather_fast", **LATER),
-    (8, 32): dict(window="dec_fast", filter="dec_fast", select="dec_fast", aggregate="dec_fast", gather="gather_fast", **LATER),
-    (16, 12): dict(window="dec_fast", filter="dec_fast", select="dec_generic", aggregate="dec_fast", gather="gather_generic", **LATER),
-}
-ROWOP_KINDS = ("lengths", "start", "alternate", "tails")
-ROWOP_CASES = [(codec, w, D, kind) for codec in BOTH for (w, D) in ROWOP_SHAPES for kind in ROWOP_KINDS]
-ROWOP_IDS = [f"{c}-u{w}x{D}-{k}" for c, w, D, k in ROWOP_CASES]
-WINDOWS = (8, 24)                                       # window_rows is a multiple of 8 at every entry point: one block a window, and
                                                         # three -- runs of 1, 2, 4, 5 ... blocks start and end inside windows
-
-
-@pytest.fixture
-def no_fast():
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-@pytest.fixture
-def chunks_per_group():
-    """set_option(OPT_CHUNKS_PER_GROUP) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(k):
-        _lib.check(_lib.set_option(_lib.OPT_CHUNKS_PER_GROUP, int(k)))
-    yield setter
-    _lib.set_option(_lib.OPT_CHUNKS_PER_GROUP, int(os.environ.get("SPRINTZ_MI355X_CHUNKS_PER_GROUP", 1)))
-
-
-def rowop_batch(sz, oracle, codec, w, D, kind):
-    """the ORACLE's container of the batch: expected values come from the models on the raw samples, never from a decode by the library"""
-    data, chunk_len, zero = batch_of(codec, w, D, kind, NCHUNKS, NB)
-    cd = sz.ChunkedCodec(codec, w // 8, D, chunk_len, device="cuda:0")
-    return cd, oracle_batch(sz, oracle, codec, D, data, chunk_len), data, chunk_len, zero
-
-
-def families(w, D, op):
-    """(NO_FAST, family) pairs: the planner's family for the shape, then decode_kernel.h on the same batch"""
-    first = ROWOP_SHAPES[(w, D)][op]
-    generic = "gather_generic" if op == "gather" else "dec_generic"
-    return [(0, first)] + ([(1, generic)] if first != generic else [])
-
-
-CPGS = (1, 3)                                          # chunks a lane group of decode_fast.h: at 3 the 16 chunks fall to groups of 3, 3, 3, 3, 3 and 1
-
-
-def legs(w, D, op):
-    """(NO_FAST, chunks_per_group, family): the planner's family at one and at three chunks a lane group -- the chunk loop of
-    decode_fast.h resets every mode's per-chunk state and reads ahead across the seam -- then decode_kernel.h, which ignores the
-    option, once"""
-    out = []
-    for fam, family in families(w, D, op):
-        out += [(fam, cpg, family) for cpg in (CPGS if family in ("dec_fast", "gather_fast") else CPGS[:1])]
-    return out
-
-
-def run_masks(zero, seed):
-    """uint8 [nchunks, MB] in filter_rows' layout (8 rows a byte: a block a byte): pseudo-random rows, exactly the rows inside runs,
-    exactly the rows outside"""
-    rng = np.random.default_rng(seed)
-    inside = np.where(zero, 0xFF, 0).astype(np.uint8)
-    return [("random", rng.integers(0, 256, zero.shape).astype(np.uint8)), ("inside runs", inside), ("outside runs", ~inside)]
 
 
 @pytest.mark.parametrize("codec,w,D,kind", ROWOP_CASES, ids=ROWOP_IDS)

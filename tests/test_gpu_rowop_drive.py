@@ -13,14 +13,12 @@ Expected values are the numpy models applied to the RAW samples, never a decode 
 launch asserts its kernel family (literals that tests/test_rowop_drive_cpu.py replays through the planner), and every comparison is
 exact.  What the batches, masks, binnings and bands below must reach is asserted without a device in tests/test_rowop_drive_cpu.py."""
 import ctypes as C
-from functools import lru_cache
 
 import numpy as np
 import pytest
 
 import extrema_model as em
 import filter_model as fm
-import fire_drive as fd
 import groupby_model as gbm
 import histogram_model as hm
 import linear_model as lm
@@ -28,101 +26,19 @@ import moments_model as mm
 import select_model as sm
 import window_model as wm
 import zone_model as zm
-import test_gpu_fire_extremes as fx
+from drive_tables import (BAD, DAMAGE_IDS, DAMAGE_SHAPES, FIRE_COL, FIRE_IDS, FIRE_SHAPES, GBY_KEY, GBY_TABLES, LIN_COL, NCHUNKS, ROWOP_CASES,
+                          ROWOP_IDS, WINDOWS, band_bounds, damaged, fire_batch, fire_change_bounds, fire_legs, fire_patched, fire_windows,
+                          gby_binning, hist_binnings, legs, linear_sets, masks_for, refs_for, rowop_batch, three_of_8, truncated, zone_band)  # noqa: F401  (fixtures)
+from fixtures import chunks_per_group, no_fast, sentinels, sz  # noqa: F401  (fixtures)
+from rowdata import bound_sets
+from rowop_runners import assert_zone_map, check_agg, check_ext, check_gby, check_hist, check_mom, raw_linear, run_linear, run_select
+from streams import OLD, options
 from dispatch import ran
-from test_gpu_aggregate import check_agg
-from test_gpu_extrema import check_ext
-from test_gpu_filter import bound_sets
-from test_gpu_fire_extremes import GENERIC, OLD, options
-from test_gpu_groupby import check_gby
-from test_gpu_histogram import check_hist
-from test_gpu_linear import quartiles, raw_linear, run_linear
-from test_gpu_moments import check_mom
-from test_gpu_rle_drive import (BOTH, NCHUNKS, ROWOP_CASES, ROWOP_IDS, WINDOWS, chunks_per_group, legs, no_fast, rowop_batch, run_masks,  # noqa: F401  (fixtures)
-                                sz)
-from test_gpu_select import run_select, sentinels
-from test_gpu_zone import assert_zone_map
 
 pytestmark = pytest.mark.gpu
 
 
 # ------------------------------------------------------------------ what the cases run on: pure functions of the seeded batches, shared with the CPU tier
-
-def masks_for(zero, seed):
-    """run_masks' three -- pseudo-random rows, exactly the rows inside runs, exactly the rows outside -- and no mask at all"""
-    return run_masks(zero, seed) + [("none", None)]
-
-
-def refs_for(D):
-    """the moments' reference column: the first, a middle and the last one"""
-    return (0, D // 2, D - 1)
-
-
-def hist_binnings(w, D):
-    """[(name, lo [D] or None, shift, nbins, chunks a histogram)]: the middle half of the range at full (8 bits) or 1 / 256 (16 bits)
-    resolution -- the delta drive's columns walk out from 0 by amplitudes of their own, so a run's value lies inside the bins in some
-    chunks and outside in others --, one histogram a batch; and bins of 4 (256) values over the whole range, a histogram every two
-    chunks: at three chunks a lane group a histogram ends inside a group"""
-    if w == 8:
-        return [("clip", np.full(D, 64, np.int64), 0, 128, 0), ("shift", None, 2, 64, 2)]
-    return [("clip", np.full(D, 0x4000, np.int64), 8, 128, 0), ("shift", None, 8, 256, 2)]
-
-
-# group-by: the key column -- the first one behind column 0 that moves in at least 12 of the delta drive's 16 chunks (a column's
-# amplitude is drawn per chunk, and 0 is one of the draws; tests/test_rowop_drive_cpu.py asserts it) -- and the bins: the middle half of
-# the key's range, as the histogram's, so that whole runs are dropped in some chunks and counted in others
-GBY_KEY = {(16, 8): 1, (8, 32): 1, (16, 12): 1}
-
-
-def gby_binning(w):
-    """(key_lo, shift, nbins)"""
-    return (64, 0, 128) if w == 8 else (0x4000, 8, 128)
-
-
-GBY_TABLES = (0, 2)                                    # chunks a table: one table; one every two chunks
-
-
-def linear_sets(x, D, col):
-    """[(name, w, u, bias, lo, hi)]: a sum over the row, a change of one column against the row in front (w + u = 0: a delta run's rows
-    all have s = bias), and a lag term with w + u != 0 (a run's rows have s = sum (w + u) x: what the shortcut evaluates once).  The
-    bounds are the quartiles of the model's sums, so that a predicate splits the rows; they are inputs, not tolerances"""
-    e = np.eye(D, dtype=np.int64)
-    ones = np.ones(D, np.int64)
-    sets = []
-    for name, w, u in (("ones", ones, None), ("change", e[col], -e[col]), ("w + u != 0", ones, 2 * e[col])):
-        sets.append((name, w, u, 0) + quartiles(lm.sums(x, D, w, u)))
-    return sets
-
-
-LIN_COL = GBY_KEY                                      # the column whose change is asked for: one that moves
-
-
-def zone_band(x, chunk_len, D, w):
-    """-> (column, lo) of the band lo <= x[column] <= the type's maximum, every other column open: the first column, and for it the
-    threshold, under which the zone map decides the most chunks while at least two are decided (a chunk whose column lies wholly above
-    or wholly below lo) and at least two must be decoded -- or None where no such band exists.  Read off the model's map alone"""
-    zmin, zmax, _ = zm.zone_map(x, chunk_len, D, w // 8)
-    zmin, zmax = zmin.astype(np.int64), zmax.astype(np.int64)
-    best = None
-    for d in range(D):
-        for lo in sorted(set((zmin[:, d] + 1).tolist()) | set(zmin[:, d].tolist()) | set((zmax[:, d] + 1).tolist())):
-            if not 0 < lo < 1 << w:
-                continue
-            decided = int(((zmin[:, d] >= lo) | (zmax[:, d] < lo)).sum())
-            if decided >= 2 and zmin.shape[0] - decided >= 2 and (best is None or decided > best[0]):
-                best = (decided, d, int(lo))
-        if best is not None:
-            break
-    return None if best is None else best[1:]
-
-
-def band_bounds(band, w, D):
-    """-> (lo [D], hi [D]) of filter_rows, (weights [D], lo, hi) of filter_linear: the same predicate twice"""
-    d, t = band
-    top = (1 << w) - 1
-    lo, hi = np.zeros(D, np.int64), np.full(D, top, np.int64)
-    lo[d] = t
-    return (lo, hi), (np.eye(D, dtype=np.int64)[d], t, top)
 
 
 # ------------------------------------------------------------------ 1 + 2. the RLE drive, at one and at three chunks a lane group
@@ -261,29 +177,6 @@ def test_zone_map_and_pruning_over_runs(sz, oracle, no_fast, chunks_per_group, c
 
 # ------------------------------------------------------------------ a chunk rejected at its header in the middle of a lane group
 
-BAD = 4                                                # at three chunks a group: the middle chunk of the second group
-DAMAGE_SHAPES = [(codec, w, D) for codec in BOTH for (w, D) in ((16, 8), (8, 32))]       # (select rows needs rows of whole 16-byte pieces on decode_fast.h)
-DAMAGE_IDS = [f"{c}-u{w}x{D}" for c, w, D in DAMAGE_SHAPES]
-
-
-@pytest.fixture
-def damaged(sz, oracle, no_fast, chunks_per_group):
-    """-> f(codec, w, D): the "lengths" batch in the oracle's container with a wrong ndims in bytes 6 .. 7 of chunk 4's stream header, on
-    decode_fast.h at three chunks a lane group.  The chunk is rejected before anything of it is parsed: its rets entry is negative, its
-    own outputs are unspecified, and chunk 5 starts after a re-prime with its neighbours' state left in the registers"""
-    import torch
-
-    def make(codec, w, D):
-        cd, batch, data, chunk_len, zero = rowop_batch(sz, oracle, codec, w, D, "lengths")
-        off = int(batch.offsets[BAD].item())
-        wrong = D ^ 5
-        batch.data[off + 6:off + 8] = torch.tensor([wrong & 0xFF, wrong >> 8], dtype=torch.uint8, device="cuda")
-        no_fast(0)
-        chunks_per_group(3)
-        return cd, batch, data, chunk_len, masks_for(zero, 31)[0][1]
-    with options(**OLD):
-        yield make
-
 
 def keep_chunks():
     return np.arange(NCHUNKS) != BAD
@@ -317,7 +210,7 @@ def test_damaged_chunk_in_a_group_query_windows(sz, damaged, codec, w, D):
 
 @pytest.mark.parametrize("codec,w,D", DAMAGE_SHAPES, ids=DAMAGE_IDS)
 def test_damaged_chunk_in_a_group_zone_map(sz, damaged, codec, w, D):
-    from test_gpu_zone import host
+    from rowop_runners import host
     cd, batch, data, chunk_len, _ = damaged(codec, w, D)
     zmin, zmax, zlen = zm.zone_map(data, chunk_len, D, w // 8)
     with ran(only=["dec_fast"], dec_fast=1):
@@ -453,28 +346,6 @@ def test_damaged_chunk_in_a_group_filter_change(sz, damaged, codec, w, D):
 
 # ------------------------------------------------------------------ ... and a chunk that goes wrong at its END in the middle of a group
 
-@pytest.fixture
-def truncated(sz, oracle, no_fast, chunks_per_group):
-    """-> f(codec, w, D): the "lengths" batch with chunk 4's stream cut short by 5 bytes and the streams packed densely again, as
-    tests/test_gpu_extrema.py truncates them, on decode_fast.h at three chunks a lane group.  Unlike a header that is rejected, this
-    chunk is decoded block by block and found damaged behind its last group: at a window of 64 rows its last window is then open, its
-    rows and sums still in the registers -- what the chunk loop's reset has to clear before chunk 5"""
-    import torch
-
-    def make(codec, w, D):
-        cd, batch, data, chunk_len, zero = rowop_batch(sz, oracle, codec, w, D, "lengths")
-        comp, offs, sizes = batch.data.cpu().numpy(), batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy()
-        parts = [comp[offs[c]:offs[c] + sizes[c] - (5 if c == BAD else 0)] for c in range(NCHUNKS)]
-        toffs = np.zeros(NCHUNKS + 1, np.int64)
-        toffs[1:] = np.cumsum([p.size for p in parts])
-        cut = sz.CompressedBatch(torch.from_numpy(np.concatenate(parts + [np.zeros(sz._lib.READ_SLACK, np.uint8)])).cuda(), torch.from_numpy(toffs).cuda(),
-                                 torch.tensor([p.size for p in parts], dtype=torch.int32).cuda(), NCHUNKS, data.size, chunk_len, D)
-        no_fast(0)
-        chunks_per_group(3)
-        return cd, cut, data, chunk_len, masks_for(zero, 32)[0][1]
-    with options(**OLD):
-        yield make
-
 
 TRUNCATED_WINDOW = 64                                  # 32 windows a chunk: the last one takes blocks 248 .. 255, of which 255 is the verbatim tail's
 
@@ -504,66 +375,7 @@ def test_truncated_chunk_in_a_group_aggregate_rows(sz, truncated, codec, w, D):
 
 # ------------------------------------------------------------------ 3. the FIRE counter drive
 
-FIRE_SHAPES = {
-    # (w, D): chunks, then (options, NO_FAST leg's chunks_per_group values, family) of every leg.  8 bits: every counter wraps, with run
-    # spans at frozen extreme coefficients.  16 bits, one column: the low-dim coefficient passes 2^23; decode_uni.h is not taught these modes
-    (8, 8): (7, [(OLD, 1, "dec_fast"), (OLD, 3, "dec_fast"), (GENERIC, 1, "dec_generic")]),
-    (16, 1): (5, [(OLD, 1, "dec_generic")]),
-}
-FIRE_IDS = [f"u{w}x{D}" for w, D in FIRE_SHAPES]
-FIRE_COL = 0                                           # the column whose change is asked for
 FIRE_KEY = 1                                           # group-by: the key column (8 columns only)
-PATCH_CHUNK, PATCH_TOP, PATCH_ZERO = 4, 140 * 64 + 13, 142 * 64 + 40        # (the middle chunk of the second group of three)
-
-
-def fire_rows(w, D):
-    return 8 * (fd.NB8 if w == 8 else fd.NB16)
-
-
-def fire_windows(w, D):
-    """64 rows, and one window a chunk"""
-    return (64, fire_rows(w, D))
-
-
-def three_of_8(nchunks, R):
-    return np.full((nchunks, R // 8), 0b00100101, np.uint8)
-
-
-@lru_cache(maxsize=None)
-def fire_patched(w, D):
-    """-> (samples, mask): a copy of the batch with one row of all ones in every column and one of zeros, in two windows of 64 rows of
-    chunk 4, under the 3-of-8 mask with those two rows as their windows' only selected ones -- a selected all-ones value is a minimum
-    with a row, a selected 0 a maximum with a row: the edges behind the extrema identities, whatever the drive gives"""
-    nchunks = FIRE_SHAPES[(w, D)][0]
-    data, chunk_len = fx.batch_of(w, D, nchunks)
-    R = chunk_len // D
-    x = data.copy().reshape(nchunks, R, D)
-    x[PATCH_CHUNK, PATCH_TOP] = (1 << w) - 1
-    x[PATCH_CHUNK, PATCH_ZERO] = 0
-    mask = three_of_8(nchunks, R)
-    for r in (PATCH_TOP, PATCH_ZERO):
-        mask[PATCH_CHUNK, r // 64 * 8:r // 64 * 8 + 8] = 0
-        mask[PATCH_CHUNK, r >> 3] = 1 << (r & 7)
-    x = x.ravel()
-    x.setflags(write=False)
-    mask.setflags(write=False)
-    return x, mask
-
-
-def fire_batch(sz, oracle, w, D, data=None):
-    nchunks = FIRE_SHAPES[(w, D)][0]
-    x, chunk_len = fx.batch_of(w, D, nchunks)
-    data = x if data is None else data
-    cd = sz.ChunkedCodec("xff", w // 8, D, chunk_len, device="cuda:0")
-    return cd, fx.oracle_batch(sz, oracle, D, data, chunk_len), data, chunk_len, nchunks
-
-
-def fire_legs(sz, w, D, chunks_per_group):
-    """every leg of the shape under its options: -> (family, chunks_per_group)"""
-    for opts, cpg, family in FIRE_SHAPES[(w, D)][1]:
-        with options(**opts):
-            chunks_per_group(cpg)
-            yield family, cpg
 
 
 @pytest.mark.parametrize("w,D", list(FIRE_SHAPES), ids=FIRE_IDS)
@@ -613,10 +425,6 @@ def test_groupby_rows_on_the_fire_drive(sz, oracle, chunks_per_group):
             for family, cpg in fire_legs(sz, w, D, chunks_per_group):
                 with ran(only=[family], **{family: 1}):
                     check_gby(data, batch, "xff", w // 8, D, chunk_len, FIRE_KEY, mask, 0, 0, 256, H, (w, D, name, H, family, cpg), want)
-
-
-def fire_change_bounds(data, D):
-    return quartiles(lm.sums(data, D, np.eye(D, dtype=np.int64)[FIRE_COL], -np.eye(D, dtype=np.int64)[FIRE_COL]))
 
 
 @pytest.mark.parametrize("w,D", list(FIRE_SHAPES), ids=FIRE_IDS)

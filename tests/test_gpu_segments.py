@@ -16,12 +16,11 @@ import segment_model as sgm
 from dispatch import counts as dispatch_counts
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_aggregate import FAST_SHAPES, PARITY_FAST, no_fast, parity_cases, rows_for, sz  # noqa: F401  (fixtures)
-from test_gpu_fire_extremes import OLD, options
-from test_gpu_query_windows import gen_data, lowdim, make_batch
-from test_gpu_rle_drive import NCHUNKS, ROWOP_CASES, ROWOP_IDS, chunks_per_group, legs, rowop_batch  # noqa: F401  (fixtures)
-from test_gpu_rowop_drive import BAD, DAMAGE_IDS, DAMAGE_SHAPES, FIRE_IDS, FIRE_SHAPES, damaged, fire_batch, fire_legs, masks_for, three_of_8, truncated  # noqa: F401
-from test_gpu_select import parity_masks, short_batch
+from drive_tables import (BAD, DAMAGE_IDS, DAMAGE_SHAPES, FIRE_IDS, FIRE_SHAPES, ROWOP_CASES, ROWOP_IDS, damaged, fire_batch, fire_legs, legs,
+                          masks_for, rowop_batch, three_of_8, truncated)  # noqa: F401  (fixtures)
+from fixtures import chunks_per_group, no_fast, sentinel, sz  # noqa: F401  (fixtures)
+from rowdata import FAST_SHAPES, PARITY_FAST, gen_data, lowdim, make_batch, masked_parity_cases as parity_cases, parity_masks, rows_for, short_batch
+from streams import OLD, options
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +28,6 @@ PAD = 1024                      # entries behind every output that must keep the
 MODES = ((sgm.RUNS, "runs"), (sgm.SPLITS, "splits"))
 OPS = {"min": sgm.MIN, "max": sgm.MAX, "sum": sgm.SUM, "rows": sgm.ROWS, "start": sgm.START}
 WIDTH = {"sum": 8, "rows": 4, "start": 8}
-
-
-def sentinel(nbytes, byte):
-    return int.from_bytes(bytes([byte]) * nbytes, "little")
 
 
 def codec_id(codec):
@@ -348,7 +343,6 @@ def assert_python(got, want, esz, ops, msg):
 def test_segment_rows_python(sz, oracle):
     """segment_rows, segments_where (with and without zones) and sessions against the model of the batch taken as one chunk, on 16 chunks"""
     import torch
-    from test_gpu_filter import bound_sets
     codec, esz, D, chunk_len, n = "xff", 2, 8, 8 * 104, 16
     R = chunk_len // D
     rng = np.random.default_rng(16)

@@ -1,8 +1,6 @@
 """GPU tests (-m gpu) of select rows (sprintz_mi355x_select_rows, ChunkedCodec.select_rows / where): stream compaction fused into the
 decode, in decode_fast.h and decode_kernel.h.  The expected value is always tests/select_model.py applied to the ORIGINAL input --
 decode is lossless and pinned elsewhere.  Every batch ends in a short last chunk of whole rows."""
-import ctypes as C
-import os
 import zlib
 
 import numpy as np
@@ -12,112 +10,13 @@ import filter_model as fm
 import select_model as sm
 from dispatch import ran
 from harness import DTYPES
-from test_gpu_filter import bound_sets, existing_rows
-from test_gpu_query_windows import chunk_len_for, gen_data, make_batch, parity_cases
+from fixtures import no_fast, sentinels, sz  # noqa: F401  (fixtures)
+from rowdata import bound_sets, chunk_len_for, existing_rows, gen_data, make_batch, parity_cases, parity_masks, short_batch
+from rowop_runners import check_select, run_select
 
 pytestmark = pytest.mark.gpu
 
-PAD = 4096                      # elements behind both outputs that must keep the sentinel
 SENTINELS = (0x5A, 0xA5)        # (the byte, repeated over the element / the id)
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
-
-
-@pytest.fixture
-def no_fast():
-    """set_option(OPT_NO_FAST) for the duration of a test, restored afterwards"""
-    from sprintz_amd import _lib
-
-    def setter(v):
-        _lib.check(_lib.set_option(_lib.OPT_NO_FAST, int(v)))
-    yield setter
-    _lib.set_option(_lib.OPT_NO_FAST, 1 if os.environ.get("SPRINTZ_MI355X_NO_FAST") is not None else 0)
-
-
-def short_batch(nchunks, chunk_len, D):
-    """elements of a batch of nchunks chunks whose last one is short by a third of its rows (whole rows)"""
-    R = chunk_len // D
-    return nchunks * chunk_len - max(1, R // 3) * D
-
-
-def sentinels(esz, byte):
-    elem = int.from_bytes(bytes([byte]) * esz, "little")
-    ident = int.from_bytes(bytes([byte]) * 8, "little", signed=True)
-    return elem, ident
-
-
-def run_select(batch, codec, esz, D, chunk_len, mask, bases, capacity, out_rows, byte=0x5A, ids=True, general=False, shift=0):
-    """the C entry point on sentinel-filled outputs of out_rows rows + PAD elements (the rows start `shift` elements into their buffer)
-    -> (rows [out_rows * D + PAD] numpy, ids [out_rows + PAD] numpy int64, rets [nchunks] numpy)"""
-    import torch
-    from sprintz_amd import _lib
-    n = batch.nchunks
-    elem, ident = sentinels(esz, byte)
-    ne = out_rows * D + PAD
-    rows_t = torch.from_numpy(np.full(ne + shift, elem, DTYPES[esz]).view(np.int8 if esz == 1 else np.int16)).cuda()
-    ids_t = torch.full((out_rows + PAD,), ident, dtype=torch.int64, device="cuda")
-    rets_t = torch.full((n + 1,), -77, dtype=torch.int64, device="cuda")
-    mask_t = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).cuda()
-    bases_t = torch.from_numpy(np.ascontiguousarray(bases, np.int64)).cuda()
-    _lib.check(_lib.select_rows(_lib.CODEC_DELTA if codec == "delta" else _lib.CODEC_XFF, esz, batch.data.data_ptr(), batch.offsets.data_ptr(),
-                                n, chunk_len, D, mask_t.data_ptr(), bases_t.data_ptr(), int(capacity), _lib.QUERY_GENERAL_LAYOUT if general else 0,
-                                rows_t.data_ptr() + shift * esz, ids_t.data_ptr() if ids else None, rets_t.data_ptr(),
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    r = rets_t.cpu().numpy()
-    assert r[n] == -77, "rets written past nchunks"
-    got = rows_t.cpu().numpy().view(DTYPES[esz])
-    assert np.all(got[:shift] == elem), "written in front of d_out"
-    return got[shift:], ids_t.cpu().numpy(), r[:n]
-
-
-def check_select(x, batch, codec, esz, D, chunk_len, mask, bases, capacity, out_rows, msg, byte=0x5A, ids=True, general=False, shift=0):
-    """rows, ids, padding and rets against the model"""
-    elem, ident = sentinels(esz, byte)
-    want_rows, want_ids = sm.select_rows(x, chunk_len, D, mask, bases, capacity, out_rows=out_rows, sentinel=elem, id_sentinel=ident)
-    rows, got_ids, rets = run_select(batch, codec, esz, D, chunk_len, mask, bases, capacity, out_rows, byte, ids, general, shift)
-    assert np.array_equal(rets, fm.chunk_counts(x.size, chunk_len)), ("rets",) + msg
-    assert np.all(rows[out_rows * D:] == elem) and np.all(got_ids[out_rows:] == ident), ("padding",) + msg
-    assert np.array_equal(rows[:out_rows * D].reshape(out_rows, D), want_rows), ("rows",) + msg
-    if ids:
-        assert np.array_equal(got_ids[:out_rows], want_ids), ("ids",) + msg
-    else:
-        assert np.all(got_ids == ident), ("a NULL d_ids was written",) + msg
-    return want_rows, want_ids
-
-
-def parity_masks(rng, x, chunk_len, esz, D):
-    """-> [(name, mask)] of the module docstring's list"""
-    R, MB = fm.geometry(chunk_len, D)
-    lens = fm.chunk_counts(x.size, chunk_len)
-    nchunks = len(lens)
-    sets, _ = bound_sets(x, chunk_len, esz, D)
-    masks = []
-    for name, mode, lo, hi, _ in sets[:3]:                 # band, alarm, all rows
-        masks.append((name, fm.filter_rows(x, chunk_len, D, lo, hi, mode)[0]))
-    masks.append(("no row", np.zeros((nchunks, MB), np.uint8)))
-    for name, p in (("p=1/2", 0.5), ("p=1/64", 1.0 / 64)):
-        masks.append((name, np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")))
-
-    def from_rows(pick):
-        bits = np.zeros((nchunks, MB * 8), np.uint8)
-        for c, ne in enumerate(lens):
-            bits[c, pick(ne // D)] = 1
-        return np.packbits(bits, axis=1, bitorder="little")
-    masks.append(("row 0", from_rows(lambda have: [0])))
-    masks.append(("last row", from_rows(lambda have: [have - 1])))
-    masks.append(("tail rows", from_rows(lambda have: np.arange(have // 16 * 16 if have % 16 else have - min(have, 16), have))))
-    alt = np.zeros((nchunks, MB), np.uint8)
-    alt[:, 1::2] = 0xFF
-    masks.append(("alternating bytes", alt))
-    masks.append(("every bit", np.full((nchunks, MB), 0xFF, np.uint8)))
-    return masks
 
 
 @pytest.mark.parametrize("codec,esz,D,shape,data,general", [c for c in parity_cases() if chunk_len_for(c[3], c[2]) % c[2] == 0])
@@ -342,7 +241,7 @@ def test_select_rows_python(sz, oracle):
 def test_where_bench_size(sz):
     """the bench's headline input at full size, once: where() against torch's boolean index of the device-decoded batch"""
     import torch
-    from test_gpu_bench_data import bench_input
+    from rowdata import bench_input
     (codec, esz, D, chunk_len, nchunks), x = bench_input("cfg2", "cuda:0")
     cd = sz.ChunkedCodec(codec, esz, D, chunk_len, device="cuda:0")
     batch = cd.compress(x)

@@ -6,18 +6,11 @@ import pytest
 
 from dispatch import ran
 from harness import DTYPES
+from fixtures import sz  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 NAMES = {0: "delta", 1: "doubledelta", 2: "xff"}
-
-
-@pytest.fixture(scope="module")
-def sz():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import sprintz_amd
-    return sprintz_amd
 
 
 def chain_takes(esz, ndims, n):

@@ -16,8 +16,9 @@ import linear_model as lm
 import zone_model as zm
 from dispatch import DECODERS, ran
 from harness import DTYPES
-from test_gpu_filter import no_fast, sz  # noqa: F401  (fixtures)
-from test_gpu_query_windows import gen_data, make_batch
+from fixtures import no_fast, sz  # noqa: F401  (fixtures)
+from rowdata import gen_data, make_batch
+from rowop_runners import assert_zone_map, host
 
 pytestmark = pytest.mark.gpu
 
@@ -50,13 +51,6 @@ def dev(a, dtype=None):
     return t if dtype is None else t.to(dtype)
 
 
-def host(t):
-    import torch
-    if t.dtype == torch.uint16:
-        return t.view(torch.int16).cpu().numpy().view(np.uint16)
-    return t.cpu().numpy()
-
-
 def box_bounds(esz, D, mode):
     """the band on every column under ALL; under ANY on the first and the last column, the others never matching"""
     top = (1 << (8 * esz)) - 1
@@ -66,13 +60,6 @@ def box_bounds(esz, D, mode):
     for d in (0, D - 1):
         lo[d], hi[d] = BAND
     return lo, hi
-
-
-def assert_zone_map(z, x, chunk_len, D, esz, msg):
-    zmin, zmax, zlen = zm.zone_map(x, chunk_len, D, esz)
-    assert np.array_equal(host(z.len), zlen), ("zlen",) + msg
-    assert np.array_equal(host(z.min), zmin) and np.array_equal(host(z.max), zmax), ("zone",) + msg
-    return zmin, zmax, zlen
 
 
 def raw_zoned(sz, cd, batch, codec, z, pred, outs="both", want_rets=True, sentinel=0x5A):

@@ -1,13 +1,10 @@
 """CPU tests of group-by rows (sprintz_mi355x_groupby_rows): the symbol and its binding are there, every validation return comes before
 the device is touched and names the operation, the numpy model the GPU tier compares with (tests/groupby_model.py) equals brute force and
 satisfies the identities that tie it to the column sums and to the histogram of the key column, and the planner (sprintz_amd/csrc/plan.h,
-built with g++: tests/binned_plan_probe.cpp) sends the mode to decode_fast.h where the windowed query goes AND the table fits the
+built with g++: tests/plan_probe.cpp) sends the mode to decode_fast.h where the windowed query goes AND the table fits the
 launch's LDS next to the groups' carves, to the generic kernel otherwise -- never to decode_uni.h -- and gives a workgroup its 32-bit
 table only where no sum can wrap."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,23 +12,17 @@ import pytest
 import filter_model as fm
 import groupby_model as gm
 import histogram_model as hm
+import planner
+from fixtures import buf_fixture, lib, random_mask, refusals  # noqa: F401  (fixtures)
+from planner import QUERY
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-Q_WINDOW, Q_AGGREGATE, Q_HISTOGRAM, Q_GROUPBY = 3, 7, 8, 10
+Q_WINDOW, Q_AGGREGATE, Q_HISTOGRAM, Q_GROUPBY = QUERY["window"], QUERY["aggregate"], QUERY["histogram"], QUERY["groupby"]
 CAP = 16384
 FAST_LDS_BUDGET = 80 * 1024           # geom.h: kHistFastLdsBudget
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 65536)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(65536)
 
 
 def test_symbol_and_binding(lib):
@@ -62,13 +53,7 @@ def test_validation_comes_before_the_device(lib, buf):
         return lib.groupby_rows(a["codec"], a["esz"], a["comp"], a["offs"], a["n"], a["cl"], a["D"], a["mask"], a["key"], a["key_lo"], a["shift"],
                                 a["nbins"], a["H"], a["ops"], a["flags"], a["count"], a["sum"], a["rets"], None)
 
-    def invalid(**kw):
-        assert call(**kw) == E.E_INVALID, kw
-        assert "groupby_rows" in lib.last_error(), (kw, lib.last_error())
-
-    def unsupported(**kw):
-        assert call(**kw) == E.E_UNSUPPORTED, kw
-        assert "groupby_rows" in lib.last_error(), (kw, lib.last_error())
+    invalid, unsupported = refusals(lib, call, "groupby_rows")
 
     invalid(cl=5121)                                                             # chunk_len % ndims != 0
     invalid(D=7)
@@ -149,10 +134,6 @@ SHAPES = [
 ]
 
 
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
-
-
 def binnings(rng, esz):
     """(shift, nbins, key_lo): the bins that cover the range, a number of bins that is no power of two, a random key_lo with wrap-around
     under fewer bins than the range, full resolution around a random value, one bin"""
@@ -203,11 +184,8 @@ def test_default_shift():
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("groupby_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "binned_plan_probe.cpp"), "-o", str(exe)])
+def plan():
+    planner.available()
 
     def ask(**fields):
         q = dict(codec=1, nchunks=4096, q=Q_GROUPBY)
@@ -215,9 +193,7 @@ def plan(tmp_path_factory):
         nbins = q.pop("nbins", 256)
         if q["q"] == Q_GROUPBY:                  # the table: nbins x (D + 1) entries, a row adds at most 2^W - 1 to one
             q.update(table_entries=nbins * (q["D"] + 1), table_row_max=(1 << (8 * q["esz"])) - 1)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
-        return out[0], {k: int(v) for k, v in (t.split("=") for t in out[1:])}
+        return planner.split(planner.ask("decode", **q))
     return ask
 
 

@@ -1,35 +1,26 @@
 """CPU tests of histogram rows (sprintz_mi355x_histogram_rows): the symbol and its binding are there, every validation return comes
 before the device is touched and names the operation, the numpy model the GPU tier compares with (tests/histogram_model.py) equals
-np.bincount / np.sort brute force, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/binned_plan_probe.cpp) sends the
+np.bincount / np.sort brute force, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp) sends the
 mode to decode_fast.h where the windowed query goes AND the table fits the launch's LDS next to the groups' carves, to the generic
 kernel otherwise -- never to decode_uni.h."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import filter_model as fm
 import histogram_model as hm
+import planner
+from fixtures import buf_fixture, lib, random_mask, refusals  # noqa: F401  (fixtures)
+from planner import QUERY
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-Q_WINDOW, Q_AGGREGATE, Q_HISTOGRAM = 3, 7, 8
+Q_WINDOW, Q_AGGREGATE, Q_HISTOGRAM = QUERY["window"], QUERY["aggregate"], QUERY["histogram"]
 CAP = 16384
 FAST_LDS_BUDGET = 80 * 1024           # geom.h: kHistFastLdsBudget
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 16384)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(16384)
 
 
 def test_symbol_and_binding(lib):
@@ -56,13 +47,7 @@ def test_validation_comes_before_the_device(lib, buf):
         return lib.histogram_rows(a["codec"], a["esz"], a["comp"], a["offs"], a["n"], a["cl"], a["D"], a["mask"], a["lo"], a["shift"],
                                   a["nbins"], a["H"], a["flags"], a["hist"], a["rets"], None)
 
-    def invalid(**kw):
-        assert call(**kw) == E.E_INVALID, kw
-        assert "histogram_rows" in lib.last_error(), (kw, lib.last_error())
-
-    def unsupported(**kw):
-        assert call(**kw) == E.E_UNSUPPORTED, kw
-        assert "histogram_rows" in lib.last_error(), (kw, lib.last_error())
+    invalid, unsupported = refusals(lib, call, "histogram_rows")
 
     invalid(cl=5121)                                                             # chunk_len % ndims != 0
     invalid(D=7)
@@ -127,10 +112,6 @@ SHAPES = [
 ]
 
 
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
-
-
 def binnings(rng, esz, D):
     """(shift, nbins, lo): full resolution / the default shift, a number of bins that is no power of two, a random lo with wrap-around, one bin"""
     W = 8 * esz
@@ -192,11 +173,8 @@ def test_quantile_model_equals_sort(esz, D, chunk_len, n):
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("histogram_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "binned_plan_probe.cpp"), "-o", str(exe)])
+def plan():
+    planner.available()
 
     def ask(**fields):
         q = dict(codec=1, nchunks=4096, q=Q_HISTOGRAM)
@@ -204,9 +182,7 @@ def plan(tmp_path_factory):
         nbins = q.pop("nbins", 256)
         if q["q"] == Q_HISTOGRAM:                # the table: D x nbins counters, a row adds at most 1 to one
             q.update(table_entries=q["D"] * nbins, table_row_max=1)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
-        return out[0], {k: int(v) for k, v in (t.split("=") for t in out[1:])}
+        return planner.split(planner.ask("decode", **q))
     return ask
 
 

@@ -11,8 +11,7 @@ import pytest
 
 import huf_drive as hd
 from harness import gen_fuzz, gen_walk
-
-DECODE_CAP = 300_000             # symbols the Python bit reader may decode per test
+from codec_helpers import check_case, decode_sample
 
 
 def nibbles(lens):
@@ -139,64 +138,6 @@ def oracle_container(oracle, bname):
     dense, offs, sizes = hd.layout(b["chunks"], b["align"], b["shift"])
     huf, ho, tables = oracle.huf_compress(dense, offs, sizes)
     return huf, ho, tables
-
-
-def unpack(table):
-    table = np.asarray(table, np.uint8)
-    lens = np.zeros(256, np.uint8)
-    lens[0::2], lens[1::2] = table & 15, table >> 4
-    return lens
-
-
-def check_case(case, chunk, huf, ho, tables, who="oracle"):
-    """the record of a record case is on the side of its edge that the case claims: read from the record's own header, the fourth
-    sub-stream's size (which no header field carries) from the drive's arithmetic and the record's length"""
-    c = case["chunk"]
-    rec = huf[int(ho[c]):int(ho[c + 1])]
-    n, stored, sz = hd.record_header(rec)
-    assert n == len(chunk), (who, case)
-    if "n" in case:
-        assert n == case["n"], (who, case)
-        return
-    assert stored == case["stored"], (who, case, n, stored, sz)
-    own_stored, own = hd.record_sizes(chunk, unpack(tables[128 * (c // hd.SEG):128 * (c // hd.SEG) + 128]))
-    assert own_stored == stored, (who, case)
-    if "enc_minus_n" in case:
-        assert sum(own) - n == case["enc_minus_n"], (who, case, own)
-    if "sub" in case:
-        assert own[case["sub"][0]] == case["sub"][1], (who, case, own)
-    if stored:
-        assert len(rec) == (4 + n + 3) & ~3 and bytes(rec[4:4 + n]) == chunk.tobytes(), (who, case)
-    else:
-        assert sz == own[:3] and len(rec) == (12 + sum(own) + 3) & ~3, (who, case, sz, own, len(rec))
-        if case.get("sub", (0, 0))[0] == 3:
-            assert own[3] >= 0xFFFF and max(sz) < 0xFFFF                       # only the sub-stream without a size field is long
-
-
-def decode_sample(b, huf, ho, tables, who="oracle"):
-    """decode_record of every edge record and of one record per segment (its largest chunk of at most 6 000 bytes; the largest of all
-    where it has none), against the chunk; the long records only at the head of each of their sub-streams.  -> symbols decoded"""
-    picks = [(c["chunk"], c.get("partial", False)) for c in b["cases"]]
-    for sname, first in b["segments"]:
-        sizes = [len(ch) for ch in b["chunks"][first:first + hd.SEG]]
-        ok = [k for k, s in enumerate(sizes) if 0 < s <= 6000] or [int(np.argmax(sizes))]
-        k = max(ok, key=lambda k: sizes[k])
-        picks.append((first + k, sizes[k] > 6000))
-    done = 0
-    for c, partial in picks:
-        chunk = b["chunks"][c]
-        rec = huf[int(ho[c]):int(ho[c + 1])]
-        tab = tables[128 * (c // hd.SEG):128 * (c // hd.SEG) + 128]
-        if partial:
-            got, mask = hd.decode_record(rec, tab, per_stream=1500)
-            got = np.frombuffer(got, np.uint8)
-            assert np.array_equal(got[mask], chunk[mask]), (who, c)
-            done += int(mask.sum()) if not hd.record_header(rec)[1] else 0
-        else:
-            assert hd.decode_record(rec, tab) == chunk.tobytes(), (who, c)
-            done += len(chunk)
-    assert done <= DECODE_CAP, done
-    return done
 
 
 @pytest.mark.parametrize("bname", list(hd.batches()))

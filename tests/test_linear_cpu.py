@@ -1,33 +1,24 @@
 """CPU tests of linear filter rows (sprintz_mi355x_filter_linear): the two symbols and their bindings are there, every validation return
 comes before the device is touched, the scratch size behaves, the numpy model the GPU tier compares with (tests/linear_model.py) equals
 brute force, rowops.linear_terms takes every form of its arguments and holds the exactness bound, and the planner
-(sprintz_amd/csrc/plan.h, built with g++: tests/linear_plan_probe.cpp) sends the mode to decode_fast.h or to the generic kernel, never
+(sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp) sends the mode to decode_fast.h or to the generic kernel, never
 to decode_uni.h."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import filter_model as fm
 import linear_model as lm
+from fixtures import buf_fixture, lib, refusals  # noqa: F401  (fixtures)
+from planner import QUERY, plan_fixture, split
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-Q_LINEAR = 12
+Q_LINEAR = QUERY["linear"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 65536)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(65536)
 
 
 def test_symbols_and_bindings(lib):
@@ -59,12 +50,7 @@ def test_validation_comes_before_the_device(lib, buf):
         return lib.filter_linear(a["codec"], a["esz"], a["comp"], a["offs"], a["n"], a["cl"], a["D"], a["w"], a["u"], a["bias"], a["lo"], a["hi"],
                                  a["flags"], a["tmp"], a["mask"], a["counts"], a["rets"], None)
 
-    def invalid(**kw):
-        assert call(**kw) == E.E_INVALID, kw
-        assert lib.last_error(), kw
-
-    def unsupported(**kw):
-        assert call(**kw) == E.E_UNSUPPORTED, kw
+    invalid, unsupported = refusals(lib, call)
 
     invalid(flags=2)                                                             # unknown flag (GENERAL_LAYOUT = 1 is the only one)
     invalid(flags=3)
@@ -213,20 +199,7 @@ def test_linear_terms():
         rowops.linear_terms(torch.tensor([1.0, 2.0]), None, 0, None, None, 2, 1, dev)
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("linear_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "linear_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        q = dict(codec=1, nchunks=4096)
-        q.update(fields)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
-        return out[0], {k: int(v) for k, v in (t.split("=") for t in out[1:])}
-    return ask
+plan = plan_fixture(shape=split, codec=1, nchunks=4096, q=Q_LINEAR)
 
 
 def test_plan(plan):

@@ -1,12 +1,9 @@
 """CPU tests of moments rows (sprintz_mi355x_moments_rows): the symbol and its binding are there, every validation return comes before
 the device is touched and names the operation, the numpy model the GPU tier compares with (tests/moments_model.py) equals a
 one-row-at-a-time brute force in Python ints and the aggregate model's sum and count, its exact rationals are what their definitions
-say, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/select_plan_probe.cpp, which takes any mode) sends the mode where
+say, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp) sends the mode where
 the windowed query goes -- except that decode_uni.h never gets it."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -15,21 +12,14 @@ import pytest
 import aggregate_model as am
 import filter_model as fm
 import moments_model as mm
+from fixtures import buf_fixture, lib, random_mask, refusals  # noqa: F401  (fixtures)
+from planner import QUERY, family, plan_fixture
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-Q_WINDOW, Q_AGGREGATE, Q_MOMENTS = 3, 7, 9
+Q_WINDOW, Q_AGGREGATE, Q_MOMENTS = QUERY["window"], QUERY["aggregate"], QUERY["moments"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 16384)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(16384)
 
 
 def test_symbol_and_binding(lib):
@@ -58,13 +48,7 @@ def test_validation_comes_before_the_device(lib, buf):
         return lib.moments_rows(a["codec"], a["esz"], a["comp"], a["offs"], a["n"], a["cl"], a["D"], a["mask"], a["W"], a["ops"], a["ref"],
                                 a["flags"], a["cnt"], a["sm"], a["sq"], a["cr"], a["rets"], None)
 
-    def invalid(**kw):
-        assert call(**kw) == E.E_INVALID, kw
-        assert "moments_rows" in lib.last_error(), (kw, lib.last_error())
-
-    def unsupported(**kw):
-        assert call(**kw) == E.E_UNSUPPORTED, kw
-        assert "moments_rows" in lib.last_error(), (kw, lib.last_error())
+    invalid, unsupported = refusals(lib, call, "moments_rows")
 
     invalid(cl=5121)                                                             # chunk_len % ndims != 0
     invalid(D=7)
@@ -122,10 +106,6 @@ SHAPES = [
     (2, 8, 8 * 64, 8 * 64 * 3),
     (1, 7, 7 * 5, 7 * 5 * 6 + 7),
 ]
-
-
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
 
 
 def windows_for(R):
@@ -199,19 +179,7 @@ def test_exact_rationals():
     assert const["var"] == 0 and const["corr2"] is None and np.isnan(mm.corr_float(const))
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("moments_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "select_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        q = dict(codec=1, nchunks=4096, q=Q_MOMENTS)
-        q.update(fields)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        return subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.strip()
-    return ask
+plan = plan_fixture(shape=family, codec=1, nchunks=4096, q=Q_MOMENTS)
 
 
 def test_planner_edges(plan):

@@ -3,50 +3,13 @@ against golden containers minted from the compiled reference, and -- where oracl
 compiled reference itself on a wider random set.  Bit-exact on every byte the reference writes (it leaves header
 padding unwritten; those bytes are 0 in the fixtures and in our output)."""
 import ctypes as C
-import json
 import os
 
 import numpy as np
 import pytest
 
-from harness import ORACLE_SO, REF_SO, gen_fuzz, gen_walk
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def golden_online():
-    gdir = os.path.join(ROOT, "tests", "golden")
-    with open(os.path.join(gdir, "golden_online_v1.json")) as f:
-        manifest = json.load(f)["cases"]
-    return manifest, np.load(os.path.join(gdir, "golden_online_v1.npz"))
-
-
-@pytest.fixture(scope="module")
-def orc(oracle):
-    lib = C.CDLL(ORACLE_SO)
-    lib.online_oracle_pack.restype = C.c_int64
-    lib.online_oracle_pack.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_size_t)]
-    lib.online_oracle_unpack.restype = C.c_int64
-    lib.online_oracle_unpack.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    lib.online_oracle_bound.restype = C.c_size_t
-    lib.online_oracle_bound.argtypes = [C.c_int, C.c_uint32]
-    return lib
-
-
-def oracle_pack(lib, kind, x):
-    x = np.ascontiguousarray(x, dtype=np.uint16)
-    out = np.zeros(lib.online_oracle_bound(kind, x.size), np.uint8)
-    nb = C.c_size_t(0)
-    ret = lib.online_oracle_pack(kind, x.ctypes.data, x.size, out.ctypes.data, C.byref(nb))
-    return out[: 2 * int(ret)].copy(), int(ret), int(nb.value)
-
-
-def oracle_unpack(lib, kind, cont, n):
-    buf = np.concatenate([np.ascontiguousarray(cont, dtype=np.uint8), np.zeros(64, np.uint8)])
-    out = np.zeros(n + 16, np.uint16)
-    ret = lib.online_oracle_unpack(kind, buf.ctypes.data, out.ctypes.data)
-    return out[:n].copy(), int(ret)
+from harness import REF_SO, gen_fuzz, gen_walk
+from codec_helpers import golden_online, oracle_pack, oracle_unpack, orc  # noqa: F401  (fixtures)
 
 
 def test_manifest_covers_every_coder_and_edge(golden_online):

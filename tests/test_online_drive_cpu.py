@@ -16,7 +16,7 @@ import pytest
 
 import online_drive as od
 from harness import REF_SO
-from test_online_cpu import oracle_pack, oracle_unpack, orc  # noqa: F401  (fixtures)
+from codec_helpers import oracle_pack, oracle_unpack, orc  # noqa: F401  (fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL_PAIRS = {(0, 0), (0, 1), (1, 0), (1, 1)}

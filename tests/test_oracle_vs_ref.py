@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from harness import (REF_TEST_SIZES, gen_fuzz, gen_patterns, gen_sparse, gen_walk)
-from test_online_cpu import oracle_pack, orc  # noqa: F401  (fixtures)
+from codec_helpers import oracle_pack, orc  # noqa: F401  (fixtures)
 
 
 def _check(oracle, reference, codec, data, ndims):

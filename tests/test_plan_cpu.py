@@ -10,44 +10,16 @@ answers one query per line.
    exactly one of plan and error, the same answer twice; with no_fast every shape of at most 512 columns on the generic kernels; a
    host-call input is dec_lat / enc_lat exactly when the same single chunk is without the flag (what the ticket path relies on);
    dec_fast's lane group holds the columns and is more than half full; dynamic LDS at most 160 KB and a grid in 1 .. 2^31 - 1."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
+import planner
 from dispatch_cases import CASES, ENC, GATHER_EDGES, OPTION_DEFAULTS
+from planner import CODEC, bound, probe  # noqa: F401  (fixtures)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CODEC = {"delta": 0, "xff": 1}
-
-
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(*queries):
-        """queries: (op, {field: value}) -> one answer dict per query"""
-        text = "".join(op + "".join(f" {k}={int(v)}" for k, v in fields.items()) + "\n" for op, fields in queries)
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
-        assert len(out) == len(queries), out
-        return [dict(tok.split("=", 1) for tok in line.split(" ") if "=" in tok) if not line.startswith("error=") else dict(error=line) for line in out]
-    ask.exe = str(exe)
-    return ask
 
 
 def knobs(lat=OPTION_DEFAULTS["lat"], blk_chunks=OPTION_DEFAULTS["blk_chunks"], mask=OPTION_DEFAULTS["mask"], pair=OPTION_DEFAULTS["pair"]):
     return dict(lat_chunks=lat, blk_chunks=blk_chunks, blk_kernels=mask, enc_pair=pair)
-
-
-def bound(esz, chunk_len, D):
-    """sprintz_mi355x_compress_bound: the slot stride ChunkedCodec uses"""
-    hdr = (2 * D * (3 if esz == 1 else 4) + 7) // 8
-    b = 8 + (chunk_len // (16 * D) + 1) * (hdr + 3) + chunk_len * esz + 32
-    return (b + 127) & ~127
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
@@ -63,7 +35,7 @@ def test_the_gpu_edge_table_replayed(probe, case):
         want_dense, = [k for k in enc if k.startswith("dense_")]
         if kw.get("src_shift") or kw.get("align", 16) != 16:        # the slot path followed by compact
             got, = probe(("encode", dict(shape, src_lo=kw.get("src_shift", 0) % 16)))
-            assert [got.get("family")] == want_enc and got.get("fused") == "0" and want_dense == "dense_compact", (tag, got)
+            assert [got.get("family")] == want_enc and got.get("fused") == 0 and want_dense == "dense_compact", (tag, got)
         else:                                                       # ChunkedCodec.compress: compress_batch_dense
             got, = probe(("dense", shape))
             assert got.get("family") == want_dense and [got.get("enc")] == (want_enc or ["none"]), (tag, got)
@@ -100,9 +72,14 @@ SWEEP_KNOWN = ()
 
 
 def test_properties_over_the_sweep(probe):
-    out = subprocess.run([probe.exe], input="sweep\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    out = planner.run("sweep\n")
     shapes = int(out[-1].split("shapes=")[1].split()[0])
     assert shapes == 2 * 516 * 5 * 6 * 2
     violations = [line for line in out[:-1] if not any(known in line for known in SWEEP_KNOWN)]
     assert len(out) - 1 - len(violations) <= shapes // 100
     assert not violations, (len(violations), violations[:20])
+
+
+def test_the_mode_numbers_are_geom_hs(probe):
+    """planner.QUERY, the one table of mode numbers the tests use, against the kQuery* constants themselves"""
+    assert {name.lower().replace("_", ""): v for name, v in planner.QUERY.items()} == {name.lower(): v for name, v in planner.modes().items()}

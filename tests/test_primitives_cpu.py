@@ -6,39 +6,7 @@ import numpy as np
 import pytest
 
 import kat
-
-# (width, columns, low-dim layout?)
-SHAPES = [(8, 8, False), (8, 5, False), (8, 1, True), (8, 3, True), (8, 4, True),
-          (16, 8, False), (16, 3, False), (16, 1, True), (16, 2, True)]
-
-
-def check_kat_streams(streams, w, ndims, lowdim):
-    """streams[e]: np.uint8 stream of chunk e (kat.kat_chunks); every header field, every payload byte, the run and the tail"""
-    fields, nb, z = kat.expected_fields(w, ndims, lowdim)
-    err = kat.kat_errors(w, ndims)
-    hb = 3 if w == 8 else 4
-    hdr = (2 * ndims * hb + 7) // 8
-    esz = w // 8
-    nblocks = kat.kat_rows(ndims) // 8
-    # the delta codecs close a run when fewer than two blocks would remain (`<`, sprintz_delta_rle.cpp:226): blocks 1 .. nblocks - 3 are
-    # the run, the last two blocks travel verbatim
-    run, tail_rows = (1, 0) if nblocks == 2 else (nblocks - 3, 16)
-    for e in range(1 << w):
-        s = streams[e]
-        if not fields[e].any():
-            continue                                                 # (chunk 0 of a one-column shape: all zero, nothing of block 0 to read)
-        assert int.from_bytes(bytes(s[0:4]), "little") == 1, (e, "one group")
-        assert int(s[4]) | int(s[5]) << 8 == tail_rows * ndims and int(s[6]) | int(s[7]) << 8 == ndims, e
-        got = kat.read_fields(s, w, ndims)
-        assert np.array_equal(got[:ndims], fields[e]), (w, ndims, lowdim, e, got[:ndims], fields[e])
-        assert not got[ndims:].any(), (e, "slot 1 is a run")
-        payload = kat.expected_block_payload(z[e], nb[e], w, lowdim)
-        at = 8 + hdr
-        assert bytes(s[at:at + len(payload)]) == payload, (w, ndims, lowdim, e)
-        at += len(payload)
-        assert s[at] == run, (e, s[at], run)
-        tail = np.tile(err[e], tail_rows).astype(np.uint8 if w == 8 else np.uint16).tobytes()
-        assert bytes(s[at + 1:]) == tail, (w, ndims, lowdim, e)
+from codec_helpers import KAT_SHAPES as SHAPES, check_kat_streams
 
 
 @pytest.mark.parametrize("w,ndims,lowdim", SHAPES)

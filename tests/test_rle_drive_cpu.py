@@ -167,44 +167,37 @@ def test_golden_streams_are_the_oracles(oracle):
 
 # ------------------------------------------------------------------ the GPU tier's kernel-family literals, replayed through the planner
 
-from test_plan_cpu import bound, probe  # noqa: E402,F401  (probe: the fixture that builds tests/plan_probe.cpp)
+from drive_tables import CAP_CASES, CASES, LAT_SINGLE, NB, NCHUNKS as ROWOP_NCHUNKS, ROWOP_SHAPES, family_of  # noqa: E402
+from planner import QUERY, plan_shape, probe  # noqa: E402,F401  (probe: a fixture)
+from streams import DEF, OLD  # noqa: E402
 
-CODEC = {"delta": 0, "xff": 1}
-QUERY = {"window": 3, "filter": 5, "select": 6, "aggregate": 7}          # csrc/geom.h: kQueryWindow, kQueryFilter, kQuerySelect, kQueryAggregate
-
-
-def plan_shape(codec, w, D, chunk_len, nchunks, lat=2048, blk_chunks=2049, mask=9, pair=1, no_fast=0, split=1):
-    """the planner's inputs for a ChunkedCodec call under test_gpu_fire_extremes.options(...)"""
-    esz = w // 8
-    return dict(codec=CODEC[codec], esz=esz, D=D, chunk_len=chunk_len, nchunks=nchunks, total_len=nchunks * chunk_len, slot_stride=bound(esz, chunk_len, D),
-                lat_chunks=lat, blk_chunks=blk_chunks, blk_kernels=mask, enc_pair=pair, no_fast=no_fast, split_lanes=split)
+ROW_OPS = ("window", "filter", "select", "aggregate")
 
 
 def test_the_gpu_tiers_literals_are_the_planners(probe):
     """every kernel family tests/test_gpu_rle_drive.py asserts from the dispatch counters is what csrc/plan.h plans for that shape and
     those options: a literal that is wrong fails here, without a device"""
-    import test_gpu_rle_drive as g
-    for tag, codecs, opts, w, D, nchunks, nblocks, r, enc, dec in g.CASES:
+    for tag, codecs, opts, w, D, nchunks, nblocks, r, enc, dec in CASES:
         for codec in codecs:
             shape = plan_shape(codec, w, D, 8 * nblocks * D + r, nchunks, **opts)
             dense, decode = probe(("dense", shape), ("decode", shape))
-            assert dense.get("enc") == g.family_of(enc)[0] and decode.get("family") == g.family_of(dec)[0], (tag, codec, dense, decode)
-    for w, D, nblocks, r in g.LAT_SINGLE:
+            assert dense.get("enc") == family_of(enc)[0] and decode.get("family") == family_of(dec)[0], (tag, codec, dense, decode)
+    for w, D, nblocks, r in LAT_SINGLE:
         for codec in ("delta", "xff"):
-            shape = plan_shape(codec, w, D, 8 * nblocks * D + r, 1, **g.DEF)
+            shape = plan_shape(codec, w, D, 8 * nblocks * D + r, 1, **DEF)
             dense, decode = probe(("dense", shape), ("decode", shape))
             assert dense.get("enc") == "enc_lat" and decode.get("family") == "dec_lat", (w, D, r, codec, dense, decode)
-    for tag, opts, w, D, enc, dec in g.CAP_CASES:
+    for tag, opts, w, D, enc, dec in CAP_CASES:
         for codec in ("delta", "xff"):
             shape = plan_shape(codec, w, D, 8 * 70002 * D, 3, **opts)
             dense, decode = probe(("dense", shape), ("decode", shape))
             assert dense.get("enc") == enc and decode.get("family") == dec, (tag, codec, dense, decode)
-    for (w, D), want in g.ROWOP_SHAPES.items():
+    for (w, D), want in ROWOP_SHAPES.items():
         for codec in ("delta", "xff"):
             for no_fast in (0, 1):
-                shape = plan_shape(codec, w, D, 8 * g.NB * D, g.NCHUNKS, no_fast=no_fast, **g.OLD)
-                for op, q in QUERY.items():
-                    got, = probe(("decode", dict(shape, q=q)))
+                shape = plan_shape(codec, w, D, 8 * NB * D, ROWOP_NCHUNKS, no_fast=no_fast, **OLD)
+                for op in ROW_OPS:
+                    got, = probe(("decode", dict(shape, q=QUERY[op])))
                     assert got.get("family") == ("dec_generic" if no_fast else want[op]), (w, D, codec, op, no_fast, got)
                 got, = probe(("gather", dict(shape, nranges=64, rows=11)))
                 assert got.get("family") == ("gather_generic" if no_fast else want["gather"]), (w, D, codec, no_fast, got)

@@ -2,10 +2,6 @@
 batches, masks, binnings, predicates and bands of the GPU tier reach the edges they are there for -- a batch that stops reaching one
 fails here and not silently --, each model equals a one-row-at-a-time restatement in Python integers on a small drive batch, and the GPU
 tier's kernel-family literals are what the planner plans, at one and at three chunks a lane group."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -16,22 +12,21 @@ import groupby_model as gbm
 import histogram_model as hm
 import linear_model as lm
 import moments_model as mm
+import planner
 import rle_drive as rd
 import zone_model as zm
-import test_gpu_fire_extremes as fx
-import test_gpu_rle_drive as g
-import test_gpu_rowop_drive as t
-from test_gpu_filter import bound_sets
-from test_plan_cpu import probe  # noqa: F401  (the fixture that builds tests/plan_probe.cpp)
-from test_rle_drive_cpu import plan_shape
+from drive_tables import (CPGS, DAMAGE_SHAPES, FIRE_COL, FIRE_SHAPES, GBY_KEY, GBY_TABLES, LIN_COL, NB, NCHUNKS,
+                          PATCH_CHUNK, PATCH_TOP, PATCH_ZERO, ROWOP_KINDS, ROWOP_SHAPES, WINDOWS, band_bounds, batch_of, fire_change_bounds,
+                          fire_patched, fire_rows, fire_windows, gby_binning, hist_binnings, linear_sets, masks_for, refs_for, three_of_8, zone_band)
+from planner import CODEC, QUERY, plan_shape, probe  # noqa: F401  (fixtures)
+from rowdata import bound_sets
+from streams import OLD, fire_batch_of
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-NCHUNKS, NB = g.NCHUNKS, g.NB
 R = 8 * NB
-SHAPES = list(g.ROWOP_SHAPES)
-KINDS = g.ROWOP_KINDS
+SHAPES = list(ROWOP_SHAPES)
+KINDS = ROWOP_KINDS
 W24 = 24                                               # windows of 3 blocks
-assert KINDS == ("lengths", "start", "alternate", "tails") and g.WINDOWS == (8, W24) and SHAPES == [(16, 8), (8, 32), (16, 12)]
+assert KINDS == ("lengths", "start", "alternate", "tails") and WINDOWS == (8, W24) and SHAPES == [(16, 8), (8, 32), (16, 12)]
 
 
 def runs_of(z):
@@ -41,7 +36,7 @@ def runs_of(z):
 
 
 def batch(codec, w, D, kind):
-    return g.batch_of(codec, w, D, kind, NCHUNKS, NB)
+    return batch_of(codec, w, D, kind, NCHUNKS, NB)
 
 
 def test_runs_against_windows_of_three_blocks():
@@ -68,7 +63,7 @@ def test_the_masks_select_what_they_are_there_for(codec, w, D):
     first_of_run = last_of_run = empty = False
     for kind in KINDS:
         data, chunk_len, zero = batch(codec, w, D, kind)
-        masks = dict(t.masks_for(zero, 21))
+        masks = dict(masks_for(zero, 21))
         out = em.extrema_rows(data, chunk_len, D, masks["outside runs"], W24)
         empty |= bool(np.any((out["count"] == 0) & np.all(out["rows"] == em.NO_ROW, axis=2) & np.all(out["argmin"] == em.NO_ROW, axis=2)))
         ins = em.extrema_rows(data, chunk_len, D, masks["inside runs"], W24)
@@ -90,7 +85,7 @@ def test_a_window_edge_cuts_a_run_at_its_extremum(w, D):
     hit = 0
     for kind in KINDS:
         data, chunk_len, zero = batch("delta", w, D, kind)
-        for name, mask in t.masks_for(zero, 21):
+        for name, mask in masks_for(zero, 21):
             if name not in ("none", "inside runs"):
                 continue
             want = em.extrema_rows(data, chunk_len, D, mask, W24)
@@ -106,7 +101,7 @@ def test_a_window_edge_cuts_a_run_at_its_extremum(w, D):
 def test_start_opens_every_chunk_with_a_run(codec, w, D):
     data, chunk_len, zero = batch(codec, w, D, "start")
     assert zero[:, 0].all()
-    col = t.LIN_COL[(w, D)]
+    col = LIN_COL[(w, D)]
     same = lm.filter_change(data, chunk_len, D, col, 0, 0)
     assert same[0][0, 0] & 1, "row 0 of chunk 0 is its own predecessor: no change"
     if codec == "delta":                                   # a delta chunk opens with zero rows, whatever the chunk in front ended with
@@ -139,7 +134,7 @@ def test_tails_end_in_runs_and_the_seams_have_work(oracle, codec, w, D):
     starts = range(0, NCHUNKS * R, R)
     for kind in KINDS:
         x, _, _ = batch(codec, w, D, kind)
-        for name, wt, u, bias, lo, hi in t.linear_sets(x, D, t.LIN_COL[(w, D)]):
+        for name, wt, u, bias, lo, hi in linear_sets(x, D, LIN_COL[(w, D)]):
             if u is None:
                 continue
             true = lm.filter_linear(x, chunk_len, D, wt, lo, hi, u, bias)[0]
@@ -151,14 +146,14 @@ def test_tails_end_in_runs_and_the_seams_have_work(oracle, codec, w, D):
 
 @pytest.mark.parametrize("w,D", SHAPES)
 def test_the_bins_take_some_runs_and_drop_others(w, D):
-    key = t.GBY_KEY[(w, D)]
+    key = GBY_KEY[(w, D)]
     data, chunk_len, zero = batch("delta", w, D, "lengths")
     v = data.reshape(NCHUNKS, R, D).astype(np.int64)
     moves = (v.max(axis=1) != v.min(axis=1)).sum(axis=0)
     assert key == next(d for d in range(1, D) if moves[d] >= 12) and moves[key] >= 12, moves.tolist()
-    name, lo, shift, nbins, H = t.hist_binnings(w, D)[0]
-    key_lo, kshift, knbins = t.gby_binning(w)
-    assert name == "clip" and t.hist_binnings(w, D)[1][2] > 0
+    name, lo, shift, nbins, H = hist_binnings(w, D)[0]
+    key_lo, kshift, knbins = gby_binning(w)
+    assert name == "clip" and hist_binnings(w, D)[1][2] > 0
     for kind in KINDS:
         data, chunk_len, zero = batch("delta", w, D, kind)
         v = data.reshape(NCHUNKS, R, D).astype(np.int64)
@@ -186,7 +181,7 @@ def test_the_bins_take_some_runs_and_drop_others(w, D):
 def test_every_predicate_splits_the_rows(codec, w, D):
     for kind in KINDS:
         data, chunk_len, zero = batch(codec, w, D, kind)
-        for name, wt, u, bias, lo, hi in t.linear_sets(data, D, t.LIN_COL[(w, D)]):
+        for name, wt, u, bias, lo, hi in linear_sets(data, D, LIN_COL[(w, D)]):
             n = int(lm.filter_linear(data, chunk_len, D, wt, lo, hi, u, bias)[1].sum())
             assert 0 < n < NCHUNKS * R, (kind, name, n)
         if kind == "lengths":                              # the damaged-chunk cases' box filter
@@ -201,13 +196,13 @@ def test_the_zone_band_prunes_and_keeps(codec, w, D):
     every column over the whole range in every chunk and NO box can decide a chunk: there the band keeps all sixteen"""
     for kind in KINDS:
         data, chunk_len, _ = batch(codec, w, D, kind)
-        band = t.zone_band(data, chunk_len, D, w)
+        band = zone_band(data, chunk_len, D, w)
         zone = zm.zone_map(data, chunk_len, D, w // 8)
         if (codec, w) == ("xff", 8):
             span = zone[1].astype(np.int64) - zone[0].astype(np.int64)
             assert band is None and int((span < 254).sum()) == 0 and int((span.min(axis=1) < 255).sum()) <= 1, kind
             band = (0, 1 << (w - 1))
-        (lo, hi), (wt, llo, lhi) = t.band_bounds(band, w, D)
+        (lo, hi), (wt, llo, lhi) = band_bounds(band, w, D)
         cls = zm.classify_box(*zone, lo, hi, fm.ALL, D)
         assert np.array_equal(cls, zm.classify_linear(*zone, wt, 0, llo, lhi, D))
         survivors = int((cls == zm.DECODE).sum())
@@ -216,26 +211,26 @@ def test_the_zone_band_prunes_and_keeps(codec, w, D):
         assert 0 < n < NCHUNKS * R, (kind, n)
 
 
-@pytest.mark.parametrize("w,D", list(t.FIRE_SHAPES))
+@pytest.mark.parametrize("w,D", list(FIRE_SHAPES))
 def test_the_fire_cases_select_and_reach_the_identities(w, D):
-    nchunks = t.FIRE_SHAPES[(w, D)][0]
-    data, chunk_len = fx.batch_of(w, D, nchunks)
-    rows = t.fire_rows(w, D)
-    assert chunk_len == rows * D and t.fire_windows(w, D) == (64, rows) and rows % 64 == 0
+    nchunks = FIRE_SHAPES[(w, D)][0]
+    data, chunk_len = fire_batch_of(w, D, nchunks)
+    rows = fire_rows(w, D)
+    assert chunk_len == rows * D and fire_windows(w, D) == (64, rows) and rows % 64 == 0
     assert (w, D, nchunks, rows) in ((8, 8, 7, 8 * fd.NB8), (16, 1, 5, 8 * fd.NB16))
-    lo, hi = t.fire_change_bounds(data, D)
-    assert 0 < int(lm.filter_change(data, chunk_len, D, t.FIRE_COL, lo, hi)[1].sum()) < nchunks * rows
-    m38 = t.three_of_8(nchunks, rows)
+    lo, hi = fire_change_bounds(data, D)
+    assert 0 < int(lm.filter_change(data, chunk_len, D, FIRE_COL, lo, hi)[1].sum()) < nchunks * rows
+    m38 = three_of_8(nchunks, rows)
     assert int(em.selected(m38, data.size, chunk_len, D).sum()) == 3 * nchunks * rows // 8
     # the edges behind the extrema identities: a selected all-ones value is a minimum with a row, a selected 0 a maximum with a row
     top = (1 << w) - 1
-    px, pmask = t.fire_patched(w, D)
+    px, pmask = fire_patched(w, D)
     assert 0 < int(em.selected(pmask, px.size, chunk_len, D).sum()) < nchunks * rows
     want = em.extrema_rows(px, chunk_len, D, pmask, 64)
-    wt, wz = t.PATCH_TOP // 64, t.PATCH_ZERO // 64
-    assert t.PATCH_CHUNK < nchunks and wt != wz
-    assert np.all(want["min"][t.PATCH_CHUNK, wt] == top) and np.all(want["argmin"][t.PATCH_CHUNK, wt] == t.PATCH_TOP) and want["count"][t.PATCH_CHUNK, wt] == 1
-    assert np.all(want["max"][t.PATCH_CHUNK, wz] == 0) and np.all(want["argmax"][t.PATCH_CHUNK, wz] == t.PATCH_ZERO) and want["count"][t.PATCH_CHUNK, wz] == 1
+    wt, wz = PATCH_TOP // 64, PATCH_ZERO // 64
+    assert PATCH_CHUNK < nchunks and wt != wz
+    assert np.all(want["min"][PATCH_CHUNK, wt] == top) and np.all(want["argmin"][PATCH_CHUNK, wt] == PATCH_TOP) and want["count"][PATCH_CHUNK, wt] == 1
+    assert np.all(want["max"][PATCH_CHUNK, wz] == 0) and np.all(want["argmax"][PATCH_CHUNK, wz] == PATCH_ZERO) and want["count"][PATCH_CHUNK, wz] == 1
     # (the drive itself sweeps the element range in every chunk, to within 1 %, but leaves no window to one value: hence the two rows)
     v = data.reshape(nchunks, rows, D).astype(np.int64)
     assert np.all(v.max(axis=1) - v.min(axis=1) >= top - top // 100)
@@ -285,21 +280,21 @@ def test_the_models_against_brute_force(codec):
     """uint8 x 5, 2 chunks of 48 blocks of the "lengths" drive"""
     w, D = 8, 5
     x, chunk_len, zero = rd.batch(codec, w, D, "lengths", 2, 48)
-    masks = t.masks_for(zero, 5)
+    masks = masks_for(zero, 5)
     for name, mask in masks:
-        for W in g.WINDOWS:
+        for W in WINDOWS:
             a, b = em.extrema_rows(x, chunk_len, D, mask, W), em.extrema_rows_brute(x, chunk_len, D, mask, W)
             assert all(np.array_equal(a[k], b[k]) for k in a), ("extrema", name, W)
-            for ref in t.refs_for(D):
+            for ref in refs_for(D):
                 a, b = mm.moments_rows(x, chunk_len, D, mask, W, ref), mm.moments_rows_brute(x, chunk_len, D, mask, W, ref)
                 assert all(np.array_equal(a[k].astype(np.uint64), np.array(b[k], np.uint64)) for k in a), ("moments", name, W, ref)
-        for bname, lo, shift, nbins, H in t.hist_binnings(w, D):
+        for bname, lo, shift, nbins, H in hist_binnings(w, D):
             assert np.array_equal(hm.histogram_rows(x, chunk_len, D, mask, lo, shift, nbins, H), hm.histogram_rows_brute(x, chunk_len, D, mask, lo, shift, nbins, H)), (name, bname)
-        key_lo, shift, nbins = t.gby_binning(w)
-        for H in t.GBY_TABLES:
+        key_lo, shift, nbins = gby_binning(w)
+        for H in GBY_TABLES:
             a, b = gbm.groupby_rows(x, chunk_len, D, 1, mask, key_lo, shift, nbins, H), gbm.groupby_rows_brute(x, chunk_len, D, 1, mask, key_lo, shift, nbins, H)
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), ("groupby", name, H)
-    for name, wt, u, bias, lo, hi in t.linear_sets(x, D, 1):
+    for name, wt, u, bias, lo, hi in linear_sets(x, D, 1):
         a, b = lm.filter_linear(x, chunk_len, D, wt, lo, hi, u, bias), lm.filter_linear_brute(x, chunk_len, D, wt, lo, hi, u, bias)
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and 0 < int(a[1].sum()) < x.size // D, ("linear", name)
     zmin, zmax, zlen = zm.zone_map(x, chunk_len, D, w // 8)
@@ -307,7 +302,7 @@ def test_the_models_against_brute_force(codec):
     assert zmin.tolist() == bmin and zmax.tolist() == bmax and zlen.tolist() == blen
     for d in range(D):
         for thr in (1, 64, 128, 255):
-            (lo, hi), (wt, llo, lhi) = t.band_bounds((d, thr), w, D)
+            (lo, hi), (wt, llo, lhi) = band_bounds((d, thr), w, D)
             cls = zm.classify_box(zmin, zmax, zlen, lo, hi, fm.ALL, D)
             assert np.array_equal(cls, zm.classify_linear(zmin, zmax, zlen, wt, 0, llo, lhi, D))
             assert all(int(k) in ok for k, ok in zip(cls, classes_brute(x, chunk_len, D, lambda r: r[d] >= thr))), (d, thr)     # noqa: B023
@@ -318,26 +313,12 @@ def test_the_models_against_brute_force(codec):
 
 # ------------------------------------------------------------------ the GPU tier's kernel-family literals, replayed through the planner
 
-QUERY = {"histogram": 8, "moments": 9, "groupby": 10, "extrema": 11, "linear": 12}          # csrc/geom.h: kQueryHistogram .. kQueryLinear
-CODEC = {"delta": 0, "xff": 1}
+LATER_OPS = ("histogram", "moments", "groupby", "extrema", "linear")
 
 
-def build(tmp_path_factory, name):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp(name) / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, name + ".cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        text = " ".join(f"{k}={int(v)}" for k, v in fields.items()) + "\n"
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.split()
-        return out[0], {k: int(v) for k, v in (tok.split("=") for tok in out[1:])}
-    return ask
-
-
-@pytest.fixture(scope="module")
-def probes(tmp_path_factory):
-    return {name: build(tmp_path_factory, name) for name in ("binned_plan_probe", "extrema_plan_probe", "linear_plan_probe")}
+def plan(**fields):
+    """-> (family, {every other field of the plan})"""
+    return planner.split(planner.ask("decode", **fields))
 
 
 def table_wg_chunks(wg_chunks, chunk_len, D, row_max):
@@ -352,46 +333,46 @@ def lanes(D):
     return dp
 
 
-def test_the_gpu_tiers_literals_are_the_planners(probe, probes):
+def test_the_gpu_tiers_literals_are_the_planners(probe):
     """every family tests/test_gpu_rowop_drive.py asserts from the dispatch counters is what csrc/plan.h plans for that shape, NO_FAST
     0 and 1, one and three chunks a lane group -- with the largest table of each case; and at three chunks a group a workgroup adds up
     three times the chunks in its table, or none where their rows could wrap an entry"""
-    for (w, D), want in g.ROWOP_SHAPES.items():
+    for (w, D), want in ROWOP_SHAPES.items():
         esz, chunk_len = w // 8, 8 * NB * D
         for codec in ("delta", "xff"):
             for no_fast in (0, 1):
-                for cpg in g.CPGS:
+                for cpg in CPGS:
                     kw = dict(esz=esz, D=D, chunk_len=chunk_len, nchunks=NCHUNKS, codec=CODEC[codec], no_fast=no_fast, chunks_per_group=cpg)
                     msg = (w, D, codec, no_fast, cpg)
-                    shape = dict(plan_shape(codec, w, D, chunk_len, NCHUNKS, no_fast=no_fast, **g.OLD), chunks_per_group=cpg)
+                    shape = dict(plan_shape(codec, w, D, chunk_len, NCHUNKS, no_fast=no_fast, **OLD), chunks_per_group=cpg)
                     for op in ("moments", "window", "filter", "aggregate", "select"):
-                        got, = probe(("decode", dict(shape, q=QUERY.get(op) or {"window": 3, "filter": 5, "aggregate": 7, "select": 6}[op])))
+                        got, = probe(("decode", dict(shape, q=QUERY[op])))
                         assert got.get("family") == ("dec_generic" if no_fast else want[op]), (op,) + msg + (got,)
                         if got.get("family") == "dec_fast":
-                            assert int(got["chunks_per_group"]) == cpg
-                    assert probes["extrema_plan_probe"](**kw)[0] == ("dec_generic" if no_fast else want["extrema"]), msg
-                    assert probes["linear_plan_probe"](**kw)[0] == ("dec_generic" if no_fast else want["linear"]), msg
-                    tables = [("histogram", D * max(b[3] for b in t.hist_binnings(w, D)), 1), ("groupby", t.gby_binning(w)[2] * (D + 1), (1 << w) - 1)]
+                            assert got["chunks_per_group"] == cpg
+                    assert plan(q=QUERY["extrema"], **kw)[0] == ("dec_generic" if no_fast else want["extrema"]), msg
+                    assert plan(q=QUERY["linear"], **kw)[0] == ("dec_generic" if no_fast else want["linear"]), msg
+                    tables = [("histogram", D * max(b[3] for b in hist_binnings(w, D)), 1), ("groupby", gby_binning(w)[2] * (D + 1), (1 << w) - 1)]
                     for op, entries, row_max in tables:
-                        fam, f = probes["binned_plan_probe"](q=QUERY[op], table_entries=entries, table_row_max=row_max, **kw)
+                        fam, f = plan(q=QUERY[op], table_entries=entries, table_row_max=row_max, **kw)
                         assert fam == ("dec_generic" if no_fast else want[op]), (op,) + msg
                         per_wg = 256 // lanes(D) * (cpg if fam == "dec_fast" else 1)
                         assert f["wg_chunks"] == table_wg_chunks(per_wg, chunk_len, D, row_max), (op,) + msg + (f,)
                         assert f["lds"] <= 80 * 1024 and (f["table_off"] > 0) == (fam == "dec_fast")
     # the group-by sums of uint16 x 8 sit on the rule's edge: 32 chunks of 2 048 rows fit an entry, 96 do not
     assert table_wg_chunks(32, 8 * NB * 8, 8, 65535) == 32 and table_wg_chunks(96, 8 * NB * 8, 8, 65535) == 0
-    assert t.DAMAGE_SHAPES == [(c, w, D) for c in ("delta", "xff") for (w, D) in ((16, 8), (8, 32))]       # (dec_fast for every mode, select rows included)
-    assert all(g.ROWOP_SHAPES[(w, D)][op] == "dec_fast" for _, w, D in t.DAMAGE_SHAPES for op in ("window", "filter", "select", "aggregate", *QUERY))
+    assert DAMAGE_SHAPES == [(c, w, D) for c in ("delta", "xff") for (w, D) in ((16, 8), (8, 32))]       # (dec_fast for every mode, select rows included)
+    assert all(ROWOP_SHAPES[(w, D)][op] == "dec_fast" for _, w, D in DAMAGE_SHAPES for op in ("window", "filter", "select", "aggregate", *LATER_OPS))
     # the FIRE drive's shapes
-    for (w, D), (nchunks, fire_legs) in t.FIRE_SHAPES.items():
-        esz, chunk_len = w // 8, t.fire_rows(w, D) * D
+    for (w, D), (nchunks, fire_legs) in FIRE_SHAPES.items():
+        esz, chunk_len = w // 8, fire_rows(w, D) * D
         for opts, cpg, family in fire_legs:
             no_fast = opts.get("no_fast", 0)
             kw = dict(esz=esz, D=D, chunk_len=chunk_len, nchunks=nchunks, codec=1, no_fast=no_fast, chunks_per_group=cpg)
-            shape = dict(plan_shape("xff", w, D, chunk_len, nchunks, **dict(g.OLD, **opts)), chunks_per_group=cpg)
+            shape = dict(plan_shape("xff", w, D, chunk_len, nchunks, **dict(OLD, **opts)), chunks_per_group=cpg)
             got, = probe(("decode", dict(shape, q=QUERY["moments"])))
             assert got.get("family") == family, (w, D, opts, got)
-            assert probes["extrema_plan_probe"](**kw)[0] == family and probes["linear_plan_probe"](**kw)[0] == family, (w, D, opts)
-            assert probes["binned_plan_probe"](q=QUERY["histogram"], table_entries=D * 256, table_row_max=1, **kw)[0] == family, (w, D, opts)
+            assert plan(q=QUERY["extrema"], **kw)[0] == family and plan(q=QUERY["linear"], **kw)[0] == family, (w, D, opts)
+            assert plan(q=QUERY["histogram"], table_entries=D * 256, table_row_max=1, **kw)[0] == family, (w, D, opts)
             if D == 8:
-                assert probes["binned_plan_probe"](q=QUERY["groupby"], table_entries=256 * (D + 1), table_row_max=255, **kw)[0] == family, (w, D, opts)
+                assert plan(q=QUERY["groupby"], table_entries=256 * (D + 1), table_row_max=255, **kw)[0] == family, (w, D, opts)

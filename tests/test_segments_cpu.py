@@ -1,10 +1,8 @@
 """CPU tier of segment rows (sprintz_mi355x_segment_count / _segment_rows, ChunkedCodec.segment_rows): the numpy model
 (tests/segment_model.py) against a plain row loop, rowops.fold_segments on torch CPU tensors against the model of the batch taken as one
 chunk, what the masks of tests/test_gpu_segments.py must reach -- asserted here without a device -- and the planner
-(sprintz_amd/csrc/plan.h, built with g++: tests/segment_plan_probe.cpp), which must give the mode what it gives aggregate rows."""
+(sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp), which must give the mode what it gives aggregate rows."""
 import os
-import shutil
-import subprocess
 import zlib
 
 import numpy as np
@@ -12,23 +10,18 @@ import pytest
 
 import dispatch_cases as dc
 import filter_model as fm
-import rle_drive as rd
+import planner
 import segment_model as sgm
-import test_gpu_aggregate as ga
-import test_gpu_rle_drive as g
-import test_gpu_rowop_drive as t
+from drive_tables import BOTH, NB, NCHUNKS, ROWOP_KINDS, ROWOP_SHAPES, batch_of, masks_for
+from fixtures import random_mask
+from planner import QUERY
+from rowdata import MASKED_SHAPES as SHAPES, gen_data, parity_masks, rows_for, short_batch
 from harness import DTYPES
-from test_gpu_query_windows import gen_data
-from test_gpu_select import parity_masks, short_batch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MODES = (sgm.RUNS, sgm.SPLITS)
-Q_AGGREGATE, Q_SEGMENT = 7, 13                           # csrc/geom.h: kQueryAggregate, kQuerySegment
+Q_AGGREGATE, Q_SEGMENT = QUERY["aggregate"], QUERY["segment"]
 KEYS = ("counts", "chunk", "start", "rows", "min", "max", "sum")
-
-
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
 
 
 def assert_same(a, b, msg):
@@ -170,8 +163,8 @@ def gpu_masks(rng, x, chunk_len, esz, D):
 def test_the_gpu_masks_reach_the_edges():
     esz, D = 2, 8
     seen = set()
-    for shape in ga.SHAPES:
-        R = ga.rows_for(shape, D)
+    for shape in SHAPES:
+        R = rows_for(shape, D)
         chunk_len = R * D
         rng = np.random.default_rng(zlib.crc32(f"segments{shape}".encode()))
         x = gen_data("walk", rng, short_batch(5, chunk_len, D), esz, D)
@@ -205,16 +198,16 @@ def test_the_gpu_masks_reach_the_edges():
     assert set((e - s).tolist()) == set(range(1, 18)) and len({int(a) % 8 for a in s}) == 8 and len({int(b) % 8 for b in e}) == 8
 
 
-@pytest.mark.parametrize("codec,w,D", [(c, w, D) for c in g.BOTH for (w, D) in g.ROWOP_SHAPES])
+@pytest.mark.parametrize("codec,w,D", [(c, w, D) for c in BOTH for (w, D) in ROWOP_SHAPES])
 def test_the_drive_masks_cut_runs_and_leave_runs_whole(codec, w, D):
     """over the drive's batches: under the masks of the GPU tier a run of zero blocks holds a start or an end in its mask bytes (the run is
     replayed block by block), and a run holds none (decode_fast.h's O(1) step), inside a segment and outside every segment"""
     seen = set()
-    for kind in g.ROWOP_KINDS:
-        data, chunk_len, zero = g.batch_of(codec, w, D, kind, g.NCHUNKS, g.NB)
-        for name, mask in t.masks_for(zero, 41)[:3]:
+    for kind in ROWOP_KINDS:
+        data, chunk_len, zero = batch_of(codec, w, D, kind, NCHUNKS, NB)
+        for name, mask in masks_for(zero, 41)[:3]:
             for mode in MODES:
-                for c in range(g.NCHUNKS):
+                for c in range(NCHUNKS):
                     z = zero[c]
                     edges_ = np.flatnonzero(np.diff(np.concatenate([[0], z.astype(np.int8), [0]])))
                     for a, b in zip(edges_[::2].tolist(), edges_[1::2].tolist()):
@@ -231,18 +224,9 @@ def test_the_drive_masks_cut_runs_and_leave_runs_whole(codec, w, D):
 # ------------------------------------------------------------------ the planner
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("segment_plan") / "plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "segment_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(queries):
-        text = "".join(" ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n" for q in queries)
-        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
-        assert len(out) == len(queries)
-        return out
-    return ask
+def plan():
+    planner.available()
+    return lambda queries: planner.ask_many(("decode", dict(q=Q_SEGMENT, **q) if "q" not in q else q) for q in queries)
 
 
 def test_planner_gives_the_mode_what_it_gives_aggregate_rows(plan):
@@ -264,11 +248,11 @@ def test_planner_gives_the_mode_what_it_gives_aggregate_rows(plan):
     seg = plan([dict(q, q=Q_SEGMENT) for q in queries])
     agg = plan([dict(q, q=Q_AGGREGATE) for q in queries])
     assert seg == agg
-    families = {line.split()[0] for line in seg}
+    families = {got["family"] for got in seg}
     assert families == {"dec_fast", "dec_generic"}, families
     # the headline shape, and the low-dimension layouts: decode_uni.h is not taught the mode
-    head = plan([dict(esz=2, D=8, chunk_len=5120, nchunks=131072, codec=1)])[0].split()
-    assert head[0] == "dec_fast" and "dp=8" in head and "cpl=1" in head and "exact=1" in head
+    head = plan([dict(esz=2, D=8, chunk_len=5120, nchunks=131072, codec=1)])[0]
+    assert head["family"] == "dec_fast" and head["dp"] == 8 and head["cpl"] == 1 and head["exact"] == 1
     low = [dict(esz=esz, D=D, chunk_len=cl, nchunks=4096, codec=1) for esz, D, cl in [(1, 1, 1024), (2, 1, 1024), (1, 2, 2048), (2, 2, 2048), (1, 3, 3000), (1, 4, 4096)]]
-    assert all(line.split()[0] == "dec_generic" for line in plan(low))
-    assert all(line.split()[0] == "dec_uni" for line in plan([dict(q, q=3) for q in low]))
+    assert all(got["family"] == "dec_generic" for got in plan(low))
+    assert all(got["family"] == "dec_uni" for got in plan([dict(q, q=QUERY["window"]) for q in low]))

@@ -1,31 +1,22 @@
 """CPU tests of select rows (sprintz_mi355x_select_rows): the symbol and its binding are there, every validation return comes before
 the device is touched, the numpy model the GPU tier compares with (tests/select_model.py) equals a one-row-at-a-time brute force and
-agrees with the filter model's row numbers, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/select_plan_probe.cpp)
+agrees with the filter model's row numbers, and the planner (sprintz_amd/csrc/plan.h, built with g++: tests/plan_probe.cpp)
 sends the mode to decode_fast.h or to the generic kernel where the header says."""
-import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import filter_model as fm
 import select_model as sm
+from fixtures import buf_fixture, lib, random_mask  # noqa: F401  (fixtures)
+from planner import QUERY, family, plan_fixture
+from rowdata import RAGGED_SHAPES as SHAPES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 8192)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(8192)
 
 
 def test_symbol_and_binding(lib):
@@ -77,20 +68,6 @@ def test_validation_comes_before_the_device(lib, buf):
         assert call(cap=0) == E.E_NO_DEVICE and call(cap=(1 << 64) - 1) == E.E_NO_DEVICE
 
 
-SHAPES = [
-    # (esz, D, chunk_len, n): whole rows, short last chunks (one ending mid-row), R % 8 != 0 and R < 8
-    (1, 3, 3 * 33, 3 * 33 * 4 + 3 * 14),
-    (2, 5, 5 * 21, 5 * 21 * 3 + 5 * 4 + 2),
-    (1, 1, 13, 13 * 5 + 6),
-    (2, 8, 8 * 64, 8 * 64 * 3),
-    (1, 7, 7 * 5, 7 * 5 * 6 + 7),
-]
-
-
-def random_mask(rng, nchunks, MB, p):
-    return np.packbits(rng.random((nchunks, MB * 8)) < p, axis=1, bitorder="little")
-
-
 @pytest.mark.parametrize("esz,D,chunk_len,n", SHAPES)
 def test_model_equals_brute_force(esz, D, chunk_len, n):
     rng = np.random.default_rng(n + D)
@@ -134,19 +111,7 @@ def test_model_with_the_filter_models_mask(esz, D, chunk_len, n):
         assert np.array_equal(rows, x.reshape(-1, D)[want_ids])
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("select_plan") / "select_plan_probe"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(HERE, "select_plan_probe.cpp"), "-o", str(exe)])
-
-    def ask(**fields):
-        q = dict(codec=1, nchunks=4096, capacity=1000, out_lo=0)
-        q.update(fields)
-        text = " ".join(f"{k}={int(v)}" for k, v in q.items()) + "\n"
-        return subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.strip()
-    return ask
+plan = plan_fixture(shape=family, q=QUERY["select"], codec=1, nchunks=4096, capacity=1000, out_lo=0)
 
 
 def test_planner_edges(plan):

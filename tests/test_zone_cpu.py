@@ -17,21 +17,13 @@ import filter_model as fm
 import linear_model as lm
 import zone_model as zm
 from harness import DTYPES
-from test_gpu_linear import weight_sets
+from fixtures import buf_fixture, lib  # noqa: F401  (fixtures)
+from rowdata import weight_sets
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from sprintz_amd import _lib
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def buf():
-    b = (C.c_uint8 * 65536)()
-    return b, (C.addressof(b) + 15) & ~15
+buf = buf_fixture(65536)
 
 
 SYMBOLS = ("sprintz_mi355x_zone_map", "sprintz_mi355x_zone_prune_tmp_bytes", "sprintz_mi355x_zone_prune_box", "sprintz_mi355x_zone_prune_linear",

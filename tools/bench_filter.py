@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import sprintz_amd as sz  # noqa: E402
 from sprintz_amd import _lib  # noqa: E402
-from test_gpu_bench_data import bench_input  # noqa: E402  (what bench.py generates for these configurations, rank 0 of 1)
+from rowdata import bench_input
 
 
 def timed(fn, steps, warmup=3):

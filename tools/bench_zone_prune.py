@@ -36,7 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import sprintz_amd as sz  # noqa: E402
 from sprintz_amd import _lib  # noqa: E402
-from test_gpu_bench_data import bench_input  # noqa: E402  (what bench.py generates for this configuration, rank 0 of 1)
+from rowdata import bench_input
 
 HYPOTHESIS = """Hypothesis, written before the first run: a filter's time is its decode, chunk by chunk, so with a zone map the zoned call (z) falls
 about in proportion to the chunks that survive, plus a constant for the prune launches, the 8-byte read-back and the expand launch that
