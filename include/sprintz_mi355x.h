@@ -53,7 +53,7 @@ extern "C" {
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
  *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
- *      float_rows, SPRINTZ_FLOAT_* */
+ *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -951,6 +951,40 @@ int sprintz_mi355x_segment_count(const uint8_t* d_mask, uint64_t nchunks, uint32
 int sprintz_mi355x_float_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                               uint32_t chunk_len, uint16_t ndims, int out_format, const float* d_scale, const float* d_offset,
                               uint32_t flags, void* d_out, int64_t* d_rets, void* hip_stream);
+/* Compress floats: float_rows' way in.  sprintz_mi355x_compress_batch / _compress_batch_dense on a source of float32 / float16 / bfloat16
+ * that the encoder quantises while it loads -- the integer tensor never exists.  Element e of the source is in column d = e % ndims
+ * (chunk_len % ndims == 0; a short last chunk may end mid-row); for the source element x
+ *   v = (float32) x                                           exact for the 16-bit formats
+ *   t = fl32(fl32(v - d_offset[d]) * d_inv_scale[d])          two IEEE float32 operations, never contracted into one
+ *   r = rint(t), ties to even -- or floor(t) with SPRINTZ_QUANT_FLOOR in flags
+ *   q = 0 where r is NaN, else r clamped to [LO, HI]          0 .. 2^W - 1, or -2^(W-1) .. 2^(W-1) - 1 with SPRINTZ_FLOAT_SIGNED (W = 8 elem_bytes)
+ * which is, bit for bit, nan_to_num(round_or_floor((x.float() - offset) * inv_scale), nan=0).clamp(LO, HI) of PyTorch on the CPU: +-inf clamp,
+ * float32 subnormals are kept.  The encoder takes q as a W-bit two's-complement element, and what the call writes -- streams, d_sizes, d_rets,
+ * container and d_offsets -- is byte for byte what sprintz_mi355x_compress_batch / _compress_batch_dense write for the integer tensor q.
+ *   d_src      : total_len elements of src_format (SPRINTZ_FLOAT_F32 / _F16 / _BF16), row-major; NO byte outside them is read (the integer
+ *                calls' READ_SLACK is not asked for)
+ *   d_inv_scale, d_offset: float32 [ndims] on the device; NULL is all 1 / all 0.  inv_scale is the RECIPROCAL of float_rows' scale: with
+ *                (1 / scale, offset) this call and float_rows(scale, offset) are each other's way back, within one quantisation step
+ *   flags      : SPRINTZ_FLOAT_SIGNED, SPRINTZ_QUANT_FLOOR and nothing else
+ *   the other arguments: as sprintz_mi355x_compress_batch / _compress_batch_dense take them (d_tmp: sprintz_mi355x_compress_dense_tmp_bytes)
+ * The launch counts under the encoder family that served it: SPRINTZ_KF_ENC_PAIR (5 .. 64 columns with blocks and chunks of whole 16-byte
+ * pieces, whatever SPRINTZ_OPT_ENC_PAIR says), _ENC_WIDE / _ENC_SPLIT (65 .. 128 columns), else _ENC_GENERIC -- also for d_src off the 16-byte
+ * grid and under SPRINTZ_OPT_NO_FAST; the container under SPRINTZ_KF_DENSE_FUSED or _DENSE_COMPACT.  No synchronisation, no allocation.
+ * Measured (profiles/compress_floats.txt; the dense call against torch's quantise expression + compress_batch_dense, ms): headline batch
+ * (uint16 x 8) float32 0.909 / 7.72, float16 0.818 / 8.42, bfloat16 0.831 / 8.34; uint8 x 80 at 10 KB chunks 0.794 / 4.91, 0.927 / 5.43,
+ * 0.925 / 5.43 -- where the integer call alone takes 0.54 - 0.62 and 0.27.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown src_format or
+ * flag, a NULL d_src / d_slots / d_sizes (or d_dense / d_offsets / d_tmp), d_src not aligned to the source element, d_inv_scale / d_offset
+ * not aligned to 4 bytes, and everything sprintz_mi355x_compress_batch refuses; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the
+ * non-RLE codecs.  Every message names the call.  total_len == 0 returns 0, launches nothing and writes nothing. */
+#define SPRINTZ_QUANT_FLOOR 4u   /* in flags, next to SPRINTZ_FLOAT_SIGNED */
+int sprintz_mi355x_compress_batch_float(int codec, int elem_bytes, const void* d_src, int src_format, const float* d_inv_scale,
+                                        const float* d_offset, uint32_t flags, uint64_t total_len, uint32_t chunk_len, uint16_t ndims,
+                                        void* d_slots, size_t slot_stride, uint32_t* d_sizes, int64_t* d_rets, void* hip_stream);
+int sprintz_mi355x_compress_batch_float_dense(int codec, int elem_bytes, const void* d_src, int src_format, const float* d_inv_scale,
+                                              const float* d_offset, uint32_t flags, uint64_t total_len, uint32_t chunk_len, uint16_t ndims,
+                                              void* d_slots, size_t slot_stride, uint32_t* d_sizes, int64_t* d_rets, void* d_dense,
+                                              uint64_t* d_offsets, void* d_tmp, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

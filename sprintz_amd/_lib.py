@@ -181,6 +181,11 @@ segment_count = _sig("sprintz_mi355x_segment_count", _i, _vp, _u64, _u32, _u16, 
 FLOAT_F32, FLOAT_F16, FLOAT_BF16 = 0, 1, 2
 FLOAT_SIGNED = 2
 float_rows = _sig("sprintz_mi355x_float_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _i, _vp, _vp, _u32, _vp, _vp, _vp)
+# compress floats: compress_batch / compress_batch_dense on a float source the encoder quantises while it loads
+QUANT_FLOOR = 4
+compress_batch_float = _sig("sprintz_mi355x_compress_batch_float", _i, _i, _i, _vp, _i, _vp, _vp, _u32, _u64, _u32, _u16, _vp, _sz, _vp, _vp, _vp)
+compress_batch_float_dense = _sig("sprintz_mi355x_compress_batch_float_dense", _i, _i, _i, _vp, _i, _vp, _vp, _u32, _u64, _u32, _u16, _vp, _sz, _vp, _vp,
+                                  _vp, _vp, _vp, _vp)
 query = {
     ("delta", 1): _sig("sprintz_mi355x_query_delta_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
     ("xff", 1): _sig("sprintz_mi355x_query_xff_8b", _i64, _vp, _vp, _i, _i, _u32, _vp),
@@ -254,7 +259,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_zone_map", "sprintz_mi355x_zone_prune_tmp_bytes", "sprintz_mi355x_zone_prune_box", "sprintz_mi355x_zone_prune_linear", "sprintz_mi355x_zone_expand",
     "sprintz_mi355x_aggregate_rows", "sprintz_mi355x_histogram_rows", "sprintz_mi355x_moments_rows", "sprintz_mi355x_groupby_rows", "sprintz_mi355x_extrema_rows",
     "sprintz_mi355x_segment_rows", "sprintz_mi355x_segment_count",
-    "sprintz_mi355x_float_rows",
+    "sprintz_mi355x_float_rows", "sprintz_mi355x_compress_batch_float", "sprintz_mi355x_compress_batch_float_dense",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",
     "sprintz_mi355x_compress_batch_colmajor", "sprintz_mi355x_compress_batch_colmajor_dense", "sprintz_mi355x_decompress_batch_colmajor",

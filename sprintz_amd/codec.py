@@ -238,6 +238,52 @@ class ChunkedCodec:
         data = dense[: total + _lib.READ_SLACK].clone()
         return CompressedBatch(data, offsets, ws["sizes"].clone(), nchunks, total_len, self.chunk_len, self.ndims)
 
+    def compress_floats(self, src, scale=None, offset=None, signed=False, rounding="nearest"):
+        """compress() of a float tensor that the encoder quantises while it loads: float_rows' way in, in one launch for the shapes
+        compress() takes in one -- the integer tensor never exists.  Element x of column d is coded as
+            q = clamp(round((x.float() - offset[d]) * (1 / scale[d])), LO, HI),   NaN -> 0,
+        LO / HI the range of the codec's unsigned element type, or of the signed one with signed=True; the batch is byte for byte
+        compress(q).  (scale, offset) are what float_rows takes -- a number, a sequence of ndims numbers or a tensor of ndims elements;
+        None is all 1 / all 0 -- so compress_floats(x, *datasets.dequantize_params(m, dt)) and float_rows(batch, *dequantize_params(m, dt))
+        are each other's way back; 1 / scale is one float32 division (rowops.quant_params).  rounding: "nearest" (ties to even) or
+        "floor" -- which matches datasets.quantize's truncation within one step, not bit for bit: quantize divides in float32 where this
+        multiplies by a reciprocal.
+
+        src: a torch.float32, float16 or bfloat16 tensor on the codec's device, any shape, row-major [.., ndims]; a non-contiguous one
+        is made contiguous (a copy).  chunk_len must be a multiple of ndims; the codec must be 'delta' or 'xff' with align 16.
+        -> a CompressedBatch, as compress() returns it."""
+        torch = self.torch
+        if not torch.is_tensor(src):
+            raise ValueError("src must be a float tensor")
+        fmt = rowops.float_format(src.dtype)
+        if src.device != self.device:
+            raise ValueError(f"src must be on {self.device}")
+        if self.align != 16:
+            raise ValueError("compress_floats builds the 16-byte aligned container")
+        if rounding not in ("nearest", "floor"):
+            raise ValueError("rounding must be 'nearest' or 'floor'")
+        D = self.ndims
+        rowops.chunk_rows(self.chunk_len, D, "compress_floats")
+        inv, off = rowops.quant_params(scale, offset, D, self.device)
+        flat = src.contiguous().reshape(-1)
+        total_len = flat.numel()
+        nchunks = int(_lib.num_chunks(total_len, self.chunk_len))
+        ws = self.workspace(nchunks)
+        dense, offsets = self._new_container(nchunks)
+        flags = (_lib.FLOAT_SIGNED if signed else 0) | (_lib.QUANT_FLOOR if rounding == "floor" else 0)
+        if total_len == 0:                                  # (an empty tensor has no address to hand over)
+            offsets.zero_()
+            return CompressedBatch(dense[: _lib.READ_SLACK].clone(), offsets, ws["sizes"].clone(), 0, 0, self.chunk_len, D)
+        with self._on():
+            _lib.check(_lib.compress_batch_float_dense(_CODEC_ID[self.codec], self.esz, flat.data_ptr(), fmt,
+                                                       inv.data_ptr() if inv is not None else None, off.data_ptr() if off is not None else None,
+                                                       flags, total_len, self.chunk_len, D, ws["slots"].data_ptr(), self.slot_stride,
+                                                       ws["sizes"].data_ptr(), ws["rets"].data_ptr(), dense.data_ptr(), offsets.data_ptr(),
+                                                       ws["tmp"].data_ptr(), self._stream()))
+        total = int(offsets[-1].item())
+        data = dense[: total + _lib.READ_SLACK].clone()
+        return CompressedBatch(data, offsets, ws["sizes"].clone(), nchunks, total_len, self.chunk_len, D)
+
     def decompress(self, batch, out=None, rets=None):
         """-> device tensor of total_len elements (chunk c at c*chunk_len)."""
         t = self.torch

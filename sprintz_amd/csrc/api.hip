@@ -490,6 +490,7 @@ Shape encode_shape(const EncodeBatch& j, bool dense, bool host_call)
     s.codec = j.codec; s.esz = j.esz; s.D = j.ndims; s.total_len = j.total_len; s.nchunks = sprintz_mi355x_num_chunks(j.total_len, j.chunk_len); s.chunk_len = j.chunk_len;
     s.general = j.general; s.col_stride = j.col_stride; s.write_size = j.write_size; s.dense = dense; s.host_call = host_call;
     s.src_lo = low4(j.src); s.slots_lo = low4(j.slots); s.slot_stride = j.slot_stride;
+    if (j.fsrc) { s.q = kQueryFloat; s.out_esz = float_out_bytes(j.q_mode); }
     return s;
 }
 
@@ -518,6 +519,9 @@ int encode_launch(const Plan& p, const EncodeBatch& j, hipStream_t st, const Den
     a.raw = p.raw;
     a.cap = p.cap;
     a.lds_group_stride = p.lds_group_stride;
+    a.q_inv = j.q_inv;
+    a.q_off = j.q_off;
+    a.q_mode = j.q_mode;
     if (p.fused) {
         a.dn.dense = (uint8_t*)dense->d_dense;
         a.dn.offsets = dense->d_offsets;
@@ -530,6 +534,15 @@ int encode_launch(const Plan& p, const EncodeBatch& j, hipStream_t st, const Den
     const unsigned grid = (unsigned)p.grid;
     hipError_t e = hipSuccess;
     const char* what = "";
+    if (j.fsrc) {                                           // a float source: the planner names no other family for one
+        if (p.family != SPRINTZ_KF_ENC_PAIR && p.family != SPRINTZ_KF_ENC_WIDE && p.family != SPRINTZ_KF_ENC_SPLIT && p.family != SPRINTZ_KF_ENC_GENERIC)
+            return fail(SPRINTZ_E_HIP, "internal: a float source on a kernel that cannot quantise");
+        e = esz == 1 ? launch_encode_float_w8(p.family, p.fire, p.lowdim, p.cpl, p.dp, p.exact, grid, (size_t)p.lds, st, a)
+                     : launch_encode_float_w16(p.family, p.fire, p.lowdim, p.cpl, p.dp, p.exact, grid, (size_t)p.lds, st, a);
+        if (e != hipSuccess) return fail(SPRINTZ_E_HIP, "encode kernel launch (float source)", e);
+        dispatched(p.family);
+        return 0;
+    }
     switch (p.family) {
     case SPRINTZ_KF_ENC_BIG: {
         int32_t* counters;
@@ -712,6 +725,69 @@ int sprintz_mi355x_compress_batch_dense(int codec, int elem_bytes, const void* d
         return 0;
     }
     return encode_dense(enc, j, dr, nchunks, hip_stream);
+}
+
+// ---- a float source, quantised inside the encoder (quant.h)
+namespace {
+// every refusal of the two calls below carries the call's name
+int named(const char* op, int rc)
+{
+    if (rc && g_last_error.rfind(op, 0) != 0) g_last_error = std::string(op) + ": " + g_last_error;
+    return rc;
+}
+// the checks the two calls share, before the device is touched; fills the float side of j
+int check_float_source(const char* op, EncodeBatch& j, int src_format, const float* d_inv_scale, const float* d_offset, uint32_t flags, const DenseRequest* dense)
+{
+    int rc = check_common(j.codec, j.esz, j.ndims);
+    if (rc) return named(op, rc);
+    if (j.chunk_len == 0 || j.chunk_len > (1u << 30)) return fail_op(SPRINTZ_E_INVALID, op, "chunk_len must be in 1..2^30");
+    if (j.chunk_len % j.ndims) return fail_op(SPRINTZ_E_INVALID, op, "chunk_len must be a multiple of ndims (element e of a chunk is in column e % ndims)");
+    static_assert(SPRINTZ_FLOAT_F32 == (int)kFloatF32 && SPRINTZ_FLOAT_F16 == (int)kFloatF16 && SPRINTZ_FLOAT_BF16 == (int)kFloatBF16, "the format travels as it is given");
+    if (src_format != SPRINTZ_FLOAT_F32 && src_format != SPRINTZ_FLOAT_F16 && src_format != SPRINTZ_FLOAT_BF16)
+        return fail_op(SPRINTZ_E_INVALID, op, "src_format must be SPRINTZ_FLOAT_F32, SPRINTZ_FLOAT_F16 or SPRINTZ_FLOAT_BF16");
+    if (flags & ~(uint32_t)(SPRINTZ_FLOAT_SIGNED | SPRINTZ_QUANT_FLOOR)) return fail_op(SPRINTZ_E_INVALID, op, "unknown flag");
+    j.fsrc = true;
+    j.q_inv = d_inv_scale;
+    j.q_off = d_offset;
+    j.q_mode = (uint32_t)src_format | ((flags & SPRINTZ_FLOAT_SIGNED) ? kFloatSignedBit : 0u) | ((flags & SPRINTZ_QUANT_FLOOR) ? kQuantFloorBit : 0u);
+    if (j.ndims > 512) return fail_op(SPRINTZ_E_UNSUPPORTED, op, "more than 512 columns");
+    if (j.codec != SPRINTZ_CODEC_DELTA && j.codec != SPRINTZ_CODEC_XFF) return fail_op(SPRINTZ_E_UNSUPPORTED, op, "the RLE codecs (delta, xff) only");
+    if ((rc = check_slots(j, dense, dense ? "slots and the container must be 16-byte aligned/strided" : "slots must be 16-byte aligned/strided"))) return named(op, rc);
+    if ((uintptr_t)j.src % (uintptr_t)float_out_bytes(j.q_mode)) return fail_op(SPRINTZ_E_INVALID, op, "d_src must be aligned to the source element size");
+    if ((uintptr_t)d_inv_scale % 4 || (uintptr_t)d_offset % 4) return fail_op(SPRINTZ_E_INVALID, op, "d_inv_scale and d_offset must be 4-byte aligned");
+    if ((rc = check_batch_tail(j.total_len, j.chunk_len, j.ndims))) return named(op, rc);
+    return 0;
+}
+}  // namespace
+
+int sprintz_mi355x_compress_batch_float(int codec, int elem_bytes, const void* d_src, int src_format, const float* d_inv_scale, const float* d_offset,
+                                        uint32_t flags, uint64_t total_len, uint32_t chunk_len, uint16_t ndims, void* d_slots, size_t slot_stride,
+                                        uint32_t* d_sizes, int64_t* d_rets, void* hip_stream)
+{
+    static const char* const op = "compress_batch_float";
+    EncodeBatch j{codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets};
+    int rc = check_float_source(op, j, src_format, d_inv_scale, d_offset, flags, nullptr);
+    if (rc) return rc;
+    if (total_len == 0) return 0;
+    if ((rc = ensure_device())) return named(op, rc);
+    return named(op, encode_batch(snapshot(), j, (hipStream_t)hip_stream));
+}
+
+int sprintz_mi355x_compress_batch_float_dense(int codec, int elem_bytes, const void* d_src, int src_format, const float* d_inv_scale, const float* d_offset,
+                                              uint32_t flags, uint64_t total_len, uint32_t chunk_len, uint16_t ndims, void* d_slots, size_t slot_stride,
+                                              uint32_t* d_sizes, int64_t* d_rets, void* d_dense, uint64_t* d_offsets, void* d_tmp, void* hip_stream)
+{
+    static const char* const op = "compress_batch_float_dense";
+    EncodeBatch j{codec, elem_bytes, d_src, total_len, chunk_len, ndims, d_slots, slot_stride, d_sizes, d_rets};
+    const DenseRequest dr{d_dense, d_offsets, d_tmp};
+    int rc = check_float_source(op, j, src_format, d_inv_scale, d_offset, flags, &dr);
+    if (rc) return rc;
+    if (total_len == 0) return 0;
+    if ((rc = ensure_device())) return named(op, rc);
+    Plan enc;
+    const Plan dp = plan_dense(encode_shape(j, false, false), snapshot(), &enc);       // (never the verbatim kernel: it copies raw source bytes)
+    if (dp.err && !enc.err) return fail_op(dp.err, op, dp.what);
+    return named(op, encode_dense(enc, j, dr, sprintz_mi355x_num_chunks(total_len, chunk_len), hip_stream));
 }
 
 size_t sprintz_mi355x_compact_tmp_bytes(uint64_t nchunks)

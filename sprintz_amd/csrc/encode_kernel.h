@@ -16,6 +16,7 @@
 
 #include "sprintz_device.h"
 #include "compact_tail.h"
+#include "quant.h"
 
 namespace sprintz {
 
@@ -46,9 +47,15 @@ struct EncodeArgs {
     // host_flag, after every lane's stores
     uint64_t* host_flag;
     uint64_t host_ticket;
+    // a float source (quant.h; the FSRC instantiations alone): src holds total_len float32 / float16 / bfloat16, q_inv / q_off are the
+    // columns' inverse scales and offsets (float32 [D]; null: all 1 / all 0), q_mode the format, kFloatSignedBit and kQuantFloorBit
+    const float* q_inv;
+    const float* q_off;
+    uint32_t q_mode;
 };
 
-template <int W, bool FIRE, bool LOWDIM, int CPL>
+// FSRC: the source is float and every read of it quantises (quant.h); row-major only, the RLE codecs only
+template <int W, bool FIRE, bool LOWDIM, int CPL, bool FSRC = false>
 __global__ void __launch_bounds__(kThreads) encode_kernel(EncodeArgs a)
 {
     using U = typename Elem<W>::U;
@@ -74,6 +81,12 @@ __global__ void __launch_bounds__(kThreads) encode_kernel(EncodeArgs a)
     auto elem = [&](uint32_t e) -> uint32_t {
         return cs ? (uint32_t)cm0[(uint64_t)(e % (uint32_t)D) * cs + e / (uint32_t)D] : (uint32_t)sc[e];
     };
+    // float source: element e of the chunk (column e % D: a chunk starts a row), quantised
+    const uint32_t qmode = FSRC ? a.q_mode : 0u, qfmt = qmode & 3u;
+    auto qelem = [&](uint32_t e) -> uint32_t {
+        const uint32_t d = e % (uint32_t)D;
+        return quant_value<W>(quant_load(a.src, qfmt, first + e), quant_inv_scale(a.q_inv, d), quant_offset(a.q_off, d), qmode);
+    };
 
     // A chunk too short for one group (n < 128 or n < 16 D: BASELINE config 3 at 1 KB chunks) is
     // stored verbatim behind its header (sprintz_xff_rle.cpp:116-124, :158-160): straight copy,
@@ -83,7 +96,11 @@ __global__ void __launch_bounds__(kThreads) encode_kernel(EncodeArgs a)
         const uint8_t* src = (const uint8_t*)sc;
         uint8_t* dst = gdst + hdr;
         const uint32_t nbytes = n * ESZ;
-        copy_verbatim<false>(src, dst, nbytes, (uint32_t)lane_d, (uint32_t)DP);      // (the compaction pass reads it next: ordinary stores)
+        if constexpr (FSRC) {                        // (dst is 8 bytes behind a 16-byte aligned slot)
+            for (uint32_t e = (uint32_t)lane_d; e < n; e += (uint32_t)DP) ((U*)dst)[e] = (U)qelem(e);
+        } else {
+            copy_verbatim<false>(src, dst, nbytes, (uint32_t)lane_d, (uint32_t)DP);      // (the compaction pass reads it next: ordinary stores)
+        }
         // slots are zero padded to 16 bytes (sprintz_mi355x_compact copies whole 16-byte units: the container's
         // alignment padding must not carry stale workspace bytes)
         for (uint32_t j = hdr + nbytes + (uint32_t)lane_d; j < ((hdr + nbytes + 15u) & ~15u); j += (uint32_t)DP) gdst[j] = 0;
@@ -151,6 +168,15 @@ __global__ void __launch_bounds__(kThreads) encode_kernel(EncodeArgs a)
     int pd[CPL], ctr[CPL];
 #pragma unroll
     for (int k = 0; k < CPL; k++) { pv[k] = 0; pd[k] = 0; ctr[k] = 0; }
+    float qinv[FSRC ? CPL : 1], qoff[FSRC ? CPL : 1];       // float source: the lane's columns' parameters, loaded once
+    if constexpr (FSRC) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            const int col = lane_d * CPL + k;
+            qinv[k] = col < D ? quant_inv_scale(a.q_inv, (uint32_t)col) : 1.0f;
+            qoff[k] = col < D ? quant_offset(a.q_off, (uint32_t)col) : 0.0f;
+        }
+    }
 
     auto start_group = [&]() {
         ngroups++;
@@ -170,7 +196,35 @@ __global__ void __launch_bounds__(kThreads) encode_kernel(EncodeArgs a)
         for (int k = 0; k < CPL; k++) {
             const int col = lane_d * CPL + k;
             uint32_t x[8];
-            if (cs) {
+            if constexpr (FSRC) {
+                const uint64_t e0 = first + (uint64_t)pos_in;
+                if (LOWDIM && D == 1) {
+                    // one column: the block's 8 samples are contiguous -- two loads of four float32, or one of eight 16-bit floats
+                    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+                    typedef v4 __attribute__((aligned(4), may_alias)) v4a4;
+                    typedef v4 __attribute__((aligned(2), may_alias)) v4a2;
+                    if (qfmt == kFloatF32) {
+                        const v4 t0 = *(const v4a4*)((const float*)a.src + e0), t1 = *(const v4a4*)((const float*)a.src + e0 + 4);
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const v4& t = i < 4 ? t0 : t1;
+                            const uint32_t b = (i & 3) == 0 ? t.x : (i & 3) == 1 ? t.y : (i & 3) == 2 ? t.z : t.w;
+                            x[i] = quant_value<W>(__uint_as_float(b), qinv[k], qoff[k], qmode);
+                        }
+                    } else {
+                        const v4 t = *(const v4a2*)((const uint16_t*)a.src + e0);
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const uint32_t b = (i >> 1) == 0 ? t.x : (i >> 1) == 1 ? t.y : (i >> 1) == 2 ? t.z : t.w;
+                            x[i] = quant_value<W>(quant_half_bits(b >> (16 * (i & 1)), qfmt), qinv[k], qoff[k], qmode);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        x[i] = (col < D) ? quant_value<W>(quant_load(a.src, qfmt, e0 + (uint64_t)(i * D + col)), qinv[k], qoff[k], qmode) : 0u;
+                }
+            } else if (cs) {
                 const U* const cp = cm0 + (uint64_t)col * cs + (uint32_t)pos_in / (uint32_t)D;
 #pragma unroll
                 for (int i = 0; i < 8; i++) x[i] = (col < D) ? (uint32_t)cp[i] : 0u;
@@ -281,11 +335,11 @@ __global__ void __launch_bounds__(kThreads) encode_kernel(EncodeArgs a)
             flush_to(wpos & ~15u);
             const uint32_t room = cap - (wpos - flushed);
             const uint32_t m = left < room ? left : room;
-            if (cs) {
+            if (FSRC || cs) {
                 const uint32_t done = remaining * ESZ - left;          // tail bytes already copied
                 for (uint32_t j = (uint32_t)lane_d; j < m; j += (uint32_t)DP) {
-                    const uint32_t tb = done + j;
-                    ring[(wpos + j) & capm] = (uint8_t)(elem((uint32_t)pos_in + tb / ESZ) >> (8u * (tb % ESZ)));
+                    const uint32_t tb = done + j, e = (uint32_t)pos_in + tb / ESZ;
+                    ring[(wpos + j) & capm] = (uint8_t)((FSRC ? qelem(e) : elem(e)) >> (8u * (tb % ESZ)));
                 }
             } else {
                 for (uint32_t j = (uint32_t)lane_d; j < m; j += (uint32_t)DP) ring[(wpos + j) & capm] = tp[j];

@@ -25,10 +25,16 @@ namespace sprintz {
 // DPT: lanes a chunk when that is not 64 (two columns per lane for NARROW streams too: 4 lanes for 5 .. 8 columns, 16 chunks a wavefront).
 // CM: column-major source (EncodeArgs::col_stride), as in encode_fast.h: a quad of lanes loads one column's 64 contiguous bytes
 // (four blocks; 32 bytes at 8 bits) one burst ahead, the pieces wait in LDS, and a lane takes its two columns' blocks from there.
-template <int W, bool FIRE, bool EXACT, bool SPLIT, int DPT, bool CM = false>
+// FSRC: a float source (quant.h), row-major: a 16-byte piece of elements is requested as the 1, 2 or 4 16-byte pieces of raw floats it is
+// made from, a block ahead as before, and is quantised where it is parked in LDS -- behind the wait, with the next block's request issued
+// right after, so that it stays in flight across this block's arithmetic.  A piece holds the same columns in every block (blocks and
+// chunks start rows), so the lane keeps their inverse scales and offsets; the format is wave-uniform.  The verbatim tail and chunks
+// shorter than 128 elements quantise element by element.
+template <int W, bool FIRE, bool EXACT, bool SPLIT, int DPT, bool CM = false, bool FSRC = false>
 __device__ __forceinline__ uint32_t encode_wide_body(const EncodeArgs& a, uint32_t wg_number)
 {
     static_assert(!(CM && SPLIT), "column-major sources: two columns per lane only");
+    static_assert(!(FSRC && CM), "float sources are row-major");
     constexpr int DP = SPLIT ? 32 : DPT, CPL = SPLIT ? 3 : 2;
     constexpr int LOG2DP = DP == 4 ? 2 : DP == 8 ? 3 : DP == 16 ? 4 : DP == 32 ? 5 : 6;
     static_assert(DP == 4 || DP == 8 || DP == 16 || DP == 32 || DP == 64, "lanes a chunk");
@@ -44,6 +50,16 @@ __device__ __forceinline__ uint32_t encode_wide_body(const EncodeArgs& a, uint32
     const uint64_t gtid = (uint64_t)wg_number * kThreads + threadIdx.x;
     const uint64_t chunk = gtid >> LOG2DP;
     const int lane_d = (int)(threadIdx.x & (uint32_t)(DP - 1));
+    // float source: the parameters of a block's 8 D elements, element by element -- [8 D] inverse scales, then [8 D] offsets -- behind the
+    // groups' carves, filled once a workgroup (every chunk of it has the same columns): a lane reads its piece's as whole 16-byte pieces
+    float* const qtab = (float*)(smem + (size_t)(kThreads >> LOG2DP) * a.lds_group_stride);
+    if constexpr (FSRC) {
+        for (uint32_t e = threadIdx.x; e < 8u * (uint32_t)D; e += kThreads) {
+            qtab[e] = quant_inv_scale(a.q_inv, e % (uint32_t)D);
+            qtab[8u * (uint32_t)D + e] = quant_offset(a.q_off, e % (uint32_t)D);
+        }
+        __syncthreads();
+    }
     if (chunk >= a.nchunks) return 0;
 
     const uint64_t first = chunk * (uint64_t)a.chunk_len;
@@ -173,12 +189,47 @@ __device__ __forceinline__ uint32_t encode_wide_body(const EncodeArgs& a, uint32
     uint32_t bno = 0;                                      // blocks taken so far (= pos_in / blk)
 
     uint4 nxt[PIECES];
+    // float source: a piece's raw floats (RAWN 16-byte pieces of float32, half as many of a 16-bit format) and its elements' parameters
+    constexpr int NE = 16 / ESZ, RAWN = 32 / W;
+    const uint32_t qmode = FSRC ? a.q_mode : 0u, qfmt = qmode & 3u, qsh = quant_src_shift(qmode);
+    const uint8_t* const fsc = (const uint8_t*)a.src + (first << qsh);
+    uint4 raw[FSRC ? PIECES : 1][RAWN];
+    // the piece at byte u of the block, quantised: its elements' parameters come from the workgroup's table (kept in registers they are
+    // 32 .. 64 more a lane: 130 .. 141 in all at 16 bits, 202 on the split mapping -- three waves a SIMD, or two, instead of four)
+    auto quantised = [&](int q, uint32_t u) {
+        float pin[NE], pof[NE];
+        const float4* const ti = (const float4*)(qtab + u / ESZ);
+        const float4* const to = (const float4*)(qtab + blk + u / ESZ);
+#pragma unroll
+        for (int j = 0; j < NE / 4; j++) {
+            const float4 vi = ti[j], vo = to[j];
+            pin[4 * j] = vi.x; pin[4 * j + 1] = vi.y; pin[4 * j + 2] = vi.z; pin[4 * j + 3] = vi.w;
+            pof[4 * j] = vo.x; pof[4 * j + 1] = vo.y; pof[4 * j + 2] = vo.z; pof[4 * j + 3] = vo.w;
+        }
+        return quant_piece<W>(raw[q], qmode, pin, pof);
+    };
     auto load_block = [&](int64_t pos) {
 #pragma unroll
         for (int q = 0; q < PIECES; q++) {
             const uint32_t u = lane16 + (uint32_t)q * DP * 16u;
-            nxt[q] = make_uint4(0, 0, 0, 0);
-            if (u < blk_bytes && pos + (int64_t)blk <= (int64_t)n) nxt[q] = *(const uint4*)((const uint8_t*)(sc + pos) + u);
+            if constexpr (FSRC) {                          // whole pieces of the block: nothing outside the chunk's n elements is read
+                const bool ok = u < blk_bytes && pos + (int64_t)blk <= (int64_t)n;
+                const uint8_t* const p = fsc + (((uint64_t)pos + u / ESZ) << qsh);
+#pragma unroll
+                for (int r = 0; r < RAWN; r++) raw[q][r] = make_uint4(0, 0, 0, 0);
+                if (ok) {
+                    if (qfmt == kFloatF32) {
+#pragma unroll
+                        for (int r = 0; r < RAWN; r++) raw[q][r] = *(const uint4*)(p + 16 * r);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < RAWN / 2; r++) raw[q][r] = *(const uint4*)(p + 16 * r);
+                    }
+                }
+            } else {
+                nxt[q] = make_uint4(0, 0, 0, 0);
+                if (u < blk_bytes && pos + (int64_t)blk <= (int64_t)n) nxt[q] = *(const uint4*)((const uint8_t*)(sc + pos) + u);
+            }
         }
     };
 
@@ -220,7 +271,11 @@ __device__ __forceinline__ uint32_t encode_wide_body(const EncodeArgs& a, uint32
 #pragma unroll
             for (int q = 0; q < PIECES; q++) {
                 const uint32_t u = lane16 + (uint32_t)q * DP * 16u;
-                if (u < blk_bytes) *(uint4*)(stage + u) = nxt[q];
+                if constexpr (FSRC) {
+                    if (u < blk_bytes) *(uint4*)(stage + u) = quantised(q, u);
+                } else {
+                    if (u < blk_bytes) *(uint4*)(stage + u) = nxt[q];
+                }
             }
             wave_lds_sync();
             load_block(pos_in + blk);
@@ -422,6 +477,13 @@ __device__ __forceinline__ uint32_t encode_wide_body(const EncodeArgs& a, uint32
                     const uint32_t xv = (uint32_t)cm0[(uint64_t)(e % (uint32_t)D) * a.col_stride + e / (uint32_t)D];
                     win[wl + j] = (uint8_t)(xv >> (8u * (tb % ESZ)));
                 }
+            } else if constexpr (FSRC) {                   // element by element: element e of the chunk is in column e % D
+                const uint32_t done = remaining * ESZ - left;
+                for (uint32_t j = (uint32_t)lane_d; j < m; j += DP) {
+                    const uint32_t tb = done + j, e = (uint32_t)pos_in + tb / ESZ, d = e % (uint32_t)D;
+                    const uint32_t xv = quant_value<W>(quant_load(a.src, qfmt, first + e), quant_inv_scale(a.q_inv, d), quant_offset(a.q_off, d), qmode);
+                    win[wl + j] = (uint8_t)(xv >> (8u * (tb % ESZ)));
+                }
             } else {
                 for (uint32_t j = (uint32_t)lane_d; j < m; j += DP) win[wl + j] = tp[j];
             }
@@ -459,6 +521,18 @@ __global__ void __launch_bounds__(kThreads) encode_wide_kernel(EncodeArgs a)
     const uint32_t wg = workgroup_number(a.dn);
     const uint32_t size = encode_wide_body<W, FIRE, EXACT, SPLIT, DPT, CM>(a, wg);
     // the container, built before the workgroup leaves (compact_tail.h); without it the caller compacts the slots
+    if (a.dn.dense) dense_tail(a.dn, wg, a.nchunks, LOG2DP, size, a.slots, a.slot_stride, smem, a.lds_group_stride);
+}
+
+// the same kernels on a float source (FSRC), the dense tail behind the body unchanged
+template <int W, bool FIRE, bool EXACT, bool SPLIT = false, int DPT = 64>
+__global__ void __launch_bounds__(kThreads) encode_wide_float_kernel(EncodeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr int DP = SPLIT ? 32 : DPT;
+    constexpr uint32_t LOG2DP = DP == 4 ? 2 : DP == 8 ? 3 : DP == 16 ? 4 : DP == 32 ? 5 : 6;
+    const uint32_t wg = workgroup_number(a.dn);
+    const uint32_t size = encode_wide_body<W, FIRE, EXACT, SPLIT, DPT, false, true>(a, wg);
     if (a.dn.dense) dense_tail(a.dn, wg, a.nchunks, LOG2DP, size, a.slots, a.slot_stride, smem, a.lds_group_stride);
 }
 

@@ -69,6 +69,12 @@ struct EncodeBatch {
     int write_size = 1;
     uint64_t col_stride = 0;    // != 0: column-major source
     int general = 0;            // 1: general row-major layout for every ndims
+    // a float source (quant.h): src holds float32 / float16 / bfloat16, quantised with the columns' inverse scales and offsets
+    // (null: all 1 / all 0) under q_mode -- the format, kFloatSignedBit, kQuantFloorBit
+    bool fsrc = false;
+    const float* q_inv = nullptr;
+    const float* q_off = nullptr;
+    uint32_t q_mode = 0;
 };
 // where the encode launch builds the dense container itself (compact_tail.h; Plan::fused)
 struct DenseRequest { void* d_dense; uint64_t* d_offsets; void* d_tmp; };

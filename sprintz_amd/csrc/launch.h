@@ -69,6 +69,11 @@ hipError_t launch_encode_fast_w16(bool fire, int dp, bool exact, unsigned grid, 
 hipError_t launch_encode_w8(bool fire, bool lowdim, int cpl, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
 hipError_t launch_encode_w16(bool fire, bool lowdim, int cpl, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
 
+// a float source quantised in the encoder (quant.h; encode_float_w8.hip / encode_float_w16.hip): the family's kernel of encode_wide.h
+// (SPRINTZ_KF_ENC_PAIR with dp lanes a chunk, _ENC_WIDE, _ENC_SPLIT) or the generic one (SPRINTZ_KF_ENC_GENERIC: lowdim, cpl)
+hipError_t launch_encode_float_w8(int family, bool fire, bool lowdim, int cpl, int dp, bool exact, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
+hipError_t launch_encode_float_w16(int family, bool fire, bool lowdim, int cpl, int dp, bool exact, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a);
+
 template <typename K, typename A>
 inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t st, const A& a)
 {
@@ -81,29 +86,32 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
     return hipGetLastError();
 }
 
-#define SPRINTZ_DISPATCH_ENC(KERNEL, W)                                                               \
+// (trailing arguments: the kernel template's further parameters -- encode_kernel's FSRC)
+#define SPRINTZ_DISPATCH_ENC_T(KERNEL, W, ...)                                                                                    \
     if (lowdim) {                                                                                     \
         if (cpl != 1) return hipErrorInvalidValue;                                                    \
-        return fire ? launch_one(KERNEL<W, true, true, 1>, grid, shmem, st, a)                        \
-                    : launch_one(KERNEL<W, false, true, 1>, grid, shmem, st, a);                      \
+        return fire ? launch_one(KERNEL<W, true, true, 1, ##__VA_ARGS__>, grid, shmem, st, a)                                     \
+                    : launch_one(KERNEL<W, false, true, 1, ##__VA_ARGS__>, grid, shmem, st, a);                                   \
     }                                                                                                 \
     switch (cpl) {                                                                                    \
-        case 1: return fire ? launch_one(KERNEL<W, true, false, 1>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 1>, grid, shmem, st, a);             \
-        case 2: return fire ? launch_one(KERNEL<W, true, false, 2>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 2>, grid, shmem, st, a);             \
-        case 3: return fire ? launch_one(KERNEL<W, true, false, 3>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 3>, grid, shmem, st, a);             \
-        case 4: return fire ? launch_one(KERNEL<W, true, false, 4>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 4>, grid, shmem, st, a);             \
-        case 5: return fire ? launch_one(KERNEL<W, true, false, 5>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 5>, grid, shmem, st, a);             \
-        case 6: return fire ? launch_one(KERNEL<W, true, false, 6>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 6>, grid, shmem, st, a);             \
-        case 8: return fire ? launch_one(KERNEL<W, true, false, 8>, grid, shmem, st, a)               \
-                            : launch_one(KERNEL<W, false, false, 8>, grid, shmem, st, a);             \
+        case 1: return fire ? launch_one(KERNEL<W, true, false, 1, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 1, ##__VA_ARGS__>, grid, shmem, st, a);                          \
+        case 2: return fire ? launch_one(KERNEL<W, true, false, 2, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 2, ##__VA_ARGS__>, grid, shmem, st, a);                          \
+        case 3: return fire ? launch_one(KERNEL<W, true, false, 3, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 3, ##__VA_ARGS__>, grid, shmem, st, a);                          \
+        case 4: return fire ? launch_one(KERNEL<W, true, false, 4, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 4, ##__VA_ARGS__>, grid, shmem, st, a);                          \
+        case 5: return fire ? launch_one(KERNEL<W, true, false, 5, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 5, ##__VA_ARGS__>, grid, shmem, st, a);                          \
+        case 6: return fire ? launch_one(KERNEL<W, true, false, 6, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 6, ##__VA_ARGS__>, grid, shmem, st, a);                          \
+        case 8: return fire ? launch_one(KERNEL<W, true, false, 8, ##__VA_ARGS__>, grid, shmem, st, a)                            \
+                            : launch_one(KERNEL<W, false, false, 8, ##__VA_ARGS__>, grid, shmem, st, a);                          \
         default: return hipErrorInvalidValue;                                                         \
     }
+
+#define SPRINTZ_DISPATCH_ENC(KERNEL, W) SPRINTZ_DISPATCH_ENC_T(KERNEL, W)
 
 #define SPRINTZ_DISPATCH_Q(KERNEL, W, Q)                                                              \
     if (lowdim) {                                                                                     \
@@ -227,5 +235,42 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
 #define SPRINTZ_DISPATCH_FAST(KERNEL, W)                                                              \
     if (a.col_stride) { SPRINTZ_DISPATCH_FAST_CM(KERNEL, W, true) }                                   \
     SPRINTZ_DISPATCH_FAST_CM(KERNEL, W, false)
+
+// a float source's translation unit: the float-source instantiations of encode_wide.h and of the generic encoder for one width
+#define SPRINTZ_FLOAT_PAIR_CASE(W, DPV)                                                                                           \
+    case DPV:                                                                                                                      \
+        if (exact) return fire ? launch_one(encode_wide_float_kernel<W, true, true, false, DPV>, grid, shmem, st, a)               \
+                               : launch_one(encode_wide_float_kernel<W, false, true, false, DPV>, grid, shmem, st, a);             \
+        return fire ? launch_one(encode_wide_float_kernel<W, true, false, false, DPV>, grid, shmem, st, a)                         \
+                    : launch_one(encode_wide_float_kernel<W, false, false, false, DPV>, grid, shmem, st, a);
+#define SPRINTZ_FLOAT_SPLIT_8                                                                                                      \
+    return fire ? launch_one(encode_wide_float_kernel<8, true, false, true>, grid, shmem, st, a)                                   \
+                : launch_one(encode_wide_float_kernel<8, false, false, true>, grid, shmem, st, a);
+#define SPRINTZ_FLOAT_SPLIT_16 return hipErrorInvalidValue;      /* (the split mapping is built for 8-bit streams) */
+#define SPRINTZ_ENCODE_FLOAT_UNIT(W)                                                                                              \
+    namespace sprintz {                                                                                                            \
+    hipError_t launch_encode_float_w##W(int family, bool fire, bool lowdim, int cpl, int dp, bool exact, unsigned grid, size_t shmem, hipStream_t st, const EncodeArgs& a) \
+    {                                                                                                                              \
+        if (a.col_stride || a.norle || a.raw) return hipErrorInvalidValue;                                                         \
+        if (family == SPRINTZ_KF_ENC_PAIR) {                                                                                       \
+            switch (dp) {                                                                                                          \
+                SPRINTZ_FLOAT_PAIR_CASE(W, 4)                                                                                      \
+                SPRINTZ_FLOAT_PAIR_CASE(W, 8)                                                                                      \
+                SPRINTZ_FLOAT_PAIR_CASE(W, 16)                                                                                     \
+                SPRINTZ_FLOAT_PAIR_CASE(W, 32)                                                                                     \
+                default: return hipErrorInvalidValue;                                                                              \
+            }                                                                                                                      \
+        }                                                                                                                          \
+        if (family == SPRINTZ_KF_ENC_WIDE) {                                                                                       \
+            switch (dp) {                                                                                                          \
+                SPRINTZ_FLOAT_PAIR_CASE(W, 64)                                                                                     \
+                default: return hipErrorInvalidValue;                                                                              \
+            }                                                                                                                      \
+        }                                                                                                                          \
+        if (family == SPRINTZ_KF_ENC_SPLIT) { SPRINTZ_FLOAT_SPLIT_##W }                                                            \
+        if (family != SPRINTZ_KF_ENC_GENERIC) return hipErrorInvalidValue;                                                         \
+        SPRINTZ_DISPATCH_ENC_T(encode_kernel, W, true)                                                                            \
+    }                                                                                                                              \
+    }
 
 }  // namespace sprintz

@@ -46,8 +46,8 @@ struct Shape {
     // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
     // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
     uint32_t table_entries = 0, table_row_max = 0;
-    // float rows: the bytes of an output element (4, or 2 for float16 / bfloat16) -- what every bound on output BYTES counts in; 0: the mode
-    // stores elements of esz bytes, or nothing
+    // the element bytes on the float side (4, or 2 for float16 / bfloat16): float rows' output element -- what every bound on output BYTES
+    // counts in -- and, for an encode with q == kQueryFloat, the float source's element; 0: the call has no float side
     int out_esz = 0;
 };
 
@@ -345,6 +345,12 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
     p.cpl = m.cpl;
     p.norle = norle ? (codec == SPRINTZ_CODEC_XFF_NORLE ? 2 : 1) : 0;
     p.raw = codec == SPRINTZ_CODEC_BITPACK_NORLE ? 1 : 0;
+    // a float source (q == kQueryFloat, out_esz the bytes of a source float; quant.h): only the kernels that are taught to quantise while they
+    // load -- encode_wide.h's (enc_pair, enc_wide, enc_split) and the generic one -- for the RLE codecs, row-major, up to 512 columns
+    const bool flt = s.q == kQueryFloat;
+    // (encode_wide.h keeps the parameters of a block's 8 D elements in LDS, once a workgroup, behind the groups' carves: 64 D bytes)
+    const uint64_t qtab = flt ? 64ull * (uint64_t)D : 0;
+    if (flt && (D > 512 || norle || col_stride)) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "a float source: the RLE codecs, row-major, at most 512 columns");
     // 513 .. 2047 columns: one workgroup per chunk, the window holds one stream group (any_ndims.hip)
     if (D > 512) {
         if (norle || col_stride) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "more than 512 columns: the RLE codecs, row-major only");
@@ -377,7 +383,7 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
     // small batches: one WORKGROUP per chunk (encode_lat.h), the counterpart of decode_lat.h -- 90 us for ONE 10 KB chunk on a lane
     // group, ~20 with the coefficient chain and the RLE state machine as the only serial parts (the container, if one was asked
     // for, is then built by the scan + copy passes: fused stays false)
-    if (!norle && !col_stride && D <= 64 && lat_chunk_fits(true, esz, nchunks, chunk_len, D) &&
+    if (!flt && !norle && !col_stride && D <= 64 && lat_chunk_fits(true, esz, nchunks, chunk_len, D) &&
         (s.src_lo % 16) == 0 && (nchunks == 1 || ((uint64_t)chunk_len * esz) % 16 == 0) && s.slot_stride % 16 == 0 && (s.slots_lo % 16) == 0 &&
         // (a chunk is read in 16-byte pieces from a 16-byte aligned start: the last piece may reach past its end, never past the piece that holds its last byte)
         // (the encoder's crossover sits higher than the decoder's -- the lane-per-column encoders take ~100 us (uint16 x 8) / ~175 us (uint8 x 8)
@@ -401,7 +407,7 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
     //  them and add their size to their block's word; the block's last finisher finds the block's place (a look-back over a few hundred blocks) and
     //  copies it.  The encoder's side alone (the stores, the s_waitcnt, one atomic a chunk; no placement at all) measured 0.302 against 0.270 ms for
     //  the whole compress call: a third of the 0.098 ms the scan + copy launches cost is gone before the placers' copies and the last block's tail.)
-    if (k.blk_chunks > 0 && (k.blk_kernels & 1) && nchunks >= (uint64_t)k.blk_chunks && codec == SPRINTZ_CODEC_DELTA && !lowdim && !col_stride && !s.host_call && s.write_size &&
+    if (!flt && k.blk_chunks > 0 && (k.blk_kernels & 1) && nchunks >= (uint64_t)k.blk_chunks && codec == SPRINTZ_CODEC_DELTA && !lowdim && !col_stride && !s.host_call && s.write_size &&
         (s.src_lo % 16) == 0 && s.slot_stride % 16 == 0 && (s.slots_lo % 16) == 0 && !k.no_fast) {
         const BlkEncGeom g = blk_enc_geom((uint32_t)esz, chunk_len, (uint32_t)D, (uint32_t)compress_bound(esz, chunk_len, (uint16_t)D));
         if (g.ok) {
@@ -410,7 +416,7 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
         }
     }
     // the same for univariate streams of the low-dim layout (BASELINE config 1): a thread per 16 bytes of the series
-    if (k.blk_chunks > 0 && (k.blk_kernels & 4) && nchunks >= (uint64_t)k.blk_chunks && codec == SPRINTZ_CODEC_DELTA && lowdim && D == 1 && !col_stride && !s.host_call && s.write_size &&
+    if (!flt && k.blk_chunks > 0 && (k.blk_kernels & 4) && nchunks >= (uint64_t)k.blk_chunks && codec == SPRINTZ_CODEC_DELTA && lowdim && D == 1 && !col_stride && !s.host_call && s.write_size &&
         (s.src_lo % 16) == 0 && s.slot_stride % 16 == 0 && (s.slots_lo % 16) == 0 && !k.no_fast) {
         const BlkEncGeom g = blk_enc_uni_geom((uint32_t)esz, chunk_len, (uint32_t)compress_bound(esz, chunk_len, (uint16_t)D));
         if (g.ok) {
@@ -431,7 +437,8 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
     // (column-major sources too: encode_fast.h's bursts, two columns' blocks per lane)
     const bool pair_layout = col_stride ? col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0
                                         : blk_bytes % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0;
-    if (k.enc_pair > 0 && nchunks >= (uint64_t)k.enc_pair && fast_common && D >= 5 && pair_layout && (uint64_t)chunk_len * esz >= 2 * blk_bytes) {
+    // (a float source takes it whatever SPRINTZ_OPT_ENC_PAIR says: nothing else serves its small batches fast)
+    if ((flt || (k.enc_pair > 0 && nchunks >= (uint64_t)k.enc_pair)) && fast_common && D >= 5 && pair_layout && (uint64_t)chunk_len * esz >= 2 * blk_bytes) {
         int pdp = 4;
         while (2 * pdp < D) pdp <<= 1;
         const size_t pgroups = kThreads / pdp;
@@ -445,9 +452,9 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
         p.dp = pdp;
         p.exact = D == 2 * pdp;
         p.fused = fuses(pgroups);
-        return plan_take(p, SPRINTZ_KF_ENC_PAIR, (nchunks * (uint64_t)pdp + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * pgroups);
+        return plan_take(p, SPRINTZ_KF_ENC_PAIR, (nchunks * (uint64_t)pdp + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * pgroups + qtab);
     }
-    if (fast) {
+    if (fast && !flt) {
         const size_t fgroups = kThreads / fdp;
         p.cap = cap_drain;
         // input staging: one 8 x D block (row-major: LDS transpose) or two bursts of 4 blocks x fdp columns (column-major)
@@ -469,14 +476,14 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
         p.dp = (int)wlanes;
         p.exact = D == 128;
         p.fused = fuses(wgroups);
-        return plan_take(p, wsplit ? SPRINTZ_KF_ENC_SPLIT : SPRINTZ_KF_ENC_WIDE, (nchunks * (uint64_t)wlanes + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * wgroups);
+        return plan_take(p, wsplit ? SPRINTZ_KF_ENC_SPLIT : SPRINTZ_KF_ENC_WIDE, (nchunks * (uint64_t)wlanes + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * wgroups + qtab);
     }
     // univariate streams: one lane per chunk, quad-loaded 64-byte input windows, 64-byte output units (encode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
     // (round 6: the container inside THIS launch was built too -- 256 chunks a workgroup, 2 048 workgroups on BASELINE config 1, a short chain --
     //  and measured: 0.405 ms with a lane-parallel copy (a piece's chunk found by bisection), 0.49 - 0.51 chunk by chunk, against 0.3945 for
     //  encode + scan + copy in a row: streams of ~440 bytes re-read from their slots cost the workgroup what the copy pass costs.  Not kept.)
-    if (lowdim && (D <= 2 || esz == 1) && !col_stride && !k.no_fast) return plan_take(p, SPRINTZ_KF_ENC_UNI, (nchunks + 255) / 256, 0);
+    if (!flt && lowdim && (D <= 2 || esz == 1) && !col_stride && !k.no_fast) return plan_take(p, SPRINTZ_KF_ENC_UNI, (nchunks + 255) / 256, 0);
     return plan_take(p, SPRINTZ_KF_ENC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, shmem);
 }
 
@@ -489,7 +496,8 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
 inline Plan plan_dense(const Shape& s, const Knobs& k, Plan* enc)
 {
     Plan p;
-    if (k.dense_mode && (s.codec == SPRINTZ_CODEC_DELTA || s.codec == SPRINTZ_CODEC_XFF) && !is_lowdim(s.esz, s.D) &&
+    // (never for a float source: the verbatim kernel copies raw source bytes -- such chunks go through the encoder's own tail)
+    if (s.q != kQueryFloat && k.dense_mode && (s.codec == SPRINTZ_CODEC_DELTA || s.codec == SPRINTZ_CODEC_XFF) && !is_lowdim(s.esz, s.D) &&
         (s.chunk_len < 128u || s.chunk_len < 16u * (uint32_t)s.D) && s.chunk_len <= 0xffffu)
         return plan_take(p, SPRINTZ_KF_DENSE_VERBATIM, (s.nchunks * 64 + kThreads - 1) / kThreads, 0);
     Shape se = s;

@@ -1,6 +1,6 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
 moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, the default bin shift, bounds and offsets as tensors, the
+fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, the default bin shift, bounds and offsets as tensors, the
 linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
@@ -205,6 +205,36 @@ def float_params(v, ndims, name, device):
     if not np.all(np.isfinite(a)) or not np.all(np.isfinite(a32)):
         raise ValueError(f"{name} must be finite in float32")
     return torch.from_numpy(a32).to(device)
+
+
+def quant_params(scale, offset, ndims, device):
+    """compress_floats' parameters from float_rows' (scale, offset) -> (inv_scale, offset): contiguous float32 tensors [ndims] on `device`,
+    or None where the argument is None (the library's all 1 / all 0).  scale / offset: a number, a sequence of ndims numbers or a tensor
+    of ndims elements.  inv_scale = 1 / scale, one float32 division an entry.  A scale that is zero or not finite -- or so small that its
+    reciprocal is not finite in float32 -- is a ValueError, as is an offset that is not finite."""
+    off = float_params(offset, ndims, "offset", device)
+    if off is not None and torch.is_tensor(offset) and not bool(torch.isfinite(off).all()):
+        raise ValueError("offset must be finite in float32")
+    if scale is None:
+        return None, off
+    if torch.is_tensor(scale):
+        if scale.numel() != ndims:
+            raise ValueError(f"scale must have {ndims} entries, not {scale.numel()}")
+        s = scale.reshape(-1).to(dtype=torch.float32)
+    else:
+        a = np.asarray(scale, dtype=np.float64).reshape(-1)
+        if a.size == 1:
+            a = np.repeat(a, ndims)
+        if a.size != ndims:
+            raise ValueError(f"scale must be a number or have {ndims} entries, not {a.size}")
+        with np.errstate(over="ignore"):
+            s = torch.from_numpy(a.astype(np.float32))
+    if not bool(torch.isfinite(s).all()) or bool((s == 0).any()):
+        raise ValueError("scale must be finite in float32 and not zero")
+    inv = torch.ones_like(s) / s
+    if not bool(torch.isfinite(inv).all()):
+        raise ValueError("1 / scale must be finite in float32")
+    return inv.to(device).contiguous(), off
 
 
 def default_shift(W, nbins):
