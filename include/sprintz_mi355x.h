@@ -53,7 +53,8 @@ extern "C" {
  *      dispatch_counts / dispatch_name, SPRINTZ_KF_*; filter_rows / filter_row_ids, SPRINTZ_FILTER_ALL / _ANY; select_rows; aggregate_rows, SPRINTZ_AGG_*;
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
  *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
- *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR */
+ *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR;
+ *      rolling_rows, SPRINTZ_ROLL_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -985,6 +986,38 @@ int sprintz_mi355x_compress_batch_float_dense(int codec, int elem_bytes, const v
                                               const float* d_offset, uint32_t flags, uint64_t total_len, uint32_t chunk_len, uint16_t ndims,
                                               void* d_slots, size_t slot_stride, uint32_t* d_sizes, int64_t* d_rets, void* d_dense,
                                               uint64_t* d_offsets, void* d_tmp, void* hip_stream);
+/* Rolling rows: per element, its column's minimum / maximum / sum over the window_rows rows that END at its row -- pandas' rolling(W,
+ * min_periods=1) -- straight from the compressed batch; the decoded tensor never exists.  The batch is given as to
+ * sprintz_mi355x_select_rows (chunk_len % ndims == 0; the RLE codecs; at most 512 columns; a short last chunk may end mid-row).  The batch's
+ * rows are g = 0 .. G - 1, row g being row g % R of chunk g / R, R = chunk_len / ndims.  For every element that exists, in row g and column d:
+ *   out[g, d] = op(x[max(0, g - W + 1) .. g, d])          a trailing window, clipped at the batch's first row
+ * with op the unsigned minimum / maximum in the element type (d_min, d_max) or the sum as an int32 (d_sum), placed where decompress_batch
+ * places the element: element e of chunk c at out[c * chunk_len + e]; nothing is written past a chunk's decoded count.  A mean is the sum
+ * divided by the row's count min(g + 1, W).
+ *   window_rows: W, a multiple of 8 with 8 <= W <= R (one predecessor chunk suffices at a seam) and W * (2^(8 elem_bytes) - 1) < 2^31.
+ *                A chunk's last W + 8 rows wait in LDS: where the rings of the chunks a workgroup decodes do not fit its 160 KB, the call
+ *                returns SPRINTZ_E_UNSUPPORTED and sprintz_mi355x_last_error names the largest window_rows the shape allows.
+ *   ops        : a non-empty OR of SPRINTZ_ROLL_MIN / _MAX / _SUM; an output must be given exactly where its op is
+ *   flags      : SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else
+ *   d_tmp      : with nchunks > 1, scratch of nchunks * stride bytes, 16-byte aligned, stride = (16 + (W - 1) * ndims * elem_bytes + 15) & ~15
+ *                (roll_tmp_stride in geom.h): a chunk leaves its element count and its last W - 1 rows there.  Its content before the call
+ *                does not matter.  Ignored (may be NULL) with one chunk.
+ *   d_rets     : (optional) exactly what sprintz_mi355x_decompress_batch writes for the same batch, damaged chunks included
+ * Two launches on the stream -- the decode (SPRINTZ_KF_DEC_FAST for rows of whole 16-byte pieces of 8 .. 64 columns with every output 16-byte aligned,
+ * while the rings fit its LDS budget; SPRINTZ_KF_DEC_GENERIC otherwise), in which a chunk is its own beginning, and with
+ * nchunks > 1 a seam pass that takes the last rows of the chunk in front into the windows of each chunk's first W - 1 rows -- no
+ * synchronisation, no allocation.  A chunk behind a damaged one keeps its chunk-local windows: exact from its row W - 1 on.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown flag, a
+ * window_rows that is no multiple of 8, below 8, above R or too large for the int32 sum, ops outside 1..7, an op without its output or an
+ * output without its op, d_min / d_max not aligned to the element size, d_sum to 4 bytes, d_rets to 8, d_tmp missing or not aligned to 16
+ * with nchunks > 1; SPRINTZ_E_UNSUPPORTED for more than 512 columns, the non-RLE codecs and a window beyond the LDS bound.  nchunks == 0
+ * returns 0 and launches nothing. */
+#define SPRINTZ_ROLL_MIN 1u
+#define SPRINTZ_ROLL_MAX 2u
+#define SPRINTZ_ROLL_SUM 4u
+int sprintz_mi355x_rolling_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
+                                void* d_min, void* d_max, int32_t* d_sum, void* d_tmp, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

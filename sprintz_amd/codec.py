@@ -726,6 +726,49 @@ class ChunkedCodec:
         res = out.view(-1)[: batch.total_len]
         return res.view(-1, D) if batch.total_len % D == 0 else res
 
+    def rolling_rows(self, batch, window_rows, ops=("min", "max", "sum"), general_layout=False, check=True):
+        """Sliding-window min / max / sum / mean of every column, one result per row -- pandas' rolling(window_rows, min_periods=1) --
+        straight from the compressed batch: the decoded tensor never exists.  Batch row g is row g % R of chunk g // R, R = chunk_len /
+        ndims (chunk_len must be a multiple of ndims), and out[g, d] = op(x[max(0, g - W + 1) .. g, d]): a trailing window, clipped at the
+        batch's first row.
+
+        window_rows: W, a multiple of 8 with 8 <= W <= R (rowops.rolling_window); the library refuses a window whose history does not fit
+        the kernel's LDS and names the largest it takes.  ops: any of "min", "max" (the codec's dtype), "sum" (int32) and "mean" (float32:
+        the sum launch plus one divide by the row's count min(g + 1, W)).
+        -> {op: [G, ndims]}, G = ceil(total_len / ndims); the columns a partial last row lacks hold 0.  One library call: the decode and,
+        with more than one chunk, its seam pass.  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        ops = rowops.normalise_ops(ops, rowops.ROLLING_OPS, '"min", "max", "sum", "mean"')
+        D, n = self.ndims, batch.nchunks
+        R, _ = rowops.chunk_rows(self.chunk_len, D, "rolling_rows")
+        W = rowops.rolling_window(window_rows, R, self.esz)
+        G = -(-batch.total_len // D)
+        want_sum = "sum" in ops or "mean" in ops
+        bits = (_lib.ROLL_MIN if "min" in ops else 0) | (_lib.ROLL_MAX if "max" in ops else 0) | (_lib.ROLL_SUM if want_sum else 0)
+        raw = {}
+        for name, dt in (("min", self.dtype), ("max", self.dtype), ("sum", torch.int32)):
+            if name in ops or (name == "sum" and want_sum):
+                raw[name] = torch.empty(max(n * self.chunk_len, 1), dtype=dt, device=self.device)
+        tmp = torch.empty(max(rowops.rolling_tmp_bytes(n, W, D, self.esz) // 16, 1) * 2, dtype=torch.int64, device=self.device)
+        rets = self._rets(n, check)
+        if n:
+            with self._on():
+                _lib.check(_lib.rolling_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n, self.chunk_len, D,
+                                             W, bits, self._general(general_layout), _ptr(raw.get("min")), _ptr(raw.get("max")), _ptr(raw.get("sum")),
+                                             tmp.data_ptr(), _ptr(rets), self._stream()))
+            if check:
+                rowops.raise_damaged("rolling_rows", rets, n, _lib.SprintzError)
+        res = {}
+        for name, v in raw.items():
+            v = v[: G * D]
+            v[batch.total_len:] = 0
+            res[name] = v.view(G, D)
+        if "mean" in ops:
+            res["mean"] = rowops.rolling_mean(res["sum"], rowops.rolling_counts(G, W, self.device))
+            if "sum" not in ops:
+                del res["sum"]
+        return {k: res[k] for k in ops}
+
     def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False, zones=None):
         """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
         filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.

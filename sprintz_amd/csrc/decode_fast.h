@@ -174,6 +174,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // descriptor's base and span, the cursor ovo -- uses the output element's size OSZ, not ESZ.
     constexpr bool FLT = Q == kQueryFloat;
     static_assert(!FLT || (!CM && !SPLIT && DS == 0), "float rows: row-major destination, plain mappings");
+    // ROLL (sprintz_mi355x_rolling_rows): nothing of the raw block is stored.  A column's 8 rows wait in arow for q_block, which runs the rolling
+    // step on the chunk's history ring -- behind the groups' carves, at a.table.table_off -- and keeps the block's results in registers (rres);
+    // behind the columns roll_out sends them through the plain decode's staging, one plane at a time, and out as 16-byte pieces: the minima and
+    // the maxima as element-type planes to their own outputs, the sum as 32 / W element-type planes (its bytes, low first) that are joined into
+    // 32-bit pieces where float rows convert theirs.  The pieces are stored at once (no held slots: three outputs would triple them).
+    constexpr bool ROLL = Q == kQueryRolling;
+    static_assert(!ROLL || (!CM && !SPLIT && DS == 0 && CPL == 1), "rolling rows: row-major destination, one column a lane (with 2 and 4 hipcc put the block's results in scratch)");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
     constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -225,6 +232,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint8_t* const ringp = smem + (size_t)(threadIdx.x >> LOG2DP) * a.lds_group_stride;
     const uint32_t ring = lds_addr(ringp);                 // LDS byte address of the ring
     uint8_t* const stage = ringp + RB + APRON;
+    // rolling rows: the chunk's history ring (decode_ops.h: rolling_ring), a ring a group behind every group's carve
+    uint8_t* rollp = nullptr;
+    if constexpr (ROLL) rollp = smem + a.table.table_off + (size_t)(threadIdx.x >> LOG2DP) * (size_t)roll_ring_bytes(a.win.rows, D, ESZ);
 
     // stream geometry.  All stream loads go through ONE wave-uniform buffer
     // descriptor that spans the container from this wavefront's first stream to its
@@ -447,10 +457,20 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         for (int k = 0; k < CPL; k++) lc[k] = linear_col(a, genk[k], col_ok[k]);
         lctx = linear_ctx(a);
     }
+    // rolling rows: each column's running sum, the chunk's blocks done, the delta-run blocks behind this one in a row, is this block one of a run,
+    // and the block's results -- [0] minima, [1] maxima, [2] sums -- of every column of the lane
+    uint32_t rsum[ROLL ? CPL : 1];
+    uint32_t rblk = 0, rrun = 0;
+    bool rinrun = false;
+    uint32_t rres[ROLL ? 3 : 1][ROLL ? CPL : 1][8];
+    if constexpr (ROLL) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) rsum[k] = 0;
+    }
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST || EXT || LIN || SEG) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -501,6 +521,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         } else if constexpr (LIN) {                        // (a lane column past the last one has weights 0; the chunk's first row leaves for the seam pass)
             if (lctx.lag && lfirst && col_ok[k]) linear_slot<W>(a, lchunk, (uint32_t)D).first[genk[k]] = (U)arow[0];
             linear_rows8<W>(lc[k], [&](int i) { return arow[i]; }, lctx.lag, lfirst, lacc, lself, lnext);
+        } else if constexpr (ROLL) {                       // (a lane column past the last one has no ring and no results)
+            if (col_ok[k])
+                rolling_step8<W>(a, rolling_ring<W>(rollp, a, (uint32_t)genk[k]), rblk, [&](int i) { return arow[i]; }, rsum[ROLL ? k : 0],
+                                 !FIRE && SPRINTZ_ROLL_RUN_SHORTCUT && rinrun && rolling_run_settled(a, rrun),
+                                 [&](uint32_t op, int j, uint32_t v) { rres[op == kRollMin ? 0 : op == kRollMax ? 1 : 2][k][j] = v; });
         } else if constexpr (MOM || GBY) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
@@ -754,8 +779,82 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
     };
+    // rolling rows: the block's results leave.  A plane is staged as the plain decode stages a block -- row i of column c at stage + i * row_stride +
+    // c * ESZ -- and read back as this lane's 16-byte pieces; `run`: the block was one of a run
+    auto roll_plane = [&](int which, uint32_t shift) __attribute__((always_inline)) {
+        wave_lds_sync();                                   // (the pieces of the plane before have been read)
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            if (!col_ok[k]) continue;
+#pragma unroll
+            for (int i = 0; i < 8; i++) *(U*)(stage_k[k] + i * row_stride) = (U)(rres[ROLL ? which : 0][ROLL ? k : 0][i] >> shift);
+        }
+        wave_lds_sync();
+    };
+    auto roll_out = [&](bool run) __attribute__((always_inline)) {
+        if constexpr (ROLL) {
+            // a descriptor an output, based like orsrc (wave-uniform: hipcc hoists them out of the step); the sum's counts 4 bytes an element
+            // (rfs: element bytes -> sum bytes, as a shift)
+            constexpr uint32_t rfs = ESZ == 1 ? 2u : 1u;
+            const uint32_t rspan = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(out_span < 0xfffffff0ull ? out_span : 0xfffffff0ull));
+            const uint32_t rspan4 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((out_span << rfs) < 0xfffffff0ull ? (out_span << rfs) : 0xfffffff0ull));
+            const __amdgpu_buffer_rsrc_t rrs_min = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.win.min + wave_uniform64(out_base)), 0, rspan, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rrs_max = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.win.max + wave_uniform64(out_base)), 0, rspan, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rrs_sum = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.win.sum + wave_uniform64(out_base << rfs)), 0, rspan4, 0x00020000);
+#pragma unroll
+            for (int op = 0; op < 2; op++) {
+                if (!(a.win.ops & (op == 0 ? kRollMin : kRollMax))) continue;
+                roll_plane(op, 0u);
+#pragma unroll
+                for (int q = 0; q < PIECES; q++) {
+                    const uint32_t u = lane16 + q * ROW16;
+                    const bool in = u < blk_bytes;
+                    const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), op == 0 ? rrs_min : rrs_max, in ? ovo + u : kDropStore, 0, kStoreAux);
+                }
+            }
+            if (a.win.ops & kRollSum) {
+                constexpr int NP = 32 / W, NE = 128 / W;   // planes of a sum, elements of a piece
+                uint4 pl[NP][PIECES];
+#pragma unroll
+                for (int p = 0; p < NP; p++) {
+                    roll_plane(2, (uint32_t)(W * p));
+#pragma unroll
+                    for (int q = 0; q < PIECES; q++) {
+                        const uint32_t u = lane16 + q * ROW16;
+                        pl[p][q] = *(const uint4*)(stage + (u < blk_bytes ? u : 0u));
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < PIECES; q++) {
+                    const uint32_t u = lane16 + q * ROW16;
+                    const bool in = u < blk_bytes;
+                    uint32_t z[NE];
+#pragma unroll
+                    for (int e = 0; e < NE; e++) {
+                        z[e] = 0;
+#pragma unroll
+                        for (int p = 0; p < NP; p++) {
+                            const uint32_t w4[4] = {pl[p][q].x, pl[p][q].y, pl[p][q].z, pl[p][q].w};
+                            const uint32_t part = W == 16 ? (w4[e >> 1] >> (16 * (e & 1))) & 0xffffu : (w4[e >> 2] >> (8 * (e & 3))) & 0xffu;
+                            z[e] |= part << (W * p);
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < NE / 4; j++) {
+                        const uint4 t = make_uint4(z[4 * j], z[4 * j + 1], z[4 * j + 2], z[4 * j + 3]);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), rrs_sum, in ? ((ovo + u) << rfs) + 16u * (uint32_t)j : kDropStore, 0, kStoreAux);
+                    }
+                }
+            }
+            ovo += blk_bytes;
+            rblk++;
+            rrun = (!FIRE && run) ? rrun + 1u : 0u;
+        }
+    };
     auto stage_out = [&](int slot) {
         if constexpr (query_reduce_only(Q)) return;
+        if constexpr (ROLL) { roll_out(slot < 0); return; }
         if constexpr (CMB) {                               // ovo counts ROW bytes here
             if (slot >= 0) {
                 const uint32_t blk = (stepno & 1u) * 2u + (uint32_t)slot;
@@ -1025,6 +1124,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             if constexpr (GATHER) { if (grow >= gp.hi) break; }   // row hi - 1 has left: the rest of the run is not replayed
             if (out_left < blk_elems) { corrupt = true; break; }
             out_left -= blk_elems;
+            if constexpr (ROLL) rinrun = true;
             if constexpr (SELECT) {
                 sm = sel_byte(fb);
                 if (!FIRE && sm == 0) { fb++; continue; }   // (a FIRE run is replayed for its state, and staged only where a bit is set)
@@ -1052,7 +1152,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     q_row(k, i);
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                    if constexpr (!query_reduce_only(Q) && !CM)
+                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL)
                         if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
 #endif
                 }
@@ -1151,6 +1251,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto packed_block = [&](const int (&e)[CPL][8], int slot) {   // forecast recurrence (:993-1150)
         if (out_left < blk_elems) { corrupt = true; return; }
         out_left -= blk_elems;
+        if constexpr (ROLL) rinrun = false;
         if constexpr (MASKED) sm = (MASK_GIVEN || smb) ? sel_byte(fb) : 0xffu;   // (block fb < chunk_len / blk_elems <= rows.stride: the guard has passed)
         seg_begin();
         auto col_step = [&](int k, int i, int coef, int& grad) {
@@ -1182,7 +1283,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 q_row(k, i);
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                if constexpr (!query_reduce_only(Q) && !CM)
+                if constexpr (!query_reduce_only(Q) && !CM && !ROLL)
                     if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
 #else
                 asm volatile("" :: "v"(pv[k]));
@@ -1315,6 +1416,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
         if constexpr (HIST) hctx.g = hist_of_chunk(a, chunk);
         if constexpr (GBY) groupby_of_chunk(a, gctx, chunk);
+        if constexpr (ROLL) {                              // the ring restarts cold with every chunk: no slot is read before this chunk wrote it
+#pragma unroll
+            for (int k = 0; k < CPL; k++) rsum[k] = 0;
+            rblk = 0; rrun = 0; rinrun = false;
+        }
         if constexpr (SELECT) {
             srank = 0;
             sbase = a.select.bases[chunk];
@@ -1437,7 +1543,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
                 for (int q = 0; q < PIECES; q++) float_store(held[s2][q], q, held_vo[s2][q]);
-        } else if constexpr (!query_reduce_only(Q)) {
+        } else if constexpr (!query_reduce_only(Q) && !ROLL) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -1544,7 +1650,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
     }
-    if constexpr (FLT) {
+    if constexpr (ROLL) {
+        // the tail walks row by row at plain 64-bit addresses, then the chunk leaves its count and last rows for the seam pass (decode_ops.h)
+        if (!corrupt) rolling_tail<W, CPL>(a, chunk, rollp, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, rsum);
+        rolling_leave<W, CPL>(a, chunk, rollp, corrupt ? 0u : out_elems + remaining, (uint32_t)D, genk, col_ok, lane_d);
+    } else if constexpr (FLT) {
         // the tail converts element by element, at plain 64-bit addresses (decode_ops.h: float_tail)
         if (!corrupt && remaining > 0) float_tail<W>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP);
     } else if constexpr (SELECT) {

@@ -40,6 +40,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // SEG (sprintz_mi355x_segment_rows): aggregate's accumulators over windows whose edges come from the mask, placed behind the chunk's base
     // (decode_ops.h: SegState, segment_rows8); runs are replayed block by block
     constexpr bool SEG = Q == kQuerySegment;
+    // ROLL (sprintz_mi355x_rolling_rows): every sample leaves as its column's min / max / sum over the W rows that end at its row; the group's LDS is
+    // the chunk's history ring (decode_ops.h: rolling_rows8), runs are replayed block by block
+    constexpr bool ROLL = Q == kQueryRolling;
     constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT || SEG;
     constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -96,6 +99,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
+            if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
             if constexpr (TAB) hbad = true; else return;
         }
         groups_left = len < 128u ? 0u : len / (16u * (uint32_t)D);
@@ -110,6 +114,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
+            if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
             if constexpr (TAB) hbad = true; else return;
         }
     } else {
@@ -242,6 +247,13 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         }
         ffmt = a.filter.mode & 3u;
         fsb = float_sign_bit<W>(a.filter.mode);
+    }
+    // rolling rows: each column's running sum over its window; the chunk's ring is the group's LDS (a.table.table_off is 0 in this kernel's launch)
+    uint32_t rsum[CPL];
+    uint32_t rrun = 0;                               // the blocks of a delta run behind this one, in a row
+    if constexpr (ROLL) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) rsum[k] = 0;
     }
 
     for (;;) {
@@ -419,6 +431,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             } else if constexpr (LIN) {          // (a lane column past the last one has weights 0; the chunk's first row leaves for the seam pass)
                 if (lctx.lag && lfirst && genk[k]) linear_slot<W>(a, chunk, (uint32_t)D).first[colk[k]] = (U)v[0][k];
                 linear_rows8<W>(lc[k], [&](int i) { return v[i][k]; }, lctx.lag, lfirst, lacc, lself, lnext);
+            } else if constexpr (ROLL) {
+                // (a delta run whose last W + 8 rows fill the ring is settled -- decode_ops.h; rrun is the group's, every column's alike)
+                if (genk[k])
+                    rolling_rows8<W>(a, rolling_ring<W>(lds + a.table.table_off, a, (uint32_t)colk[k]), out_elems / blk_elems, [&](int i) { return v[i][k]; }, rsum[k],
+                                     chunk * (uint64_t)a.chunk_len + out_elems + (uint64_t)colk[k], (uint32_t)D,
+                                     !FIRE && SPRINTZ_ROLL_RUN_SHORTCUT && run_block && rolling_run_settled(a, rrun));
             } else if constexpr (MOM || GBY) {   // (the products / the adds wait for the reference / key column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
@@ -474,6 +492,8 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             }
         }
 
+        if constexpr (ROLL) rrun = (!FIRE && run_block) ? rrun + 1u : 0u;
+
         if constexpr (SEG) segment_block_done(a, sblk, sst, sbase, grow0, out_elems / (uint32_t)D, lane_d);   // behind the block's columns
 
         if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride (checked above)
@@ -490,7 +510,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         // ---- store the 8 x D block (contiguous 8*D*ESZ bytes of the output)
         U* const ob = o + out_elems;
-        if constexpr (query_reduce_only(Q)) {
+        if constexpr (query_reduce_only(Q) || ROLL) {       // (rolling rows: the block's results left from the column loop, the raw rows went to the ring)
             (void)ob;
         } else if constexpr (Q == kQueryGather) {
             // rows [lo, hi) of the chunk alone, each at its place in the range; the parse stops after row hi - 1
@@ -649,6 +669,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (Q == kQuerySelect) {
         if (!corrupt) select_tail<W>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / (uint32_t)D, sbase, srank, lane_d, DP,
                                      [&](uint32_t b) { return (uint32_t)smb[b]; });
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        return;
+    }
+    if constexpr (ROLL) {
+        if (!corrupt) rolling_tail<W, CPL>(a, chunk, lds + a.table.table_off, s + pos, out_elems, remaining, (uint32_t)D, colk, genk, rsum);
+        rolling_leave<W, CPL>(a, chunk, lds + a.table.table_off, corrupt ? 0u : out_elems + remaining, (uint32_t)D, colk, genk, lane_d);
         if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }

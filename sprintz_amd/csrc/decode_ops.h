@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments, group-by, extrema, linear filter, segment and float rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by, extrema, linear filter, segment, float and rolling rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -16,12 +16,12 @@ namespace sprintz {
 // slot) and column d land at entry (c*count + w)*D + d of each selected output.  Aggregate and moments rows walk the same windows
 // and may count each one's selected rows: chunk c's window w in row_count[c * count + w]
 struct WindowArgs {
-    uint32_t rows;              // W, a multiple of 8: a block of 8 rows never straddles a window edge
+    uint32_t rows;              // W, a multiple of 8: a block of 8 rows never straddles a window edge (rolling rows: the trailing window's rows)
     uint32_t count;             // windows per chunk slot: ceil(ceil(chunk_len / D) / W)
-    uint32_t ops;               // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4
+    uint32_t ops;               // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4 (rolling rows: SPRINTZ_ROLL_*, the same bits)
     void* min;                  // element type
     void* max;                  // element type
-    uint64_t* sum;
+    uint64_t* sum;              // (rolling rows: read as uint32_t*, an entry an element)
     uint32_t* row_count;        // optional (SPRINTZ_AGG_COUNT, SPRINTZ_MOM_COUNT)
 };
 // gather rows (Q == kQueryGather; sprintz_mi355x_gather_rows): range i is batch rows [starts[i], starts[i] + rows), batch row g
@@ -57,7 +57,7 @@ struct RowMaskArgs {
 struct BinTableArgs {
     uint64_t span_chunks;       // H; 0: the whole batch is one table
     uint32_t shift, nbins;
-    uint32_t table_off;
+    uint32_t table_off;         // (rolling rows: where the chunks' history rings start in the launch's LDS)
     uint32_t wg_chunks;
     uint32_t entries;           // histogram: D * nbins counters; group-by: nbins * D sums, then nbins counts
 };
@@ -113,7 +113,7 @@ struct ExtremaArgs {
 struct LinearArgs {
     const int32_t* w;           // [D], on the device
     const int32_t* lag;         // [D], or null: no lag term
-    void* tmp;                  // nchunks x linear_tmp_stride (geom.h) bytes where lag is given
+    void* tmp;                  // nchunks x linear_tmp_stride (geom.h) bytes where lag is given (rolling rows: nchunks x roll_tmp_stride, or null with one chunk)
     int32_t lo, hi, bias;
     uint32_t pad;
 };
@@ -158,7 +158,8 @@ struct DecodeArgs {
     // arguments in front of them), and the struct keeps the length it has had since group-by rows: those kernels keep their code.
     // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.  The linear filter's took the
     //  other 40: the spare bytes are used up, and the next mode's arguments have to share a struct that is here, as the linear filter shares
-    //  FilterArgs, or move the kernels named above.  Float rows do: scale, offset and format ride in FilterArgs' lo, hi and mode.)
+    //  FilterArgs, or move the kernels named above.  Float rows do: scale, offset and format ride in FilterArgs' lo, hi and mode.  Rolling rows
+    //  do: WindowArgs, LinearArgs::tmp and BinTableArgs::table_off.)
     WindowArgs win;
     MomentArgs mom;
     BinTableArgs table;
@@ -1349,6 +1350,193 @@ __device__ __forceinline__ void float_piece(const uint4& t, uint32_t mode, const
             h[j] = fmt == kFloatF16 ? float_to_f16(z[2 * j]) | (float_to_f16(z[2 * j + 1]) << 16) : float_to_bf16(z[2 * j]) | (float_to_bf16(z[2 * j + 1]) << 16);
 #pragma unroll
         for (int q = 0; q < NE / 8; q++) store(q, make_uint4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]));
+    }
+}
+
+// ---- rolling rows (Q == kQueryRolling; sprintz_mi355x_rolling_rows): element e of chunk c, in row r = e / D and column d = e % D, leaves at
+// place c * chunk_len + e of every selected output as op(x[max(0, r - W + 1) .. r, d]) -- the minimum and the maximum in the element type, the
+// sum as a uint32 -- in place of the element itself.  The window is clipped at the chunk's row 0 inside the launch; the seam pass
+// (decode_rolling.hip) grows the first W - 1 rows of every chunk behind the first by the rows of the chunk in front.  The mode has no struct of its
+// own (DecodeArgs has no spare byte): W, the ops (kRollMin | kRollMax | kRollSum) and the outputs travel in WindowArgs (rows, ops, min, max and sum
+// -- read as uint32_t*), the seam scratch in LinearArgs::tmp (null: one chunk, no seam pass), the ring's place in the launch's LDS in
+// BinTableArgs::table_off.
+// A chunk's history ring holds its last W + 8 raw rows, column by column: column d's rows at elements [d * (W + 8), (d + 1) * (W + 8)), row r in
+// slot r % (W + 8).  W + 8 is a multiple of 8, so a block of 8 rows never wraps, and when block b arrives the W rows in front of it are all
+// there.  A column belongs to one lane from the chunk's first row to its last, so a lane reads only what it wrote: the ring needs no barrier.  It
+// starts cold with every chunk -- no slot is read before the chunk wrote it.
+template <int W> __device__ __forceinline__ typename Elem<W>::U* rolling_ring(uint8_t* ring, const DecodeArgs& a, uint32_t col)
+{
+    return (typename Elem<W>::U*)ring + (size_t)col * (a.win.rows + 8u);
+}
+// One block: the 8 new rows x(0 .. 7) of a column, block `blk` of the chunk (rows 8 blk .. 8 blk + 7), whose row 0 is element `e0` of the batch.
+// The sum is S += x[r] - x[r - W], the row that leaves read from the ring.  The minimum / maximum of row j is made of three parts: the
+// suffix of rows j + 1 .. 7 of the block W / 8 back, the whole blocks in between -- common to the 8 rows -- and the prefix of rows 0 .. j of the
+// new block.  The blocks in between are re-read from the ring's raw rows, W - 8 ring reads a block and column: their minima are not kept (the
+// ring stays (W + 8) D elements, and the lane needs no further state than S).  A block whose window reaches in front of row 0 has fewer parts.
+// put(op, j, v): row j's result v of op (kRollMin / kRollMax / kRollSum, a selected one) -- the generic kernel stores it at its place, decode_fast.h
+// keeps it for its staging passes
+template <int W, typename F, typename P>
+__device__ __forceinline__ void rolling_step8(const DecodeArgs& a, typename Elem<W>::U* rc, uint32_t blk, F x, uint32_t& S, bool settled, P put)
+{
+    using U = typename Elem<W>::U;
+    constexpr uint32_t MASK = Elem<W>::MASK;
+    const uint32_t wb = a.win.rows >> 3, nb = wb + 1u;          // blocks of a window, of the ring
+    const uint32_t slot = blk % nb;
+    const bool leaving = blk >= wb;                             // the block W rows back exists: it lies in the slot the NEXT block takes
+    const U* const ob = rc + 8u * (slot + 1u == nb ? 0u : slot + 1u);
+    uint32_t xs[8], old[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        xs[i] = x(i) & MASK;
+        old[i] = settled ? xs[i] : leaving ? (uint32_t)ob[i] : 0u;      // (settled: the ring holds this one value in every slot -- see below)
+    }
+    if (a.win.ops & kRollSum) {
+        uint32_t s = S;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            s += xs[i] - old[i];
+            put(kRollSum, i, s);
+        }
+        S = s;
+    }
+    if (a.win.ops & (kRollMin | kRollMax)) {
+        // the whole blocks in between: blk - wb + 1 .. blk - 1, those of them the chunk has
+        uint32_t mn = MASK, mx = 0;
+        const uint32_t nmid = settled ? 0u : blk < wb - 1u ? blk : wb - 1u;
+        uint32_t ms = slot;
+        for (uint32_t j = 0; j < nmid; j++) {
+            ms = ms == 0 ? nb - 1u : ms - 1u;
+            const U* const mb = rc + 8u * ms;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const uint32_t y = mb[i];
+                mn = y < mn ? y : mn;
+                mx = y > mx ? y : mx;
+            }
+        }
+        // the suffixes of the block that leaves: smn[j] over its rows j + 1 .. 7 (the identities where it does not exist)
+        uint32_t smn[8], smx[8];
+        uint32_t rn = MASK, rx = 0;
+#pragma unroll
+        for (int j = 7; j >= 0; j--) {
+            smn[j] = rn;
+            smx[j] = rx;
+            if (leaving || settled) {
+                rn = old[j] < rn ? old[j] : rn;
+                rx = old[j] > rx ? old[j] : rx;
+            }
+        }
+        // the prefixes of the new block run on from the blocks in between
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            mn = xs[j] < mn ? xs[j] : mn;
+            mx = xs[j] > mx ? xs[j] : mx;
+            if (a.win.ops & kRollMin) put(kRollMin, j, smn[j] < mn ? smn[j] : mn);
+            if (a.win.ops & kRollMax) put(kRollMax, j, smx[j] > mx ? smx[j] : mx);
+        }
+    }
+    if (settled) return;
+    U* const nbk = rc + 8u * slot;
+#pragma unroll
+    for (int i = 0; i < 8; i++) nbk[i] = (U)xs[i];
+}
+// the generic kernel's form: every result leaves at once, at a plain 64-bit address; e0 is the batch element of the block's row 0 in this column
+template <int W, typename F>
+__device__ __forceinline__ void rolling_rows8(const DecodeArgs& a, typename Elem<W>::U* rc, uint32_t blk, F x, uint32_t& S, uint64_t e0, uint32_t D, bool settled = false)
+{
+    using U = typename Elem<W>::U;
+    rolling_step8<W>(a, rc, blk, x, S, settled, [&](uint32_t op, int j, uint32_t v) {
+        const uint64_t e = e0 + (uint64_t)j * D;
+        if (op == kRollSum) ((uint32_t*)a.win.sum)[e] = v;
+        else if (op == kRollMin) ((U*)a.win.min)[e] = (U)v;
+        else ((U*)a.win.max)[e] = (U)v;
+    });
+}
+// Delta runs.  A delta run repeats the previous row: once W + 8 consecutive rows of a run lie behind a block -- nb = W / 8 + 1 run blocks, so that
+// every slot of the ring, the leaving block's included, holds the column's one value c -- the next run block is `settled`: rolling_rows8 takes
+// the leaving block and the blocks in between as c without reading them and leaves the ring as it is; S stays W c.  `done` counts the run blocks
+// behind a block in a row (the kernel resets it at every block that is not one of a delta run).  A first form -- a branch of its own that stored
+// the constants -- cost the uint16 x 8 delta kernel 32 registers and a wave a SIMD, and was slower than no shortcut; this one shares the step's
+// stores.  Timed both ways on constant data (-DSPRINTZ_ROLL_RUN_SHORTCUT=0 is the per-block path alone): profiles/rolling_rows.txt.
+#ifndef SPRINTZ_ROLL_RUN_SHORTCUT
+#define SPRINTZ_ROLL_RUN_SHORTCUT 1
+#endif
+__device__ __forceinline__ bool rolling_run_settled(const DecodeArgs& a, uint32_t done) { return done >= (a.win.rows >> 3) + 1u; }
+// One row: the per-row form of the same step, for the verbatim tail -- row r of the chunk takes x; its window is read back from the ring
+template <int W>
+__device__ __forceinline__ void rolling_row(const DecodeArgs& a, typename Elem<W>::U* rc, uint32_t r, uint32_t x, uint32_t& S, uint64_t e)
+{
+    using U = typename Elem<W>::U;
+    const uint32_t w = a.win.rows, cap = w + 8u;
+    uint32_t slot = r % cap;
+    S += x - (r >= w ? (uint32_t)rc[(r - w) % cap] : 0u);
+    rc[slot] = (U)x;
+    if (a.win.ops & kRollSum) ((uint32_t*)a.win.sum)[e] = S;
+    if (a.win.ops & (kRollMin | kRollMax)) {
+        uint32_t mn = x, mx = x;
+        const uint32_t n = r + 1u < w ? r + 1u : w;
+        for (uint32_t j = 1; j < n; j++) {
+            slot = slot == 0 ? cap - 1u : slot - 1u;
+            const uint32_t y = rc[slot];
+            mn = y < mn ? y : mn;
+            mx = y > mx ? y : mx;
+        }
+        if (a.win.ops & kRollMin) ((U*)a.win.min)[e] = (U)mn;
+        if (a.win.ops & kRollMax) ((U*)a.win.max)[e] = (U)mx;
+    }
+}
+// The verbatim tail: `remaining` elements at t behind the chunk's `out_elems` (a multiple of 8 * D: element e of the tail is in column e % D, one
+// row further on than the column's previous one).  Each lane walks its own columns (`col`, a list), row by row; a partial last row has the
+// columns it has, and nothing is stored for the others.
+template <int W, int CPL>
+__device__ __forceinline__ void rolling_tail(const DecodeArgs& a, uint64_t chunk, uint8_t* ring, const uint8_t* t, uint32_t out_elems, uint32_t remaining, uint32_t D,
+                                             const int (&col)[CPL], const bool (&genuine)[CPL], uint32_t (&S)[CPL])
+{
+    const uint64_t base = chunk * (uint64_t)a.chunk_len + out_elems;
+    const uint32_t r0 = out_elems / D;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        typename Elem<W>::U* const rc = rolling_ring<W>(ring, a, (uint32_t)col[k]);
+        uint32_t r = r0;
+        for (uint32_t e = (uint32_t)col[k]; e < remaining; e += D, r++) rolling_row<W>(a, rc, r, tail_elem<W>(t, e), S[k], base + e);
+    }
+}
+// what chunk `chunk` leaves for the seam pass (geom.h: roll_tmp_stride): the library's own layout
+template <int W> struct RollSlot {
+    uint32_t* elems;                // the elements the chunk decoded to; 0: damaged, or empty
+    typename Elem<W>::U* rows;      // [W - 1][D]: rows R - (W - 1) .. R - 1 of a full chunk (elems == chunk_len), R = chunk_len / D
+};
+template <int W> __device__ __forceinline__ RollSlot<W> rolling_slot(const DecodeArgs& a, uint64_t chunk)
+{
+    uint8_t* const p = (uint8_t*)a.lin.tmp + chunk * roll_tmp_stride(a.win.rows, a.D, W / 8);
+    return RollSlot<W>{(uint32_t*)p, (typename Elem<W>::U*)(p + 16)};
+}
+// a chunk that is refused before its ring exists: one lane says so
+template <int W> __device__ __forceinline__ void rolling_mark(const DecodeArgs& a, uint64_t chunk, int lane_d)
+{
+    if (a.lin.tmp && lane_d == 0) *rolling_slot<W>(a, chunk).elems = 0u;
+}
+// At the chunk's end, with a seam pass to come: the element count, and -- from a full chunk, the only kind that has a successor whose windows
+// it can complete -- its last W - 1 rows out of the ring (W <= R: the host checks, so they exist; the ring holds the last W + 8)
+template <int W, int CPL>
+__device__ __forceinline__ void rolling_leave(const DecodeArgs& a, uint64_t chunk, uint8_t* ring, uint32_t elems, uint32_t D, const int (&col)[CPL],
+                                              const bool (&genuine)[CPL], int lane_d)
+{
+    if (!a.lin.tmp) return;
+    const RollSlot<W> s = rolling_slot<W>(a, chunk);
+    if (lane_d == 0) *s.elems = elems;
+    if (elems != a.chunk_len) return;
+    const uint32_t w = a.win.rows, cap = w + 8u, first = a.chunk_len / D - (w - 1u);
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        const typename Elem<W>::U* const rc = rolling_ring<W>(ring, a, (uint32_t)col[k]);
+        uint32_t slot = first % cap;
+        for (uint32_t j = 0; j + 1u < w; j++) {
+            s.rows[(size_t)j * D + (uint32_t)col[k]] = rc[slot];
+            slot = slot + 1u == cap ? 0u : slot + 1u;
+        }
     }
 }
 

@@ -34,10 +34,12 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 12 = linear filter: one bit per row -- does bias + sum_d w[d] x[g, d] + sum_d u[d] x[g - 1, d], in wrapping 32-bit arithmetic, lie in [lo, hi]? -- and the
 // chunk's count of them, in the filter's mask layout, reduce only;
 // 13 = segment: per run of rows that a mask names (or per stretch between two set bits) its start, length and min / max / sum, placed behind the chunk's base, reduce only;
-// 14 = float: a plain decode whose stores convert -- every sample leaves as fl32(fl32(x * scale[d]) + offset[d]) in float32, float16 or bfloat16, never as an integer.
+// 14 = float: a plain decode whose stores convert -- every sample leaves as fl32(fl32(x * scale[d]) + offset[d]) in float32, float16 or bfloat16, never as an integer;
+// 15 = rolling: per element the min / max / sum of its column over the W rows that end at its row (a trailing window, clipped at the chunk's first row
+// inside the launch; the seam pass of decode_rolling.hip carries it over the chunk seams), stored at the element's place in place of the element.
 // 6 .. 11 and 13 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
-              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14;
+              kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14, kQueryRolling = 15;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
@@ -47,6 +49,24 @@ constexpr bool query_reduce_only(int q)
 // an output element's bytes
 constexpr uint32_t kFloatF32 = 0, kFloatF16 = 1, kFloatBF16 = 2, kFloatSignedBit = 4;
 constexpr int float_out_bytes(uint32_t mode) { return (mode & 3u) == kFloatF32 ? 4 : 2; }
+// rolling rows: the ops (SPRINTZ_ROLL_MIN / _MAX / _SUM, WindowArgs::ops) and the LDS a workgroup's launch can be given.  A chunk's history
+// ring holds the last W + 8 raw rows of its columns, column by column (a lane reads 8 rows of a column as one piece), rounded up to 16 bytes
+constexpr uint32_t kRollMin = 1, kRollMax = 2, kRollSum = 4;
+constexpr uint64_t kRollLdsMax = 160ull * 1024ull;
+constexpr uint64_t roll_ring_bytes(uint32_t W, int D, int esz) { return (((uint64_t)W + 8ull) * (uint64_t)D * (uint64_t)esz + 15ull) & ~15ull; }
+// the largest window the sum's int32 holds exactly, W (2^(8 esz) - 1) < 2^31, as a multiple of 8
+constexpr uint32_t roll_sum_max_window(int esz) { return (uint32_t)(0x7fffffffull / ((1ull << (8 * esz)) - 1ull)) & ~7u; }
+// the largest window (a multiple of 8; 0: none) whose rings -- one for each of the `groups` chunks of a workgroup -- fit kRollLdsMax and whose
+// sum fits int32: what the planner refuses beyond and what the host wrapper names in its refusal
+constexpr uint32_t roll_max_window(int D, int esz, uint32_t groups)
+{
+    const uint64_t rows = (kRollLdsMax / groups & ~15ull) / ((uint64_t)D * (uint64_t)esz);      // rows of one ring
+    const uint64_t w = rows < 16 ? 0 : (rows - 8) & ~7ull;
+    return w > roll_sum_max_window(esz) ? roll_sum_max_window(esz) : (uint32_t)w;
+}
+// with more than one chunk: what one chunk leaves for the seam pass (decode_ops.h: RollSlot) -- a word with the elements the chunk decoded to (0: damaged),
+// 12 bytes of padding, then its last W - 1 rows in the element type where it is full; a multiple of 16 bytes
+constexpr uint64_t roll_tmp_stride(uint32_t W, int D, int esz) { return (16ull + ((uint64_t)W - 1ull) * (uint64_t)D * (uint64_t)esz + 15ull) & ~15ull; }
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB
 constexpr uint32_t kHistMaxCounters = 16384;
@@ -99,6 +119,15 @@ inline Mapping choose_mapping(int D, bool lowdim)
         }
     }
     return m;
+}
+
+// rolling rows: the largest window a SHAPE takes -- roll_max_window at the chunks a workgroup of the generic kernel decodes, kThreads over the
+// lanes of its column group (`general`: the general layout asked for, or a codec that has no other).  plan_decode refuses by it and the host
+// wrapper names it in its refusal: one function, so that the two cannot drift apart
+inline uint32_t roll_shape_max_window(int D, int esz, bool general)
+{
+    const Mapping m = choose_mapping(D, general ? false : is_lowdim(esz, D));
+    return roll_max_window(D, esz, (uint32_t)(kThreads >> m.log2DP));
 }
 
 inline uint32_t next_pow2(uint32_t x)

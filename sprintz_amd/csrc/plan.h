@@ -41,7 +41,7 @@ struct Shape {
     unsigned src_lo = 0, slots_lo = 0, out_lo = 0, comp_lo = 0;   // the low four bits of the source, slot, output and container addresses
     uint64_t slot_stride = 0;
     uint64_t nranges = 0;                  // gather
-    uint32_t rows = 0;
+    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W
     uint64_t capacity = 0;                 // select: rows of the output
     // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
     // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
@@ -174,6 +174,42 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     const bool flt = s.q == kQueryFloat;
     const int osz = flt ? s.out_esz : esz;
 
+    // rolling rows (W in s.rows; s.out_esz the widest output element: 4 with the sum, else esz; s.out_lo the low bits of EVERY selected output).
+    // decode_fast.h takes rows of whole 16-byte pieces -- gather's, select's and float rows' mappings -- with 16-byte aligned outputs, within the
+    // descriptors' reach counted in OUTPUT bytes (out_esz), where the chunks' history rings (geom.h: roll_ring_bytes) fit behind the groups' carves:
+    // (f.ring + roll_ring) x groups <= kHistFastLdsBudget -- on the one-column-a-lane mappings (up to 64 columns): with two and four columns a lane
+    // hipcc kept the block's results in scratch, for min and max as for the sum, so those mappings are not instantiated.  min, max and sum alike: the
+    // sum leaves as 32 / W element-type planes through the plain staging, free of scratch on every mapping kept.  Everything else runs the generic
+    // kernel, whose launch LDS is the rings alone and which stores element by element; rings that do not fit a workgroup's 160 KB there are refused
+    // (roll_shape_max_window).  decode_uni.h is not taught the mode.
+    if (s.q == kQueryRolling) {
+        if (D > 512 || norle || cs) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "rolling_rows: the RLE codecs, row-major, at most 512 columns");
+        if (s.rows < 8 || s.rows % 8) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "rolling_rows: window_rows must be a multiple of 8, at least 8");
+        const uint64_t ring = roll_ring_bytes(s.rows, D, esz);
+        const int osz = s.out_esz ? s.out_esz : esz;
+        const FastMap f = decode_fast_map(esz, D, 0, false);
+        const uint64_t fgroups = (uint64_t)(kThreads / f.dp);
+        const bool fast = !lowdim && !s.noheader && f.cpl == 1 && 2 * D > f.dp * f.cpl && (uint64_t)chunk_len * esz * 2 >= f.ring && !k.no_fast &&
+                          ((uint64_t)D * esz) % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0 && (s.out_lo % 16) == 0 &&
+                          (uint64_t)chunk_len * osz * 64 * 64 < 0xf0000000ull && ((uint64_t)f.ring + ring) * fgroups <= kHistFastLdsBudget;
+        if (fast) {
+            p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
+            p.exact = D == f.dp * f.cpl;
+            p.log2DP = f.log2dp;
+            p.lds_group_stride = f.ring;
+            p.vec_store = 1;
+            p.chunks_per_group = (uint32_t)k.chunks_per_group;
+            p.table_off = f.ring * (uint32_t)fgroups;
+            const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
+            return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, ((uint64_t)f.ring + ring) * fgroups);
+        }
+        const uint32_t groups = (uint32_t)(kThreads / DP);
+        if (s.rows > roll_shape_max_window(D, esz, !lowdim))
+            return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "rolling_rows: window_rows must be a multiple of 8 whose history rings fit a workgroup's LDS (roll_shape_max_window)");
+        p.lds_group_stride = (uint32_t)ring;
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * groups);
+    }
+
     // 513 .. 2047 columns: one workgroup per chunk (any_ndims.hip) -- the RLE codecs, row-major, plain decode
     if (D > 512) {
         if (norle || cs || s.q != kQueryOff) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "more than 512 columns: the RLE codecs, row-major, without query only");
@@ -281,7 +317,7 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
     }
     // univariate streams: one lane per chunk, LDS ring in, quad-transposed 64-byte bursts out (decode_uni.h)
     // (and the other low-dim shapes: 2 columns, 3 and 4 at 8 bits)
-    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by, nor the extrema, nor the linear filter, nor the segments, nor float rows: those shapes go to the generic kernel)
+    // (decode_uni.h is not taught to select or to aggregate rows, nor the histogram, nor the moments, nor the group-by, nor the extrema, nor the linear filter, nor the segments, nor float rows (rolling rows left above): those shapes go to the generic kernel)
     if (lowdim && (D <= 2 || esz == 1) && !s.noheader && !cs && s.q != kQuerySelect && s.q != kQueryAggregate && s.q != kQueryHistogram && s.q != kQueryMoments && s.q != kQueryGroupBy && s.q != kQueryExtrema && s.q != kQueryLinear && s.q != kQuerySegment && s.q != kQueryFloat && !k.no_fast) return plan_take(p, SPRINTZ_KF_DEC_UNI, (nchunks + 255) / 256, 0);
     if (table_bytes) {                                         // nothing is staged: the table is the launch's LDS
         p.wg_chunks = table_wg_chunks((uint64_t)(kThreads / DP), chunk_len, D, s.table_row_max);

@@ -1,5 +1,5 @@
 // row_ops.hip -- the row operations of the C-ABI (include/sprintz_mi355x.h): queries, the zone map, filters, select, aggregate,
-// moments, extrema, segments, float rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
+// moments, extrema, segments, float rows, rolling rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
 // fills its QuerySpec and hands over to decode_batch (entry.h); what the decoders then do with a row is decode_ops.h's.
 #include "entry.h"
 
@@ -54,17 +54,23 @@ QuerySpec row_query(int q, uint32_t flags)
     return qs;
 }
 
-// ---- what aggregate_rows, moments_rows, histogram_rows, groupby_rows and extrema_rows check and fill alike.  Each refusal carries the operation's
-// name `op` (fail_op), and each helper is called where its refusals stand among the operation's own.
-// the four masked operations, in front of their own checks: the common refusals, whole rows a chunk; then the mode, the layout and the
-// row mask (null: every row, where the operation allows it)
-int masked_row_op(const char* op, int q, const Batch& b, uint32_t flags, const uint8_t* d_mask, QuerySpec& qs)
+// the refusals every one of them shares, and rolling rows, which takes every row and no mask: the common ones, whole rows a chunk
+int unmasked_row_op(const char* op, const Batch& b, uint32_t flags)
 {
     int rc = check_common(b.codec, b.esz, b.ndims);
     if (rc) return rc;
     const std::string many = std::string(op) + ": more than 512 columns", rle = std::string(op) + ": the RLE codecs (delta, xff) only";
     if ((rc = check_row_op(b, flags, many.c_str(), rle.c_str(), op))) return rc;
     if (b.chunk_len % b.ndims) return fail_op(SPRINTZ_E_INVALID, op, "chunk_len must be a multiple of ndims (rows must not straddle chunks)");
+    return 0;
+}
+// ---- what aggregate_rows, moments_rows, histogram_rows, groupby_rows and extrema_rows check and fill alike.  Each refusal carries the operation's
+// name `op` (fail_op), and each helper is called where its refusals stand among the operation's own.
+// the four masked operations, in front of their own checks: the common refusals, whole rows a chunk; then the mode, the layout and the
+// row mask (null: every row, where the operation allows it)
+int masked_row_op(const char* op, int q, const Batch& b, uint32_t flags, const uint8_t* d_mask, QuerySpec& qs)
+{
+    if (int rc = unmasked_row_op(op, b, flags)) return rc;
     qs = row_query(q, flags);
     qs.rows = RowMaskArgs{d_mask, (b.chunk_len / b.ndims + 7) / 8};
     return 0;
@@ -464,6 +470,56 @@ int sprintz_mi355x_float_rows(int codec, int elem_bytes, const void* d_comp, con
     qs.filter.hi = d_offset;
     qs.filter.mode = mode;
     return decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
+}
+
+// ---------------------------------------------------------------- rolling rows
+int sprintz_mi355x_rolling_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
+                                void* d_min, void* d_max, int32_t* d_sum, void* d_tmp, int64_t* d_rets, void* hip_stream)
+{
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims};
+    int rc = unmasked_row_op("rolling_rows", b, flags);
+    if (rc) return rc;
+    if (window_rows < 8 || window_rows % 8) return fail_op(SPRINTZ_E_INVALID, "rolling_rows", "window_rows must be a multiple of 8, at least 8");
+    if (window_rows > chunk_len / ndims) return fail_op(SPRINTZ_E_INVALID, "rolling_rows", "window_rows must not exceed the rows of a chunk, chunk_len / ndims");
+    if (window_rows > roll_sum_max_window(elem_bytes)) return fail_op(SPRINTZ_E_INVALID, "rolling_rows", "window_rows x the largest element must stay below 2^31: the sum is an int32");
+    if (ops < 1 || ops > 7) return fail(SPRINTZ_E_INVALID, "rolling_rows: ops must be a non-empty OR of SPRINTZ_ROLL_MIN / _MAX / _SUM");
+    static_assert(SPRINTZ_ROLL_MIN == kRollMin && SPRINTZ_ROLL_MAX == kRollMax && SPRINTZ_ROLL_SUM == kRollSum, "out[i] is op bit i");
+    // an output WITHOUT its op is refused too: min, max and sum are this operation's only results
+    if ((d_min && !(ops & kRollMin)) || (d_max && !(ops & kRollMax)) || (d_sum && !(ops & kRollSum)))
+        return fail_op(SPRINTZ_E_INVALID, "rolling_rows", "an output buffer without its op");
+    OpOutput out[3] = {{d_min, elem_bytes}, {d_max, elem_bytes}, {d_sum, 4}};
+    if ((rc = check_op_outputs("rolling_rows", ops, out, d_rets, "min / max must be aligned to the element size, sum to 4 bytes, d_rets to 8"))) return rc;
+    if (nchunks > 1 && (!d_tmp || (uintptr_t)d_tmp % 16))
+        return fail_op(SPRINTZ_E_INVALID, "rolling_rows", "with more than one chunk, d_tmp must hold nchunks x the seam stride bytes, aligned to 16");
+    // the rings of a workgroup's chunks must fit its LDS: the bound the planner refuses by, named here
+    const uint32_t wmax = roll_shape_max_window(ndims, elem_bytes, (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) != 0);
+    if (window_rows > wmax) {
+        const std::string what = "rolling_rows: window_rows " + std::to_string(window_rows) + " needs more LDS than a workgroup has for this shape's history rings: the largest window_rows allowed is " +
+                                 std::to_string(wmax);
+        return fail(SPRINTZ_E_UNSUPPORTED, what.c_str());
+    }
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    // the mode shares structs that exist (decode_ops.h, rolling rows): W, the ops and the outputs in WindowArgs, the seam scratch in LinearArgs::tmp
+    QuerySpec qs = row_query(kQueryRolling, flags);
+    qs.win.rows = window_rows;
+    qs.win.ops = ops;
+    qs.win.min = out[0].p;
+    qs.win.max = out[1].p;
+    qs.win.sum = (uint64_t*)out[2].p;
+    qs.lin.tmp = nchunks > 1 ? d_tmp : nullptr;
+    rc = decode_batch(b, nullptr, d_rets, (hipStream_t)hip_stream, qs);
+    if (rc || nchunks < 2) return rc;
+    // the seam pass, behind the decode on the same stream
+    DecodeArgs a{};
+    a.nchunks = nchunks;
+    a.chunk_len = chunk_len;
+    a.D = ndims;
+    a.win = qs.win;
+    a.lin = qs.lin;
+    if (launch_rolling_seam(elem_bytes, a, (hipStream_t)hip_stream) != hipSuccess) return fail(SPRINTZ_E_HIP, "rolling_rows seam kernel launch");
+    return 0;
 }
 
 // ---------------------------------------------------------------- histogram rows

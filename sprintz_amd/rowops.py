@@ -1,6 +1,6 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, the default bin shift, bounds and offsets as tensors, the
+moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, rolling_rows' window rules, counts, mean and scratch size, the default bin shift, bounds and offsets as tensors, the
 linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
@@ -235,6 +235,37 @@ def quant_params(scale, offset, ndims, device):
     if not bool(torch.isfinite(inv).all()):
         raise ValueError("1 / scale must be finite in float32")
     return inv.to(device).contiguous(), off
+
+
+ROLLING_OPS = ("min", "max", "sum", "mean")
+
+
+def rolling_window(window_rows, R, esz):
+    """rolling_rows' window -> W as an int: a multiple of 8 with 8 <= W <= R rows of a chunk (one predecessor chunk suffices at a seam) and
+    W * (2^(8 esz) - 1) < 2^31 (the sum is an int32).  The bound by the kernel's LDS is the library's to refuse: it depends on the lane mapping."""
+    W = int(window_rows)
+    if W != window_rows or W < 8 or W % 8:
+        raise ValueError(f"window_rows must be a multiple of 8, at least 8, not {window_rows}")
+    if W > R:
+        raise ValueError(f"window_rows {W} exceeds the {R} rows of a chunk: a window may reach into one chunk in front, not two")
+    if W * ((1 << (8 * esz)) - 1) >= 1 << 31:
+        raise ValueError(f"window_rows {W} x the largest {8 * esz}-bit element does not fit the int32 sum")
+    return W
+
+
+def rolling_counts(G, W, device=None):
+    """the rows in the trailing window of W rows that ends at batch row g, clipped at row 0: min(g + 1, W), int32 [G]"""
+    return torch.clamp(torch.arange(1, G + 1, dtype=torch.int64, device=device), max=W).to(torch.int32)
+
+
+def rolling_mean(total, counts):
+    """rolling sums int32 [G, D] and their rows' counts [G] -> the means, float32 [G, D]: one float32 divide of the converted integers"""
+    return total.to(torch.float32) / counts.to(torch.float32).unsqueeze(1)
+
+
+def rolling_tmp_bytes(nchunks, W, ndims, esz):
+    """the seam scratch rolling_rows needs with more than one chunk (include/sprintz_mi355x.h: d_tmp), a multiple of 16 bytes a chunk"""
+    return nchunks * ((16 + (W - 1) * ndims * esz + 15) & ~15) if nchunks > 1 else 0
 
 
 def default_shift(W, nbins):
