@@ -54,7 +54,7 @@ extern "C" {
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
  *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
  *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR;
- *      rolling_rows, SPRINTZ_ROLL_* */
+ *      rolling_rows, SPRINTZ_ROLL_*; project_rows, SPRINTZ_PROJECT_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -1018,6 +1018,41 @@ int sprintz_mi355x_compress_batch_float_dense(int codec, int elem_bytes, const v
 int sprintz_mi355x_rolling_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                 uint32_t chunk_len, uint16_t ndims, uint32_t window_rows, uint32_t ops, uint32_t flags,
                                 void* d_min, void* d_max, int32_t* d_sum, void* d_tmp, int64_t* d_rets, void* hip_stream);
+/* Project rows: SELECT a, b -- the batch decoded into a dense [rows, ncolumns] tensor of the columns a slot table names, in the element type or
+ * as float_rows converts; the other columns are decoded (the predictors need them) and never stored.  The batch is given as to
+ * sprintz_mi355x_select_rows (chunk_len % ndims == 0; the RLE codecs; at most 512 columns; a short last chunk may end mid-row).  The batch's
+ * rows are g = 0 .. G - 1, row g being row g % R of chunk g / R, R = chunk_len / ndims; chunk c's rows start at output row c * R.  For every
+ * element that exists, in row g and column d with s = d_slots[d] in 0 .. ncolumns - 1:
+ *   out[g * ncolumns + s] = x[g, d]                                          format SPRINTZ_PROJECT_RAW, in the element type
+ *                         = float_rows' value with d_scale[s], d_offset[s]    format SPRINTZ_PROJECT_F32 / _F16 / _BF16, bit for bit float_rows' rule
+ *   d_slots    : int32 [ndims] on the device: column d's slot in an output row, or -1 for a column that is not wanted.  ANY entry outside
+ *                0 .. ncolumns - 1 is read as "not wanted": a damaged table can misplace values inside d_out and never writes outside it.  Two
+ *                columns with one slot leave one of their values there.  A slot no column names is not written.
+ *   ncolumns   : K, 1 .. ndims
+ *   format     : SPRINTZ_PROJECT_RAW (0), or 1 + a SPRINTZ_FLOAT_* format
+ *   d_scale, d_offset: float32 [ncolumns] on the device, indexed by SLOT; NULL is all 1 / all 0.  Only with a float format.
+ *   flags      : SPRINTZ_QUERY_GENERAL_LAYOUT, SPRINTZ_FLOAT_SIGNED (a float format alone) and nothing else
+ *   d_out      : nchunks * R * ncolumns elements of the output type (a chunk slot each chunk, as for every batch call: a damaged stream may
+ *                decode to more rows than its chunk had, never to more than R); the first G * ncolumns of them are the result, G the rows
+ *                the batch decodes to.  Nothing is written past a chunk's decoded count: where the batch ends mid-row the elements of that
+ *                row that do not exist are not written.  (SPRINTZ_KF_DEC_FAST reaches the chunks of a wavefront with
+ *                32-bit offsets, as for float_rows: where 4096 projected chunk slots, R * ncolumns output elements each, pass 0xf0000000
+ *                bytes the generic kernel runs.)
+ *   d_rets     : (optional) exactly what sprintz_mi355x_decompress_batch writes for the same batch -- a chunk's count of ALL its elements --
+ *                damaged chunks included
+ * One launch (SPRINTZ_KF_DEC_FAST for 3 .. 64 columns where the plain decode runs there and the projected block, 8 * ncolumns * elem_bytes, is a
+ * whole number of 16-byte pieces, with d_out 16-byte aligned; SPRINTZ_KF_DEC_GENERIC otherwise), no synchronisation, no allocation.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for ncolumns == 0 or above ndims, chunk_len % ndims != 0, chunk_len outside
+ * 1..2^30, an unknown flag or format, d_scale / d_offset / SPRINTZ_FLOAT_SIGNED with SPRINTZ_PROJECT_RAW, a NULL d_comp / d_offsets / d_slots /
+ * d_out, d_out not aligned to the output element size, d_slots / d_scale / d_offset not aligned to 4 bytes, d_rets to 8;
+ * SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs.  nchunks == 0 returns 0 and launches nothing. */
+#define SPRINTZ_PROJECT_RAW  0
+#define SPRINTZ_PROJECT_F32  1   /* 1 + SPRINTZ_FLOAT_F32 */
+#define SPRINTZ_PROJECT_F16  2
+#define SPRINTZ_PROJECT_BF16 3
+int sprintz_mi355x_project_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint32_t ndims, const int32_t* d_slots, uint32_t ncolumns, int format,
+                                const float* d_scale, const float* d_offset, uint32_t flags, void* d_out, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

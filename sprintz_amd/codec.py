@@ -769,6 +769,53 @@ class ChunkedCodec:
                 del res["sum"]
         return {k: res[k] for k in ops}
 
+    def project_rows(self, batch, columns, dtype=None, scale=None, offset=None, signed=False, out=None, rets=None, general_layout=False, check=True):
+        """SELECT a, b: the columns `columns` names, decoded straight into a dense [G, K] tensor, G = ceil(total_len / ndims) -- out[g, j] =
+        x[g, columns[j]] -- in one launch; the other columns are never stored, and the full tensor never exists.
+
+        columns: K >= 1 distinct column numbers in 0 .. ndims - 1, in any order (rowops.project_slots).  dtype: None for the codec's dtype,
+        or torch.float32 / torch.float16 / torch.bfloat16 for float_rows' conversion, (x.to(float32) * scale[j] + offset[j]).to(dtype), bit
+        for bit what torch computes on the CPU.  scale / offset: float_rows' forms with K entries, indexed by output column, a float dtype
+        only; signed=True reads the elements as int8 / int16, a float dtype only.  chunk_len must be a multiple of ndims.
+        -> a [G, K] tensor; where the batch ends mid-row, the columns that last row lacks hold 0.  out: a contiguous tensor of the output
+        dtype with at least nchunks x R x K elements (a chunk slot each chunk, R = chunk_len / ndims) to write into -- its first G x K are the result; rets: an int64 tensor of nchunks entries for the per-chunk element counts (of
+        all ndims columns, as decompress reports them).  check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        D, n = self.ndims, batch.nchunks
+        R, _ = rowops.chunk_rows(self.chunk_len, D, "project_rows")
+        slots = rowops.project_slots(columns, D, self.device)
+        K = int((slots >= 0).sum())
+        if dtype is None or dtype == self.dtype:
+            if scale is not None or offset is not None or signed:
+                raise ValueError("scale, offset and signed go with a float dtype")
+            dtype, fmt = self.dtype, _lib.PROJECT_RAW
+        else:
+            fmt = 1 + rowops.float_format(dtype)
+            scale = rowops.float_params(scale, K, "scale", self.device)
+            offset = rowops.float_params(offset, K, "offset", self.device)
+        G = -(-batch.total_len // D)
+        if out is None:
+            out = torch.empty(n * R * K, dtype=dtype, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != dtype or out.device != self.device or out.numel() < n * R * K or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor of at least {n} x {R} x {K} elements on {self.device}")
+        if rets is None:
+            rets = self._rets(n, check)
+        res = out.view(-1)[: G * K].view(G, K)
+        if n:
+            with self._on():
+                _lib.check(_lib.project_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n, self.chunk_len, D,
+                                             slots.data_ptr(), K, fmt, _ptr(scale), _ptr(offset),
+                                             self._general(general_layout) | (_lib.FLOAT_SIGNED if signed else 0), out.data_ptr(), _ptr(rets), self._stream()))
+            if check:
+                rowops.raise_damaged("project_rows", rets, n, _lib.SprintzError)
+            if batch.total_len % D:                        # the batch ends mid-row: the columns that row lacks are not written
+                there = slots[: batch.total_len % D]
+                lacks = torch.ones(K, dtype=torch.bool, device=self.device)
+                lacks[there[there >= 0].long()] = False
+                # (zero bits through a signed view of the same width: torch fills no uint16 tensor under a mask)
+                res.view({1: torch.int8, 2: torch.int16, 4: torch.int32}[res.element_size()])[G - 1, lacks] = 0
+        return res
+
     def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False, zones=None):
         """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
         filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.

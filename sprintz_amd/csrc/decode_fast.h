@@ -181,6 +181,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // 32-bit pieces where float rows convert theirs.  The pieces are stored at once (no held slots: three outputs would triple them).
     constexpr bool ROLL = Q == kQueryRolling;
     static_assert(!ROLL || (!CM && !SPLIT && DS == 0 && CPL == 1), "rolling rows: row-major destination, one column a lane (with 2 and 4 hipcc put the block's results in scratch)");
+    // PROJ (sprintz_mi355x_project_rows): a plain decode, or float rows, whose staged block holds only the K columns a slot table names.  A lane
+    // loads its column's slot once; a selected column is staged at slot * ESZ of rows of K * ESZ bytes, an unselected one at a spare place behind
+    // the projected block that no piece reads.  Every output-byte quantity -- row_stride, blk_bytes, the chunk's base in the descriptor, the
+    // descriptor's span, the tail -- counts K columns; blk_elems and out_left keep counting all D, as the stream and d_rets do.  The projected
+    // block is a whole number of 16-byte pieces (the launch checks), a projected ROW need not be: a piece may wrap from one row into the next, so
+    // the scale and the offset of its element j are slot (c0 + j) % K's.  Unconverted or converted is a wave-uniform switch (filter.mode).
+    constexpr bool PROJ = Q == kQueryProject;
+    static_assert(!PROJ || (!CM && !SPLIT && DS == 0 && CPL == 1), "project rows: row-major destination, one column a lane");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
     constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -264,13 +272,21 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     //  end of the last column; offsets are column*col_stride + row, in bytes)
     const uint32_t rows_per_chunk = CM ? a.chunk_len / (uint32_t)(EXACT ? DCAP : a.D) : 0u;
     // float rows: the output element's bytes, and the shift that turns a byte offset among decoded elements into one among converted ones
-    const uint32_t OSZ = FLT ? (uint32_t)float_out_bytes(a.filter.mode) : (uint32_t)ESZ;
-    const uint32_t fshift = FLT ? (OSZ == 4u ? (ESZ == 1 ? 2u : 1u) : (ESZ == 1 ? 1u : 0u)) : 0u;
-    const uint64_t out_base = FLT ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * OSZ
+    // (project rows: the same two, with the element type itself as one more format -- pflt: the pieces convert; and the elements of a chunk's
+    //  projected slot, R x K)
+    const bool pflt = PROJ && !(a.filter.mode & kProjectRawBit);
+    const uint32_t OSZ = FLT ? (uint32_t)float_out_bytes(a.filter.mode) : PROJ ? (uint32_t)project_out_bytes(a.filter.mode, ESZ) : (uint32_t)ESZ;
+    const uint32_t fshift = FLT ? (OSZ == 4u ? (ESZ == 1 ? 2u : 1u) : (ESZ == 1 ? 1u : 0u))
+                          : PROJ ? (OSZ == 4u ? (ESZ == 1 ? 2u : 1u) : (OSZ == 2u && ESZ == 1 ? 1u : 0u)) : 0u;
+    const uint32_t pK = PROJ ? project_k(a) : 0u;
+    const uint32_t pslot_elems = PROJ ? a.chunk_len / (uint32_t)(EXACT ? DCAP : a.D) * pK : 0u;
+    const uint64_t out_base = PROJ ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)pslot_elems * OSZ
+                            : FLT ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * OSZ
                             : CM ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)rows_per_chunk * ESZ
                             : SELECT ? 0
                                  : (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * ESZ;
-    const uint64_t out_span = FLT ? a.nchunks * (uint64_t)a.chunk_len * OSZ - out_base
+    const uint64_t out_span = PROJ ? a.nchunks * (uint64_t)pslot_elems * OSZ - out_base
+                            : FLT ? a.nchunks * (uint64_t)a.chunk_len * OSZ - out_base
                             : CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
                             : GATHER ? a.gather.nranges * (uint64_t)a.gather.rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
                             : SELECT ? a.select.capacity * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
@@ -351,8 +367,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 
     const uint32_t hdr_bytes = (2u * (uint32_t)D * HB + 7u) >> 3;
     const uint32_t blk_elems = 8u * (uint32_t)D;
-    const uint32_t blk_bytes = blk_elems * ESZ;
-    const uint32_t row_stride = (uint32_t)D * ESZ;
+    const uint32_t blk_bytes = PROJ ? 8u * pK * ESZ : blk_elems * ESZ;      // (project rows: the bytes of a staged, projected block and of its rows)
+    const uint32_t row_stride = PROJ ? pK * ESZ : (uint32_t)D * ESZ;
     const int col0 = lane_d * CPL;                         // first column of this lane
     // A lane column past the last one (ndims is not DP*CPL) stands in for column D-1: it reads the same header fields and
     // bit fields, runs the same recurrence and stages the same bytes at the same place as the genuine one -- so the per-sample
@@ -378,6 +394,16 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             colk[k] = EXACT ? genk[k] : (genk[k] < D ? genk[k] : D - 1);
         }
         stage_k[k] = stage + colk[k] * ESZ;
+    }
+    // project rows: the lane's slot (a stand-in lane takes its genuine twin's: the same bytes at the same place) and the stride of its staged rows
+    // -- 0 for a column that is not selected, whose 8 samples all go to the spare bytes behind the projected block (8 K ESZ <= 8 D ESZ, and the
+    // carve ends 16 bytes behind that: geom.h, decode_fast_lds_bytes)
+    uint32_t prs = 0;
+    if constexpr (PROJ) {
+        const uint32_t sl = (uint32_t)project_slot(a, (uint32_t)colk[0]);
+        const bool psel = sl < pK;
+        prs = psel ? row_stride : 0u;
+        stage_k[0] = stage + (psel ? sl * ESZ : blk_bytes);
     }
 
     uint32_t pv[CPL];
@@ -630,7 +656,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // float rows: the scale and the offset of every element of each of this lane's store pieces (a row is a whole number of pieces, so piece
     // q starts in the same column of its row in every block); a piece past the block's end (never stored) reads some row's columns too
     constexpr int FNE = 128 / W;                           // elements of a 16-byte piece
-    float fsc[FLT ? PIECES : 1][FNE], fof[FLT ? PIECES : 1][FNE];
+    float fsc[(FLT || PROJ) ? PIECES : 1][FNE], fof[(FLT || PROJ) ? PIECES : 1][FNE];
     if constexpr (FLT) {
 #pragma unroll
         for (int q = 0; q < PIECES; q++) {
@@ -642,9 +668,25 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
     }
+    // (project rows: a block is a whole number of pieces and of rows, so piece q starts in the same slot in every block -- but a piece may run
+    //  over a row's end into the next row's first slots: element j is slot (c0 + j) % K's, always inside the K entries)
+    if constexpr (PROJ) {
+        if (pflt) {
+#pragma unroll
+            for (int q = 0; q < PIECES; q++) {
+                uint32_t c = ((lane16 + (uint32_t)q * ROW16) / ESZ) % pK;
+#pragma unroll
+                for (int j = 0; j < FNE; j++) {
+                    fsc[q][j] = float_scale(a, c);
+                    fof[q][j] = float_offset(a, c);
+                    c = c + 1u == pK ? 0u : c + 1u;
+                }
+            }
+        }
+    }
     // a held or immediate piece leaves converted: output piece j of it 16 j bytes behind vo, or nowhere
     auto float_store = [&](const uint4& t, int q, uint32_t vo) {
-        if constexpr (FLT) {
+        if constexpr (FLT || PROJ) {
             float_piece<W>(t, a.filter.mode, fsc[q], fof[q], [&](int j, const uint4& p) {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, p), orsrc, vo == kDropStore ? kDropStore : vo + 16u * (uint32_t)j, 0, kStoreAux);
             });
@@ -893,11 +935,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 in = in && ((sm >> prow[q]) & 1u) && p < a.select.capacity;
                 vo = (uint32_t)p * row_stride + pcol[q];   // (select.capacity rows fit 32-bit offsets: the launch checks)
             }
-            if constexpr (FLT) vo = ovo + (u << fshift);   // ovo counts output bytes; the piece's OSZ / ESZ output pieces follow each other
+            if constexpr (FLT || PROJ) vo = ovo + (u << fshift);   // ovo counts output bytes; the piece's OSZ / ESZ output pieces follow each other
             const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
             if constexpr (FLT) {
                 if (slot >= 0) { held[slot][q] = t; held_vo[slot][q] = in ? vo : kDropStore; }
                 else float_store(t, q, in ? vo : kDropStore);
+            } else if constexpr (PROJ) {                   // held as it is; converted, or not, where it is stored
+                if (slot >= 0) { held[slot][q] = t; held_vo[slot][q] = in ? vo : kDropStore; }
+                else if (pflt) float_store(t, q, in ? vo : kDropStore);
+                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), orsrc, in ? vo : kDropStore, 0, kStoreAux);
             } else
             if (slot >= 0) {
                 held[slot][q] = t;
@@ -920,7 +966,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             }
         }
         wave_lds_sync();
-        ovo += FLT ? blk_bytes << fshift : blk_bytes;
+        ovo += (FLT || PROJ) ? blk_bytes << fshift : blk_bytes;
     };
     auto run_blocks = [&](uint32_t len) {                  // RUN slot: `len` blocks of zero error (:828-958)
         if constexpr (Q == kQueryFilter && !FIRE) {
@@ -1153,7 +1199,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
                     if constexpr (!query_reduce_only(Q) && !CM && !ROLL)
-                        if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];
+                        if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];
 #endif
                 }
                 q_block(k);
@@ -1284,7 +1330,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
                 if constexpr (!query_reduce_only(Q) && !CM && !ROLL)
-                    if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * row_stride) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
+                    if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
 #else
                 asm volatile("" :: "v"(pv[k]));
 #endif
@@ -1427,7 +1473,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             srow0 = chunk * (uint64_t)a.select.rpc;
         }
         out_left = a.chunk_len;
-        ovo = FLT ? (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * OSZ)
+        ovo = PROJ ? (uint32_t)((chunk - wave_first) * (uint64_t)pslot_elems * OSZ)
+          : FLT ? (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * OSZ)
           : CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
           : GATHER ? (uint32_t)(uint64_t)(gp.obase * ESZ)  // where the chunk's row 0 would land: only rows [lo, hi) are stored, and those lie in `out`
                  : (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * ESZ);
@@ -1543,6 +1590,19 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
                 for (int q = 0; q < PIECES; q++) float_store(held[s2][q], q, held_vo[s2][q]);
+        } else if constexpr (PROJ) {                       // one wave-uniform switch a step: the held pieces leave converted, or as they are
+            if (pflt) {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+                    for (int q = 0; q < PIECES; q++) float_store(held[s2][q], q, held_vo[s2][q]);
+            } else {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+                    for (int q = 0; q < PIECES; q++)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, held[s2][q]), orsrc, held_vo[s2][q], 0, kStoreAux);
+            }
         } else if constexpr (!query_reduce_only(Q) && !ROLL) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
@@ -1654,6 +1714,9 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // the tail walks row by row at plain 64-bit addresses, then the chunk leaves its count and last rows for the seam pass (decode_ops.h)
         if (!corrupt) rolling_tail<W, CPL>(a, chunk, rollp, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, rsum);
         rolling_leave<W, CPL>(a, chunk, rollp, corrupt ? 0u : out_elems + remaining, (uint32_t)D, genk, col_ok, lane_d);
+    } else if constexpr (PROJ) {
+        // the tail's selected columns leave element by element, at plain 64-bit addresses (decode_ops.h: project_tail)
+        if (!corrupt && remaining > 0) project_tail<W>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP);
     } else if constexpr (FLT) {
         // the tail converts element by element, at plain 64-bit addresses (decode_ops.h: float_tail)
         if (!corrupt && remaining > 0) float_tail<W>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP);

@@ -248,6 +248,19 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         ffmt = a.filter.mode & 3u;
         fsb = float_sign_bit<W>(a.filter.mode);
     }
+    // project rows: each of the lane's columns' slot in the output row, K for "not selected" (any entry outside 0 .. K - 1), and the chunk's first row
+    uint32_t pslot[CPL];
+    uint32_t pK = 0;
+    uint64_t prow0 = 0;
+    if constexpr (Q == kQueryProject) {
+        pK = project_k(a);
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+            const uint32_t sl = genk[k] ? (uint32_t)project_slot(a, (uint32_t)colk[k]) : pK;
+            pslot[k] = sl < pK ? sl : pK;
+        }
+        prow0 = chunk * (uint64_t)(a.chunk_len / (uint32_t)D);
+    }
     // rolling rows: each column's running sum over its window; the chunk's ring is the group's LDS (a.table.table_off is 0 in this kernel's launch)
     uint32_t rsum[CPL];
     uint32_t rrun = 0;                               // the blocks of a delta run behind this one, in a row
@@ -562,6 +575,18 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     for (int i = 0; i < 8; i++) float_put(a.out, ffmt, eb + (uint64_t)(i * D + col), float_value(v[i][k], fsb, fsc[k], fof[k]));
                 }
             }
+        } else if constexpr (Q == kQueryProject) {
+            // the selected columns' samples, each at its slot of its output row (out_elems + blk_elems <= chunk_len: checked above, so the
+            // rows lie inside the chunk's R); 64-bit addresses, so this kernel takes every layout, every K and every alignment of the output
+            (void)ob;
+            const uint64_t rb = prow0 + out_elems / (uint32_t)D;
+#pragma unroll
+            for (int k = 0; k < CPL; k++) {
+                if (pslot[k] < pK) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) project_put<W>(a, (rb + (uint64_t)i) * (uint64_t)pK + pslot[k], v[i][k], pslot[k]);
+                }
+            }
         } else if (cs) {
             const uint32_t r0 = out_elems / (uint32_t)D;
 #pragma unroll
@@ -680,6 +705,11 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     }
     if constexpr (Q == kQueryFloat) {
         if (!corrupt) float_tail<W>(a, chunk, s + pos, out_elems, remaining, (uint32_t)D, lane_d, DP);
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        return;
+    }
+    if constexpr (Q == kQueryProject) {
+        if (!corrupt) project_tail<W>(a, chunk, s + pos, out_elems, remaining, (uint32_t)D, lane_d, DP);
         if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }

@@ -36,12 +36,12 @@ struct GatherArgs {
 // filter rows (Q == kQueryFilter; sprintz_mi355x_filter_rows): row r of chunk c matches if every (mode 0) / some (mode 1) column d
 // has lo[d] <= x <= hi[d], unsigned; bit r & 7 of mask[c * mask_stride + (r >> 3)], the chunk's matches in counts[c]
 struct FilterArgs {
-    const void* lo;             // [D], element type, on the device (float rows: the scale, float32 [D] or null)
+    const void* lo;             // [D], element type, on the device (float rows: the scale, float32 [D] or null; project rows: of every slot, [K])
     const void* hi;             // (float rows: the offset)
     uint32_t mode;              // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter (float rows: format | kFloatSignedBit)
-    uint8_t* mask;              // optional
+    uint8_t* mask;              // optional (project rows: the slot table, int32 [D])
     uint32_t* counts;           // optional
-    uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8)
+    uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8) (project rows: K, the columns of an output row)
 };
 // the rows that select, aggregate, histogram, moments, group-by and extrema rows take: those whose bits are set in chunk c's mask bytes
 // mask[c * stride ...] (filter_rows' layout).  mask == null -- where the operation allows it -- is every existing row: a run-time,
@@ -1350,6 +1350,37 @@ __device__ __forceinline__ void float_piece(const uint4& t, uint32_t mode, const
             h[j] = fmt == kFloatF16 ? float_to_f16(z[2 * j]) | (float_to_f16(z[2 * j + 1]) << 16) : float_to_bf16(z[2 * j]) | (float_to_bf16(z[2 * j + 1]) << 16);
 #pragma unroll
         for (int q = 0; q < NE / 8; q++) store(q, make_uint4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]));
+    }
+}
+
+// ---- project rows (Q == kQueryProject; sprintz_mi355x_project_rows): a plain decode, or float rows, that stores K of the D columns.  Row r
+// of chunk c is row c * R + r of a dense [rows, K] output, R = chunk_len / D, and column d leaves at slot slots[d] of it -- or nowhere: any
+// table entry outside 0 .. K - 1 (tested unsigned) is "not selected", so a bad table misplaces data inside the output and never writes
+// outside it.  The arguments travel in FilterArgs, as float rows' do: filter.lo / filter.hi the scale and the offset of every SLOT (float32
+// [K], or null), filter.mode float rows' word with kProjectRawBit for "the element type, unconverted", filter.mask the slot table (int32
+// [D]) and filter.mask_stride K.
+__device__ __forceinline__ uint32_t project_k(const DecodeArgs& a) { return a.filter.mask_stride; }
+__device__ __forceinline__ int32_t project_slot(const DecodeArgs& a, uint32_t col) { return ((const int32_t*)a.filter.mask)[col]; }
+// one element to place idx of the output, plain 64-bit addresses (the generic kernel's blocks, every kernel's tail); mode is wave-uniform
+template <int W>
+__device__ __forceinline__ void project_put(const DecodeArgs& a, uint64_t idx, uint32_t x, uint32_t slot)
+{
+    using U = typename Elem<W>::U;
+    const uint32_t mode = a.filter.mode;
+    if (mode & kProjectRawBit) ((U*)a.out)[idx] = (U)x;
+    else float_put(a.out, mode & 3u, idx, float_value(x, float_sign_bit<W>(mode), float_scale(a, slot), float_offset(a, slot)));
+}
+// The verbatim tail: `remaining` elements at t behind the chunk's `out_elems` (a multiple of 8 * D: element e of the tail is in row
+// out_elems / D + e / D and column e % D), spread over the group's lanes.  Only elements that exist are written: a batch that ends
+// mid-row leaves the rest of that output row as it was.
+template <int W>
+__device__ __forceinline__ void project_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t out_elems, uint32_t remaining, uint32_t D, int lane_d, int DP)
+{
+    const uint32_t K = project_k(a);
+    const uint64_t row0 = chunk * (uint64_t)(a.chunk_len / D) + out_elems / D;
+    for (uint32_t e = (uint32_t)lane_d; e < remaining; e += (uint32_t)DP) {
+        const uint32_t slot = (uint32_t)project_slot(a, e % D);
+        if (slot < K) project_put<W>(a, (row0 + e / D) * (uint64_t)K + slot, tail_elem<W>(t, e), slot);
     }
 }
 

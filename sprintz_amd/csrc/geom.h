@@ -36,10 +36,12 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 13 = segment: per run of rows that a mask names (or per stretch between two set bits) its start, length and min / max / sum, placed behind the chunk's base, reduce only;
 // 14 = float: a plain decode whose stores convert -- every sample leaves as fl32(fl32(x * scale[d]) + offset[d]) in float32, float16 or bfloat16, never as an integer;
 // 15 = rolling: per element the min / max / sum of its column over the W rows that end at its row (a trailing window, clipped at the chunk's first row
-// inside the launch; the seam pass of decode_rolling.hip carries it over the chunk seams), stored at the element's place in place of the element.
+// inside the launch; the seam pass of decode_rolling.hip carries it over the chunk seams), stored at the element's place in place of the element;
+// 16 = project: a plain decode (or float rows) that stores only the K columns a slot table names, each at its slot of a dense [rows, K] output.
 // 6 .. 11 and 13 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
               kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14, kQueryRolling = 15;
+constexpr int kQueryProject = 16;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
@@ -49,6 +51,9 @@ constexpr bool query_reduce_only(int q)
 // an output element's bytes
 constexpr uint32_t kFloatF32 = 0, kFloatF16 = 1, kFloatBF16 = 2, kFloatSignedBit = 4;
 constexpr int float_out_bytes(uint32_t mode) { return (mode & 3u) == kFloatF32 ? 4 : 2; }
+// project rows: the same word, with one bit more for "the element type, unconverted"; an output element's bytes
+constexpr uint32_t kProjectRawBit = 8;
+constexpr int project_out_bytes(uint32_t mode, int esz) { return (mode & kProjectRawBit) ? esz : float_out_bytes(mode); }
 // rolling rows: the ops (SPRINTZ_ROLL_MIN / _MAX / _SUM, WindowArgs::ops) and the LDS a workgroup's launch can be given.  A chunk's history
 // ring holds the last W + 8 raw rows of its columns, column by column (a lane reads 8 rows of a column as one piece), rounded up to 16 bytes
 constexpr uint32_t kRollMin = 1, kRollMax = 2, kRollSum = 4;

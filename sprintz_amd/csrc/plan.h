@@ -41,13 +41,14 @@ struct Shape {
     unsigned src_lo = 0, slots_lo = 0, out_lo = 0, comp_lo = 0;   // the low four bits of the source, slot, output and container addresses
     uint64_t slot_stride = 0;
     uint64_t nranges = 0;                  // gather
-    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W
+    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W; project rows: the columns K of the output
     uint64_t capacity = 0;                 // select: rows of the output
     // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
     // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
     uint32_t table_entries = 0, table_row_max = 0;
     // the element bytes on the float side (4, or 2 for float16 / bfloat16): float rows' output element -- what every bound on output BYTES
-    // counts in -- and, for an encode with q == kQueryFloat, the float source's element; 0: the call has no float side
+    // counts in (project rows: the output element whatever it is, esz unconverted) -- and, for an encode with q == kQueryFloat, the float
+    // source's element; 0: the call has no float side
     int out_esz = 0;
 };
 
@@ -208,6 +209,37 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
             return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "rolling_rows: window_rows must be a multiple of 8 whose history rings fit a workgroup's LDS (roll_shape_max_window)");
         p.lds_group_stride = (uint32_t)ring;
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * groups);
+    }
+
+    // project rows (K in s.rows; s.out_esz the bytes of an output element: esz for the element type, 4 / 2 for the floats).  A chunk's R = chunk_len / D
+    // rows leave as R x K elements from output element c x R x K on.  decode_fast.h takes, on its one-column-a-lane mappings (up to 64 columns), every
+    // shape the plain decode takes there whose PROJECTED block, 8 K esz bytes, is a whole number of 16-byte store pieces -- every K at 16 bits, the even
+    // ones at 8 -- with the reach of the store descriptor counted in projected output bytes.  A chunk's projected slot need not be a multiple of 16
+    // bytes: its pieces are then stored at addresses aligned to the output element alone.  With two and four columns a lane the mode is not instantiated
+    // (plan.h names no such mapping), and everything else runs the generic kernel, which stores element by element at 64-bit addresses and stages nothing.
+    if (s.q == kQueryProject) {
+        const uint32_t K = s.rows;
+        if (K == 0 || K > (uint32_t)D) return plan_fail(p, SPRINTZ_E_INVALID, "project_rows: ncolumns must be in 1 .. ndims");
+        if (D > 512 || norle || cs) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "project_rows: the RLE codecs, row-major, at most 512 columns");
+        const int posz = s.out_esz ? s.out_esz : esz;
+        const uint64_t slot_bytes = (uint64_t)(chunk_len / (uint32_t)D) * K * (uint64_t)posz;      // a chunk's projected output
+        const FastMap f = decode_fast_map(esz, D, 0, false);
+        const bool fast = !lowdim && !s.noheader && f.cpl == 1 && 2 * D > f.dp * f.cpl && (uint64_t)chunk_len * esz * 2 >= f.ring && !k.no_fast &&
+                          // the plain decode's terms for the shape (whole 16-byte pieces a block and a chunk, a 16-byte aligned output) ...
+                          ((uint64_t)8 * D * esz) % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0 && (s.out_lo % 16) == 0 &&
+                          // ... and the projection's: whole pieces a projected block, the wave's chunks within reach of 32-bit offsets
+                          ((uint64_t)8 * K * esz) % 16 == 0 && slot_bytes * 64 * 64 < 0xf0000000ull;
+        if (fast) {
+            p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
+            p.exact = D == f.dp * f.cpl;
+            p.log2DP = f.log2dp;
+            p.lds_group_stride = f.ring;
+            p.vec_store = 1;
+            p.chunks_per_group = (uint32_t)k.chunks_per_group;
+            const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
+            return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * (kThreads / f.dp));
+        }
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, 0);
     }
 
     // 513 .. 2047 columns: one workgroup per chunk (any_ndims.hip) -- the RLE codecs, row-major, plain decode

@@ -1,5 +1,5 @@
 // row_ops.hip -- the row operations of the C-ABI (include/sprintz_mi355x.h): queries, the zone map, filters, select, aggregate,
-// moments, extrema, segments, float rows, rolling rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
+// moments, extrema, segments, float rows, rolling rows, project rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
 // fills its QuerySpec and hands over to decode_batch (entry.h); what the decoders then do with a row is decode_ops.h's.
 #include "entry.h"
 
@@ -520,6 +520,42 @@ int sprintz_mi355x_rolling_rows(int codec, int elem_bytes, const void* d_comp, c
     a.lin = qs.lin;
     if (launch_rolling_seam(elem_bytes, a, (hipStream_t)hip_stream) != hipSuccess) return fail(SPRINTZ_E_HIP, "rolling_rows seam kernel launch");
     return 0;
+}
+
+// ---------------------------------------------------------------- project rows
+int sprintz_mi355x_project_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                uint32_t chunk_len, uint32_t ndims, const int32_t* d_slots, uint32_t ncolumns, int format,
+                                const float* d_scale, const float* d_offset, uint32_t flags, void* d_out, int64_t* d_rets, void* hip_stream)
+{
+    if (ndims > 0xffffu) return fail(SPRINTZ_E_UNSUPPORTED, "project_rows: more than 512 columns");
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, (uint16_t)ndims};
+    // (the signed bit is float rows' flag: the shared checks see the rest)
+    int rc = unmasked_row_op("project_rows", b, flags & ~(uint32_t)SPRINTZ_FLOAT_SIGNED);
+    if (rc) return rc;
+    if (ncolumns == 0) return fail_op(SPRINTZ_E_INVALID, "project_rows", "ncolumns == 0: an output row has at least one column");
+    if (ncolumns > ndims) return fail_op(SPRINTZ_E_INVALID, "project_rows", "ncolumns above ndims: the columns of the output are distinct columns of the batch");
+    static_assert(SPRINTZ_PROJECT_F32 == 1 + SPRINTZ_FLOAT_F32 && SPRINTZ_PROJECT_F16 == 1 + SPRINTZ_FLOAT_F16 && SPRINTZ_PROJECT_BF16 == 1 + SPRINTZ_FLOAT_BF16,
+                  "a float format travels as float rows' number");
+    if (format != SPRINTZ_PROJECT_RAW && format != SPRINTZ_PROJECT_F32 && format != SPRINTZ_PROJECT_F16 && format != SPRINTZ_PROJECT_BF16)
+        return fail(SPRINTZ_E_INVALID, "project_rows: format must be SPRINTZ_PROJECT_RAW, SPRINTZ_PROJECT_F32, SPRINTZ_PROJECT_F16 or SPRINTZ_PROJECT_BF16");
+    const bool raw = format == SPRINTZ_PROJECT_RAW;
+    if (raw && (d_scale || d_offset || (flags & SPRINTZ_FLOAT_SIGNED)))
+        return fail_op(SPRINTZ_E_INVALID, "project_rows", "d_scale, d_offset and SPRINTZ_FLOAT_SIGNED go with a float format only");
+    if (!d_slots || !d_out) return fail(SPRINTZ_E_INVALID, "project_rows: null device pointer");
+    const uint32_t mode = raw ? kProjectRawBit : (uint32_t)(format - 1) | ((flags & SPRINTZ_FLOAT_SIGNED) ? kFloatSignedBit : 0u);
+    if ((uintptr_t)d_out % (uintptr_t)project_out_bytes(mode, elem_bytes)) return fail(SPRINTZ_E_INVALID, "project_rows: d_out must be aligned to the output element size");
+    if ((uintptr_t)d_slots % 4 || (uintptr_t)d_scale % 4 || (uintptr_t)d_offset % 4 || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "project_rows: d_slots, d_scale and d_offset must be aligned to 4 bytes, d_rets to 8");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    // the mode shares FilterArgs, as float rows do (decode_ops.h, project rows): lo the scale, hi the offset, mode the format; mask the slot table, mask_stride K
+    QuerySpec qs = row_query(kQueryProject, flags);
+    qs.filter.lo = d_scale;
+    qs.filter.hi = d_offset;
+    qs.filter.mode = mode;
+    qs.filter.mask = (uint8_t*)const_cast<int32_t*>(d_slots);
+    qs.filter.mask_stride = ncolumns;
+    return decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
 }
 
 // ---------------------------------------------------------------- histogram rows

@@ -1,6 +1,6 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, rolling_rows' window rules, counts, mean and scratch size, the default bin shift, bounds and offsets as tensors, the
+moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, project_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, rolling_rows' window rules, counts, mean and scratch size, project_rows' slot table, the default bin shift, bounds and offsets as tensors, the
 linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
@@ -266,6 +266,24 @@ def rolling_mean(total, counts):
 def rolling_tmp_bytes(nchunks, W, ndims, esz):
     """the seam scratch rolling_rows needs with more than one chunk (include/sprintz_mi355x.h: d_tmp), a multiple of 16 bytes a chunk"""
     return nchunks * ((16 + (W - 1) * ndims * esz + 15) & ~15) if nchunks > 1 else 0
+
+
+def project_slots(columns, ndims, device=None):
+    """project_rows' columns -> the slot table the library reads, int32 [ndims] on `device`: slots[c_j] = j, -1 for a column that is not
+    wanted.  columns: K >= 1 distinct ints in 0 .. ndims - 1, in any order (a permutation, and the identity, are legal)."""
+    cols = columns.tolist() if torch.is_tensor(columns) or isinstance(columns, np.ndarray) else list(columns)
+    if not cols:
+        raise ValueError("columns must name at least one column")
+    slots = [-1] * ndims
+    for j, c in enumerate(cols):
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+            raise ValueError(f"columns must be ints, not {c!r}")
+        if not 0 <= c < ndims:
+            raise ValueError(f"column {c} is outside 0 .. {ndims - 1}")
+        if slots[c] >= 0:
+            raise ValueError(f"column {c} is named twice")
+        slots[c] = j
+    return torch.tensor(slots, dtype=torch.int32, device=device)
 
 
 def default_shift(W, nbins):
