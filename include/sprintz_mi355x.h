@@ -54,7 +54,7 @@ extern "C" {
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
  *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
  *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR;
- *      rolling_rows, SPRINTZ_ROLL_*; project_rows, SPRINTZ_PROJECT_* */
+ *      rolling_rows, SPRINTZ_ROLL_*; project_rows, SPRINTZ_PROJECT_*; cumulative_rows / cumulative_tmp_bytes, SPRINTZ_CUM_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -1053,6 +1053,49 @@ int sprintz_mi355x_rolling_rows(int codec, int elem_bytes, const void* d_comp, c
 int sprintz_mi355x_project_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                 uint32_t chunk_len, uint32_t ndims, const int32_t* d_slots, uint32_t ncolumns, int format,
                                 const float* d_scale, const float* d_offset, uint32_t flags, void* d_out, int64_t* d_rets, void* hip_stream);
+/* Cumulative rows: per element, its column's running minimum / maximum / sum from the batch's first row to its own row -- cummin, cummax and cumsum
+ * (the expanding window; pandas' expanding()) -- straight from the compressed batch; the decoded tensor never exists.  The batch is given as to
+ * sprintz_mi355x_rolling_rows (chunk_len % ndims == 0; the RLE codecs; at most 512 columns; a short last chunk may end mid-row: a column has the
+ * rows it has).  The batch's rows are g = 0 .. G - 1, row g being row g % R of chunk g / R, R = chunk_len / ndims.  For every element that exists,
+ * in row g and column d:
+ *   min[g, d] = min(seed_min[d], x[0 .. g, d])        unsigned, in the element type
+ *   max[g, d] = max(seed_max[d], x[0 .. g, d])        unsigned, in the element type
+ *   sum[g, d] = seed_sum[d] + sum(x[0 .. g, d])       modulo 2^64, stored as an int64 (sum_bytes 8) or its low 32 bits as an int32 (sum_bytes 4)
+ * placed where decompress_batch places the element: element e of chunk c at out[c * chunk_len + e]; nothing is written past a chunk's decoded
+ * count.  The samples are the ones sprintz_mi355x_decompress_batch writes under the same options, SPRINTZ_OPT_REF_DECODER_QUIRK included.  An
+ * expanding mean is the sum divided by the rows so far, g + 1.
+ *   ops        : a non-empty OR of SPRINTZ_CUM_MIN / _MAX / _SUM; an output must be given exactly where its op is
+ *   sum_bytes  : 4 or 8, the bytes of an element of d_sum (checked whatever ops holds)
+ *   flags      : SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else
+ *   d_carry_in : (optional) the seeds, uint64 [3 * ndims]: a min row, a max row and a sum row.  The min and the max seeds are read modulo 2^(8
+ *                elem_bytes).  NULL: the identities -- all ones of the element type, 0 and 0.
+ *   d_carry_out: (optional) the same layout: the state behind the batch's last element of each column.  carry_out of one call, given as carry_in
+ *                to the next, yields exactly the cumulative of the concatenated batches: this is how a stream longer than one batch, or one rank's
+ *                share of it, is continued.  The row of an op that was not asked for is its seed, passed through.  It may be the buffer d_carry_in is.
+ *   d_tmp      : with nchunks > 1, scratch of sprintz_mi355x_cumulative_tmp_bytes(nchunks, ndims) bytes, 16-byte aligned (36 bytes a chunk and
+ *                column, 8 a chunk, and rounding: the chunks' entering states, and the totals they are made from).  Its content before the call does
+ *                not matter.  Ignored (may be NULL) with nchunks <= 1, for which cumulative_tmp_bytes returns 0.
+ *   d_rets     : (optional) exactly what sprintz_mi355x_decompress_batch writes for the same batch, damaged chunks included
+ * A damaged chunk (d_rets < 0) contributes the identity to everything behind it and to d_carry_out: the chunks behind it continue from the state
+ * in front of it.  Its own slot of the outputs is unspecified; nothing outside that slot is touched.
+ * With nchunks > 1, three launches on the stream, none of which waits for a workgroup of its own or of another launch: the totals (the windowed
+ * query with one window a chunk: every chunk's min / max / sum and return value into d_tmp), the scan (a workgroup a column walks the chunks and
+ * leaves each chunk's entering state, seeded with d_carry_in; it writes d_carry_out) and the decode (SPRINTZ_KF_DEC_FAST for rows of whole 16-byte
+ * pieces of 8 .. 64 columns with every output 16-byte aligned; SPRINTZ_KF_DEC_GENERIC otherwise), in which a lane keeps the running values of its
+ * column in registers.  With one chunk the decode alone, which reads d_carry_in and writes d_carry_out itself.  nchunks == 0 launches nothing, or,
+ * with d_carry_out given, one tiny kernel that copies the seeds there.  No synchronisation, no allocation.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown flag, ops outside
+ * 1..7, an op without its output or an output without its op, sum_bytes other than 4 or 8, d_min / d_max not aligned to the element size, d_sum
+ * to sum_bytes, d_carry_in / d_carry_out / d_rets to 8, d_tmp to 16, d_tmp missing with nchunks > 1; SPRINTZ_E_UNSUPPORTED for more than 512
+ * columns and for the non-RLE codecs. */
+#define SPRINTZ_CUM_MIN 1u
+#define SPRINTZ_CUM_MAX 2u
+#define SPRINTZ_CUM_SUM 4u
+size_t sprintz_mi355x_cumulative_tmp_bytes(uint64_t nchunks, uint16_t ndims);
+int sprintz_mi355x_cumulative_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                   uint32_t chunk_len, uint16_t ndims, uint32_t ops, int sum_bytes /* 4 or 8 */, uint32_t flags,
+                                   void* d_min, void* d_max, void* d_sum, const uint64_t* d_carry_in, uint64_t* d_carry_out,
+                                   void* d_tmp, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

@@ -816,6 +816,56 @@ class ChunkedCodec:
                 res.view({1: torch.int8, 2: torch.int16, 4: torch.int32}[res.element_size()])[G - 1, lacks] = 0
         return res
 
+    def cumulative_rows(self, batch, ops=("min", "max", "sum"), sum_dtype=None, carry=None, return_carry=False, general_layout=False, check=True):
+        """Running min / max / sum / mean of every column from the first row on, one result per row -- cummin, cummax, cumsum and pandas'
+        expanding().mean() -- straight from the compressed batch: the decoded tensor never exists.  Batch row g is row g % R of chunk g // R,
+        R = chunk_len / ndims (chunk_len must be a multiple of ndims), and out[g, d] = op(seed[d], x[0 .. g, d]).
+
+        ops: any of "min", "max" (the codec's dtype, unsigned), "sum" (sum_dtype: torch.int64, the default, exact modulo 2^64, or torch.int32,
+        its low half) and "mean" (float64: the int64 sum over the rows so far; it needs int64 sums).  carry: what an earlier call returned
+        with return_carry=True -- the stream goes on where that batch ended, as if the two were one; None: a fresh start.
+        -> {op: [G, ndims]}, G = ceil(total_len / ndims); the columns a partial last row lacks hold 0.  With return_carry=True -> (that, carry).
+        One library call: with more than one chunk the chunks' totals, their scan and the decode.  A damaged chunk counts as no rows for
+        everything behind it; check=True raises SprintzError naming the first one."""
+        torch = self.torch
+        ops = rowops.normalise_ops(ops, rowops.CUMULATIVE_OPS, '"min", "max", "sum", "mean"')
+        sum_dtype = torch.int64 if sum_dtype is None else sum_dtype
+        if sum_dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"sum_dtype must be torch.int64 or torch.int32, not {sum_dtype}")
+        if "mean" in ops and sum_dtype != torch.int64:
+            raise ValueError('"mean" needs int64 sums: sum_dtype=torch.int32 keeps only the low half')
+        D, n = self.ndims, batch.nchunks
+        rowops.chunk_rows(self.chunk_len, D, "cumulative_rows")
+        G = -(-batch.total_len // D)
+        cin = None if carry is None else rowops.check_carry(carry, D, self.device)
+        cout = rowops.CumulativeCarry(torch.empty((3, D), dtype=torch.int64, device=self.device), (cin.rows if cin else 0) + G) if return_carry else None
+        want_sum = "sum" in ops or "mean" in ops
+        bits = (_lib.CUM_MIN if "min" in ops else 0) | (_lib.CUM_MAX if "max" in ops else 0) | (_lib.CUM_SUM if want_sum else 0)
+        raw = {}
+        for name, dt in (("min", self.dtype), ("max", self.dtype), ("sum", sum_dtype)):
+            if name in ops or (name == "sum" and want_sum):
+                raw[name] = torch.empty(max(n * self.chunk_len, 1), dtype=dt, device=self.device)
+        tmp = torch.empty(max(rowops.cumulative_tmp_bytes(n, D) // 16, 1) * 2, dtype=torch.int64, device=self.device)
+        rets = self._rets(n, check)
+        with self._on():
+            _lib.check(_lib.cumulative_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n, self.chunk_len, D,
+                                            bits, 8 if sum_dtype == torch.int64 else 4, self._general(general_layout),
+                                            _ptr(raw.get("min")), _ptr(raw.get("max")), _ptr(raw.get("sum")),
+                                            _ptr(cin.table if cin else None), _ptr(cout.table if cout else None), tmp.data_ptr(), _ptr(rets), self._stream()))
+        if check and n:
+            rowops.raise_damaged("cumulative_rows", rets, n, _lib.SprintzError)
+        res = {}
+        for name, v in raw.items():
+            v = v[: G * D]
+            v[batch.total_len:] = 0
+            res[name] = v.view(G, D)
+        if "mean" in ops:
+            res["mean"] = rowops.cumulative_mean(res["sum"], cin.rows if cin else 0)
+            if batch.total_len < G * D:
+                res["mean"].view(-1)[batch.total_len:] = 0
+        res = {k: res[k] for k in ops}
+        return (res, cout) if return_carry else res
+
     def where(self, batch, lo, hi, mode="all", ids=False, general_layout=False, zones=None):
         """SELECT * WHERE: the rows that satisfy the bounds (filter_rows' lo / hi / mode), straight from the compressed batch -- the
         filter launch, a prefix sum of its counts and the select launch; the batch is never materialised.

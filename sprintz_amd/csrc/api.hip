@@ -303,15 +303,15 @@ const DecodeUnit kDecodeUnits[][2] = {SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS, 
                                       SPRINTZ_ROW_OP_UNITS(SPRINTZ_ROW_OP_UNIT_ROW)};
 #undef SPRINTZ_ROW_OP_UNIT_ROW
 #undef SPRINTZ_WIDTH_UNITS
-static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryProject + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
+static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryCumulative + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryProject) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryCumulative) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].generic(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryProject) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryCumulative) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].fast(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
@@ -392,6 +392,10 @@ Shape decode_shape(const Batch& b, const void* d_out, const QuerySpec& qs)
     if (qs.q == kQueryRolling) {                            // the window, the widest output element, and the low bits of every selected output
         s.rows = qs.win.rows;
         s.out_esz = (qs.win.ops & kRollSum) ? 4 : b.esz;
+        s.out_lo = low4(qs.win.min) | low4(qs.win.max) | low4(qs.win.sum);
+    }
+    if (qs.q == kQueryCumulative) {                         // the widest output element (win.count carries sum_bytes) and the low bits of every selected output
+        s.out_esz = (qs.win.ops & kCumSum) ? (int)qs.win.count : b.esz;
         s.out_lo = low4(qs.win.min) | low4(qs.win.max) | low4(qs.win.sum);
     }
     if (qs.q == kQueryProject) {                            // the columns of the output and the bytes of one of its elements

@@ -27,6 +27,8 @@
 //   * OUTPUT. the 8 x D block is transposed through LDS, leaves as dwordx4.
 #pragma once
 
+#include <type_traits>
+
 #include "decode_kernel.h"
 #include "group_ops.h"
 
@@ -189,6 +191,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // the scale and the offset of its element j are slot (c0 + j) % K's.  Unconverted or converted is a wave-uniform switch (filter.mode).
     constexpr bool PROJ = Q == kQueryProject;
     static_assert(!PROJ || (!CM && !SPLIT && DS == 0 && CPL == 1), "project rows: row-major destination, one column a lane");
+    // CUM (sprintz_mi355x_cumulative_rows): nothing of the raw block is stored.  A column's 8 rows wait in arow for q_block, which runs the running
+    // min / max / sum on (decode_ops.h: cumulative_step8) and keeps the block's results in registers (rres: the minima, the maxima, the sums' low
+    // and high words); behind the columns cum_out sends them through the plain decode's staging a plane at a time, as rolling rows do: the minima
+    // and the maxima as element-type planes to their own outputs, the sums sum_bytes / ESZ times the block's bytes, a quarter or an eighth of the
+    // block's rows at a pass.  No LDS of its own, and no barrier the plain decode has not.
+    constexpr bool CUM = Q == kQueryCumulative;
+    static_assert(!CUM || (!CM && !SPLIT && DS == 0 && CPL == 1), "cumulative rows: row-major destination, one column a lane");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
     constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -488,15 +497,18 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint32_t rsum[ROLL ? CPL : 1];
     uint32_t rblk = 0, rrun = 0;
     bool rinrun = false;
-    uint32_t rres[ROLL ? 3 : 1][ROLL ? CPL : 1][8];
+    // (cumulative rows: [0] minima, [1] maxima, [2] and [3] the sums' low and high words)
+    uint32_t rres[ROLL ? 3 : CUM ? 4 : 1][(ROLL || CUM) ? CPL : 1][8];
     if constexpr (ROLL) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) rsum[k] = 0;
     }
+    // cumulative rows: each column's running min / max / sum (set at each chunk start)
+    CumState cums[CUM ? CPL : 1];
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL || CUM) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -552,6 +564,16 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 rolling_step8<W>(a, rolling_ring<W>(rollp, a, (uint32_t)genk[k]), rblk, [&](int i) { return arow[i]; }, rsum[ROLL ? k : 0],
                                  !FIRE && SPRINTZ_ROLL_RUN_SHORTCUT && rinrun && rolling_run_settled(a, rrun),
                                  [&](uint32_t op, int j, uint32_t v) { rres[op == kRollMin ? 0 : op == kRollMax ? 1 : 2][k][j] = v; });
+        } else if constexpr (CUM) {                        // (a lane column past the last one has no results)
+            if (col_ok[k])
+                cumulative_step8<W>(a, [&](int i) { return arow[i]; }, cums[CUM ? k : 0], [&](uint32_t op, int j, uint64_t v) {
+                    if (op == kCumSum) {
+                        rres[CUM ? 2 : 0][k][j] = (uint32_t)v;
+                        rres[CUM ? 3 : 0][k][j] = (uint32_t)(v >> 32);
+                    } else {
+                        rres[op == kCumMin ? 0 : CUM ? 1 : 0][k][j] = (uint32_t)v;
+                    }
+                });
         } else if constexpr (MOM || GBY) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
@@ -829,7 +851,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         for (int k = 0; k < CPL; k++) {
             if (!col_ok[k]) continue;
 #pragma unroll
-            for (int i = 0; i < 8; i++) *(U*)(stage_k[k] + i * row_stride) = (U)(rres[ROLL ? which : 0][ROLL ? k : 0][i] >> shift);
+            for (int i = 0; i < 8; i++) *(U*)(stage_k[k] + i * row_stride) = (U)(rres[(ROLL || CUM) ? which : 0][(ROLL || CUM) ? k : 0][i] >> shift);
         }
         wave_lds_sync();
     };
@@ -892,6 +914,67 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             ovo += blk_bytes;
             rblk++;
             rrun = (!FIRE && run) ? rrun + 1u : 0u;
+        }
+    };
+    // cumulative rows: the block's results leave through the plain decode's staging, as rolling rows' do.  The sums -- OB bytes each, NP = OB / ESZ
+    // times the block's bytes -- are staged AS SUMS, in their output order, 8 / NP rows of the block at a pass: a pass fills exactly the block's
+    // staging (8 / NP rows x D x OB = 8 D ESZ bytes), and its 16-byte pieces lie in the output as they lie in LDS, so a store instruction writes one
+    // contiguous stretch.  (Joined from element-type planes instead, a lane's NP output pieces were 16 bytes of every 16 NP: the int64 sum's
+    // stores took 6.4 ms on the headline batch -- profiles/cumulative_rows.txt.)
+    auto cum_sum_out = [&](auto ob) __attribute__((always_inline)) {
+        if constexpr (CUM) {
+            constexpr int OB = decltype(ob)::value;
+            constexpr int NP = OB / ESZ, RPP = 8 / NP;     // passes a block, rows a pass
+            constexpr uint32_t cfs = NP == 2 ? 1u : NP == 4 ? 2u : 3u;      // element bytes -> sum bytes, as a shift
+            const uint32_t cspan = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((out_span << cfs) < 0xfffffff0ull ? (out_span << cfs) : 0xfffffff0ull));
+            const __amdgpu_buffer_rsrc_t crs_sum = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.win.sum + wave_uniform64(out_base << cfs)), 0, cspan, 0x00020000);
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                wave_lds_sync();                           // (the pieces of the pass before have been read)
+#pragma unroll
+                for (int k = 0; k < CPL; k++) {
+                    if (!col_ok[k]) continue;
+#pragma unroll
+                    for (int r = 0; r < RPP; r++) {
+                        uint8_t* const at = stage + (uint32_t)r * (uint32_t)D * OB + (uint32_t)genk[k] * OB;
+                        if constexpr (OB == 8) *(uint2*)at = make_uint2(rres[CUM ? 2 : 0][k][p * RPP + r], rres[CUM ? 3 : 0][k][p * RPP + r]);
+                        else *(uint32_t*)at = rres[CUM ? 2 : 0][k][p * RPP + r];
+                    }
+                }
+                wave_lds_sync();
+#pragma unroll
+                for (int q = 0; q < PIECES; q++) {
+                    const uint32_t u = lane16 + q * ROW16;
+                    const bool in = u < blk_bytes;
+                    const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), crs_sum, in ? (ovo << cfs) + (uint32_t)p * blk_bytes + u : kDropStore, 0, kStoreAux);
+                }
+            }
+        }
+    };
+    auto cum_out = [&]() __attribute__((always_inline)) {
+        if constexpr (CUM) {
+            // a descriptor an output, based like orsrc (wave-uniform: hipcc hoists them out of the step)
+            const uint32_t cspan = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(out_span < 0xfffffff0ull ? out_span : 0xfffffff0ull));
+            const __amdgpu_buffer_rsrc_t crs_min = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.win.min + wave_uniform64(out_base)), 0, cspan, 0x00020000);
+            const __amdgpu_buffer_rsrc_t crs_max = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.win.max + wave_uniform64(out_base)), 0, cspan, 0x00020000);
+#pragma unroll
+            for (int op = 0; op < 2; op++) {
+                if (!(a.win.ops & (op == 0 ? kCumMin : kCumMax))) continue;
+                roll_plane(op, 0u);
+#pragma unroll
+                for (int q = 0; q < PIECES; q++) {
+                    const uint32_t u = lane16 + q * ROW16;
+                    const bool in = u < blk_bytes;
+                    const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), op == 0 ? crs_min : crs_max, in ? ovo + u : kDropStore, 0, kStoreAux);
+                }
+            }
+            if (a.win.ops & kCumSum) {                     // (wave-uniform: sum_bytes is the call's)
+                if (a.win.count == 8u) cum_sum_out(std::integral_constant<int, 8>{});
+                else cum_sum_out(std::integral_constant<int, 4>{});
+            }
+            ovo += blk_bytes;                              // (nothing else is staged in this mode: the next plane's own barrier comes first)
         }
     };
     auto stage_out = [&](int slot) {
@@ -1198,7 +1281,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     q_row(k, i);
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL)
+                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM)
                         if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];
 #endif
                 }
@@ -1229,6 +1312,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             } else if constexpr (SELECT) {
                 if (sm != 0) stage_out(-1);
                 s_block();
+            } else if constexpr (CUM) {                    // (called here, not through stage_out: hipcc did not inline that lambda into the 8-bit kernels, and its captures went to scratch)
+                cum_out();
             } else {
                 stage_out(-1);
             }
@@ -1329,7 +1414,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 q_row(k, i);
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                if constexpr (!query_reduce_only(Q) && !CM && !ROLL)
+                if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM)
                     if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
 #else
                 asm volatile("" :: "v"(pv[k]));
@@ -1362,7 +1447,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
         q_window();
         f_block();
-        stage_out(slot);
+        if constexpr (CUM) cum_out(); else stage_out(slot);
         s_block();
         if constexpr (GATHER) grow += 8u;
     };
@@ -1466,6 +1551,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
             for (int k = 0; k < CPL; k++) rsum[k] = 0;
             rblk = 0; rrun = 0; rinrun = false;
+        }
+        if constexpr (CUM) {                               // the running values enter the chunk as the scan left them
+#pragma unroll
+            for (int k = 0; k < CPL; k++) cums[CUM ? k : 0] = col_ok[k] ? cumulative_enter<W>(a, chunk, (uint32_t)D, (uint32_t)genk[k]) : CumState{MASK, 0u, 0ull};
         }
         if constexpr (SELECT) {
             srank = 0;
@@ -1603,7 +1692,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     for (int q = 0; q < PIECES; q++)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, held[s2][q]), orsrc, held_vo[s2][q], 0, kStoreAux);
             }
-        } else if constexpr (!query_reduce_only(Q) && !ROLL) {
+        } else if constexpr (!query_reduce_only(Q) && !ROLL && !CUM) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -1714,6 +1803,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // the tail walks row by row at plain 64-bit addresses, then the chunk leaves its count and last rows for the seam pass (decode_ops.h)
         if (!corrupt) rolling_tail<W, CPL>(a, chunk, rollp, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, rsum);
         rolling_leave<W, CPL>(a, chunk, rollp, corrupt ? 0u : out_elems + remaining, (uint32_t)D, genk, col_ok, lane_d);
+    } else if constexpr (CUM) {
+        // the tail walks row by row at plain 64-bit addresses; in a call of one chunk the state behind it is the call's carry_out (decode_ops.h)
+        if (!corrupt) cumulative_tail<W, CPL>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, cums);
+        cumulative_leave<W, CPL>(a, chunk, corrupt, (uint32_t)D, genk, col_ok, cums);
     } else if constexpr (PROJ) {
         // the tail's selected columns leave element by element, at plain 64-bit addresses (decode_ops.h: project_tail)
         if (!corrupt && remaining > 0) project_tail<W>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP);

@@ -43,6 +43,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // ROLL (sprintz_mi355x_rolling_rows): every sample leaves as its column's min / max / sum over the W rows that end at its row; the group's LDS is
     // the chunk's history ring (decode_ops.h: rolling_rows8), runs are replayed block by block
     constexpr bool ROLL = Q == kQueryRolling;
+    // CUM (sprintz_mi355x_cumulative_rows): every sample leaves as its column's running min / max / sum from the batch's first row on; a lane keeps the
+    // running values of its columns in registers, loaded at the chunk's start from the scan's table (decode_ops.h: cumulative_rows8)
+    constexpr bool CUM = Q == kQueryCumulative;
     constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT || SEG;
     constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -100,6 +103,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
+            if constexpr (CUM) cumulative_mark(a, chunk, (uint32_t)D, lane_d, DP, W);
             if constexpr (TAB) hbad = true; else return;
         }
         groups_left = len < 128u ? 0u : len / (16u * (uint32_t)D);
@@ -115,6 +119,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
+            if constexpr (CUM) cumulative_mark(a, chunk, (uint32_t)D, lane_d, DP, W);
             if constexpr (TAB) hbad = true; else return;
         }
     } else {
@@ -267,6 +272,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (ROLL) {
 #pragma unroll
         for (int k = 0; k < CPL; k++) rsum[k] = 0;
+    }
+    // cumulative rows: each column's running min / max / sum, entering the chunk as the scan left them
+    CumState cst[CUM ? CPL : 1];
+    if constexpr (CUM) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) cst[k] = genk[k] ? cumulative_enter<W>(a, chunk, (uint32_t)D, (uint32_t)colk[k]) : CumState{MASK, 0u, 0ull};
     }
 
     for (;;) {
@@ -450,6 +461,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     rolling_rows8<W>(a, rolling_ring<W>(lds + a.table.table_off, a, (uint32_t)colk[k]), out_elems / blk_elems, [&](int i) { return v[i][k]; }, rsum[k],
                                      chunk * (uint64_t)a.chunk_len + out_elems + (uint64_t)colk[k], (uint32_t)D,
                                      !FIRE && SPRINTZ_ROLL_RUN_SHORTCUT && run_block && rolling_run_settled(a, rrun));
+            } else if constexpr (CUM) {
+                if (genk[k])
+                    cumulative_rows8<W>(a, [&](int i) { return v[i][k]; }, cst[k], chunk * (uint64_t)a.chunk_len + out_elems + (uint64_t)colk[k], (uint32_t)D);
             } else if constexpr (MOM || GBY) {   // (the products / the adds wait for the reference / key column's rows: behind the column loop)
             } else if constexpr (Q != 0) {       // the query functor sees every decoded row (sprintz_xff_rle_query.hpp:346-596)
                 uint32_t bs = 0;
@@ -523,7 +537,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         // ---- store the 8 x D block (contiguous 8*D*ESZ bytes of the output)
         U* const ob = o + out_elems;
-        if constexpr (query_reduce_only(Q) || ROLL) {       // (rolling rows: the block's results left from the column loop, the raw rows went to the ring)
+        if constexpr (query_reduce_only(Q) || ROLL || CUM) {       // (rolling rows: the block's results left from the column loop, the raw rows went to the ring; cumulative rows: likewise, no ring)
             (void)ob;
         } else if constexpr (Q == kQueryGather) {
             // rows [lo, hi) of the chunk alone, each at its place in the range; the parse stops after row hi - 1
@@ -700,6 +714,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (ROLL) {
         if (!corrupt) rolling_tail<W, CPL>(a, chunk, lds + a.table.table_off, s + pos, out_elems, remaining, (uint32_t)D, colk, genk, rsum);
         rolling_leave<W, CPL>(a, chunk, lds + a.table.table_off, corrupt ? 0u : out_elems + remaining, (uint32_t)D, colk, genk, lane_d);
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        return;
+    }
+    if constexpr (CUM) {
+        if (!corrupt) cumulative_tail<W, CPL>(a, chunk, s + pos, out_elems, remaining, (uint32_t)D, colk, genk, cst);
+        cumulative_leave<W, CPL>(a, chunk, corrupt, (uint32_t)D, colk, genk, cst);
         if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }

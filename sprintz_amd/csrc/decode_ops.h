@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments, group-by, extrema, linear filter, segment, float and rolling rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by, extrema, linear filter, segment, float, rolling, project and cumulative rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -17,11 +17,11 @@ namespace sprintz {
 // and may count each one's selected rows: chunk c's window w in row_count[c * count + w]
 struct WindowArgs {
     uint32_t rows;              // W, a multiple of 8: a block of 8 rows never straddles a window edge (rolling rows: the trailing window's rows)
-    uint32_t count;             // windows per chunk slot: ceil(ceil(chunk_len / D) / W)
-    uint32_t ops;               // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4 (rolling rows: SPRINTZ_ROLL_*, the same bits)
+    uint32_t count;             // windows per chunk slot: ceil(ceil(chunk_len / D) / W) (cumulative rows: sum_bytes, 4 or 8)
+    uint32_t ops;               // SPRINTZ_QUERY_WIN_MIN 1 | _MAX 2 | _SUM 4 (rolling rows: SPRINTZ_ROLL_*, cumulative rows: SPRINTZ_CUM_*, the same bits)
     void* min;                  // element type
     void* max;                  // element type
-    uint64_t* sum;              // (rolling rows: read as uint32_t*, an entry an element)
+    uint64_t* sum;              // (rolling rows: read as uint32_t*, an entry an element; cumulative rows: an entry an element, uint64 or uint32 by sum_bytes)
     uint32_t* row_count;        // optional (SPRINTZ_AGG_COUNT, SPRINTZ_MOM_COUNT)
 };
 // gather rows (Q == kQueryGather; sprintz_mi355x_gather_rows): range i is batch rows [starts[i], starts[i] + rows), batch row g
@@ -111,9 +111,9 @@ struct ExtremaArgs {
 // null), as aggregate rows reuses WindowArgs.  Inside the decode launch a chunk's first row is its own predecessor; with lag given the
 // decode leaves every chunk's first and last existing row in tmp (LinearSlot) and the seam pass puts row 0 of the chunks behind the first right
 struct LinearArgs {
-    const int32_t* w;           // [D], on the device
+    const int32_t* w;           // [D], on the device (cumulative rows: the caller's carry_out, uint64 [3][D], in a call of one chunk; else null)
     const int32_t* lag;         // [D], or null: no lag term
-    void* tmp;                  // nchunks x linear_tmp_stride (geom.h) bytes where lag is given (rolling rows: nchunks x roll_tmp_stride, or null with one chunk)
+    void* tmp;                  // nchunks x linear_tmp_stride (geom.h) bytes where lag is given (rolling rows: nchunks x roll_tmp_stride, or null with one chunk; cumulative rows: the chunks' entering states, uint64 [nchunks][3][D], or null)
     int32_t lo, hi, bias;
     uint32_t pad;
 };
@@ -159,7 +159,7 @@ struct DecodeArgs {
     // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.  The linear filter's took the
     //  other 40: the spare bytes are used up, and the next mode's arguments have to share a struct that is here, as the linear filter shares
     //  FilterArgs, or move the kernels named above.  Float rows do: scale, offset and format ride in FilterArgs' lo, hi and mode.  Rolling rows
-    //  do: WindowArgs, LinearArgs::tmp and BinTableArgs::table_off.)
+    //  do: WindowArgs, LinearArgs::tmp and BinTableArgs::table_off.  Cumulative rows do: WindowArgs, LinearArgs::tmp and LinearArgs::w.)
     WindowArgs win;
     MomentArgs mom;
     BinTableArgs table;
@@ -1568,6 +1568,133 @@ __device__ __forceinline__ void rolling_leave(const DecodeArgs& a, uint64_t chun
             s.rows[(size_t)j * D + (uint32_t)col[k]] = rc[slot];
             slot = slot + 1u == cap ? 0u : slot + 1u;
         }
+    }
+}
+
+// ---- cumulative rows (Q == kQueryCumulative; sprintz_mi355x_cumulative_rows): element e of chunk c, in row r = e / D and column d = e % D, leaves at
+// place c * chunk_len + e of every selected output as the column's running value from the batch's first row to its own: the minimum and the maximum
+// in the element type, the sum modulo 2^64 as an int64 or its low half as an int32.  A chunk does not start from the identities but from its
+// ENTERING state -- the seeds taken through every chunk in front of it -- which the scan (decode_cumulative.hip) left in a table of uint64
+// [nchunks][3][D]: a min row, a max row and a sum row a chunk, the layout of the call's carries.  The mode has no struct of its own (DecodeArgs has
+// no spare byte): the ops (kCumMin | kCumMax | kCumSum) and the outputs travel in WindowArgs (ops, min, max, sum), sum_bytes in WindowArgs::count,
+// the table in LinearArgs::tmp (null: the identities) and -- in a call of one chunk, which has no scan: the table is then the caller's carry_in
+// -- the caller's carry_out in LinearArgs::w (null: none), which the last chunk's lanes fill.
+// A lane walks its column from the chunk's first row to its last, so the running values are registers: no LDS, no barrier.
+struct CumState {
+    uint32_t mn, mx;
+    uint64_t sum;
+};
+template <int W> __device__ __forceinline__ CumState cumulative_enter(const DecodeArgs& a, uint64_t chunk, uint32_t D, uint32_t col)
+{
+    const uint64_t* const st = (const uint64_t*)a.lin.tmp;
+    if (!st) return CumState{Elem<W>::MASK, 0u, 0ull};
+    const uint64_t* const p = st + chunk * 3ull * D + col;
+    return CumState{(uint32_t)p[0] & Elem<W>::MASK, (uint32_t)p[D] & Elem<W>::MASK, p[2u * D]};
+}
+__device__ __forceinline__ uint64_t* cumulative_carry_out(const DecodeArgs& a) { return (uint64_t*)const_cast<int32_t*>(a.lin.w); }
+// One block: the 8 new rows x(0 .. 7) of a column.  put(op, j, v): row j's result v of op (a selected one) -- the generic kernel stores it at its
+// place, decode_fast.h keeps it for its staging passes
+template <int W, typename F, typename P>
+__device__ __forceinline__ void cumulative_step8(const DecodeArgs& a, F x, CumState& s, P put)
+{
+    constexpr uint32_t MASK = Elem<W>::MASK;
+    uint32_t xs[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) xs[i] = x(i) & MASK;
+    if (a.win.ops & kCumMin) {
+        uint32_t m = s.mn;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            m = xs[i] < m ? xs[i] : m;
+            put(kCumMin, i, (uint64_t)m);
+        }
+        s.mn = m;
+    }
+    if (a.win.ops & kCumMax) {
+        uint32_t m = s.mx;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            m = xs[i] > m ? xs[i] : m;
+            put(kCumMax, i, (uint64_t)m);
+        }
+        s.mx = m;
+    }
+    if (a.win.ops & kCumSum) {
+        uint64_t t = s.sum;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            t += xs[i];
+            put(kCumSum, i, t);
+        }
+        s.sum = t;
+    }
+}
+// one result at its place, a plain 64-bit address: batch element e
+template <int W> __device__ __forceinline__ void cumulative_put(const DecodeArgs& a, uint32_t op, uint64_t e, uint64_t v)
+{
+    using U = typename Elem<W>::U;
+    if (op == kCumMin) ((U*)a.win.min)[e] = (U)v;
+    else if (op == kCumMax) ((U*)a.win.max)[e] = (U)v;
+    else if (a.win.count == 8u) a.win.sum[e] = v;
+    else ((uint32_t*)a.win.sum)[e] = (uint32_t)v;
+}
+// the generic kernel's form: every result leaves at once; e0 is the batch element of the block's row 0 in this column
+template <int W, typename F>
+__device__ __forceinline__ void cumulative_rows8(const DecodeArgs& a, F x, CumState& s, uint64_t e0, uint32_t D)
+{
+    cumulative_step8<W>(a, x, s, [&](uint32_t op, int j, uint64_t v) { cumulative_put<W>(a, op, e0 + (uint64_t)j * D, v); });
+}
+// The verbatim tail: `remaining` elements at t behind the chunk's `out_elems` (a multiple of 8 * D: element e of the tail is in column e % D, one
+// row further on than the column's previous one).  Each lane walks its own columns (`col`, a list), row by row; a partial last row has the
+// columns it has, and nothing is stored for the others.
+template <int W, int CPL>
+__device__ __forceinline__ void cumulative_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t out_elems, uint32_t remaining, uint32_t D,
+                                                const int (&col)[CPL], const bool (&genuine)[CPL], CumState (&s)[CPL])
+{
+    const uint64_t base = chunk * (uint64_t)a.chunk_len + out_elems;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        for (uint32_t e = (uint32_t)col[k]; e < remaining; e += D) {
+            const uint32_t x = tail_elem<W>(t, e);
+            s[k].mn = x < s[k].mn ? x : s[k].mn;
+            s[k].mx = x > s[k].mx ? x : s[k].mx;
+            s[k].sum += x;
+            if (a.win.ops & kCumMin) cumulative_put<W>(a, kCumMin, base + e, s[k].mn);
+            if (a.win.ops & kCumMax) cumulative_put<W>(a, kCumMax, base + e, s[k].mx);
+            if (a.win.ops & kCumSum) cumulative_put<W>(a, kCumSum, base + e, s[k].sum);
+        }
+    }
+}
+// At the chunk's end, in a call of one chunk: the state behind the chunk's last element goes to carry_out -- of a damaged chunk the state it
+// entered with, since it counts as the identity.  (Only the ops asked for were kept up: the rows of the others leave as they entered.)
+template <int W, int CPL>
+__device__ __forceinline__ void cumulative_leave(const DecodeArgs& a, uint64_t chunk, bool damaged, uint32_t D, const int (&col)[CPL], const bool (&genuine)[CPL],
+                                                 const CumState (&s)[CPL])
+{
+    uint64_t* const out = cumulative_carry_out(a);
+    if (!out || chunk + 1 != a.nchunks) return;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        const CumState in = cumulative_enter<W>(a, chunk, D, (uint32_t)col[k]);
+        const bool keep = !damaged;
+        out[(uint32_t)col[k]] = keep && (a.win.ops & kCumMin) ? s[k].mn : in.mn;
+        out[D + (uint32_t)col[k]] = keep && (a.win.ops & kCumMax) ? s[k].mx : in.mx;
+        out[2u * D + (uint32_t)col[k]] = keep && (a.win.ops & kCumSum) ? s[k].sum : in.sum;
+    }
+}
+// a chunk that is refused before its lanes have their columns: the group's lanes share the columns out
+__device__ __forceinline__ void cumulative_mark(const DecodeArgs& a, uint64_t chunk, uint32_t D, int lane_d, int DP, int W)
+{
+    uint64_t* const out = cumulative_carry_out(a);
+    if (!out || chunk + 1 != a.nchunks) return;
+    const uint64_t mask = W == 8 ? 0xffull : 0xffffull;
+    const uint64_t* const st = (const uint64_t*)a.lin.tmp;
+    for (uint32_t d = (uint32_t)lane_d; d < D; d += (uint32_t)DP) {
+        out[d] = st ? st[chunk * 3ull * D + d] & mask : mask;
+        out[D + d] = st ? st[chunk * 3ull * D + D + d] & mask : 0ull;
+        out[2u * D + d] = st ? st[chunk * 3ull * D + 2u * D + d] : 0ull;
     }
 }
 

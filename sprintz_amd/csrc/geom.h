@@ -37,11 +37,14 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 14 = float: a plain decode whose stores convert -- every sample leaves as fl32(fl32(x * scale[d]) + offset[d]) in float32, float16 or bfloat16, never as an integer;
 // 15 = rolling: per element the min / max / sum of its column over the W rows that end at its row (a trailing window, clipped at the chunk's first row
 // inside the launch; the seam pass of decode_rolling.hip carries it over the chunk seams), stored at the element's place in place of the element;
-// 16 = project: a plain decode (or float rows) that stores only the K columns a slot table names, each at its slot of a dense [rows, K] output.
+// 16 = project: a plain decode (or float rows) that stores only the K columns a slot table names, each at its slot of a dense [rows, K] output;
+// 17 = cumulative: per element the running min / max / sum of its column from the batch's first row to its row, stored at the element's place in place of
+// the element; a chunk starts from the state the scan of decode_cumulative.hip left for it.
 // 6 .. 11 and 13 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
               kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14, kQueryRolling = 15;
 constexpr int kQueryProject = 16;
+constexpr int kQueryCumulative = 17;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
@@ -72,6 +75,24 @@ constexpr uint32_t roll_max_window(int D, int esz, uint32_t groups)
 // with more than one chunk: what one chunk leaves for the seam pass (decode_ops.h: RollSlot) -- a word with the elements the chunk decoded to (0: damaged),
 // 12 bytes of padding, then its last W - 1 rows in the element type where it is full; a multiple of 16 bytes
 constexpr uint64_t roll_tmp_stride(uint32_t W, int D, int esz) { return (16ull + ((uint64_t)W - 1ull) * (uint64_t)D * (uint64_t)esz + 15ull) & ~15ull; }
+// cumulative rows: the ops (SPRINTZ_CUM_MIN / _MAX / _SUM, WindowArgs::ops; WindowArgs::count carries sum_bytes) and the scan over the chunks'
+// totals (decode_cumulative.hip).  A workgroup of the scan owns one column and walks the chunks kCumScanTile at a step: each of its kThreads
+// threads takes kCumScanChunks consecutive chunks.
+constexpr uint32_t kCumMin = 1, kCumMax = 2, kCumSum = 4;
+constexpr uint32_t kCumScanChunks = 8;
+constexpr uint32_t kCumScanTile = (uint32_t)kThreads * kCumScanChunks;
+// The call's scratch (sprintz_mi355x_cumulative_tmp_bytes), five regions that each start on 16 bytes: the chunks' entering states -- chunk c's at
+// uint64 [c][3][D], a min row, a max row and a sum row, the carries' own layout -- then what the totals pass writes: its return values int64 [n],
+// the chunks' sums uint64 [n][D], their minima and their maxima in the element type [n][D] (sized for 2-byte elements)
+struct CumTmp { uint64_t state, rets, sum, min, max, bytes; };
+constexpr uint64_t cum_round16(uint64_t x) { return (x + 15ull) & ~15ull; }
+constexpr CumTmp cum_tmp_layout(uint64_t nchunks, int D)
+{
+    const uint64_t nd = nchunks * (uint64_t)D;
+    const uint64_t rets = cum_round16(nd * 24ull), sum = rets + cum_round16(nchunks * 8ull), mn = sum + cum_round16(nd * 8ull),
+                   mx = mn + cum_round16(nd * 2ull);
+    return CumTmp{0, rets, sum, mn, mx, mx + cum_round16(nd * 2ull)};
+}
 // histogram rows: the counters of one call (ndims x nbins; SPRINTZ_HIST_MAX_COUNTERS), 4 bytes each in a workgroup's LDS table, and the
 // dynamic LDS a decode_fast.h launch may ask for with its table behind the groups' carves: two such workgroups fit a CU's 160 KB
 constexpr uint32_t kHistMaxCounters = 16384;

@@ -16,7 +16,7 @@
 
 namespace sprintz {
 
-// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryProject).  Each forwards to the
+// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryCumulative).  Each forwards to the
 // translation unit that holds the instantiation -- decode_w8.hip / decode_w16.hip for the plain decode and the reduce / window
 // queries, a unit of its own for every other mode (SPRINTZ_ROW_OP_UNITS below) -- so that every unit keeps its compile flags.
 // generic lane mapping, both layouts, up to 512 columns (decode_kernel.h)
@@ -24,7 +24,7 @@ hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, 
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h); gather and select for rows of whole 16-byte pieces
 // (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments, group-by, extrema, the linear filter, segments, float rows, rolling rows and project rows
+// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments, group-by, extrema, the linear filter, segments, float rows, rolling rows, project rows and cumulative rows
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // internal -- the units' own entry points, reached through the three launchers above alone (api.hip).  A unit refuses a width or
 // a mode it does not hold; the decode_uni units size their grid themselves (decode_uni_threads) and ignore `grid`
@@ -34,7 +34,7 @@ hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hip
 SPRINTZ_DECODE_UNIT_DECL(w8)
 SPRINTZ_DECODE_UNIT_DECL(w16)
 // the row operations' units, a mode each, in the order of their kQuery* numbers (api.hip builds its table of units from this list)
-#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby) X(extrema) X(linear) X(segment) X(float) X(rolling) X(project)
+#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby) X(extrema) X(linear) X(segment) X(float) X(rolling) X(project) X(cumulative)
 SPRINTZ_ROW_OP_UNITS(SPRINTZ_DECODE_UNIT_DECL)
 hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
@@ -47,6 +47,9 @@ hipError_t launch_segment_count(const uint8_t* mask, uint64_t nchunks, uint32_t 
 hipError_t launch_linear_seam(int esz, const DecodeArgs& a, hipStream_t st);
 // rolling_rows' seam pass: the first W - 1 rows of every chunk behind the first take the last rows of the chunk in front into their windows (decode_rolling.hip)
 hipError_t launch_rolling_seam(int esz, const DecodeArgs& a, hipStream_t st);
+// cumulative_rows' scan: the chunks' totals in d_tmp (geom.h: cum_tmp_layout) become each chunk's entering state, seeded with carry_in (null: the
+// identities); a damaged chunk counts as the identity; carry_out (optional) takes the state behind the last chunk (decode_cumulative.hip)
+hipError_t launch_cumulative_scan(int esz, uint64_t nchunks, uint32_t D, uint32_t ops, void* d_tmp, const uint64_t* carry_in, uint64_t* carry_out, hipStream_t st);
 // small batches: one workgroup per chunk, both layouts, 1 .. 64 columns (decode_lat.h); bound_bytes = the longest stream a chunk can have
 hipError_t launch_decode_lat(int w, bool fire, int dp, bool lowdim, unsigned grid, uint32_t bound_bytes, hipStream_t st, const DecodeArgs& a);
 hipError_t launch_encode_lat(int w, bool fire, int dp, bool lowdim, unsigned grid, uint32_t bound_bytes, hipStream_t st, const EncodeArgs& a);   // encode_lat.h
@@ -180,7 +183,7 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
 
 // every mapping the windowed query has, row-major: the row operations that store no rows (filter, aggregate, histogram, moments, group-by, extrema, linear filter, segments)
 #define SPRINTZ_DISPATCH_DECODE_FAST_ROWS(KERNEL, W, Q) SPRINTZ_DISPATCH_DECODE_FAST_Q(KERNEL, W, Q, false)
-// gather, select, float rows and rolling rows: row-major destination, rows of whole 16-byte store pieces -- 16 columns and more, or 8 columns of 16 bits
+// gather, select, float rows, rolling rows and cumulative rows: row-major destination, rows of whole 16-byte store pieces -- 16 columns and more, or 8 columns of 16 bits
 #define SPRINTZ_FAST_PIECES_8(KERNEL, Q)
 #define SPRINTZ_FAST_PIECES_16(KERNEL, Q) SPRINTZ_FAST_CASE(KERNEL, 16, 8, 1, Q, false)
 #define SPRINTZ_DISPATCH_DECODE_FAST_PIECES(KERNEL, W, Q)                                             \
@@ -192,7 +195,7 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
     SPRINTZ_FAST_CASE(KERNEL, W, 64, 4, Q, false)                                                     \
     return hipErrorInvalidValue;
 
-// rolling rows: the one-column-a-lane mappings of the set above, 8 .. 64 columns -- with two and four columns a lane hipcc kept the block's results in
+// rolling rows, cumulative rows: the one-column-a-lane mappings of the set above, 8 .. 64 columns -- for rolling rows with two and four columns a lane hipcc kept the block's results in
 // scratch (tools/kernel_regs.sh), so those shapes stay on the generic kernel (plan.h)
 #define SPRINTZ_DISPATCH_DECODE_FAST_PIECES_1(KERNEL, W, Q)                                           \
     SPRINTZ_FAST_PIECES_##W(KERNEL, Q)                                                                \

@@ -211,6 +211,32 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * groups);
     }
 
+    // cumulative rows (s.out_esz the widest output element: sum_bytes with the sum, else esz; s.out_lo the low bits of EVERY selected output).
+    // decode_fast.h takes what it takes for rolling rows, without the rings: rows of whole 16-byte pieces on the one-column-a-lane mappings (8 .. 64
+    // columns), 16-byte aligned outputs, within the descriptors' reach counted in OUTPUT bytes (out_esz: the int64 sum's offsets are eight times the
+    // element's at 8 bits).  Two and four columns a lane are not instantiated, as for rolling rows; everything else -- the low-dim shapes too:
+    // decode_uni.h is not taught the mode -- runs the generic kernel, which stores element by element at 64-bit addresses and stages nothing.
+    if (s.q == kQueryCumulative) {
+        if (D > 512 || norle || cs) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "cumulative_rows: the RLE codecs, row-major, at most 512 columns");
+        const int cosz = s.out_esz ? s.out_esz : esz;
+        const FastMap f = decode_fast_map(esz, D, 0, false);
+        const uint64_t fgroups = (uint64_t)(kThreads / f.dp);
+        const bool fast = !lowdim && !s.noheader && f.cpl == 1 && 2 * D > f.dp * f.cpl && (uint64_t)chunk_len * esz * 2 >= f.ring && !k.no_fast &&
+                          ((uint64_t)D * esz) % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0 && (s.out_lo % 16) == 0 &&
+                          (uint64_t)chunk_len * cosz * 64 * 64 < 0xf0000000ull;
+        if (fast) {
+            p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
+            p.exact = D == f.dp * f.cpl;
+            p.log2DP = f.log2dp;
+            p.lds_group_stride = f.ring;
+            p.vec_store = 1;
+            p.chunks_per_group = (uint32_t)k.chunks_per_group;
+            const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
+            return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * fgroups);
+        }
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, 0);
+    }
+
     // project rows (K in s.rows; s.out_esz the bytes of an output element: esz for the element type, 4 / 2 for the floats).  A chunk's R = chunk_len / D
     // rows leave as R x K elements from output element c x R x K on.  decode_fast.h takes, on its one-column-a-lane mappings (up to 64 columns), every
     // shape the plain decode takes there whose PROJECTED block, 8 K esz bytes, is a whole number of 16-byte store pieces -- every K at 16 bits, the even

@@ -558,6 +558,74 @@ int sprintz_mi355x_project_rows(int codec, int elem_bytes, const void* d_comp, c
     return decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
 }
 
+// ---------------------------------------------------------------- cumulative rows
+size_t sprintz_mi355x_cumulative_tmp_bytes(uint64_t nchunks, uint16_t ndims)
+{
+    return nchunks > 1 ? (size_t)cum_tmp_layout(nchunks, ndims ? ndims : 1).bytes : 0;
+}
+
+int sprintz_mi355x_cumulative_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                                   uint32_t chunk_len, uint16_t ndims, uint32_t ops, int sum_bytes, uint32_t flags,
+                                   void* d_min, void* d_max, void* d_sum, const uint64_t* d_carry_in, uint64_t* d_carry_out,
+                                   void* d_tmp, int64_t* d_rets, void* hip_stream)
+{
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims};
+    const hipStream_t st = (hipStream_t)hip_stream;
+    int rc = unmasked_row_op("cumulative_rows", b, flags);
+    if (rc) return rc;
+    if (ops < 1 || ops > 7) return fail(SPRINTZ_E_INVALID, "cumulative_rows: ops must be a non-empty OR of SPRINTZ_CUM_MIN / _MAX / _SUM");
+    static_assert(SPRINTZ_CUM_MIN == kCumMin && SPRINTZ_CUM_MAX == kCumMax && SPRINTZ_CUM_SUM == kCumSum, "out[i] is op bit i");
+    static_assert(SPRINTZ_CUM_MIN == SPRINTZ_QUERY_WIN_MIN && SPRINTZ_CUM_MAX == SPRINTZ_QUERY_WIN_MAX && SPRINTZ_CUM_SUM == SPRINTZ_QUERY_WIN_SUM,
+                  "the totals pass takes the ops as they are");
+    // an output WITHOUT its op is refused too: min, max and sum are this operation's only results
+    if ((d_min && !(ops & kCumMin)) || (d_max && !(ops & kCumMax)) || (d_sum && !(ops & kCumSum)))
+        return fail_op(SPRINTZ_E_INVALID, "cumulative_rows", "an output buffer without its op");
+    if (sum_bytes != 4 && sum_bytes != 8) return fail(SPRINTZ_E_INVALID, "cumulative_rows: sum_bytes must be 4 (int32, the low half) or 8 (int64)");
+    OpOutput out[3] = {{d_min, elem_bytes}, {d_max, elem_bytes}, {d_sum, sum_bytes}};
+    if ((rc = check_op_outputs("cumulative_rows", ops, out, d_rets, "min / max must be aligned to the element size, sum to sum_bytes, d_rets to 8"))) return rc;
+    if ((uintptr_t)d_carry_in % 8 || (uintptr_t)d_carry_out % 8) return fail(SPRINTZ_E_INVALID, "cumulative_rows: d_carry_in and d_carry_out must be aligned to 8 bytes");
+    if ((uintptr_t)d_tmp % 16) return fail(SPRINTZ_E_INVALID, "cumulative_rows: d_tmp must be aligned to 16 bytes");
+    if (nchunks > 1 && !d_tmp)
+        return fail_op(SPRINTZ_E_INVALID, "cumulative_rows", "with more than one chunk, d_tmp must hold sprintz_mi355x_cumulative_tmp_bytes(nchunks, ndims) bytes");
+    if (nchunks == 0 && !d_carry_out) return 0;
+    if ((rc = ensure_device())) return rc;
+    if (nchunks == 0) {                                     // nothing to decode: the seeds are the state behind the batch (the scan over no chunk)
+        if (launch_cumulative_scan(elem_bytes, 0, ndims, ops, nullptr, d_carry_in, d_carry_out, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "cumulative_rows scan kernel launch");
+        return 0;
+    }
+    // the mode shares structs that exist (decode_ops.h, cumulative rows): the ops, sum_bytes and the outputs in WindowArgs, the chunks' entering
+    // states in LinearArgs::tmp
+    QuerySpec qs = row_query(kQueryCumulative, flags);
+    qs.win.ops = ops;
+    qs.win.count = (uint32_t)sum_bytes;
+    qs.win.min = out[0].p;
+    qs.win.max = out[1].p;
+    qs.win.sum = (uint64_t*)out[2].p;
+    if (nchunks == 1) {
+        // one chunk enters with the seeds themselves and leaves its state to carry_out: no totals, no scan, and no scratch
+        qs.lin.tmp = const_cast<uint64_t*>(d_carry_in);
+        qs.lin.w = (const int32_t*)d_carry_out;
+        return decode_batch(b, nullptr, d_rets, st, qs);
+    }
+    // 1. the totals: every chunk's per-column min / max / sum and its return value, the windowed query with one window a chunk
+    const CumTmp lay = cum_tmp_layout(nchunks, ndims);
+    uint8_t* const tmp = (uint8_t*)d_tmp;
+    const uint32_t rows = chunk_len / ndims;
+    QuerySpec tq = row_query(kQueryWindow, flags);
+    tq.win.rows = rows < 8 ? 8u : (rows + 7u) & ~7u;
+    tq.win.count = 1;
+    tq.win.ops = ops;
+    tq.win.min = (ops & kCumMin) ? tmp + lay.min : nullptr;
+    tq.win.max = (ops & kCumMax) ? tmp + lay.max : nullptr;
+    tq.win.sum = (ops & kCumSum) ? (uint64_t*)(tmp + lay.sum) : nullptr;
+    if ((rc = decode_batch(b, nullptr, (int64_t*)(tmp + lay.rets), st, tq))) return rc;
+    // 2. the scan: each chunk's entering state, and the state behind the last one
+    if (launch_cumulative_scan(elem_bytes, nchunks, ndims, ops, tmp, d_carry_in, d_carry_out, st) != hipSuccess) return fail(SPRINTZ_E_HIP, "cumulative_rows scan kernel launch");
+    // 3. the decode
+    qs.lin.tmp = tmp + lay.state;
+    return decode_batch(b, nullptr, d_rets, st, qs);
+}
+
 // ---------------------------------------------------------------- histogram rows
 int sprintz_mi355x_histogram_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
                                   uint32_t chunk_len, uint16_t ndims, const uint8_t* d_mask, const void* d_lo, uint32_t shift, uint32_t nbins,

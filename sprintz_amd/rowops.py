@@ -1,6 +1,6 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, project_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
-fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, rolling_rows' window rules, counts, mean and scratch size, project_rows' slot table, the default bin shift, bounds and offsets as tensors, the
+moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, project_rows, cumulative_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, rolling_rows' window rules, counts, mean and scratch size, project_rows' slot table, cumulative_rows' ops, carry, mean and scratch size, the default bin shift, bounds and offsets as tensors, the
 linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
@@ -284,6 +284,54 @@ def project_slots(columns, ndims, device=None):
             raise ValueError(f"column {c} is named twice")
         slots[c] = j
     return torch.tensor(slots, dtype=torch.int32, device=device)
+
+
+CUMULATIVE_OPS = ("min", "max", "sum", "mean")
+
+
+class CumulativeCarry:
+    """what one cumulative_rows call hands to the next: `table`, int64 [3, ndims] -- the library's carry, a min row, a max row and a sum row (the
+    bits of its uint64) -- and `rows`, the batch rows behind it, which the expanding mean divides by"""
+
+    def __init__(self, table, rows=0):
+        self.table = table
+        self.rows = int(rows)
+
+
+def cumulative_carry(ndims, esz, device=None):
+    """the carry in front of a stream's first batch: the identities -- all ones of the element type, 0 and 0 -- and no row"""
+    table = torch.zeros((3, ndims), dtype=torch.int64, device=device)
+    table[0] = (1 << (8 * esz)) - 1
+    return CumulativeCarry(table, 0)
+
+
+def check_carry(carry, ndims, device):
+    """a carry as cumulative_rows returned it, for a codec of ndims columns on `device` -> the same"""
+    t = getattr(carry, "table", None)
+    if not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != device or tuple(t.shape) != (3, ndims) or not t.is_contiguous():
+        raise ValueError(f"carry must be what cumulative_rows returned for {ndims} columns on {device}")
+    return carry
+
+
+def cumulative_mean(total, rows_before=0):
+    """cumulative sums int64 [G, D], behind rows_before rows of earlier batches -> the expanding means, float64 [G, D]: the converted sum
+    over the rows so far, rows_before + g + 1"""
+    G = total.shape[0]
+    n = torch.arange(rows_before + 1, rows_before + G + 1, dtype=torch.float64, device=total.device)
+    return total.to(torch.float64) / n.unsqueeze(1)
+
+
+def cumulative_tmp_bytes(nchunks, ndims):
+    """the scratch cumulative_rows needs with more than one chunk (sprintz_mi355x_cumulative_tmp_bytes; geom.h: cum_tmp_layout): the chunks'
+    entering states, the totals pass' return values, and the chunks' sums, minima and maxima, each region rounded up to 16 bytes"""
+    if nchunks <= 1:
+        return 0
+    nd = nchunks * ndims
+
+    def r16(x):
+        return (x + 15) & ~15
+
+    return r16(nd * 24) + r16(nchunks * 8) + r16(nd * 8) + 2 * r16(nd * 2)
 
 
 def default_shift(W, nbins):
