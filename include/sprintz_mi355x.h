@@ -390,6 +390,12 @@ int sprintz_mi355x_huf_decompress_batch(const void* d_huf, const uint64_t* d_huf
  *   decompress: col_stride >= nchunks * rows_per_chunk (ragged last chunk:
  *               rows past nrows are not written by a valid stream)
  * Containers are interchangeable with the row-major entry points.
+ * Any col_stride is taken: the lane-per-column kernels serve strides of whole
+ * blocks (a multiple of 8, with rows_per_chunk a multiple of 8 and a 16-byte
+ * aligned base) within their 32-bit reach -- compress: col_stride < 2^32
+ * elements; decompress: ndims * col_stride * elem_bytes < 0xf0000000 -- and
+ * everything else falls back to the generic kernels, which address every
+ * element at 64 bits.  Same streams, same matrix, either way.
  * ---------------------------------------------------------------------- */
 int sprintz_mi355x_compress_batch_colmajor(int codec, int elem_bytes, const void* d_src, uint64_t nrows, uint64_t col_stride,
                                            uint32_t rows_per_chunk, uint16_t ndims, void* d_slots, size_t slot_stride,

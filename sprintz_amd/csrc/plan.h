@@ -472,7 +472,10 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
     while (fdp < D) fdp <<= 1;
     const size_t blk_bytes = (size_t)8 * D * esz;
     const bool fast_common = !lowdim && !p.raw && D <= 64 && 2 * D > fdp && (s.src_lo % 16) == 0 && !k.no_fast;
-    const bool fast = col_stride ? fast_common && col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0
+    // (column-major: the burst loads of encode_fast.h and encode_wide.h keep the stride as a 32-bit element count -- a stride of 2^32 elements
+    //  or more goes to the generic kernel, whose stride is 64 bits wide)
+    const bool cm_reach = col_stride <= 0xffffffffull;
+    const bool fast = col_stride ? fast_common && col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0 && cm_reach
                                  : fast_common && blk_bytes % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0;
     // small batches: one WORKGROUP per chunk (encode_lat.h), the counterpart of decode_lat.h -- 90 us for ONE 10 KB chunk on a lane
     // group, ~20 with the coefficient chain and the RLE state machine as the only serial parts (the container, if one was asked
@@ -529,7 +532,7 @@ inline Plan plan_encode(const Shape& s, const Knobs& k)
     // (not for a handful of chunks: there a chunk's latency is what counts, and half the lanes per chunk make it longer -- a single 10 KB
     //  sprintz_compress_xff_16b call 127 us against 111 with one column per lane; from a thousand chunks on the two are level or better)
     // (column-major sources too: encode_fast.h's bursts, two columns' blocks per lane)
-    const bool pair_layout = col_stride ? col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0
+    const bool pair_layout = col_stride ? col_stride % 8 == 0 && (chunk_len / (uint32_t)D) % 8 == 0 && cm_reach
                                         : blk_bytes % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0;
     // (a float source takes it whatever SPRINTZ_OPT_ENC_PAIR says: nothing else serves its small batches fast)
     if ((flt || (k.enc_pair > 0 && nchunks >= (uint64_t)k.enc_pair)) && fast_common && D >= 5 && pair_layout && (uint64_t)chunk_len * esz >= 2 * blk_bytes) {

@@ -1,5 +1,5 @@
 """What the GPU tests of cumulative rows share: the C entry point on sentinel-filled buffers with guard bands, the comparison with the model
-(tests/cumulative_model.py), the launches a call must make according to the planner, and a batch with one truncated stream."""
+(tests/cumulative_model.py), and the launches a call must make according to the planner."""
 import ctypes as C
 from types import SimpleNamespace
 
@@ -110,18 +110,6 @@ def check(res, x, chunk_len, nchunks, D, ops, sb, msg, carry=None, shift=0, bad=
     if res.carry is not None:
         assert np.array_equal(res.carry, left), ("carry_out", res.carry.tolist(), left.tolist()) + msg
     return want, left
-
-
-def truncated_batch(sz, batch, cut):
-    """the container with chunk `cut`'s stream 5 bytes short, the streams packed densely again"""
-    import torch
-    n = batch.nchunks
-    comp, offs, sizes = batch.data.cpu().numpy(), batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy()
-    parts = [comp[offs[c]:offs[c] + sizes[c] - (5 if c == cut else 0)].copy() for c in range(n)]
-    toffs = np.zeros(n + 1, np.int64)
-    toffs[1:] = np.cumsum([p.size for p in parts])
-    return sz.CompressedBatch(torch.from_numpy(np.concatenate(parts + [np.zeros(sz._lib.READ_SLACK, np.uint8)])).cuda(), torch.from_numpy(toffs).cuda(),
-                              torch.tensor([p.size for p in parts], dtype=torch.int32).cuda(), n, batch.total_len, batch.chunk_len, batch.ndims)
 
 
 def random_carry(rng, D, esz):

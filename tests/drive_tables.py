@@ -13,7 +13,7 @@ import rle_drive as rd
 import zone_model as zm
 from dispatch import ROUND6
 from rowdata import quartiles
-from streams import DEF, GENERIC, OLD, fire_batch_of, fire_oracle_batch, options
+from streams import DEF, GENERIC, OLD, fire_batch_of, fire_oracle_batch, options, truncated_batch
 
 
 # ------------------------------------------------------------------ the run drive's
@@ -286,16 +286,9 @@ def truncated(sz, oracle, no_fast, chunks_per_group):
     tests/test_gpu_extrema.py truncates them, on decode_fast.h at three chunks a lane group.  Unlike a header that is rejected, this
     chunk is decoded block by block and found damaged behind its last group: at a window of 64 rows its last window is then open, its
     rows and sums still in the registers -- what the chunk loop's reset has to clear before chunk 5"""
-    import torch
-
     def make(codec, w, D):
         cd, batch, data, chunk_len, zero = rowop_batch(sz, oracle, codec, w, D, "lengths")
-        comp, offs, sizes = batch.data.cpu().numpy(), batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy()
-        parts = [comp[offs[c]:offs[c] + sizes[c] - (5 if c == BAD else 0)] for c in range(NCHUNKS)]
-        toffs = np.zeros(NCHUNKS + 1, np.int64)
-        toffs[1:] = np.cumsum([p.size for p in parts])
-        cut = sz.CompressedBatch(torch.from_numpy(np.concatenate(parts + [np.zeros(sz._lib.READ_SLACK, np.uint8)])).cuda(), torch.from_numpy(toffs).cuda(),
-                                 torch.tensor([p.size for p in parts], dtype=torch.int32).cuda(), NCHUNKS, data.size, chunk_len, D)
+        cut = truncated_batch(sz, batch, BAD)
         no_fast(0)
         chunks_per_group(3)
         return cd, cut, data, chunk_len, masks_for(zero, 32)[0][1]

@@ -1,5 +1,6 @@
 """Option sets and stream checks of the row-major kernel families: the knobs that choose a family (options, OLD / DEF / DENSE / GENERIC), the
-FIRE drive's batches as the oracle's containers, and the comparison of a container's streams with the oracle's."""
+FIRE drive's batches as the oracle's containers, the comparison of a container's streams with the oracle's, and a container with one
+truncated stream (truncated_batch)."""
 import os
 from contextlib import contextmanager
 from functools import lru_cache
@@ -18,6 +19,18 @@ def check_streams(oracle, codec, data, chunk_len, D, comp, offs, sizes, tag):
     for c, w in enumerate(want):
         assert sizes[c] == w.size, (tag, c, int(sizes[c]), w.size)
         assert np.array_equal(comp[offs[c]:offs[c] + sizes[c]], w), (tag, "chunk", c, "differs from the oracle's stream")
+
+
+def truncated_batch(sz, batch, cut):
+    """the container with chunk `cut`'s stream 5 bytes short, the streams packed densely again"""
+    import torch
+    n = batch.nchunks
+    comp, offs, sizes = batch.data.cpu().numpy(), batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy()
+    parts = [comp[offs[c]:offs[c] + sizes[c] - (5 if c == cut else 0)].copy() for c in range(n)]
+    toffs = np.zeros(n + 1, np.int64)
+    toffs[1:] = np.cumsum([p.size for p in parts])
+    return sz.CompressedBatch(torch.from_numpy(np.concatenate(parts + [np.zeros(sz._lib.READ_SLACK, np.uint8)])).cuda(), torch.from_numpy(toffs).cuda(),
+                              torch.tensor([p.size for p in parts], dtype=torch.int32).cuda(), n, batch.total_len, batch.chunk_len, batch.ndims)
 
 
 # ------------------------------------------------------------------ option sets and the FIRE drive's batches

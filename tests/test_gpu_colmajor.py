@@ -6,31 +6,18 @@ import zlib
 import numpy as np
 import pytest
 
+import colmajor_runner as cr
+from colmajor_runner import CM_CONFIGS                  # (with the kernel families each case claims: tests/test_colmajor_cpu.py replays them)
+from dispatch import ran
 from harness import DTYPES
 from fixtures import sz  # noqa: F401  (fixtures)
+from streams import DENSE
 
 pytestmark = pytest.mark.gpu
 
 
-CM_CONFIGS = [
-    # name, codec, esz, ndims, rows_per_chunk, nrows, col_stride (0 = nrows)
-    ("cfg5 u16 D=32 xff 160-row chunks (fast kernels)", "xff", 2, 32, 160, 160 * 41 + 57, 160 * 42),
-    ("u16 D=8 xff 640-row chunks", "xff", 2, 8, 640, 640 * 20, 0),
-    ("u16 D=8 delta", "delta", 2, 8, 640, 640 * 7 + 8, 640 * 8),
-    ("u8 D=16 xff", "xff", 1, 16, 256, 256 * 9 + 100, 256 * 10 + 8),
-    ("u8 D=64 delta", "delta", 1, 64, 128, 128 * 12, 0),
-    ("u16 D=5 (generic kernels: odd column count)", "xff", 2, 5, 200, 200 * 6 + 33, 0),
-    ("u16 D=8, unaligned stride (generic kernels)", "xff", 2, 8, 100, 100 * 9 + 3, 903),
-    ("u8 D=2 low-dim", "delta", 1, 2, 512, 512 * 5 + 1, 0),
-    ("u16 D=100 (2 columns per lane)", "xff", 2, 100, 64, 64 * 7 + 5, 64 * 8),
-    ("u16 D=6 (fast kernels, group not full)", "xff", 2, 6, 160, 160 * 9 + 48, 160 * 10),
-    ("u8 D=12 (fast kernels, group not full)", "delta", 1, 12, 256, 256 * 5 + 64, 256 * 6),
-    ("u16 D=48 delta (fast kernels, group not full)", "delta", 2, 48, 104, 104 * 11 + 16, 104 * 12),
-]
-
-
 @pytest.mark.parametrize("enc_pair", [1, 0])          # two columns per lane (encode_wide.h, column-major source) / one (encode_fast.h)
-@pytest.mark.parametrize("name,codec,esz,ndims,rpc,nrows,cs", CM_CONFIGS)
+@pytest.mark.parametrize("name,codec,esz,ndims,rpc,nrows,cs", [c[:7] for c in CM_CONFIGS])
 def test_colmajor_matches_oracle_on_the_transposed_view(sz, oracle, request, name, codec, esz, ndims, rpc, nrows, cs, enc_pair):
     import torch
     from sprintz_amd import _lib
@@ -46,7 +33,10 @@ def test_colmajor_matches_oracle_on_the_transposed_view(sz, oracle, request, nam
     cols[:, :nrows] = rows.T
     cd = sz.ChunkedCodec(codec, esz, ndims, rpc * ndims, device="cuda:0")
     ct = torch.from_numpy(cols.view(np.int8 if esz == 1 else np.int16)).cuda().view(cd.dtype)
-    batch = cd.compress_colmajor(ct, nrows)
+    enc_two, enc_one, dec = next(c[7:] for c in CM_CONFIGS if c[0] == name)
+    enc = enc_two if enc_pair else enc_one
+    with ran(only=[enc, *DENSE], what=name, **{enc: 1}):
+        batch = cd.compress_colmajor(ct, nrows)
     want = oracle.compress_chunks(codec, rows.reshape(-1), rpc * ndims, ndims)
     comp, offs, sizes = batch.data.cpu().numpy(), batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy()
     assert batch.nchunks == len(want)
@@ -60,11 +50,19 @@ def test_colmajor_matches_oracle_on_the_transposed_view(sz, oracle, request, nam
     nch = batch.nchunks
     out = torch.full((ndims, nch * rpc + 8), 0x77, dtype=torch.uint8, device="cuda:0").to(cd.dtype) if esz == 1 else \
         torch.full((ndims, nch * rpc + 8), 0x7777, dtype=torch.int32, device="cuda:0").to(torch.uint16)
-    got = cd.decompress_colmajor(batch, out=out)
+    with ran(only=[dec], what=name, **{dec: 1}):
+        got = cd.decompress_colmajor(batch, out=out)
     g = got.cpu().numpy().view(DTYPES[esz])
     assert np.array_equal(g, rows.T), name
     rest = out[:, nrows:].cpu().numpy().view(DTYPES[esz])
     assert (rest == (0x77 if esz == 1 else 0x7777)).all(), name
+    # both calls again through the runner: d_rets of either side, the whole destination, the families as the planner answers
+    res = cr.encode(sz, rows, codec, rpc, cs=cs, pair=enc_pair)
+    cr.check_encode(res, oracle, codec, rows, (name, enc_pair))
+    assert res.family == enc, (name, res.family)
+    res = cr.decode(sz, batch, codec, esz, ndims, rpc, nch * rpc + 8)
+    cr.check_decode(res, rows, (name, enc_pair))
+    assert res.family == dec, (name, res.family)
 
 
 def test_cfg5_full_shape(sz):

@@ -19,7 +19,7 @@ from drive_tables import FIRE_SHAPES as FIRE_TABLE
 from fixtures import chunks_per_group, no_fast, sz  # noqa: F401  (fixtures)
 from harness import DTYPES
 from rowdata import FLOAT_FAST_SHAPES as FAST_SHAPES, GENERIC_SHAPES, RAGGED_SHAPES, gen_data, lowdim, make_batch
-from streams import OLD, options
+from streams import OLD, options, truncated_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -336,7 +336,7 @@ def test_cumulative_rows_damaged_chunk(sz, oracle, chunks_per_group, plan, codec
     n = nchunks * chunk_len - 5 * D
     x = gen_data("walk", rng, n, esz, D)
     cd, good = make_batch(sz, oracle, codec, esz, D, chunk_len, x, False)
-    batch = cr.truncated_batch(sz, good, cut)
+    batch = truncated_batch(sz, good, cut)
     with options(**OLD):
         for cpg in (1, 3):
             chunks_per_group(cpg)
@@ -366,7 +366,7 @@ def test_cumulative_rows_damaged_single_chunk(sz, oracle, plan):
         chunk_len = D * 48
         x = gen_data("walk", rng, chunk_len, esz, D)
         cd, good = make_batch(sz, oracle, codec, esz, D, chunk_len, x, False)
-        batch = cr.truncated_batch(sz, good, 0)
+        batch = truncated_batch(sz, good, 0)
         seed = cr.random_carry(rng, D, esz)
         _, res = launch(plan, batch, x, codec, esz, D, chunk_len, 7, 8, (codec, esz, D), seed, bad=(0,), with_tmp=False)
         assert np.array_equal(res.carry, seed)

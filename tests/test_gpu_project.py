@@ -18,7 +18,7 @@ from drive_tables import ROWOP_CASES, ROWOP_IDS, fire_batch, rowop_batch
 from drive_tables import FIRE_SHAPES as FIRE_TABLE
 from fixtures import chunks_per_group, no_fast, sz  # noqa: F401  (fixtures)
 from rowdata import FLOAT_FAST_SHAPES as FAST_SHAPES, GENERIC_SHAPES, gen_data, lowdim, make_batch
-from streams import OLD, options
+from streams import OLD, options, truncated_batch
 from dispatch import ran
 from harness import DTYPES
 
@@ -287,18 +287,6 @@ def test_project_rows_no_chunks(sz):
 
 
 # ------------------------------------------------------------------ damage
-
-def truncated_batch(sz, batch, cut):
-    """the container with chunk `cut`'s stream 5 bytes short, the streams packed densely again"""
-    import torch
-    n = batch.nchunks
-    comp, offs, sizes = batch.data.cpu().numpy(), batch.offsets.cpu().numpy(), batch.sizes.cpu().numpy()
-    parts = [comp[offs[c]:offs[c] + sizes[c] - (5 if c == cut else 0)].copy() for c in range(n)]
-    toffs = np.zeros(n + 1, np.int64)
-    toffs[1:] = np.cumsum([p.size for p in parts])
-    return sz.CompressedBatch(torch.from_numpy(np.concatenate(parts + [np.zeros(sz._lib.READ_SLACK, np.uint8)])).cuda(), torch.from_numpy(toffs).cuda(),
-                              torch.tensor([p.size for p in parts], dtype=torch.int32).cuda(), n, batch.total_len, batch.chunk_len, batch.ndims)
-
 
 @pytest.mark.parametrize("codec,esz,D", [("xff", 2, 8), ("delta", 1, 32), ("delta", 2, 12)])
 def test_project_rows_damaged_chunk(sz, oracle, chunks_per_group, plan, codec, esz, D):

@@ -67,6 +67,16 @@ def test_an_output_of_4_GB_stays_on_the_older_kernel(probe):
     assert at.get("family") == "dec_fast" and below.get("family") == "dec_row", (at, below)
 
 
+@pytest.mark.parametrize("pair,family", [(1, "enc_pair"), (0, "enc_fast")])
+def test_a_column_stride_of_2_to_the_32_stays_on_the_generic_encoder(probe, pair, family):
+    """encode_fast.h and encode_wide.h keep a column-major source's stride as a 32-bit element count in their burst loads: 2^32 elements or
+    more are the generic kernel's (a 64-bit stride), eight less is theirs (the GPU tier needs 17 GB of HBM for this)"""
+    D, R, nchunks = 8, 64, 3
+    shape = dict(codec=CODEC["xff"], esz=2, D=D, chunk_len=R * D, nchunks=nchunks, total_len=nchunks * R * D, slot_stride=bound(2, R * D, D), **knobs(pair=pair))
+    at, below = probe(("encode", dict(shape, col_stride=1 << 32)), ("encode", dict(shape, col_stride=(1 << 32) - 8)))
+    assert at.get("family") == "enc_generic" and below.get("family") == family, (at, below)
+
+
 # shapes on which the PARENT's logic already violates a property of the sweep: findings, not behaviour changes (at most 1 % of the sweep)
 SWEEP_KNOWN = ()
 
