@@ -54,7 +54,8 @@ extern "C" {
  *      histogram_rows, SPRINTZ_HIST_MAX_COUNTERS; moments_rows, SPRINTZ_MOM_*; groupby_rows, SPRINTZ_GBY_*;
  *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
  *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR;
- *      rolling_rows, SPRINTZ_ROLL_*; project_rows, SPRINTZ_PROJECT_*; cumulative_rows / cumulative_tmp_bytes, SPRINTZ_CUM_* */
+ *      rolling_rows, SPRINTZ_ROLL_*; project_rows, SPRINTZ_PROJECT_*; cumulative_rows / cumulative_tmp_bytes, SPRINTZ_CUM_*;
+ *      derive_rows / derive_rows_tmp_bytes, SPRINTZ_DERIVE_* */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -1102,6 +1103,50 @@ int sprintz_mi355x_cumulative_rows(int codec, int elem_bytes, const void* d_comp
                                    uint32_t chunk_len, uint16_t ndims, uint32_t ops, int sum_bytes /* 4 or 8 */, uint32_t flags,
                                    void* d_min, void* d_max, void* d_sum, const uint64_t* d_carry_in, uint64_t* d_carry_out,
                                    void* d_tmp, int64_t* d_rets, void* hip_stream);
+/* Derive rows: SELECT <expression> -- K linear forms of every row and of the row in front of it, straight from the compressed batch; the decoded
+ * tensor never exists.  This is sprintz_mi355x_filter_linear's sum itself, K of them a row, returned instead of tested: the spread of two columns
+ * (a - b), the sum of a few, a column minus twice its neighbour, or, with lag weights, numpy.diff / pandas' diff().  The batch is given as to
+ * sprintz_mi355x_filter_linear (chunk_len % ndims == 0; the RLE codecs; at most 512 columns; a short last chunk may end mid-row: only whole rows are
+ * rows).  The batch's rows are g = 0 .. G - 1, row g being row g % R of chunk g / R, R = chunk_len / ndims.  For 1 <= nforms <= 16 and every row g:
+ *   s[g, k] = d_bias[k] + sum_d d_weights[k][d] x[g, d] + sum_d d_lag_weights[k][d] x[p(g), d]      modulo 2^32, read as an int32
+ * with x the unsigned sample, p(g) = g - 1 and p(0) = 0 -- row 0 is its own predecessor (numpy.diff(prepend = x[0])) -- unless d_prev gives the row
+ * in front of row 0: ndims elements of the element type, the last row of the batch before this one, so that a stream continued over batches
+ * differentiates exactly.  d_lag_weights == NULL: no lag term, no scratch, no second launch, and d_prev is ignored.  s is exact wherever
+ * |bias| + sum (|w| + |u|) (2^(8 elem_bytes) - 1) < 2^31 (the bound the Python layer refuses by); beyond it the value is the wrapped one.
+ * Output: a dense [G, nforms] tensor, row g at element g * nforms; a chunk's rows start at element c * R * nforms; rows that do not exist are not
+ * written.
+ *   format   : SPRINTZ_DERIVE_I32: out[g * nforms + k] = s[g, k], an int32
+ *              SPRINTZ_DERIVE_F32 / _F16 / _BF16: z = fl32(fl32((float)s * d_scale[k]) + d_offset[k]) -- the int32 -> float32 conversion rounds to
+ *              nearest even (from |s| >= 2^24 on), the two float32 operations are never one fma -- stored as float32, or rounded to nearest even to
+ *              float16 / bfloat16 as float_rows rounds: bit for bit torch's CPU (s.to(float32) * scale + offset).to(dtype)
+ *   d_scale, d_offset : float32 [nforms], or NULL: all 1 / all 0; with a float format only
+ *   flags    : SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else
+ *   d_tmp    : with d_lag_weights, scratch of sprintz_mi355x_derive_rows_tmp_bytes(elem_bytes, nchunks, ndims) bytes, 8-byte aligned (the first and the
+ *              last row of every chunk; filter_linear's layout and size).  Its content before the call does not matter.
+ *   d_rets   : (optional) exactly what sprintz_mi355x_decompress_batch writes for the same batch, damaged chunks included
+ * A damaged chunk (d_rets < 0): its own rows are unspecified, and so is row 0 of the chunk behind it where a lag term is given; every other row is
+ * exact, and nothing outside the batch's chunk slots is written.
+ * One launch (SPRINTZ_KF_DEC_FAST on the one-column-a-lane mappings, up to 64 columns, for the shapes the plain decode takes there with a 16-byte
+ * aligned d_out; SPRINTZ_KF_DEC_GENERIC otherwise); with a lag term and more than one chunk, or d_prev, a second small one behind it on the stream that
+ * writes row 0 of the chunks again with their true predecessors.  nchunks == 0 returns 0 and launches nothing.  No synchronisation, no allocation.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for a NULL d_comp / d_offsets / d_weights / d_out, nforms outside 1..16, chunk_len %
+ * ndims != 0, chunk_len outside 1..2^30, an unknown format or flag, d_scale / d_offset with SPRINTZ_DERIVE_I32, d_out not aligned to the output
+ * element, d_weights / d_lag_weights / d_bias / d_scale / d_offset not aligned to 4, d_prev to the element size, d_rets to 8, d_tmp NULL or not
+ * aligned to 8 with d_lag_weights; SPRINTZ_E_UNSUPPORTED for more than 512 columns and for the non-RLE codecs. */
+#define SPRINTZ_DERIVE_I32  0
+#define SPRINTZ_DERIVE_F32  1   /* 1 + SPRINTZ_FLOAT_F32 */
+#define SPRINTZ_DERIVE_F16  2
+#define SPRINTZ_DERIVE_BF16 3
+uint64_t sprintz_mi355x_derive_rows_tmp_bytes(int elem_bytes, uint64_t nchunks, uint16_t ndims);
+int sprintz_mi355x_derive_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, uint32_t nforms,
+                               const int32_t* d_weights,      /* [nforms][ndims] */
+                               const int32_t* d_lag_weights,  /* [nforms][ndims] or NULL */
+                               const int32_t* d_bias,         /* [nforms] or NULL: all 0 */
+                               int format,                    /* SPRINTZ_DERIVE_I32 0, _F32 1, _F16 2, _BF16 3 */
+                               const float* d_scale, const float* d_offset,   /* [nforms], float formats only */
+                               const void* d_prev,            /* [ndims] element type, or NULL */
+                               uint32_t flags, void* d_tmp, void* d_out, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

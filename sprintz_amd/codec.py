@@ -816,6 +816,87 @@ class ChunkedCodec:
                 res.view({1: torch.int8, 2: torch.int16, 4: torch.int32}[res.element_size()])[G - 1, lacks] = 0
         return res
 
+    def derive_rows(self, batch, forms, lag_forms=None, bias=0, dtype=None, scale=None, offset=None, prev=None, out=None, rets=None,
+                    general_layout=False, check=True):
+        """SELECT <expression>: K linear forms of every row, and of the row in front of it, decoded straight into a dense [G, K] tensor, G =
+        total_len // ndims -- filter_linear's sum itself, returned instead of tested; the integer tensor never exists.  For batch row g (row
+        g % R of chunk g // R, R = chunk_len / ndims: chunk_len must be a multiple of ndims; only whole rows are rows) and form k
+
+            out[g, k] = bias[k] + sum_d forms[k][d] x[g, d] + sum_d lag_forms[k][d] x[g - 1, d]
+
+        with x the unsigned samples as integers; row 0 is its own predecessor (numpy.diff(..., prepend=x[0])) unless prev gives the row in
+        front of it -- ndims entries, the last row of the batch before this one: a stream continued over batches then differentiates exactly.
+        forms / lag_forms: an integer tensor [K, ndims] or a sequence of K entries, each as filter_linear takes its weights (a scalar, a
+        sequence of ndims entries, a dict {column: weight}, a tensor); 1 <= K <= 16; lag_forms=None: no lag term (and prev is ignored).  bias: a
+        scalar or K entries.  Every form is exact: one that could reach 2^31 in magnitude is a ValueError (rowops.derive_forms).
+
+            spread = codec.derive_rows(batch, [{0: 1, 1: -1}])                               # SELECT a - b            -> int32 [G, 1]
+            both = codec.derive_rows(batch, [{0: 1, 1: -1}, {2: 1, 3: 1, 4: 1}])             # SELECT a - b, c + d + e -> int32 [G, 2]
+            volts = codec.derive_rows(batch, [{0: 1, 1: -1}], dtype=torch.float32, scale=0.01)
+            step = codec.derive_rows(batch, [{3: 1}], lag_forms=[{3: -1}])                   # x[g, 3] - x[g - 1, 3]: diff() of one column
+
+        dtype: None or torch.int32 for the sums themselves, or torch.float32 / torch.float16 / torch.bfloat16 for
+        (s.to(float32) * scale[k] + offset[k]).to(dtype), bit for bit what torch computes on the CPU; scale / offset: float_rows' forms with K
+        entries, a float dtype only.
+        -> a [G, K] tensor.  out: a contiguous tensor of the output dtype with at least nchunks x R x K elements (a chunk slot each chunk) to
+        write into -- its first G x K are the result; rets: an int64 tensor of nchunks entries for the per-chunk element counts (as decompress
+        reports them).  One library call: the decode and, with a lag term, its seam pass.  A damaged chunk's rows are unspecified, and row 0 of
+        the chunk behind it; check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        D, n = self.ndims, batch.nchunks
+        R, _ = rowops.chunk_rows(self.chunk_len, D, "derive_rows")
+        w, u, b = rowops.derive_forms(forms, lag_forms, bias, D, self.esz, self.device)
+        K = int(w.shape[0])
+        if dtype is None or dtype == torch.int32:
+            if scale is not None or offset is not None:
+                raise ValueError("scale and offset go with a float dtype")
+            dtype, fmt = torch.int32, _lib.DERIVE_I32
+        else:
+            fmt = 1 + rowops.float_format(dtype)
+            scale = rowops.float_params(scale, K, "scale", self.device)
+            offset = rowops.float_params(offset, K, "offset", self.device)
+        if prev is not None and u is not None:
+            prev = rowops.elem_tensor(prev, D, self.esz, self.dtype, self.device, "prev")
+        else:
+            prev = None
+        G = batch.total_len // D
+        if out is None:
+            out = torch.empty(n * R * K, dtype=dtype, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != dtype or out.device != self.device or out.numel() < n * R * K or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor of at least {n} x {R} x {K} elements on {self.device}")
+        if rets is None:
+            rets = self._rets(n, check)
+        tmp = torch.empty(max(_lib.derive_rows_tmp_bytes(self.esz, n, D) // 8, 1), dtype=torch.int64, device=self.device) if u is not None else None
+        res = out.view(-1)[: G * K].view(G, K)
+        if n:
+            with self._on():
+                _lib.check(_lib.derive_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n, self.chunk_len, D, K,
+                                            w.data_ptr(), _ptr(u), b.data_ptr(), fmt, _ptr(scale), _ptr(offset), _ptr(prev),
+                                            self._general(general_layout), _ptr(tmp), out.data_ptr(), _ptr(rets), self._stream()))
+            if check:
+                rowops.raise_damaged("derive_rows", rets, n, _lib.SprintzError)
+        return res
+
+    def diff_rows(self, batch, columns=None, **kw):
+        """pandas' diff(): out[g, j] = x[g, columns[j]] - x[g - 1, columns[j]] as int32 (derive_rows with forms e_c and lag_forms -e_c; row 0
+        changes by 0, or by its distance to prev's row where prev is given).  columns: up to 16 column numbers, None for all of them -- more
+        than 16 is a ValueError: call it once per 16 columns.  Every other argument is derive_rows'.
+
+            d = codec.diff_rows(batch)                         # torch.diff(x.to(int32), dim=0, prepend=x[:1])
+            d = codec.diff_rows(batch, [3], dtype=torch.float32, scale=0.5)"""
+        cols = list(range(self.ndims)) if columns is None else (columns.tolist() if self.torch.is_tensor(columns) or isinstance(columns, np.ndarray) else list(columns))
+        if not cols:
+            raise ValueError("columns must name at least one column")
+        if len(cols) > rowops.DERIVE_MAX_FORMS:
+            raise ValueError(f"diff_rows takes at most {rowops.DERIVE_MAX_FORMS} columns a call (derive_rows' forms), not {len(cols)}: call it once per {rowops.DERIVE_MAX_FORMS} columns")
+        for c in cols:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < self.ndims:
+                raise ValueError(f"column {c!r} is not an int in 0 .. {self.ndims - 1}")
+        for name in ("forms", "lag_forms"):
+            if name in kw:
+                raise ValueError(f"diff_rows builds {name} itself")
+        return self.derive_rows(batch, [{int(c): 1} for c in cols], lag_forms=[{int(c): -1} for c in cols], **kw)
+
     def cumulative_rows(self, batch, ops=("min", "max", "sum"), sum_dtype=None, carry=None, return_carry=False, general_layout=False, check=True):
         """Running min / max / sum / mean of every column from the first row on, one result per row -- cummin, cummax, cumsum and pandas'
         expanding().mean() -- straight from the compressed batch: the decoded tensor never exists.  Batch row g is row g % R of chunk g // R,

@@ -198,6 +198,15 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // block's rows at a pass.  No LDS of its own, and no barrier the plain decode has not.
     constexpr bool CUM = Q == kQueryCumulative;
     static_assert(!CUM || (!CM && !SPLIT && DS == 0 && CPL == 1), "cumulative rows: row-major destination, one column a lane");
+    // DER (sprintz_mi355x_derive_rows): nothing of the raw block is stored or staged.  A column's 8 rows wait in arow for der_out, behind the column:
+    // a form at a time, the lane multiplies its rows (and the rows in front of them: dlast hands row 7 over the block seam) by its column's two weights
+    // -- read from the workgroup's table in LDS, [K][D] pairs at a.table.table_off, filled once at the kernel's start -- the group adds the 8 partial
+    // sums up (group_add), and lane i mod DP puts row i's value, converted or not, at its place of the derived block in the group's staging: 8 rows
+    // of K values, in output order.  The block then leaves as whole 16-byte pieces, stored at once as rolling rows' are.  Every output-byte quantity
+    // -- the chunk's base in the descriptor, the descriptor's span, the cursor ovo -- counts K values of OSZ bytes a row; the launch sizes the staging
+    // for 8 K OSZ bytes where that is more than the decoded block (plan.h).
+    constexpr bool DER = Q == kQueryDerive;
+    static_assert(!DER || (!CM && !SPLIT && DS == 0 && CPL == 1), "derive rows: row-major destination, one column a lane");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
     constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -240,6 +249,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         c_sel = gp.chunk;
     }
     const uint64_t c_first = c_sel;
+    if constexpr (DER) {                                   // the workgroup's table of weights, every lane of it, before any leaves
+        uint2* const wt = (uint2*)(smem + a.table.table_off);
+        const uint32_t n = derive_k(a) * (uint32_t)D;
+        for (uint32_t i = threadIdx.x; i < n; i += kThreads) wt[i] = make_uint2((uint32_t)a.lin.w[i], a.lin.lag ? (uint32_t)a.lin.lag[i] : 0u);
+        __syncthreads();
+    }
     if constexpr (!HIST && !GBY) {
         if (c_first >= a.nchunks) return;
     }                                                      // (histogram, group-by: c_end <= c_first below, and the chunk loop does not run)
@@ -284,17 +299,19 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // (project rows: the same two, with the element type itself as one more format -- pflt: the pieces convert; and the elements of a chunk's
     //  projected slot, R x K)
     const bool pflt = PROJ && !(a.filter.mode & kProjectRawBit);
-    const uint32_t OSZ = FLT ? (uint32_t)float_out_bytes(a.filter.mode) : PROJ ? (uint32_t)project_out_bytes(a.filter.mode, ESZ) : (uint32_t)ESZ;
+    const uint32_t OSZ = FLT ? (uint32_t)float_out_bytes(a.filter.mode) : PROJ ? (uint32_t)project_out_bytes(a.filter.mode, ESZ)
+                       : DER ? (uint32_t)derive_out_bytes(a.filter.mode) : (uint32_t)ESZ;
     const uint32_t fshift = FLT ? (OSZ == 4u ? (ESZ == 1 ? 2u : 1u) : (ESZ == 1 ? 1u : 0u))
                           : PROJ ? (OSZ == 4u ? (ESZ == 1 ? 2u : 1u) : (OSZ == 2u && ESZ == 1 ? 1u : 0u)) : 0u;
-    const uint32_t pK = PROJ ? project_k(a) : 0u;
-    const uint32_t pslot_elems = PROJ ? a.chunk_len / (uint32_t)(EXACT ? DCAP : a.D) * pK : 0u;
-    const uint64_t out_base = PROJ ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)pslot_elems * OSZ
+    // (derive rows: K and the elements of a chunk's derived slot, R x K, in the same two)
+    const uint32_t pK = PROJ ? project_k(a) : DER ? derive_k(a) : 0u;
+    const uint32_t pslot_elems = (PROJ || DER) ? a.chunk_len / (uint32_t)(EXACT ? DCAP : a.D) * pK : 0u;
+    const uint64_t out_base = (PROJ || DER) ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)pslot_elems * OSZ
                             : FLT ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * OSZ
                             : CM ? (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)rows_per_chunk * ESZ
                             : SELECT ? 0
                                  : (wave_first < a.nchunks ? wave_first : 0) * (uint64_t)a.chunk_len * ESZ;
-    const uint64_t out_span = PROJ ? a.nchunks * (uint64_t)pslot_elems * OSZ - out_base
+    const uint64_t out_span = (PROJ || DER) ? a.nchunks * (uint64_t)pslot_elems * OSZ - out_base
                             : FLT ? a.nchunks * (uint64_t)a.chunk_len * OSZ - out_base
                             : CM ? (uint64_t)(EXACT ? DCAP : a.D) * a.col_stride * ESZ - out_base
                             : GATHER ? a.gather.nranges * (uint64_t)a.gather.rows * (uint64_t)(EXACT ? DCAP : a.D) * ESZ
@@ -505,10 +522,14 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     }
     // cumulative rows: each column's running min / max / sum (set at each chunk start)
     CumState cums[CUM ? CPL : 1];
+    // derive rows: the row in front of the block being decoded (clean), no row of the chunk is done, and the bytes of a derived block
+    uint32_t dlast[1] = {0};
+    uint32_t dfirst = 1;
+    const uint32_t dblk_bytes = DER ? 8u * pK * OSZ : 0u;
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL || CUM) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL || CUM || DER) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -574,6 +595,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                         rres[op == kCumMin ? 0 : CUM ? 1 : 0][k][j] = (uint32_t)v;
                     }
                 });
+        } else if constexpr (DER) {                        // (the chunk's first row leaves for the seam pass; the block's values leave in der_out)
+            if (a.lin.lag && dfirst && col_ok[k]) linear_slot<W>(a, lchunk, (uint32_t)D).first[genk[k]] = (U)arow[0];
         } else if constexpr (MOM || GBY) {
         } else if constexpr (Q != 0) { qsum[k] += qbs[k]; qbs[k] = 0; }
     };
@@ -977,6 +1000,50 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             ovo += blk_bytes;                              // (nothing else is staged in this mode: the next plane's own barrier comes first)
         }
     };
+    // derive rows: the block's 8 x K values leave (see DER above)
+    auto der_out = [&]() __attribute__((always_inline)) {
+        if constexpr (DER) {
+            const uint2* const wt = (const uint2*)(smem + a.table.table_off);
+            const uint32_t dmode = a.filter.mode;
+            uint32_t x[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) x[i] = arow[i] & MASK;
+            const uint32_t xp = dfirst ? x[0] : dlast[0];
+            wave_lds_sync();                               // (the pieces of the block before have been read)
+            for (uint32_t k = 0; k < pK; k++) {
+                const uint2 wu = wt[k * (uint32_t)D + (uint32_t)colk[0]];
+                const uint32_t w = col_ok[0] ? wu.x : 0u, u = col_ok[0] ? wu.y : 0u;      // (a stand-in lane contributes nothing)
+                uint32_t p[8];
+                p[0] = w * x[0] + u * xp;
+#pragma unroll
+                for (int i = 1; i < 8; i++) p[i] = w * x[i] + u * x[i - 1];
+                const uint32_t b = derive_bias(a, k);
+                const float sc = (dmode & kDeriveI32Bit) ? 1.0f : float_scale(a, k), of = (dmode & kDeriveI32Bit) ? 0.0f : float_offset(a, k);
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const uint32_t s = group_add<DP>(p[i]) + b;
+                    if (lane_d == (i & (DP - 1))) {
+                        uint8_t* const at = stage + ((uint32_t)i * pK + k) * OSZ;
+                        if (dmode & kDeriveI32Bit) {
+                            *(uint32_t*)at = s;
+                        } else {
+                            const float z = derive_value(s, sc, of);
+                            if ((dmode & 3u) == kFloatF32) *(uint32_t*)at = __float_as_uint(z);
+                            else *(uint16_t*)at = (uint16_t)((dmode & 3u) == kFloatF16 ? float_to_f16(z) : float_to_bf16(z));
+                        }
+                    }
+                }
+            }
+            wave_lds_sync();
+            for (uint32_t uo = lane16; uo < dblk_bytes; uo += ROW16) {
+                const uint4 t = *(const uint4*)(stage + uo);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), orsrc, ovo + uo, 0, kStoreAux);
+            }
+            ovo += dblk_bytes;
+            dlast[0] = x[7];
+            dfirst = 0;
+        }
+    };
     auto stage_out = [&](int slot) {
         if constexpr (query_reduce_only(Q)) return;
         if constexpr (ROLL) { roll_out(slot < 0); return; }
@@ -1281,7 +1348,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     q_row(k, i);
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM)
+                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM && !DER)
                         if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];
 #endif
                 }
@@ -1314,6 +1381,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 s_block();
             } else if constexpr (CUM) {                    // (called here, not through stage_out: hipcc did not inline that lambda into the 8-bit kernels, and its captures went to scratch)
                 cum_out();
+            } else if constexpr (DER) {                    // (called here too, for the same reason)
+                der_out();
             } else {
                 stage_out(-1);
             }
@@ -1414,7 +1483,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 q_row(k, i);
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM)
+                if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM && !DER)
                     if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
 #else
                 asm volatile("" :: "v"(pv[k]));
@@ -1447,7 +1516,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
         q_window();
         f_block();
-        if constexpr (CUM) cum_out(); else stage_out(slot);
+        if constexpr (CUM) cum_out(); else if constexpr (DER) der_out(); else stage_out(slot);
         s_block();
         if constexpr (GATHER) grow += 8u;
     };
@@ -1556,13 +1625,18 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
             for (int k = 0; k < CPL; k++) cums[CUM ? k : 0] = col_ok[k] ? cumulative_enter<W>(a, chunk, (uint32_t)D, (uint32_t)genk[k]) : CumState{MASK, 0u, 0ull};
         }
+        if constexpr (DER) {                               // the chunk's first row is its own predecessor inside the launch
+            dfirst = 1;
+            dlast[0] = 0;
+            lchunk = chunk;
+        }
         if constexpr (SELECT) {
             srank = 0;
             sbase = a.select.bases[chunk];
             srow0 = chunk * (uint64_t)a.select.rpc;
         }
         out_left = a.chunk_len;
-        ovo = PROJ ? (uint32_t)((chunk - wave_first) * (uint64_t)pslot_elems * OSZ)
+        ovo = (PROJ || DER) ? (uint32_t)((chunk - wave_first) * (uint64_t)pslot_elems * OSZ)
           : FLT ? (uint32_t)((chunk - wave_first) * (uint64_t)a.chunk_len * OSZ)
           : CM ? (uint32_t)((chunk - wave_first) * (uint64_t)rows_per_chunk * ESZ)
           : GATHER ? (uint32_t)(uint64_t)(gp.obase * ESZ)  // where the chunk's row 0 would land: only rows [lo, hi) are stored, and those lie in `out`
@@ -1692,7 +1766,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     for (int q = 0; q < PIECES; q++)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, held[s2][q]), orsrc, held_vo[s2][q], 0, kStoreAux);
             }
-        } else if constexpr (!query_reduce_only(Q) && !ROLL && !CUM) {
+        } else if constexpr (!query_reduce_only(Q) && !ROLL && !CUM && !DER) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -1807,6 +1881,11 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // the tail walks row by row at plain 64-bit addresses; in a call of one chunk the state behind it is the call's carry_out (decode_ops.h)
         if (!corrupt) cumulative_tail<W, CPL>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, cums);
         cumulative_leave<W, CPL>(a, chunk, corrupt, (uint32_t)D, genk, col_ok, cums);
+    } else if constexpr (DER) {
+        // the tail's whole rows leave value by value, at plain 64-bit addresses, then the chunk's rows for the seam pass (decode_ops.h: derive_tail);
+        // a damaged chunk has no row the seam pass may use
+        if (!corrupt) derive_tail<W, CPL>(a, chunk, a.comp + gabs + rp, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, genk, col_ok, dlast);
+        else linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
     } else if constexpr (PROJ) {
         // the tail's selected columns leave element by element, at plain 64-bit addresses (decode_ops.h: project_tail)
         if (!corrupt && remaining > 0) project_tail<W>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, lane_d, DP);

@@ -46,6 +46,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // CUM (sprintz_mi355x_cumulative_rows): every sample leaves as its column's running min / max / sum from the batch's first row on; a lane keeps the
     // running values of its columns in registers, loaded at the chunk's start from the scan's table (decode_ops.h: cumulative_rows8)
     constexpr bool CUM = Q == kQueryCumulative;
+    // DER (sprintz_mi355x_derive_rows): K linear forms of every row and the row in front of it leave as a dense [rows, K] output, a form at a time
+    // (decode_ops.h: derive_rows8); nothing of the decoded block is stored or staged, runs are replayed block by block
+    constexpr bool DER = Q == kQueryDerive;
     constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT || SEG;
     constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)nd != D || len > a.chunk_len) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
-            if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
+            if constexpr (LIN || DER) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
             if constexpr (CUM) cumulative_mark(a, chunk, (uint32_t)D, lane_d, DP, W);
             if constexpr (TAB) hbad = true; else return;
@@ -117,7 +120,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         if ((int)(w1 >> 16) != D) {
             if constexpr (Q == kQueryGather) { if (lane_d == 0) gather_fail(a, gp.range, kErrCorrupt); }
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
-            if constexpr (LIN) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
+            if constexpr (LIN || DER) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
             if constexpr (CUM) cumulative_mark(a, chunk, (uint32_t)D, lane_d, DP, W);
             if constexpr (TAB) hbad = true; else return;
@@ -215,6 +218,14 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
         for (int k = 0; k < CPL; k++) lc[k] = linear_col(a, colk[k], genk[k]);
         lctx = linear_ctx(a);
         if (a.filter.mask) fmb = a.filter.mask + chunk * (uint64_t)a.filter.mask_stride;
+    }
+
+    // derive rows: each column's row in front of the block being decoded (the lag term's predecessor); no row of the chunk is done
+    uint32_t dlast[DER ? CPL : 1];
+    bool dfirst = true;
+    if constexpr (DER) {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) dlast[k] = 0;
     }
 
     // select rows: the chunk's first output row and the set bits of the blocks done so far
@@ -521,6 +532,19 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         if constexpr (ROLL) rrun = (!FIRE && run_block) ? rrun + 1u : 0u;
 
+        if constexpr (DER) {
+            // the chunk's first row leaves for the seam pass; then the block's 8 x K values, each at its place (out_elems + blk_elems <= chunk_len:
+            // checked above, so the rows lie inside the chunk's R); 64-bit addresses, so this kernel takes every layout, every K and every alignment
+            if (dfirst && a.lin.lag) {
+#pragma unroll
+                for (int k = 0; k < CPL; k++)
+                    if (genk[k]) linear_slot<W>(a, chunk, (uint32_t)D).first[colk[k]] = (U)v[0][k];
+            }
+            derive_rows8<CPL>(a, chunk * (uint64_t)(a.chunk_len / (uint32_t)D) + out_elems / (uint32_t)D, (uint32_t)D, lane_d, DP, colk, genk, [&](int c, int i) { return v[i][c]; }, dfirst, dlast,
+                              [&](uint32_t x) { return group_sum(x, DP); });
+            dfirst = false;
+        }
+
         if constexpr (SEG) segment_block_done(a, sblk, sst, sbase, grow0, out_elems / (uint32_t)D, lane_d);   // behind the block's columns
 
         if constexpr (Q == kQueryFilter) {       // block out_elems / blk_elems < chunk_len / blk_elems <= mask_stride (checked above)
@@ -537,7 +561,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         // ---- store the 8 x D block (contiguous 8*D*ESZ bytes of the output)
         U* const ob = o + out_elems;
-        if constexpr (query_reduce_only(Q) || ROLL || CUM) {       // (rolling rows: the block's results left from the column loop, the raw rows went to the ring; cumulative rows: likewise, no ring)
+        if constexpr (query_reduce_only(Q) || ROLL || CUM || DER) {       // (derive rows: the block's values left above; rolling rows: the block's results left from the column loop, the raw rows went to the ring; cumulative rows: likewise, no ring)
             (void)ob;
         } else if constexpr (Q == kQueryGather) {
             // rows [lo, hi) of the chunk alone, each at its place in the range; the parse stops after row hi - 1
@@ -720,6 +744,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (CUM) {
         if (!corrupt) cumulative_tail<W, CPL>(a, chunk, s + pos, out_elems, remaining, (uint32_t)D, colk, genk, cst);
         cumulative_leave<W, CPL>(a, chunk, corrupt, (uint32_t)D, colk, genk, cst);
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        return;
+    }
+    if constexpr (DER) {
+        if (!corrupt) derive_tail<W, CPL>(a, chunk, s + pos, remaining, (uint32_t)D, out_elems / blk_elems, lane_d, DP, colk, genk, dlast);
+        else linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
         if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }

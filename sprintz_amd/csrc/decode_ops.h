@@ -1,5 +1,5 @@
 // decode_ops.h -- the row operations the decoders carry out while they decode (reduce / window queries, gather, filter, select,
-// aggregate, histogram, moments, group-by, extrema, linear filter, segment, float, rolling, project and cumulative rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
+// aggregate, histogram, moments, group-by, extrema, linear filter, segment, float, rolling, project, cumulative and derive rows): each one's arguments, its per-block helpers and its verbatim tail, written once for
 // every lane mapping -- and what several of them share, once for all of them: the row mask that names the rows to take (RowMaskArgs,
 // run_selected_rows, masked_tail_rows), the walk over a chunk's windows (window_advance, window_tail_rows) and the workgroup's table of
 // bins in LDS (BinTableArgs, table_begin .. table_end).  A kernel hands over its lane's columns (`col`, with `genuine` false for a lane
@@ -39,9 +39,9 @@ struct FilterArgs {
     const void* lo;             // [D], element type, on the device (float rows: the scale, float32 [D] or null; project rows: of every slot, [K])
     const void* hi;             // (float rows: the offset)
     uint32_t mode;              // SPRINTZ_FILTER_ALL 0 / SPRINTZ_FILTER_ANY 1: wave-uniform, not a template parameter (float rows: format | kFloatSignedBit)
-    uint8_t* mask;              // optional (project rows: the slot table, int32 [D])
-    uint32_t* counts;           // optional
-    uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8) (project rows: K, the columns of an output row)
+    uint8_t* mask;              // optional (project rows: the slot table, int32 [D]; derive rows: the biases, int32 [K], or null)
+    uint32_t* counts;           // optional (derive rows: the caller's `prev` row, [D] of the element type, or null)
+    uint32_t mask_stride;       // MB: mask bytes of a chunk slot, ceil(ceil(chunk_len / D) / 8) (project rows: K, the columns of an output row; derive rows: K, the forms)
 };
 // the rows that select, aggregate, histogram, moments, group-by and extrema rows take: those whose bits are set in chunk c's mask bytes
 // mask[c * stride ...] (filter_rows' layout).  mask == null -- where the operation allows it -- is every existing row: a run-time,
@@ -112,7 +112,7 @@ struct ExtremaArgs {
 // decode leaves every chunk's first and last existing row in tmp (LinearSlot) and the seam pass puts row 0 of the chunks behind the first right
 struct LinearArgs {
     const int32_t* w;           // [D], on the device (cumulative rows: the caller's carry_out, uint64 [3][D], in a call of one chunk; else null)
-    const int32_t* lag;         // [D], or null: no lag term
+    const int32_t* lag;         // [D], or null: no lag term (derive rows: w and lag are [K][D])
     void* tmp;                  // nchunks x linear_tmp_stride (geom.h) bytes where lag is given (rolling rows: nchunks x roll_tmp_stride, or null with one chunk; cumulative rows: the chunks' entering states, uint64 [nchunks][3][D], or null)
     int32_t lo, hi, bias;
     uint32_t pad;
@@ -159,7 +159,9 @@ struct DecodeArgs {
     // (Extrema rows' arguments came out of keep_size: 40 of its 80 spare bytes, behind every field that was there.  The linear filter's took the
     //  other 40: the spare bytes are used up, and the next mode's arguments have to share a struct that is here, as the linear filter shares
     //  FilterArgs, or move the kernels named above.  Float rows do: scale, offset and format ride in FilterArgs' lo, hi and mode.  Rolling rows
-    //  do: WindowArgs, LinearArgs::tmp and BinTableArgs::table_off.  Cumulative rows do: WindowArgs, LinearArgs::tmp and LinearArgs::w.)
+    //  do: WindowArgs, LinearArgs::tmp and BinTableArgs::table_off.  Cumulative rows do: WindowArgs, LinearArgs::tmp and LinearArgs::w.  Derive rows
+    //  do: the [K][D] weight tables and the seam scratch in LinearArgs' w, lag and tmp; scale, offset, format, biases, `prev` and K in FilterArgs' lo,
+    //  hi, mode, mask, counts and mask_stride; decode_fast.h's table of weights in LDS at BinTableArgs::table_off.)
     WindowArgs win;
     MomentArgs mom;
     BinTableArgs table;
@@ -1695,6 +1697,112 @@ __device__ __forceinline__ void cumulative_mark(const DecodeArgs& a, uint64_t ch
         out[d] = st ? st[chunk * 3ull * D + d] & mask : mask;
         out[D + d] = st ? st[chunk * 3ull * D + D + d] & mask : 0ull;
         out[2u * D + d] = st ? st[chunk * 3ull * D + 2u * D + d] : 0ull;
+    }
+}
+
+// ---- derive rows (Q == kQueryDerive; sprintz_mi355x_derive_rows): the linear filter's sum itself, K forms of it a row.  Row r of chunk c is row
+// g = c * R + r of a dense [rows, K] output, R = chunk_len / D, and form k's value s[g, k] = bias[k] + sum_d w[k, d] x[g, d] + sum_d u[k, d] x[g - 1, d]
+// (wrapping 32-bit arithmetic, the unsigned element) leaves at element g * K + k: as the int32 it is, or as fl32(fl32((float)s * scale[k]) +
+// offset[k]) in float32 / float16 / bfloat16.  The arguments travel in structs that are here: LinearArgs' w and lag are the [K][D] tables and tmp the
+// seam scratch (LinearSlot, as the linear filter leaves it); FilterArgs' lo / hi are the scale and the offset of every FORM (float32 [K], or null),
+// mode float rows' format with kDeriveI32Bit for "the sum, unconverted", mask the biases (int32 [K], or null: all 0), counts the caller's `prev` row
+// ([D], element type, or null; the seam pass alone reads it) and mask_stride K.  Inside the decode launch a chunk's first row is its own
+// predecessor, as for the linear filter; with a lag term the seam pass of decode_derive.hip then writes row 0 of every chunk again.
+__device__ __forceinline__ uint32_t derive_k(const DecodeArgs& a) { return a.filter.mask_stride; }
+__device__ __forceinline__ uint32_t derive_bias(const DecodeArgs& a, uint32_t k) { return a.filter.mask ? (uint32_t)((const int32_t*)a.filter.mask)[k] : 0u; }
+__device__ __forceinline__ const void* derive_prev(const DecodeArgs& a) { return (const void*)a.filter.counts; }
+// the int32 -> float32 conversion rounds to nearest even (from |s| >= 2^24 on); both operations behind it are IEEE float32 and never one fma
+__device__ __forceinline__ float derive_value(uint32_t s, float sc, float of)
+{
+#pragma clang fp contract(off)
+    const float f = (float)(int32_t)s;
+    const float m = f * sc;
+    return m + of;
+}
+// one value to place idx of the output, plain 64-bit addresses (the generic kernel's blocks, every kernel's tail, the seam pass); mode is wave-uniform
+__device__ __forceinline__ void derive_put(const DecodeArgs& a, uint64_t idx, uint32_t s, uint32_t k)
+{
+    const uint32_t mode = a.filter.mode;
+    if (mode & kDeriveI32Bit) ((uint32_t*)a.out)[idx] = s;
+    else float_put(a.out, mode & 3u, idx, derive_value(s, float_scale(a, k), float_offset(a, k)));
+}
+// A block's 8 rows on the generic kernel, every lane of the group: at(c, i) is row i of the lane's column slot c (clean), row0 the batch row of the
+// block's row 0, `first`: the block is the chunk's first (its row 0 is its own predecessor), last[c]: the row in front of the block, and behind
+// it the block's row 7.  A form at a time: the lane's partial sums of the 8 rows over its columns, the group's sums (gsum), and lane i mod DP
+// stores row i's value -- no K-sized array waits in registers, whatever K is.
+template <int CPL, typename F, typename S>
+__device__ __forceinline__ void derive_rows8(const DecodeArgs& a, uint64_t row0, uint32_t D, int lane_d, int DP, const int (&col)[CPL], const bool (&genuine)[CPL],
+                                             F at, bool first, uint32_t (&last)[CPL], S gsum)
+{
+    const uint32_t K = derive_k(a);
+    const bool lag = a.lin.lag != nullptr;
+    for (uint32_t k = 0; k < K; k++) {
+        uint32_t p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < CPL; c++) {
+            if (!genuine[c]) continue;
+            const uint32_t w = (uint32_t)a.lin.w[k * D + (uint32_t)col[c]];
+#pragma unroll
+            for (int i = 0; i < 8; i++) p[i] += w * at(c, i);
+            if (lag) {
+                const uint32_t u = (uint32_t)a.lin.lag[k * D + (uint32_t)col[c]];
+                p[0] += u * (first ? at(c, 0) : last[c]);
+#pragma unroll
+                for (int i = 0; i < 7; i++) p[i + 1] += u * at(c, i);
+            }
+        }
+        const uint32_t b = derive_bias(a, k);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const uint32_t s = gsum(p[i]) + b;
+            if ((uint32_t)lane_d == ((uint32_t)i & (uint32_t)(DP - 1))) derive_put(a, (row0 + (uint64_t)i) * K + k, s, k);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CPL; c++) last[c] = at(c, 7);
+}
+// The verbatim tail, linear_tail's walk with values out instead of bits: `remaining` elements at t, row-major from the row behind the chunk's
+// `blocks_done` blocks.  Only whole rows are rows; the tail's first row takes the last decoded row (last[c], clean) as its predecessor or, in a chunk
+// that is all tail, itself; the rows behind it take the tail's previous row.  Then, with a lag term, the chunk's first and last existing rows and
+// whether it has a row at all leave for the seam pass, exactly as the linear filter leaves them.
+template <int W, int CPL>
+__device__ __forceinline__ void derive_tail(const DecodeArgs& a, uint64_t chunk, const uint8_t* t, uint32_t remaining, uint32_t D, uint32_t blocks_done,
+                                            int lane_d, int DP, const int (&col)[CPL], const bool (&genuine)[CPL], const uint32_t (&last)[CPL])
+{
+    using U = typename Elem<W>::U;
+    const uint32_t nfull = remaining / D, K = derive_k(a);
+    const bool lag = a.lin.lag != nullptr;
+    const uint64_t row0 = chunk * (uint64_t)(a.chunk_len / D) + 8ull * blocks_done;
+    for (uint32_t r = 0; r < nfull; r++) {
+        for (uint32_t k = 0; k < K; k++) {
+            uint32_t p = 0;
+#pragma unroll
+            for (int c = 0; c < CPL; c++) {
+                if (!genuine[c]) continue;
+                const uint32_t x = tail_elem<W>(t, r * D + (uint32_t)col[c]);
+                p += (uint32_t)a.lin.w[k * D + (uint32_t)col[c]] * x;
+                if (lag) {
+                    const uint32_t xp = r != 0 ? tail_elem<W>(t, (r - 1u) * D + (uint32_t)col[c]) : blocks_done != 0 ? last[c] : x;
+                    p += (uint32_t)a.lin.lag[k * D + (uint32_t)col[c]] * xp;
+                }
+            }
+            const uint32_t s = group_sum(p, DP) + derive_bias(a, k);
+            if ((uint32_t)lane_d == (k & (uint32_t)(DP - 1))) derive_put(a, (row0 + r) * K + k, s, k);
+        }
+    }
+    if (lag) {
+        const LinearSlot<W> s = linear_slot<W>(a, chunk, D);
+#pragma unroll
+        for (int c = 0; c < CPL; c++) {
+            if (!genuine[c]) continue;
+            if (nfull != 0) {
+                if (blocks_done == 0) s.first[col[c]] = (U)tail_elem<W>(t, (uint32_t)col[c]);
+                s.last[col[c]] = (U)tail_elem<W>(t, (nfull - 1u) * D + (uint32_t)col[c]);
+            } else if (blocks_done != 0) {
+                s.last[col[c]] = (U)last[c];
+            }
+        }
+        if (lane_d == 0) *s.has = (nfull != 0 || blocks_done != 0) ? 1u : 0u;
     }
 }
 

@@ -90,7 +90,7 @@ struct HostCall {
 
 // query-on-compressed options of one decode launch (the decoders' Q template parameter; decode_ops.h)
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryCumulative (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryDerive (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -109,7 +109,9 @@ struct QuerySpec {
     // (kQuerySegment has no struct of its own: win, select and rows carry it -- decode_ops.h, segment rows; kQueryFloat rides in filter: lo the scale, hi the offset, mode the format;
     //  kQueryRolling in win -- W, the ops, the outputs -- and lin.tmp, the seam scratch: decode_ops.h, rolling rows; kQueryProject in filter, as
     //  kQueryFloat does, with mask the slot table and mask_stride K: decode_ops.h, project rows;
-    //  kQueryCumulative in win -- the ops, sum_bytes in count, the outputs -- lin.tmp, the chunks' entering states, and lin.w, carry_out: decode_ops.h, cumulative rows)
+    //  kQueryCumulative in win -- the ops, sum_bytes in count, the outputs -- lin.tmp, the chunks' entering states, and lin.w, carry_out: decode_ops.h, cumulative rows;
+    //  kQueryDerive in lin -- the [K][D] weight tables and the seam scratch -- and filter: lo the scale, hi the offset, mode the format, mask the biases,
+    //  counts the `prev` row, mask_stride K: decode_ops.h, derive rows)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;

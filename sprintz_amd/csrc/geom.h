@@ -39,12 +39,15 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // inside the launch; the seam pass of decode_rolling.hip carries it over the chunk seams), stored at the element's place in place of the element;
 // 16 = project: a plain decode (or float rows) that stores only the K columns a slot table names, each at its slot of a dense [rows, K] output;
 // 17 = cumulative: per element the running min / max / sum of its column from the batch's first row to its row, stored at the element's place in place of
-// the element; a chunk starts from the state the scan of decode_cumulative.hip left for it.
+// the element; a chunk starts from the state the scan of decode_cumulative.hip left for it;
+// 18 = derive: nothing of a decoded row is stored but K linear forms of it and of the row in front of it -- the linear filter's sum itself, K times, as int32
+// or converted as float rows convert -- each at its place of a dense [rows, K] output; the seam pass of decode_derive.hip carries the lag term over the chunk seams.
 // 6 .. 11 and 13 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
               kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14, kQueryRolling = 15;
 constexpr int kQueryProject = 16;
 constexpr int kQueryCumulative = 17;
+constexpr int kQueryDerive = 18;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
@@ -57,6 +60,11 @@ constexpr int float_out_bytes(uint32_t mode) { return (mode & 3u) == kFloatF32 ?
 // project rows: the same word, with one bit more for "the element type, unconverted"; an output element's bytes
 constexpr uint32_t kProjectRawBit = 8;
 constexpr int project_out_bytes(uint32_t mode, int esz) { return (mode & kProjectRawBit) ? esz : float_out_bytes(mode); }
+// derive rows: float rows' word, with one bit more for "the int32 sum, unconverted" (the same bit project rows use for their raw format); an output
+// element's bytes; the most forms a call takes
+constexpr uint32_t kDeriveI32Bit = 8;
+constexpr int derive_out_bytes(uint32_t mode) { return (mode & kDeriveI32Bit) ? 4 : float_out_bytes(mode); }
+constexpr uint32_t kDeriveMaxForms = 16;
 // rolling rows: the ops (SPRINTZ_ROLL_MIN / _MAX / _SUM, WindowArgs::ops) and the LDS a workgroup's launch can be given.  A chunk's history
 // ring holds the last W + 8 raw rows of its columns, column by column (a lane reads 8 rows of a column as one piece), rounded up to 16 bytes
 constexpr uint32_t kRollMin = 1, kRollMax = 2, kRollSum = 4;

@@ -41,13 +41,13 @@ struct Shape {
     unsigned src_lo = 0, slots_lo = 0, out_lo = 0, comp_lo = 0;   // the low four bits of the source, slot, output and container addresses
     uint64_t slot_stride = 0;
     uint64_t nranges = 0;                  // gather
-    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W; project rows: the columns K of the output
+    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W; project rows: the columns K of the output; derive rows: the forms K
     uint64_t capacity = 0;                 // select: rows of the output
     // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
     // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
     uint32_t table_entries = 0, table_row_max = 0;
     // the element bytes on the float side (4, or 2 for float16 / bfloat16): float rows' output element -- what every bound on output BYTES
-    // counts in (project rows: the output element whatever it is, esz unconverted) -- and, for an encode with q == kQueryFloat, the float
+    // counts in (project rows: the output element whatever it is, esz unconverted; derive rows: 4 for int32 and float32, 2 for the 16-bit floats) -- and, for an encode with q == kQueryFloat, the float
     // source's element; 0: the call has no float side
     int out_esz = 0;
 };
@@ -264,6 +264,44 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
             p.chunks_per_group = (uint32_t)k.chunks_per_group;
             const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
             return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, (uint64_t)f.ring * (kThreads / f.dp));
+        }
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, 0);
+    }
+
+    // derive rows (K in s.rows; s.out_esz the bytes of an output element: 4 for int32 and float32, 2 for float16 / bfloat16).  A chunk's R = chunk_len / D
+    // rows leave as R x K values from output element c x R x K on.  decode_fast.h takes, on its one-column-a-lane mappings (up to 64 columns), every shape
+    // the plain decode takes there: the DERIVED block, 8 K osz bytes, is a whole number of 16-byte store pieces for every K, the reach of the store
+    // descriptor is counted in derived output bytes, and the output must be 16-byte aligned.  The group's staging is sized for the derived block where
+    // that is more than the decoded one, and the workgroup's table of weights ([K][D] pairs of words) sits behind the groups' carves (table_off), both
+    // within the budget the histogram's launch has.  With two and four columns a lane the mode is not instantiated (a lane would keep the block's rows of
+    // every column in registers next to the plain decode's state; plan.h names no such mapping), and everything else -- the low-dim shapes too:
+    // decode_uni.h is not taught the mode -- runs the generic kernel, which stores value by value at 64-bit addresses and stages nothing.
+    if (s.q == kQueryDerive) {
+        const uint32_t K = s.rows;
+        if (K == 0 || K > kDeriveMaxForms) return plan_fail(p, SPRINTZ_E_INVALID, "derive_rows: nforms must be in 1 .. 16");
+        if (D > 512 || norle || cs) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "derive_rows: the RLE codecs, row-major, at most 512 columns");
+        const int dosz = s.out_esz ? s.out_esz : 4;
+        const uint64_t slot_bytes = (uint64_t)(chunk_len / (uint32_t)D) * K * (uint64_t)dosz;      // a chunk's derived output
+        const FastMap f = decode_fast_map(esz, D, 0, false);
+        const uint64_t fgroups = (uint64_t)(kThreads / f.dp);
+        const uint64_t staged = ((uint64_t)8 * D * esz + 15) & ~15ull, derived = (uint64_t)8 * K * dosz;
+        const uint64_t dstride = (uint64_t)f.ring + (derived > staged ? derived - staged : 0);
+        const uint64_t wtable = (uint64_t)K * D * 8;
+        const bool fast = !lowdim && !s.noheader && f.cpl == 1 && 2 * D > f.dp * f.cpl && (uint64_t)chunk_len * esz * 2 >= f.ring && !k.no_fast &&
+                          // the plain decode's terms for the shape (whole 16-byte pieces a block and a chunk, a 16-byte aligned output) ...
+                          ((uint64_t)8 * D * esz) % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0 && (s.out_lo % 16) == 0 &&
+                          // ... and the derivation's: the wave's chunks within reach of 32-bit offsets, staging and table within the LDS budget
+                          slot_bytes * 64 * 64 < 0xf0000000ull && dstride * fgroups + wtable <= kHistFastLdsBudget;
+        if (fast) {
+            p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
+            p.exact = D == f.dp * f.cpl;
+            p.log2DP = f.log2dp;
+            p.lds_group_stride = (uint32_t)dstride;
+            p.vec_store = 1;
+            p.chunks_per_group = (uint32_t)k.chunks_per_group;
+            p.table_off = (uint32_t)(dstride * fgroups);
+            const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
+            return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, dstride * fgroups + wtable);
         }
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, 0);
     }

@@ -1,5 +1,5 @@
 // row_ops.hip -- the row operations of the C-ABI (include/sprintz_mi355x.h): queries, the zone map, filters, select, aggregate,
-// moments, extrema, segments, float rows, rolling rows, project rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
+// moments, extrema, segments, float rows, rolling rows, project rows, derive rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
 // fills its QuerySpec and hands over to decode_batch (entry.h); what the decoders then do with a row is decode_ops.h's.
 #include "entry.h"
 
@@ -556,6 +556,61 @@ int sprintz_mi355x_project_rows(int codec, int elem_bytes, const void* d_comp, c
     qs.filter.mask = (uint8_t*)const_cast<int32_t*>(d_slots);
     qs.filter.mask_stride = ncolumns;
     return decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
+}
+
+// ---------------------------------------------------------------- derive rows
+uint64_t sprintz_mi355x_derive_rows_tmp_bytes(int elem_bytes, uint64_t nchunks, uint16_t ndims)
+{
+    return sprintz_mi355x_filter_linear_tmp_bytes(elem_bytes, nchunks, ndims);      // the linear filter's scratch, as it is (decode_ops.h: LinearSlot)
+}
+
+int sprintz_mi355x_derive_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                               uint32_t chunk_len, uint16_t ndims, uint32_t nforms, const int32_t* d_weights, const int32_t* d_lag_weights,
+                               const int32_t* d_bias, int format, const float* d_scale, const float* d_offset, const void* d_prev,
+                               uint32_t flags, void* d_tmp, void* d_out, int64_t* d_rets, void* hip_stream)
+{
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims};
+    int rc = unmasked_row_op("derive_rows", b, flags);
+    if (rc) return rc;
+    if (nforms < 1 || nforms > kDeriveMaxForms) return fail_op(SPRINTZ_E_INVALID, "derive_rows", "nforms must be in 1 .. 16");
+    static_assert(SPRINTZ_DERIVE_F32 == 1 + SPRINTZ_FLOAT_F32 && SPRINTZ_DERIVE_F16 == 1 + SPRINTZ_FLOAT_F16 && SPRINTZ_DERIVE_BF16 == 1 + SPRINTZ_FLOAT_BF16,
+                  "a float format travels as float rows' number");
+    if (format != SPRINTZ_DERIVE_I32 && format != SPRINTZ_DERIVE_F32 && format != SPRINTZ_DERIVE_F16 && format != SPRINTZ_DERIVE_BF16)
+        return fail(SPRINTZ_E_INVALID, "derive_rows: format must be SPRINTZ_DERIVE_I32, SPRINTZ_DERIVE_F32, SPRINTZ_DERIVE_F16 or SPRINTZ_DERIVE_BF16");
+    const bool i32 = format == SPRINTZ_DERIVE_I32;
+    if (i32 && (d_scale || d_offset)) return fail_op(SPRINTZ_E_INVALID, "derive_rows", "d_scale and d_offset go with a float format only");
+    if (!d_weights || !d_out) return fail(SPRINTZ_E_INVALID, "derive_rows: null device pointer");
+    const uint32_t mode = i32 ? kDeriveI32Bit : (uint32_t)(format - 1);
+    if ((uintptr_t)d_out % (uintptr_t)derive_out_bytes(mode)) return fail(SPRINTZ_E_INVALID, "derive_rows: d_out must be aligned to the output element size");
+    if ((uintptr_t)d_weights % 4 || (uintptr_t)d_lag_weights % 4 || (uintptr_t)d_bias % 4 || (uintptr_t)d_scale % 4 || (uintptr_t)d_offset % 4 ||
+        (uintptr_t)d_prev % (uintptr_t)elem_bytes || (uintptr_t)d_rets % 8)
+        return fail(SPRINTZ_E_INVALID, "derive_rows: d_weights, d_lag_weights, d_bias, d_scale and d_offset must be aligned to 4 bytes, d_prev to the element size, d_rets to 8");
+    if (d_lag_weights && (!d_tmp || (uintptr_t)d_tmp % 8))
+        return fail(SPRINTZ_E_INVALID, "derive_rows: with d_lag_weights, d_tmp must hold sprintz_mi355x_derive_rows_tmp_bytes bytes, aligned to 8");
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    // the mode shares structs that exist (decode_ops.h, derive rows): the weight tables and the seam scratch in LinearArgs; scale, offset, format,
+    // biases, the `prev` row and K in FilterArgs
+    QuerySpec qs = row_query(kQueryDerive, flags);
+    qs.lin = LinearArgs{d_weights, d_lag_weights, d_lag_weights ? d_tmp : nullptr, 0, 0, 0, 0u};
+    qs.filter.lo = d_scale;
+    qs.filter.hi = d_offset;
+    qs.filter.mode = mode;
+    qs.filter.mask = (uint8_t*)const_cast<int32_t*>(d_bias);
+    qs.filter.counts = d_lag_weights ? (uint32_t*)const_cast<void*>(d_prev) : nullptr;
+    qs.filter.mask_stride = nforms;
+    rc = decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
+    if (rc || !d_lag_weights || (nchunks < 2 && !d_prev)) return rc;
+    // the seam pass, behind the decode on the same stream: row 0 of every chunk behind the first -- and of the first, with d_prev -- takes its true predecessor
+    DecodeArgs a{};
+    a.nchunks = nchunks;
+    a.chunk_len = chunk_len;
+    a.D = ndims;
+    a.out = d_out;
+    a.filter = qs.filter;
+    a.lin = qs.lin;
+    if (launch_derive_seam(elem_bytes, a, (hipStream_t)hip_stream) != hipSuccess) return fail(SPRINTZ_E_HIP, "derive_rows seam kernel launch");
+    return 0;
 }
 
 // ---------------------------------------------------------------- cumulative rows

@@ -401,6 +401,16 @@ def _weights(v, ndims, name):
     return [int(e) for e in _entries(v, ndims, name)]
 
 
+def linear_bound(w, u, bias, esz, what="the linear form"):
+    """B = |bias| + (2^W - 1) sum_d (|w[d]| + |u[d]|) of one form (lists of ints; u None: no lag term): below 2^31 the kernels' wrapping 32-bit
+    sum is the exact integer, so a form that can reach 2^31 is a ValueError -- filter_linear's rule and derive_rows', stated once"""
+    B = abs(bias) + ((1 << (8 * esz)) - 1) * (sum(abs(e) for e in w) + sum(abs(e) for e in u or ()))
+    if B >= 1 << 31:
+        raise ValueError(f"{what} can reach {B} in magnitude: |bias| + (2^{8 * esz} - 1) sum(|w| + |u|) must stay below 2^31, "
+                         "or the 32-bit sum wraps")
+    return B
+
+
 def linear_terms(weights, lag_weights, bias, lo, hi, ndims, esz, device):
     """filter_linear's arguments -> (w, u, bias, lo, hi): w and u contiguous int32 tensors [ndims] on `device` (u None where
     lag_weights is None: no lag term), bias / lo / hi Python ints that fit int32.  weights / lag_weights: a scalar (every column), a
@@ -416,12 +426,40 @@ def linear_terms(weights, lag_weights, bias, lo, hi, ndims, esz, device):
     for name, v in (("lo", lo), ("hi", hi)):
         if not INT32_MIN <= v <= INT32_MAX:
             raise ValueError(f"{name} = {v} does not fit int32")
-    B = abs(bias) + ((1 << (8 * esz)) - 1) * (sum(abs(e) for e in w) + sum(abs(e) for e in u or ()))
-    if B >= 1 << 31:
-        raise ValueError(f"the linear form can reach {B} in magnitude: |bias| + (2^{8 * esz} - 1) sum(|w| + |u|) must stay below 2^31, "
-                         "or the 32-bit sum wraps")
+    linear_bound(w, u, bias, esz)
     as_t = lambda vals: torch.from_numpy(np.array(vals, np.int32)).to(device)      # noqa: E731
     return as_t(w), None if u is None else as_t(u), bias, lo, hi
+
+
+DERIVE_MAX_FORMS = 16
+
+
+def derive_forms(forms, lag_forms, bias, ndims, esz, device):
+    """derive_rows' arguments -> (w, u, bias): w and u contiguous int32 tensors [K, ndims] on `device` (u None where lag_forms is None: no lag
+    term) and bias an int32 tensor [K].  forms / lag_forms: an integer tensor [K, ndims], or a sequence of K entries, each as filter_linear takes
+    its weights -- a scalar (every column), a sequence of ndims entries, a dict {column: weight} or a tensor of ndims integers.  bias: a scalar
+    (every form) or K entries.  1 <= K <= 16, and lag_forms, where given, has K entries too.  Every form is held to linear_terms' bound
+    (linear_bound): one that can reach 2^31 in magnitude is refused, by its number."""
+    def rows(v, name):
+        if torch.is_tensor(v):
+            if v.dim() != 2 or v.shape[1] != ndims or v.dtype.is_floating_point or v.dtype == torch.bool:
+                raise ValueError(f"{name} must be an integer tensor [K, {ndims}]")
+            return [[int(e) for e in r] for r in v.cpu().tolist()]
+        if isinstance(v, dict) or np.isscalar(v):
+            raise ValueError(f"{name} must be a sequence of forms (K entries), not one form")
+        return [_weights(f, ndims, f"{name}[{k}]") for k, f in enumerate(v)]
+    w = rows(forms, "forms")
+    K = len(w)
+    if not 1 <= K <= DERIVE_MAX_FORMS:
+        raise ValueError(f"derive_rows takes 1 .. {DERIVE_MAX_FORMS} forms, not {K}")
+    u = None if lag_forms is None else rows(lag_forms, "lag_forms")
+    if u is not None and len(u) != K:
+        raise ValueError(f"lag_forms must have as many entries as forms ({K}), not {len(u)}")
+    b = [int(e) for e in _entries(bias, K, "bias")]
+    for k in range(K):
+        linear_bound(w[k], None if u is None else u[k], b[k], esz, f"form {k}")
+    as_t = lambda vals: torch.from_numpy(np.array(vals, np.int32).reshape(K, -1)).to(device)      # noqa: E731
+    return as_t(w), None if u is None else as_t(u), as_t(b).reshape(K)
 
 
 ZONE_NONE, ZONE_ALL, ZONE_DECODE = 0, 1, 2
