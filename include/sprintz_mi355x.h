@@ -55,7 +55,7 @@ extern "C" {
  *      extrema_rows, SPRINTZ_EXT_*; filter_linear / filter_linear_tmp_bytes; segment_rows / segment_count, SPRINTZ_SEG_*;
  *      float_rows, SPRINTZ_FLOAT_*; compress_batch_float / compress_batch_float_dense, SPRINTZ_QUANT_FLOOR;
  *      rolling_rows, SPRINTZ_ROLL_*; project_rows, SPRINTZ_PROJECT_*; cumulative_rows / cumulative_tmp_bytes, SPRINTZ_CUM_*;
- *      derive_rows / derive_rows_tmp_bytes, SPRINTZ_DERIVE_* */
+ *      derive_rows / derive_rows_tmp_bytes, SPRINTZ_DERIVE_*; fir_rows / fir_rows_tmp_bytes */
 #define SPRINTZ_MI355X_ABI_VERSION 7
 
 /* codec ids */
@@ -1147,6 +1147,51 @@ int sprintz_mi355x_derive_rows(int codec, int elem_bytes, const void* d_comp, co
                                const float* d_scale, const float* d_offset,   /* [nforms], float formats only */
                                const void* d_prev,            /* [ndims] element type, or NULL */
                                uint32_t flags, void* d_tmp, void* d_out, int64_t* d_rets, void* hip_stream);
+/* FIR rows: a per-column tap filter over the rows -- a weighted history of every column, straight from the compressed batch; the decoded tensor never
+ * exists.  Where sprintz_mi355x_rolling_rows looks back W rows with weights of one and sprintz_mi355x_derive_rows weighs the one row in front, this
+ * takes ntaps integer weights a column: a smoothing filter (binomial, triangular taps), the k-row difference x[g] - x[g - k] (pandas' diff(periods=k)),
+ * shift(k), a second difference, a band-pass or differentiator kernel, a matched filter against a short template.  The batch is given as to
+ * sprintz_mi355x_rolling_rows (chunk_len % ndims == 0; the RLE codecs; at most 512 columns; a short last chunk may end mid-row).  The batch's rows are
+ * g = 0 .. G - 1, row g being row g % R of chunk g / R, R = chunk_len / ndims.  For T = ntaps, 1 <= T <= 256 with T - 1 <= R, and every element that
+ * exists, in row g and column d:
+ *   y[g, d] = d_bias[d] + sum_{j = 0 .. T - 1} d_taps[j][d] x[g - j, d]          modulo 2^32, read as an int32
+ * with x the unsigned sample; d_taps[0] weighs the row itself.  Rows in front of row 0 come from d_prev: [T - 1][ndims] of the element type, the last
+ * rows of the batch before this one, its last row being row -1 -- a stream continued over batches then filters exactly.  d_prev == NULL: rows in front
+ * of row 0 equal row 0 (edge replication: derive_rows' "row 0 is its own predecessor"; a smoothing filter has no start-up transient).  The zero
+ * initial state of scipy.signal.lfilter is a d_prev of zeros.  y is exact wherever |bias[d]| + sum_j |taps[j][d]| (2^(8 elem_bytes) - 1) < 2^31 (the
+ * bound the Python layer refuses by); beyond it the value is the wrapped one.
+ * Output: every element at its own place, element e of chunk c at d_out[c * chunk_len + e], as rolling_rows places its results -- for whole-row
+ * batches a dense [G, ndims] view; elements that do not exist are not written.
+ *   format   : SPRINTZ_DERIVE_I32: the int32 y; SPRINTZ_DERIVE_F32 / _F16 / _BF16: fl32(fl32((float)y * d_scale[d]) + d_offset[d]), converted and
+ *              rounded exactly as derive_rows converts: bit for bit torch's CPU (y.to(float32) * scale + offset).to(dtype)
+ *   d_scale, d_offset : float32 [ndims], or NULL: all 1 / all 0; with a float format only
+ *   flags    : SPRINTZ_QUERY_GENERAL_LAYOUT and nothing else
+ *   d_tmp    : with ntaps > 1, scratch of sprintz_mi355x_fir_rows_tmp_bytes(elem_bytes, nchunks, ndims, ntaps) bytes, 16-byte aligned: per chunk a
+ *              16-byte head (the elements the chunk decoded to; 0: damaged), its first T - 1 raw rows, then its last T - 1 raw rows, the stride
+ *              rounded up to 16 (fir_tmp_stride in geom.h).  Its content before the call does not matter.  ntaps == 1: no scratch, no second launch,
+ *              and d_prev is ignored.
+ *   d_rets   : (optional) exactly what sprintz_mi355x_decompress_batch writes for the same batch, damaged chunks included
+ * A chunk's last Wh + 8 raw rows, Wh = T - 1 rounded up to a multiple of 8, wait in LDS (rolling_rows' ring): where the rings of the chunks a
+ * workgroup decodes do not fit its 160 KB, the call returns SPRINTZ_E_UNSUPPORTED and sprintz_mi355x_last_error names the largest ntaps the shape takes.
+ * A damaged chunk (d_rets < 0): its own rows are unspecified, and so are the first T - 1 rows of the chunk behind it; every other row is exact, and
+ * nothing outside the batch's chunk slots or outside the scratch is written.
+ * Two launches on the stream -- the decode (SPRINTZ_KF_DEC_FAST for rows of whole 16-byte pieces of 8 .. 64 columns with a 16-byte aligned d_out, while
+ * rings and taps fit its LDS budget; SPRINTZ_KF_DEC_GENERIC otherwise), in which rows in front of a chunk's first contribute nothing, and with ntaps > 1
+ * a seam pass that computes the first T - 1 rows of every chunk again from raw rows -- no synchronisation, no allocation.  nchunks == 0 returns 0 and
+ * launches nothing.
+ * Returns, before the device is touched: SPRINTZ_E_INVALID for a NULL d_comp / d_offsets / d_taps / d_out, ntaps outside 1..256, ntaps - 1 >
+ * chunk_len / ndims, chunk_len % ndims != 0, chunk_len outside 1..2^30, an unknown format or flag, d_scale / d_offset with SPRINTZ_DERIVE_I32, d_out not
+ * aligned to the output element, d_taps / d_bias / d_scale / d_offset not aligned to 4, d_prev to the element size, d_rets to 8, d_tmp NULL or not
+ * aligned to 16 with ntaps > 1; SPRINTZ_E_UNSUPPORTED for more than 512 columns, the non-RLE codecs and a history beyond the LDS bound. */
+uint64_t sprintz_mi355x_fir_rows_tmp_bytes(int elem_bytes, uint64_t nchunks, uint16_t ndims, uint32_t ntaps);
+int sprintz_mi355x_fir_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                            uint32_t chunk_len, uint16_t ndims, uint32_t ntaps,
+                            const int32_t* d_taps,   /* [ntaps][ndims] */
+                            const int32_t* d_bias,   /* [ndims] or NULL: all 0 */
+                            int format,              /* SPRINTZ_DERIVE_I32 / _F32 / _F16 / _BF16 */
+                            const float* d_scale, const float* d_offset,   /* [ndims], float formats only */
+                            const void* d_prev,      /* [ntaps - 1][ndims] element type, or NULL */
+                            uint32_t flags, void* d_tmp, void* d_out, int64_t* d_rets, void* hip_stream);
 /* single-call forms over host buffers; result: ndims uint64 (may be NULL);
  * return value as decompress (elements), < 0 on error */
 int64_t sprintz_mi355x_query_delta_8b(const int8_t* src, uint8_t* dest, int op, int materialize, uint32_t flags, uint64_t* result);

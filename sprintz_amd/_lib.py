@@ -196,6 +196,10 @@ DERIVE_I32, DERIVE_F32, DERIVE_F16, DERIVE_BF16 = 0, 1, 2, 3
 DERIVE_MAX_FORMS = 16
 derive_rows_tmp_bytes = _sig("sprintz_mi355x_derive_rows_tmp_bytes", _u64, _i, _u64, _u16)
 derive_rows = _sig("sprintz_mi355x_derive_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _u32, _vp, _vp, _vp, _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp)
+# FIR rows: per element bias[d] + sum_j taps[j][d] x[g - j, d] over the ntaps rows that end at its row, as int32 or as derive rows convert (include/sprintz_mi355x.h)
+FIR_MAX_TAPS = 256
+fir_rows_tmp_bytes = _sig("sprintz_mi355x_fir_rows_tmp_bytes", _u64, _i, _u64, _u16, _u32)
+fir_rows = _sig("sprintz_mi355x_fir_rows", _i, _i, _i, _vp, _vp, _u64, _u32, _u16, _u32, _vp, _vp, _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp)
 # compress floats: compress_batch / compress_batch_dense on a float source the encoder quantises while it loads
 QUANT_FLOOR = 4
 compress_batch_float = _sig("sprintz_mi355x_compress_batch_float", _i, _i, _i, _vp, _i, _vp, _vp, _u32, _u64, _u32, _u16, _vp, _sz, _vp, _vp, _vp)
@@ -277,6 +281,7 @@ EXPORTED_SYMBOLS = [
     "sprintz_mi355x_float_rows", "sprintz_mi355x_compress_batch_float", "sprintz_mi355x_compress_batch_float_dense",
     "sprintz_mi355x_rolling_rows", "sprintz_mi355x_project_rows", "sprintz_mi355x_cumulative_tmp_bytes", "sprintz_mi355x_cumulative_rows",
     "sprintz_mi355x_derive_rows_tmp_bytes", "sprintz_mi355x_derive_rows",
+    "sprintz_mi355x_fir_rows_tmp_bytes", "sprintz_mi355x_fir_rows",
     "sprintz_mi355x_query_delta_8b", "sprintz_mi355x_query_xff_8b",
     "sprintz_mi355x_query_delta_16b", "sprintz_mi355x_query_xff_16b",
     "sprintz_mi355x_compress_batch_colmajor", "sprintz_mi355x_compress_batch_colmajor_dense", "sprintz_mi355x_decompress_batch_colmajor",

@@ -897,6 +897,119 @@ class ChunkedCodec:
                 raise ValueError(f"diff_rows builds {name} itself")
         return self.derive_rows(batch, [{int(c): 1} for c in cols], lag_forms=[{int(c): -1} for c in cols], **kw)
 
+    def fir_rows(self, batch, taps, bias=0, dtype=None, scale=None, offset=None, prev=None, return_tail=False, out=None, rets=None,
+                 general_layout=False, check=True):
+        """A per-column tap filter over the rows -- a weighted history of every column -- straight from the compressed batch; the decoded tensor
+        never exists.  For batch row g (row g % R of chunk g // R, R = chunk_len / ndims: chunk_len must be a multiple of ndims) and column d
+
+            out[g, d] = bias[d] + sum_{j = 0 .. T - 1} taps[j][d] x[g - j, d]
+
+        with x the unsigned samples as integers; taps[0] weighs the row itself.  taps: T integers shared by all columns, or [T, ndims] (a
+        sequence or an integer tensor); 1 <= T <= 256 and T - 1 <= R.  bias: a scalar or ndims entries.  Every column's filter is exact: one
+        that could reach 2^31 in magnitude is a ValueError (rowops.fir_taps).  Rows in front of row 0 come from prev -- [T - 1, ndims], the last
+        rows of the batch before this one, its last row being row -1 -- so that a stream continued over batches filters exactly; without prev
+        they equal row 0 (edge replication: a smoothing filter has no start-up transient).  scipy.signal.lfilter's zero initial state is a prev
+        of zeros.
+
+            smooth = codec.fir_rows(batch, [1, 2, 1], dtype=torch.float32, scale=0.25)        # binomial smoothing
+            season = codec.fir_rows(batch, [1] + [0] * 23 + [-1])                             # x[g] - x[g - 24]: diff(periods=24)
+            second = codec.fir_rows(batch, [1, -2, 1])                                        # second difference
+
+        dtype: None or torch.int32 for the sums themselves, or torch.float32 / torch.float16 / torch.bfloat16 for
+        (y.to(float32) * scale[d] + offset[d]).to(dtype), bit for bit what torch computes on the CPU; scale / offset: float_rows' forms, a float
+        dtype only.
+        -> a [G, ndims] tensor, G = total_len / ndims; of a batch that ends mid-row the flat view of its total_len elements, as rolling_rows
+        places them.  return_tail=True: -> (result, tail), tail the batch's last T - 1 raw rows [T - 1, ndims] (read_rows; completed from prev,
+        or by row 0, where the batch is shorter): the prev of the next batch.  out: a contiguous tensor of the output dtype with at least
+        nchunks x chunk_len elements to write into; rets: an int64 tensor of nchunks entries for the per-chunk element counts.  One library
+        call: the decode and, with more than one tap, its seam pass.  A damaged chunk's rows are unspecified, and the first T - 1 rows of the
+        chunk behind it; check=True raises SprintzError naming the first damaged chunk."""
+        torch = self.torch
+        D, n = self.ndims, batch.nchunks
+        R, _ = rowops.chunk_rows(self.chunk_len, D, "fir_rows")
+        t, b = rowops.fir_taps(taps, bias, D, self.esz, self.device)
+        T = int(t.shape[0])
+        if T - 1 > R:
+            raise ValueError(f"{T} taps reach {T - 1} rows back, more than the {R} rows of a chunk: a filter may reach into one chunk in front, not two")
+        if dtype is None or dtype == torch.int32:
+            if scale is not None or offset is not None:
+                raise ValueError("scale and offset go with a float dtype")
+            dtype, fmt = torch.int32, _lib.DERIVE_I32
+        else:
+            fmt = 1 + rowops.float_format(dtype)
+            scale = rowops.float_params(scale, D, "scale", self.device)
+            offset = rowops.float_params(offset, D, "offset", self.device)
+        if prev is not None and T > 1:
+            if not torch.is_tensor(prev):
+                prev = np.asarray(prev).reshape(-1).tolist()
+            prev = rowops.elem_tensor(prev, (T - 1) * D, self.esz, self.dtype, self.device, "prev").view(T - 1, D)
+        else:
+            prev = None
+        if out is None:
+            out = torch.empty(max(n * self.chunk_len, 1), dtype=dtype, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != dtype or out.device != self.device or out.numel() < n * self.chunk_len or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor of at least {n} x {self.chunk_len} elements on {self.device}")
+        if rets is None:
+            rets = self._rets(n, check)
+        tmp = torch.empty(max(rowops.fir_tmp_bytes(n, T, D, self.esz) // 16, 1) * 2, dtype=torch.int64, device=self.device) if T > 1 else None
+        if n:
+            with self._on():
+                _lib.check(_lib.fir_rows(_CODEC_ID[self.codec], self.esz, batch.data.data_ptr(), batch.offsets.data_ptr(), n, self.chunk_len, D, T,
+                                         t.data_ptr(), b.data_ptr(), fmt, _ptr(scale), _ptr(offset), _ptr(prev), self._general(general_layout),
+                                         _ptr(tmp), out.data_ptr(), _ptr(rets), self._stream()))
+            if check:
+                rowops.raise_damaged("fir_rows", rets, n, _lib.SprintzError)
+        res = out.view(-1)[: batch.total_len]
+        res = res.view(-1, D) if batch.total_len % D == 0 else res
+        if not return_tail:
+            return res
+        G = batch.total_len // D
+        have = min(G, T - 1)
+        tail = self.read_rows(batch, G - have, G) if have else torch.empty((0, D), dtype=self.dtype, device=self.device)
+        if have < T - 1:
+            if prev is not None:
+                front = prev[have:]
+            elif G:
+                front = self.read_rows(batch, 0, 1).expand(T - 1 - have, D)
+            else:
+                raise ValueError("return_tail of a batch without a row needs prev")
+            sv = torch.int8 if self.esz == 1 else torch.int16                   # (through the signed type of the same width, as elem_tensor goes)
+            tail = torch.cat([front.view(sv), tail.view(sv)]).view(self.dtype).contiguous()
+        return res, tail
+
+    def _fir_own_taps(self, name, kw):
+        if "taps" in kw:
+            raise ValueError(f"{name} builds taps itself")
+
+    def shift_rows(self, batch, k, **kw):
+        """pandas' shift(k) with the edge replicated: out[g, d] = x[g - k, d] as int32 (fir_rows with a unit tap at lag k; the first k rows hold
+        row 0, or the rows prev gives).  Every other argument is fir_rows'."""
+        self._fir_own_taps("shift_rows", kw)
+        return self.fir_rows(batch, rowops.shift_taps(k), **kw)
+
+    def lag_diff_rows(self, batch, periods=1, **kw):
+        """pandas' diff(periods): out[g, d] = x[g, d] - x[g - periods, d] as int32, the seasonal difference (fir_rows with +1 at lag 0 and -1 at
+        lag periods; the first `periods` rows change against row 0, or against the rows prev gives).  Every other argument is fir_rows'."""
+        self._fir_own_taps("lag_diff_rows", kw)
+        return self.fir_rows(batch, rowops.lag_diff_taps(periods), **kw)
+
+    def smooth_rows(self, batch, taps, dtype=None, **kw):
+        """A smoothing filter: fir_rows with a float dtype (float32 unless given) and scale = 1 / sum(taps), so that taps of any positive sum
+        average -- [1, 2, 1] is the binomial, [1, 2, 3, 2, 1] a triangular window.  taps: T integers shared by all columns.  Every other argument
+        is fir_rows'; scale is this wrapper's."""
+        if "scale" in kw:
+            raise ValueError("smooth_rows builds scale itself")
+        dtype = self.torch.float32 if dtype is None else dtype
+        if dtype == self.torch.int32:
+            raise ValueError("smooth_rows needs a float dtype")
+        vals = taps.tolist() if self.torch.is_tensor(taps) or isinstance(taps, np.ndarray) else taps
+        if np.isscalar(vals) or isinstance(vals, dict) or vals is None or not all(np.isscalar(e) for e in vals):
+            raise ValueError("smooth_rows takes 1-D taps, T integers shared by all columns: per-column taps have no one sum to scale by (use fir_rows with scale)")
+        total = sum(int(e) for e in vals)
+        if total <= 0:
+            raise ValueError(f"smooth_rows needs taps of a positive sum, not {total}")
+        return self.fir_rows(batch, taps, dtype=dtype, scale=1.0 / total, **kw)
+
     def cumulative_rows(self, batch, ops=("min", "max", "sum"), sum_dtype=None, carry=None, return_carry=False, general_layout=False, check=True):
         """Running min / max / sum / mean of every column from the first row on, one result per row -- cummin, cummax, cumsum and pandas'
         expanding().mean() -- straight from the compressed batch: the decoded tensor never exists.  Batch row g is row g % R of chunk g // R,

@@ -303,15 +303,15 @@ const DecodeUnit kDecodeUnits[][2] = {SPRINTZ_WIDTH_UNITS, SPRINTZ_WIDTH_UNITS, 
                                       SPRINTZ_ROW_OP_UNITS(SPRINTZ_ROW_OP_UNIT_ROW)};
 #undef SPRINTZ_ROW_OP_UNIT_ROW
 #undef SPRINTZ_WIDTH_UNITS
-static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryDerive + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
+static_assert(sizeof(kDecodeUnits) / sizeof(kDecodeUnits[0]) == kQueryFir + 1 && kQueryGather == 4, "a row of units per kQuery* mode");
 hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryDerive) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryFir) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].generic(w, fire, lowdim, cpl, q, grid, shmem, st, a);
 }
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)
 {
-    if (q < 0 || q > kQueryDerive) return hipErrorInvalidValue;
+    if (q < 0 || q > kQueryFir) return hipErrorInvalidValue;
     return kDecodeUnits[q][w == 16].fast(w, fire, dp, cpl, exact, q, ds, grid, shmem, st, a);
 }
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a)
@@ -404,6 +404,10 @@ Shape decode_shape(const Batch& b, const void* d_out, const QuerySpec& qs)
     }
     if (qs.q == kQueryDerive) {                             // the forms of the output and the bytes of one of its elements
         s.rows = qs.filter.mask_stride;
+        s.out_esz = derive_out_bytes(qs.filter.mode);
+    }
+    if (qs.q == kQueryFir) {                                // the taps (win.rows carries the history's rows, for the ring) and the bytes of an output element
+        s.rows = qs.win.count;
         s.out_esz = derive_out_bytes(qs.filter.mode);
     }
     return s;

@@ -207,6 +207,13 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     // for 8 K OSZ bytes where that is more than the decoded block (plan.h).
     constexpr bool DER = Q == kQueryDerive;
     static_assert(!DER || (!CM && !SPLIT && DS == 0 && CPL == 1), "derive rows: row-major destination, one column a lane");
+    // FIR (sprintz_mi355x_fir_rows): nothing of the raw block is stored.  A column's 8 rows wait in arow for q_block, which runs the filter step on the
+    // chunk's history ring -- rolling rows' ring, behind the groups' carves at a.table.table_off -- with the column's taps from the workgroup's table in
+    // LDS ([T][D] int32 behind the rings, filled once at the kernel's start), converts where a float format is asked and keeps the block's 8 results in
+    // registers (rres); behind the columns fir_out sends them through the plain decode's staging AS OUTPUT ELEMENTS, in output order, 8 ESZ / OSZ rows
+    // of the block at a pass, and out as 16-byte pieces, as cumulative rows' sums leave.  The pieces are stored at once.
+    constexpr bool FIR = Q == kQueryFir;
+    static_assert(!FIR || (!CM && !SPLIT && DS == 0 && CPL == 1), "FIR rows: row-major destination, one column a lane");
     // the modes that take the rows a mask names (decode_ops.h: RowMaskArgs); all but select, aggregate and segments take a null mask for "every row"
     constexpr bool MASKED = SELECT || AGG || HIST || MOM || GBY || EXT || SEG;
     constexpr bool MASK_GIVEN = SELECT || AGG || SEG;      // (no test for a null mask where there always is one: select measured 1 % slower with it)
@@ -255,6 +262,12 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         for (uint32_t i = threadIdx.x; i < n; i += kThreads) wt[i] = make_uint2((uint32_t)a.lin.w[i], a.lin.lag ? (uint32_t)a.lin.lag[i] : 0u);
         __syncthreads();
     }
+    if constexpr (FIR) {                                   // the workgroup's table of taps, every lane of it, before any leaves
+        uint32_t* const tt = (uint32_t*)(smem + a.table.table_off + (size_t)(kThreads >> LOG2DP) * (size_t)roll_ring_bytes(a.win.rows, D, ESZ));
+        const uint32_t n = fir_ntaps(a) * (uint32_t)D;
+        for (uint32_t i = threadIdx.x; i < n; i += kThreads) tt[i] = (uint32_t)a.lin.w[i];
+        __syncthreads();
+    }
     if constexpr (!HIST && !GBY) {
         if (c_first >= a.nchunks) return;
     }                                                      // (histogram, group-by: c_end <= c_first below, and the chunk loop does not run)
@@ -266,7 +279,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     uint8_t* const stage = ringp + RB + APRON;
     // rolling rows: the chunk's history ring (decode_ops.h: rolling_ring), a ring a group behind every group's carve
     uint8_t* rollp = nullptr;
-    if constexpr (ROLL) rollp = smem + a.table.table_off + (size_t)(threadIdx.x >> LOG2DP) * (size_t)roll_ring_bytes(a.win.rows, D, ESZ);
+    if constexpr (ROLL || FIR) rollp = smem + a.table.table_off + (size_t)(threadIdx.x >> LOG2DP) * (size_t)roll_ring_bytes(a.win.rows, D, ESZ);
 
     // stream geometry.  All stream loads go through ONE wave-uniform buffer
     // descriptor that spans the container from this wavefront's first stream to its
@@ -520,6 +533,16 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
 #pragma unroll
         for (int k = 0; k < CPL; k++) rsum[k] = 0;
     }
+    // FIR rows: the lane's column's taps in the workgroup's table, its bias, scale and offset (loaded once), and the format
+    const uint32_t* firt = nullptr;
+    uint32_t firb = 0, firmode = 0;
+    float firsc = 1.0f, firof = 0.0f;
+    if constexpr (FIR) {
+        firt = (const uint32_t*)(smem + a.table.table_off + (size_t)(kThreads >> LOG2DP) * (size_t)roll_ring_bytes(a.win.rows, D, ESZ)) + colk[0];
+        firmode = a.filter.mode;
+        firb = fir_bias(a, (uint32_t)colk[0]);
+        if (!(firmode & kDeriveI32Bit)) { firsc = float_scale(a, (uint32_t)colk[0]); firof = float_offset(a, (uint32_t)colk[0]); }
+    }
     // cumulative rows: each column's running min / max / sum (set at each chunk start)
     CumState cums[CUM ? CPL : 1];
     // derive rows: the row in front of the block being decoded (clean), no row of the chunk is done, and the bytes of a derived block
@@ -529,7 +552,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
     auto q_row = [&](int k, int i) {                       // pv[k] carries garbage above bit W: the queries select the element
         if constexpr (Q == kQueryFilter) {                 // with SDWA, the filter with the mask of its difference (plain C++)
             fcm |= filter_hit<W>(fc[k], pv[k]) << i;
-        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL || CUM || DER) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
+        } else if constexpr (AGG || HIST || EXT || LIN || SEG || ROLL || CUM || DER || FIR) {  // the column's 8 rows wait for q_block: one test of the mask byte a column
             arow[i] = pv[k];
         } else if constexpr (MOM || GBY) {                 // every slot's rows wait for q_window: the reference / key column's may come last
             mrow[k][i] = pv[k];
@@ -595,6 +618,17 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                         rres[op == kCumMin ? 0 : CUM ? 1 : 0][k][j] = (uint32_t)v;
                     }
                 });
+        } else if constexpr (FIR) {                        // (a lane column past the last one has no ring and no results; the chunk's first T - 1 rows leave for the seam pass)
+            if (col_ok[k])
+                fir_step8<W>(a, rolling_ring<W>(rollp, a, (uint32_t)genk[k]), rblk, [&](int i) { return arow[i]; }, [&](uint32_t j) { return firt[j * (uint32_t)D]; }, firb,
+                             (a.lin.tmp && 8u * rblk + 1u < fir_ntaps(a)) ? fir_slot<W>(a, lchunk).first + genk[k] : nullptr, (uint32_t)D, [&](int j, uint32_t y) {
+                                 if (firmode & kDeriveI32Bit) {
+                                     rres[0][0][j] = y;
+                                 } else {
+                                     const float z = derive_value(y, firsc, firof);
+                                     rres[0][0][j] = (firmode & 3u) == kFloatF32 ? __float_as_uint(z) : (firmode & 3u) == kFloatF16 ? float_to_f16(z) : float_to_bf16(z);
+                                 }
+                             });
         } else if constexpr (DER) {                        // (the chunk's first row leaves for the seam pass; the block's values leave in der_out)
             if (a.lin.lag && dfirst && col_ok[k]) linear_slot<W>(a, lchunk, (uint32_t)D).first[genk[k]] = (U)arow[0];
         } else if constexpr (MOM || GBY) {
@@ -1044,6 +1078,45 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
             dfirst = 0;
         }
     };
+    // FIR rows: the block's 8 results a column leave (see FIR above): OB bytes each, NP = OB / ESZ times the block's bytes, 8 / NP rows of the block at a
+    // pass -- a pass fills exactly the block's staging, and its 16-byte pieces lie in the output as they lie in LDS
+    auto fir_store = [&](auto ob) __attribute__((always_inline)) {
+        if constexpr (FIR) {
+            constexpr int OB = decltype(ob)::value;
+            constexpr int NP = OB / ESZ, RPP = 8 / NP;     // passes a block, rows a pass
+            constexpr uint32_t cfs = NP == 1 ? 0u : NP == 2 ? 1u : 2u;      // element bytes -> output bytes, as a shift
+            const uint32_t fspan = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((out_span << cfs) < 0xfffffff0ull ? (out_span << cfs) : 0xfffffff0ull));
+            const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void*)((uint8_t*)a.out + wave_uniform64(out_base << cfs)), 0, fspan, 0x00020000);
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                wave_lds_sync();                           // (the pieces of the pass before have been read)
+                if (col_ok[0]) {
+#pragma unroll
+                    for (int r = 0; r < RPP; r++) {
+                        uint8_t* const at = stage + (uint32_t)r * (uint32_t)D * OB + (uint32_t)genk[0] * OB;
+                        if constexpr (OB == 4) *(uint32_t*)at = rres[0][0][p * RPP + r];
+                        else *(uint16_t*)at = (uint16_t)rres[0][0][p * RPP + r];
+                    }
+                }
+                wave_lds_sync();
+#pragma unroll
+                for (int q = 0; q < PIECES; q++) {
+                    const uint32_t u = lane16 + q * ROW16;
+                    const bool in = u < blk_bytes;
+                    const uint4 t = *(const uint4*)(stage + (in ? u : 0u));
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), frs, in ? (ovo << cfs) + (uint32_t)p * blk_bytes + u : kDropStore, 0, kStoreAux);
+                }
+            }
+        }
+    };
+    auto fir_out = [&]() __attribute__((always_inline)) {
+        if constexpr (FIR) {
+            if ((firmode & kDeriveI32Bit) || (firmode & 3u) == kFloatF32) fir_store(std::integral_constant<int, 4>{});      // (wave-uniform: the format is the call's)
+            else fir_store(std::integral_constant<int, 2>{});
+            ovo += blk_bytes;
+            rblk++;
+        }
+    };
     auto stage_out = [&](int slot) {
         if constexpr (query_reduce_only(Q)) return;
         if constexpr (ROLL) { roll_out(slot < 0); return; }
@@ -1348,7 +1421,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     q_row(k, i);
                     pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM && !DER)
+                    if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM && !DER && !FIR)
                         if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];
 #endif
                 }
@@ -1383,6 +1456,8 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 cum_out();
             } else if constexpr (DER) {                    // (called here too, for the same reason)
                 der_out();
+            } else if constexpr (FIR) {
+                fir_out();
             } else {
                 stage_out(-1);
             }
@@ -1483,7 +1558,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                 q_row(k, i);
                 pack_row(k, i);
 #ifndef SPRINTZ_ABL_NO_STAGE
-                if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM && !DER)
+                if constexpr (!query_reduce_only(Q) && !CM && !ROLL && !CUM && !DER && !FIR)
                     if (!SELECT || sm != 0) *(U*)(stage_k[k] + i * (PROJ ? prs : row_stride)) = (U)pv[k];   // (a block whose mask byte is 0 is not staged)
 #else
                 asm volatile("" :: "v"(pv[k]));
@@ -1516,7 +1591,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         }
         q_window();
         f_block();
-        if constexpr (CUM) cum_out(); else if constexpr (DER) der_out(); else stage_out(slot);
+        if constexpr (CUM) cum_out(); else if constexpr (DER) der_out(); else if constexpr (FIR) fir_out(); else stage_out(slot);
         s_block();
         if constexpr (GATHER) grow += 8u;
     };
@@ -1624,6 +1699,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         if constexpr (CUM) {                               // the running values enter the chunk as the scan left them
 #pragma unroll
             for (int k = 0; k < CPL; k++) cums[CUM ? k : 0] = col_ok[k] ? cumulative_enter<W>(a, chunk, (uint32_t)D, (uint32_t)genk[k]) : CumState{MASK, 0u, 0ull};
+        }
+        if constexpr (FIR) {                               // the ring restarts cold with every chunk: no slot is read before this chunk wrote it
+            rblk = 0;
+            lchunk = chunk;
         }
         if constexpr (DER) {                               // the chunk's first row is its own predecessor inside the launch
             dfirst = 1;
@@ -1766,7 +1845,7 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
                     for (int q = 0; q < PIECES; q++)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, held[s2][q]), orsrc, held_vo[s2][q], 0, kStoreAux);
             }
-        } else if constexpr (!query_reduce_only(Q) && !ROLL && !CUM && !DER) {
+        } else if constexpr (!query_reduce_only(Q) && !ROLL && !CUM && !DER && !FIR) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -1877,6 +1956,10 @@ __global__ void __launch_bounds__(kThreads) decode_fast_kernel(DecodeArgs a)
         // the tail walks row by row at plain 64-bit addresses, then the chunk leaves its count and last rows for the seam pass (decode_ops.h)
         if (!corrupt) rolling_tail<W, CPL>(a, chunk, rollp, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, rsum);
         rolling_leave<W, CPL>(a, chunk, rollp, corrupt ? 0u : out_elems + remaining, (uint32_t)D, genk, col_ok, lane_d);
+    } else if constexpr (FIR) {
+        // the tail walks row by row at plain 64-bit addresses, taps from global memory, then the chunk leaves its count and last rows for the seam pass
+        if (!corrupt) fir_tail<W, CPL>(a, chunk, rollp, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok);
+        fir_leave<W, CPL>(a, chunk, rollp, corrupt ? 0u : out_elems + remaining, (uint32_t)D, genk, col_ok, lane_d);
     } else if constexpr (CUM) {
         // the tail walks row by row at plain 64-bit addresses; in a call of one chunk the state behind it is the call's carry_out (decode_ops.h)
         if (!corrupt) cumulative_tail<W, CPL>(a, chunk, a.comp + gabs + rp, out_elems, remaining, (uint32_t)D, genk, col_ok, cums);

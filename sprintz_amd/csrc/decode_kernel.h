@@ -49,6 +49,9 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     // DER (sprintz_mi355x_derive_rows): K linear forms of every row and the row in front of it leave as a dense [rows, K] output, a form at a time
     // (decode_ops.h: derive_rows8); nothing of the decoded block is stored or staged, runs are replayed block by block
     constexpr bool DER = Q == kQueryDerive;
+    // FIR (sprintz_mi355x_fir_rows): every sample leaves as its column's tap filter over the T rows that end at its row, as int32 or converted; the group's
+    // LDS is the chunk's history ring (decode_ops.h: fir_rows8), taps come from global memory, runs are replayed block by block
+    constexpr bool FIR = Q == kQueryFir;
     constexpr bool MASKED = Q == kQuerySelect || Q == kQueryAggregate || HIST || MOM || GBY || EXT || SEG;
     constexpr bool COUNTED = Q == kQueryAggregate || MOM || EXT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -106,6 +109,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             if constexpr (LIN || DER) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
+            if constexpr (FIR) fir_mark<W>(a, chunk, lane_d);
             if constexpr (CUM) cumulative_mark(a, chunk, (uint32_t)D, lane_d, DP, W);
             if constexpr (TAB) hbad = true; else return;
         }
@@ -122,6 +126,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
             else if (lane_d == 0 && a.rets) a.rets[chunk] = kErrCorrupt;
             if constexpr (LIN || DER) linear_mark(a, chunk, (uint32_t)D, W, 0u, lane_d);
             if constexpr (ROLL) rolling_mark<W>(a, chunk, lane_d);
+            if constexpr (FIR) fir_mark<W>(a, chunk, lane_d);
             if constexpr (CUM) cumulative_mark(a, chunk, (uint32_t)D, lane_d, DP, W);
             if constexpr (TAB) hbad = true; else return;
         }
@@ -472,6 +477,10 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
                     rolling_rows8<W>(a, rolling_ring<W>(lds + a.table.table_off, a, (uint32_t)colk[k]), out_elems / blk_elems, [&](int i) { return v[i][k]; }, rsum[k],
                                      chunk * (uint64_t)a.chunk_len + out_elems + (uint64_t)colk[k], (uint32_t)D,
                                      !FIRE && SPRINTZ_ROLL_RUN_SHORTCUT && run_block && rolling_run_settled(a, rrun));
+            } else if constexpr (FIR) {          // (a.table.table_off is 0 in this kernel's launch)
+                if (genk[k])
+                    fir_rows8<W>(a, chunk, rolling_ring<W>(lds + a.table.table_off, a, (uint32_t)colk[k]), out_elems / blk_elems, [&](int i) { return v[i][k]; },
+                                 chunk * (uint64_t)a.chunk_len + out_elems + (uint64_t)colk[k], (uint32_t)D, (uint32_t)colk[k]);
             } else if constexpr (CUM) {
                 if (genk[k])
                     cumulative_rows8<W>(a, [&](int i) { return v[i][k]; }, cst[k], chunk * (uint64_t)a.chunk_len + out_elems + (uint64_t)colk[k], (uint32_t)D);
@@ -561,7 +570,7 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
 
         // ---- store the 8 x D block (contiguous 8*D*ESZ bytes of the output)
         U* const ob = o + out_elems;
-        if constexpr (query_reduce_only(Q) || ROLL || CUM || DER) {       // (derive rows: the block's values left above; rolling rows: the block's results left from the column loop, the raw rows went to the ring; cumulative rows: likewise, no ring)
+        if constexpr (query_reduce_only(Q) || ROLL || CUM || DER || FIR) {       // (FIR rows: as rolling rows; derive rows: the block's values left above; rolling rows: the block's results left from the column loop, the raw rows went to the ring; cumulative rows: likewise, no ring)
             (void)ob;
         } else if constexpr (Q == kQueryGather) {
             // rows [lo, hi) of the chunk alone, each at its place in the range; the parse stops after row hi - 1
@@ -738,6 +747,12 @@ __global__ void __launch_bounds__(kThreads) decode_kernel(DecodeArgs a)
     if constexpr (ROLL) {
         if (!corrupt) rolling_tail<W, CPL>(a, chunk, lds + a.table.table_off, s + pos, out_elems, remaining, (uint32_t)D, colk, genk, rsum);
         rolling_leave<W, CPL>(a, chunk, lds + a.table.table_off, corrupt ? 0u : out_elems + remaining, (uint32_t)D, colk, genk, lane_d);
+        if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
+        return;
+    }
+    if constexpr (FIR) {
+        if (!corrupt) fir_tail<W, CPL>(a, chunk, lds + a.table.table_off, s + pos, out_elems, remaining, (uint32_t)D, colk, genk);
+        fir_leave<W, CPL>(a, chunk, lds + a.table.table_off, corrupt ? 0u : out_elems + remaining, (uint32_t)D, colk, genk, lane_d);
         if (lane_d == 0 && a.rets) a.rets[chunk] = corrupt ? kErrCorrupt : (int64_t)out_elems + remaining;
         return;
     }

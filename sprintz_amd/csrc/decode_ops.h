@@ -1806,4 +1806,185 @@ __device__ __forceinline__ void derive_tail(const DecodeArgs& a, uint64_t chunk,
     }
 }
 
+// ---- FIR rows (Q == kQueryFir; sprintz_mi355x_fir_rows): element e of chunk c, in row r = e / D and column d = e % D, leaves at place c * chunk_len + e
+// of the output as y = bias[d] + sum_{j < T} taps[j][d] x[r - j, d] (wrapping 32-bit arithmetic, the unsigned element) -- as the int32 it is or converted as
+// derive rows convert (derive_put, with the column's scale and offset) -- in place of the element itself.  Rows in front of the chunk's row 0 contribute
+// nothing inside the launch: the seam pass (decode_fir.hip) computes the first T - 1 rows of every chunk again, wholly, from the raw rows the chunks
+// leave in the scratch.  The mode has no struct of its own: T travels in WindowArgs::count and the history's rows Wh = fir_history_rows(T) in
+// WindowArgs::rows -- so that the history IS rolling rows' ring (rolling_ring, roll_ring_bytes), Wh + 8 raw rows a column -- the taps ([T][D] int32) in
+// LinearArgs::w, the biases ([D] int32, or null: all 0) in LinearArgs::lag, the scratch in LinearArgs::tmp (null: T == 1, no seam pass); the format, the
+// scale and the offset of every COLUMN in FilterArgs' mode, lo and hi and the caller's `prev` rows in FilterArgs::counts, as derive rows carry theirs; the
+// ring's place in the launch's LDS in BinTableArgs::table_off.
+__device__ __forceinline__ uint32_t fir_ntaps(const DecodeArgs& a) { return a.win.count; }
+__device__ __forceinline__ uint32_t fir_bias(const DecodeArgs& a, uint32_t d) { return a.lin.lag ? (uint32_t)a.lin.lag[d] : 0u; }
+// what chunk `chunk` leaves for the seam pass (geom.h: fir_tmp_stride): the library's own layout
+template <int W> struct FirSlot {
+    uint32_t* elems;                // the elements the chunk decoded to; 0: damaged, or empty
+    typename Elem<W>::U* first;     // [T - 1][D]: the chunk's rows 0 .. T - 2, those it has
+    typename Elem<W>::U* last;      // [T - 1][D]: rows R - (T - 1) .. R - 1 of a full chunk (elems == chunk_len), R = chunk_len / D
+};
+template <int W> __device__ __forceinline__ FirSlot<W> fir_slot(const DecodeArgs& a, uint64_t chunk)
+{
+    using U = typename Elem<W>::U;
+    uint8_t* const p = (uint8_t*)a.lin.tmp + chunk * fir_tmp_stride(fir_ntaps(a), a.D, W / 8);
+    return FirSlot<W>{(uint32_t*)p, (U*)(p + 16), (U*)(p + 16) + (size_t)(fir_ntaps(a) - 1u) * (uint32_t)a.D};
+}
+// a ring block -- 8 rows of a column, 16 bytes (uint16) or 8 (uint8), aligned to its size -- as one LDS access, whatever type the rows were written by
+template <int W> __device__ __forceinline__ void fir_block_get(const typename Elem<W>::U* b, uint32_t (&v)[8])
+{
+    if constexpr (W == 16) {
+        uint32_t w[4];
+        __builtin_memcpy(w, __builtin_assume_aligned(b, 16), 16);
+#pragma unroll
+        for (int i = 0; i < 8; i++) v[i] = (w[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+    } else {
+        uint32_t w[2];
+        __builtin_memcpy(w, __builtin_assume_aligned(b, 8), 8);
+#pragma unroll
+        for (int i = 0; i < 8; i++) v[i] = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+    }
+}
+template <int W> __device__ __forceinline__ void fir_block_set(typename Elem<W>::U* b, const uint32_t (&v)[8])
+{
+    if constexpr (W == 16) {
+        uint32_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) w[i] = v[2 * i] | (v[2 * i + 1] << 16);
+        __builtin_memcpy(__builtin_assume_aligned(b, 16), w, 16);
+    } else {
+        uint32_t w[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) w[i] = v[4 * i] | (v[4 * i + 1] << 8) | (v[4 * i + 2] << 16) | (v[4 * i + 3] << 24);
+        __builtin_memcpy(__builtin_assume_aligned(b, 8), w, 8);
+    }
+}
+// One block: the 8 new rows x(0 .. 7) of a column, block `blk` of the chunk (rows 8 blk .. 8 blk + 7).  They are written to the ring (and, with a seam
+// pass to come, those of them among the chunk's first T - 1 rows to first[r * D]: the ring will not hold them at the chunk's end); then the 8 outputs
+// are accumulated from the ring's blocks, newest to oldest.  The block m blocks back holds rows 8 (blk - m) + p; row p of it meets output i with tap
+// 8 m + i - p -- the 15 taps around 8 m, those of them inside 0 .. T - 1 -- so a block is one LDS read, 15 taps and 64 multiply-adds; the new block
+// itself, m = 0, takes taps 0 .. 7 and the 36 products with p <= i.  Blocks in front of the chunk's row 0 do not exist and contribute nothing.
+// tap(j): the column's tap j, 0 <= j < T; put(i, y): row i's result
+template <int W, typename F, typename TP, typename P>
+__device__ __forceinline__ void fir_step8(const DecodeArgs& a, typename Elem<W>::U* rc, uint32_t blk, F x, TP tap, uint32_t bias, typename Elem<W>::U* first, uint32_t D, P put)
+{
+    using U = typename Elem<W>::U;
+    constexpr uint32_t MASK = Elem<W>::MASK;
+    const uint32_t T = fir_ntaps(a), nb = (a.win.rows >> 3) + 1u;      // blocks of the ring
+    const uint32_t slot = blk % nb;
+    uint32_t xs[8], acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) xs[i] = x(i) & MASK;
+    fir_block_set<W>(rc + 8u * slot, xs);
+    if (first && 8u * blk + 1u < T) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (8u * blk + (uint32_t)i + 1u < T) first[(size_t)(8u * blk + (uint32_t)i) * D] = (U)xs[i];
+    }
+    {
+        uint32_t t[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) t[q] = (uint32_t)q < T ? tap((uint32_t)q) : 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            uint32_t s = bias;
+#pragma unroll
+            for (int p = 0; p <= i; p++) s += t[i - p] * xs[p];
+            acc[i] = s;
+        }
+    }
+    const uint32_t nm = blk < nb - 1u ? blk : nb - 1u;          // the older blocks the chunk has, of those T - 1 rows reach
+    uint32_t ms = slot;
+    for (uint32_t m = 1; m <= nm; m++) {
+        ms = ms == 0 ? nb - 1u : ms - 1u;
+        uint32_t v[8], t[15];
+        fir_block_get<W>(rc + 8u * ms, v);
+#pragma unroll
+        for (int q = 0; q < 15; q++) {
+            const uint32_t j = 8u * m + (uint32_t)q - 7u;
+            t[q] = j < T ? tap(j) : 0u;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int p = 0; p < 8; p++) acc[i] += t[i - p + 7] * v[p];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) put(i, acc[i]);
+}
+// One row: the per-row form of the same step, for the verbatim tail -- row r of the chunk takes x; its history is read back from the ring
+template <int W, typename TP>
+__device__ __forceinline__ uint32_t fir_row(const DecodeArgs& a, typename Elem<W>::U* rc, uint32_t r, uint32_t x, TP tap, uint32_t bias, typename Elem<W>::U* first, uint32_t D)
+{
+    using U = typename Elem<W>::U;
+    const uint32_t T = fir_ntaps(a), cap = a.win.rows + 8u;
+    uint32_t slot = r % cap;
+    rc[slot] = (U)x;
+    if (first && r + 1u < T) first[(size_t)r * D] = (U)x;
+    uint32_t y = bias + tap(0u) * x;
+    const uint32_t n = r + 1u < T ? r + 1u : T;
+    for (uint32_t j = 1; j < n; j++) {
+        slot = slot == 0 ? cap - 1u : slot - 1u;
+        y += tap(j) * (uint32_t)rc[slot];
+    }
+    return y;
+}
+// The verbatim tail: `remaining` elements at t behind the chunk's `out_elems` (a multiple of 8 * D: element e of the tail is in column e % D, one
+// row further on than the column's previous one).  Each lane walks its own columns (`col`, a list), row by row, taps from global memory; a partial
+// last row has the columns it has, and nothing is stored for the others.
+template <int W, int CPL>
+__device__ __forceinline__ void fir_tail(const DecodeArgs& a, uint64_t chunk, uint8_t* ring, const uint8_t* t, uint32_t out_elems, uint32_t remaining, uint32_t D,
+                                         const int (&col)[CPL], const bool (&genuine)[CPL])
+{
+    using U = typename Elem<W>::U;
+    const uint64_t base = chunk * (uint64_t)a.chunk_len + out_elems;
+    const uint32_t r0 = out_elems / D;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        const uint32_t d = (uint32_t)col[k];
+        U* const rc = rolling_ring<W>(ring, a, d);
+        U* const first = a.lin.tmp ? fir_slot<W>(a, chunk).first + d : nullptr;
+        const uint32_t bias = fir_bias(a, d);
+        uint32_t r = r0;
+        for (uint32_t e = d; e < remaining; e += D, r++)
+            derive_put(a, base + e, fir_row<W>(a, rc, r, tail_elem<W>(t, e), [&](uint32_t j) { return (uint32_t)a.lin.w[(size_t)j * D + d]; }, bias, first, D), d);
+    }
+}
+// a chunk that is refused before its ring exists: one lane says so
+template <int W> __device__ __forceinline__ void fir_mark(const DecodeArgs& a, uint64_t chunk, int lane_d)
+{
+    if (a.lin.tmp && lane_d == 0) *fir_slot<W>(a, chunk).elems = 0u;
+}
+// At the chunk's end, with a seam pass to come: the element count, and -- from a full chunk, the only kind that has a successor whose first rows it
+// can complete -- its last T - 1 rows out of the ring (T - 1 <= R: the host checks, so they exist; the ring holds the last Wh + 8 >= T - 1)
+template <int W, int CPL>
+__device__ __forceinline__ void fir_leave(const DecodeArgs& a, uint64_t chunk, uint8_t* ring, uint32_t elems, uint32_t D, const int (&col)[CPL],
+                                          const bool (&genuine)[CPL], int lane_d)
+{
+    if (!a.lin.tmp) return;
+    const FirSlot<W> s = fir_slot<W>(a, chunk);
+    if (lane_d == 0) *s.elems = elems;
+    if (elems != a.chunk_len) return;
+    const uint32_t h = fir_ntaps(a) - 1u, cap = a.win.rows + 8u, from = a.chunk_len / D - h;
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+        if (!genuine[k]) continue;
+        const typename Elem<W>::U* const rc = rolling_ring<W>(ring, a, (uint32_t)col[k]);
+        uint32_t slot = from % cap;
+        for (uint32_t j = 0; j < h; j++) {
+            s.last[(size_t)j * D + (uint32_t)col[k]] = rc[slot];
+            slot = slot + 1u == cap ? 0u : slot + 1u;
+        }
+    }
+}
+// the generic kernel's form of the block step: taps from global memory, every result at once to its place, at a plain 64-bit address; e0 is the batch
+// element of the block's row 0 in column d
+template <int W, typename F>
+__device__ __forceinline__ void fir_rows8(const DecodeArgs& a, uint64_t chunk, typename Elem<W>::U* rc, uint32_t blk, F x, uint64_t e0, uint32_t D, uint32_t d)
+{
+    typename Elem<W>::U* const first = a.lin.tmp ? fir_slot<W>(a, chunk).first + d : nullptr;
+    fir_step8<W>(a, rc, blk, x, [&](uint32_t j) { return (uint32_t)a.lin.w[(size_t)j * D + d]; }, fir_bias(a, d), first, D,
+                 [&](int i, uint32_t y) { derive_put(a, e0 + (uint64_t)i * D, y, d); });
+}
+
 }  // namespace sprintz

@@ -90,7 +90,7 @@ struct HostCall {
 
 // query-on-compressed options of one decode launch (the decoders' Q template parameter; decode_ops.h)
 struct QuerySpec {
-    int q = kQueryOff;          // kQueryOff .. kQueryDerive (geom.h)
+    int q = kQueryOff;          // kQueryOff .. kQueryFir (geom.h)
     int qop = 0;                // 1 max, 2 sum
     uint64_t* qres = nullptr;   // [nchunks][ndims]
     // the mode's own arguments, as the kernels take them (decode_ops.h)
@@ -111,7 +111,9 @@ struct QuerySpec {
     //  kQueryFloat does, with mask the slot table and mask_stride K: decode_ops.h, project rows;
     //  kQueryCumulative in win -- the ops, sum_bytes in count, the outputs -- lin.tmp, the chunks' entering states, and lin.w, carry_out: decode_ops.h, cumulative rows;
     //  kQueryDerive in lin -- the [K][D] weight tables and the seam scratch -- and filter: lo the scale, hi the offset, mode the format, mask the biases,
-    //  counts the `prev` row, mask_stride K: decode_ops.h, derive rows)
+    //  counts the `prev` row, mask_stride K: decode_ops.h, derive rows;
+    //  kQueryFir in win -- T in count, the history's rows in rows -- lin -- w the taps, lag the biases, tmp the seam scratch -- and filter: lo the scale, hi the
+    //  offset, mode the format, counts the `prev` rows: decode_ops.h, FIR rows)
     int general = 0;            // 1: general row-major layout for every ndims (the reference's *_rowmajor_*_rle_* family)
     uint64_t col_stride = 0;    // != 0: column-major destination (DecodeArgs::col_stride)
     const HostCall* hc = nullptr;

@@ -41,13 +41,17 @@ constexpr int kThreads = SPRINTZ_THREADS;        // wavefronts per workgroup x 6
 // 17 = cumulative: per element the running min / max / sum of its column from the batch's first row to its row, stored at the element's place in place of
 // the element; a chunk starts from the state the scan of decode_cumulative.hip left for it;
 // 18 = derive: nothing of a decoded row is stored but K linear forms of it and of the row in front of it -- the linear filter's sum itself, K times, as int32
-// or converted as float rows convert -- each at its place of a dense [rows, K] output; the seam pass of decode_derive.hip carries the lag term over the chunk seams.
+// or converted as float rows convert -- each at its place of a dense [rows, K] output; the seam pass of decode_derive.hip carries the lag term over the chunk seams;
+// 19 = fir: per element bias[d] + sum_j taps[j][d] x[g - j, d] over the T rows that end at its row -- a per-column tap filter, as int32 or converted as derive
+// rows convert -- stored at the element's place; rows in front of the chunk's first contribute nothing inside the launch, and the seam pass of decode_fir.hip
+// computes the first T - 1 rows of every chunk again from raw rows.
 // 6 .. 11 and 13 read one row mask (decode_ops.h: RowMaskArgs), 3, 7, 9 and 11 walk one set of windows (WindowArgs), 8 and 10 fill one table of bins (BinTableArgs)
 constexpr int kQueryOff = 0, kQueryMaterialize = 1, kQueryReduceOnly = 2, kQueryWindow = 3, kQueryGather = 4, kQueryFilter = 5, kQuerySelect = 6,
               kQueryAggregate = 7, kQueryHistogram = 8, kQueryMoments = 9, kQueryGroupBy = 10, kQueryExtrema = 11, kQueryLinear = 12, kQuerySegment = 13, kQueryFloat = 14, kQueryRolling = 15;
 constexpr int kQueryProject = 16;
 constexpr int kQueryCumulative = 17;
 constexpr int kQueryDerive = 18;
+constexpr int kQueryFir = 19;
 // the modes that never store a decoded sample
 constexpr bool query_reduce_only(int q)
 {
@@ -83,6 +87,19 @@ constexpr uint32_t roll_max_window(int D, int esz, uint32_t groups)
 // with more than one chunk: what one chunk leaves for the seam pass (decode_ops.h: RollSlot) -- a word with the elements the chunk decoded to (0: damaged),
 // 12 bytes of padding, then its last W - 1 rows in the element type where it is full; a multiple of 16 bytes
 constexpr uint64_t roll_tmp_stride(uint32_t W, int D, int esz) { return (16ull + ((uint64_t)W - 1ull) * (uint64_t)D * (uint64_t)esz + 15ull) & ~15ull; }
+// FIR rows: the most taps a call takes; the history a filter of T taps keeps -- rolling rows' ring with W replaced by Wh, T - 1 rounded up to whole blocks
+// of 8 rows (roll_ring_bytes(fir_history_rows(T), D, esz)); and what one chunk leaves for the seam pass (decode_ops.h: FirSlot) -- a word with the elements
+// the chunk decoded to (0: damaged), 12 bytes of padding, its first T - 1 raw rows, then its last T - 1 raw rows where it is full; a multiple of 16 bytes
+constexpr uint32_t kFirMaxTaps = 256;
+constexpr uint32_t fir_history_rows(uint32_t T) { return (T + 6u) & ~7u; }
+constexpr uint64_t fir_tmp_stride(uint32_t T, int D, int esz) { return (16ull + 2ull * ((uint64_t)T - 1ull) * (uint64_t)D * (uint64_t)esz + 15ull) & ~15ull; }
+// the most taps (0: none) whose rings -- one for each of the `groups` chunks of a workgroup -- fit kRollLdsMax
+constexpr uint32_t fir_max_taps(int D, int esz, uint32_t groups)
+{
+    const uint64_t rows = (kRollLdsMax / groups & ~15ull) / ((uint64_t)D * (uint64_t)esz);      // rows of one ring
+    const uint64_t t = rows < 8 ? 0 : ((rows - 8) & ~7ull) + 1;
+    return t > kFirMaxTaps ? kFirMaxTaps : (uint32_t)t;
+}
 // cumulative rows: the ops (SPRINTZ_CUM_MIN / _MAX / _SUM, WindowArgs::ops; WindowArgs::count carries sum_bytes) and the scan over the chunks'
 // totals (decode_cumulative.hip).  A workgroup of the scan owns one column and walks the chunks kCumScanTile at a step: each of its kThreads
 // threads takes kCumScanChunks consecutive chunks.
@@ -162,6 +179,14 @@ inline uint32_t roll_shape_max_window(int D, int esz, bool general)
 {
     const Mapping m = choose_mapping(D, general ? false : is_lowdim(esz, D));
     return roll_max_window(D, esz, (uint32_t)(kThreads >> m.log2DP));
+}
+
+// FIR rows: the most taps a SHAPE takes, by the same rule -- fir_max_taps at the chunks a workgroup of the generic kernel decodes.  plan_decode refuses
+// by it and the host wrapper names it in its refusal
+inline uint32_t fir_shape_max_taps(int D, int esz, bool general)
+{
+    const Mapping m = choose_mapping(D, general ? false : is_lowdim(esz, D));
+    return fir_max_taps(D, esz, (uint32_t)(kThreads >> m.log2DP));
 }
 
 inline uint32_t next_pow2(uint32_t x)

@@ -16,7 +16,7 @@
 
 namespace sprintz {
 
-// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryDerive).  Each forwards to the
+// The lane-per-column decoders, one launcher a family; q is the row operation (geom.h: kQueryOff .. kQueryFir).  Each forwards to the
 // translation unit that holds the instantiation -- decode_w8.hip / decode_w16.hip for the plain decode and the reduce / window
 // queries, a unit of its own for every other mode (SPRINTZ_ROW_OP_UNITS below) -- so that every unit keeps its compile flags.
 // generic lane mapping, both layouts, up to 512 columns (decode_kernel.h)
@@ -24,7 +24,7 @@ hipError_t launch_decode_generic(int w, bool fire, bool lowdim, int cpl, int q, 
 // fast path: general layout, one column per lane, LDS-transposed stores (see decode_fast.h); gather and select for rows of whole 16-byte pieces
 // (ds: columns the LDS carve is sized for when that is fewer than dp * cpl -- decode_fast.h, DS; 0 = dp * cpl)
 hipError_t launch_decode_fast(int w, bool fire, int dp, int cpl, bool exact, int q, int ds, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a);
-// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments, group-by, extrema, the linear filter, segments, float rows, rolling rows, project rows, cumulative rows and derive rows
+// low-dim streams with 1, 2 or 4 columns (8 bits) / 1 or 2 (16 bits), one lane per chunk (decode_uni.h): every mode but gather, select, aggregate, histogram, moments, group-by, extrema, the linear filter, segments, float rows, rolling rows, project rows, cumulative rows, derive rows and FIR rows
 hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 // internal -- the units' own entry points, reached through the three launchers above alone (api.hip).  A unit refuses a width or
 // a mode it does not hold; the decode_uni units size their grid themselves (decode_uni_threads) and ignore `grid`
@@ -34,7 +34,7 @@ hipError_t launch_decode_uni(int w, bool fire, int nd, int q, unsigned grid, hip
 SPRINTZ_DECODE_UNIT_DECL(w8)
 SPRINTZ_DECODE_UNIT_DECL(w16)
 // the row operations' units, a mode each, in the order of their kQuery* numbers (api.hip builds its table of units from this list)
-#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby) X(extrema) X(linear) X(segment) X(float) X(rolling) X(project) X(cumulative) X(derive)
+#define SPRINTZ_ROW_OP_UNITS(X) X(gather) X(filter) X(select) X(aggregate) X(histogram) X(moments) X(groupby) X(extrema) X(linear) X(segment) X(float) X(rolling) X(project) X(cumulative) X(derive) X(fir)
 SPRINTZ_ROW_OP_UNITS(SPRINTZ_DECODE_UNIT_DECL)
 hipError_t decode_uni_w8(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
 hipError_t decode_uni_w16(int w, bool fire, int nd, int q, unsigned grid, hipStream_t st, const DecodeArgs& a);
@@ -48,6 +48,9 @@ hipError_t launch_linear_seam(int esz, const DecodeArgs& a, hipStream_t st);
 // derive_rows' seam pass: row 0 of every chunk behind the first -- and of the first, where the caller gave a `prev` row -- is computed again with its
 // true predecessor and stored over what the decode left (decode_derive.hip)
 hipError_t launch_derive_seam(int esz, const DecodeArgs& a, hipStream_t st);
+// fir_rows' seam pass: the first T - 1 rows of every chunk are computed again, wholly, from the raw rows the chunks left in the scratch -- their own first
+// rows and the last rows of the chunk in front (chunk 0: the caller's `prev` rows, or its row 0 replicated) -- and stored over what the decode left (decode_fir.hip)
+hipError_t launch_fir_seam(int esz, const DecodeArgs& a, hipStream_t st);
 // rolling_rows' seam pass: the first W - 1 rows of every chunk behind the first take the last rows of the chunk in front into their windows (decode_rolling.hip)
 hipError_t launch_rolling_seam(int esz, const DecodeArgs& a, hipStream_t st);
 // cumulative_rows' scan: the chunks' totals in d_tmp (geom.h: cum_tmp_layout) become each chunk's entering state, seeded with carry_in (null: the
@@ -221,13 +224,13 @@ inline hipError_t launch_one(K kernel, unsigned grid, size_t shmem, hipStream_t 
 // The kernels of decode_w8.hip / decode_w16.hip keep the code and the flags they had, and hipcc builds the units in parallel.
 // FAST_DISPATCH(KERNEL, W, Q) is the set of decode_fast mappings the mode has.  The generic kernel stages nothing in these modes:
 // whatever the plan carved, its launch asks for LDS only where that is the workgroup's table (histogram, group-by) or the chunks' history
-// rings (rolling rows) -- and for the filter, which keeps the launch it always had.
+// rings (rolling rows, FIR rows) -- and for the filter, which keeps the launch it always had.
 #define SPRINTZ_ROW_OP_UNIT(NAME, Q, FAST_DISPATCH)                                                                                                             \
     namespace sprintz {                                                                                                                                         \
     hipError_t decode_generic_##NAME(int w, bool fire, bool lowdim, int cpl, int q, unsigned grid, size_t shmem, hipStream_t st, const DecodeArgs& a)           \
     {                                                                                                                                                           \
         if (q != Q) return hipErrorInvalidValue;                                                                                                                \
-        if (Q != kQueryFilter && Q != kQueryHistogram && Q != kQueryGroupBy && Q != kQueryRolling) shmem = 0;                                                                      \
+        if (Q != kQueryFilter && Q != kQueryHistogram && Q != kQueryGroupBy && Q != kQueryRolling && Q != kQueryFir) shmem = 0;                                                   \
         if (w == 8) { SPRINTZ_DISPATCH_Q(decode_kernel, 8, Q) }                                                                                                 \
         if (w == 16) { SPRINTZ_DISPATCH_Q(decode_kernel, 16, Q) }                                                                                               \
         return hipErrorInvalidValue;                                                                                                                            \

@@ -41,13 +41,13 @@ struct Shape {
     unsigned src_lo = 0, slots_lo = 0, out_lo = 0, comp_lo = 0;   // the low four bits of the source, slot, output and container addresses
     uint64_t slot_stride = 0;
     uint64_t nranges = 0;                  // gather
-    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W; project rows: the columns K of the output; derive rows: the forms K
+    uint32_t rows = 0;                     // gather: rows of a range; rolling rows: the window W; project rows: the columns K of the output; derive rows: the forms K; FIR rows: the taps T
     uint64_t capacity = 0;                 // select: rows of the output
     // histogram, group-by: the uint32 entries of a workgroup's table (D x nbins, at most kHistMaxCounters; nbins x (D + 1), at most
     // kGroupByMaxCounters) and the most that one row can add to an entry (1; 2^W - 1).  0 entries: the mode has no table
     uint32_t table_entries = 0, table_row_max = 0;
     // the element bytes on the float side (4, or 2 for float16 / bfloat16): float rows' output element -- what every bound on output BYTES
-    // counts in (project rows: the output element whatever it is, esz unconverted; derive rows: 4 for int32 and float32, 2 for the 16-bit floats) -- and, for an encode with q == kQueryFloat, the float
+    // counts in (project rows: the output element whatever it is, esz unconverted; derive rows and FIR rows: 4 for int32 and float32, 2 for the 16-bit floats) -- and, for an encode with q == kQueryFloat, the float
     // source's element; 0: the call has no float side
     int out_esz = 0;
 };
@@ -304,6 +304,44 @@ inline Plan plan_decode(const Shape& s, const Knobs& k)
             return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, dstride * fgroups + wtable);
         }
         return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, 0);
+    }
+
+    // FIR rows (T in s.rows; s.out_esz the bytes of an output element: 4 for int32 and float32, 2 for float16 / bfloat16).  The history is rolling rows'
+    // ring with W replaced by Wh = fir_history_rows(T).  decode_fast.h takes the shapes it takes for rolling rows -- rows of whole 16-byte pieces on the
+    // one-column-a-lane mappings (8 .. 64 columns), a 16-byte aligned output, within the descriptor's reach counted in OUTPUT bytes -- where the chunks'
+    // rings behind the groups' carves and the workgroup's table of taps ([T][D] int32) behind the rings fit the budget the histogram's launch has:
+    // (f.ring + ring) x groups + 4 T D <= kHistFastLdsBudget.  Two and four columns a lane are not instantiated, as for rolling rows.  Everything else runs
+    // the generic kernel, whose launch LDS is the rings alone, which reads its taps from global memory and stores element by element; a history that does
+    // not fit a workgroup's 160 KB there is refused (fir_shape_max_taps).  decode_uni.h is not taught the mode.
+    if (s.q == kQueryFir) {
+        const uint32_t T = s.rows;
+        if (D > 512 || norle || cs) return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "fir_rows: the RLE codecs, row-major, at most 512 columns");
+        if (T < 1 || T > kFirMaxTaps) return plan_fail(p, SPRINTZ_E_INVALID, "fir_rows: ntaps must be in 1 .. 256");
+        if (T - 1u > chunk_len / (uint32_t)D) return plan_fail(p, SPRINTZ_E_INVALID, "fir_rows: ntaps - 1 must not exceed the rows of a chunk, chunk_len / ndims");
+        const uint64_t ring = roll_ring_bytes(fir_history_rows(T), D, esz);
+        const int fosz = s.out_esz ? s.out_esz : 4;
+        const FastMap f = decode_fast_map(esz, D, 0, false);
+        const uint64_t fgroups = (uint64_t)(kThreads / f.dp);
+        const uint64_t ttable = (uint64_t)T * D * 4;
+        const bool fast = !lowdim && !s.noheader && f.cpl == 1 && 2 * D > f.dp * f.cpl && (uint64_t)chunk_len * esz * 2 >= f.ring && !k.no_fast &&
+                          ((uint64_t)D * esz) % 16 == 0 && ((uint64_t)chunk_len * esz) % 16 == 0 && (s.out_lo % 16) == 0 &&
+                          (uint64_t)chunk_len * fosz * 64 * 64 < 0xf0000000ull && ((uint64_t)f.ring + ring) * fgroups + ttable <= kHistFastLdsBudget;
+        if (fast) {
+            p.dp = f.dp; p.cpl = f.cpl; p.ds = f.ds;
+            p.exact = D == f.dp * f.cpl;
+            p.log2DP = f.log2dp;
+            p.lds_group_stride = f.ring;
+            p.vec_store = 1;
+            p.chunks_per_group = (uint32_t)k.chunks_per_group;
+            p.table_off = f.ring * (uint32_t)fgroups;
+            const uint64_t ngroups_launch = (nchunks + p.chunks_per_group - 1) / p.chunks_per_group;
+            return plan_take(p, SPRINTZ_KF_DEC_FAST, (ngroups_launch * (uint64_t)f.dp + kThreads - 1) / kThreads, ((uint64_t)f.ring + ring) * fgroups + ttable);
+        }
+        const uint32_t groups = (uint32_t)(kThreads / DP);
+        if (T > fir_shape_max_taps(D, esz, !lowdim))
+            return plan_fail(p, SPRINTZ_E_UNSUPPORTED, "fir_rows: ntaps must leave the history rings within a workgroup's LDS (fir_shape_max_taps)");
+        p.lds_group_stride = (uint32_t)ring;
+        return plan_take(p, SPRINTZ_KF_DEC_GENERIC, (nchunks * (uint64_t)DP + kThreads - 1) / kThreads, (uint64_t)p.lds_group_stride * groups);
     }
 
     // 513 .. 2047 columns: one workgroup per chunk (any_ndims.hip) -- the RLE codecs, row-major, plain decode

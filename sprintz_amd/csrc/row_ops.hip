@@ -1,5 +1,5 @@
 // row_ops.hip -- the row operations of the C-ABI (include/sprintz_mi355x.h): queries, the zone map, filters, select, aggregate,
-// moments, extrema, segments, float rows, rolling rows, project rows, derive rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
+// moments, extrema, segments, float rows, rolling rows, project rows, derive rows, FIR rows, histogram, group-by and gather on a compressed batch.  Each entry point names its batch, runs its checks,
 // fills its QuerySpec and hands over to decode_batch (entry.h); what the decoders then do with a row is decode_ops.h's.
 #include "entry.h"
 
@@ -610,6 +610,69 @@ int sprintz_mi355x_derive_rows(int codec, int elem_bytes, const void* d_comp, co
     a.filter = qs.filter;
     a.lin = qs.lin;
     if (launch_derive_seam(elem_bytes, a, (hipStream_t)hip_stream) != hipSuccess) return fail(SPRINTZ_E_HIP, "derive_rows seam kernel launch");
+    return 0;
+}
+
+// ---------------------------------------------------------------- FIR rows
+uint64_t sprintz_mi355x_fir_rows_tmp_bytes(int elem_bytes, uint64_t nchunks, uint16_t ndims, uint32_t ntaps)
+{
+    if ((elem_bytes != 1 && elem_bytes != 2) || ndims == 0 || ntaps < 2 || ntaps > kFirMaxTaps) return 0;
+    return nchunks * fir_tmp_stride(ntaps, ndims, elem_bytes);
+}
+
+int sprintz_mi355x_fir_rows(int codec, int elem_bytes, const void* d_comp, const uint64_t* d_offsets, uint64_t nchunks,
+                            uint32_t chunk_len, uint16_t ndims, uint32_t ntaps, const int32_t* d_taps, const int32_t* d_bias, int format,
+                            const float* d_scale, const float* d_offset, const void* d_prev, uint32_t flags, void* d_tmp, void* d_out,
+                            int64_t* d_rets, void* hip_stream)
+{
+    const Batch b{codec, elem_bytes, d_comp, d_offsets, nchunks, chunk_len, ndims};
+    int rc = unmasked_row_op("fir_rows", b, flags);
+    if (rc) return rc;
+    if (ntaps < 1 || ntaps > kFirMaxTaps) return fail_op(SPRINTZ_E_INVALID, "fir_rows", "ntaps must be in 1 .. 256");
+    if (ntaps - 1u > chunk_len / ndims) return fail_op(SPRINTZ_E_INVALID, "fir_rows", "ntaps - 1 must not exceed the rows of a chunk, chunk_len / ndims");
+    if (format != SPRINTZ_DERIVE_I32 && format != SPRINTZ_DERIVE_F32 && format != SPRINTZ_DERIVE_F16 && format != SPRINTZ_DERIVE_BF16)
+        return fail(SPRINTZ_E_INVALID, "fir_rows: format must be SPRINTZ_DERIVE_I32, SPRINTZ_DERIVE_F32, SPRINTZ_DERIVE_F16 or SPRINTZ_DERIVE_BF16");
+    const bool i32 = format == SPRINTZ_DERIVE_I32;
+    if (i32 && (d_scale || d_offset)) return fail_op(SPRINTZ_E_INVALID, "fir_rows", "d_scale and d_offset go with a float format only");
+    if (!d_taps || !d_out) return fail(SPRINTZ_E_INVALID, "fir_rows: null device pointer");
+    const uint32_t mode = i32 ? kDeriveI32Bit : (uint32_t)(format - 1);
+    if ((uintptr_t)d_out % (uintptr_t)derive_out_bytes(mode)) return fail(SPRINTZ_E_INVALID, "fir_rows: d_out must be aligned to the output element size");
+    if ((uintptr_t)d_taps % 4 || (uintptr_t)d_bias % 4 || (uintptr_t)d_scale % 4 || (uintptr_t)d_offset % 4 ||
+        (ntaps > 1 && (uintptr_t)d_prev % (uintptr_t)elem_bytes) || (uintptr_t)d_rets % 8)      // (one tap: d_prev is ignored, whatever it is)
+        return fail(SPRINTZ_E_INVALID, "fir_rows: d_taps, d_bias, d_scale and d_offset must be aligned to 4 bytes, d_prev to the element size, d_rets to 8");
+    if (ntaps > 1 && (!d_tmp || (uintptr_t)d_tmp % 16))
+        return fail(SPRINTZ_E_INVALID, "fir_rows: with ntaps > 1, d_tmp must hold sprintz_mi355x_fir_rows_tmp_bytes bytes, aligned to 16");
+    // the rings of a workgroup's chunks must fit its LDS: the bound the planner refuses by, named here
+    const uint32_t tmax = fir_shape_max_taps(ndims, elem_bytes, (flags & SPRINTZ_QUERY_GENERAL_LAYOUT) != 0);
+    if (ntaps > tmax) {
+        const std::string what = "fir_rows: ntaps " + std::to_string(ntaps) + " needs more LDS than a workgroup has for this shape's history rings: the largest ntaps allowed is " +
+                                 std::to_string(tmax);
+        return fail(SPRINTZ_E_UNSUPPORTED, what.c_str());
+    }
+    if (nchunks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    // the mode shares structs that exist (decode_ops.h, FIR rows): T and the history's rows in WindowArgs; the taps, the biases and the seam scratch in
+    // LinearArgs; scale, offset, format and the `prev` rows in FilterArgs
+    QuerySpec qs = row_query(kQueryFir, flags);
+    qs.win.rows = fir_history_rows(ntaps);
+    qs.win.count = ntaps;
+    qs.lin = LinearArgs{d_taps, d_bias, ntaps > 1 ? d_tmp : nullptr, 0, 0, 0, 0u};
+    qs.filter.lo = d_scale;
+    qs.filter.hi = d_offset;
+    qs.filter.mode = mode;
+    qs.filter.counts = ntaps > 1 ? (uint32_t*)const_cast<void*>(d_prev) : nullptr;
+    rc = decode_batch(b, d_out, d_rets, (hipStream_t)hip_stream, qs);
+    if (rc || ntaps < 2) return rc;
+    // the seam pass, behind the decode on the same stream: the first ntaps - 1 rows of every chunk, computed again from raw rows
+    DecodeArgs a{};
+    a.nchunks = nchunks;
+    a.chunk_len = chunk_len;
+    a.D = ndims;
+    a.out = d_out;
+    a.win = qs.win;
+    a.filter = qs.filter;
+    a.lin = qs.lin;
+    if (launch_fir_seam(elem_bytes, a, (hipStream_t)hip_stream) != hipSuccess) return fail(SPRINTZ_E_HIP, "fir_rows seam kernel launch");
     return 0;
 }
 

@@ -1,7 +1,7 @@
 """The host-side rules ChunkedCodec's row operations share (query_windows, filter_rows, filter_linear, select_rows, aggregate_rows, histogram_rows,
-moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, project_rows, cumulative_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
+moments_rows, groupby_rows, extrema_rows, segment_rows, float_rows, rolling_rows, project_rows, cumulative_rows, derive_rows, fir_rows, gather_rows), each defined once: a chunk's rows and mask bytes, the mask's shape, the kernel window and the
 fold of its results into windows over the batch's rows, the segments' stitching over the chunk seams, the first damaged chunk, float_rows' format and parameters, compress_floats' reciprocal scales, rolling_rows' window rules, counts, mean and scratch size, project_rows' slot table, cumulative_rows' ops, carry, mean and scratch size, the default bin shift, bounds and offsets as tensors, the
-linear filter's weights and exactness bound, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
+linear filter's weights and exactness bound, fir_rows' taps, bound and scratch size, the zone map's classes and the expansion of a pruned filter's results, and the moments' derived values.  Pure functions on torch tensors of any device -- nothing here touches the library, so the CPU tier tests
 them (tests/test_rowops_cpu.py)."""
 import numpy as np
 import torch
@@ -460,6 +460,61 @@ def derive_forms(forms, lag_forms, bias, ndims, esz, device):
         linear_bound(w[k], None if u is None else u[k], b[k], esz, f"form {k}")
     as_t = lambda vals: torch.from_numpy(np.array(vals, np.int32).reshape(K, -1)).to(device)      # noqa: E731
     return as_t(w), None if u is None else as_t(u), as_t(b).reshape(K)
+
+
+FIR_MAX_TAPS = 256
+
+
+def fir_taps(taps, bias, ndims, esz, device):
+    """fir_rows' arguments -> (taps, bias): taps a contiguous int32 tensor [T, ndims] on `device`, taps[0] weighing the row itself, and bias an
+    int32 tensor [ndims].  taps: a 1-D sequence (or tensor) of T integers, shared by all columns, or [T, ndims] -- a sequence of T rows of ndims
+    integers, or an integer tensor.  bias: a scalar (every column) or ndims entries.  1 <= T <= 256.  Every column's filter is held to
+    linear_bound: |bias[d]| + (2^W - 1) sum_j |taps[j][d]| must stay below 2^31, and one that can reach it is refused, by its column."""
+    if torch.is_tensor(taps):
+        if taps.dtype.is_floating_point or taps.dtype == torch.bool or taps.dim() not in (1, 2) or (taps.dim() == 2 and taps.shape[1] != ndims):
+            raise ValueError(f"taps must be an integer tensor [T] or [T, {ndims}]")
+        rows = taps.cpu().tolist()
+    elif isinstance(taps, dict) or np.isscalar(taps) or taps is None:
+        raise ValueError("taps must be a sequence of T entries, not one entry")
+    else:
+        rows = list(taps)
+    T = len(rows)
+    if not 1 <= T <= FIR_MAX_TAPS:
+        raise ValueError(f"fir_rows takes 1 .. {FIR_MAX_TAPS} taps, not {T}")
+    if all(np.isscalar(r) for r in rows):
+        rows = [[r] * ndims for r in rows]
+    t = []
+    for j, r in enumerate(rows):
+        if np.isscalar(r) or len(r) != ndims:
+            raise ValueError(f"taps[{j}] must have {ndims} entries: taps is [T] (shared by all columns) or [T, {ndims}]")
+        if any(isinstance(e, (float, np.floating)) for e in r):
+            raise ValueError(f"taps[{j}] must hold integers")
+        t.append([int(e) for e in r])
+    b = [int(e) for e in _entries(bias, ndims, "bias")]
+    for d in range(ndims):
+        linear_bound([t[j][d] for j in range(T)], None, b[d], esz, f"column {d}'s filter")
+    return torch.from_numpy(np.array(t, np.int32).reshape(T, ndims)).to(device), torch.from_numpy(np.array(b, np.int32)).to(device)
+
+
+def fir_tmp_bytes(nchunks, T, ndims, esz):
+    """the seam scratch fir_rows needs with more than one tap (include/sprintz_mi355x.h: d_tmp; fir_tmp_stride in geom.h), a multiple of 16 bytes a chunk"""
+    return nchunks * ((16 + 2 * (T - 1) * ndims * esz + 15) & ~15) if T > 1 else 0
+
+
+def shift_taps(k):
+    """shift_rows' taps: a unit tap at lag k"""
+    k = int(k)
+    if not 0 <= k < FIR_MAX_TAPS:
+        raise ValueError(f"k must be in 0 .. {FIR_MAX_TAPS - 1}, not {k}")
+    return [0] * k + [1]
+
+
+def lag_diff_taps(periods):
+    """lag_diff_rows' taps: +1 at lag 0 and -1 at lag `periods`"""
+    p = int(periods)
+    if not 1 <= p < FIR_MAX_TAPS:
+        raise ValueError(f"periods must be in 1 .. {FIR_MAX_TAPS - 1}, not {periods}")
+    return [1] + [0] * (p - 1) + [-1]
 
 
 ZONE_NONE, ZONE_ALL, ZONE_DECODE = 0, 1, 2
